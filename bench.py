@@ -11,9 +11,17 @@ in HBM.  One independent chain per GPU (chain_id = rank); no data-path collectiv
 the chains' final metrics rows.  Rank 0 prints ONE JSON line.
 
 `--gpus N` without WORLD_SIZE in the environment starts the N ranks itself (fresh child processes,
-before anything here touches the GPU).  The timed region is repeated `--reps` times (default 9), each
-repetition timing EXACTLY `--steps` iterations between barriers; `value` is the median repetition
-(SURVEY.md 8d protocol) and every repetition is listed under `rep_values`.
+before anything here touches the GPU).
+
+A plain run does only what the headline needs: set-up, `--warmup` iterations (at least SETTLE_ITERS) issued
+as calls of the timed shape (rounded up to whole calls of `--steps`), ONE timed region of EXACTLY `--steps`
+iterations between barriers, the outputs of its last step if `--dump-outputs DIR` is given, and the result line.
+
+`--full` adds everything else the benchmark measures, as before: the serialised per-kernel profile pass and
+the roofline of the allocation kernel (before the timed region), the timed region repeated `--reps` times
+(default 9 with --full; `value` is the median repetition, SURVEY.md 8d protocol), full mode (save_Z), the
+BASELINE configs 2-5 (`--no-secondary` skips them), the CPU baseline (`--no-cpu-baseline` skips it) and, with
+more than one rank, the gather of the chains' MAP window statistics.
 """
 import argparse
 import json
@@ -31,6 +39,9 @@ sys.path.insert(0, ROOT)
 K_, G_, N_, R_TRUE, DATA_SEED = 96, 10000, 20, 8, 20250218
 MAP_OVER = 1000                # new_convergence_control() default: depth of the record_sample ring
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+SETTLE_ITERS = 1500            # least warm-up of a plain run (0.12 s at the metric configuration)
+METRIC_COLUMNS = ("iter", "RMSE", "KL", "loglikelihood", "logposterior", "n_params", "BIC", "rank", "temp")   # --dump-outputs' metrics.npy
+DUMP_BYTES = 60 << 20          # --dump-outputs: bytes written at most (a larger array is written as a fixed, seeded sample)
 PROFILE_TAG = "r05"                         # profiles/<tag>_pmc_*.json: the committed counter passes the roofline quotes (falls back to r03)
 
 
@@ -177,6 +188,30 @@ def make_chain(M, N, seed, chain_id, device, save_Z=False, window=MAP_OVER, prio
     return e
 
 
+def dump_outputs(out_dir, chain, met, save_Z):
+    """--dump-outputs: what the timed path computed in its last step, as <out_dir>/<name>.npy (float64): the metrics row of
+    that iteration and the chain's state it left (P, E, the allocation's sums ZsumK / ZsumG, and Z itself in full mode).
+    An array whose share of DUMP_BYTES is too small for it is written as a sample at fixed, seeded positions of its
+    column-major flattening (<name>_sample.npy).  Returns {file name: shape}.
+    The metrics row keeps the columns this model defines (METRIC_COLUMNS): the MH acceptance rates are NaN by definition in
+    a sweep without Metropolis-Hastings steps and are left out."""
+    from bayesnmf_amd.engine import METRIC_NAMES
+    arrays = {"metrics": met[-1][[METRIC_NAMES.index(c) for c in METRIC_COLUMNS]], "P": chain.get("P"), "E": chain.get("E"), "ZsumK": chain.get("ZsumK"), "ZsumG": chain.get("ZsumG")}
+    if save_Z:
+        arrays["Z"] = chain.get("Z")
+    cap = DUMP_BYTES // len(arrays) // 8
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(DATA_SEED).choice(a.size, cap, replace=False))
+            a, name = a.ravel(order="F")[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
+
+
 def _time_oracle(M, N, cores, budget_s):
     import oracle as O
     from bayesnmf_amd.setup import apply_hyperprior_params
@@ -308,15 +343,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--reps", type=int, default=9, help="repetitions of the timed K-step region; value = median")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step region; value = median (default 1; 9 with --full)")
     ap.add_argument("--window", type=int, default=MAP_OVER, help="record_sample ring depth (MAP_over); 0 = recording off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the timings of BASELINE configs 2-5")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel profile pass and roofline, repeated timed "
+                                                        "regions, full mode, BASELINE configs 2-5, CPU baseline, MAP gather across ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the timings of BASELINE configs 2-5")
     ap.add_argument("--save-z", action="store_true", help="full mode: materialise Z every iteration")
     ap.add_argument("--G", type=int, default=G_)
     ap.add_argument("--force-dist", action="store_true", help="initialise the nccl (RCCL) process group and run the gather / all-reduce "
                                                                "legs even with one rank (exercises the collectives on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    reps = args.reps if args.reps is not None else (9 if args.full else 1)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
@@ -369,20 +410,29 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    chain.run(args.warmup, metrics=False)
-    n_prof = min(200, max(20, args.steps // 10))
-    n_refill = max(args.warmup, 1500)   # (0.14 s at the metric configuration: the device clocks have settled by the first timed repetition)
-    # roofline of the dominant kernel (k_zalloc): HIP events on the chain's own stream, one kernel at a time.
-    # Done before the timed region (it advances the chain like any other iterations and keeps the clocks up).
-    prof, roof = roofline_of(chain, K_, args.G, N_, args.save_z, total_counts, n_prof, device=local_rank)
-    chain.run(n_refill, metrics=False)  # refill the stream pipeline after the serialised profile pass; keeps the clocks up
-    n_shape = 2                         # ... and two untimed repetitions of exactly the timed shape (on some boxes the first calls after the
-    for _ in range(n_shape):            # profile pass run 3 % slower than the ones behind them)
-        chain.run(args.steps, metrics=True)
+    if args.full:
+        chain.run(args.warmup, metrics=False)
+        n_prof = min(200, max(20, args.steps // 10))
+        n_refill = max(args.warmup, 1500)   # (0.14 s at the metric configuration: the device clocks have settled by the first timed repetition)
+        # roofline of the dominant kernel (k_zalloc): HIP events on the chain's own stream, one kernel at a time.
+        # Done before the timed region (it advances the chain like any other iterations and keeps the clocks up).
+        prof, roof = roofline_of(chain, K_, args.G, N_, args.save_z, total_counts, n_prof, device=local_rank)
+        chain.run(n_refill, metrics=False)  # refill the stream pipeline after the serialised profile pass; keeps the clocks up
+        n_shape = 2                         # ... and two untimed repetitions of exactly the timed shape (on some boxes the first calls after the
+        for _ in range(n_shape):            # profile pass run 3 % slower than the ones behind them)
+            chain.run(args.steps, metrics=True)
+        warmup_effective = args.warmup + n_prof + n_refill + n_shape * args.steps
+    else:
+        # --warmup iterations, at least SETTLE_ITERS, as calls of the timed shape: a call longer than any before it sizes the handle's
+        # metrics rows anew, and a short warm-up leaves the device slower than it runs after a fraction of a second of steady work
+        n_warm = -(-max(args.warmup, SETTLE_ITERS) // args.steps)
+        for _ in range(n_warm):
+            chain.run(args.steps, metrics=True)
+        warmup_effective = n_warm * args.steps
 
     rep_dt = []
     met = None
-    for _ in range(max(1, args.reps)):
+    for _ in range(max(1, reps)):
         barrier()
         t0 = time.perf_counter()
         met = chain.run(args.steps, metrics=True)       # synchronises the chain's streams at the end
@@ -393,13 +443,14 @@ def main():
         if dist is not None:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         rep_dt.append(float(tmax.item()))
+    dumped = dump_outputs(args.dump_outputs, chain, met, args.save_z) if args.dump_outputs and rank == 0 else None
     gathered = None
     if dist is not None:
         from bayesnmf_amd.multichain import gather_rows
         gathered = gather_rows(met[-1:], dist, device=tdev)     # RCCL: gather the chains' last metrics rows
-        # ... and (SURVEY 8e ii) the chains' MAP window statistics: mode of A and the renormalised window means of P and E from
-        # bnmf_map on every rank (N + K N + N G doubles per chain), all-gathered like the launcher does at a MAP check
-        mp = chain.map(min(args.window, 200), None) if args.window > 0 else None
+        # ... and (SURVEY 8e ii, --full) the chains' MAP window statistics: mode of A and the renormalised window means of P and E
+        # from bnmf_map on every rank (N + K N + N G doubles per chain), all-gathered like the launcher does at a MAP check
+        mp = chain.map(min(args.window, 200), None) if args.window > 0 and args.full else None
         gathered_map = None
         if mp is not None:
             vec = np.concatenate([np.ravel(mp["A"]), np.ravel(mp["P"], order="F"), np.ravel(mp["E"], order="F")]).reshape(1, -1)
@@ -413,9 +464,10 @@ def main():
             "value": world * args.steps / tmed,
             "unit": "Gibbs iterations/s (aggregate over chains)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            # what ran before the first timed repetition: --warmup iterations, the serialised per-kernel profile pass the roofline
-            # comes from, a refill of the stream pipeline, and two untimed repetitions of the timed shape
-            "warmup_effective": args.warmup + n_prof + n_refill + n_shape * args.steps,
+            # iterations run before the first timed repetition: --warmup rounded up to whole calls of the timed shape; with --full,
+            # --warmup iterations, the serialised per-kernel profile pass the roofline comes from, a refill of the stream pipeline,
+            # and two untimed repetitions of the timed shape
+            "warmup_effective": warmup_effective,
             "rng": "philox4x32-7 (count-allocation words, variable Z) / philox4x32-10 (every other stream)",
             "ms_per_step": 1e3 * tmed / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -427,10 +479,12 @@ def main():
                                    f"({'on' if args.window > 0 else 'OFF'}) and a metrics row every iteration",
                        "chains": world, "seed": 1, "sum_M": total_counts, "record_window": args.window},
             "reps": len(rep_dt), "rep_values": [world * args.steps / t for t in rep_dt],
-            "roofline": roof,
-            "kernel_ms": prof,
+            **({"outputs": {"dir": args.dump_outputs, "files": dumped}} if dumped is not None else {}),
         }
-        if world == 1 and not args.save_z:
+        if args.full:
+            out["roofline"] = roof
+            out["kernel_ms"] = prof
+        if args.full and world == 1 and not args.save_z:
             out["full_mode"] = full_mode(M, total_counts, args, local_rank)
             out["value_save_Z"] = out["full_mode"]["records"]["value"]
             out["roofline_save_Z"] = out["full_mode"]["materialised"]["roofline"]
@@ -440,12 +494,12 @@ def main():
                                   "gathered": ["last metrics row per chain"] + ([f"MAP window statistics per chain ({gathered_map.shape[2]} doubles)"] if gathered_map is not None else [])}
     chain.close()
     if rank == 0:
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 out["secondary"] = secondary_configs(local_rank)
             except Exception as ex:  # noqa: BLE001  (a secondary timing must not lose the headline line)
                 out["secondary_error"] = repr(ex)[:300]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(M, N_)
         print(json.dumps(out), flush=True)
     if dist is not None:

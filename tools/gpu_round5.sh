@@ -2,9 +2,9 @@
 # One GPU-box pass of round 5: the evidence committed under profiles/r05_*.  Usage: tools/gpu_round5.sh (from the repository root)
 export TMPDIR=/tmp
 O=gpurun_out/r05; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-python bench.py --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err; echo "bench20 rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu-baseline --no-secondary --reps 2 > $O/bench_prof.json 2> $O/bench_prof.err; echo "prof rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err; echo "bench20 rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --no-cpu-baseline --no-secondary --reps 2 > $O/bench_prof.json 2> $O/bench_prof.err; echo "prof rc=$?"
 cp $(ls $O/prof/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv; rm -rf $O/prof
 bash tools/pmc_r5.sh $O/pmc > $O/pmc.txt 2>&1; echo "pmc rc=$?"; tail -1 $O/pmc.txt; rm -rf $O/pmc/*/
 for c in 3 3c 4; do CFG=$c ITERS=30 bash tools/prof_cfg.sh $c r05/cfg$c 14 > $O/cfg$c.txt 2>&1; cp $(ls $O/cfg$c/*/*kernel_stats.csv | head -1) $O/cfg${c}_kernel_stats.csv; rm -rf $O/cfg$c; done
