@@ -2547,23 +2547,34 @@ int bnmf_window(bnmf_handle* h, int id, int last_n, double* out) {
 }
 
 
-// copy `n` consecutive samples (oldest first) of a ring to the host: at most two contiguous runs
-static int ring_read(const bnmf_handle* h, int id, int last_n, double* out) {
+// copy the `last_n` consecutive samples that end at iteration `end_iter` (oldest first) of a ring to the host: at most two contiguous runs
+static int ring_read(const bnmf_handle* h, int id, int end_iter, int last_n, double* out) {
   const Arr& a = h->arr[id];
-  const size_t len = id_len(h, id), C = (size_t)h->wcap, s0 = (size_t)(h->iter - last_n) % C;
+  const size_t len = id_len(h, id), C = (size_t)h->wcap, s0 = (size_t)(end_iter - last_n) % C;
   const size_t n1 = (s0 + (size_t)last_n <= C) ? (size_t)last_n : C - s0;
   HIPCHK(hipMemcpy(out, a.ring + s0 * len, n1 * len * sizeof(double), hipMemcpyDeviceToHost));
   if (n1 < (size_t)last_n) HIPCHK(hipMemcpy(out + n1 * len, a.ring, ((size_t)last_n - n1) * len * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
-int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
-             double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
-  if (!h || !A_mode || !info) return fail(BNMF_EINVAL, "bnmf_map: null argument");
-  const int W = h->cfg.window;
-  if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_map: the handle timed out inside a kernel; its state is invalid");
-  if (W <= 0) return fail(BNMF_ESTATE, "bnmf_map: the handle was created with window = 0");
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_map: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+// Iterations first..last must be recorded and still kept: [max(1, iter - window + 1), iter] (the ring holds window + 1 slots, the
+// slot ahead of the oldest kept sample belongs to the iteration in flight).
+static int check_kept(const bnmf_handle* h, const char* fn, long long first, long long last) {
+  const int lo = std::max(1, h->iter - h->cfg.window + 1);
+  if (first > last || first < lo || last > h->iter)
+    return fail(BNMF_ESIZE, "%s: iterations %lld..%lld requested but only iterations %d..%d are kept (window = %d, iter = %d)", fn, first, last, lo,
+                h->iter, h->cfg.window, h->iter);
+  return 0;
+}
+static int check_recorded(const bnmf_handle* h, const char* fn) {
+  if (h->poisoned) return fail(BNMF_ESTATE, "%s: the handle timed out inside a kernel; its state is invalid", fn);
+  if (h->cfg.window <= 0) return fail(BNMF_ESTATE, "%s: the handle was created with window = 0", fn);
+  return 0;
+}
+
+// get_MAP_ over the last_n samples that end at iteration end_iter (checked by the caller)
+static int map_impl(bnmf_handle* h, int end_iter, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
+                    double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
   if (ci >= 1.0) return fail(BNMF_EINVAL, "bnmf_map: credible_interval must be below 1");
   const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
   const size_t lenP = (size_t)K * N, lenE = (size_t)N * G;
@@ -2574,7 +2585,7 @@ int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_me
   HIPCHK(hipStreamSynchronize(h->side2));
   // i. mode of A (get_mode): patterns as strings, most frequent first, ties in alphabetical order
   std::vector<double> Aw((size_t)last_n * N);
-  if (int rc = ring_read(h, BNMF_A, last_n, Aw.data())) return rc;
+  if (int rc = ring_read(h, BNMF_A, end_iter, last_n, Aw.data())) return rc;
   std::vector<std::string> keys(last_n, std::string(N, '0'));
   std::map<std::string, int> tab;
   for (int s = 0; s < last_n; ++s) { for (int n = 0; n < N; ++n) if (Aw[(size_t)s * N + n] != 0.0) keys[s][n] = '1'; tab[keys[s]]++; }
@@ -2590,7 +2601,7 @@ int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_me
   for (int s = 0; s < last_n; ++s) {
     const bool u = keys[s] == mode;
     if (used) used[s] = u ? 1 : 0;
-    if (u) slots.push_back((int)((size_t)(h->iter - last_n + s) % (size_t)h->wcap));
+    if (u) slots.push_back((int)((size_t)(end_iter - last_n + s) % (size_t)h->wcap));
   }
   const int nu = (int)slots.size();
   info->n_used = nu; info->_pad = 0;
@@ -2659,6 +2670,21 @@ int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_me
   info->rmse = std::sqrt(sse / ((double)K * (double)G));
   info->kl = kl;
   return 0;
+}
+int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
+             double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
+  if (!h || !A_mode || !info) return fail(BNMF_EINVAL, "bnmf_map: null argument");
+  if (int rc = check_recorded(h, "bnmf_map")) return rc;
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_map: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return map_impl(h, h->iter, last_n, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
+}
+int bnmf_map_at(bnmf_handle* h, int end_iter, int n_samples, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
+                double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
+  if (!h || !A_mode || !info) return fail(BNMF_EINVAL, "bnmf_map_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_map_at")) return rc;
+  if (int rc = check_kept(h, "bnmf_map_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return map_impl(h, end_iter, n_samples, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
 }
 
 // One MAP check (R/bayesNMF_sampler.R:297-321): get_MAP_ over the last min(MAP_over, iter) samples on the device, the
@@ -2777,17 +2803,13 @@ static double quantile7(std::vector<double> x, double prob) {
   return (1.0 - g) * x[j] + g * x[std::min(j + 1, x.size() - 1)];
 }
 
-int bnmf_assign(bnmf_handle* h, int last_n, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
-                double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
-  if (!h || !ref || !votes || !assigned) return fail(BNMF_EINVAL, "bnmf_assign: null argument");
-  const int W = h->cfg.window;
-  if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_assign: the handle timed out inside a kernel; its state is invalid");
-  if (W <= 0 || !h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign: no recorded samples (window = 0)");
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_assign: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+// assign_signatures_ensemble_ over the last_n samples that end at iteration end_iter (checked by the caller)
+static int assign_impl(bnmf_handle* h, int end_iter, int last_n, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
+                       double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
   if (R < 1) return fail(BNMF_EINVAL, "bnmf_assign: empty reference");
   const int K = h->cfg.K, N = h->cfg.N;
   std::vector<int> slots, sig;
-  for (int s = 0; s < last_n; ++s) if (!used || used[s]) slots.push_back((int)((size_t)(h->iter - last_n + s) % (size_t)h->wcap));
+  for (int s = 0; s < last_n; ++s) if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - last_n + s) % (size_t)h->wcap));
   for (int n = 0; n < N; ++n) if (!keep || keep[n]) sig.push_back(n);
   const int nu = (int)slots.size(), nk = (int)sig.size();
   for (int i = 0; i < N * R; ++i) votes[i] = 0.0;
@@ -2856,6 +2878,104 @@ int bnmf_assign(bnmf_handle* h, int last_n, const int32_t* used, const double* r
       if (upper) upper[n] = quantile7(x, 1.0 - (1.0 - ci) / 2.0);
     }
   }
+  return 0;
+}
+int bnmf_assign(bnmf_handle* h, int last_n, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
+                double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
+  if (!h || !ref || !votes || !assigned) return fail(BNMF_EINVAL, "bnmf_assign: null argument");
+  const int W = h->cfg.window;
+  if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_assign: the handle timed out inside a kernel; its state is invalid");
+  if (W <= 0 || !h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign: no recorded samples (window = 0)");
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_assign: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return assign_impl(h, h->iter, last_n, used, ref, R, keep, MAP_P, ci, votes, assigned, MAP_cosine, lower, upper);
+}
+int bnmf_assign_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
+                   double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
+  if (!h || !ref || !votes || !assigned) return fail(BNMF_EINVAL, "bnmf_assign_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_assign_at")) return rc;
+  if (!h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign_at: nothing recorded yet");
+  if (int rc = check_kept(h, "bnmf_assign_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return assign_impl(h, end_iter, n_samples, used, ref, R, keep, MAP_P, ci, votes, assigned, MAP_cosine, lower, upper);
+}
+
+// plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:
+// 598-669) over the recorded iterations iters[]: k_label_switch, one wave per sample with the cosine matrix in the LDS; past the LDS,
+// k_ref_cosine + k_hungarian (what bnmf_assign runs) over chunks of samples whose cosines stay within LS_CHUNK_BYTES, then k_label_gather.
+static const size_t LS_CHUNK_BYTES = (size_t)256 << 20;
+int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, const double* ref, int R, int32_t* assigned, double* cosine,
+                         int32_t* included) {
+  if (!h || !iters || !ref || !assigned || !cosine) return fail(BNMF_EINVAL, "bnmf_label_switching: null argument");
+  if (int rc = check_recorded(h, "bnmf_label_switching")) return rc;
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "bnmf_label_switching: nothing recorded yet");
+  if (n_iters < 0) return fail(BNMF_EINVAL, "bnmf_label_switching: n_iters < 0");
+  if (R < 1) return fail(BNMF_EINVAL, "bnmf_label_switching: empty reference");
+  const int K = h->cfg.K, N = h->cfg.N;
+  std::vector<int> slots(n_iters);
+  for (int i = 0; i < n_iters; ++i) {
+    if (int rc = check_kept(h, "bnmf_label_switching", iters[i], iters[i])) return rc;
+    slots[i] = (int)((size_t)(iters[i] - 1) % (size_t)h->wcap);
+  }
+  if (n_iters == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  std::vector<double> refT((size_t)K * R), rn2(R, 0.0);                 // as bnmf_assign: the catalogue row-major [k][j], its squared norms
+  for (int j = 0; j < R; ++j) for (int k = 0; k < K; ++k) { const double v = ref[k + (size_t)K * j]; refT[(size_t)k * R + j] = v; rn2[j] += v * v; }
+  const int tr = N > R ? 1 : 0, nrow = tr ? R : N, ncol = tr ? N : R;
+  const size_t hung_lds = (size_t)(ncol + 1) * (16 + 12) + (size_t)(nrow + 1) * 8;
+  const size_t ls_lds = (size_t)N * R * sizeof(double) + hung_lds;
+  const bool fused = ls_lds <= 160 * 1024;
+  if (!fused && hung_lds > 160 * 1024) return fail(BNMF_ESIZE, "bnmf_label_switching: %d x %d assignment problem exceeds the LDS of one workgroup", nrow, ncol);
+  const size_t per = (size_t)N * R * sizeof(double);
+  const int chunk = fused ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)n_iters, LS_CHUNK_BYTES / per));
+  const size_t out_n = (size_t)n_iters * N;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t oRef = 0, oN2 = oRef + up(refT.size() * 8), oSl = oN2 + up((size_t)R * 8), oAs = oSl + up((size_t)n_iters * sizeof(int)),
+               oCs = oAs + up(out_n * sizeof(int32_t)), oInc = oCs + up(out_n * sizeof(double)), oSig = oInc + up(out_n * sizeof(int32_t)),
+               oCos = oSig + up((size_t)N * sizeof(int)), oCol = oCos + up((size_t)chunk * per),
+               need = oCol + up((size_t)chunk * nrow * sizeof(int32_t));
+  if (need > h->asg_bytes) {                                             // bnmf_assign's scratch, grown on demand
+    if (h->dAsg) { HIPCHK(dfree(h->dAsg)); h->dAsg = nullptr; h->asg_bytes = 0; }
+    HIPCHK(dmalloc(&h->dAsg, need));
+    h->asg_bytes = need;
+  }
+  double *dRef = (double*)(h->dAsg + oRef), *dN2 = (double*)(h->dAsg + oN2), *dCs = (double*)(h->dAsg + oCs);
+  int *dSl = (int*)(h->dAsg + oSl), *dSig = (int*)(h->dAsg + oSig);
+  int32_t *dAs = (int32_t*)(h->dAsg + oAs), *dInc = (int32_t*)(h->dAsg + oInc);
+  HIPCHK(hipMemcpy(dRef, refT.data(), refT.size() * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dN2, rn2.data(), R * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dSl, slots.data(), (size_t)n_iters * sizeof(int), hipMemcpyHostToDevice));
+  const double* ringP = h->arr[BNMF_P].ring;
+  const double* ringA = h->arr[BNMF_A].ring;
+  if (fused) {
+    if (ls_lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_label_switch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls_lds));
+    hipLaunchKernelGGL(k_label_switch, dim3(n_iters), dim3(64), ls_lds, h->stream, ringP, ringA, K, N, (const int*)dSl, (const double*)dRef,
+                       (const double*)dN2, R, dAs, dCs, dInc);
+    HIPCHK(hipGetLastError());
+  } else {
+    std::vector<int> sig(N);
+    for (int n = 0; n < N; ++n) sig[n] = n;
+    HIPCHK(hipMemcpy(dSig, sig.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    double* dCos = (double*)(h->dAsg + oCos);
+    int32_t* dCol = (int32_t*)(h->dAsg + oCol);
+    HIPCHK(hipFuncSetAttribute((const void*)k_hungarian, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hung_lds));
+    for (int s0 = 0; s0 < n_iters; s0 += chunk) {
+      const int ns = std::min(chunk, n_iters - s0);
+      hipLaunchKernelGGL(k_ref_cosine, dim3(ns, N), dim3(128), 0, h->stream, ringP, (size_t)K * N, K, (const int*)dSl + s0, (const int*)dSig, N,
+                         (const double*)dRef, (const double*)dN2, R, dCos);
+      HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)ns * nrow * sizeof(int32_t), h->stream));
+      hipLaunchKernelGGL(k_hungarian, dim3(ns), dim3(64), hung_lds, h->stream, (const double*)dCos, N, R, tr, dCol);
+      hipLaunchKernelGGL(k_label_gather, dim3((ns + 63) / 64), dim3(64), 0, h->stream, (const double*)dCos, (const int32_t*)dCol, N, R, ns, ringA,
+                         (const int*)dSl + s0, dAs + (size_t)s0 * N, dCs + (size_t)s0 * N, dInc + (size_t)s0 * N);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  HIPCHK(hipMemcpyAsync(assigned, dAs, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(cosine, dCs, out_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (included) HIPCHK(hipMemcpyAsync(included, dInc, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n_iters; ++i)
+    if (assigned[(size_t)i * N] == -2 && N > 0) return fail(BNMF_ESTATE, "bnmf_label_switching: iteration %d has no assignment (a cosine is not finite)", iters[i]);
   return 0;
 }
 

@@ -1225,14 +1225,14 @@ __global__ __launch_bounds__(128) void k_ref_cosine(const double* ringP, size_t 
 // The rectangular assignment problem, n rows <= m columns, minimising sum cost[row][col(row)], by the shortest-augmenting-path method
 // with potentials (O(n^2 m)): the columns are spread over the lanes (the scan for the next column and the update of the potentials are
 // the two loops over m), ties go to the lowest column index, every floating-point operation is the one the sequential algorithm makes —
-// the assignment is the sequential algorithm's.  cost[row][col] = -cos[sig][ref]: rows are the kept signatures (tr = 0), or, with more
-// signatures than references, the references (tr = 1).  out[s][row] = column of the row.
-__global__ __launch_bounds__(64) void k_hungarian(const double* cosv /* [s][nk][R] */, int nk, int R, int tr, int32_t* out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// the assignment is the sequential algorithm's.  cost[row][col] = -c[sig][ref] (c = [nk][R], in global memory or the LDS): rows are the
+// signatures (tr = 0), or, with more signatures than references, the references (tr = 1).  scratch: (m + 1) * 28 + (n + 1) * 8 bytes of
+// LDS.  Returns p[0..m] in the scratch (p[col] = row + 1 matched to column col - 1, 0: none), or nullptr when no finite reduced cost is
+// left (a cosine is NaN).  Shared by k_hungarian and k_label_switch.
+BNMF_DEV const int* hungarian_wave(const double* c, int nk, int R, int tr, unsigned char* scratch) {
   const int n = tr ? R : nk, m = tr ? nk : R;
-  const int lane = threadIdx.x;
-  const double* c = cosv + (size_t)blockIdx.x * nk * R;
-  double* v = (double*)smem;                               // [m + 1]
+  const int lane = threadIdx.x & 63;
+  double* v = (double*)scratch;                            // [m + 1]
   double* minv = v + (m + 1);                              // [m + 1]
   double* u = minv + (m + 1);                              // [n + 1]
   int* p = (int*)(u + (n + 1));                            // [m + 1] row matched to the column (0: none)
@@ -1273,13 +1273,81 @@ __global__ __launch_bounds__(64) void k_hungarian(const double* cosv /* [s][nk][
         else minv[j] = minv[j] - delta;
       }
       wave_lds_fence();
-      if (j1 > m) return;                                  // no finite reduced cost (a cosine is NaN): the rows stay -1, the host reports it
+      if (j1 > m) return nullptr;                          // no finite reduced cost (a cosine is NaN)
       j0 = j1;
     } while (p[j0] != 0);
     if (lane == 0) { do { const int jn = way[j0]; p[j0] = p[jn]; j0 = jn; } while (j0); }
     wave_lds_fence();
   }
-  for (int j = lane + 1; j <= m; j += 64) if (p[j]) out[(size_t)blockIdx.x * n + (p[j] - 1)] = j - 1;
+  return p;
+}
+// cosv [s][nk][R] in global memory; out[s][row] = column of the row (the rows of a sample with a NaN cosine stay -1, the host reports it)
+__global__ __launch_bounds__(64) void k_hungarian(const double* cosv /* [s][nk][R] */, int nk, int R, int tr, int32_t* out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int n = tr ? R : nk, m = tr ? nk : R;
+  const int* p = hungarian_wave(cosv + (size_t)blockIdx.x * nk * R, nk, R, tr, smem);
+  if (!p) return;
+  for (int j = threadIdx.x + 1; j <= m; j += 64) if (p[j]) out[(size_t)blockIdx.x * n + (p[j] - 1)] = j - 1;
+}
+
+// ---- label switching (plot_label_switching, R/postprocessing_visualizations.R:598-669): for one recorded sample per workgroup (one wave),
+// hungarian_assignment(P_t, reference_P, return_mat = TRUE, keep_all_est = TRUE) (R/helpers.R:287-398) of ALL N factors, kept as its
+// diagonal.  The N x R cosine matrix is formed in the LDS with k_ref_cosine's operations, element for element (the cosines are the bits
+// bnmf_assign votes with), the assignment by hungarian_wave over it.  assigned[s][n] = reference column (-1: no partner, N > R; the
+// reference's "None" padding, cosine 0.0), cosine[s][n] its cosine, included[s][n] = (A_t[n] != 0); a sample with a cosine that is not
+// finite gets -2 everywhere (the host reports it).  LDS: N R 8 + (max(N,R) + 1) 28 + (min(N,R) + 1) 8 bytes.
+__global__ __launch_bounds__(64) void k_label_switch(const double* ringP, const double* ringA, int K, int N, const int* slots, const double* refT,
+                                                      const double* refnorm2, int R, int32_t* assigned, double* cosine, int32_t* included) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const size_t slot = (size_t)slots[s];
+  double* c = (double*)smem;                               // [N][R]
+  const double* P = ringP + slot * (size_t)K * N;
+  for (int e = lane; e < N * R; e += 64) {
+    const int n = e / R, j = e - n * R;
+    const double* Pn = P + (size_t)K * n;
+    double dot = 0.0, nn = 0.0;
+    for (int k = 0; k < K; ++k) { const double p = Pn[k]; dot = dot + p * refT[(size_t)k * R + j]; nn = nn + p * p; }
+    c[e] = dot / dsqrt(nn * refnorm2[j]);
+  }
+  wave_lds_fence();
+  const int tr = N > R ? 1 : 0, m = tr ? N : R;
+  const int* p = hungarian_wave(c, N, R, tr, smem + (size_t)N * R * sizeof(double));
+  int32_t* as = assigned + (size_t)s * N;
+  double* cs = cosine + (size_t)s * N;
+  for (int n = lane; n < N; n += 64) included[(size_t)s * N + n] = ringA[slot * N + n] != 0.0 ? 1 : 0;
+  if (!p) {
+    for (int n = lane; n < N; n += 64) { as[n] = -2; cs[n] = __builtin_nan(""); }
+    return;
+  }
+  // every factor is written once: a matched row (tr = 0: all N are), or its column (tr = 1: matched or not)
+  for (int j = lane + 1; j <= m; j += 64) {
+    if (!tr) { if (p[j]) { const int f = p[j] - 1; as[f] = j - 1; cs[f] = c[(size_t)f * R + (j - 1)]; } }
+    else if (p[j]) { as[j - 1] = p[j] - 1; cs[j - 1] = c[(size_t)(j - 1) * R + (p[j] - 1)]; }
+    else { as[j - 1] = -1; cs[j - 1] = 0.0; }
+  }
+}
+// the same outputs from k_ref_cosine + k_hungarian over a chunk of ns samples (the fallback when the cosine matrix does not fit the LDS):
+// cosv [s][N][R] (all N factors), col [s][nrow]; one thread per sample
+__global__ __launch_bounds__(64) void k_label_gather(const double* cosv, const int32_t* col, int N, int R, int ns, const double* ringA,
+                                                      const int* slots, int32_t* assigned, double* cosine, int32_t* included) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= ns) return;
+  const int tr = N > R ? 1 : 0, nrow = tr ? R : N;
+  const int32_t* a = col + (size_t)s * nrow;
+  bool ok = true;
+  for (int r = 0; r < nrow; ++r) ok = ok && a[r] >= 0;
+  int32_t* as = assigned + (size_t)s * N;
+  double* cs = cosine + (size_t)s * N;
+  for (int n = 0; n < N; ++n) {
+    as[n] = ok ? -1 : -2; cs[n] = ok ? 0.0 : __builtin_nan("");
+    included[(size_t)s * N + n] = ringA[(size_t)slots[s] * N + n] != 0.0 ? 1 : 0;
+  }
+  if (!ok) return;
+  for (int r = 0; r < nrow; ++r) {
+    const int f = tr ? a[r] : r, j = tr ? r : a[r];
+    as[f] = j; cs[f] = cosv[((size_t)s * N + f) * R + j];
+  }
 }
 
 // ---- constructor draws of the prior parameters from the hyper-priors ----

@@ -66,7 +66,8 @@ CC_METRICS = ["loglikelihood", "logposterior", "RMSE", "KL", "BIC"]
 WHY = {0: None, 1: "no change", 2: "no best", 3: "max iters"}
 
 ABI_SYMBOLS = ["bnmf_create", "bnmf_destroy", "bnmf_set_array", "bnmf_get_array", "bnmf_get_array_i32",
-               "bnmf_init", "bnmf_run", "bnmf_window", "bnmf_map", "bnmf_run_until", "bnmf_run_post_warmup", "bnmf_assign", "bnmf_get_iter", "bnmf_profile",
+               "bnmf_init", "bnmf_run", "bnmf_window", "bnmf_map", "bnmf_run_until", "bnmf_run_post_warmup", "bnmf_assign", "bnmf_map_at",
+               "bnmf_assign_at", "bnmf_label_switching", "bnmf_get_iter", "bnmf_profile",
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat"]
 
@@ -93,6 +94,9 @@ def lib():
         L.bnmf_run_post_warmup.argtypes = [C.c_void_p, C.POINTER(BnmfConvergenceControl), C.POINTER(BnmfConvergenceState), C.c_int, dp, C.c_int,
                                            C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
         L.bnmf_assign.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, C.c_double, dp, ip, dp, dp, dp]
+        L.bnmf_map_at.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp, dp, dp, ip, C.POINTER(BnmfMapInfo)]
+        L.bnmf_assign_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, C.c_double, dp, ip, dp, dp, dp]
+        L.bnmf_label_switching.argtypes = [C.c_void_p, ip, C.c_int, dp, C.c_int, ip, dp, ip]
         L.bnmf_get_iter.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.bnmf_profile.argtypes = [C.c_void_p, C.c_int, C.c_int, dp]
         L.bnmf_kernel_name.restype = C.c_char_p
@@ -306,9 +310,10 @@ class Engine:
                                         cap_checks, C.byref(nc)))
         return rows[:nr.value].copy(), maps[:nc.value].copy(), state
 
-    def assign(self, last_n, reference_P, used=None, keep=None, MAP_P=None, credible_interval=0.95):
+    def assign(self, last_n, reference_P, used=None, keep=None, MAP_P=None, credible_interval=0.95, end_iter=None):
         """assign_signatures_ensemble_ over recorded samples: votes (N x R), assigned reference per signature (-1 = not
-        kept), cosine of the MAP estimate and credible bounds of the per-sample cosines."""
+        kept), cosine of the MAP estimate and credible bounds of the per-sample cosines.  The samples are the last `last_n`
+        recorded ones, or with end_iter the `last_n` that end at iteration end_iter (bnmf_assign_at)."""
         N = self.N
         ref = np.asfortranarray(reference_P, dtype=np.float64)
         R = ref.shape[1]
@@ -318,28 +323,46 @@ class Engine:
         mp = None if MAP_P is None else np.asfortranarray(MAP_P, dtype=np.float64)
         votes, asg = np.zeros(N * R), np.empty(N, dtype=np.int32)
         mc, lo, hi = np.empty(N), np.empty(N), np.empty(N)
-        _chk(lib().bnmf_assign(self._h, last_n, None if u is None else u.ctypes.data_as(ip), _dp(ref.ravel(order="F")), R,
-                               None if kp is None else kp.ctypes.data_as(ip), None if mp is None else _dp(mp.ravel(order="F")),
-                               float(credible_interval), _dp(votes), asg.ctypes.data_as(ip), _dp(mc), _dp(lo), _dp(hi)))
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_assign if end_iter is None else lib().bnmf_assign_at)(
+            self._h, *rng, None if u is None else u.ctypes.data_as(ip), _dp(ref.ravel(order="F")), R,
+            None if kp is None else kp.ctypes.data_as(ip), None if mp is None else _dp(mp.ravel(order="F")),
+            float(credible_interval), _dp(votes), asg.ctypes.data_as(ip), _dp(mc), _dp(lo), _dp(hi)))
         return dict(votes=votes.reshape((N, R), order="F"), assigned=asg, MAP_cosine=mc, lower_cosine=lo, upper_cosine=hi)
 
-    def map(self, last_n, credible_interval=0.95):
-        """get_MAP_ over the last `last_n` recorded samples, on the device (one C-ABI call)."""
+    def map(self, last_n, credible_interval=0.95, end_iter=None):
+        """get_MAP_ over the last `last_n` recorded samples, or with end_iter the `last_n` that end at iteration end_iter
+        (bnmf_map_at), on the device (one C-ABI call)."""
         K, G, N = self.K, self.G, self.N
         Pm, Em, Am, top = np.empty(K * N), np.empty(N * G), np.empty(N), np.empty(5 * N)
         ci = credible_interval is not None and credible_interval > 0
         Pl, Pu, El, Eu = (np.empty(K * N), np.empty(K * N), np.empty(N * G), np.empty(N * G)) if ci else (None,) * 4
         used = np.empty(last_n, dtype=np.int32)
         info = BnmfMapInfo()
-        _chk(lib().bnmf_map(self._h, last_n, float(credible_interval) if ci else 0.0, _dp(Pm), _dp(Em), _dp(Am), _dp(top),
-                            *[_dp(a) if a is not None else None for a in (Pl, Pu, El, Eu)],
-                            used.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_map if end_iter is None else lib().bnmf_map_at)(
+            self._h, *rng, float(credible_interval) if ci else 0.0, _dp(Pm), _dp(Em), _dp(Am), _dp(top),
+            *[_dp(a) if a is not None else None for a in (Pl, Pu, El, Eu)], used.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
         f = lambda a, shp: None if a is None else a.reshape(shp, order="F")   # noqa: E731
         npat = min(info.n_patterns, 5)
         return dict(P=f(Pm, (K, N)), E=f(Em, (N, G)), A=Am.reshape(1, N), used=used.astype(bool),
                     P_lower=f(Pl, (K, N)), P_upper=f(Pu, (K, N)), E_lower=f(El, (N, G)), E_upper=f(Eu, (N, G)),
                     top_A=top.reshape(5, N)[:npat], top_counts=[int(c) for c in info.top_counts][:npat],
                     n_used=info.n_used, n_patterns=info.n_patterns, rmse=info.rmse, kl=info.kl)
+
+    def label_switching(self, iters, reference_P):
+        """plot_label_switching's per-sample hungarian_assignment diagonal over the recorded iterations `iters`, on the device
+        (bnmf_label_switching): assigned (0-based reference column, -1 = no partner), cosine and included (A_t != 0), each
+        (len(iters), N)."""
+        N = self.N
+        it = np.ascontiguousarray(np.atleast_1d(iters), dtype=np.int32)
+        ref = np.asfortranarray(reference_P, dtype=np.float64)
+        R = ref.shape[1]
+        ip = C.POINTER(C.c_int32)
+        asg, cos, inc = np.empty((it.size, N), dtype=np.int32), np.empty((it.size, N)), np.empty((it.size, N), dtype=np.int32)
+        _chk(lib().bnmf_label_switching(self._h, it.ctypes.data_as(ip), it.size, _dp(ref.ravel(order="F")), R, asg.ctypes.data_as(ip),
+                                        _dp(cos), inc.ctypes.data_as(ip)))
+        return dict(assigned=asg, cosine=cos, included=inc.astype(bool))
 
     def stat(self, what):
         """Sizes of the handle's per-iteration buffers (bnmf_get_stat)."""

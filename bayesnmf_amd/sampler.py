@@ -240,15 +240,39 @@ class bayesNMF_sampler:
         Mhat = np.maximum(self.get_Mhat(P, A, E), 1e-6)
         return float(poisson.logpmf(self.data, Mhat).sum())
 
-    def get_MAP(self, final=False, credible_interval=0.95):
-        """get_MAP_ (R/utils.R:194-288) over the window state$MAP_idx of recorded samples."""
+    def _kept_range(self):
+        """The recorded iterations the engine still keeps: [max(1, iter - window + 1), iter], window = all iterations with
+        save_all_samples, else MAP_over (as `samples`)."""
+        it = self.state["iter"]
+        W = len(self.temperature_schedule) if self.specs["save_all_samples"] else self.specs["convergence_control"]["MAP_over"]
+        return max(1, it - W + 1), it
+
+    def get_MAP(self, end_iter=None, n_samples=None, final=False, credible_interval=0.95):
+        """get_MAP_ (R/utils.R:194-288).  end_iter = iter (the default): over the window state$MAP_idx of recorded samples, whatever
+        n_samples says (as the reference).  Any other end_iter (save_all_samples only): over iterations end_iter - n_samples + 1 ...
+        end_iter, n_samples defaulting to MAP_over.  MAP["idx"]: the iterations of that range whose A is the mode."""
         cc = self.specs["convergence_control"]
-        n = min(cc["MAP_over"], self.state["iter"])
-        first_iter = self.state["iter"] - n + 1
+        it = self.state["iter"]
+        end_iter = it if end_iter is None else int(end_iter)
+        if not self.specs["save_all_samples"] and end_iter != it:
+            raise ValueError("end_iter cannot be provided unless self$specs$save_all_samples is TRUE")
+        at = None
+        if end_iter == it:
+            n = min(cc["MAP_over"], it)
+        else:
+            n = cc["MAP_over"] if n_samples is None else int(n_samples)
+            lo, hi = self._kept_range()
+            if n < 1 or end_iter - n + 1 < lo or end_iter > hi:
+                raise ValueError(f"iterations {end_iter - n + 1}..{end_iter} are not all recorded: the kept samples are iterations {lo}..{hi}")
+            at = end_iter
+        first_iter = end_iter - n + 1
+
+        def window(name):                                  # the n samples of the range, oldest first
+            return self._chain.window(name, n) if at is None else self._chain.window(name, it - first_iter + 1)[:n]
         if hasattr(self._chain, "map"):
             # on-device window statistics: one C-ABI call returns K*N + N*G means (+ credible bounds), no window copy
             try:
-                r = self._chain.map(n, credible_interval)
+                r = self._chain.map(n, credible_interval) if at is None else self._chain.map(n, credible_interval, end_iter=at)
             except Exception as ex:     # e.g. a credible interval that needs more order statistics than the device keeps
                 if "bnmf_window" not in str(ex):
                     raise
@@ -263,11 +287,11 @@ class bayesNMF_sampler:
                     self.credible_intervals = dict(P=dict(lower=r["P_lower"][:, keep], upper=r["P_upper"][:, keep]),
                                                    E=dict(lower=r["E_lower"][keep, :], upper=r["E_upper"][keep, :]))
                 return self.MAP
-        A_list = self._chain.window("A", n)
+        A_list = window("A")
         mode = get_mode(A_list)
         idx = mode["idx"]
         keep = np.where(np.ravel(mode["matrix"]) == 1)[0] if final else np.arange(self.dims["N"])
-        Ps, Es = self._chain.window("P", n), self._chain.window("E", n)
+        Ps, Es = window("P"), window("E")
         rs = [renormalize(Ps[i], Es[i]) for i in idx]
         Pm = np.mean([r[0][:, keep] for r in rs], axis=0)
         Em = np.mean([r[1][keep, :] for r in rs], axis=0)
@@ -490,9 +514,9 @@ class bayesNMF_sampler:
             self.log(f"Converged at {self.state['iter']} due to {self.state['why']}", verbosity=1)
 
     def assign_signatures_ensemble(self, reference_P, reference_names=None, idxs="MAP_idx", credible_interval=0.95):
-        """assign_signatures_ensemble_ (R/postprocessing.R:175-341): every posterior sample of the MAP window votes, with
-        its cosine similarity as weight, for the Hungarian assignment of its included signatures to the reference
-        catalogue `reference_P` (K x R matrix; the reference's default is its bundled COSMIC v3.3.1 SBS table).
+        """assign_signatures_ensemble_ (R/postprocessing.R:175-341): every posterior sample of the MAP window (or of the recorded
+        iterations `idxs`) votes, with its cosine similarity as weight, for the Hungarian assignment of its included signatures to
+        the reference catalogue `reference_P` (K x R matrix; the reference's default is its bundled COSMIC v3.3.1 SBS table).
         Returns dict(assignments, votes) (data frames with the reference's columns) and stores them in
         self.reference_comparison (fields reference_P, idxs, keep_sigs, assignments, votes)."""
         ref = np.asarray(reference_P, dtype=float)
@@ -503,8 +527,16 @@ class bayesNMF_sampler:
         n = min(cc["MAP_over"], self.state["iter"])
         first_iter = self.state["iter"] - n + 1
         idx = self.MAP["idx"] if isinstance(idxs, str) else list(idxs)
+        ia = np.asarray(idx, dtype=int)
+        lo, hi = self._kept_range()
+        if ia.size and (ia.min() < lo or ia.max() > hi):
+            raise ValueError(f"idxs must be recorded iterations that are still kept: {lo}..{hi}")
+        at = None
+        if ia.size and ia.min() < first_iter:          # past the last window: the samples min(idxs) ... max(idxs) (bnmf_assign_at)
+            at, first_iter = int(ia.max()), int(ia.min())
+            n = at - first_iter + 1
         used = np.zeros(n, dtype=np.int32)
-        used[np.asarray(idx) - first_iter] = 1
+        used[ia - first_iter] = 1
         N = self.dims["N"]
         A = np.ravel(self.MAP["A"])
         if len(self.MAP["keep_sigs"]) == N and (A == 0).any():      # get_MAP(final = FALSE): only included signatures
@@ -515,7 +547,8 @@ class bayesNMF_sampler:
             self.MAP["sig_idx"] = np.arange(len(keep_sigs))
         keep = np.zeros(N, dtype=np.int32); keep[keep_sigs] = 1
         MAP_full = np.zeros((self.dims["K"], N)); MAP_full[:, keep_sigs] = np.asarray(self.MAP["P"])[:, self.MAP["sig_idx"]]
-        r = self._chain.assign(n, ref, used=used, keep=keep, MAP_P=MAP_full, credible_interval=credible_interval)
+        kw = {} if at is None else dict(end_iter=at)
+        r = self._chain.assign(n, ref, used=used, keep=keep, MAP_P=MAP_full, credible_interval=credible_interval, **kw)
         rows = []
         for i in keep_sigs:
             tot = r["votes"][i].sum()
@@ -527,6 +560,40 @@ class bayesNMF_sampler:
                                          lower_cosine=r["lower_cosine"][i], upper_cosine=r["upper_cosine"][i]) for i in keep_sigs])
         self.reference_comparison.update(reference_P=ref, idxs=idx, keep_sigs=keep_sigs, assignments=assignments, votes=votes)
         return dict(assignments=assignments, votes=votes)
+
+    def label_switching(self, reference_P, reference_names=None, idx="all"):
+        """The data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below: for every
+        recorded iteration in `idx` ("all": every kept sample) the diagonal of hungarian_assignment(P_t, reference_P,
+        return_mat = TRUE, keep_all_est = TRUE) over all N latent factors, computed on the device (bnmf_label_switching).
+        Columns iter, estimated ("Est<k>"), assigned (reference name, "None" without a partner), cosine_sim, k, included
+        ("Included" / "Excluded"), ordered by iter then k.  With idx = "all" it is kept in reference_comparison["label_switching_df"]."""
+        ref = np.asarray(reference_P, dtype=float)
+        if ref.shape[0] != self.dims["K"]:
+            raise ValueError(f"Reference matrix has {ref.shape[0]} rows, but data has {self.dims['K']} rows.")
+        names = list(reference_names) if reference_names is not None else [f"Ref{j}" for j in range(1, ref.shape[1] + 1)]
+        lo, hi = self._kept_range()
+        save = isinstance(idx, str)
+        if save:
+            if idx != "all":
+                raise ValueError("Parameter `idx` must be a vector of indices or 'all'")
+            iters = np.arange(lo, hi + 1)
+        else:
+            iters = np.sort(np.asarray(idx, dtype=int).ravel(), kind="stable")
+            if iters.size and iters.min() > self.state["iter"]:
+                raise ValueError("Parameter `idx` must be a vector of indices less than or equal to the total number of iterations: "
+                                 f"{self.state['iter']}")
+            if iters.size and (iters.min() < lo or iters.max() > hi):
+                raise ValueError(f"idx must be recorded iterations that are still kept: {lo}..{hi}")
+        N = self.dims["N"]
+        r = self._chain.label_switching(iters, ref)
+        a = r["assigned"].ravel()
+        df = pd.DataFrame(dict(iter=np.repeat(iters, N), estimated=[f"Est{k}" for k in range(1, N + 1)] * len(iters),
+                               assigned=["None" if j < 0 else names[j] for j in a], cosine_sim=r["cosine"].ravel(),
+                               k=np.tile(np.arange(1.0, N + 1), len(iters)),
+                               included=np.where(r["included"].ravel(), "Included", "Excluded")))
+        if save:
+            self.reference_comparison["label_switching_df"] = df
+        return df
 
     def save_object(self):
         """save_object (R/bayesNMF_sampler.R:414-416): sampler.rds -> sampler.pkl (fields, not the device handle)."""

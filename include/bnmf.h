@@ -119,6 +119,12 @@ typedef struct {
 int bnmf_map(bnmf_handle* h, int last_n, double credible_interval, double* P_mean, double* E_mean,
              double* A_mode, double* top_A, double* P_lower, double* P_upper, double* E_lower,
              double* E_upper, int32_t* used, bnmf_map_info* info);
+/* bnmf_map over any kept range (get_MAP_(end_iter, n_samples), R/utils.R:194-230): the n_samples recorded samples that end at
+ * iteration end_iter, i.e. iterations end_iter - n_samples + 1 ... end_iter (used[n_samples], oldest first).  Every one must lie in
+ * [max(1, iter - window + 1), iter], else BNMF_ESIZE.  bnmf_map(h, n, ...) is bnmf_map_at(h, iter, n, ...). */
+int bnmf_map_at(bnmf_handle* h, int end_iter, int n_samples, double credible_interval, double* P_mean, double* E_mean,
+                double* A_mode, double* top_A, double* P_lower, double* P_upper, double* E_lower, double* E_upper,
+                int32_t* used, bnmf_map_info* info);
 
 /* The sampling loop up to convergence as ONE call (run_gibbs_sampler, R/bayesNMF_sampler.R:268-330, warm-up part):
  * blocks of iterations up to the next MAP check; at a check get_MAP_ over the last MAP_over samples on the device,
@@ -161,6 +167,20 @@ int bnmf_run_post_warmup(bnmf_handle* h, const bnmf_convergence_control* cc, bnm
 int bnmf_assign(bnmf_handle* h, int last_n, const int32_t* used, const double* reference_P, int R,
                 const int32_t* keep, const double* MAP_P, double credible_interval, double* votes,
                 int32_t* assigned_ref, double* MAP_cosine, double* lower_cosine, double* upper_cosine);
+/* bnmf_assign over any kept range: used[n_samples] flags iterations end_iter - n_samples + 1 ... end_iter (NULL = all); the range
+ * rule and BNMF_ESIZE as for bnmf_map_at.  bnmf_assign(h, n, ...) is bnmf_assign_at(h, iter, n, ...). */
+int bnmf_assign_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* reference_P, int R,
+                   const int32_t* keep, const double* MAP_P, double credible_interval, double* votes,
+                   int32_t* assigned_ref, double* MAP_cosine, double* lower_cosine, double* upper_cosine);
+
+/* The label-switching trace (plot_label_switching, R/postprocessing_visualizations.R:598-669): for every recorded iteration iters[i]
+ * (each in [max(1, iter - window + 1), iter], else BNMF_ESIZE), the diagonal of hungarian_assignment(P_t, reference_P,
+ * return_mat = TRUE, keep_all_est = TRUE) (R/helpers.R:287-398) over ALL N factors, included or not: the reference column that
+ * maximises the total cosine and that cosine (the bits bnmf_assign votes with).  With N > R the factors left without a partner get
+ * -1 and cosine 0.0 (the reference's "None" padding).  included[i][n] = (A_t[n] != 0).  Row-major [n_iters][N] outputs. */
+int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, const double* reference_P, int R,
+                         int32_t* assigned /* [n_iters][N], 0-based column or -1 */, double* cosine /* [n_iters][N] */,
+                         int32_t* included /* [n_iters][N], may be NULL */);
 
 int bnmf_get_iter(bnmf_handle* h, int* iter);
 /* sizes of the handle's per-iteration buffers (bench.py's byte counts): what = 0 bytes of item records written per iteration (save_Z on the

@@ -9,7 +9,8 @@
 # the tested equivalent and performs the same C-ABI call sequence; keep this file logic-free.  The MAP checks use
 # bnmf_map (get_MAP_ on the device: no window copy), the warm-up loop and the MH tail one call each (bnmf_run_until,
 # bnmf_run_post_warmup) unless periodic_save asks for the block-by-block loop; the recorded samples are materialised
-# into self$samples ONCE, at the end; assign_signatures_ensemble goes through bnmf_assign.  See INTEGRATION.md.
+# into self$samples ONCE, at the end; assign_signatures_ensemble goes through bnmf_assign (bnmf_assign_at for a MAP of an earlier
+# range, get_MAP(end_iter, n_samples) -> bnmf_map_at), label_switching_df through bnmf_label_switching.  See INTEGRATION.md.
 
 .bnmf_ids <- c(P = 0L, E = 1L, A = 2L, R = 3L, Z = 4L, sigmasq = 7L,
                Alpha_p = 10L, Beta_p = 11L, Alpha_e = 12L, Beta_e = 13L, Mu_p = 14L, Sigmasq_p = 15L,
@@ -68,13 +69,25 @@ bayesNMF_sampler_hip <- R6::R6Class(
       self$time$per_iter <- self$time$total / self$state$iter
       self$save_object()
     },
-    # get_MAP_ (R/utils.R:194-288) on the device: mode of A, renormalised means, 95 % bounds at the final MAP
-    get_MAP = function(final = FALSE, credible_interval = 0.95) {
-      n <- min(self$specs$convergence_control$MAP_over, self$state$iter)
-      r <- .Call("C_bnmf_map", self$handle, as.integer(n), as.double(if (final) credible_interval else 0),
-                 c(self$dims$K, self$dims$G, self$dims$N))
+    # get_MAP_ (R/utils.R:194-288) on the device: mode of A, renormalised means, 95 % bounds at the final MAP.  end_iter = iter: the
+    # window state$MAP_idx (n_samples is not used, as in the reference); another end_iter (save_all_samples only): iterations
+    # end_iter - n_samples + 1 ... end_iter (bnmf_map_at)
+    get_MAP = function(end_iter = self$state$iter, n_samples = self$specs$convergence_control$MAP_over, final = FALSE,
+                       credible_interval = 0.95) {
+      if (!self$specs$save_all_samples & end_iter != self$state$iter) {
+        stop("end_iter cannot be provided unless self$specs$save_all_samples is TRUE")
+      }
+      if (end_iter == self$state$iter) {
+        n <- min(self$specs$convergence_control$MAP_over, self$state$iter)
+        r <- .Call("C_bnmf_map", self$handle, as.integer(n), as.double(if (final) credible_interval else 0),
+                   c(self$dims$K, self$dims$G, self$dims$N))
+      } else {
+        n <- n_samples
+        r <- .Call("C_bnmf_map_at", self$handle, as.integer(end_iter), as.integer(n), as.double(if (final) credible_interval else 0),
+                   c(self$dims$K, self$dims$G, self$dims$N))
+      }
       keep <- if (final) which(r$A[1, ] == 1) else seq_len(self$dims$N)
-      first <- self$state$iter - n + 1
+      first <- end_iter - n + 1
       pats <- apply(r$top_A[seq_len(min(5, r$n_patterns)), , drop = FALSE], 1, paste, collapse = "")
       self$MAP <- list(P = r$P[, keep, drop = FALSE], A = r$A[, keep, drop = FALSE], E = r$E[keep, , drop = FALSE],
                        idx = first + which(r$used) - 1, A_counts = stats::setNames(r$top_counts[seq_along(pats)], pats),
@@ -83,14 +96,21 @@ bayesNMF_sampler_hip <- R6::R6Class(
                                                  E = list(lower = r$E_lower[keep, , drop = FALSE], upper = r$E_upper[keep, , drop = FALSE]))
       invisible(self$MAP)
     },
-    # assign_signatures_ensemble_ (R/postprocessing.R:175-341) on the recorded window: cosine matrices on the device
+    # assign_signatures_ensemble_ (R/postprocessing.R:175-341) on the recorded samples MAP$idx: cosine matrices on the device
     assign_signatures_ensemble = function(reference_P, credible_interval = 0.95) {
       n <- min(self$specs$convergence_control$MAP_over, self$state$iter)
-      used <- rep(FALSE, n); used[self$MAP$idx - (self$state$iter - n)] <- TRUE
       keep <- rep(FALSE, self$dims$N); keep[self$MAP$keep_sigs] <- TRUE
       Pfull <- matrix(0, self$dims$K, self$dims$N); Pfull[, self$MAP$keep_sigs] <- self$MAP$P
-      r <- .Call("C_bnmf_assign", self$handle, as.integer(n), used, as.matrix(reference_P), keep, Pfull, as.double(credible_interval),
-                 c(self$dims$K, self$dims$G, self$dims$N))
+      if (min(self$MAP$idx) > self$state$iter - n) {          # within the last window
+        used <- rep(FALSE, n); used[self$MAP$idx - (self$state$iter - n)] <- TRUE
+        r <- .Call("C_bnmf_assign", self$handle, as.integer(n), used, as.matrix(reference_P), keep, Pfull, as.double(credible_interval),
+                   c(self$dims$K, self$dims$G, self$dims$N))
+      } else {                                                # a MAP of get_MAP(end_iter, n_samples): min(idx) ... max(idx)
+        first <- min(self$MAP$idx); last <- max(self$MAP$idx)
+        used <- rep(FALSE, last - first + 1); used[self$MAP$idx - first + 1] <- TRUE
+        r <- .Call("C_bnmf_assign_at", self$handle, as.integer(last), as.integer(last - first + 1), used, as.matrix(reference_P), keep, Pfull,
+                   as.double(credible_interval), c(self$dims$K, self$dims$G, self$dims$N))
+      }
       self$reference_comparison$reference_P <- reference_P
       self$reference_comparison$votes <- r$votes[self$MAP$keep_sigs, , drop = FALSE]
       self$reference_comparison$assignments <- data.frame(sig = self$MAP$keep_sigs, ref = colnames(reference_P)[r$assigned[self$MAP$keep_sigs]],
@@ -98,6 +118,28 @@ bayesNMF_sampler_hip <- R6::R6Class(
                                                           upper = r$upper[self$MAP$keep_sigs])
       self$reference_comparison$idxs <- self$MAP$idx
       invisible(self$reference_comparison)
+    },
+    # the data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below, on the device
+    # (bnmf_label_switching): per recorded iteration in idx ("all": every kept sample) and latent factor, the reference signature
+    # hungarian_assignment(keep_all_est = TRUE) gives it ("None": no partner), that cosine, and whether A includes the factor
+    label_switching_df = function(reference_P, idx = "all") {
+      save_df <- FALSE
+      if (is.character(idx)) {
+        if (idx != "all") stop("Parameter `idx` must be a vector of indices or 'all'")
+        save_df <- TRUE
+        W <- if (self$specs$save_all_samples) length(self$temperature_schedule) else self$specs$convergence_control$MAP_over
+        idx <- seq(max(1, self$state$iter - W + 1), self$state$iter)
+      }
+      idx <- sort(as.integer(idx))
+      N <- self$dims$N
+      r <- .Call("C_bnmf_label_switching", self$handle, idx, as.matrix(reference_P), c(self$dims$K, self$dims$G, self$dims$N))
+      ref_names <- if (is.null(colnames(reference_P))) paste0("Ref", seq_len(ncol(reference_P))) else colnames(reference_P)
+      df <- data.frame(iter = rep(idx, each = N), estimated = paste0("Est", rep(seq_len(N), length(idx))),
+                       assigned = ifelse(is.na(as.vector(r$assigned)), "None", ref_names[as.vector(r$assigned)]),
+                       cosine_sim = as.vector(r$cosine), k = as.numeric(rep(seq_len(N), length(idx))),
+                       included = ifelse(as.vector(r$included), "Included", "Excluded"))
+      if (save_df) self$reference_comparison$label_switching_df <- df
+      df
     }
   ),
   private = list(

@@ -88,29 +88,58 @@ static SEXP named_list(int n, const char** names) {
 /* get_MAP_ on the device (R/utils.R:194-288): C_bnmf_map(ptr, last_n, credible_interval (<= 0: no bounds), dims c(K,G,N)) ->
  * list(P K x N, E N x G, A, top_A 5 x N (row i = i-th most frequent pattern), P_lower, P_upper, E_lower, E_upper, used (logical),
  *      n_used, n_patterns, top_counts, rmse, kl) */
-SEXP C_bnmf_map(SEXP ptr, SEXP last_n, SEXP ci, SEXP dims) {
-  const int n = INTEGER(last_n)[0]; const int* d = INTEGER(dims); const int K = d[0], G = d[1], N = d[2];
-  const double c = REAL(ci)[0]; const int want = c > 0.0;
+/* the result list of C_bnmf_map / C_bnmf_map_at, its buffers allocated (elements 0-8: P, E, A, top_A (5 x N row-major until
+ * map_finish), the four bounds or NULL, used (integer until map_finish)); returned unprotected */
+static SEXP map_alloc(int n, int want, SEXP dims) {
+  const int* d = INTEGER(dims); const int K = d[0], G = d[1], N = d[2];
   static const char* nms[] = {"P", "E", "A", "top_A", "P_lower", "P_upper", "E_lower", "E_upper", "used", "n_used", "n_patterns", "top_counts", "rmse", "kl"};
   SEXP out = PROTECT(named_list(14, nms));
-  SEXP P = PROTECT(Rf_allocMatrix(REALSXP, K, N)), E = PROTECT(Rf_allocMatrix(REALSXP, N, G)), A = PROTECT(Rf_allocMatrix(REALSXP, 1, N));
-  SEXP top = PROTECT(Rf_allocVector(REALSXP, 5 * (R_xlen_t)N)), used = PROTECT(Rf_allocVector(INTSXP, n));
-  SEXP Pl = PROTECT(want ? Rf_allocMatrix(REALSXP, K, N) : R_NilValue), Pu = PROTECT(want ? Rf_allocMatrix(REALSXP, K, N) : R_NilValue);
-  SEXP El = PROTECT(want ? Rf_allocMatrix(REALSXP, N, G) : R_NilValue), Eu = PROTECT(want ? Rf_allocMatrix(REALSXP, N, G) : R_NilValue);
-  bnmf_map_info info;
-  chk(bnmf_map(get_handle(ptr), n, c, REAL(P), REAL(E), REAL(A), REAL(top), want ? REAL(Pl) : NULL, want ? REAL(Pu) : NULL,
-               want ? REAL(El) : NULL, want ? REAL(Eu) : NULL, INTEGER(used), &info));
+  SET_VECTOR_ELT(out, 0, Rf_allocMatrix(REALSXP, K, N)); SET_VECTOR_ELT(out, 1, Rf_allocMatrix(REALSXP, N, G));
+  SET_VECTOR_ELT(out, 2, Rf_allocMatrix(REALSXP, 1, N)); SET_VECTOR_ELT(out, 3, Rf_allocVector(REALSXP, 5 * (R_xlen_t)N));
+  if (want) {
+    SET_VECTOR_ELT(out, 4, Rf_allocMatrix(REALSXP, K, N)); SET_VECTOR_ELT(out, 5, Rf_allocMatrix(REALSXP, K, N));
+    SET_VECTOR_ELT(out, 6, Rf_allocMatrix(REALSXP, N, G)); SET_VECTOR_ELT(out, 7, Rf_allocMatrix(REALSXP, N, G));
+  }
+  SET_VECTOR_ELT(out, 8, Rf_allocVector(INTSXP, n));
+  UNPROTECT(1);
+  return out;
+}
+static double* map_buf(SEXP out, int i) { SEXP x = VECTOR_ELT(out, i); return x == R_NilValue ? NULL : REAL(x); }
+static void map_finish(SEXP out, int n, SEXP dims, const bnmf_map_info* info) {
+  const int N = INTEGER(dims)[2];
   SEXP topm = PROTECT(Rf_allocMatrix(REALSXP, 5, N));                     /* row-major 5 x N -> R matrix */
-  for (int i = 0; i < 5; ++i) for (int j = 0; j < N; ++j) REAL(topm)[i + 5 * j] = REAL(top)[(size_t)i * N + j];
+  const double* top = REAL(VECTOR_ELT(out, 3));
+  for (int i = 0; i < 5; ++i) for (int j = 0; j < N; ++j) REAL(topm)[i + 5 * j] = top[(size_t)i * N + j];
   SEXP usedl = PROTECT(Rf_allocVector(LGLSXP, n));
-  for (int i = 0; i < n; ++i) LOGICAL(usedl)[i] = INTEGER(used)[i] != 0;
+  const int* used = INTEGER(VECTOR_ELT(out, 8));
+  for (int i = 0; i < n; ++i) LOGICAL(usedl)[i] = used[i] != 0;
   SEXP tc = PROTECT(Rf_allocVector(INTSXP, 5));
-  for (int i = 0; i < 5; ++i) INTEGER(tc)[i] = info.top_counts[i];
-  SET_VECTOR_ELT(out, 0, P); SET_VECTOR_ELT(out, 1, E); SET_VECTOR_ELT(out, 2, A); SET_VECTOR_ELT(out, 3, topm);
-  SET_VECTOR_ELT(out, 4, Pl); SET_VECTOR_ELT(out, 5, Pu); SET_VECTOR_ELT(out, 6, El); SET_VECTOR_ELT(out, 7, Eu);
-  SET_VECTOR_ELT(out, 8, usedl); SET_VECTOR_ELT(out, 9, Rf_ScalarInteger(info.n_used)); SET_VECTOR_ELT(out, 10, Rf_ScalarInteger(info.n_patterns));
-  SET_VECTOR_ELT(out, 11, tc); SET_VECTOR_ELT(out, 12, Rf_ScalarReal(info.rmse)); SET_VECTOR_ELT(out, 13, Rf_ScalarReal(info.kl));
-  UNPROTECT(13);
+  for (int i = 0; i < 5; ++i) INTEGER(tc)[i] = info->top_counts[i];
+  SET_VECTOR_ELT(out, 3, topm); SET_VECTOR_ELT(out, 8, usedl); SET_VECTOR_ELT(out, 11, tc);
+  UNPROTECT(3);
+  SET_VECTOR_ELT(out, 9, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 10, Rf_ScalarInteger(info->n_patterns));
+  SET_VECTOR_ELT(out, 12, Rf_ScalarReal(info->rmse)); SET_VECTOR_ELT(out, 13, Rf_ScalarReal(info->kl));
+}
+SEXP C_bnmf_map(SEXP ptr, SEXP last_n, SEXP ci, SEXP dims) {
+  const int n = INTEGER(last_n)[0]; const double c = REAL(ci)[0];
+  SEXP out = PROTECT(map_alloc(n, c > 0.0, dims));
+  bnmf_map_info info;
+  chk(bnmf_map(get_handle(ptr), n, c, map_buf(out, 0), map_buf(out, 1), map_buf(out, 2), map_buf(out, 3), map_buf(out, 4), map_buf(out, 5),
+               map_buf(out, 6), map_buf(out, 7), INTEGER(VECTOR_ELT(out, 8)), &info));
+  map_finish(out, n, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
+/* get_MAP_(end_iter, n_samples) (R/utils.R:194-230): C_bnmf_map_at(ptr, end_iter, n_samples, credible_interval, dims) -> the list of
+ * C_bnmf_map over iterations end_iter - n_samples + 1 ... end_iter */
+SEXP C_bnmf_map_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP ci, SEXP dims) {
+  const int n = INTEGER(n_samples)[0]; const double c = REAL(ci)[0];
+  SEXP out = PROTECT(map_alloc(n, c > 0.0, dims));
+  bnmf_map_info info;
+  chk(bnmf_map_at(get_handle(ptr), INTEGER(end_iter)[0], n, c, map_buf(out, 0), map_buf(out, 1), map_buf(out, 2), map_buf(out, 3), map_buf(out, 4),
+                  map_buf(out, 5), map_buf(out, 6), map_buf(out, 7), INTEGER(VECTOR_ELT(out, 8)), &info));
+  map_finish(out, n, dims, &info);
+  UNPROTECT(1);
   return out;
 }
 /* convergence control / state marshalling: cc_int = c(MAP_over, MAP_every, Ninarow_nochange, Ninarow_nobest, miniters, maxiters,
@@ -169,20 +198,60 @@ SEXP C_bnmf_run_post_warmup(SEXP ptr, SEXP cc_int, SEXP tol, SEXP state, SEXP po
 /* assign_signatures_ensemble_ (R/postprocessing.R:175-341): C_bnmf_assign(ptr, last_n, used (logical, or NULL = all), reference_P
  * (K x R), keep (logical length N, or NULL), MAP_P (K x N, or NULL), credible_interval, dims c(K,G,N)) ->
  * list(votes N x R, assigned (1-based column of reference_P, NA = not kept), MAP_cosine, lower, upper) */
-SEXP C_bnmf_assign(SEXP ptr, SEXP last_n, SEXP used, SEXP reference_P, SEXP keep, SEXP MAP_P, SEXP ci, SEXP dims) {
-  const int n = INTEGER(last_n)[0], N = INTEGER(dims)[2], R = Rf_ncols(reference_P);
-  int32_t* u = NULL; int32_t* kp = NULL;
-  if (used != R_NilValue) { u = (int32_t*)R_alloc(n, sizeof(int32_t)); for (int i = 0; i < n; ++i) u[i] = LOGICAL(used)[i] == TRUE; }
-  if (keep != R_NilValue) { kp = (int32_t*)R_alloc(N, sizeof(int32_t)); for (int i = 0; i < N; ++i) kp[i] = LOGICAL(keep)[i] == TRUE; }
+/* the result list of C_bnmf_assign / C_bnmf_assign_at, its buffers allocated; returned unprotected */
+static SEXP assign_alloc(int N, int R) {
   static const char* nms[] = {"votes", "assigned", "MAP_cosine", "lower", "upper"};
   SEXP out = PROTECT(named_list(5, nms));
-  SEXP votes = PROTECT(Rf_allocMatrix(REALSXP, N, R)), asg = PROTECT(Rf_allocVector(INTSXP, N));
-  SEXP mc = PROTECT(Rf_allocVector(REALSXP, N)), lo = PROTECT(Rf_allocVector(REALSXP, N)), hi = PROTECT(Rf_allocVector(REALSXP, N));
-  chk(bnmf_assign(get_handle(ptr), n, u, REAL(reference_P), R, kp, MAP_P == R_NilValue ? NULL : REAL(MAP_P), REAL(ci)[0], REAL(votes),
-                  INTEGER(asg), REAL(mc), REAL(lo), REAL(hi)));
-  for (int i = 0; i < N; ++i) INTEGER(asg)[i] = INTEGER(asg)[i] < 0 ? NA_INTEGER : INTEGER(asg)[i] + 1;
-  SET_VECTOR_ELT(out, 0, votes); SET_VECTOR_ELT(out, 1, asg); SET_VECTOR_ELT(out, 2, mc); SET_VECTOR_ELT(out, 3, lo); SET_VECTOR_ELT(out, 4, hi);
-  UNPROTECT(6);
+  SET_VECTOR_ELT(out, 0, Rf_allocMatrix(REALSXP, N, R)); SET_VECTOR_ELT(out, 1, Rf_allocVector(INTSXP, N));
+  for (int i = 2; i < 5; ++i) SET_VECTOR_ELT(out, i, Rf_allocVector(REALSXP, N));
+  UNPROTECT(1);
+  return out;
+}
+static int32_t* lgl_flags(SEXP x, int n) {                                /* logical (or NULL) -> 0/1 flags (NA counts as FALSE) */
+  if (x == R_NilValue) return NULL;
+  int32_t* f = (int32_t*)R_alloc(n, sizeof(int32_t));
+  for (int i = 0; i < n; ++i) f[i] = LOGICAL(x)[i] == TRUE;
+  return f;
+}
+static void assign_finish(SEXP out, int N) {                              /* 1-based columns of reference_P, NA = not kept */
+  int* a = INTEGER(VECTOR_ELT(out, 1));
+  for (int i = 0; i < N; ++i) a[i] = a[i] < 0 ? NA_INTEGER : a[i] + 1;
+}
+SEXP C_bnmf_assign(SEXP ptr, SEXP last_n, SEXP used, SEXP reference_P, SEXP keep, SEXP MAP_P, SEXP ci, SEXP dims) {
+  const int n = INTEGER(last_n)[0], N = INTEGER(dims)[2], R = Rf_ncols(reference_P);
+  int32_t* u = lgl_flags(used, n); int32_t* kp = lgl_flags(keep, N);
+  SEXP out = PROTECT(assign_alloc(N, R));
+  chk(bnmf_assign(get_handle(ptr), n, u, REAL(reference_P), R, kp, MAP_P == R_NilValue ? NULL : REAL(MAP_P), REAL(ci)[0], REAL(VECTOR_ELT(out, 0)),
+                  INTEGER(VECTOR_ELT(out, 1)), REAL(VECTOR_ELT(out, 2)), REAL(VECTOR_ELT(out, 3)), REAL(VECTOR_ELT(out, 4))));
+  assign_finish(out, N);
+  UNPROTECT(1);
+  return out;
+}
+/* C_bnmf_assign_at(ptr, end_iter, n_samples, used (logical length n_samples, or NULL = all), reference_P, keep, MAP_P, credible_interval,
+ * dims) -> the list of C_bnmf_assign over iterations end_iter - n_samples + 1 ... end_iter */
+SEXP C_bnmf_assign_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP reference_P, SEXP keep, SEXP MAP_P, SEXP ci, SEXP dims) {
+  const int n = INTEGER(n_samples)[0], N = INTEGER(dims)[2], R = Rf_ncols(reference_P);
+  int32_t* u = lgl_flags(used, n); int32_t* kp = lgl_flags(keep, N);
+  SEXP out = PROTECT(assign_alloc(N, R));
+  chk(bnmf_assign_at(get_handle(ptr), INTEGER(end_iter)[0], n, u, REAL(reference_P), R, kp, MAP_P == R_NilValue ? NULL : REAL(MAP_P), REAL(ci)[0],
+                     REAL(VECTOR_ELT(out, 0)), INTEGER(VECTOR_ELT(out, 1)), REAL(VECTOR_ELT(out, 2)), REAL(VECTOR_ELT(out, 3)), REAL(VECTOR_ELT(out, 4))));
+  assign_finish(out, N);
+  UNPROTECT(1);
+  return out;
+}
+/* plot_label_switching's per-sample hungarian_assignment diagonal (R/postprocessing_visualizations.R:598-669):
+ * C_bnmf_label_switching(ptr, iters (integer iteration numbers), reference_P (K x R), dims c(K,G,N)) ->
+ * list(assigned N x n_iters (1-based column of reference_P, NA = "None"), cosine N x n_iters, included N x n_iters logical):
+ * one column per iteration, factor k in row k */
+SEXP C_bnmf_label_switching(SEXP ptr, SEXP iters, SEXP reference_P, SEXP dims) {
+  const int n = (int)XLENGTH(iters), N = INTEGER(dims)[2], R = Rf_ncols(reference_P);
+  static const char* nms[] = {"assigned", "cosine", "included"};
+  SEXP out = PROTECT(named_list(3, nms));
+  SEXP asg = PROTECT(Rf_allocMatrix(INTSXP, N, n)), cs = PROTECT(Rf_allocMatrix(REALSXP, N, n)), inc = PROTECT(Rf_allocMatrix(LGLSXP, N, n));
+  chk(bnmf_label_switching(get_handle(ptr), INTEGER(iters), n, REAL(reference_P), R, INTEGER(asg), REAL(cs), LOGICAL(inc)));
+  for (R_xlen_t i = 0; i < (R_xlen_t)N * n; ++i) INTEGER(asg)[i] = INTEGER(asg)[i] < 0 ? NA_INTEGER : INTEGER(asg)[i] + 1;
+  SET_VECTOR_ELT(out, 0, asg); SET_VECTOR_ELT(out, 1, cs); SET_VECTOR_ELT(out, 2, inc);
+  UNPROTECT(4);
   return out;
 }
 SEXP C_bnmf_destroy(SEXP ptr) { handle_finalizer(ptr); return R_NilValue; }
@@ -198,7 +267,8 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_run", (DL_FUNC)&C_bnmf_run, 3}, {"C_bnmf_window", (DL_FUNC)&C_bnmf_window, 4},
   {"C_bnmf_get_iter", (DL_FUNC)&C_bnmf_get_iter, 1}, {"C_bnmf_map", (DL_FUNC)&C_bnmf_map, 4},
   {"C_bnmf_run_until", (DL_FUNC)&C_bnmf_run_until, 4}, {"C_bnmf_run_post_warmup", (DL_FUNC)&C_bnmf_run_post_warmup, 5},
-  {"C_bnmf_assign", (DL_FUNC)&C_bnmf_assign, 8},
+  {"C_bnmf_assign", (DL_FUNC)&C_bnmf_assign, 8}, {"C_bnmf_map_at", (DL_FUNC)&C_bnmf_map_at, 5},
+  {"C_bnmf_assign_at", (DL_FUNC)&C_bnmf_assign_at, 9}, {"C_bnmf_label_switching", (DL_FUNC)&C_bnmf_label_switching, 4},
   {"C_bnmf_destroy", (DL_FUNC)&C_bnmf_destroy, 1}, {"C_bnmf_device_info", (DL_FUNC)&C_bnmf_device_info, 1},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
