@@ -149,6 +149,7 @@ struct bnmf_handle {
   double *dLut = nullptr, *dTemp = nullptr, *dMetrics = nullptr, *dRaw = nullptr, *dRankCol = nullptr, *dRankMhat = nullptr;
   uint32_t* dRankSync = nullptr; int rank_grid = 0; bool rank_reg = false, rank_half = false; void* dRankDbg = nullptr;
   int32_t* dMt = nullptr; double* dEt = nullptr;
+  double *dMf = nullptr, *dMtf = nullptr;   // Normal handles: the data as fp64, M's layout and the [G][K] transpose (dM, dMt stay unset)
   int32_t* zring = nullptr;            // save_Z with a window: samples$Z, [wcap][K*N*G] int32 (only if it fits BNMF_ZRING_GB, default 32)
   double *dMhat = nullptr, *dAccPn = nullptr, *dAccEpart = nullptr; int* dNzE = nullptr; int mh_S = 1; size_t mhe_lds = 0; int mhe_gw = 0;
   size_t metrics_rows = 0;
@@ -237,7 +238,7 @@ static void refresh_dev(bnmf_handle* h) {
   d.zsumk_accum = (h->z_tile || (h->z_sort && h->zs_shared)) ? 1 : 0;
   d.k0 = (uint32_t)c.seed; d.k1 = (uint32_t)(c.seed >> 32) ^ c.chain_id;
   d.maxM = h->maxM;
-  d.M = h->dM; d.Mt = h->dMt; d.Et = h->dEt; d.R = h->dR;
+  d.M = h->dM; d.Mt = h->dMt; d.Mf = h->dMf; d.Mtf = h->dMtf; d.Et = h->dEt; d.R = h->dR;
   d.P = h->arr[BNMF_P].d; d.E = h->arr[BNMF_E].d; d.A = h->arr[BNMF_A].d;
   d.ZsumK = h->dZsumK; d.ZsumG = h->dZsumG; d.Z = h->dZ;
   d.Alpha_p = h->arr[BNMF_ALPHA_P].d; d.Beta_p = h->arr[BNMF_BETA_P].d;
@@ -287,7 +288,7 @@ int bnmf_device_info(int device, char* buf, size_t buflen) {
   return 0;
 }
 
-static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h);
+static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* Mf, bnmf_handle* h);
 // lgamma / digamma table of the Alpha sampler's tangent points (dsamplers.h g_alut): filled once per device
 static int ensure_alut(int device) {
   static bool done[64] = {};
@@ -303,10 +304,15 @@ static int ensure_alut(int device) {
   return 0;
 }
 
-int bnmf_create(const bnmf_config* cfg, const int32_t* M, bnmf_handle** out) {
-  if (!cfg || !M || !out) return fail(BNMF_EINVAL, "bnmf_create: null argument");
-  if (cfg->K < 1 || cfg->G < 1 || cfg->N < 1) return fail(BNMF_EINVAL, "bnmf_create: dims must be positive");
-  if (cfg->N > 1024) return fail(BNMF_EINVAL, "bnmf_create: N > 1024 unsupported");
+// what both entry points refuse before they look at the data
+static int check_args(const char* who, const bnmf_config* cfg, const void* M, bnmf_handle** out) {
+  if (!cfg || !M || !out) return fail(BNMF_EINVAL, "%s: null argument", who);
+  if (cfg->K < 1 || cfg->G < 1 || cfg->N < 1) return fail(BNMF_EINVAL, "%s: dims must be positive", who);
+  if (cfg->N > 1024) return fail(BNMF_EINVAL, "%s: N > 1024 unsupported", who);
+  return 0;
+}
+// M: int32 counts (bnmf_create), Mf: fp64 data (bnmf_create_f64, Normal only); exactly one is given
+static int create_handle(const bnmf_config* cfg, const int32_t* M, const double* Mf, bnmf_handle** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
     return fail(BNMF_ENODEVICE, "bnmf_create: no HIP device visible (libbnmf has no CPU fallback)");
@@ -323,7 +329,7 @@ int bnmf_create(const bnmf_config* cfg, const int32_t* M, bnmf_handle** out) {
   bnmf_handle* h = new bnmf_handle();
   h->cfg = *cfg;
   h->device = cfg->device;
-  if (int rc = create_impl(cfg, M, h)) {             // every failure path releases the handle and its device memory
+  if (int rc = create_impl(cfg, M, Mf, h)) {         // every failure path releases the handle and its device memory
     char keep[sizeof g_err]; memcpy(keep, g_err, sizeof keep);
     bnmf_destroy(h);
     memcpy(g_err, keep, sizeof keep);
@@ -331,6 +337,34 @@ int bnmf_create(const bnmf_config* cfg, const int32_t* M, bnmf_handle** out) {
   }
   *out = h;
   return 0;
+}
+
+int bnmf_create(const bnmf_config* cfg, const int32_t* M, bnmf_handle** out) {
+  if (int rc = check_args("bnmf_create", cfg, M, out)) return rc;
+  return create_handle(cfg, M, nullptr, out);
+}
+
+// Real-valued data.  Every cell is checked here, on the host, before any device call.  Normal: any finite value (the handle keeps
+// them as fp64); Poisson: whole numbers in [0, 2^31 - 1] only, converted exactly, then bnmf_create.
+int bnmf_create_f64(const bnmf_config* cfg, const double* M, bnmf_handle** out) {
+  if (int rc = check_args("bnmf_create_f64", cfg, M, out)) return rc;
+  const size_t K = cfg->K, G = cfg->G;
+  if (cfg->likelihood == BNMF_NORMAL) {
+    for (size_t g = 0; g < G; ++g)
+      for (size_t k = 0; k < K; ++k)
+        if (!std::isfinite(M[k + K * g])) return fail(BNMF_EINVAL, "bnmf_create_f64: M[%zu, %zu] = %g is not finite", k, g, M[k + K * g]);
+    return create_handle(cfg, nullptr, M, out);
+  }
+  if (cfg->likelihood != BNMF_POISSON) return fail(BNMF_EMODEL, "likelihood must be one of normal, poisson");
+  std::vector<int32_t> mi(K * G);
+  for (size_t g = 0; g < G; ++g)
+    for (size_t k = 0; k < K; ++k) {
+      const double v = M[k + K * g];
+      if (!(v >= 0.0 && v <= 2147483647.0 && v == std::floor(v)))      // (NaN fails the first test)
+        return fail(BNMF_EINVAL, "bnmf_create_f64: non-integer count M[%zu, %zu] = %g (likelihood = poisson takes whole numbers in [0, 2^31 - 1])", k, g, v);
+      mi[k + K * g] = (int32_t)v;
+    }
+  return bnmf_create(cfg, mi.data(), out);
 }
 
 // Static schedule of k_zalloc_sort (zalloc_sort.h): columns dealt into blocks of equal total count (largest column first,
@@ -987,8 +1021,9 @@ extern "C" int bnmf_probe_overlap(int device, int* overlap) {
   return probe_overlap(device, overlap);
 }
 
-static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h) {
+static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* Mf, bnmf_handle* h) {
   const size_t K = cfg->K, G = cfg->G, N = cfg->N;
+  const bool normal = cfg->likelihood == BNMF_NORMAL;
   CreateClock clk;
   if (int rc = take_stream(h->device, &h->stream)) return rc;
   if (int rc = take_stream(h->device, &h->side, 1)) return rc;
@@ -1011,11 +1046,25 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h)
   HIPCHK(hipEventCreateWithFlags(&h->ev_z, hipEventDisableTiming | hipEventDisableSystemFence));
   HIPCHK(hipEventCreateWithFlags(&h->ev_red, hipEventDisableTiming | hipEventDisableSystemFence));
   clk.mark("events");
-  HIPCHK(dmalloc(&h->dM, K * G * sizeof(int32_t)));
-  HIPCHK(hipMemcpy(h->dM, M, K * G * sizeof(int32_t), hipMemcpyHostToDevice));
-  clk.mark("M to the device");
   int mx = 0;
-  for (size_t i = 0; i < K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); if (M[i] > mx) mx = M[i]; }
+  std::vector<double> mconv;                                  // Normal data given as int32 counts: converted here (exact)
+  if (!normal) {
+    HIPCHK(dmalloc(&h->dM, K * G * sizeof(int32_t)));
+    HIPCHK(hipMemcpy(h->dM, M, K * G * sizeof(int32_t), hipMemcpyHostToDevice));
+    clk.mark("M to the device");
+    for (size_t i = 0; i < K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); if (M[i] > mx) mx = M[i]; }
+  } else {
+    // a Normal handle holds its data as fp64 whichever entry point created it; nothing is sized by counts (maxM = 0: the
+    // one-entry tables below, which no Normal kernel reads)
+    if (M) {
+      mconv.resize(K * G);
+      for (size_t i = 0; i < K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); mconv[i] = (double)M[i]; }
+      Mf = mconv.data();
+    }
+    HIPCHK(dmalloc(&h->dMf, K * G * sizeof(double)));
+    HIPCHK(hipMemcpy(h->dMf, Mf, K * G * sizeof(double), hipMemcpyHostToDevice));
+    clk.mark("M to the device");
+  }
   h->maxM = mx;
   HIPCHK(dmalloc(&h->dZsumK, N * G * sizeof(int32_t)));
   HIPCHK(dmalloc(&h->dZsumG, K * N * sizeof(int32_t)));
@@ -1104,6 +1153,8 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h)
       if (h->mhe_lds > 160 * 1024) return fail(BNMF_EINVAL, "bnmf_create: K = %zu too large for the column kernel of the MH / Normal models (LDS)", K);
       HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     // k_mh_ecol16 (K <= 128: several columns per wave): its LDS grows with N — above 64 KiB it needs the attribute, above the CU's 160 KiB
     // the sweep takes k_mh_ecol
@@ -1114,7 +1165,11 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h)
         const void* ks[] = {(const void*)k_mh_ecol16<false, false, 16>, (const void*)k_mh_ecol16<false, true, 16>, (const void*)k_mh_ecol16<false, false, 32>,
                             (const void*)k_mh_ecol16<false, true, 32>, (const void*)k_mh_ecol16<true, false, 16>, (const void*)k_mh_ecol16<true, false, 32>,
                             (const void*)k_mh_ecol16<false, false, 16, 96>, (const void*)k_mh_ecol16<false, true, 16, 96>, (const void*)k_mh_ecol16<false, false, 32, 96>,
-                            (const void*)k_mh_ecol16<false, true, 32, 96>, (const void*)k_mh_ecol16<true, false, 16, 96>, (const void*)k_mh_ecol16<true, false, 32, 96>};
+                            (const void*)k_mh_ecol16<false, true, 32, 96>, (const void*)k_mh_ecol16<true, false, 16, 96>, (const void*)k_mh_ecol16<true, false, 32, 96>,
+                            (const void*)k_mh_ecol16<false, false, 16, MHE16_KMAX, true>, (const void*)k_mh_ecol16<false, false, 32, MHE16_KMAX, true>,
+                            (const void*)k_mh_ecol16<true, false, 16, MHE16_KMAX, true>, (const void*)k_mh_ecol16<true, false, 32, MHE16_KMAX, true>,
+                            (const void*)k_mh_ecol16<false, false, 16, 96, true>, (const void*)k_mh_ecol16<false, false, 32, 96, true>,
+                            (const void*)k_mh_ecol16<true, false, 16, 96, true>, (const void*)k_mh_ecol16<true, false, 32, 96, true>};
         for (const void* kf : ks) HIPCHK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       }
     }
@@ -1125,8 +1180,13 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h)
     HIPCHK(dmalloc(&h->dAccEpart, 3 * (size_t)h->nblkE * sizeof(double)));
     HIPCHK(dmalloc(&h->dNzE, 6 * N * sizeof(int)));         // nzE[N], nzP[N] (k_mh_tail's), then the hosted form's nzE[2][N], nzP[2][N] by iteration parity
     HIPCHK(dmalloc(&h->dEt, N * G * sizeof(double)));
-    HIPCHK(dmalloc(&h->dMt, K * G * sizeof(int32_t)));
-    {
+    if (normal) {
+      HIPCHK(dmalloc(&h->dMtf, K * G * sizeof(double)));
+      std::vector<double> mt(K * G);
+      for (size_t g = 0; g < G; ++g) for (size_t k = 0; k < K; ++k) mt[g + G * k] = Mf[k + K * g];
+      HIPCHK(hipMemcpy(h->dMtf, mt.data(), K * G * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+      HIPCHK(dmalloc(&h->dMt, K * G * sizeof(int32_t)));
       std::vector<int32_t> mt(K * G);
       for (size_t g = 0; g < G; ++g) for (size_t k = 0; k < K; ++k) mt[g + G * k] = M[k + K * g];
       HIPCHK(hipMemcpy(h->dMt, mt.data(), K * G * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1152,7 +1212,8 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, bnmf_handle* h)
   clk.mark("tables kernel done");
   // Allocation-kernel geometry: independent waves, one LDS slab per wave, zacc (and P) shared per workgroup.
   // N <= 24 takes k_zalloc_reg (zalloc_reg.h), larger N the general LDS-search kernel k_zalloc (kernels.h).
-  {
+  // The Poisson Gibbs sweep alone allocates counts: a Normal handle skips all of it (its data need not be counts).
+  if (!normal) {
     ZGeom& zg = h->zg;
     zg.KP = (K % 32 == 0) ? (int)K + 1 : (int)(K | 1);
     zg.HW = (int)((N + 3) / 4);
@@ -1301,7 +1362,7 @@ int bnmf_destroy(bnmf_handle* h) {
   if (h->dZpItems) dfree(h->dZpItems); if (h->dZpWgs) dfree(h->dZpWgs); if (h->dZpBatches) dfree(h->dZpBatches); if (h->dZpSteps) dfree(h->dZpSteps); if (h->dZpCols) dfree(h->dZpCols);
   if (h->dZsItems) dfree(h->dZsItems); if (h->dZsBlocks) dfree(h->dZsBlocks); if (h->dZsCols) dfree(h->dZsCols); if (h->dZsProf) dfree(h->dZsProf); if (h->dZsM) dfree(h->dZsM); if (h->dZsRec) dfree(h->dZsRec); if (h->dZsRecRing) dfree(h->dZsRecRing); if (h->dZsMh) dfree(h->dZsMh);
   if (h->dMhat) dfree(h->dMhat); if (h->dAccPn) dfree(h->dAccPn); if (h->dAccEpart) dfree(h->dAccEpart); if (h->dNzE) dfree(h->dNzE);
-  if (h->dEt) dfree(h->dEt); if (h->dMt) dfree(h->dMt); if (h->zring) dfree(h->zring);
+  if (h->dEt) dfree(h->dEt); if (h->dMt) dfree(h->dMt); dfree(h->dMf); dfree(h->dMtf); if (h->zring) dfree(h->zring);
   if (h->ev_draw) hipEventDestroy(h->ev_draw); if (h->ev_side) hipEventDestroy(h->ev_side); if (h->ev_sideP) hipEventDestroy(h->ev_sideP); if (h->ev_p) hipEventDestroy(h->ev_p); if (h->ev_rank) hipEventDestroy(h->ev_rank); if (h->ev_z) hipEventDestroy(h->ev_z); if (h->ev_red) hipEventDestroy(h->ev_red); give_stream(h->device, h->side, 1); give_stream(h->device, h->side2, 1);
   if (h->have_ev) for (auto& e : h->ev) hipEventDestroy(e);
   if (h->dMap) dfree(h->dMap);
@@ -2029,12 +2090,18 @@ static void launch_mh_PE(bnmf_handle* h, uint32_t t, int converged, bool poll = 
     const size_t lds16x = pipe ? std::max<size_t>(lds16, RT * sizeof(double)) : lds16;
     int* nzE_set = pipe ? nzb + (t & 1u) * N : nullptr;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(g16 + nhostE), dim3(MHE_T), lds16x, h->stream, h->dev, t, (const int*)nzP_io, accE, 0, nzE_set, g16, pt); };
-    if (K <= 96 && !h->mhe_k128) {                         // register arrays for 96 rows (BNMF_MHE_K128=1: the 128-row form)
+    if (normal) {                                          // the Normal forms: fp64 data in the registers, no MH step
+      if (K <= 96 && !h->mhe_k128) { if (gw == 16) go(k_mh_ecol16<false, false, 16, 96, true>); else go(k_mh_ecol16<false, false, 32, 96, true>); }
+      else if (gw == 16) go(k_mh_ecol16<false, false, 16, MHE16_KMAX, true>);
+      else go(k_mh_ecol16<false, false, 32, MHE16_KMAX, true>);
+    } else if (K <= 96 && !h->mhe_k128) {                  // register arrays for 96 rows (BNMF_MHE_K128=1: the 128-row form)
       if (gw == 16) { if (mhstep) go(k_mh_ecol16<false, true, 16, 96>); else go(k_mh_ecol16<false, false, 16, 96>); }
       else { if (mhstep) go(k_mh_ecol16<false, true, 32, 96>); else go(k_mh_ecol16<false, false, 32, 96>); }
     } else if (gw == 16) { if (mhstep) go(k_mh_ecol16<false, true, 16>); else go(k_mh_ecol16<false, false, 16>); }
     else { if (mhstep) go(k_mh_ecol16<false, true, 32>); else go(k_mh_ecol16<false, false, 32>); }
-  } else
+  } else if (normal)
+  hipLaunchKernelGGL((k_mh_ecol<false, true>), dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)(h->dNzE + N), accE, 0);
+  else
   hipLaunchKernelGGL(k_mh_ecol<false>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, mhstep, (const int*)(h->dNzE + N), accE, 0);
 }
 static int launch_mh_metrics(bnmf_handle* h, uint32_t t, bool cells, bool with_record = false, bool with_side = false) {   // with_record: record_sample inside k_mh_tail; with_side: and the hyper sweep of t + 1
@@ -2047,13 +2114,20 @@ static int launch_mh_metrics(bnmf_handle* h, uint32_t t, bool cells, bool with_r
       int g16 = ((G + cpw - 1) / cpw + 3) / 4; if (g16 > 2048) g16 = 2048;
       const size_t lds16 = (4 * (size_t)cpw * N * (1 + PRE_W) + 2 * (size_t)N) * sizeof(double);
       const bool k96 = h->cfg.K <= 96 && !h->mhe_k128;
-      if (gw == 16 && k96) hipLaunchKernelGGL((k_mh_ecol16<true, false, 16, 96>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
+      auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{}); };
+      if (draw_sig) {                                        // the Normal forms (fp64 data)
+        if (gw == 16 && k96) go(k_mh_ecol16<true, false, 16, 96, true>);
+        else if (gw == 16) go(k_mh_ecol16<true, false, 16, MHE16_KMAX, true>);
+        else if (k96) go(k_mh_ecol16<true, false, 32, 96, true>);
+        else go(k_mh_ecol16<true, false, 32, MHE16_KMAX, true>);
+      } else if (gw == 16 && k96) hipLaunchKernelGGL((k_mh_ecol16<true, false, 16, 96>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
       else if (gw == 16) hipLaunchKernelGGL((k_mh_ecol16<true, false, 16>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
       else if (k96) hipLaunchKernelGGL((k_mh_ecol16<true, false, 32, 96>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
       else hipLaunchKernelGGL((k_mh_ecol16<true, false, 32>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
     } else {
       int grid = (G + 3) / 4; if (grid > 2048) grid = 2048;
-      hipLaunchKernelGGL(k_mh_ecol<true>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
+      if (draw_sig) hipLaunchKernelGGL((k_mh_ecol<true, true>), dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
+      else hipLaunchKernelGGL(k_mh_ecol<true>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
     }
   }
   // log-priors and acceptance sums, (for the next iteration's P sweep) Et, nzE, nzP = 0, and record_sample: one launch
@@ -2652,7 +2726,8 @@ static int map_impl(bnmf_handle* h, int end_iter, int last_n, double ci, double*
     if (r16) { if (int rc = go(k_map_quant<0, 16>, h->arr[BNMF_P].ring, lenP, mP, loP, hiP)) return rc; if (int rc = go(k_map_quant<1, 16>, h->arr[BNMF_E].ring, lenE, mE, loE, hiE)) return rc; }
     else { if (int rc = go(k_map_quant<0, 32>, h->arr[BNMF_P].ring, lenP, mP, loP, hiP)) return rc; if (int rc = go(k_map_quant<1, 32>, h->arr[BNMF_E].ring, lenE, mE, loE, hiE)) return rc; }
   }
-  hipLaunchKernelGGL(k_map_fit, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
+  if (h->dMf) hipLaunchKernelGGL(k_map_fit<double>, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const double*)h->dMf, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
+  else hipLaunchKernelGGL(k_map_fit<int32_t>, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
   HIPCHK(hipGetLastError());
   if (P_mean) HIPCHK(hipMemcpyAsync(P_mean, mP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (E_mean) HIPCHK(hipMemcpyAsync(E_mean, mE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -11,6 +11,7 @@
 // All fp64; all cross-lane sums use the canonical orders of dmath.h so results are bitwise
 // independent of scheduling.  No MFMA: the path is sampling + reductions.
 #pragma once
+#include <type_traits>
 #include "dsamplers.h"
 #include "colterms.h"
 #include "../../include/bnmf.h"
@@ -26,8 +27,10 @@ struct Dev {
   int zsumk_accum;      // the allocation kernel accumulates ZsumK across row chunks (k_zalloc_tile): k_edraw zeroes what it has consumed
   uint32_t k0, k1;
   int maxM;
-  const int32_t* M;
-  const int32_t* Mt;    // [G][K] transpose of M (MH / Normal models: lanes walk the columns of one row)
+  const int32_t* M;     // Poisson: the counts
+  const int32_t* Mt;    // [G][K] transpose of M (MH models: lanes walk the columns of one row)
+  const double* Mf;     // Normal: the data as fp64 (any finite value), M's layout
+  const double* Mtf;    // [G][K] transpose of Mf (the row sweep)
   double* Et;           // [G][N] transpose of E, refreshed by k_mh_nz before the P-side updates
   double *P, *E, *A;
   int* R;
@@ -49,6 +52,11 @@ struct RecDst { double *P, *E, *A, *R; double* pp[4]; };
 // prior parameters of iteration t live in slot t&1, so the hyper sweep of iteration t+1 can run
 // (on the side stream) while iteration t's values are still being read
 template <int SIDE> BNMF_DEV double* slot(const Dev& d, double* base, uint32_t t) { return base + (size_t)(t & 1u) * (SIDE ? d.lenE : d.lenP); }
+// the data as a kernel of either likelihood reads them: int32 counts (Poisson) or fp64 values (Normal), column-major [K][G] or the
+// [G][K] transpose.  A compile-time choice: the Poisson instantiations keep their int32 registers and code.
+template <bool NORMAL> using MElem = typename std::conditional<NORMAL, double, int32_t>::type;
+template <bool NORMAL> BNMF_DEV const MElem<NORMAL>* m_cols(const Dev& d) { if constexpr (NORMAL) return d.Mf; else return d.M; }
+template <bool NORMAL> BNMF_DEV const MElem<NORMAL>* m_rows(const Dev& d) { if constexpr (NORMAL) return d.Mtf; else return d.Mt; }
 
 BNMF_DEV double clamp_tiny(double v) { return (v < 1e-300) ? 1e-300 : v; }
 
@@ -1188,7 +1196,9 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
 }
 // compute_metrics_(P = MAP$P, A = MAP$A, E = MAP$E, MAP = TRUE) (R/utils.R:412-455): per-column squared error and
 // padded KL of Mhat = P diag(A) E; one wave per column
-__global__ __launch_bounds__(256) void k_map_fit(const int32_t* M, const double* P, const double* A, const double* E, int K, int N, int G,
+// (MT: int32 counts of a Poisson handle, fp64 data of a Normal one)
+template <typename MT>
+__global__ __launch_bounds__(256) void k_map_fit(const MT* M, const double* P, const double* A, const double* E, int K, int N, int G,
                                                   double* colsse, double* colkl) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = blockIdx.x * 4 + wave;

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
   double* lrow = mhlog + (size_t)k * G;                 // !REG: log(max(Mhat, 1e-6)) of the row; candidates at lrow + K G
   double* lcand = lrow + (size_t)K * G;
   const double LOG1 = dlog(1.0);
-  const int32_t* Mk = d.Mt + (size_t)G * k;             // M[k, g] at Mt[g + G k]
+  const MElem<NORMAL>* Mk = m_rows<NORMAL>(d) + (size_t)G * k;   // M[k, g] at Mt[g + G k] (Normal: the fp64 data)
   for (int j = tid; j < N; j += MHP_T) {
     const double pj = d.P[k + (size_t)K * j]; pa[j] = pj * d.A[j]; pcur[j] = pj;
     anz[j] = d.A[j]; anz[N + j] = nzE[j] == 0 ? 1.0 : 0.0;
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
   if (wave == MHP_W - 1) for (int j = lane; j < N; j += 64) pre_store(prq + PRE_W * j, draw_pre<0>(d, k + K * j, t, MHSTEP));
   double mh[REG ? MH_CPL : 1], enr[REG ? MH_CPL : 1], enx[REG ? MH_CPL : 1], sgr[(REG && NORMAL) ? MH_CPL : 1];
   double lg[(REG && MHSTEP) ? MH_CPL : 1];              // log(max(Mhat, 1e-6)) of the lane's cells
-  int mr[REG ? MH_CPL : 1];
+  MElem<NORMAL> mr[REG ? MH_CPL : 1];
   const int g0r = wave * MH_SEG + lane;                 // REG: this lane's cells are g0r + 64 i
   // fresh Mhat of the row (factor order), by the lane that owns the cell
   if (REG) {
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
           if (wave < S && g < min(G, (wave + 1) * MH_SEG)) {
             const double en = enr[i];
             const double m0 = mh[i], m1 = (m0 - pold * en) + pnew * en;
-            const int m = mr[i];
+            const int m = (int)mr[i];
             const MhTerms tm = mh_cell_terms(m, m0, m1, lg[MHSTEP ? i : 0], d.lgfact[m], LOG1);
             lgc[i * MHP_T] = tm.L1;
             a0 = a0 + tm.pn; a1 = a1 + tm.nold; a2 = a2 + tm.po; a3 = a3 + tm.nnew;
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
           for (int g = g0 + lane; g < gend; g += 64) {
             const double en = En[g];
             const double m0 = row[g], m1 = (m0 - pold * en) + pnew * en;
-            const int m = Mk[g];
+            const int m = (int)Mk[g];
             const int mi = m < 0 ? 0 : (m > d.maxM ? d.maxM : m);
             const MhTerms tm = mh_cell_terms(m, m0, m1, lrow[g], d.lgfact[mi], LOG1);
             lcand[g] = tm.L1;
@@ -491,11 +491,13 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
 
 // ---- E side: one wave per column, all factors in order; METRICS_ONLY skips the updates (iteration 1) ----
 // The column's Mhat[., g] lives in the wave's LDS array mhc[K] (entry kk belongs to lane kk & 63) and is maintained
-// incrementally like the rows of the P side.
+// incrementally like the rows of the P side.  NRM: the Normal model's form, on the fp64 data (no MH step).
 constexpr int MHE_T = 256;
-template <bool METRICS_ONLY>
+template <bool METRICS_ONLY, bool NRM = false>
 __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep, const int* nzP, double* accE, int draw_sig) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (NRM) mhstep = 0;
+  const MElem<NRM>* Mc = m_cols<NRM>(d);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = d.K, G = d.G, N = d.N;
   const int KR = (K + 63) >> 6;
@@ -510,7 +512,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep
     for (int j = lane; j < N; j += 64) { ec[j] = d.E[j + (size_t)N * g]; av[j] = d.A[j]; }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const bool normal = d.likelihood == BNMF_NORMAL;
+    const bool normal = NRM || d.likelihood == BNMF_NORMAL;
     double sg_col = normal ? d.sigmasq[g] : 1.0;
     if (!METRICS_ONLY) {
       for (int r = 0; r < KR; ++r) {                          // fresh Mhat of the column
@@ -543,7 +545,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep
               const double mno = mh - (pn * a_n) * eold;
               const double V = normal ? sg_col : mh;
               const double rV = 1.0 / V;
-              s1 = s1 + pn * (((double)d.M[kk + (size_t)K * g] - mno) * rV);
+              s1 = s1 + pn * (((double)Mc[kk + (size_t)K * g] - mno) * rV);
               s2 = s2 + (a_n * (pn * pn)) * rV;
             }
           }
@@ -558,7 +560,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep
             if (kk < K) {
               const double pna = Pn[kk] * a_n;
               const double m0 = mhc[kk], m1 = (m0 - pna * eold) + pna * pr;
-              const int m = d.M[kk + (size_t)K * g];
+              const int m = (int)Mc[kk + (size_t)K * g];
               const int mi = m < 0 ? 0 : (m > d.maxM ? d.maxM : m);
               const MhTerms tm = mh_cell_terms(m, m0, m1, l0c[kk], d.lgfact[mi], LOG1);
               l1c[kk] = tm.L1;
@@ -592,7 +594,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep
         if (kk < K) {
           double c = 0.0;
           for (int j = 0; j < N; ++j) c = c + (d.P[kk + (size_t)K * j] * av[j]) * ec[j];
-          const double rr = (double)d.M[kk + (size_t)K * g] - c;
+          const double rr = (double)Mc[kk + (size_t)K * g] - c;
           ss = ss + rr * rr;
         }
       }
@@ -608,7 +610,16 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep
       if (kk < K) {
         double c = 0.0;
         for (int j = 0; j < N; ++j) c = c + (d.P[kk + (size_t)K * j] * av[j]) * ec[j];
-        const int m = d.M[kk + (size_t)K * g];
+        if constexpr (NRM) {                                   // any real m: pmax(M, 1e-6) and its log here
+          const double m = Mc[kk + (size_t)K * g];
+          const double dd = c - m;
+          const double lmh = dlog(c < 1e-6 ? 1e-6 : c);
+          const double mt = m < 1e-6 ? 1e-6 : m;
+          a_sse = a_sse + dd * dd;
+          a_ll = a_ll + dnorm_log_sd(m, c, sg_col);                               // get_loglik_ normal branch R/utils.R:72-97
+          a_kl = a_kl + mt * (dlog(mt) - lmh);
+        } else {
+        const int m = Mc[kk + (size_t)K * g];
         const double dd = c - (double)m;
         const double mh = c < 1e-6 ? 1e-6 : c;
         const double lmh = dlog(mh);
@@ -618,6 +629,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol(Dev d, uint32_t t, int mhstep
         if (normal) a_ll = a_ll + dnorm_log_sd((double)m, c, sg_col);           // get_loglik_ normal branch R/utils.R:72-97
         else a_ll = a_ll + (((double)m * lmh - mh) - d.lgfact[mi]);
         a_kl = a_kl + mt * (d.logm[mi] - lmh);
+        }
       }
     }
     a_sse = wave_tree64(a_sse); a_ll = wave_tree64(a_ll); a_kl = wave_tree64(a_kl);
@@ -665,9 +677,11 @@ BNMF_DEV double grp_bcast0(double v, int lane) {          // lane 0 of the group
   return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 // KM: the rows the lanes' register arrays are sized for — 128, or 96 (the 96 trinucleotide contexts: a quarter fewer registers and no empty
-// rounds over rows 96..127; the kernel sits at the edge of two waves per SIMD)
-template <bool METRICS_ONLY, bool MHSTEP, int GW, int KM = MHE16_KMAX>
+// rounds over rows 96..127; the kernel sits at the edge of two waves per SIMD).  NRM: the Normal model's form — the lanes' cells of M are
+// fp64 registers (a compile-time choice: the Poisson forms keep their int32 registers)
+template <bool METRICS_ONLY, bool MHSTEP, int GW, int KM = MHE16_KMAX, bool NRM = false>
 __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const int* nzP, double* accE, int draw_sig, int* nzE_set, int ncolblk, MhPTail pt) {
+  static_assert(!(NRM && MHSTEP), "the Normal model has no MH step");
   constexpr int MHE16_RPL = KM / GW;                      // rows per lane
   constexpr int NS = 64 / GW;                             // accumulator slots per lane
   constexpr int CPW = 64 / GW;                            // columns per wave
@@ -687,7 +701,8 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const in
   for (int i = tid; i < N; i += MHE_T) { anz[i] = d.A[i]; anz[N + i] = (nzP && nzP[i] == 0) ? 1.0 : 0.0; }
   __syncthreads();
   const double LOG1 = dlog(1.0);
-  const bool normal = d.likelihood == BNMF_NORMAL;
+  const bool normal = NRM || d.likelihood == BNMF_NORMAL;
+  const MElem<NRM>* Mc = m_cols<NRM>(d);
   const int ngrp = (G + CPW - 1) / CPW;                       // sets of CPW columns
   for (int gq = blockIdx.x * (MHE_T / 64) + wave; gq < ngrp; gq += ncolblk * (MHE_T / 64)) {
     MHSTAMP(S0);
@@ -700,9 +715,13 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const in
     __builtin_amdgcn_wave_barrier();
     double sg_col = normal ? d.sigmasq[gc] : 1.0;
     double mh[MHE16_RPL], l0[MHSTEP ? MHE16_RPL : 1], l1[MHSTEP ? MHE16_RPL : 1];
-    int mr[MHE16_RPL];
+    MElem<NRM> mr[MHE16_RPL];
+    // the Normal metric pass reads its cells of M where it uses them (L1 / L2 hits): fp64 cells held through the fresh Mhat and the sigmasq
+    // draw cost the GW = 32, 96-row form its third wave per SIMD
+    constexpr bool LATE_M = NRM && METRICS_ONLY;
 #pragma unroll
-    for (int r = 0; r < MHE16_RPL; ++r) { const int kk = j + GW * r; mr[r] = kk < K ? d.M[kk + (size_t)K * gc] : 0; mh[r] = 0.0; }
+    for (int r = 0; r < MHE16_RPL; ++r) { const int kk = j + GW * r; mr[r] = (!LATE_M && kk < K) ? Mc[kk + (size_t)K * gc] : 0; mh[r] = 0.0; }
+    auto mcell = [&](int r) -> MElem<NRM> { if constexpr (LATE_M) return Mc[j + GW * r + (size_t)K * gc]; else return mr[r]; };   // (row < K)
     if (!METRICS_ONLY) {
       // fresh Mhat of the column: factor by factor with the lane's rows side by side, every load made (a row beyond K reads row K - 1 and is
       // zeroed afterwards; each row's sum in factor order), see k_mh_prow — in the forms that keep two waves per SIMD with it (the others go
@@ -792,7 +811,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const in
             if (j + GW * r < K) {
               const double pna = pn[r] * a_n;
               const double m0 = mh[r], m1 = (m0 - pna * eold) + pna * pr;
-              const int m = mr[r];
+              const int m = (int)mr[r];
               const int mi = m < 0 ? 0 : (m > d.maxM ? d.maxM : m);
               const MhTerms tm = mh_cell_terms(m, m0, m1, l0[MHSTEP ? r : 0], d.lgfact[mi], LOG1);
               l1[MHSTEP ? r : 0] = tm.L1;
@@ -841,7 +860,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const in
       // sample_sigmasq R/sample_params.R:275-286: sigmasq_g ~ InvGamma(Alpha_g + K/2, Beta_g + sum_k resid^2 / 2)
       double sa[NS] = {};
 #pragma unroll
-      for (int r = 0; r < MHE16_RPL; ++r) if (j + GW * r < K) { const double rr = (double)mr[r] - cfresh[r]; sa[r % NS] = sa[r % NS] + rr * rr; }
+      for (int r = 0; r < MHE16_RPL; ++r) if (j + GW * r < K) { const double rr = (double)mcell(r) - cfresh[r]; sa[r % NS] = sa[r % NS] + rr * rr; }
       const double ss = grp_bcast0<GW>(grp_tree<GW>(sa), lane);
       Stream s(d.k0, d.k1, BNMF_V_SIGMASQ, (uint32_t)gc, t);
       sg_col = rinvgamma(s, hy(d.hAlphaS, gc) + (double)K / 2.0, hy(d.hBetaS, gc) + 0.5 * ss);
@@ -852,6 +871,15 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const in
     for (int r = 0; r < MHE16_RPL; ++r) {
       if (j + GW * r < K) {
         const double c = cfresh[r];
+        if constexpr (NRM) {                                   // any real m: pmax(M, 1e-6) and its log here
+          const double m = mcell(r);
+          const double dd = c - m;
+          const double lmh = dlog(c < 1e-6 ? 1e-6 : c);
+          const double mt = m < 1e-6 ? 1e-6 : m;
+          qs[r % NS] = qs[r % NS] + dd * dd;
+          ql[r % NS] = ql[r % NS] + dnorm_log_sd(m, c, sg_col);                           // get_loglik_ normal branch R/utils.R:72-97
+          qk[r % NS] = qk[r % NS] + mt * (dlog(mt) - lmh);
+        } else {
         const int m = mr[r];
         const double dd = c - (double)m;
         const double mhv = c < 1e-6 ? 1e-6 : c;
@@ -862,6 +890,7 @@ __global__ __launch_bounds__(MHE_T) void k_mh_ecol16(Dev d, uint32_t t, const in
         if (normal) ql[r % NS] = ql[r % NS] + dnorm_log_sd((double)m, c, sg_col);           // get_loglik_ normal branch R/utils.R:72-97
         else ql[r % NS] = ql[r % NS] + (((double)m * lmh - mhv) - d.lgfact[mi]);
         qk[r % NS] = qk[r % NS] + mt * (d.logm[mi] - lmh);
+        }
       }
     }
     const double a_sse = grp_tree<GW>(qs), a_ll = grp_tree<GW>(ql), a_kl = grp_tree<GW>(qk);

@@ -83,8 +83,8 @@ BNMF_DEV double rank_cell_ll(const Dev& d, int m, double c, double sg, double lg
   const double h = c < 1e-6 ? 1e-6 : c;
   return ((double)m * dlog(h) - h) - lgf;
 }
-template <bool NORMAL>
-BNMF_DEV double rank_cell_ll_t(int m, double c, double sg, double lgf) {   // rank_cell_ll without the run-time model branch
+template <bool NORMAL, typename MT>
+BNMF_DEV double rank_cell_ll_t(MT m, double c, double sg, double lgf) {   // rank_cell_ll without the run-time model branch (MT: MElem<NORMAL>)
   if (NORMAL) {
     const double sd = dsqrt(sg);
     const double z = ((double)m - c) / sd;
@@ -97,6 +97,13 @@ BNMF_DEV double rank_cell_ll_t(int m, double c, double sg, double lgf) {   // ra
   return ((double)m * lh - h) - lgf;
 }
 BNMF_DEV double rank_lgf(const Dev& d, int m) { return d.lgfact[m < 0 ? 0 : (m > d.maxM ? d.maxM : m)]; }
+// the cell's term as the sweep of either model evaluates it: Poisson as rank_cell_ll with lgamma(m + 1) from the table, Normal on the
+// fp64 data (no table: the value need not be a count)
+template <bool NORMAL>
+BNMF_DEV double rank_cell_ll_m(const Dev& d, MElem<NORMAL> m, double c, double sg) {
+  if constexpr (NORMAL) return rank_cell_ll_t<true>(m, c, sg, 0.0);
+  else return rank_cell_ll(d, m, c, sg, rank_lgf(d, m));
+}
 // All-gather of the block sums without a separate barrier: a value is published as two 8-byte granules
 // {tag, low word}, {tag, high word} (one agent-scope relaxed store each: write-through, never torn), tag = a number
 // unique to (iteration, phase).  The DECISION WAVE of every workgroup (below) sweeps all granules with agent-scope relaxed
@@ -312,6 +319,7 @@ __global__ __launch_bounds__(HALF ? RK_TH : RK_T) void k_rank_sweep(Dev d, uint3
   const int wg = wblk * gridDim.x + blockIdx.x, Wt = gridDim.x * CW;
   const int cb = wg * RK_MAXC + whalf * CPW;               // the wave's first column (REG)
   constexpr bool normal = NORMAL;
+  const MElem<NORMAL>* Mc = m_cols<NORMAL>(d);           // the counts (Poisson) or the fp64 data (Normal)
   // tags of this launch, unique over the chain: tag0 + 1 = log-likelihood of the current state, tag0 + 2 + 2n + redo = the
   // alternative of factor n (redo = 1: evaluated again after factor n-1 flipped, see the factor loop)
   const unsigned tag0 = t * (unsigned)(2 * N + 4);
@@ -400,7 +408,7 @@ __global__ __launch_bounds__(HALF ? RK_TH : RK_T) void k_rank_sweep(Dev d, uint3
   constexpr int RK_P = CPW / 2;                           // column pairs of the second row slot
   double mh0[REG ? CPW : 1], mh1[REG ? RK_P : 1], sgc[(REG && NORMAL) ? CPW : 1];
   double lg0[(REG && !NORMAL) ? CPW : 1], lg1[(REG && !NORMAL) ? RK_P : 1];   // lgamma(M + 1) of the wave's cells
-  int mm0[REG ? CPW : 1], mm1[REG ? RK_P : 1];
+  MElem<NORMAL> mm0[REG ? CPW : 1], mm1[REG ? RK_P : 1];
   unsigned xc = 0u;                                        // HALF: publications so far (the same count in both waves of a block)
   bool xdead = false;                                      // HALF: a wait for the first half has timed out: the launch is lost, wait for nothing more
   const int half = lane >> 5, row1 = 64 + (lane & 31);    // slot 1: this lane's column of the pair and its row
@@ -447,13 +455,16 @@ __global__ __launch_bounds__(HALF ? RK_TH : RK_T) void k_rank_sweep(Dev d, uint3
   const unsigned phase = 1;
   if (REG) {
     double accv[CPW];
-    auto fresh = [&](int kk, int g, double sg, double& mhv, int& mv, double& lgv) {   // Mhat, M, lgamma(M+1) and the cell's term
+    auto fresh = [&](int kk, int g, double sg, double& mhv, MElem<NORMAL>& mv, double& lgv) {   // Mhat, M, lgamma(M+1) and the cell's term
       double cc = 0.0;
       for (int j = 0; j < N; ++j) cc = cc + (d.P[kk + (size_t)K * j] * Ash[j]) * d.E[j + (size_t)N * g];
-      const int m = d.M[kk + (size_t)K * g];
-      const double lgf = rank_lgf(d, m);
-      mhv = cc; mv = m; lgv = lgf;
-      return rank_cell_ll(d, m, cc, sg, lgf);
+      const MElem<NORMAL> m = Mc[kk + (size_t)K * g];
+      if constexpr (NORMAL) { mhv = cc; mv = m; lgv = 0.0; return rank_cell_ll_t<true>(m, cc, sg, 0.0); }
+      else {
+        const double lgf = rank_lgf(d, m);
+        mhv = cc; mv = m; lgv = lgf;
+        return rank_cell_ll(d, m, cc, sg, lgf);
+      }
     };
 #pragma unroll
     for (int c = 0; c < CPW; ++c) {                       // slot 0: rows 0..63 (cells beyond G / K: harmless values, never added)
@@ -495,8 +506,7 @@ __global__ __launch_bounds__(HALF ? RK_TH : RK_T) void k_rank_sweep(Dev d, uint3
             double cc = 0.0;
             for (int j = 0; j < N; ++j) cc = cc + (d.P[kk + (size_t)K * j] * Ash[j]) * d.E[j + (size_t)N * g];
             mhg[kk + (size_t)K * g] = cc;
-            const int m = d.M[kk + (size_t)K * g];
-            acc = acc + rank_cell_ll(d, m, cc, sg, rank_lgf(d, m));
+            acc = acc + rank_cell_ll_m<NORMAL>(d, Mc[kk + (size_t)K * g], cc, sg);
           }
         }
         bs = bs + wave_tree64(acc);
@@ -571,8 +581,7 @@ __global__ __launch_bounds__(HALF ? RK_TH : RK_T) void k_rank_sweep(Dev d, uint3
               const double tt = Pf[kk] * en;
               const double cur = mhg[kk + (size_t)K * g];
               const double alt = (a_f == 1.0) ? cur - tt : cur + tt;
-              const int m = d.M[kk + (size_t)K * g];
-              acc = acc + rank_cell_ll(d, m, alt, sg, rank_lgf(d, m));
+              acc = acc + rank_cell_ll_m<NORMAL>(d, Mc[kk + (size_t)K * g], alt, sg);
             }
           }
           bs = bs + wave_tree64(acc);

@@ -65,7 +65,7 @@ NMAPROW = 17
 CC_METRICS = ["loglikelihood", "logposterior", "RMSE", "KL", "BIC"]
 WHY = {0: None, 1: "no change", 2: "no best", 3: "max iters"}
 
-ABI_SYMBOLS = ["bnmf_create", "bnmf_destroy", "bnmf_set_array", "bnmf_get_array", "bnmf_get_array_i32",
+ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array", "bnmf_get_array", "bnmf_get_array_i32",
                "bnmf_init", "bnmf_run", "bnmf_window", "bnmf_map", "bnmf_run_until", "bnmf_run_post_warmup", "bnmf_assign", "bnmf_map_at",
                "bnmf_assign_at", "bnmf_label_switching", "bnmf_get_iter", "bnmf_profile",
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
@@ -81,6 +81,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         dp, ip, up = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
         L.bnmf_create.argtypes = [C.POINTER(BnmfConfig), ip, C.POINTER(C.c_void_p)]
+        L.bnmf_create_f64.argtypes = [C.POINTER(BnmfConfig), dp, C.POINTER(C.c_void_p)]
         L.bnmf_destroy.argtypes = [C.c_void_p]
         L.bnmf_set_array.argtypes = [C.c_void_p, C.c_int, dp, C.c_size_t]
         L.bnmf_get_array.argtypes = [C.c_void_p, C.c_int, dp, C.c_size_t]
@@ -200,7 +201,9 @@ class Engine:
     def __init__(self, M, N, likelihood="poisson", prior="gamma", MH=False, learning_rank=False,
                  rank_method="SBFI", seed=1, chain_id=0, temperature=None, save_Z=False,
                  window=0, device=0):
-        M = np.asfortranarray(M, dtype=np.int32)
+        # Normal: the data as float64, any real value (bnmf_create_f64); Poisson: int32 counts (bnmf_create)
+        normal = likelihood == "normal"
+        M = np.asfortranarray(M, dtype=np.float64 if normal else np.int32)
         self.K, self.G = M.shape
         self.N = int(N)
         self._temp = None if temperature is None else np.ascontiguousarray(temperature, dtype=np.float64)
@@ -210,7 +213,10 @@ class Engine:
                          _dp(self._temp) if self._temp is not None else None,
                          0 if self._temp is None else self._temp.size)
         h = C.c_void_p()
-        _chk(lib().bnmf_create(C.byref(cfg), M.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
+        if normal:
+            _chk(lib().bnmf_create_f64(C.byref(cfg), _dp(M), C.byref(h)))
+        else:
+            _chk(lib().bnmf_create(C.byref(cfg), M.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
         self._h = h
         self._hv = h.value
         self._run = _run_fn()

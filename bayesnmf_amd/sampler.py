@@ -142,7 +142,9 @@ class bayesNMF_sampler:
                   seed=seed, chain_id=chain_id, temperature=self.temperature_schedule, save_Z=save_Z)
         if engine_factory is None:
             kw.update(window=window, device=device)
-        self._chain = factory(np.asfortranarray(data, dtype=np.int32), self.dims["N"], **kw)
+        # Normal: real-valued data as they are (float64); Poisson: counts (int32)
+        dt = np.float64 if likelihood == "normal" else np.int32
+        self._chain = factory(np.asfortranarray(data, dtype=dt), self.dims["N"], **kw)
         self.hyperprior_params = apply_hyperprior_params(self._chain, prior, data, self.dims["N"], hyperprior_params)
         self.log("Initializing prior parameters and parameters", verbosity=1)
         for name, val in (init_prior_params or {}).items():

@@ -77,6 +77,13 @@ typedef struct {
 /* create: copies M (int32, column-major K x G) to the device.  Replaces the data/dims part of
  * bayesNMF_sampler$new (R/bayesNMF_sampler.R:140-145). */
 int bnmf_create(const bnmf_config* cfg, const int32_t* M_colmajor, bnmf_handle** out);
+/* create from real-valued data (double, column-major K x G), every cell checked on the host before any device call:
+ *  BNMF_NORMAL   any finite value, negative ones included (NaN / +-Inf: BNMF_EINVAL naming the first bad cell [k, g]);
+ *  BNMF_POISSON  whole numbers in [0, 2^31 - 1] only (anything else: BNMF_EINVAL, "non-integer count"), converted exactly,
+ *                then as bnmf_create.
+ * A Normal handle holds its data on the device as fp64 whichever entry point created it: integer data give the same chain, bit
+ * for bit, through either. */
+int bnmf_create_f64(const bnmf_config* cfg, const double* M_colmajor, bnmf_handle** out);
 int bnmf_destroy(bnmf_handle* h);
 
 /* set/get any array by id (column-major doubles; integer arrays are converted).  Hyper-prior

@@ -153,10 +153,18 @@ bayesNMF_sampler_hip <- R6::R6Class(
                 if (isTRUE(self$specs$rank_method == "BFI")) 1L else 0L, as.integer(private$hip$save_Z),
                 as.integer(if (self$specs$save_all_samples) length(self$temperature_schedule)
                            else self$specs$convergence_control$MAP_over))
-      storage.mode(self$data) <- "integer"
-      self$handle <- .Call("C_bnmf_create", self$data, c(self$dims$K, self$dims$G, self$dims$N), spec,
-                           as.double(self$temperature_schedule), as.double(private$hip$seed),
-                           as.integer(private$hip$chain_id), as.integer(private$hip$device))
+      if (self$specs$likelihood == "normal") {
+        # real-valued data, as the reference's Normal sampler reads them (R/sample_Pn.R, R/sample_params.R, R/utils.R)
+        storage.mode(self$data) <- "double"
+        self$handle <- .Call("C_bnmf_create_f64", self$data, c(self$dims$K, self$dims$G, self$dims$N), spec,
+                             as.double(self$temperature_schedule), as.double(private$hip$seed),
+                             as.integer(private$hip$chain_id), as.integer(private$hip$device))
+      } else {
+        storage.mode(self$data) <- "integer"
+        self$handle <- .Call("C_bnmf_create", self$data, c(self$dims$K, self$dims$G, self$dims$N), spec,
+                             as.double(self$temperature_schedule), as.double(private$hip$seed),
+                             as.integer(private$hip$chain_id), as.integer(private$hip$device))
+      }
       for (nm in names(self$hyperprior_params)) if (nm %in% names(.bnmf_ids) && is.matrix(self$hyperprior_params[[nm]]))
         .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$hyperprior_params[[nm]]))
       # prior parameters of iteration 1: the reference's constructor has already filled self$prior_params (user-supplied

@@ -23,9 +23,7 @@ static bnmf_handle* get_handle(SEXP ptr) {
   return h;
 }
 
-/* C_bnmf_create(data (integer K x G), dims c(K,G,N), spec c(likelihood, prior, MH, learning_rank,
- *               rank_method, save_Z, window), temperature (double), seed (double), chain_id, device) */
-SEXP C_bnmf_create(SEXP data, SEXP dims, SEXP spec, SEXP temperature, SEXP seed, SEXP chain_id, SEXP device) {
+static bnmf_config make_config(SEXP dims, SEXP spec, SEXP temperature, SEXP seed, SEXP chain_id, SEXP device) {
   bnmf_config cfg;
   const int* d = INTEGER(dims); const int* s = INTEGER(spec);
   cfg.K = d[0]; cfg.G = d[1]; cfg.N = d[2];
@@ -33,12 +31,28 @@ SEXP C_bnmf_create(SEXP data, SEXP dims, SEXP spec, SEXP temperature, SEXP seed,
   cfg.rank_method = s[4]; cfg.save_Z = s[5]; cfg.window = s[6];
   cfg.seed = (uint64_t)REAL(seed)[0]; cfg.chain_id = (uint32_t)INTEGER(chain_id)[0]; cfg.device = INTEGER(device)[0];
   cfg.temperature = REAL(temperature); cfg.n_temperature = (int64_t)XLENGTH(temperature);
-  bnmf_handle* h = NULL;
-  chk(bnmf_create(&cfg, INTEGER(data), &h));
+  return cfg;
+}
+static SEXP wrap_handle(bnmf_handle* h) {
   SEXP ptr = PROTECT(R_MakeExternalPtr(h, R_NilValue, R_NilValue));
   R_RegisterCFinalizerEx(ptr, handle_finalizer, TRUE);
   UNPROTECT(1);
   return ptr;
+}
+/* C_bnmf_create(data (integer K x G), dims c(K,G,N), spec c(likelihood, prior, MH, learning_rank,
+ *               rank_method, save_Z, window), temperature (double), seed (double), chain_id, device) */
+SEXP C_bnmf_create(SEXP data, SEXP dims, SEXP spec, SEXP temperature, SEXP seed, SEXP chain_id, SEXP device) {
+  const bnmf_config cfg = make_config(dims, spec, temperature, seed, chain_id, device);
+  bnmf_handle* h = NULL;
+  chk(bnmf_create(&cfg, INTEGER(data), &h));
+  return wrap_handle(h);
+}
+/* C_bnmf_create_f64: the same arguments with data as a double K x G matrix (real-valued data of the Normal likelihood) */
+SEXP C_bnmf_create_f64(SEXP data, SEXP dims, SEXP spec, SEXP temperature, SEXP seed, SEXP chain_id, SEXP device) {
+  const bnmf_config cfg = make_config(dims, spec, temperature, seed, chain_id, device);
+  bnmf_handle* h = NULL;
+  chk(bnmf_create_f64(&cfg, REAL(data), &h));
+  return wrap_handle(h);
 }
 SEXP C_bnmf_set_array(SEXP ptr, SEXP id, SEXP value) {
   chk(bnmf_set_array(get_handle(ptr), INTEGER(id)[0], REAL(value), (size_t)XLENGTH(value)));
@@ -262,7 +276,8 @@ SEXP C_bnmf_device_info(SEXP device) {
 }
 
 static const R_CallMethodDef call_methods[] = {
-  {"C_bnmf_create", (DL_FUNC)&C_bnmf_create, 7}, {"C_bnmf_set_array", (DL_FUNC)&C_bnmf_set_array, 3},
+  {"C_bnmf_create", (DL_FUNC)&C_bnmf_create, 7}, {"C_bnmf_create_f64", (DL_FUNC)&C_bnmf_create_f64, 7},
+  {"C_bnmf_set_array", (DL_FUNC)&C_bnmf_set_array, 3},
   {"C_bnmf_get_array", (DL_FUNC)&C_bnmf_get_array, 3}, {"C_bnmf_init", (DL_FUNC)&C_bnmf_init, 1},
   {"C_bnmf_run", (DL_FUNC)&C_bnmf_run, 3}, {"C_bnmf_window", (DL_FUNC)&C_bnmf_window, 4},
   {"C_bnmf_get_iter", (DL_FUNC)&C_bnmf_get_iter, 1}, {"C_bnmf_map", (DL_FUNC)&C_bnmf_map, 4},
