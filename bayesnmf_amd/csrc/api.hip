@@ -193,6 +193,8 @@ struct bnmf_handle {
   bool poisoned = false;                          // a bounded in-kernel wait timed out: the state is no longer the chain's, every call fails
   std::vector<double> hist;                       // [wcap][4]: loglikelihood, logposterior, P / E mean acceptance of the last iterations
   std::vector<double> temp_host;                  // temperature schedule (host copy, for the convergence rule)
+  uint64_t data_hash = 0;                         // hash of the data as the handle holds it (int32 counts, fp64 for Normal): bnmf_save_state's file header
+  unsigned char* hStage = nullptr;                // two pinned halves of bnmf_save_state / bnmf_load_state (state_io.h), made at the first of them
 };
 
 static size_t id_len(const bnmf_handle* h, int id) {
@@ -1021,6 +1023,7 @@ extern "C" int bnmf_probe_overlap(int device, int* overlap) {
   return probe_overlap(device, overlap);
 }
 
+static uint64_t state_data_hash(const void* p, size_t bytes);   // state_io.h
 static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* Mf, bnmf_handle* h) {
   const size_t K = cfg->K, G = cfg->G, N = cfg->N;
   const bool normal = cfg->likelihood == BNMF_NORMAL;
@@ -1066,6 +1069,7 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* M
     clk.mark("M to the device");
   }
   h->maxM = mx;
+  h->data_hash = normal ? state_data_hash(Mf, K * G * sizeof(double)) : state_data_hash(M, K * G * sizeof(int32_t));
   HIPCHK(dmalloc(&h->dZsumK, N * G * sizeof(int32_t)));
   HIPCHK(dmalloc(&h->dZsumG, K * N * sizeof(int32_t)));
   HIPCHK(hipMemset(h->dZsumK, 0, N * G * sizeof(int32_t)));
@@ -1370,6 +1374,7 @@ int bnmf_destroy(bnmf_handle* h) {
   if (h->devlock_fd >= 0) close(h->devlock_fd);
   if (h->devgate_fd >= 0) close(h->devgate_fd);
   if (h->dFlags) dfree(h->dFlags); if (h->dDrawOwn) dfree(h->dDrawOwn); if (h->dScal) dfree(h->dScal); if (h->hErr) hipHostFree(h->hErr);
+  if (h->hStage) hipHostFree(h->hStage);
   give_stream(h->device, h->stream);                    // synchronised at the top of this function
   delete h;
   return 0;
@@ -3150,3 +3155,5 @@ int bnmf_test_philox(int device, const uint32_t ctr[4], const uint32_t key[2], u
 int bnmf_test_philox7(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) { return test_philox_r(device, ctr, key, out, 7); }
 
 }  // extern "C"
+
+#include "state_io.h"

@@ -61,6 +61,14 @@ class BnmfConvergenceState(C.Structure):
                 ("prev_MAP_metric", C.c_double), ("best_MAP_metric", C.c_double), ("prev_percent_change", C.c_double)]
 
 
+class BnmfStateDesc(C.Structure):
+    _fields_ = [("K", C.c_int32), ("G", C.c_int32), ("N", C.c_int32), ("likelihood", C.c_int32), ("prior", C.c_int32), ("MH", C.c_int32),
+                ("learning_rank", C.c_int32), ("rank_method", C.c_int32), ("save_Z", C.c_int32), ("window", C.c_int32),
+                ("seed", C.c_uint64), ("chain_id", C.c_uint32), ("format_version", C.c_int32), ("n_temperature", C.c_int64),
+                ("data_hash", C.c_uint64), ("temperature_hash", C.c_uint64), ("first_iter", C.c_int32), ("last_iter", C.c_int32),
+                ("n_records", C.c_int32), ("_pad", C.c_int32), ("bytes", C.c_int64)]
+
+
 NMAPROW = 17
 CC_METRICS = ["loglikelihood", "logposterior", "RMSE", "KL", "BIC"]
 WHY = {0: None, 1: "no change", 2: "no best", 3: "max iters"}
@@ -69,7 +77,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_init", "bnmf_run", "bnmf_window", "bnmf_map", "bnmf_run_until", "bnmf_run_post_warmup", "bnmf_assign", "bnmf_map_at",
                "bnmf_assign_at", "bnmf_label_switching", "bnmf_get_iter", "bnmf_profile",
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
-               "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat"]
+               "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
+               "bnmf_save_state", "bnmf_load_state", "bnmf_state_info"]
 
 
 def lib():
@@ -113,6 +122,9 @@ def lib():
         L.bnmf_probe_overlap.argtypes = [C.c_int, C.POINTER(C.c_int)]
         L.bnmf_trim.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
         L.bnmf_get_stat.argtypes = [C.c_void_p, C.c_int, dp]
+        L.bnmf_save_state.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_size_t)]
+        L.bnmf_load_state.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
+        L.bnmf_state_info.argtypes = [C.c_char_p, C.POINTER(BnmfStateDesc)]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -156,6 +168,17 @@ def trim(device=0):
     b = C.c_size_t(0)
     _chk(lib().bnmf_trim(device, C.byref(b)))
     return b.value
+
+
+def state_info(path):
+    """Validate a chain state file (every checksum) and describe it, without a handle or a device (bnmf_state_info)."""
+    d = BnmfStateDesc()
+    _chk(lib().bnmf_state_info(os.fsencode(path), C.byref(d)))
+    out = {name: getattr(d, name) for name, _ in BnmfStateDesc._fields_ if name != "_pad"}
+    inv = lambda m, v: next(k for k, x in m.items() if x == v)   # noqa: E731
+    out.update(likelihood=inv(LIKELIHOOD, d.likelihood), prior=inv(PRIOR, d.prior), rank_method=inv(RANK_METHOD, d.rank_method),
+               MH=bool(d.MH), learning_rank=bool(d.learning_rank), save_Z=bool(d.save_Z))
+    return out
 
 
 def device_info(device=0):
@@ -369,6 +392,19 @@ class Engine:
         _chk(lib().bnmf_label_switching(self._h, it.ctypes.data_as(ip), it.size, _dp(ref.ravel(order="F")), R, asg.ctypes.data_as(ip),
                                         _dp(cos), inc.ctypes.data_as(ip)))
         return dict(assigned=asg, cosine=cos, included=inc.astype(bool))
+
+    def save_state(self, path, since_iter=0):
+        """Write the chain's state to `path` (bnmf_save_state): since_iter = 0 a full record (file created or truncated), S > 0 a delta
+        appended to a file whose last record is this chain at iteration S.  Returns the bytes written."""
+        b = C.c_size_t(0)
+        _chk(lib().bnmf_save_state(self._h, os.fsencode(path), int(since_iter), C.byref(b)))
+        return b.value
+
+    def load_state(self, path):
+        """Replay the records of `path` into this engine, instead of init() (bnmf_load_state).  Returns the iteration it is then at."""
+        it = C.c_int(0)
+        _chk(lib().bnmf_load_state(self._h, os.fsencode(path), C.byref(it)))
+        return it.value
 
     def stat(self, what):
         """Sizes of the handle's per-iteration buffers (bnmf_get_stat)."""

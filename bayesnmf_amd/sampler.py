@@ -66,7 +66,7 @@ class bayesNMF_sampler:
                  output_dir=None, overwrite=False, hyperprior_params=None, init_prior_params=None,
                  init_params=None, verbosity=1, periodic_save=True, save_all_samples=False,
                  seed=1, chain_id=0, device=0, save_Z=False, engine_factory=None, intermediate_credible_intervals=False,
-                 engine_side_convergence=True):
+                 engine_side_convergence=True, save_engine_state=False):
         if MH is None:
             MH = likelihood == "poisson" and prior in ("truncnormal", "exponential")
         cc = dict(convergence_control) if convergence_control is not None else new_convergence_control()
@@ -107,6 +107,11 @@ class bayesNMF_sampler:
             self.specs["rank_method"] = rank_method
         if MH:
             self.specs["post_warmup"] = post_warmup
+        window = n_iters if save_all_samples else cc["MAP_over"]
+        if save_engine_state:
+            # what load_sampler needs to rebuild the engine the saved state belongs to
+            self.specs.update(save_engine_state=True, seed=seed, chain_id=chain_id, window=window, device=device,
+                              engine_rank_method=rank_method if rank_method in ("SBFI", "BFI") else "SBFI")
         self.state = dict(iter=1, indent=0, converged=False)
         self.MAP = dict(assignment_res=None)
         self.credible_intervals = {}
@@ -135,7 +140,6 @@ class bayesNMF_sampler:
         self._check_model()
         self.log("Model check passed", verbosity=1)
 
-        window = n_iters if save_all_samples else cc["MAP_over"]
         factory = engine_factory or Engine
         kw = dict(likelihood=likelihood, prior=prior, MH=bool(MH), learning_rank=learning_rank,
                   rank_method=rank_method if rank_method in ("SBFI", "BFI") else "SBFI",
@@ -145,6 +149,9 @@ class bayesNMF_sampler:
         # Normal: real-valued data as they are (float64); Poisson: counts (int32)
         dt = np.float64 if likelihood == "normal" else np.int32
         self._chain = factory(np.asfortranarray(data, dtype=dt), self.dims["N"], **kw)
+        if save_engine_state and not hasattr(self._chain, "save_state"):
+            self.close()
+            raise ValueError("save_engine_state = TRUE needs an engine that can save its state (save_state); this engine_factory's cannot")
         self.hyperprior_params = apply_hyperprior_params(self._chain, prior, data, self.dims["N"], hyperprior_params)
         self.log("Initializing prior parameters and parameters", verbosity=1)
         for name, val in (init_prior_params or {}).items():
@@ -395,11 +402,14 @@ class bayesNMF_sampler:
             self.time["warmup"] = (start_MH - start) / 60.0
             pw = self.specs["post_warmup"]
             self.log(f"Warmup done, sampling {pw} with MH for inference", verbosity=1)
-            done = 0
-            if (hasattr(self._chain, "run_post_warmup") and self._block_hook is None and not self.specs["periodic_save"]
+            # a sampler resumed from a saved engine state (load_sampler) continues the tail where the save left it
+            done = int(self.state.get("post_warmup_done", 0)) if self.specs.get("save_engine_state") else 0
+            if (hasattr(self._chain, "run_post_warmup") and done == 0 and self._block_hook is None and not self.specs["periodic_save"]
                     and not self.specs["save_all_samples"] and self.specs.get("engine_side_convergence", True) and pw > 0):
                 self._post_warmup_on_engine(cc, pw)      # the tail as one engine call (bnmf_run_post_warmup)
                 done = pw
+                if self.specs.get("save_engine_state"):
+                    self.state["post_warmup_done"] = done
             while done < pw:
                 it = self.state["iter"]
                 nxt = (it // cc["MAP_every"] + 1) * cc["MAP_every"]
@@ -408,6 +418,8 @@ class bayesNMF_sampler:
                 self._append_metrics(rows)
                 self.state["iter"] = it + n
                 done += n
+                if self.specs.get("save_engine_state"):
+                    self.state["post_warmup_done"] = done
                 if self.state["iter"] % cc["MAP_every"] == 0 or done == pw:
                     self._check(final=(done == pw))
                     if self.specs["periodic_save"]:
@@ -598,10 +610,22 @@ class bayesNMF_sampler:
         return df
 
     def save_object(self):
-        """save_object (R/bayesNMF_sampler.R:414-416): sampler.rds -> sampler.pkl (fields, not the device handle)."""
+        """save_object (R/bayesNMF_sampler.R:414-416): sampler.rds -> sampler.pkl (fields, not the device handle).  With
+        save_engine_state the device state goes to engine_state.bin beside it: a full record at the first save, then a delta since
+        the previous save (load_sampler reopens both)."""
+        eng = self.specs.get("save_engine_state")
+        if eng:
+            since, it = int(self.state.get("engine_state_iter", 0)), int(self.state["iter"])
+            self.state["engine_state_iter"] = it               # (the pickle below describes the chain as the file will end)
         keep = {k: v for k, v in self.__dict__.items() if k not in ("_chain", "log_con", "_block_hook")}
         with open(os.path.join(self.specs["output_dir"], "sampler.pkl"), "wb") as f:
             pickle.dump(keep, f)
+        if eng:
+            path = os.path.join(self.specs["output_dir"], ENGINE_STATE_FILE)
+            if since == 0 or not os.path.exists(path):
+                self._chain.save_state(path)
+            elif since < it:                                    # (since == it: the file already ends at this iteration)
+                self._chain.save_state(path, since_iter=since)
 
     def close(self):
         if getattr(self, "log_con", None) is not None:
@@ -613,11 +637,46 @@ class bayesNMF_sampler:
             self._chain = None
 
 
+ENGINE_STATE_FILE = "engine_state.bin"
+
+
+def load_sampler(output_dir, device=None):
+    """A live sampler from a directory that bayesNMF_sampler(save_engine_state=True) saved into: sampler.pkl unpickled, an Engine made
+    with the saved config (on `device`, default the saved one) and engine_state.bin replayed into it, log.txt reopened for append.
+    samples, get_MAP(end_iter, n_samples), assign_signatures_ensemble, label_switching and run_gibbs_sampler() (resume) all work."""
+    pkl, st = os.path.join(output_dir, "sampler.pkl"), os.path.join(output_dir, ENGINE_STATE_FILE)
+    if not os.path.exists(st):
+        raise FileNotFoundError(f"load_sampler: {st} does not exist (was the sampler run with save_engine_state=True?)")
+    if not os.path.exists(pkl):
+        raise FileNotFoundError(f"load_sampler: {pkl} does not exist")
+    with open(pkl, "rb") as f:
+        fields = pickle.load(f)
+    s = bayesNMF_sampler.__new__(bayesNMF_sampler)
+    s.__dict__.update(fields)
+    sp = s.specs
+    if not sp.get("save_engine_state"):
+        raise ValueError(f"load_sampler: {pkl} was not saved with save_engine_state=True")
+    dev = sp["device"] if device is None else int(device)
+    normal = sp["likelihood"] == "normal"
+    s._chain = Engine(np.asfortranarray(s.data, dtype=np.float64 if normal else np.int32), s.dims["N"], likelihood=sp["likelihood"],
+                      prior=sp["prior"], MH=sp["MH"], learning_rank=sp["learning_rank"], rank_method=sp["engine_rank_method"],
+                      seed=sp["seed"], chain_id=sp["chain_id"], temperature=s.temperature_schedule, save_Z=sp["save_Z"],
+                      window=sp["window"], device=dev)
+    it = s._chain.load_state(st)
+    if it != int(s.state["iter"]):
+        s._chain.close()
+        raise RuntimeError(f"load_sampler: {st} ends at iteration {it}, {pkl} at iteration {int(s.state['iter'])}")
+    sp["output_dir"], sp["device"] = output_dir, dev
+    s._block_hook = None
+    s.log_con = open(os.path.join(output_dir, "log.txt"), "a")
+    return s
+
+
 def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method="SBFI", MH=None,
              convergence_control=None, prop_temp=0.2, post_warmup=None, output_dir=None, overwrite=False,
              hyperprior_params=None, init_prior_params=None, init_params=None, periodic_save=True,
              save_all_samples=True, seed=1, chain_id=0, device=0, save_Z=False, engine_factory=None,
-             intermediate_credible_intervals=False, n_chains=1, devices=None, engine_side_convergence=True):
+             intermediate_credible_intervals=False, n_chains=1, devices=None, engine_side_convergence=True, save_engine_state=False):
     """bayesNMF() (R/bayesNMF.R:24-138): build the sampler and run it; with rank_method = "BIC" run one
     fixed-rank sampler per rank and return dict(results, best_rank, sampler).
 
@@ -631,7 +690,7 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
                   hyperprior_params=hyperprior_params, init_prior_params=init_prior_params, init_params=init_params,
                   periodic_save=periodic_save, save_all_samples=save_all_samples, seed=seed, save_Z=save_Z,
                   engine_factory=engine_factory, intermediate_credible_intervals=intermediate_credible_intervals,
-                  engine_side_convergence=engine_side_convergence)
+                  engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state)
         return run_chains(data, rank, n_chains=n_chains, devices=devices, **kw)
     if output_dir is None:
         output_dir = f"nmf_{likelihood}_{prior}"
@@ -641,7 +700,7 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
                   init_params=init_params, verbosity=1, periodic_save=periodic_save,
                   save_all_samples=save_all_samples, seed=seed, chain_id=chain_id, device=device, save_Z=save_Z,
                   engine_factory=engine_factory, intermediate_credible_intervals=intermediate_credible_intervals,
-                  engine_side_convergence=engine_side_convergence)
+                  engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state)
     ranks = np.atleast_1d(np.asarray(rank, dtype=int))
     if ranks.size > 1 and rank_method == "BIC":
         # One fixed-rank sampler per rank (R/bayesNMF.R:66-126).  The reference runs them one after the other; they are

@@ -190,6 +190,36 @@ int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, cons
                          int32_t* included /* [n_iters][N], may be NULL */);
 
 int bnmf_get_iter(bnmf_handle* h, int* iter);
+
+/* A chain's state in a file, and back (checkpoint / resume; the reference's save_object, saveRDS(self), R/bayesNMF_sampler.R:414-416).
+ * The file is self-describing and deterministic: magic, a format version of its own, the bnmf_config without device,
+ * a hash of the data as the handle holds it and of the temperature schedule, then records, each with since_iter, iter, typed sections
+ * and a checksum.  A record holds what the chain's future and every kept read depend on: P, E, A, R, sigmasq, the current prior
+ * parameters, the MH acceptance arrays, ZsumK / ZsumG (Poisson), Z and its records (save_Z), the record_sample rings of the kept
+ * iterations [max(1, iter - window + 1), iter], the loglikelihood / logposterior / acceptance history of the MAP metrics; the base
+ * record also the hyper-prior values.  What the next bnmf_run recomputes is not saved.
+ * bnmf_save_state: since_iter = 0 writes a full record (the file is created or truncated); since_iter = S > 0 appends a delta — the
+ *   file's last record must be this chain at iteration S — with the current state and the kept samples of iterations S+1 .. iter.
+ *   Read-only for the chain: a chain that saves gives the same bits as one that does not.  bytes_written may be NULL.
+ * bnmf_load_state: replays every record of `path` into a handle that bnmf_create / bnmf_create_f64 has just made with the same config
+ *   and data, before bnmf_init (instead of it); the handle is then at the last record's iteration (*iter_out, may be NULL) and
+ *   continues bit for bit as the saved chain would have.  Refused (BNMF_EINVAL / BNMF_ESTATE, the mismatch named) before any device
+ *   write: another K / G / N, model, seed, chain_id, window or save_Z, other data, another schedule, bad magic or version, a truncated
+ *   file or a bad checksum (the record named), a delta that does not follow its predecessor, a handle that has run.
+ * bnmf_state_info: validates `path` (every checksum) and describes it without a handle and without a device. */
+typedef struct {
+  int32_t K, G, N, likelihood, prior, MH, learning_rank, rank_method, save_Z, window;
+  uint64_t seed;
+  uint32_t chain_id;
+  int32_t format_version;
+  int64_t n_temperature;
+  uint64_t data_hash, temperature_hash;
+  int32_t first_iter, last_iter, n_records, _pad;   /* first_iter: the full record's iteration; last_iter: where a load ends */
+  int64_t bytes;
+} bnmf_state_desc;
+int bnmf_save_state(bnmf_handle* h, const char* path, int since_iter, size_t* bytes_written);
+int bnmf_load_state(bnmf_handle* h, const char* path, int* iter_out);
+int bnmf_state_info(const char* path, bnmf_state_desc* out);
 /* sizes of the handle's per-iteration buffers (bench.py's byte counts): what = 0 bytes of item records written per iteration (save_Z on the
  * sorted schedule: samples$Z is kept as these records and expanded when read), 1 bytes of Mhat left for the per-column metric terms,
  * 2 whether samples$Z is a ring of records, 3 whether Z is expanded every iteration (BNMF_ZEAGER=1), 4 whether the MH sweep hosts what followed

@@ -11,6 +11,9 @@
 # bnmf_run_post_warmup) unless periodic_save asks for the block-by-block loop; the recorded samples are materialised
 # into self$samples ONCE, at the end; assign_signatures_ensemble goes through bnmf_assign (bnmf_assign_at for a MAP of an earlier
 # range, get_MAP(end_iter, n_samples) -> bnmf_map_at), label_switching_df through bnmf_label_switching.  See INTEGRATION.md.
+# The handle is an external pointer: readRDS of a saved sampler gives a dead one.  With save_engine_state = TRUE every save_object()
+# also writes the device state to engine_state.bin (a full record, then deltas: bnmf_save_state), and load_bayesNMF_hip(output_dir)
+# (end of this file) reads sampler.rds back, recreates the handle with the stored spec and replays that file into it (bnmf_load_state).
 
 .bnmf_ids <- c(P = 0L, E = 1L, A = 2L, R = 3L, Z = 4L, sigmasq = 7L,
                Alpha_p = 10L, Beta_p = 11L, Alpha_e = 12L, Beta_e = 13L, Mu_p = 14L, Sigmasq_p = 15L,
@@ -25,9 +28,23 @@ bayesNMF_sampler_hip <- R6::R6Class(
   "bayesNMF_sampler", inherit = bayesNMF::bayesNMF_sampler,
   public = list(
     handle = NULL,
-    initialize = function(..., seed = 1, chain_id = 0L, device = 0L, save_Z = FALSE) {
-      private$hip <- list(seed = seed, chain_id = chain_id, device = device, save_Z = save_Z)
+    initialize = function(..., seed = 1, chain_id = 0L, device = 0L, save_Z = FALSE, save_engine_state = FALSE) {
+      private$hip <- list(seed = seed, chain_id = chain_id, device = device, save_Z = save_Z, save_engine_state = save_engine_state,
+                          state_iter = 0L, post_warmup_done = 0)
       super$initialize(...)     # runs the reference constructor; its prior draws are redirected below
+    },
+    # save_object (R/bayesNMF_sampler.R:414-416): sampler.rds, then (save_engine_state) the device state beside it — a full record at
+    # the first save, a delta since the previous save afterwards
+    save_object = function() {
+      since <- private$hip$state_iter
+      if (isTRUE(private$hip$save_engine_state)) private$hip$state_iter <- as.integer(self$state$iter)
+      super$save_object()
+      if (isTRUE(private$hip$save_engine_state)) {
+        path <- file.path(self$specs$output_dir, "engine_state.bin")
+        if (since == 0L || !file.exists(path)) .Call("C_bnmf_save_state", self$handle, path, 0L)
+        else if (since < self$state$iter) .Call("C_bnmf_save_state", self$handle, path, as.integer(since))
+      }
+      invisible(self)
     },
     run_gibbs_sampler = function() {
       cc <- self$specs$convergence_control
@@ -51,11 +68,11 @@ bayesNMF_sampler_hip <- R6::R6Class(
                                as.integer(self$specs$post_warmup)), cc)
           self$get_MAP(final = TRUE)
         } else {
-          done <- 0
+          done <- private$hip$post_warmup_done                 # (a sampler reopened by load_bayesNMF_hip continues its tail)
           while (done < self$specs$post_warmup) {
             nxt <- (self$state$iter %/% cc$MAP_every + 1) * cc$MAP_every
             n <- min(nxt - self$state$iter, self$specs$post_warmup - done)
-            private$run_block(n, converged = TRUE); done <- done + n
+            private$run_block(n, converged = TRUE); done <- done + n; private$hip$post_warmup_done <- done
             if (self$state$iter %% cc$MAP_every == 0 | done == self$specs$post_warmup) {
               self$get_MAP(final = done == self$specs$post_warmup)
               private$check_convergence(final = done == self$specs$post_warmup)
@@ -147,6 +164,21 @@ bayesNMF_sampler_hip <- R6::R6Class(
     # the constructor's sample_params(from_prior = TRUE) + record_sample + update_sample_metrics
     sample_params = function(skip = c(), from_prior = FALSE) {
       if (!from_prior) stop("per-iteration sampling goes through run_block()")
+      private$create_handle()
+      for (nm in names(self$hyperprior_params)) if (nm %in% names(.bnmf_ids) && is.matrix(self$hyperprior_params[[nm]]))
+        .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$hyperprior_params[[nm]]))
+      # prior parameters of iteration 1: the reference's constructor has already filled self$prior_params (user-supplied
+      # init_prior_params verbatim, the rest drawn from the hyper-priors in R, R/sample_priors.R:15-141).  All of them go
+      # to the device, which keeps supplied arrays verbatim (bnmf_set_array before bnmf_init), so samples$<name>[[1]]
+      # equals what the constructor produced (vignettes/advanced.qmd:181-185, :245-249, :315-319).
+      for (nm in names(self$prior_params)) if (nm %in% names(.bnmf_ids) && is.matrix(self$prior_params[[nm]]))
+        .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$prior_params[[nm]]))
+      for (nm in skip) if (nm %in% names(.bnmf_ids)) .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$params[[nm]]))
+      row <- .Call("C_bnmf_init", self$handle)
+      private$pull_state(); private$bind_metrics(matrix(row, ncol = 1))
+    },
+    # the handle for this sampler's spec and data (C_bnmf_create, or C_bnmf_create_f64 for likelihood = "normal")
+    create_handle = function() {
       lk <- c(poisson = 0L, normal = 1L); pr <- c(truncnormal = 0L, exponential = 1L, gamma = 2L)
       spec <- c(lk[[self$specs$likelihood]], pr[[self$specs$prior]], as.integer(self$specs$MH),
                 as.integer(self$specs$learning_rank),
@@ -165,17 +197,22 @@ bayesNMF_sampler_hip <- R6::R6Class(
                              as.double(self$temperature_schedule), as.double(private$hip$seed),
                              as.integer(private$hip$chain_id), as.integer(private$hip$device))
       }
-      for (nm in names(self$hyperprior_params)) if (nm %in% names(.bnmf_ids) && is.matrix(self$hyperprior_params[[nm]]))
-        .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$hyperprior_params[[nm]]))
-      # prior parameters of iteration 1: the reference's constructor has already filled self$prior_params (user-supplied
-      # init_prior_params verbatim, the rest drawn from the hyper-priors in R, R/sample_priors.R:15-141).  All of them go
-      # to the device, which keeps supplied arrays verbatim (bnmf_set_array before bnmf_init), so samples$<name>[[1]]
-      # equals what the constructor produced (vignettes/advanced.qmd:181-185, :245-249, :315-319).
-      for (nm in names(self$prior_params)) if (nm %in% names(.bnmf_ids) && is.matrix(self$prior_params[[nm]]))
-        .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$prior_params[[nm]]))
-      for (nm in skip) if (nm %in% names(.bnmf_ids)) .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$params[[nm]]))
-      row <- .Call("C_bnmf_init", self$handle)
-      private$pull_state(); private$bind_metrics(matrix(row, ncol = 1))
+      invisible(self$handle)
+    },
+    # load_bayesNMF_hip: a new handle on `device` with the stored spec, the saved device state replayed into it (bnmf_load_state:
+    # parameters, hyper-priors, the kept samples, the MAP metrics' history), the log reopened for append
+    reopen = function(output_dir, device) {
+      path <- file.path(output_dir, "engine_state.bin")
+      if (!file.exists(path)) stop(glue::glue("{path} does not exist: was the sampler run with save_engine_state = TRUE?"))
+      info <- .Call("C_bnmf_state_info", path)           # every checksum, before a device is touched
+      if (info$last_iter != self$state$iter) stop(glue::glue("{path} ends at iteration {info$last_iter}, sampler.rds at iteration {self$state$iter}"))
+      private$hip$device <- as.integer(device)
+      private$create_handle()
+      it <- .Call("C_bnmf_load_state", self$handle, path)
+      private$hip$state_iter <- as.integer(it)
+      self$specs$output_dir <- output_dir
+      self$log_con <- file(file.path(output_dir, "log.txt"), open = "at")
+      invisible(self)
     },
     cc_int = function() {
       cc <- self$specs$convergence_control
@@ -251,3 +288,13 @@ bayesNMF_sampler_hip <- R6::R6Class(
     }
   )
 )
+
+# readRDS of a bayesNMF_sampler_hip gives a sampler whose handle is a dead external pointer ("bnmf: handle was destroyed"): this
+# reopens it.  The sampler must have been run with save_engine_state = TRUE.  The result is live: get_MAP(end_iter, n_samples),
+# assign_signatures_ensemble, label_switching_df and run_gibbs_sampler() (resume, bit for bit as the uninterrupted chain) all reach
+# the device again.
+load_bayesNMF_hip <- function(output_dir, device = 0L) {
+  sampler <- readRDS(file.path(output_dir, "sampler.rds"))
+  sampler$.__enclos_env__$private$reopen(output_dir, device)
+  sampler
+}

@@ -268,6 +268,49 @@ SEXP C_bnmf_label_switching(SEXP ptr, SEXP iters, SEXP reference_P, SEXP dims) {
   UNPROTECT(4);
   return out;
 }
+/* a chain's state in a file and back (bnmf_save_state / bnmf_load_state / bnmf_state_info): path is a character string */
+static const char* path_arg(SEXP path) {
+  if (XLENGTH(path) != 1) Rf_error("bnmf: path must be one character string");
+  return CHAR(STRING_ELT(path, 0));
+}
+/* C_bnmf_save_state(ptr, path, since_iter): 0 = a full record (file created), S > 0 = a delta on a file that ends at iteration S;
+ * returns the bytes written (double) */
+SEXP C_bnmf_save_state(SEXP ptr, SEXP path, SEXP since_iter) {
+  size_t bytes = 0;
+  chk(bnmf_save_state(get_handle(ptr), path_arg(path), INTEGER(since_iter)[0], &bytes));
+  return Rf_ScalarReal((double)bytes);
+}
+/* C_bnmf_load_state(ptr, path): into a handle fresh from C_bnmf_create / C_bnmf_create_f64 (instead of C_bnmf_init); returns the
+ * iteration the handle is then at */
+SEXP C_bnmf_load_state(SEXP ptr, SEXP path) {
+  int it = 0;
+  chk(bnmf_load_state(get_handle(ptr), path_arg(path), &it));
+  return Rf_ScalarInteger(it);
+}
+/* C_bnmf_state_info(path) -> list(dims c(K,G,N), spec c(likelihood, prior, MH, learning_rank, rank_method, save_Z, window), seed,
+ * chain_id, format_version, first_iter, last_iter, n_records, bytes) — no handle, no device */
+SEXP C_bnmf_state_info(SEXP path) {
+  bnmf_state_desc d;
+  chk(bnmf_state_info(path_arg(path), &d));
+  static const char* nms[] = {"dims", "spec", "seed", "chain_id", "format_version", "first_iter", "last_iter", "n_records", "bytes"};
+  SEXP out = PROTECT(named_list(9, nms));
+  SEXP dims = Rf_allocVector(INTSXP, 3);
+  SET_VECTOR_ELT(out, 0, dims);
+  INTEGER(dims)[0] = d.K; INTEGER(dims)[1] = d.G; INTEGER(dims)[2] = d.N;
+  SEXP spec = Rf_allocVector(INTSXP, 7);
+  SET_VECTOR_ELT(out, 1, spec);
+  const int sv[7] = {d.likelihood, d.prior, d.MH, d.learning_rank, d.rank_method, d.save_Z, d.window};
+  for (int i = 0; i < 7; ++i) INTEGER(spec)[i] = sv[i];
+  SET_VECTOR_ELT(out, 2, Rf_ScalarReal((double)d.seed));
+  SET_VECTOR_ELT(out, 3, Rf_ScalarInteger((int)d.chain_id));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarInteger(d.format_version));
+  SET_VECTOR_ELT(out, 5, Rf_ScalarInteger(d.first_iter));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarInteger(d.last_iter));
+  SET_VECTOR_ELT(out, 7, Rf_ScalarInteger(d.n_records));
+  SET_VECTOR_ELT(out, 8, Rf_ScalarReal((double)d.bytes));
+  UNPROTECT(1);
+  return out;
+}
 SEXP C_bnmf_destroy(SEXP ptr) { handle_finalizer(ptr); return R_NilValue; }
 SEXP C_bnmf_device_info(SEXP device) {
   char buf[512];
@@ -285,6 +328,8 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_assign", (DL_FUNC)&C_bnmf_assign, 8}, {"C_bnmf_map_at", (DL_FUNC)&C_bnmf_map_at, 5},
   {"C_bnmf_assign_at", (DL_FUNC)&C_bnmf_assign_at, 9}, {"C_bnmf_label_switching", (DL_FUNC)&C_bnmf_label_switching, 4},
   {"C_bnmf_destroy", (DL_FUNC)&C_bnmf_destroy, 1}, {"C_bnmf_device_info", (DL_FUNC)&C_bnmf_device_info, 1},
+  {"C_bnmf_save_state", (DL_FUNC)&C_bnmf_save_state, 3}, {"C_bnmf_load_state", (DL_FUNC)&C_bnmf_load_state, 2},
+  {"C_bnmf_state_info", (DL_FUNC)&C_bnmf_state_info, 1},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
