@@ -55,6 +55,8 @@ def lib():
         dp, ip, up = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
         L.orc_create.restype = C.c_void_p
         L.orc_create.argtypes = [C.POINTER(OrcConfig), ip]
+        L.orc_create_f64.restype = C.c_void_p
+        L.orc_create_f64.argtypes = [C.POINTER(OrcConfig), dp]
         L.orc_destroy.argtypes = [C.c_void_p]
         L.orc_set_array.argtypes = [C.c_void_p, C.c_int, dp, C.c_long]
         L.orc_get_array.argtypes = [C.c_void_p, C.c_int, dp, C.c_long]
@@ -62,6 +64,7 @@ def lib():
         L.orc_run.argtypes = [C.c_void_p, C.c_int, C.c_int, dp]
         L.orc_get_iter.argtypes = [C.c_void_p]
         L.orc_set_M.argtypes = [C.c_void_p, ip]
+        L.orc_set_M_f64.argtypes = [C.c_void_p, dp]
         L.orc_set_fresh_mhat.argtypes = [C.c_void_p, C.c_int]
         L.orc_t_step.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int]
         L.orc_last_error.restype = C.c_char_p
@@ -153,12 +156,33 @@ def alpha_h(x, c, tau):
     return h.value, hp.value
 
 
+def _data(M, likelihood):
+    """The data as the oracle takes them: integer arrays as int32 counts (orc_create); real arrays as float64 — the Normal
+    likelihood keeps any finite value, the Poisson likelihood takes whole numbers in [0, 2^31 - 1] only (bnmf_create_f64's rule), which
+    orc_create_f64 converts to counts."""
+    M = np.asarray(M)
+    if M.dtype.kind in "biu":
+        return np.asfortranarray(M, dtype=np.int32)
+    M = np.asfortranarray(M, dtype=np.float64)
+    if likelihood == "normal":
+        if not np.isfinite(M).all():
+            k, g = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"M[{k}, {g}] = {M[k, g]} is not finite")
+    else:
+        bad = ~((M >= 0) & (M <= 2147483647.0) & (M == np.floor(M)))
+        if bad.any():
+            k, g = np.argwhere(bad)[0]
+            raise ValueError(f"non-integer count M[{k}, {g}] = {M[k, g]} (likelihood = poisson takes whole numbers in [0, 2^31 - 1])")
+    return M
+
+
 class Oracle:
     """One chain on the CPU oracle.  Mirrors bayesnmf_amd.engine.Engine's method names."""
 
     def __init__(self, M, N, likelihood="poisson", prior="gamma", MH=False, learning_rank=False,
                  rank_method="SBFI", seed=1, chain_id=0, temperature=None, save_Z=False, nthreads=1):
-        M = np.asfortranarray(M, dtype=np.int32)
+        self._lik = likelihood
+        M = _data(M, likelihood)
         self.K, self.G = M.shape
         self.N = int(N)
         self._temp = None if temperature is None else np.ascontiguousarray(temperature, dtype=np.float64)
@@ -167,8 +191,13 @@ class Oracle:
                         int(seed), int(chain_id), 0,
                         _dp(self._temp) if self._temp is not None else None,
                         0 if self._temp is None else self._temp.size)
-        self._h = lib().orc_create(C.byref(cfg), M.ctypes.data_as(C.POINTER(C.c_int32)))
-        self.M = M
+        if M.dtype == np.float64:
+            self._h = lib().orc_create_f64(C.byref(cfg), _dp(M))
+        else:
+            self._h = lib().orc_create(C.byref(cfg), M.ctypes.data_as(C.POINTER(C.c_int32)))
+        if not self._h:
+            raise RuntimeError("orc_create failed")
+        self.M = M if self._lik == "normal" else np.asfortranarray(M, dtype=np.int32)
 
     def close(self):
         if self._h:
@@ -241,10 +270,16 @@ class Oracle:
         lib().orc_set_fresh_mhat(self._h, int(bool(on)))
 
     def set_M(self, M):
-        M = np.asfortranarray(M, dtype=np.int32)
+        """Swap the data, with the rules of the constructor."""
+        M = _data(M, self._lik)
         assert M.shape == (self.K, self.G)
-        lib().orc_set_M(self._h, M.ctypes.data_as(C.POINTER(C.c_int32)))
-        self.M = M
+        if M.dtype == np.float64:
+            rc = lib().orc_set_M_f64(self._h, _dp(M))
+        else:
+            rc = lib().orc_set_M(self._h, M.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != 0:
+            raise ValueError(f"orc_set_M failed rc={rc}")
+        self.M = M if self._lik == "normal" else np.asfortranarray(M, dtype=np.int32)
 
     @property
     def iter(self):

@@ -21,6 +21,8 @@
  *   bayesNMF_sampler.R:232-257 (constructor order), :273-285 (loop body)
  * All matrices are column-major exactly like R: M[k+K*g], P[k+K*n], E[n+N*g],
  * Z[k+K*(n+N*g)].
+ * Data: the Poisson likelihood reads int32 counts (M); the Normal likelihood reads the data as doubles (Mf), any real value, whichever
+ * entry point (orc_create with int32, orc_create_f64) brought them in.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -66,7 +68,8 @@ typedef struct orc_handle {
   orc_config cfg;
   int iter, converged, R;
   int fresh_mhat;   /* checker of the checker (orc_set_fresh_mhat): recompute P diag(A) E from scratch wherever the stream spec maintains it */
-  int32_t* M;
+  int32_t* M;       /* Poisson: the counts (NULL for Normal) */
+  double* Mf;       /* Normal: the data, any real value (NULL for Poisson) */
   int32_t *Z, *ZsumK, *ZsumG;
   arr_t a[ID_MAX];
   double* temperature;
@@ -95,12 +98,27 @@ static int is_hyper(int id) { return (id >= 30 && id < 50) || id == ID_ALPHA_S |
 #define AR(id) (o->a[id].p)
 #define HY(id, e) (o->a[id].p[(e) * o->a[id].stride])
 
-orc_handle* orc_create(const orc_config* cfg, const int32_t* M) {
+/* whole numbers in [0, 2^31 - 1] (the rule of bnmf_create_f64 for Poisson data) */
+static int whole_counts(const double* M, long n) {
+  for (long i = 0; i < n; ++i)
+    if (!(M[i] >= 0.0 && M[i] <= 2147483647.0 && M[i] == floor(M[i]))) return 0;
+  return 1;
+}
+static void store_M(orc_handle* o, const int32_t* M, const double* Mf) {   /* exactly one of M, Mf */
+  const long KG = (long)o->cfg.K * o->cfg.G;
+  if (o->cfg.likelihood == LIK_NORMAL) {
+    if (!o->Mf) o->Mf = (double*)malloc(sizeof(double) * KG);
+    for (long i = 0; i < KG; ++i) o->Mf[i] = M ? (double)M[i] : Mf[i];
+  } else {
+    if (!o->M) o->M = (int32_t*)malloc(sizeof(int32_t) * KG);
+    for (long i = 0; i < KG; ++i) o->M[i] = M ? M[i] : (int32_t)Mf[i];
+  }
+}
+static orc_handle* create(const orc_config* cfg, const int32_t* M, const double* Mf) {
   orc_handle* o = (orc_handle*)calloc(1, sizeof(orc_handle));
   o->cfg = *cfg;
   long K = cfg->K, G = cfg->G, N = cfg->N;
-  o->M = (int32_t*)malloc(sizeof(int32_t) * K * G);
-  memcpy(o->M, M, sizeof(int32_t) * K * G);
+  store_M(o, M, Mf);
   o->ZsumK = (int32_t*)calloc(N * G, sizeof(int32_t));
   o->ZsumG = (int32_t*)calloc(K * N, sizeof(int32_t));
   o->Z = cfg->save_Z ? (int32_t*)calloc(K * N * G, sizeof(int32_t)) : NULL;
@@ -113,10 +131,16 @@ orc_handle* orc_create(const orc_config* cfg, const int32_t* M) {
   o->iter = 0; o->converged = 0; o->R = (int)N;
   return o;
 }
+orc_handle* orc_create(const orc_config* cfg, const int32_t* M) { return create(cfg, M, NULL); }
+/* real-valued data: Normal keeps them as doubles; Poisson takes whole numbers only (NULL otherwise) and continues as orc_create */
+orc_handle* orc_create_f64(const orc_config* cfg, const double* M) {
+  if (cfg->likelihood != LIK_NORMAL && !whole_counts(M, (long)cfg->K * cfg->G)) return NULL;
+  return create(cfg, NULL, M);
+}
 void orc_destroy(orc_handle* o) {
   if (!o) return;
   for (int i = 0; i < ID_MAX; ++i) free(o->a[i].p);
-  free(o->M); free(o->Z); free(o->ZsumK); free(o->ZsumG); free(o->temperature);
+  free(o->M); free(o->Mf); free(o->Z); free(o->ZsumK); free(o->ZsumG); free(o->temperature);
   free(o->colsse); free(o->colll); free(o->colkl); free(o->lpE); free(o->lpP); free(o->Mhat);
   free(o);
 }
@@ -336,6 +360,16 @@ static void cell_terms(const orc_handle* o, int32_t m, double mhat, double* sse,
   *ll = ((double)m * lmh - mh) - orc_lgamma((double)m + 1.0);   /* dpois(M, Mhat, log=TRUE) */
   *kl = mt * (orc_log(mt) - lmh);
 }
+/* RMSE and padded-KL terms of a cell of real data (R/utils.R:412-471): pmax(Mhat, 1e-6), pmax(M, 1e-6) (padded_KL_ :467-470).  No
+ * dpois term: the Normal log-likelihood is dnorm.  On whole numbers these are the bits of cell_terms. */
+static void cell_terms_real(double m, double mhat, double* sse, double* kl) {
+  double d = mhat - m;
+  *sse = d * d;
+  double mh = mhat < 1e-6 ? 1e-6 : mhat;
+  double lmh = orc_log(mh);
+  double mt = m < 1e-6 ? 1e-6 : m;
+  *kl = mt * (orc_log(mt) - lmh);
+}
 static void sample_Z_and_metrics(orc_handle* o, uint32_t t) {
   const long K = o->cfg.K, G = o->cfg.G, N = o->cfg.N;
   memset(o->ZsumG, 0, sizeof(int32_t) * K * N);
@@ -425,9 +459,10 @@ static double pois_ll_cell(int32_t m, double mhat) {
  * evaluated, alt = Mhat -/+ P[k,n] E[n,g] (A[n] = 1 / 0 now), the log-likelihood of the current state being the one
  * carried from the previous decision.  Sums: per column 64-strided over k + tree; the column sums are added in blocks
  * of 8 consecutive columns (sequentially, ascending); W = 1024 over the blocks. */
-static double ll_cell_rank(const orc_handle* o, int32_t m, double mhat, long g) {
-  if (o->cfg.likelihood == LIK_NORMAL) return dnorm_log_fwd((double)m, mhat, o->a[ID_SIGMASQ].p[g]);
-  return pois_ll_cell(m, mhat);
+static double ll_cell_rank(const orc_handle* o, long k, double mhat, long g) {
+  const long i = k + (long)o->cfg.K * g;
+  if (o->cfg.likelihood == LIK_NORMAL) return dnorm_log_fwd(o->Mf[i], mhat, o->a[ID_SIGMASQ].p[g]);
+  return pois_ll_cell(o->M[i], mhat);
 }
 static double hsum_cols(const double* col, long G) {
   long nb = (G + 7) / 8;
@@ -454,7 +489,7 @@ static void sample_A(orc_handle* o, uint32_t t, int from_prior) {
       double c = 0.0;
       for (long j = 0; j < N; ++j) c = c + (AR(ID_P)[k + K * j] * AR(ID_A)[j]) * AR(ID_E)[j + N * g];
       mh[k + K * g] = c;
-      l[k] = ll_cell_rank(o, o->M[k + K * g], c, g);
+      l[k] = ll_cell_rank(o, k, c, g);
     }
     col[g] = orc_canon_sum(l, K, 1, 64);
   }
@@ -468,7 +503,7 @@ static void sample_A(orc_handle* o, uint32_t t, int from_prior) {
       for (long k = 0; k < K; ++k) {
         double tt = AR(ID_P)[k + K * n] * en;
         double alt = (a_old == 1.0) ? mh[k + K * g] - tt : mh[k + K * g] + tt;
-        l[k] = ll_cell_rank(o, o->M[k + K * g], alt, g);
+        l[k] = ll_cell_rank(o, k, alt, g);
       }
       col[g] = orc_canon_sum(l, K, 1, 64);
     }
@@ -482,7 +517,7 @@ static void sample_A(orc_handle* o, uint32_t t, int from_prior) {
           for (long k = 0; k < K; ++k) {
             double c = 0.0;
             for (long j = 0; j < N; ++j) c = c + (AR(ID_P)[k + K * j] * (j == n ? (double)state : AR(ID_A)[j])) * AR(ID_E)[j + N * g];
-            l[k] = ll_cell_rank(o, o->M[k + K * g], c, g);
+            l[k] = ll_cell_rank(o, k, c, g);
           }
           col[g] = orc_canon_sum(l, K, 1, 64);
         }
@@ -625,7 +660,8 @@ static void sample_P_seq(orc_handle* o, uint32_t t) {
           double mno = fresh ? mhat_cell(o, k, g, n, NULL, 0) : row[g] - pa * en;  /* Mhat_no_n */
           double V = normal ? AR(ID_SIGMASQ)[g] : row[g];                          /* sigmasq_kg :137-147 */
           double rV = 1.0 / V;                                                     /* one reciprocal serves both sums (stream spec) */
-          x1[g] = en * (((double)o->M[k + K * g] - mno) * rV);                     /* :155-161 */
+          const double m = normal ? o->Mf[k + K * g] : (double)o->M[k + K * g];
+          x1[g] = en * ((m - mno) * rV);                                           /* :155-161 */
           x2[g] = (a_n * (en * en)) * rV;                                          /* :163-169 */
         }
         num1 = canon_rowsum(x1, G); den = canon_rowsum(x2, G);
@@ -691,7 +727,8 @@ static void sample_E_seq(orc_handle* o, uint32_t t) {
           double mno = fresh ? mhat_cell(o, k, g, n, NULL, 0) : mhc[k] - (pn * a_n) * eold;
           double V = normal ? sg : mhc[k];
           double rV = 1.0 / V;
-          x1[k] = pn * (((double)o->M[k + K * g] - mno) * rV);
+          const double m = normal ? o->Mf[k + K * g] : (double)o->M[k + K * g];
+          x1[k] = pn * ((m - mno) * rV);
           x2[k] = (a_n * (pn * pn)) * rV;
         }
         num1 = orc_canon_sum(x1, K, 1, 64); den = orc_canon_sum(x2, K, 1, 64);
@@ -748,7 +785,7 @@ static void sample_sigmasq(orc_handle* o, uint32_t t) {
 #pragma omp parallel for schedule(static) num_threads(o->cfg.nthreads)
   for (long g = 0; g < G; ++g) {
     double r2[K];
-    for (long k = 0; k < K; ++k) { double r = (double)o->M[k + K * g] - mhat_cell(o, k, g, -1, NULL, 0); r2[k] = r * r; }
+    for (long k = 0; k < K; ++k) { double r = o->Mf[k + K * g] - mhat_cell(o, k, g, -1, NULL, 0); r2[k] = r * r; }
     double ss = orc_canon_sum(r2, K, 1, 64);
     orc_stream s = ST(o, V_SIGMASQ, (uint32_t)g, t);
     AR(ID_SIGMASQ)[g] = orc_rinvgamma(&s, HY(ID_ALPHA_S, g) + (double)K / 2.0, HY(ID_BETA_S, g) + 0.5 * ss);
@@ -762,9 +799,9 @@ static void metrics_cells_normal(orc_handle* o) {
     double a[K], b[K], c[K];
     double sg = AR(ID_SIGMASQ)[g];
     for (long k = 0; k < K; ++k) {
-      double mh = mhat_cell(o, k, g, -1, NULL, 0), dummy;
-      cell_terms(o, o->M[k + K * g], mh, &a[k], &dummy, &c[k]);
-      b[k] = dnorm_log_fwd((double)o->M[k + K * g], mh, sg);
+      double mh = mhat_cell(o, k, g, -1, NULL, 0), m = o->Mf[k + K * g];
+      cell_terms_real(m, mh, &a[k], &c[k]);
+      b[k] = dnorm_log_fwd(m, mh, sg);
     }
     o->colsse[g] = orc_canon_sum(a, K, 1, 64);
     o->colll[g] = orc_canon_sum(b, K, 1, 64);
@@ -931,8 +968,10 @@ const char* orc_last_error(orc_handle* o) { return o->err; }
  * oracle does what R does — every Mhat, Mhat without factor n and Mhat with the proposed value from scratch, in factor order —
  * so that tests/test_oracle.py can tie the maintained form to the R semantics without the GPU (agreement to rounding). */
 int orc_set_fresh_mhat(orc_handle* o, int on) { o->fresh_mhat = on; return 0; }
-int orc_set_M(orc_handle* o, const int32_t* M) {
-  memcpy(o->M, M, sizeof(int32_t) * (size_t)o->cfg.K * o->cfg.G);
+int orc_set_M(orc_handle* o, const int32_t* M) { store_M(o, M, NULL); return 0; }
+int orc_set_M_f64(orc_handle* o, const double* M) {   /* the rules of orc_create_f64; -1: Poisson data that are not whole numbers */
+  if (o->cfg.likelihood != LIK_NORMAL && !whole_counts(M, (long)o->cfg.K * o->cfg.G)) return -1;
+  store_M(o, NULL, M);
   return 0;
 }
 enum { STEP_HYPER = 0, STEP_P = 1, STEP_E = 2, STEP_R = 3, STEP_A = 4, STEP_Z = 5, STEP_SIGMASQ = 6 };

@@ -32,7 +32,42 @@ def chain(prior, learning_rank, K, G, N, R_true, data_seed, seed, iters, temp=No
     return out
 
 
+def real_data(K, G, R_true, data_seed):
+    """P E + N(0, 0.5^2): fractional everywhere, some cells negative, and the first cells at the edges of the padded KL
+    (exact 0 and -0, below and at 1e-6, just below 1) and of a cast to integer (-0.5)."""
+    rng = np.random.default_rng(data_seed)
+    P = rng.dirichlet(0.5 * np.ones(K), size=R_true).T
+    E = rng.gamma(4.0, 2.0, size=(R_true, G))
+    M = np.asfortranarray(P @ E + rng.normal(0.0, 0.5, size=(K, G)))
+    M[:6, 0] = [0.0, -0.0, 5e-7, 1e-6, np.nextafter(1.0, 0.0), -0.5]
+    return M
+
+
+def normal_chain(prior, learning_rank, K, G, N, R_true, data_seed, seed, iters, temp=None):
+    """A Normal-likelihood chain on real-valued data (the oracle keeps them as float64)."""
+    M = real_data(K, G, R_true, data_seed)
+    o = O.Oracle(M, N, likelihood="normal", prior=prior, learning_rank=learning_rank, seed=seed, temperature=temp, nthreads=4)
+    apply_hyperprior_params(o, prior, M, N)
+    rows = [o.init()]
+    rows += list(o.run(iters))
+    names = ["P", "E", "A", "R", "sigmasq"] + (["Mu_p", "Sigmasq_p", "Mu_e", "Sigmasq_e"] if prior == "truncnormal" else ["Lambda_p", "Lambda_e"])
+    out = {nm: o.get(nm) for nm in names}
+    out["metrics"] = np.array(rows)
+    out["M"] = M
+    if temp is not None:
+        out["temperature"] = temp
+    return out
+
+
+NORMAL_TEMP = np.concatenate([np.zeros(3), 10.0 ** np.linspace(-4, 0, 12), np.ones(30)])
+
+
+def normal_golden():
+    return normal_chain("truncnormal", True, 12, 10, 3, 2, 13, 5, 40, temp=NORMAL_TEMP)
+
+
 if __name__ == "__main__":
+    np.savez_compressed(os.path.join(HERE, "nt_sbfi_real_k12_g10_n3.npz"), **normal_golden())
     np.savez_compressed(os.path.join(HERE, "pg_k8_g6_n3.npz"), **chain("gamma", False, 8, 6, 3, 2, 11, 7, 50))
     np.savez_compressed(os.path.join(HERE, "pe_k8_g6_n3.npz"), **chain("exponential", False, 8, 6, 3, 2, 11, 7, 50))
     temp = np.concatenate([np.zeros(3), 10.0 ** np.linspace(-6, 0, 20), np.ones(40)])

@@ -1,7 +1,12 @@
 """Real-valued data for the Normal likelihood on the device (bnmf_create_f64).
 
 * integer data give the same chain, bit for bit, through bnmf_create_f64 (fp64) and bnmf_create (int32), in every form of the
-  Normal kernels — and both equal the CPU oracle, which reads the data as the int32 kernels did;
+  Normal kernels — and both equal the CPU oracle;
+* on real data — fractional and negative cells, values that truncation and floor map differently, signed zeros, cells in (0, 1e-6),
+  at 1e-6 and just below 1, an all-negative row and column, a cell of 1e6 — every form of the Normal kernels, and the edge shapes
+  (K = 97, K = 130, G = 1, N = 1, rank learning whose inclusion draws flip), equal the oracle bit for bit, which reads the same fp64
+  data: the init row, every metric row, the state after calls of uneven length and every sample of the recorded window; so do the
+  committed real-data golden chain and a run with every side-stream kernel held back;
 * on real data with fractional parts and negative cells the metric rows are the reference's metrics of the recorded samples;
 * the full conditionals of P and sigmasq are the reference's laws of the REAL data (a floored copy of the data is detected);
 * bayesNMF() on P E + noise of small magnitude recovers the signatures."""
@@ -124,6 +129,135 @@ def test_poisson_integer_float64_data_same_as_bnmf_create():
             _same(a.get(nm), b.get(nm), nm)
         assert np.array_equal(a.get("ZsumK"), b.get("ZsumK"))
     a.close(); b.close()
+
+
+# ---------------------------------------------------------------------------------------------- real data: parity with the oracle
+EDGE = [-0.5, 0.7, 0.0, -0.0, 5e-7, 1e-6, np.nextafter(1.0, 0.0), 0.999999]   # trunc / floor differ; signed zeros; the KL's pmax edge
+RANK_TEMP = np.concatenate([np.zeros(3), 10.0 ** np.linspace(-4, 0, 9), np.ones(10)])   # cold start: the inclusion draws flip
+
+
+def _edge_real(K, G, seed, big=False):
+    """P E + N(0, 0.5^2) with magnitudes around 1, fractional everywhere, some cells negative, plus the EDGE values (down column 0,
+    wrapping to the next columns), an all-negative last column and last row (where the shape leaves others), and with big one cell
+    of magnitude 1e6"""
+    rng = np.random.default_rng(seed)
+    M = rng.gamma(4.0, 0.06, size=(K, 3)) @ rng.gamma(4.0, 0.3, size=(3, G)) + rng.normal(0.0, 0.5, size=(K, G))
+    M = np.asfortranarray(M)
+    for i, v in enumerate(EDGE[:K * G]):
+        M[i % K, i // K] = v
+    if G >= 3:
+        M[:, G - 1] = -np.abs(M[:, G - 1]) - 0.01
+    if K >= 3:
+        M[K - 1, :] = -np.abs(M[K - 1, :]) - 0.01
+    if big:
+        M[K // 2, G // 2] = 1.234567e6
+    if M.mean() <= 0:                                     # the default hyper-priors take sqrt(mean(M))
+        M[K // 2, 0] += 1.0 - M.sum()
+    return M
+
+
+def _parity_real(M, N, prior, learning_rank=False, rank_method="SBFI", temperature=None, seed=3, calls=(1, 4, 7), W=7):
+    """Engine (bnmf_create_f64) against the oracle (orc_create_f64) on real data, bit for bit: the init row, every metric row, P, E, A, R,
+    sigmasq and the prior-parameter arrays after each call, and every sample of the recorded window against the oracle's state at that
+    iteration.  Returns the metric rows."""
+    import oracle as O
+    from bayesnmf_amd import Engine
+    from bayesnmf_amd.setup import apply_hyperprior_params
+    kw = dict(likelihood="normal", prior=prior, learning_rank=learning_rank, rank_method=rank_method, temperature=temperature, seed=seed)
+    o = O.Oracle(M, N, nthreads=8, **kw)
+    e = Engine(M, N, window=W, **kw)
+    assert o.M.dtype == np.float64 and e.M.dtype == np.float64
+    for c in (o, e):
+        apply_hyperprior_params(c, prior, M, N)
+    ro, re_ = o.init(), e.init()
+    _same(re_[:9], ro[:9], "init row")
+    names = ["P", "E", "A", "R", "sigmasq", "Alpha", "Beta"] + PRIOR_IDS[prior]
+    hist, rows = [], [ro]
+    for c, n in enumerate(calls):
+        me = e.run(n)
+        mo = []
+        for _ in range(n):
+            mo.append(o.run(1)[0])
+            hist.append({nm: o.get(nm).copy() for nm in names})
+        mo = np.array(mo)
+        rows += list(mo)
+        for i in range(n):
+            _same(me[i, :9], mo[i, :9], f"metric row {i} of call {c} (iteration {o.iter - n + i + 1})")
+        for nm in names:
+            _same(e.get(nm), o.get(nm), f"{nm} after call {c}")
+    for nm in ("P", "E", "A", "R", "sigmasq") + tuple(PRIOR_IDS[prior]):
+        win = e.window(nm, W)
+        for j in range(W):
+            _same(win[j], hist[len(hist) - W + j][nm], f"window {nm}, sample {j}")
+    o.close(); e.close()
+    return np.array(rows)
+
+
+@pytest.mark.parametrize("form", FORMS, ids=[f[0] for f in FORMS])
+def test_real_data_parity_with_the_oracle_in_every_form(form, monkeypatch):
+    """Every form a Normal handle can take, on real data with the EDGE cells and an all-negative row and column, against the oracle that
+    reads the same fp64 data.  The rank forms run with a cold start, so that the inclusion draws flip."""
+    name, K, G, N, prior, lr, env = form
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    M = _edge_real(K, G, 1000 + K + G)
+    rows = _parity_real(M, N, prior, learning_rank=lr, temperature=RANK_TEMP if lr else None, seed=7)
+    if lr:
+        assert len(np.unique(rows[:, 7])) >= 2, "the rank never moved: the rank sweep's decisions are untested"
+
+
+EDGE_SHAPES = [
+    ("K97", 97, 60, 3, "exponential", False, False),                  # wave tails of the column kernels
+    ("K97-rank", 97, 60, 4, "truncnormal", True, False),
+    ("K130", 130, 40, 3, "truncnormal", False, False),                # above MHE16_KMAX: k_mh_ecol
+    ("K130-rank", 130, 40, 3, "exponential", True, False),
+    ("G1", 12, 1, 3, "truncnormal", False, False),
+    ("N1", 40, 30, 1, "exponential", False, False),
+    ("cell-1e6", 64, 80, 3, "exponential", False, True),
+    ("BFI", 40, 50, 4, "exponential", True, False),
+]
+
+
+@pytest.mark.parametrize("case", EDGE_SHAPES, ids=[c[0] for c in EDGE_SHAPES])
+def test_real_data_parity_at_edge_shapes(case):
+    name, K, G, N, prior, lr, big = case
+    M = _edge_real(K, G, 2000 + K + G, big=big)
+    rows = _parity_real(M, N, prior, learning_rank=lr, rank_method="BFI" if name == "BFI" else "SBFI",
+                        temperature=RANK_TEMP if lr else None, seed=11)
+    if lr:
+        assert len(np.unique(rows[:, 7])) >= 2, "the rank never moved"
+
+
+def test_real_data_with_every_side_stream_kernel_held_back(monkeypatch):
+    """test_gpu_parity.py's test_every_side_stream_kernel_held_back on real data: a 400 us delay in front of every side-stream kernel."""
+    monkeypatch.setenv("BNMF_DEBUG_ALLSIDE_DELAY_US", "400")
+    _parity_real(_edge_real(60, 400, 991), 4, "truncnormal", calls=(7, 6), W=6)
+
+
+def test_randomised_parity_sweep_with_real_data():
+    """tools/fuzz_parity.py with FUZZ_REAL=1: the 60 cases of test_gpu_configs.py's sweep, half of the Normal ones on real-valued data
+    (fractional and negative cells, large ones among them), engine against the oracle, bit-exact."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, FUZZ_N="60", FUZZ_SEED="77", FUZZ_REAL="1")
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_parity.py")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_engine_matches_golden_chain_of_real_data():
+    """The HIP engine against the committed real-data golden chain (tests/golden/make_golden.py normal_golden)."""
+    import os
+    from bayesnmf_amd import Engine
+    from bayesnmf_amd.setup import apply_hyperprior_params
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nt_sbfi_real_k12_g10_n3.npz"))
+    M, N = g["M"], g["P"].shape[1]
+    e = Engine(M, N, likelihood="normal", prior="truncnormal", learning_rank=True, seed=5, temperature=g["temperature"])
+    apply_hyperprior_params(e, "truncnormal", M, N)
+    rows = [e.init()] + list(e.run(g["metrics"].shape[0] - 1))
+    _same(np.array(rows)[:, :9], g["metrics"][:, :9], "metric rows")
+    for nm in ("P", "E", "A", "R", "sigmasq") + tuple(PRIOR_IDS["truncnormal"]):
+        _same(e.get(nm), g[nm], nm)
+    e.close()
 
 
 # ---------------------------------------------------------------------------------------------- real data: metrics

@@ -37,7 +37,7 @@ def test_oracle_suites_under_sanitizers():
 
 
 def test_golden_chains_regenerate_identically_under_sanitizers(tmp_path):
-    """tests/golden/make_golden.py's three chains (fixed rank gamma / exponential, learned rank with tempering) and shapes that
+    """tests/golden/make_golden.py's four chains (fixed rank gamma / exponential, learned rank with tempering, Normal on real data) and shapes that
     exercise every model family once — MH, Normal likelihood, N above 64, K above 64 — on the sanitizer build: no finding, and the
     regenerated golden arrays equal the committed ones bit for bit."""
     env = _asan_env()
@@ -52,6 +52,7 @@ assert O.lib()._name.endswith("liboracle_asan.so"), O.lib()._name
 out = {"pg": mk.chain("gamma", False, 8, 6, 3, 2, 11, 7, 50), "pe": mk.chain("exponential", False, 8, 6, 3, 2, 11, 7, 50)}
 temp = np.concatenate([np.zeros(3), 10.0 ** np.linspace(-6, 0, 20), np.ones(40)])
 out["sbfi"] = mk.chain("gamma", True, 12, 10, 4, 2, 12, 9, 40, temp=temp)
+out["nreal"] = mk.normal_golden()                  # the Normal likelihood on real data: negative, fractional and edge cells
 for k, d in out.items():
     np.savez(os.path.join(%r, k + ".npz"), **d)
 from bayesnmf_amd.setup import synth_counts, apply_hyperprior_params
@@ -69,7 +70,7 @@ print("ok")
     assert r.returncode == 0 and "ok" in r.stdout, tail
     assert "ERROR: AddressSanitizer" not in tail and "runtime error:" not in tail, tail
     gold = os.path.join(ROOT, "tests", "golden")
-    for mine, ref in (("pg", "pg_k8_g6_n3"), ("pe", "pe_k8_g6_n3"), ("sbfi", "pg_sbfi_k12_g10_n4")):
+    for mine, ref in (("pg", "pg_k8_g6_n3"), ("pe", "pe_k8_g6_n3"), ("sbfi", "pg_sbfi_k12_g10_n4"), ("nreal", "nt_sbfi_real_k12_g10_n3")):
         a, b = np.load(os.path.join(str(tmp_path), mine + ".npz")), np.load(os.path.join(gold, ref + ".npz"))
         for nm in a.files:
             x, y = np.ascontiguousarray(a[nm], dtype=np.float64), np.ascontiguousarray(b[nm], dtype=np.float64)

@@ -365,3 +365,100 @@ def test_geweke_joint_distribution(oracle_lib, prior):
         se = np.hypot(_batch_se(sc[:, j]), mc[:, j].std(ddof=1) / np.sqrt(len(mc)))
         z = (sc[:, j].mean() - mc[:, j].mean()) / se
         assert abs(z) < 4.5, (prior, j, sc[:, j].mean(), mc[:, j].mean(), z)
+
+
+# ---------------------------------------------------------------------------------------------- Normal likelihood, real data
+def _real_law_setup(seed):
+    """Real data with negative and fractional cells, and a state to condition on (K = 12, G = 10, N = 3)."""
+    rng = np.random.default_rng(seed)
+    K, G, N = 12, 10, 3
+    M = np.asfortranarray(rng.gamma(4.0, 0.04, size=(K, N)) @ rng.gamma(4.0, 0.5, size=(N, G)) + rng.normal(0.0, 0.5, size=(K, G)))
+    assert (M < 0).sum() >= 5 and (M != np.trunc(M)).all()
+    P0 = rng.gamma(4.0, 0.04, size=(K, N))
+    E0 = rng.gamma(4.0, 0.5, size=(N, G))
+    sg0 = rng.uniform(0.1, 0.3, size=G)
+    return M, P0, E0, sg0
+
+
+def _real_law_oracle(O, M_oracle, M, P0, E0, sg0, prior, seed):
+    """An oracle holding M_oracle, with the hyper-priors and the state that the laws computed with M assume"""
+    N = P0.shape[1]
+    o = O.Oracle(M_oracle, N, likelihood="normal", prior=prior, seed=seed)
+    _hyper(o, prior, M, N)
+    o.set("P", P0); o.set("E", E0); o.set("sigmasq", sg0)
+    o.init()
+    return o
+
+
+def _tn_pit(x, num1, den, prior, o, side):
+    """PIT of draws x under the truncated-normal full conditional of sample_Pn_normal / sample_En_normal (R/sample_Pn.R:131-187,
+    R/sample_En.R): mean (num1 - lambda) / den, var 1 / den (exponential prior); mean (num1 + mu / s2) / (den + 1 / s2),
+    var 1 / (den + 1 / s2) (truncated-normal prior); truncated at 0."""
+    from scipy.special import ndtr
+    if prior == "exponential":
+        la = o.get("Lambda_" + side)
+        la = la[:, 0] if side == "p" else la[0, :]
+        mu, var = (num1 - la) / den, 1.0 / den
+    else:
+        mp, s2 = o.get("Mu_" + side), o.get("Sigmasq_" + side)
+        mp, s2 = (mp[:, 0], s2[:, 0]) if side == "p" else (mp[0, :], s2[0, :])
+        den2 = den + 1.0 / s2
+        mu, var = (num1 + mp / s2) / den2, 1.0 / den2
+    sd = np.sqrt(var)
+    lo = ndtr(-mu / sd)
+    return (ndtr((x - mu) / sd) - lo) / (1.0 - lo)
+
+
+@pytest.mark.parametrize("prior", ["exponential", "truncnormal"])
+def test_normal_P_and_E_full_conditionals_of_real_data(oracle_lib, prior):
+    """P[:, 0] and E[:, 0] — the first factor each sweep draws, so that their conditionals involve only the state that was set — against
+    their truncated-normal full conditionals computed with the REAL data: sum_g E[0,g] (M - Mhat without factor 0) / sigmasq_g and
+    sum_g E[0,g]^2 / sigmasq_g (P side, R/sample_Pn.R:131-181), the sums over k for the E side.  Negative control: the oracle holds the
+    data truncated toward zero (what an integer cast would read), the laws are those of M."""
+    M, P0, E0, sg0 = _real_law_setup(41)
+    K, G = M.shape
+    MnoP = M - P0[:, 1:] @ E0[1:, :]
+    num_p = (MnoP * E0[0][None, :] / sg0[None, :]).sum(1)
+    den_p = np.full(K, (E0[0] ** 2 / sg0).sum())
+    num_e = (P0[:, :1] * MnoP).sum(0) / sg0
+    den_e = (P0[:, 0] ** 2).sum() / sg0
+
+    def pits(M_oracle):
+        o = _real_law_oracle(oracle_lib, M_oracle, M, P0, E0, sg0, prior, 19)
+        up, ue = [], []
+        for t in range(2, 1502):
+            o.set("P", P0); o.set("E", E0)
+            o.step("P", t)
+            up.append(_tn_pit(o.get("P")[:, 0], num_p, den_p, prior, o, "p"))
+            o.set("P", P0)
+            o.step("E", t)
+            ue.append(_tn_pit(o.get("E")[0, :], num_e, den_e, prior, o, "e"))
+        o.close()
+        return np.concatenate(up), np.concatenate(ue)
+
+    up, ue = pits(M)
+    assert st.kstest(up, "uniform").pvalue > 1e-3, "P[:, 0] under its full conditional"
+    assert st.kstest(ue, "uniform").pvalue > 1e-3, "E[:, 0] under its full conditional"
+    cp, ce = pits(np.asfortranarray(np.trunc(M)))
+    assert st.kstest(cp, "uniform").pvalue < 1e-6
+    assert st.kstest(ce, "uniform").pvalue < 1e-6
+
+
+def test_sigmasq_invgamma_law_of_real_data(oracle_lib):
+    """sample_sigmasq (R/sample_params.R:275-286) on real data: sigmasq_g ~ InvGamma(Alpha + K/2, Beta + ss_g / 2) with ss_g the residual
+    sum of squares of the REAL data; the data truncated toward zero in the oracle fail it."""
+    M, P0, E0, sg0 = _real_law_setup(43)
+    K = M.shape[0]
+    ss = ((M - P0 @ E0) ** 2).sum(0)
+
+    def pits(M_oracle):
+        o = _real_law_oracle(oracle_lib, M_oracle, M, P0, E0, sg0, "exponential", 12)
+        us = []
+        for t in range(2, 1502):
+            o.step("sigmasq", t)
+            us.append(st.gamma.sf((3.0 + ss / 2.0) / o.get("sigmasq"), 3.0 + K / 2.0))      # P(X <= x), X ~ InvGamma(a, b): Q(a, b / x)
+        o.close()
+        return np.concatenate(us)
+
+    assert st.kstest(pits(M), "uniform").pvalue > 1e-3
+    assert st.kstest(pits(np.asfortranarray(np.trunc(M))), "uniform").pvalue < 1e-6

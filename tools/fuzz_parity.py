@@ -14,6 +14,10 @@ def same_bits(a, b):
     return np.array_equal(a_.view(np.uint64), b_.view(np.uint64))
 rng = np.random.default_rng(int(os.environ.get("FUZZ_SEED", "1")))
 rng_big = np.random.default_rng(7919 + int(os.environ.get("FUZZ_SEED", "1")))    # (its own stream: the cases of a seed stay what they were)
+# FUZZ_REAL=1: half the Normal cases take real-valued data instead (fractional and negative cells; the oracle takes float64), drawn
+# from a stream of their own; unset, every case of a seed is what it always was
+fuzz_real = os.environ.get("FUZZ_REAL") == "1"
+rng_real = np.random.default_rng(104729 + int(os.environ.get("FUZZ_SEED", "1")))
 n_cases = int(os.environ.get("FUZZ_N", "60"))
 bad = 0
 t0 = time.time()
@@ -32,6 +36,9 @@ for case in range(n_cases):
     if rng_big.random() < 0.25:                           # a few large cells: the sorted schedule exports their fragments to other blocks
         for _ in range(int(rng_big.integers(1, 5))):
             M[rng_big.integers(0, K), rng_big.integers(0, G)] = int(rng_big.integers(8_193, 150_000))
+    real = fuzz_real and bool(rng_real.random() < 0.5) and model.startswith("normal")
+    if real:
+        M = np.asfortranarray(M + rng_real.normal(0.0, 1.0 + 0.2 * M.std(), size=M.shape))
     kw = dict(seed=int(rng.integers(1, 1000)), learning_rank=lr)
     save_Z = bool(rng.random() < 0.4) and model in ("gamma", "exponential")      # full mode of the Gibbs sweep: Z itself is compared
     if save_Z: kw["save_Z"] = True
@@ -63,6 +70,6 @@ for case in range(n_cases):
         ok = False; print("EXC", ex)
     if not ok:
         bad += 1
-        print("MISMATCH", case, model, K, G, N, lr, window, kw["seed"], "save_Z" if save_Z else "", flush=True)
+        print("MISMATCH", case, model, K, G, N, lr, window, kw["seed"], "save_Z" if save_Z else "", "real" if real else "", flush=True)
 print("cases %d, mismatches %d, %.0f s" % (n_cases, bad, time.time() - t0))
 sys.exit(1 if bad else 0)
