@@ -172,6 +172,7 @@ struct bnmf_handle {
   long colmax = 0;                      // largest column total of M
   bool zs_shared = false;               // the sorted schedule spreads large cells over the blocks: ZsumK is accumulated (atomics), the draw kernels zero it
   int n_cu = 256;
+  int zs_nempty = 0;                    // blocks of the sorted schedule without an own column (bnmf_get_stat 7)
   // k_zalloc_step (zalloc_step.h): stats mode, 25 <= N <= 100, any K — the static schedule built from M at bnmf_create
   bool z_step = false; ZPGeom zpg{}; int zp_ns = 0 /* waves per workgroup */, zp_gbp = 0; size_t zp_lds = 0;
   bool zp_it16 = false;                // k_zalloc_step's items as uint16
@@ -372,17 +373,27 @@ int bnmf_create_f64(const bnmf_config* cfg, const double* M, bnmf_handle** out) 
 // Static schedule of k_zalloc_sort (zalloc_sort.h): columns dealt into blocks of equal total count (largest column first,
 // to the lightest block that still has room), the non-empty cells of a block as items sorted by their number of quads,
 // 64 items per task.  M is fixed for the life of the handle, so this runs once.
-static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
-  const bnmf_config& c = h->cfg;
-  const size_t K = c.K, G = c.G, N = c.N;
-  h->z_sort = false;
-  if (!h->z_reg || N > (size_t)ZS_NMAX - 1 || K > 1024) return 0;
+//
+// plan_zsort is the schedule itself: pure host code (no HIP call, no handle), so that its contract can be checked on any machine and for
+// any number of CUs (bnmf_test_zsort_plan, tests/test_schedule_host.py); build_zsort uploads what it returns.  p.ok = false: declined.
+struct ZSortPlan {
+  bool ok = false, it16 = false, pk = false, shared = false;
+  int KP = 0, GBc = 0, nb = 0, W = 0, nblk = 0, qmax = 0, nempty = 0;   // nempty: blocks without an own column
+  std::vector<ZSBlock> blocks;
+  std::vector<int> cols;              // the blocks' columns (own, then guests) in block order, then ONE trailing entry (column 0): see the end of plan_zsort
+  std::vector<uint32_t> items;        // 4-byte form, always
+  std::vector<uint16_t> items16;      // 2-byte form of the same items, if it16
+  std::vector<int32_t> Mblk;
+};
+static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int maxM, bool z_reg, int n_cu, ZSortPlan& p) {
+  p = ZSortPlan();
+  if (!z_reg || N > (size_t)ZS_NMAX - 1 || K > 1024) return 0;
   // save_Z: a cell's counts per factor meet as 16-bit halves in k_zexpand's slab
-  if (c.save_Z && h->maxM > 65535) return 0;
+  if (save_Z && maxM > 65535) return 0;
   if (const char* e = getenv("BNMF_ZSORT")) if (atoi(e) == 0) return 0;          // diagnostics / tests: the register kernel
   // an item word holds 16 bits of fragment index (k | gl << 10 | f << 16), and f = 65535 with k = 1023, gl = 63 is the empty-lane
   // sentinel: a cell above 65,534 fragments of 4 ZS_QMAX counts stays with the register kernel
-  if ((long long)h->maxM > 65534LL * 4 * ZS_QMAX16) return 0;
+  if ((long long)maxM > 65534LL * 4 * ZS_QMAX16) return 0;
   // Round 5: LARGE CELLS ARE SPREAD OVER THE BLOCKS.  A block's work is the counts of its columns, and the columns are dealt whole: a cell of
   // 10^6 counts (six times an average block at the metric configuration) made its block, and with it the launch, six times as long.  The
   // fragments of a cell above ZS_BIG counts beyond its first ZS_HOME are now "exported" in units of ZS_UNIT fragments to the lightest blocks,
@@ -392,7 +403,7 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
   // save_Z (k_zexpand writes whole columns of Z per block).  The per-count work stays O(sum M) — the reference's rmultinom is O(N) per cell
   // (R/sample_params.R:263) — but a 10^7-count cell is 25 % more counts for the whole chip, not a 60-fold longer block.
   constexpr int ZS_BIG = 8192, ZS_HOME = 16, ZS_UNIT = 32;
-  const bool spread = !c.save_Z && (long long)h->maxM > ZS_BIG && !(getenv("BNMF_ZSSPREAD") && atoi(getenv("BNMF_ZSSPREAD")) == 0);   // (tests: 0 = every cell at home)
+  const bool spread = !save_Z && (long long)maxM > ZS_BIG && !(getenv("BNMF_ZSSPREAD") && atoi(getenv("BNMF_ZSSPREAD")) == 0);   // (tests: 0 = every cell at home)
   const int nblk = (int)((N + 4) / 5);                                             // threshold blocks per cell
   const int KP = (K % 32 == 0) ? (int)K + 1 : (int)(K | 1);
   size_t budget = 156 * 1024;                                                     // of 160: the side streams' workgroups (2 KB each) keep room on the CU
@@ -413,8 +424,8 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
   if (!W || GBc > 64) return 0;
   if (const char* e = getenv("BNMF_ZSW")) { const int w = atoi(e); if (w == 4 || w == 6 || w == 8 || w == 12 || w == 14 || w == 16) W = w; }
   // columns -> blocks
-  const bool it16_pre = K <= 127 && GBc <= 64 && (long long)h->maxM <= 8LL * 4 * ZS_QMAX16;
-  const int qmax_pre = (it16_pre || (long long)h->maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;   // quads per fragment (the item format is fixed below: the same rule)
+  const bool it16_pre = K <= 127 && GBc <= 64 && (long long)maxM <= 8LL * 4 * ZS_QMAX16;
+  const int qmax_pre = (it16_pre || (long long)maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;   // quads per fragment (the item format is fixed below: the same rule)
   struct Unit { int g, k, f0, nf; long counts; };
   std::vector<Unit> units;
   std::vector<long> ctot(G, 0), cfull(G, 0);
@@ -503,7 +514,7 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
   // 25.3 / 20.2 / 19.6 / 21.2; 2,000: 36.2 / 26.5 / 23.3 / 24.0 / 29.1; 4,000: 37.2 / 31.6 / 30.1 / 34.0 / 44.1; 10,000: 52.7 / 53.4 / 56.7 / 69.0 /
   // 94.1.  The draws do not depend on it (Philox counter = cell, count index).  BNMF_ZSQMAX: tests.
   int qsel = 0;
-  if (!spread && (long long)h->maxM <= ZS_BIG) {          // (above: the fragment index of a 4-byte item is 16 bits)
+  if (!spread && (long long)maxM <= ZS_BIG) {          // (above: the fragment index of a 4-byte item is 16 bits)
     const int cand[5] = {64, 32, 16, 8, 4};
     double worst[5] = {0, 0, 0, 0, 0};
     for (int b = 0; b < nb; ++b) {
@@ -523,10 +534,10 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
     if (const char* e = getenv("BNMF_ZSQMAX")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) qsel = v; }
   }
   // 2-byte items where row, column-in-block and fragment index fit 7 + 6 + 3 bits (and 0xFFFF stays free for the empty lane)
-  bool it16 = K <= 127 && GBc <= 64 && (long long)h->maxM <= 8LL * 4 * (qsel ? qsel : ZS_QMAX16);
+  bool it16 = K <= 127 && GBc <= 64 && (long long)maxM <= 8LL * 4 * (qsel ? qsel : ZS_QMAX16);
   if (const char* e = getenv("BNMF_ZSIT16")) it16 = it16 && atoi(e) != 0;           // diagnostics / tests: 0 = 4-byte items
   // (large cells spread over the blocks: 4-byte items of 128 counts per fragment, 256 where a cell would need more than 65,534 of them)
-  const int qmax = qsel ? qsel : (it16 || (long long)h->maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;
+  const int qmax = qsel ? qsel : (it16 || (long long)maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;
   std::vector<ZSBlock> blocks(nb);
   std::vector<int> cols;
   std::vector<uint32_t> items;
@@ -606,11 +617,39 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
   }
   if (items.empty()) items.push_back(0xFFFFFFFFu);
   if (it16) {
-    std::vector<uint16_t> i16(items.size());
+    p.items16.resize(items.size());
     for (size_t i = 0; i < items.size(); ++i) {
       const uint32_t v = items[i];
-      i16[i] = v == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)((v & 127u) | (((v >> 10) & 63u) << 7) | ((v >> 16) << 13));
+      p.items16[i] = v == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)((v & 127u) | (((v >> 10) & 63u) << 7) | ((v >> 16) << 13));
     }
+  }
+  // WHAT A KERNEL MAY READ OF A BLOCK WITHOUT COLUMNS.  All-zero columns add no load: they pile onto the lightest block until it is full, and
+  // with G between one and two times the number of blocks and most columns empty the last blocks get none (ncols = 0, col0 = the length of
+  // the list; the exported units of large cells go to exactly those blocks, as guests).  The set-up of k_zalloc_sort reads cols[col0 + 0] for
+  // the lanes beyond its block's A E products, whatever ncols is, and E of that column (the product is discarded): cols[col0 .. col0 +
+  // max(ncols, 1)) must be inside the list and name real columns.  Hence one trailing entry, column 0, which no block owns through it.
+  cols.push_back(0);
+  for (int b = 0; b < nb; ++b) p.nempty += bcols[b].empty() ? 1 : 0;
+  p.ok = true; p.it16 = it16; p.pk = pk; p.shared = !units.empty();
+  p.KP = KP; p.GBc = GBc; p.nb = (int)nb; p.W = W; p.nblk = nblk; p.qmax = qmax;
+  p.blocks.swap(blocks); p.cols.swap(cols); p.items.swap(items); p.Mblk.swap(Mblk);
+  return 0;
+}
+static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
+  const bnmf_config& c = h->cfg;
+  const size_t K = c.K, G = c.G, N = c.N;
+  h->z_sort = false;
+  ZSortPlan p;
+  if (int rc = plan_zsort(M, K, G, N, c.save_Z != 0, h->maxM, h->z_reg, n_cu, p)) return rc;
+  if (!p.ok) return 0;
+  const bool it16 = p.it16, pk = p.pk;
+  const int qmax = p.qmax, GBc = p.GBc, KP = p.KP, W = p.W, nblk = p.nblk, nb = p.nb;
+  const std::vector<ZSBlock>& blocks = p.blocks;
+  const std::vector<int>& cols = p.cols;
+  const std::vector<uint32_t>& items = p.items;
+  const std::vector<int32_t>& Mblk = p.Mblk;
+  if (it16) {
+    const std::vector<uint16_t>& i16 = p.items16;
     HIPCHK(dmalloc(&h->dZsItems, ((i16.size() * sizeof(uint16_t) + 3) & ~(size_t)3)));
     HIPCHK(hipMemcpy(h->dZsItems, i16.data(), i16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
   } else {
@@ -641,8 +680,8 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
     HIPCHK(hipFuncSetAttribute((const void*)k_zexpand, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
   h->zsg = ZSGeom{KP, GBc, (int)nb};
-  h->zs_shared = !units.empty();                           // columns with several writers of ZsumK: atomics + zeroing by the consumer (refresh_dev)
-  h->zs_nblk = nblk; h->zs_w = W; h->zs_pk = pk;
+  h->zs_shared = p.shared;                                 // columns with several writers of ZsumK: atomics + zeroing by the consumer (refresh_dev)
+  h->zs_nblk = nblk; h->zs_w = W; h->zs_pk = pk; h->zs_nempty = p.nempty;
   h->zs_lds = (zsort_shared_bytes((int)K, (int)N, KP, GBc, pk) + (size_t)W * zsort_wave_bytes(nblk, (int)N) + 15) & ~(size_t)15;
   h->z_sort = true;
 #ifdef ZSPROF
@@ -657,11 +696,22 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
 // 32; the cells of a step (chunk x batch) as items — zero-count cells too: their Mhat feeds the metric terms — sorted by
 // their number of quads (counting sort) and dealt to the workgroup's waves in snake order, 64 per task: the waves of a step
 // get the same number of items of the same sizes.  M is fixed for the life of the handle, so this runs once.
-static int build_zstep(bnmf_handle* h, const int32_t* M, int n_cu) {
-  const bnmf_config& c = h->cfg;
-  const size_t K = c.K, G = c.G, N = c.N;
-  h->z_step = false;
-  if (c.save_Z || N <= (size_t)ZNMAX || N > (size_t)ZP_NMAX) return 0;
+//
+// plan_zstep / build_zstep: the schedule as pure host code, and its upload (as plan_zsort / build_zsort).  Every workgroup has a column:
+// a column costs its counts plus a fixed 64 K, so a workgroup without one is lighter than any with one and is dealt to first.
+struct ZStepPlan {
+  bool ok = false, it16 = false;
+  int nch = 0, nwg = 0, W = 0, GBP = 0, L = 0, maxfrag = 0;
+  std::vector<ZPWg> wgs;
+  std::vector<ZPBatch> batches;
+  std::vector<ZPStep> steps;
+  std::vector<int> cols;
+  std::vector<uint32_t> items;        // 4-byte form, always
+  std::vector<uint16_t> items16;      // 2-byte form of the same items, if it16
+};
+static int plan_zstep(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int n_cu, ZStepPlan& p) {
+  p = ZStepPlan();
+  if (save_Z || N <= (size_t)ZNMAX || N > (size_t)ZP_NMAX) return 0;
   if (const char* e = getenv("BNMF_ZSTEP")) if (atoi(e) == 0) return 0;            // diagnostics / tests: the tile kernel
   const int L = 4;                                                                 // lanes per cell (with <= 20 included factors the search then skips a level)
   size_t budget = 156 * 1024;                                                      // of 160: the side streams' workgroups keep room on the CU
@@ -747,10 +797,31 @@ static int build_zstep(bnmf_handle* h, const int32_t* M, int n_cu) {
   if (items.empty()) items.push_back(0xFFFFFFFFu);
   // 2-byte items where the fragment index fits 5 bits beside row (5) and column (6), 0xFFFF staying the empty lane (column 63 does not
   // occur): BNMF_ZPIT16=0 keeps the 4-byte form (diagnostics / tests)
-  h->zp_it16 = maxfrag <= 30 && !(getenv("BNMF_ZPIT16") && atoi(getenv("BNMF_ZPIT16")) == 0);
+  const bool it16 = maxfrag <= 30 && !(getenv("BNMF_ZPIT16") && atoi(getenv("BNMF_ZPIT16")) == 0);
+  if (it16) {
+    p.items16.resize(items.size());
+    for (size_t i = 0; i < items.size(); ++i) p.items16[i] = items[i] == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)items[i];
+  }
+  p.ok = true; p.it16 = it16; p.nch = nch; p.nwg = (int)nwg; p.W = W; p.GBP = GBP; p.L = L; p.maxfrag = maxfrag;
+  p.wgs.swap(wgs); p.batches.swap(batches); p.steps.swap(steps); p.cols.swap(cols); p.items.swap(items);
+  return 0;
+}
+static int build_zstep(bnmf_handle* h, const int32_t* M, int n_cu) {
+  const bnmf_config& c = h->cfg;
+  const size_t N = c.N;
+  h->z_step = false;
+  ZStepPlan p;
+  if (int rc = plan_zstep(M, c.K, c.G, N, c.save_Z != 0, n_cu, p)) return rc;
+  if (!p.ok) return 0;
+  const int nch = p.nch, nwg = p.nwg, W = p.W, GBP = p.GBP, L = p.L;
+  const std::vector<ZPWg>& wgs = p.wgs;
+  const std::vector<ZPBatch>& batches = p.batches;
+  const std::vector<ZPStep>& steps = p.steps;
+  const std::vector<int>& cols = p.cols;
+  const std::vector<uint32_t>& items = p.items;
+  h->zp_it16 = p.it16;
   if (h->zp_it16) {
-    std::vector<uint16_t> i16(items.size());
-    for (size_t i = 0; i < items.size(); ++i) i16[i] = items[i] == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)items[i];
+    const std::vector<uint16_t>& i16 = p.items16;
     HIPCHK(dmalloc(&h->dZpItems, (i16.size() * sizeof(uint16_t) + 3) & ~(size_t)3));
     HIPCHK(hipMemcpy(h->dZpItems, i16.data(), i16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
   } else {
@@ -956,6 +1027,46 @@ extern "C" int bnmf_test_devlock(const char* bus_tag, int* lock_ok, int* gate_ok
   if (a >= 0) close(a);
   if (b >= 0) close(b);
   return rc;
+}
+// the two static schedules as the host plans them (tests/test_schedule_host.py; no GPU involved): the call with every array NULL is the
+// size query, the call with arrays fills those given.  maxM and the register kernel's N bound are derived as bnmf_create derives them.
+// zsort desc: ok, KP, GBc, blocks, W, qmax, it16, pk, shared, blocks without an own column, ints of the column list as uploaded, items,
+// words of Mblk, threshold blocks per cell.  zstep desc: ok, nch, workgroups, W, GBP, it16, maxfrag, batches, steps, columns, items.
+extern "C" int bnmf_test_zsort_plan(int K, int G, int N, int save_Z, int n_cu, const int32_t* M, long long* desc, int32_t* blocks, int32_t* cols,
+                                    uint32_t* items, uint16_t* items16, int32_t* Mblk) {
+  if (!M || !desc || K < 1 || G < 1 || N < 1 || n_cu < 1) return fail(BNMF_EINVAL, "bnmf_test_zsort_plan: bad argument");
+  int mx = 0;
+  for (size_t i = 0; i < (size_t)K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_test_zsort_plan: negative count in M"); if (M[i] > mx) mx = M[i]; }
+  ZSortPlan p;
+  if (int rc = plan_zsort(M, (size_t)K, (size_t)G, (size_t)N, save_Z != 0, mx, N <= ZNMAX, n_cu, p)) return rc;
+  const long long d[14] = {p.ok, p.KP, p.GBc, p.nb, p.W, p.qmax, p.it16, p.pk, p.shared, p.nempty, (long long)p.cols.size(), (long long)p.items.size(),
+                           (long long)p.Mblk.size(), p.nblk};
+  memcpy(desc, d, sizeof d);
+  static_assert(sizeof(ZSBlock) == 4 * sizeof(int32_t), "ZSBlock is four ints");
+  if (blocks) memcpy(blocks, p.blocks.data(), p.blocks.size() * sizeof(ZSBlock));
+  if (cols) memcpy(cols, p.cols.data(), p.cols.size() * sizeof(int));
+  if (items) memcpy(items, p.items.data(), p.items.size() * sizeof(uint32_t));
+  if (items16) memcpy(items16, p.items16.data(), p.items16.size() * sizeof(uint16_t));
+  if (Mblk) memcpy(Mblk, p.Mblk.data(), p.Mblk.size() * sizeof(int32_t));
+  return 0;
+}
+extern "C" int bnmf_test_zstep_plan(int K, int G, int N, int save_Z, int n_cu, const int32_t* M, long long* desc, int32_t* wgs, int32_t* batches,
+                                    void* steps, int32_t* cols, uint32_t* items, uint16_t* items16) {
+  if (!M || !desc || K < 1 || G < 1 || N < 1 || n_cu < 1) return fail(BNMF_EINVAL, "bnmf_test_zstep_plan: bad argument");
+  for (size_t i = 0; i < (size_t)K * G; ++i) if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_test_zstep_plan: negative count in M");
+  ZStepPlan p;
+  if (int rc = plan_zstep(M, (size_t)K, (size_t)G, (size_t)N, save_Z != 0, n_cu, p)) return rc;
+  const long long d[11] = {p.ok, p.nch, p.nwg, p.W, p.GBP, p.it16, p.maxfrag, (long long)p.batches.size(), (long long)p.steps.size(), (long long)p.cols.size(),
+                           (long long)p.items.size()};
+  memcpy(desc, d, sizeof d);
+  static_assert(sizeof(ZPWg) == 8 && sizeof(ZPBatch) == 8 && sizeof(ZPStep) == 16, "layout of the step schedule's tables");
+  if (wgs) memcpy(wgs, p.wgs.data(), p.wgs.size() * sizeof(ZPWg));
+  if (batches) memcpy(batches, p.batches.data(), p.batches.size() * sizeof(ZPBatch));
+  if (steps) memcpy(steps, p.steps.data(), p.steps.size() * sizeof(ZPStep));                  // { int64 item0; int32 ntw, pad; }
+  if (cols) memcpy(cols, p.cols.data(), p.cols.size() * sizeof(int));
+  if (items) memcpy(items, p.items.data(), p.items.size() * sizeof(uint32_t));
+  if (items16) memcpy(items16, p.items16.data(), p.items16.size() * sizeof(uint16_t));
+  return 0;
 }
 
 // ---- can two kernels on two streams of this device run at the same time?  (once per device and process) ----
@@ -1524,6 +1635,8 @@ int bnmf_get_stat(bnmf_handle* h, int what, double* out) {   // sizes of the sch
     case 3: *out = h->zs_eager ? 1.0 : 0.0; return 0;
     case 5: *out = h->z_sort ? (double)h->zs_qmax : 0.0; return 0;                          // quads per item of the sorted schedule (chosen per data set)
     case 4: *out = h->mh_pipe ? 1.0 : 0.0; return 0;                                        // MH sweep: k_mh_tail's work hosted by the two sweep kernels
+    case 6: *out = h->z_sort ? (double)h->zsg.nblocks : h->z_step ? (double)h->zpg.nwg : 0.0; return 0;   // blocks (workgroups) of the static schedule
+    case 7: *out = h->z_sort ? (double)h->zs_nempty : 0.0; return 0;                        // ... of them without an own column (k_zalloc_step: never)
     default: return fail(BNMF_EINVAL, "bnmf_get_stat: unknown statistic %d", what);
   }
 }

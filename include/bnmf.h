@@ -223,7 +223,8 @@ int bnmf_state_info(const char* path, bnmf_state_desc* out);
 /* sizes of the handle's per-iteration buffers (bench.py's byte counts): what = 0 bytes of item records written per iteration (save_Z on the
  * sorted schedule: samples$Z is kept as these records and expanded when read), 1 bytes of Mhat left for the per-column metric terms,
  * 2 whether samples$Z is a ring of records, 3 whether Z is expanded every iteration (BNMF_ZEAGER=1), 4 whether the MH sweep hosts what followed
- * its two kernels inside them (Poisson MH models at fixed rank; BNMF_MHPIPE=0: no), 5 the quads (4 counts) per item of the sorted schedule */
+ * its two kernels inside them (Poisson MH models at fixed rank; BNMF_MHPIPE=0: no), 5 the quads (4 counts) per item of the sorted schedule,
+ * 6 the blocks (workgroups) of the static allocation schedule, 7 how many of them have no column of their own (sorted schedule) */
 int bnmf_get_stat(bnmf_handle* h, int what, double* out);
 
 /* average device time (ms) of each kernel class over n_iter iterations, measured with HIP
@@ -255,6 +256,17 @@ int bnmf_test_philox7(int device, const uint32_t ctr[4], const uint32_t key[2], 
  * opening of the device's two lock files under BNMF_LOCKDIR (or /tmp) with the lock order of bnmf_run.  Not part of the drop-in boundary. */
 int bnmf_test_gate(int n_sharers, int calls_per_sharer, int hold_us, long* excl_wait_us, long* admitted_while_waiting);
 int bnmf_test_devlock(const char* bus_tag, int* lock_ok, int* gate_ok);
+/* host-only (no GPU): the static schedules of the allocation kernels as bnmf_create would plan them for this data on a device of n_cu
+ * compute units, under the same environment switches (tests/test_schedule_host.py).  Every array may be NULL (size query: desc alone).
+ * zsort: desc[14] = accepted, KP, GBc, blocks, waves, quads per item, 2-byte items, pk, large cells spread, blocks without an own column,
+ *   ints of the column list as uploaded, items, words of Mblk, threshold blocks; blocks[4 per block] = item0, ntask, col0, ncols; items
+ *   (4-byte form, always) and items16 (if 2-byte items are chosen: what is uploaded).
+ * zstep: desc[11] = accepted, row chunks, workgroups, waves, GBP, 2-byte items, largest fragment index, batches, steps, columns, items;
+ *   wgs[2 per workgroup] = batch0, nbatch; batches[2 per batch] = col0, ncols; steps[16 bytes per step] = int64 item0, int32 ntw, pad. */
+int bnmf_test_zsort_plan(int K, int G, int N, int save_Z, int n_cu, const int32_t* M, long long* desc, int32_t* blocks, int32_t* cols,
+                         uint32_t* items, uint16_t* items16, int32_t* Mblk);
+int bnmf_test_zstep_plan(int K, int G, int N, int save_Z, int n_cu, const int32_t* M, long long* desc, int32_t* wgs, int32_t* batches,
+                         void* steps, int32_t* cols, uint32_t* items, uint16_t* items16);
 int bnmf_debug_rank(bnmf_handle* h, unsigned long long* out, size_t n);
 int bnmf_debug_zsort(bnmf_handle* h, unsigned long long* out);
 int bnmf_debug_set_timeout(bnmf_handle* h, int word);
