@@ -1,6 +1,7 @@
 // bayesnmf_amd/csrc/api.hip — C ABI of libbnmf.so (include/bnmf.h) over the gfx950 kernels.
-// Host side: device memory, one HIP stream per handle, launch sequencing of the sweep
-// (R/bayesNMF_sampler.R:273-285) and of the constructor draws (:232-257).  There is no CPU path.
+// Host side: device memory, three HIP streams per handle, the constructor draws (R/bayesNMF_sampler.R:232-257).  The launch sequencing of
+// the sweep (:273-285) is in sweep.h, the allocation kernels' static schedules in zplan.h, the state file in state_io.h: all three are
+// included here (one translation unit).  There is no CPU path.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <chrono>
@@ -104,6 +105,58 @@ static hipError_t dfree(void* p) {
 struct Arr { double* d = nullptr; size_t n = 0; int stride = 1; bool set = false; std::vector<int> redraw; double* ring = nullptr;
              bool slab = false; };   // slab: d points into the handle's block of scalars (a broadcast hyper-prior value), not an allocation of its own
 
+// What one sweep hands to the next: the host's record of what is in flight on the three streams (sweep.h is its only writer
+// apart from the two resets below).  Configuration chosen at bnmf_create (mh_pipe, mh_side_main, gate_forced, serial, dbg_*) is
+// not in here.  The default member initialisers ARE the reset values: a chain starts (bnmf_init on a used handle, bnmf_load_state)
+// with `pipe = Pipe{}` behind drained streams and cleared sync words.  "t" below is the iteration a sweep is about to run.
+//
+// The hyper sweep of t (prior parameters, Esum; issued during t - 1)
+//   side_valid     it has been issued.  Set by every launch_side* (launch_side_early only with its launch_side_late), by k_mh_tail / the
+//                  hosted MH sweep when they carry it; read at the top of every sweep, which issues it by launch_side if not.
+//   side_main      ... on the main stream (launch_side_main, k_mh_tail, the hosted MH sweep): the draws of t need neither poll nor wait.
+//                  MH / Normal sweeps only.  side_main implies side_valid and !flags_valid.
+//   flags_valid    ... by kernels that publish flags [1] (E side) and [3] (Esum) = t, which the draw kernels may poll instead of a stream
+//                  wait.  Read as `poll = flags_valid && !profile && !serial`; meaningful only while side_valid (bnmf_set_array
+//                  leaves it, the launch_side that follows clears it).
+//   side_ev_stale  ev_sideP / ev_side have not been recorded behind it.  True only after launch_side_E / launch_side_merged (the fixed-rank
+//                  Gibbs sweep, where nobody waits for them in the steady state); whoever needs the events calls refresh_side_events.
+//   gate_f0        the flag that says its E side (merged path: its P side) is done, beside [3]: 9 after launch_side_merged (P side on `side`
+//                  under [9], E side inside k_draw), 1 after a split sweep's k_pdraw.  Read by the allocation kernel's gate (zargs) and by the
+//                  split sweep that follows a merged one.  Never 9 when the rank is learned.
+// The allocation kernel's gate (merged draw path)
+//   z_gate_next    != 0 only inside sweep(), around launch_zalloc: the kernel being launched waits at its end for the hyper sweep of this
+//                  iteration (t + 1).  Set and cleared by sweep(), read by zargs.
+//   z_gated_for    what z_gate_next was for the last allocation kernel.  z_gated_for == t only if the allocation kernel of t - 1 was launched
+//                  with a gate: then k_draw of t may start without a poll of its own.  Read by sweep()'s choice only, and only under poll.
+// Reductions issued late (all three are empty between two API calls: bnmf_init and run_impl flush them at their ends)
+//   red_pending, red_t, red_row   k_reduce of iteration red_t into metric row red_row has not been issued (launch_reduce); taken by the next
+//                  sweep's side launches (issue_pending_reduce), by the MH tail kernels as workgroups (take_reduce_slots), or by flush_reduce.
+//   red_issued     ev_red has been recorded at least once (a k_reduce off side2): side2's log-prior kernels wait for it (lpPn slot reuse).
+//   red_on_side2   the last k_reduce went to side2 itself: stream order, no wait for ev_red.
+//   ct_pending     iteration whose column terms (sorted schedule) have not been summed; taken by take_colterms / flush_colterms.
+//   mh_etail_pending   hosted MH sweep: iteration whose E side has not been issued; taken by the next row sweep or flush_mh_etail.
+// Buffers a sweep leaves prepared for the next
+//   mh_prep_valid  MH / Normal sweeps: Et, nzE are current and nzP is zero (k_mh_tail of the previous iteration).
+//   mh_pipe_valid  hosted MH sweep: its Et / parity flag buffers are current.  At most one of the two is true: launch_mh_PE prepares the
+//                  form it runs and invalidates the other.
+//   z_expanded_iter   save_Z on the sorted schedule: the iteration whose Z is in dZ, expanded from its records (ensure_Z).
+struct Pipe {
+  bool side_valid = false, side_main = false, flags_valid = false, side_ev_stale = false;
+  int gate_f0 = 1;
+  uint32_t z_gate_next = 0, z_gated_for = 0;
+  bool red_pending = false, red_issued = false, red_on_side2 = false; uint32_t red_t = 0; int red_row = 0;
+  uint32_t ct_pending = 0, mh_etail_pending = 0;
+  bool mh_prep_valid = false, mh_pipe_valid = false;
+  int z_expanded_iter = 0;
+  // bnmf_set_array (streams drained, the chain goes on): the hyper sweep of iter + 1 and the MH sweeps' prepared buffers were made from
+  // the value just replaced.  Narrower than a reset, and enough: the next sweep finds !side_valid and calls launch_side, which
+  // clears flags_valid, side_main and side_ev_stale and records ev_side; hence poll is false in that sweep, the main stream waits for
+  // ev_side, and what survives is not read before it is rewritten — gate_f0 and z_gated_for are read only under poll (the allocation kernel
+  // is gated only under poll, too), z_gated_for is written by every sweep and gate_f0 by every sweep that leaves flags_valid set; red_issued only says that ev_red may be waited for, which stays true.
+  // A full reset would also change that first sweep's runtime calls (no wait for ev_red).
+  void invalidate_prepared() { side_valid = false; side_main = false; mh_prep_valid = false; mh_pipe_valid = false; }
+};
+
 struct bnmf_handle {
   bnmf_config cfg{};
   int device = 0;
@@ -111,32 +164,23 @@ struct bnmf_handle {
   hipStream_t side = nullptr;          // side stream: k_side (E part) of the next iteration (overlaps k_zalloc), k_reduce
   hipStream_t side2 = nullptr;         // second side stream: k_side P part (starts right after k_pdraw) and Esum
   hipEvent_t ev_draw = nullptr, ev_side = nullptr, ev_sideP = nullptr, ev_p = nullptr, ev_z = nullptr, ev_red = nullptr, ev_rank = nullptr;
-  bool side_valid = false;             // k_side of iteration iter+1 has been issued
-  bool side_main = false;              // ... on the main stream (MH / Normal sweeps: launch_side_main)
   bool mh_side_tail = true;            // BNMF_MHSIDETAIL=0 (diagnostics): the main-stream hyper sweep as a launch of its own in front of k_mh_tail
   bool mh_side_main = true;            // BNMF_MHSIDE=0 (diagnostics / tests): the MH / Normal sweeps' hyper sweep on the side stream, as in round 3
   int gate_forced = -1;                // BNMF_GATE at bnmf_create: 0 / 1 forces the merged draw kernel off / on, else by size
   int draw_bw = 0;                     // lanes per workgroup of the merged draw kernel (chosen at the first launch)
   double* dScal = nullptr;              // [BNMF_ID_MAX] broadcast scalars of bnmf_set_array (hyper-prior values given as one number)
-  unsigned* dDrawOwn = nullptr; unsigned draw_seq = 0;   // k_draw: owner word per column of P, launch sequence number (kernels.h)
+  unsigned* dDrawOwn = nullptr; unsigned draw_seq = 0;   // k_draw: owner word per column of P, launch sequence number (kernels.h).  draw_seq is NOT part of
+                                       // Pipe: it only has to differ from launch to launch, so bnmf_init leaves it running; bnmf_load_state zeroes it with dDrawOwn
   int dbg_draw_no_p = 0;               // BNMF_DEBUG_DRAW_NO_P (tests): the P workgroups of k_draw leave without claiming their columns
   int dbg_main_delay_us = 0;           // BNMF_DEBUG_MAIN_DELAY_US (tests): a delay kernel in front of the main stream's kernels of every sweep
   int dbg_allside_delay_us = 0;        // BNMF_DEBUG_ALLSIDE_DELAY_US (tests): a delay kernel in front of EVERY kernel launched on the two side streams
   int dbg_side_delay_us = 0;           // BNMF_DEBUG_SIDE_DELAY_US (tests): a delay kernel in front of the P-side hyper sweep of launch_side_merged
-  int gate_f0 = 1;                     // flag the gate waits for beside [3]: [1] E-side sweep (k_side), [9] P-side sweep on its own stream (merged draw path)
-  uint32_t z_gate_next = 0;            // != 0: the allocation kernel being launched waits at its end for the hyper sweep of this iteration
-  uint32_t z_gated_for = 0;            // the last allocation kernel gated for this iteration's hyper sweep (merged draw kernel, BNMF_GATE)
-  bool side_ev_stale = false;          // ev_sideP / ev_side not recorded since the last side launches (fixed-rank sweep: recorded on demand)
   bool mhe_k128 = false;               // BNMF_MHE_K128=1 (diagnostics / tests): k_mh_ecol16's 128-row form also where K <= 96
   bool mhe16 = false;                  // the MH / Normal column sweep by k_mh_ecol16 (K <= 128 and its LDS fits)
-  bool red_on_side2 = false;           // the last k_reduce was issued on side2 (then side2 needs no event to be ordered behind it)
   double* E_alt = nullptr;             // Gibbs sweep: the other E buffer (k_edraw of t+1 does not overwrite what k_lpe of t still reads)
-  bool mh_prep_valid = false;          // MH / Normal models: Et, nzE are current and nzP is zero (k_mh_tail of the previous iteration)
   bool mh_pipe = false;                // Poisson MH models at fixed rank through k_mh_ecol16: what followed the two sweeps is hosted BY them (mh.h; BNMF_MHPIPE=0: k_mh_tail)
-  bool mh_pipe_valid = false;          // ... and its Et / parity flag buffers are current
-  uint32_t mh_etail_pending = 0;       // ... the iteration whose E side (hyper sweep of the next, log-prior, record) has not been issued yet
-  const void* z_attr_kernel = nullptr;   // allocation kernel whose dynamic-LDS limit has been raised for this handle
-  bool red_pending = false, red_issued = false; uint32_t red_t = 0; int red_row = 0;   // k_reduce of the previous iteration, issued late
+  const void* z_attr_kernel = nullptr;   // allocation kernel whose dynamic-LDS limit has been raised for this handle (raise_lds_limit, sweep.h)
+  Pipe pipe;                           // what one sweep hands to the next (above); reset where a chain starts: bnmf_init, bnmf_load_state
   int iter = 0;
   bool inited = false;
   Dev dev{};
@@ -165,10 +209,9 @@ struct bnmf_handle {
   // Round 5: Z of the sorted schedule is kept AS RECORDS (two 16-bit counts per word and item: 44 MB per iteration at the metric configuration
   // against 77 MB of Z) and expanded when somebody reads it (bnmf_get_array, bnmf_window): k_zexpand left the loop.  With a window the
   // records of iteration t live in slot (t - 1) % wcap of dZsRecRing (samples$Z); zs_eager (BNMF_ZEAGER=1, measurements): expand every iteration.
-  uint32_t* dZsRecRing = nullptr; size_t zs_recwords = 0; int z_expanded_iter = 0; bool zs_eager = false;
+  uint32_t* dZsRecRing = nullptr; size_t zs_recwords = 0; bool zs_eager = false;
   uint32_t* dZsItems = nullptr; ZSBlock* dZsBlocks = nullptr; int* dZsCols = nullptr; unsigned long long* dZsProf = nullptr;
   double* dZsMh = nullptr;              // [G][K] Mhat left by k_zalloc_sort for the per-column metric terms (colterms.h)
-  uint32_t ct_pending = 0;              // iteration whose column terms have not been summed yet (0: none)
   long colmax = 0;                      // largest column total of M
   bool zs_shared = false;               // the sorted schedule spreads large cells over the blocks: ZsumK is accumulated (atomics), the draw kernels zero it
   int n_cu = 256;
@@ -188,7 +231,6 @@ struct bnmf_handle {
                                                   // [8], [9] P-side sweep on its own stream
   int* hErr = nullptr; int* dErr = nullptr;       // time-out words of the bounded in-kernel waits, in mapped host memory (read without a copy):
                                                   // [0] a draw kernel waiting for the hyper sweep, [1] the rank sweep's exchange
-  bool flags_valid = false;                       // the side work of the next iteration publishes its flags
   bool serial = false;                            // no kernel may wait for a kernel of another stream (serialised dispatch: counter
                                                   // collection, AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING; or BNMF_SERIAL=1): stream waits only
   bool poisoned = false;                          // a bounded in-kernel wait timed out: the state is no longer the chain's, every call fails
@@ -218,7 +260,7 @@ static size_t id_len(const bnmf_handle* h, int id) {
 static bool is_hyper(int id) { return (id >= 30 && id < 50) || id == BNMF_ALPHA || id == BNMF_BETA; }
 static bool is_prior_param(int id) { return id >= BNMF_ALPHA_P && id <= BNMF_LAMBDA_E; }   // 2 slots, slot(t) = t & 1
 static int cur_slot(const bnmf_handle* h) { return (h->iter > 0 ? h->iter : 1) & 1; }
-static bool is_pside(int id) { size_t dummy = 0; (void)dummy; return id == BNMF_P || id == BNMF_ALPHA_P || id == BNMF_BETA_P || id == BNMF_MU_P || id == BNMF_SIGMASQ_P || id == BNMF_LAMBDA_P; }
+static bool is_pside(int id) { return id == BNMF_P || id == BNMF_ALPHA_P || id == BNMF_BETA_P || id == BNMF_MU_P || id == BNMF_SIGMASQ_P || id == BNMF_LAMBDA_P; }
 
 static int ensure_Z(bnmf_handle* h);   // save_Z on the sorted schedule: Z of the current iteration expanded from its records, if it is not
 static int ensure(bnmf_handle* h, int id) {
@@ -269,6 +311,8 @@ struct CreateClock {
   void mark(const char* what) { if (!on) return; const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[bnmf_create] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count()); t0 = t; }
 };
 __global__ void k_set_scalar(double* p, double v) { *p = v; }
+
+#include "zplan.h"   // plan_zsort, plan_zstep: the allocation kernels' static schedules (device-free)
 
 extern "C" {
 
@@ -370,271 +414,7 @@ int bnmf_create_f64(const bnmf_config* cfg, const double* M, bnmf_handle** out) 
   return bnmf_create(cfg, mi.data(), out);
 }
 
-// Static schedule of k_zalloc_sort (zalloc_sort.h): columns dealt into blocks of equal total count (largest column first,
-// to the lightest block that still has room), the non-empty cells of a block as items sorted by their number of quads,
-// 64 items per task.  M is fixed for the life of the handle, so this runs once.
-//
-// plan_zsort is the schedule itself: pure host code (no HIP call, no handle), so that its contract can be checked on any machine and for
-// any number of CUs (bnmf_test_zsort_plan, tests/test_schedule_host.py); build_zsort uploads what it returns.  p.ok = false: declined.
-struct ZSortPlan {
-  bool ok = false, it16 = false, pk = false, shared = false;
-  int KP = 0, GBc = 0, nb = 0, W = 0, nblk = 0, qmax = 0, nempty = 0;   // nempty: blocks without an own column
-  std::vector<ZSBlock> blocks;
-  std::vector<int> cols;              // the blocks' columns (own, then guests) in block order, then ONE trailing entry (column 0): see the end of plan_zsort
-  std::vector<uint32_t> items;        // 4-byte form, always
-  std::vector<uint16_t> items16;      // 2-byte form of the same items, if it16
-  std::vector<int32_t> Mblk;
-};
-static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int maxM, bool z_reg, int n_cu, ZSortPlan& p) {
-  p = ZSortPlan();
-  if (!z_reg || N > (size_t)ZS_NMAX - 1 || K > 1024) return 0;
-  // save_Z: a cell's counts per factor meet as 16-bit halves in k_zexpand's slab
-  if (save_Z && maxM > 65535) return 0;
-  if (const char* e = getenv("BNMF_ZSORT")) if (atoi(e) == 0) return 0;          // diagnostics / tests: the register kernel
-  // an item word holds 16 bits of fragment index (k | gl << 10 | f << 16), and f = 65535 with k = 1023, gl = 63 is the empty-lane
-  // sentinel: a cell above 65,534 fragments of 4 ZS_QMAX counts stays with the register kernel
-  if ((long long)maxM > 65534LL * 4 * ZS_QMAX16) return 0;
-  // Round 5: LARGE CELLS ARE SPREAD OVER THE BLOCKS.  A block's work is the counts of its columns, and the columns are dealt whole: a cell of
-  // 10^6 counts (six times an average block at the metric configuration) made its block, and with it the launch, six times as long.  The
-  // fragments of a cell above ZS_BIG counts beyond its first ZS_HOME are now "exported" in units of ZS_UNIT fragments to the lightest blocks,
-  // which host the cell's column as a GUEST column (up to GX extra column slots per block: its A E products, a row of zK); Mhat is still left
-  // by the lane of fragment 0, which stays at home.  ZsumK of a column then has several writers: every block adds its share with integer
-  // atomics (exact, order-independent) and the draw kernels zero what they have consumed (Dev::zsumk_accum, as for the tile kernel).  Not with
-  // save_Z (k_zexpand writes whole columns of Z per block).  The per-count work stays O(sum M) — the reference's rmultinom is O(N) per cell
-  // (R/sample_params.R:263) — but a 10^7-count cell is 25 % more counts for the whole chip, not a 60-fold longer block.
-  constexpr int ZS_BIG = 8192, ZS_HOME = 16, ZS_UNIT = 32;
-  const bool spread = !save_Z && (long long)maxM > ZS_BIG && !(getenv("BNMF_ZSSPREAD") && atoi(getenv("BNMF_ZSSPREAD")) == 0);   // (tests: 0 = every cell at home)
-  const int nblk = (int)((N + 4) / 5);                                             // threshold blocks per cell
-  const int KP = (K % 32 == 0) ? (int)K + 1 : (int)(K | 1);
-  size_t budget = 156 * 1024;                                                     // of 160: the side streams' workgroups (2 KB each) keep room on the CU
-  if (const char* e = getenv("BNMF_ZSLDS")) budget = (size_t)atol(e) * 1024;
-  long nb = std::min<long>((long)G, n_cu);
-  int GBc = 0, W = 0;
-  for (int tries = 0; tries < 12; ++tries, nb = std::min<long>((long)G, nb * 2)) {
-    GBc = (int)((G + nb - 1) / nb);
-    if (spread) GBc = std::min(64, GBc + 8);                                      // guest column slots
-    if (GBc <= 64 && (long)nb * GBc >= (long)G) {
-      const size_t sh = zsort_shared_bytes((int)K, (int)N, KP, GBc, false), wv = zsort_wave_bytes(nblk, (int)N);
-      W = 0;
-      for (int w : {16, 14, 12, 8, 6, 4}) if (sh + (size_t)w * wv <= budget) { W = w; break; }
-      if (W) break;
-    }
-    if (nb >= (long)G) break;
-  }
-  if (!W || GBc > 64) return 0;
-  if (const char* e = getenv("BNMF_ZSW")) { const int w = atoi(e); if (w == 4 || w == 6 || w == 8 || w == 12 || w == 14 || w == 16) W = w; }
-  // columns -> blocks
-  const bool it16_pre = K <= 127 && GBc <= 64 && (long long)maxM <= 8LL * 4 * ZS_QMAX16;
-  const int qmax_pre = (it16_pre || (long long)maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;   // quads per fragment (the item format is fixed below: the same rule)
-  struct Unit { int g, k, f0, nf; long counts; };
-  std::vector<Unit> units;
-  std::vector<long> ctot(G, 0), cfull(G, 0);
-  for (size_t g = 0; g < G; ++g) {
-    long sacc = 0, exported = 0;
-    for (size_t k = 0; k < K; ++k) {
-      const long m = M[k + K * g];
-      sacc += m;
-      if (spread && m > ZS_BIG) {
-        const long qt = (m + 3) >> 2, F = (qt + qmax_pre - 1) / qmax_pre;
-        for (long f0 = ZS_HOME; f0 < F; f0 += ZS_UNIT) {
-          const long nf = std::min<long>(ZS_UNIT, F - f0);
-          const long cnt = std::min<long>(m, (f0 + nf) * 4L * qmax_pre) - f0 * 4L * qmax_pre;
-          units.push_back({(int)g, (int)k, (int)f0, (int)nf, cnt});
-          exported += cnt;
-        }
-      }
-    }
-    cfull[g] = sacc; ctot[g] = sacc - exported;
-  }
-  std::vector<int> order(G);
-  for (size_t g = 0; g < G; ++g) order[g] = (int)g;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ctot[a] > ctot[b]; });
-  std::vector<std::vector<int>> bcols(nb);
-  std::vector<long> bload(nb, 0);
-  const int own_cap = spread ? std::max(1, (int)((G + nb - 1) / nb)) : GBc;        // own columns per block (the rest of GBc: guest slots)
-  {
-    // min-heap of (load, block) over the blocks that still have room
-    std::vector<std::pair<long, int>> heap;
-    for (int b = 0; b < nb; ++b) heap.push_back({0L, b});
-    auto cmp = [](const std::pair<long, int>& a, const std::pair<long, int>& b) { return a > b; };
-    std::make_heap(heap.begin(), heap.end(), cmp);
-    for (int g : order) {
-      std::pop_heap(heap.begin(), heap.end(), cmp);
-      auto top = heap.back(); heap.pop_back();
-      bcols[top.second].push_back(g);
-      top.first += ctot[g];
-      if ((int)bcols[top.second].size() < own_cap) { heap.push_back(top); std::push_heap(heap.begin(), heap.end(), cmp); }
-    }
-  }
-  for (int b = 0; b < nb; ++b) { std::sort(bcols[b].begin(), bcols[b].end()); long l = 0; for (int g : bcols[b]) l += ctot[g]; bload[b] = l; }
-  // the exported units -> the lightest blocks (largest unit first); a block takes a unit if it owns the column, hosts it already, or has a
-  // guest slot left; a unit nobody can take stays with its column's owner
-  std::vector<std::vector<int>> gcols(nb);                                         // guest columns per block, in slot order
-  struct BUnit { int k, gl, f0, nf; };
-  std::vector<std::vector<BUnit>> bunits(nb);
-  if (!units.empty()) {
-    std::vector<int> owner(G, -1);
-    for (int b = 0; b < nb; ++b) for (int g : bcols[b]) owner[g] = b;
-    std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.counts > b.counts; });
-    std::vector<std::pair<long, int>> heap;
-    for (int b = 0; b < nb; ++b) heap.push_back({bload[b], b});
-    auto cmp = [](const std::pair<long, int>& a, const std::pair<long, int>& b) { return a > b; };
-    std::make_heap(heap.begin(), heap.end(), cmp);
-    auto slot_of = [&](int b, int g, bool take) -> int {
-      if (owner[g] == b) return (int)(std::lower_bound(bcols[b].begin(), bcols[b].end(), g) - bcols[b].begin());
-      for (size_t i = 0; i < gcols[b].size(); ++i) if (gcols[b][i] == g) return (int)(bcols[b].size() + i);
-      if (take && (int)(bcols[b].size() + gcols[b].size()) < GBc) { gcols[b].push_back(g); return (int)(bcols[b].size() + gcols[b].size() - 1); }
-      return -1;
-    };
-    for (const Unit& u : units) {
-      std::vector<std::pair<long, int>> skipped;
-      int dst = -1, gl = -1;
-      for (int tries = 0; tries < 16 && !heap.empty(); ++tries) {
-        std::pop_heap(heap.begin(), heap.end(), cmp);
-        auto top = heap.back(); heap.pop_back();
-        gl = slot_of(top.second, u.g, true);
-        if (gl >= 0) { dst = top.second; top.first += u.counts; heap.push_back(top); std::push_heap(heap.begin(), heap.end(), cmp); break; }
-        skipped.push_back(top);
-      }
-      for (auto& x : skipped) { heap.push_back(x); std::push_heap(heap.begin(), heap.end(), cmp); }
-      if (dst < 0) {                                                               // home: its load grows (the heap entry is found and raised)
-        dst = owner[u.g]; gl = slot_of(dst, u.g, false);
-        for (auto& x : heap) if (x.second == dst) x.first += u.counts;
-        std::make_heap(heap.begin(), heap.end(), cmp);
-      }
-      bunits[dst].push_back({u.k, gl, u.f0, u.nf});
-    }
-  }
-  // Quads per item.  Round 5 (end): chosen per data set where no cell is large enough to be spread.  A wave alone with its task runs a quad in
-  // ~0.33 us (one dependent chain; tools/zstamps.py, tools/zsmall.py) and the waves of a SIMD share its issue at about twice that per wave
-  // and quad: with few cells per block (K = 96, G = 2,000: 13 tasks for 14 waves) the kernel WAS its largest task — 64 quads with 2-byte
-  // items, 20 of its 34 us.  Estimated per block in quad units, T = 6 for a task's thresholds: max(T + largest item, 2 (quads / 64 + T tasks)
-  // / W); the candidate with the smallest worst block wins, the larger one on a near-tie (fewer items, fewer thresholds).  Measured, device
-  // time of the kernel in us at K = 96, N = 20 with 64 / 32 / 16 / 8 / 4 quads per item: G = 250: 35.1 / 24.8 / 19.6 / 16.9 / 16.3; 1,000: 35.8 /
-  // 25.3 / 20.2 / 19.6 / 21.2; 2,000: 36.2 / 26.5 / 23.3 / 24.0 / 29.1; 4,000: 37.2 / 31.6 / 30.1 / 34.0 / 44.1; 10,000: 52.7 / 53.4 / 56.7 / 69.0 /
-  // 94.1.  The draws do not depend on it (Philox counter = cell, count index).  BNMF_ZSQMAX: tests.
-  int qsel = 0;
-  if (!spread && (long long)maxM <= ZS_BIG) {          // (above: the fragment index of a 4-byte item is 16 bits)
-    const int cand[5] = {64, 32, 16, 8, 4};
-    double worst[5] = {0, 0, 0, 0, 0};
-    for (int b = 0; b < nb; ++b) {
-      long Q = 0, I[5] = {0, 0, 0, 0, 0}; int maxqt = 0;
-      for (int g : bcols[b]) for (size_t k = 0; k < K; ++k) {
-        const int m = M[k + K * (size_t)g], qt = m > 0 ? (m + 3) >> 2 : 0;
-        Q += qt; maxqt = std::max(maxqt, qt);
-        for (int c = 0; c < 5; ++c) I[c] += qt ? (qt + cand[c] - 1) / cand[c] : 1;
-      }
-      for (int c = 0; c < 5; ++c) {
-        const double est = std::max(6.0 + std::min(cand[c], maxqt), 2.0 * ((double)Q / 64.0 + 6.0 * (double)((I[c] + 63) / 64)) / (double)W);
-        worst[c] = std::max(worst[c], est);
-      }
-    }
-    double best = 1e300;
-    for (int c = 0; c < 5; ++c) if (worst[c] < 0.95 * best) { best = worst[c]; qsel = cand[c]; }
-    if (const char* e = getenv("BNMF_ZSQMAX")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) qsel = v; }
-  }
-  // 2-byte items where row, column-in-block and fragment index fit 7 + 6 + 3 bits (and 0xFFFF stays free for the empty lane)
-  bool it16 = K <= 127 && GBc <= 64 && (long long)maxM <= 8LL * 4 * (qsel ? qsel : ZS_QMAX16);
-  if (const char* e = getenv("BNMF_ZSIT16")) it16 = it16 && atoi(e) != 0;           // diagnostics / tests: 0 = 4-byte items
-  // (large cells spread over the blocks: 4-byte items of 128 counts per fragment, 256 where a cell would need more than 65,534 of them)
-  const int qmax = qsel ? qsel : (it16 || (long long)maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;
-  std::vector<ZSBlock> blocks(nb);
-  std::vector<int> cols;
-  std::vector<uint32_t> items;
-  // two factors per word in the block's zG / zK tables (16-bit halves): only if no half can overflow, i.e. every column total
-  // (bound of a ZsumK entry) and every row total over a block's columns (bound of the block's share of a ZsumG entry) < 2^16
-  bool pk = *std::max_element(cfull.begin(), cfull.end()) < 65536;                  // (the WHOLE column: units of a large cell may be dealt back to its owner)
-  // the blocks are independent: their item lists are built by a few host threads (the schedule was 20 of the 50 ms of bnmf_create
-  // at the metric configuration)
-  std::vector<std::vector<uint32_t>> bitems(nb);
-  std::vector<char> bpk(nb, 1);
-  auto build_blocks = [&](long b0, long b1) {
-    std::vector<std::pair<int, uint32_t>> tmp;
-    for (long b = b0; b < b1; ++b) {
-      for (size_t k = 0; k < K && bpk[b]; ++k) {
-        long r = 0;
-        for (int g : bcols[b]) r += M[k + K * (size_t)g];
-        for (int g : gcols[b]) r += M[k + K * (size_t)g];                          // (a guest column's share: bounded by the whole cell)
-        if (r >= 65536) bpk[b] = 0;
-      }
-      tmp.clear();
-      for (size_t gl = 0; gl < bcols[b].size(); ++gl) {
-        const size_t g = (size_t)bcols[b][gl];
-        for (size_t k = 0; k < K; ++k) {
-          const int m = M[k + K * g];
-          if (m <= 0) { tmp.push_back({0, (uint32_t)k | ((uint32_t)gl << 10)}); continue; }   // an item without counts: its lane leaves Mhat of the cell (s.mh)
-          const int qt = (m + 3) >> 2;
-          const int fend = (spread && m > ZS_BIG) ? ZS_HOME : INT_MAX;                // a large cell: the fragments beyond the first ZS_HOME are units (below, or in other blocks)
-          for (int f = 0; f * qmax < qt && f < fend; ++f)
-            tmp.push_back({std::min(qmax, qt - f * qmax), (uint32_t)k | ((uint32_t)gl << 10) | ((uint32_t)f << 16)});
-        }
-      }
-      for (const BUnit& u : bunits[b]) {                                             // units of large cells this block works on (its own columns' or guests')
-        const size_t g = u.gl < (int)bcols[b].size() ? (size_t)bcols[b][u.gl] : (size_t)gcols[b][u.gl - (int)bcols[b].size()];
-        const int m = M[u.k + K * g], qt = (m + 3) >> 2;
-        for (int f = u.f0; f < u.f0 + u.nf && f * qmax < qt; ++f)
-          tmp.push_back({std::min(qmax, qt - f * qmax), (uint32_t)u.k | ((uint32_t)u.gl << 10) | ((uint32_t)f << 16)});
-      }
-      std::stable_sort(tmp.begin(), tmp.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-      // inside a task (64 consecutive items) the order is free: ascending row, so that neighbouring lanes read neighbouring
-      // rows of the LDS copy of P and add to neighbouring words of the block's ZsumG table (few bank conflicts)
-      for (size_t i0 = 0; i0 < tmp.size(); i0 += 64)
-        std::sort(tmp.begin() + i0, tmp.begin() + std::min(tmp.size(), i0 + 64), [](const auto& a, const auto& b) { return (a.second & 1023u) < (b.second & 1023u); });
-      std::vector<uint32_t>& it = bitems[b];
-      it.reserve(tmp.size() + 64);
-      for (const auto& x : tmp) it.push_back(x.second);
-      while (it.size() % 64) it.push_back(0xFFFFFFFFu);
-    }
-  };
-  {
-    const long nthr = std::max<long>(1, std::min<long>({(long)std::thread::hardware_concurrency(), 16L, nb}));
-    std::vector<std::thread> pool;
-    for (long i = 1; i < nthr; ++i) pool.emplace_back(build_blocks, nb * i / nthr, nb * (i + 1) / nthr);
-    build_blocks(0, nb / nthr);
-    for (auto& th : pool) th.join();
-  }
-  for (int b = 0; b < nb; ++b) pk = pk && bpk[b];
-  if (const char* e = getenv("BNMF_ZSPK")) pk = pk && atoi(e) != 0;                 // diagnostics / tests: 0 = one factor per word
-  // the waves per workgroup were sized for one factor per word (the block tables' larger form); with two per word the tables are half as
-  // large and, at the metric configuration, 14 waves fit where 12 did.  tools/ablong.py, sixteen processes alternating on one box: 12 waves
-  // 80.3 us per iteration in three of eight processes and 81.4-83.0 in the others (the stop-event mode of DESIGN.md 5b), 14 waves 81.3-81.6
-  // in seven of eight (80.3 in one): 82.1 against 81.3 us on average
-  if (pk && !getenv("BNMF_ZSW")) {
-    const size_t sh = zsort_shared_bytes((int)K, (int)N, KP, GBc, true), wv = zsort_wave_bytes(nblk, (int)N);
-    for (int w : {16, 14, 12, 8, 6, 4}) if (sh + (size_t)w * wv <= budget) { W = std::max(W, w); break; }
-  }
-  std::vector<int32_t> Mblk(K * G);
-  for (int b = 0; b < nb; ++b) {
-    ZSBlock& bk = blocks[b];
-    bk.item0 = (int)items.size(); bk.col0 = (int)cols.size(); bk.ncols = (int)(bcols[b].size() + gcols[b].size());
-    items.insert(items.end(), bitems[b].begin(), bitems[b].end());
-    bk.ntask = (int)(bitems[b].size() / 64);
-    for (int pass = 0; pass < 2; ++pass)
-      for (int g : (pass ? gcols[b] : bcols[b])) {
-        if (Mblk.size() < K * (cols.size() + 1)) Mblk.resize(K * (cols.size() + 1));
-        memcpy(Mblk.data() + K * cols.size(), M + K * (size_t)g, K * sizeof(int32_t)); cols.push_back(g);
-      }
-  }
-  if (items.empty()) items.push_back(0xFFFFFFFFu);
-  if (it16) {
-    p.items16.resize(items.size());
-    for (size_t i = 0; i < items.size(); ++i) {
-      const uint32_t v = items[i];
-      p.items16[i] = v == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)((v & 127u) | (((v >> 10) & 63u) << 7) | ((v >> 16) << 13));
-    }
-  }
-  // WHAT A KERNEL MAY READ OF A BLOCK WITHOUT COLUMNS.  All-zero columns add no load: they pile onto the lightest block until it is full, and
-  // with G between one and two times the number of blocks and most columns empty the last blocks get none (ncols = 0, col0 = the length of
-  // the list; the exported units of large cells go to exactly those blocks, as guests).  The set-up of k_zalloc_sort reads cols[col0 + 0] for
-  // the lanes beyond its block's A E products, whatever ncols is, and E of that column (the product is discarded): cols[col0 .. col0 +
-  // max(ncols, 1)) must be inside the list and name real columns.  Hence one trailing entry, column 0, which no block owns through it.
-  cols.push_back(0);
-  for (int b = 0; b < nb; ++b) p.nempty += bcols[b].empty() ? 1 : 0;
-  p.ok = true; p.it16 = it16; p.pk = pk; p.shared = !units.empty();
-  p.KP = KP; p.GBc = GBc; p.nb = (int)nb; p.W = W; p.nblk = nblk; p.qmax = qmax;
-  p.blocks.swap(blocks); p.cols.swap(cols); p.items.swap(items); p.Mblk.swap(Mblk);
-  return 0;
-}
+// build_zsort uploads what plan_zsort (zplan.h) returns
 static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
   const bnmf_config& c = h->cfg;
   const size_t K = c.K, G = c.G, N = c.N;
@@ -691,121 +471,7 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
   return 0;
 }
 
-// Static schedule of k_zalloc_step (zalloc_step.h): columns dealt to the workgroups by total count (largest first, to the
-// lightest workgroup that still has room), a workgroup's columns cut into batches of <= GBP, a batch's rows into chunks of
-// 32; the cells of a step (chunk x batch) as items — zero-count cells too: their Mhat feeds the metric terms — sorted by
-// their number of quads (counting sort) and dealt to the workgroup's waves in snake order, 64 per task: the waves of a step
-// get the same number of items of the same sizes.  M is fixed for the life of the handle, so this runs once.
-//
-// plan_zstep / build_zstep: the schedule as pure host code, and its upload (as plan_zsort / build_zsort).  Every workgroup has a column:
-// a column costs its counts plus a fixed 64 K, so a workgroup without one is lighter than any with one and is dealt to first.
-struct ZStepPlan {
-  bool ok = false, it16 = false;
-  int nch = 0, nwg = 0, W = 0, GBP = 0, L = 0, maxfrag = 0;
-  std::vector<ZPWg> wgs;
-  std::vector<ZPBatch> batches;
-  std::vector<ZPStep> steps;
-  std::vector<int> cols;
-  std::vector<uint32_t> items;        // 4-byte form, always
-  std::vector<uint16_t> items16;      // 2-byte form of the same items, if it16
-};
-static int plan_zstep(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int n_cu, ZStepPlan& p) {
-  p = ZStepPlan();
-  if (save_Z || N <= (size_t)ZNMAX || N > (size_t)ZP_NMAX) return 0;
-  if (const char* e = getenv("BNMF_ZSTEP")) if (atoi(e) == 0) return 0;            // diagnostics / tests: the tile kernel
-  const int L = 4;                                                                 // lanes per cell (with <= 20 included factors the search then skips a level)
-  size_t budget = 156 * 1024;                                                      // of 160: the side streams' workgroups keep room on the CU
-  int GBP = 0, W = 0;
-  // 8 waves (two per SIMD).  12 waves fit the LDS up to N = 60 and were measured at config 4: 114.5 against 121 us per launch, but
-  // at the 168 registers three waves per SIMD leave, the kernel spills 16-36 bytes per lane — not kept
-  for (int gbp : {40, 32}) if (zstep_shared_bytes((int)N, gbp) + 8 * zstep_wave_bytes(L) <= budget) { GBP = gbp; W = 8; break; }
-  if (const char* e = getenv("BNMF_ZPGB")) { const int v = atoi(e); if (v == 32 || v == 40) GBP = v; }   // diagnostics / tests
-  if (!GBP) return 0;
-  const int nch = (int)((K + ZP_KC - 1) / ZP_KC);
-  const long nwg = std::min<long>((long)G, n_cu);
-  // columns -> workgroups
-  std::vector<long> ctot(G, 0);
-  for (size_t g = 0; g < G; ++g) { long sacc = 0; for (size_t k = 0; k < K; ++k) sacc += M[k + K * g]; ctot[g] = sacc; }
-  std::vector<int> order(G);
-  for (size_t g = 0; g < G; ++g) order[g] = (int)g;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ctot[a] > ctot[b]; });
-  const size_t cap = (G + nwg - 1) / nwg + 2;                                      // the threshold work of a column does not depend on its counts
-  std::vector<std::vector<int>> wcols(nwg);
-  {
-    std::vector<std::pair<long, int>> heap;
-    for (int b = 0; b < nwg; ++b) heap.push_back({0L, b});
-    auto cmp = [](const std::pair<long, int>& a, const std::pair<long, int>& b) { return a > b; };
-    std::make_heap(heap.begin(), heap.end(), cmp);
-    for (int g : order) {
-      std::pop_heap(heap.begin(), heap.end(), cmp);
-      auto top = heap.back(); heap.pop_back();
-      wcols[top.second].push_back(g);
-      top.first += ctot[g] + 64 * (long)K;                                         // + the cells' fixed cost (Mhat, thresholds), in counts
-      if (wcols[top.second].size() < cap) { heap.push_back(top); std::push_heap(heap.begin(), heap.end(), cmp); }
-    }
-  }
-  std::vector<ZPWg> wgs(nwg);
-  std::vector<ZPBatch> batches;
-  std::vector<int> cols;
-  for (int b = 0; b < nwg; ++b) {
-    std::sort(wcols[b].begin(), wcols[b].end());
-    const int nc = (int)wcols[b].size(), nb = (nc + GBP - 1) / GBP;
-    wgs[b] = ZPWg{(int)batches.size(), nb};
-    for (int i = 0; i < nb; ++i) {
-      const int c0 = (int)((long)nc * i / nb), c1 = (int)((long)nc * (i + 1) / nb);
-      batches.push_back(ZPBatch{(int)cols.size(), c1 - c0});
-      for (int x = c0; x < c1; ++x) cols.push_back(wcols[b][x]);
-    }
-  }
-  std::vector<ZPStep> steps(batches.size() * (size_t)nch);
-  std::vector<uint32_t> items;
-  items.reserve((size_t)((double)K * (double)G * 1.05) + 64 * steps.size());
-  std::vector<uint32_t> bucket[ZP_QMAX + 1], wlist[ZP_WMAX], sorted;
-  int maxfrag = 0;
-  for (size_t bi = 0; bi < batches.size(); ++bi) {
-    const ZPBatch& bt = batches[bi];
-    for (int ch = 0; ch < nch; ++ch) {
-      const size_t k0 = (size_t)ch * ZP_KC, kc = std::min<size_t>(ZP_KC, K - k0);
-      for (auto& v : bucket) v.clear();
-      for (int gl = 0; gl < bt.ncols; ++gl) {
-        const size_t g = (size_t)cols[bt.col0 + gl];
-        for (size_t kl = 0; kl < kc; ++kl) {
-          const int m = M[k0 + kl + K * g];
-          const int qt = m > 0 ? (m + 3) >> 2 : 0;
-          const uint32_t base = (uint32_t)kl | ((uint32_t)gl << 5);
-          if (qt == 0) { bucket[0].push_back(base); continue; }
-          for (int f = 0; f * ZP_QMAX < qt; ++f) {
-            if (f >= (1 << 21)) return fail(BNMF_EINVAL, "bnmf_create: a cell of M holds %d counts: unsupported", m);
-            bucket[std::min(ZP_QMAX, qt - f * ZP_QMAX)].push_back(base | ((uint32_t)f << 11));
-            maxfrag = std::max(maxfrag, f);
-          }
-        }
-      }
-      // sorted by size, then dealt to the waves in snake order: every wave gets the same number of items (+-1) of the same sizes
-      sorted.clear();
-      for (int qn = ZP_QMAX; qn >= 0; --qn) sorted.insert(sorted.end(), bucket[qn].begin(), bucket[qn].end());
-      for (int w = 0; w < W; ++w) wlist[w].clear();
-      for (size_t i = 0; i < sorted.size(); ++i) { const int r = (int)(i % (2 * (size_t)W)); wlist[r < W ? r : 2 * W - 1 - r].push_back(sorted[i]); }
-      size_t mx = 0;
-      for (int w = 0; w < W; ++w) mx = std::max(mx, wlist[w].size());
-      ZPStep& st = steps[bi * (size_t)nch + ch];
-      st.item0 = (long long)items.size(); st.pad = 0;
-      st.ntw = (int)((mx + 63) / 64);
-      for (int w = 0; w < W; ++w) { const auto& v = wlist[w]; items.insert(items.end(), v.begin(), v.end()); items.insert(items.end(), (size_t)st.ntw * 64 - v.size(), 0xFFFFFFFFu); }
-    }
-  }
-  if (items.empty()) items.push_back(0xFFFFFFFFu);
-  // 2-byte items where the fragment index fits 5 bits beside row (5) and column (6), 0xFFFF staying the empty lane (column 63 does not
-  // occur): BNMF_ZPIT16=0 keeps the 4-byte form (diagnostics / tests)
-  const bool it16 = maxfrag <= 30 && !(getenv("BNMF_ZPIT16") && atoi(getenv("BNMF_ZPIT16")) == 0);
-  if (it16) {
-    p.items16.resize(items.size());
-    for (size_t i = 0; i < items.size(); ++i) p.items16[i] = items[i] == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)items[i];
-  }
-  p.ok = true; p.it16 = it16; p.nch = nch; p.nwg = (int)nwg; p.W = W; p.GBP = GBP; p.L = L; p.maxfrag = maxfrag;
-  p.wgs.swap(wgs); p.batches.swap(batches); p.steps.swap(steps); p.cols.swap(cols); p.items.swap(items);
-  return 0;
-}
+// ... and build_zstep what plan_zstep returns
 static int build_zstep(bnmf_handle* h, const int32_t* M, int n_cu) {
   const bnmf_config& c = h->cfg;
   const size_t N = c.N;
@@ -1503,8 +1169,7 @@ int bnmf_set_array(bnmf_handle* h, int id, const double* x, size_t n) {
   clk.mark("set_array: sync side");
   HIPCHK(hipStreamSynchronize(h->side2));
   clk.mark("set_array: sync side2");
-  h->side_valid = false; h->side_main = false;   // state changed: the pre-issued k_side must be redone
-  h->mh_prep_valid = false; h->mh_pipe_valid = false;
+  h->pipe.invalidate_prepared();   // state changed: the pre-issued k_side must be redone
   if (id == BNMF_R) { int r = (int)x[0]; HIPCHK(hipMemcpy(h->dR, &r, sizeof(int), hipMemcpyHostToDevice)); h->arr[BNMF_R].set = true; return 0; }
   if (id == BNMF_ZSUMK || id == BNMF_ZSUMG || id == BNMF_Z) {
     int32_t* dst = id == BNMF_ZSUMK ? h->dZsumK : id == BNMF_ZSUMG ? h->dZsumG : h->dZ;
@@ -1513,7 +1178,7 @@ int bnmf_set_array(bnmf_handle* h, int id, const double* x, size_t n) {
     std::vector<int32_t> tmp(n);
     for (size_t i = 0; i < n; ++i) tmp[i] = (int32_t)x[i];
     HIPCHK(hipMemcpy(dst, tmp.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (id == BNMF_Z) h->z_expanded_iter = h->iter;        // (what the caller stored is what a read returns until the next sweep)
+    if (id == BNMF_Z) h->pipe.z_expanded_iter = h->iter;        // (what the caller stored is what a read returns until the next sweep)
     return 0;
   }
   Arr& a = h->arr[id];
@@ -1644,835 +1309,7 @@ int bnmf_get_iter(bnmf_handle* h, int* iter) { if (!h || !iter) return fail(BNMF
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ launch helpers
-static int need_hyper(bnmf_handle* h, std::initializer_list<int> ids) {
-  for (int id : ids) if (!h->arr[id].d) return fail(BNMF_EUNSET, "hyper-prior array id %d was not set (fill_hyperprior_params, R/setup.R:15-88)", id);
-  return 0;
-}
-static int ensure_metrics(bnmf_handle* h, size_t rows) {
-  if (rows <= h->metrics_rows) return 0;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipHostFree(h->hMetrics));
-  h->hMetrics = nullptr; h->dMetrics = nullptr;
-  h->metrics_rows = rows;
-  HIPCHK(hipHostMalloc((void**)&h->hMetrics, rows * BNMF_NMETRIC * sizeof(double), hipHostMallocMapped));
-  HIPCHK(hipHostGetDevicePointer((void**)&h->dMetrics, h->hMetrics, 0));
-  HIPCHK(dfree(h->dRaw));
-  HIPCHK(dmalloc(&h->dRaw, rows * 8 * sizeof(double)));
-  refresh_dev(h);
-  return 0;
-}
-// Per-iteration partial sums (per-column metric terms, log-prior partials, MH acceptance partials) live in
-// three slots (t % 3): k_reduce of iteration t is issued during iteration t+1 (see launch_side / launch_side_E), and the
-// next writers of its slot are the kernels of iteration t+3.  Fixed-rank sweep: k_reduce(t) sits on side2 in front of
-// Esum(t+2), whose flag releases k_pdraw(t+2) and with it everything of iteration t+2 and later on the main stream; the
-// log-prior workgroups of side2 follow it in stream order.  Other sweeps: through ev_side (main stream) and ev_red (side2).
-static void set_slot(const bnmf_handle* h, Dev& d, uint32_t t) {
-  const size_t sl = t % 3u, G = h->cfg.G, N = h->cfg.N;
-  d.colsse = h->dcol + sl * 3 * G; d.colll = d.colsse + G; d.colkl = d.colsse + 2 * G;
-  d.lpE_part = h->dlpE + sl * (size_t)h->nblkE;
-  d.lpPn = h->dlpPn + sl * N;
-}
-static void use_slot(bnmf_handle* h, uint32_t t) { set_slot(h, h->dev, t); }
-static double* accPn_slot(const bnmf_handle* h, uint32_t t) { return h->dAccPn ? h->dAccPn + (size_t)(t % 3u) * h->cfg.N : nullptr; }
-static double* accEp_slot(const bnmf_handle* h, uint32_t t) { return h->dAccEpart ? h->dAccEpart + (size_t)(t % 3u) * h->nblkE : nullptr; }
-struct Timer {   // optional per-kernel HIP-event bracketing (serialises the two streams: profile mode only)
-  bnmf_handle* h; bool on; double acc[BNMF_NKERNEL]{}; int cnt[BNMF_NKERNEL]{};
-  void begin(int k, hipStream_t st) { if (on) { hipStreamSynchronize(h->stream); hipStreamSynchronize(h->side); hipStreamSynchronize(h->side2); hipEventRecord(h->ev[2 * k], st); } }
-  void end(int k, hipStream_t st) { if (on) { hipEventRecord(h->ev[2 * k + 1], st); hipEventSynchronize(h->ev[2 * k + 1]); float ms = 0; hipEventElapsedTime(&ms, h->ev[2 * k], h->ev[2 * k + 1]); acc[k] += ms; cnt[k]++; } }
-};
-static RecDst rec_at(const bnmf_handle* h, uint32_t t, bool on);
-static bool fused_rec(const bnmf_handle* h);
-static double* ring_at(const bnmf_handle* h, int id, uint32_t t);
-static RecDst rec_pdraw(const bnmf_handle* h, uint32_t t, bool on) {   // what k_pdraw records
-  RecDst r = rec_at(h, t, on);
-  if (h->cfg.learning_rank) { r.A = nullptr; r.R = nullptr; }          // then k_sumA records them, after the rank update
-  return r;
-}
-static void launch_pdraw(bnmf_handle* h, uint32_t t, int from_prior, bool rec) {
-  const size_t lds = 2 * (size_t)h->cfg.K * sizeof(double);
-  hipLaunchKernelGGL(k_pdraw, dim3(h->cfg.N), dim3(PD_T), lds, h->stream, h->dev, t, from_prior, 1, rec_pdraw(h, t, rec), SideWait{});
-}
-static void launch_edraw(bnmf_handle* h, uint32_t t, int from_prior, bool rec) {
-  hipLaunchKernelGGL(k_edraw, dim3(h->nblkE), dim3(ES_T), 0, h->stream, h->dev, t, from_prior, 1, rec_at(h, t, rec).E);
-}
-// k_side for iteration t (reads P_{t-1}, E_{t-1}): issued on the side stream right after the draws
-// of iteration t-1, so that it overlaps k_zalloc of iteration t-1
-// tests (BNMF_DEBUG_ALLSIDE_DELAY_US): hold a side stream back in front of its next kernel — whatever then reads too early or writes too early shows
-// as a bit that differs from the oracle's
-static void dbg_delay(bnmf_handle* h, hipStream_t st) {
-  if (h->dbg_allside_delay_us && st != h->stream) hipLaunchKernelGGL(k_debug_delay, dim3(1), dim3(64), 0, st, h->dbg_allside_delay_us);
-}
-// ... and the other way round (BNMF_DEBUG_MAIN_DELAY_US): the main stream held back, so that a side-stream kernel that runs on the main stream's
-// results without waiting for them reads the values of the iteration before
-static void dbg_delay_main(bnmf_handle* h) {
-  if (h->dbg_main_delay_us) hipLaunchKernelGGL(k_debug_delay, dim3(1), dim3(64), 0, h->stream, h->dbg_main_delay_us);
-}
-static void issue_reduce(bnmf_handle* h, uint32_t t, int row, Timer& tm, hipStream_t st = nullptr) {
-  if (!st) st = h->side;
-  dbg_delay(h, st);
-  Dev dr = h->dev;
-  set_slot(h, dr, t);
-  tm.begin(KN_REDUCE, st);
-  hipLaunchKernelGGL(k_reduce, dim3(h->cfg.MH ? 5 : 4), dim3(RT), 0, st, dr, row, h->nblkE, (const double*)accPn_slot(h, t), (const double*)accEp_slot(h, t));
-  tm.end(KN_REDUCE, st);
-  // k_lpp's workgroups (side2) rewrite an lpPn slot this kernel read three iterations earlier: side2 waits for ev_red, unless the
-  // reduce was issued on side2 itself (the fixed-rank sweep), where stream order does it without two runtime calls
-  h->red_on_side2 = st == h->side2;
-  if (!h->red_on_side2) { hipEventRecord(h->ev_red, st); h->red_issued = true; }
-}
-// The per-column metric terms of iteration t from the Mhat k_zalloc_sort left (colterms.h), into the iteration's slot of the partial sums
-static CtArgs ct_args(const bnmf_handle* h, uint32_t t) {
-  const size_t G = h->cfg.G;
-  double* sse = h->dcol + (size_t)(t % 3u) * 3 * G;
-  return CtArgs{h->dZsMh + (size_t)(t % 3u) * h->cfg.K * G, h->dev.M, h->dev.lgfact, h->dev.logm, sse, sse + G, sse + 2 * G, h->cfg.K, h->cfg.G, h->dev.maxM};
-}
-// ... as a launch of its own on the main stream (behind the allocation kernel in stream order): whenever the next kernel on that stream
-// is not a merged draw kernel that could take the work along (first sweeps of a chain, two-kernel sweep, profile mode, end of a call)
-static void flush_colterms(bnmf_handle* h) {
-  if (!h->ct_pending) return;
-  const CtArgs a = ct_args(h, h->ct_pending);
-  hipLaunchKernelGGL(k_colterms, dim3((unsigned)((h->cfg.G + 2 * (CT_T / 64) - 1) / (2 * (CT_T / 64)))), dim3(CT_T), 0, h->stream, a);
-  h->ct_pending = 0;
-}
-// ev_sideP (side2 done) and ev_side (side done, behind ev_sideP) are what a main-stream wait or flush_reduce needs; in the
-// steady state of the fixed-rank sweep nobody waits for them (k_pdraw polls flags), so they are recorded on demand: a later
-// record covers everything enqueued before it
-static void refresh_side_events(bnmf_handle* h) {
-  if (!h->side_ev_stale) return;
-  hipEventRecord(h->ev_sideP, h->side2);
-  hipStreamWaitEvent(h->side, h->ev_sideP, 0);
-  hipEventRecord(h->ev_side, h->side);
-  h->side_ev_stale = false;
-}
-static void launch_side(bnmf_handle* h, uint32_t t, Timer& tm, bool publish = false) {
-  const int nbP = (int)(((size_t)h->cfg.K * h->cfg.N + RT - 1) / RT);
-  const int nbE = (int)(((size_t)h->cfg.N * h->cfg.G + RT - 1) / RT);
-  hipEventRecord(h->ev_draw, h->stream);
-  hipStreamWaitEvent(h->side, h->ev_draw, 0);
-  tm.begin(KN_SIDE, h->side);
-  // publish (MH / Normal sweeps): the last workgroup raises flag [1] = t, which the next P-row kernel polls (no barrier packet)
-  dbg_delay(h, h->side);
-  hipLaunchKernelGGL(k_side, dim3(h->cfg.N + nbP + nbE), dim3(RT), 0, h->side, h->dev, t, nbP, 0, rec_at(h, t, fused_rec(h)),
-                     publish ? SideDone{h->dFlags, h->dFlags + 1, (unsigned)(h->cfg.N + nbP + nbE), t} : SideDone{});
-  h->flags_valid = publish;
-  tm.end(KN_SIDE, h->side);
-  hipEventRecord(h->ev_side, h->side);
-  hipEventRecord(h->ev_sideP, h->side);
-  h->side_ev_stale = false;
-  h->side_valid = true;
-  h->side_main = false;
-  // k_reduce of the PREVIOUS iteration: its inputs are complete once the draws of this iteration have run
-  // (main-stream order), which ev_draw above implies, so the main stream needs no marker after k_zalloc
-  if (h->red_pending) { issue_reduce(h, h->red_t, h->red_row, tm); h->red_pending = false; }
-}
-// MH / Normal sweeps, steady state (round 4): the hyper sweep of iteration t on the MAIN stream, between the column kernel of t-1 and
-// its tail kernel.  On the side stream it was released by the column kernel through an event (12 us late), ran 20 us beside a 12 us tail
-// kernel, and the next P-row kernel waited 13.6 us of its 101 for the flag (profiles/r04_cfg3_kernel_stats.csv, r04_mh_prow_stamps.txt);
-// alone on the device it is shorter than that wait, and the row kernel behind it needs neither flag nor event.
-static void launch_side_main(bnmf_handle* h, uint32_t t, Timer& tm) {
-  const int nbP = (int)(((size_t)h->cfg.K * h->cfg.N + RT - 1) / RT);
-  const int nbE = (int)(((size_t)h->cfg.N * h->cfg.G + RT - 1) / RT);
-  tm.begin(KN_SIDE, h->stream);
-  hipLaunchKernelGGL(k_side, dim3(h->cfg.N + nbP + nbE), dim3(RT), 0, h->stream, h->dev, t, nbP, 0, rec_at(h, t, fused_rec(h)), SideDone{});
-  tm.end(KN_SIDE, h->stream);
-  h->flags_valid = false;
-  h->side_valid = true;
-  h->side_main = true;
-  // (k_reduce of the PREVIOUS iteration: inside this iteration's k_mh_tail, see launch_mh_metrics)
-}
-// The same work in three launches, for the Gibbs sweep.  The P-side hyper sweep depends on P_{t-1} only and has
-// the longest per-lane latency (rejection sampling of Alpha): it starts right behind k_pdraw on its own stream.
-// Esum follows it once k_edraw is done; both are over long before k_zalloc, so that the event the next k_pdraw
-// waits for is already satisfied when the main stream reaches it (a late cross-stream event costs ~12 us).
-// The E-side sweep (needed only by the next k_edraw) shares the CUs with k_zalloc and ends with it.
-// what k_lpe reads as E_t: the ring slot of iteration t when the sweep records (safe for a whole window), else the live E
-// (then sweep() double-buffers E)
-static bool lpe_from_ring(const bnmf_handle* h) { return fused_rec(h) && h->arr[BNMF_E].ring != nullptr; }
-static const double* lpe_src(const bnmf_handle* h, uint32_t t) { return lpe_from_ring(h) ? ring_at(h, BNMF_E, t) : h->dev.E; }
-static void launch_side_P(bnmf_handle* h, uint32_t t, hipEvent_t after = nullptr) {   // ev_p = completion of k_pdraw(t-1)
-  const int nbP = (int)(((size_t)h->cfg.K * h->cfg.N + RT - 1) / RT);
-  hipStreamWaitEvent(h->side2, after ? after : h->ev_p, 0);
-  // k_lpp below rewrites lpPn slot (t-1) % 3, last read by k_reduce of iteration t-4 (side stream): order behind it
-  if (h->red_issued && !h->red_on_side2) hipStreamWaitEvent(h->side2, h->ev_red, 0);
-  // ... and the log-prior of the P just drawn (k_lpp's work, iteration t-1) in the same launch
-  dbg_delay(h, h->side2);
-  hipLaunchKernelGGL(k_side_lp, dim3(nbP + h->cfg.N), dim3(RT), 0, h->side2, h->dev, t, nbP, h->cfg.N, rec_at(h, t, fused_rec(h)), SideDone{},
-                     SideExtra{nbP, h->cfg.N, 0, t - 1, nullptr, 0}, CtArgs{});
-}
-static void launch_side_E(bnmf_handle* h, uint32_t t, Timer& tm, bool e_done = false) {   // ev_draw = completion of k_edraw(t-1); e_done: k_draw ran the E-side sweep
-  const int nbP = (int)(((size_t)h->cfg.K * h->cfg.N + RT - 1) / RT);
-  const int nbE = (int)(((size_t)h->cfg.N * h->cfg.G + RT - 1) / RT);
-  hipStreamWaitEvent(h->side2, h->ev_draw, 0);
-  // Esum closes the side2 work the next k_pdraw needs (the P part ran before it on the same stream): it publishes flag [3]
-  // ... and, in the same launch, the log-prior of the E just drawn (k_lpe's work; iteration t-1, whose slot pointers h->dev
-  // still holds): off the critical path
-  dbg_delay(h, h->side2);
-  // (the per-column metric terms of the iteration before ride along as in launch_side_merged: workgroups behind the log-prior ones)
-  CtArgs ct{};
-  int n_ct = 0;
-  if (h->ct_pending) { ct = ct_args(h, h->ct_pending); n_ct = (h->cfg.G + 2 * (RT / 64) - 1) / (2 * (RT / 64)); h->ct_pending = 0; }
-  hipLaunchKernelGGL(k_side_lp, dim3(h->cfg.N + h->nblkE + n_ct), dim3(RT), 0, h->side2, h->dev, t, nbP, 0, RecDst{}, SideDone{h->dFlags + 2, h->dFlags + 3, (unsigned)(h->cfg.N + h->nblkE), t},
-                     SideExtra{h->cfg.N, 0, h->nblkE, t - 1, lpe_src(h, t - 1), 1}, ct);
-  // k_reduce of the PREVIOUS iteration here, behind the kernels that produce its inputs on this stream (k_lpp, k_lpe) and
-  // behind ev_draw (k_zalloc of that iteration): on the E part's stream it sat in front of the next E-side sweep, and the
-  // P part waited for its event
-  if (h->red_pending) { issue_reduce(h, h->red_t, h->red_row, tm, h->side2); h->red_pending = false; }
-  if (!e_done) {
-    hipStreamWaitEvent(h->side, h->ev_draw, 0);
-    dbg_delay(h, h->side);
-    hipLaunchKernelGGL(k_side, dim3(nbE), dim3(RT), 0, h->side, h->dev, t, nbP, h->cfg.N + nbP, rec_at(h, t, fused_rec(h)), SideDone{h->dFlags, h->dFlags + 1, (unsigned)nbE, t});
-  }
-  h->flags_valid = true;
-  // ev_side (the E part AND the P part / Esum / log-priors done) for a main-stream wait: on demand, see refresh_side_events
-  h->side_ev_stale = true;
-  h->side_valid = true;
-}
-// Behind the merged draw kernel (which runs the E-side sweep itself): the P-side hyper sweep of iteration t on `side`, with a
-// flag of its own ([9]); Esum(t) and the log-priors of iteration t-1 in ONE launch on side2 (flag [3] counts all its
-// workgroups), k_reduce behind it.  The two no longer share a stream: the P-side sweep is a few long per-lane chains and
-// held Esum's flag back.
-static void launch_side_merged(bnmf_handle* h, uint32_t t, Timer& tm) {
-  const int N = h->cfg.N;
-  const int nbP = (int)(((size_t)h->cfg.K * N + RT - 1) / RT);
-  hipStreamWaitEvent(h->side, h->ev_draw, 0);
-  if (h->dbg_side_delay_us) hipLaunchKernelGGL(k_debug_delay, dim3(1), dim3(64), 0, h->side, h->dbg_side_delay_us);   // tests: a late P-side sweep
-  dbg_delay(h, h->side);
-  hipLaunchKernelGGL(k_side, dim3(nbP), dim3(RT), 0, h->side, h->dev, t, nbP, N, rec_at(h, t, fused_rec(h)), SideDone{h->dFlags + 8, h->dFlags + 9, (unsigned)nbP, t});
-  // (Round 5, measured and NOT adopted: releasing the side streams by the draw kernel's flag — one polling wavefront at the head of each side
-  // stream, P / E stored write-through, no stop event on the draw kernel.  The stop event costs ~6 us between the draw kernel's end and the
-  // allocation kernel's start in the traces and its signal reaches the side queues 12-20 us later, differently from process to process
-  // (tools/bimodal.sh: steady iteration 80.6 us in most processes, 83.3 us in about a quarter) — but with the flag the side kernels start
-  // WITH the allocation kernel and take its issue slots from its first task on: 80.3 -> 96.4 us per iteration, bit-exact.)
-  hipStreamWaitEvent(h->side2, h->ev_draw, 0);
-  if (h->red_issued && !h->red_on_side2) hipStreamWaitEvent(h->side2, h->ev_red, 0);   // lpPn slot reuse, see launch_side_P
-  dbg_delay(h, h->side2);
-  // the per-column metric terms of iteration t - 2 ride along (its allocation kernel ran before the draw kernel whose stop event this stream
-  // has just waited for): extra workgroups behind the log-prior ones, beside the allocation kernel of t - 1; k_reduce(t - 2) follows below
-  CtArgs ct{};
-  int n_ct = 0;
-  if (h->ct_pending) { ct = ct_args(h, h->ct_pending); n_ct = (h->cfg.G + 2 * (RT / 64) - 1) / (2 * (RT / 64)); h->ct_pending = 0; }
-  hipLaunchKernelGGL(k_side_lp, dim3(2 * N + h->nblkE + n_ct), dim3(RT), 0, h->side2, h->dev, t, nbP, 0, RecDst{}, SideDone{h->dFlags + 2, h->dFlags + 3, (unsigned)(2 * N + h->nblkE), t},
-                     SideExtra{N, N, h->nblkE, t - 1, lpe_src(h, t - 1), 1}, ct);
-  if (h->red_pending) { issue_reduce(h, h->red_t, h->red_row, tm, h->side2); h->red_pending = false; }
-  h->flags_valid = true;
-  h->side_ev_stale = true;
-  h->side_valid = true;
-  h->gate_f0 = 9;
-}
-// Rank learning: the hyper sweep of t+1 in two parts.  Early (released by k_edraw): the k_side kernels.  They hold 64+ VGPRs
-// and cannot be scheduled on a CU whose SIMDs carry two waves of the rank sweep (230 VGPRs each): they run on the ~100 CUs
-// the rank sweep leaves free and are done before k_zalloc starts.  Late (released by the rank sweep): the small log-prior
-// kernels (16-28 VGPRs), which DO fit beside rank-sweep waves and delayed the whole co-resident grid at every factor, and
-// Esum, whose flag releases the next iteration's draws and therefore has to come after them.
-static void launch_side_early(bnmf_handle* h, uint32_t t) {
-  const int nbP = (int)(((size_t)h->cfg.K * h->cfg.N + RT - 1) / RT);
-  const int nbE = (int)(((size_t)h->cfg.N * h->cfg.G + RT - 1) / RT);
-  hipStreamWaitEvent(h->side2, h->ev_draw, 0);
-  dbg_delay(h, h->side2);
-  hipLaunchKernelGGL(k_side, dim3(nbP), dim3(RT), 0, h->side2, h->dev, t, nbP, h->cfg.N, rec_at(h, t, fused_rec(h)), SideDone{});
-  // Esum of t needs E only: summed here, beside the rank sweep (end of round 5).  Behind the rank sweep — where its flag has to be raised, see
-  // launch_side_late — its 50 workgroups sat beside the allocation kernel for 121 us of a 10 us reduction, and the next k_pdraw polled for them
-  dbg_delay(h, h->side2);
-  hipLaunchKernelGGL(k_side, dim3(h->cfg.N), dim3(RT), 0, h->side2, h->dev, t, nbP, 0, RecDst{}, SideDone{});
-  hipStreamWaitEvent(h->side, h->ev_draw, 0);
-  dbg_delay(h, h->side);
-  hipLaunchKernelGGL(k_side, dim3(nbE), dim3(RT), 0, h->side, h->dev, t, nbP, h->cfg.N + nbP, rec_at(h, t, fused_rec(h)), SideDone{h->dFlags, h->dFlags + 1, (unsigned)nbE, t});
-  h->flags_valid = true;
-}
-static void launch_side_late(bnmf_handle* h, uint32_t t, Timer& tm) {
-  hipStreamWaitEvent(h->side2, h->ev_rank, 0);
-  // k_lpp rewrites lpPn slot (t-1) % 3, last read by k_reduce of iteration t-4 (side stream): order behind it
-  if (h->red_issued) hipStreamWaitEvent(h->side2, h->ev_red, 0);
-  dbg_delay(h, h->side2);
-  hipLaunchKernelGGL(k_lpp, dim3(h->cfg.N), dim3(64), 0, h->side2, h->dev, t - 1);   // log-prior of the P just drawn
-  dbg_delay(h, h->side2);
-  hipLaunchKernelGGL(k_lpe, dim3(h->nblkE), dim3(ES_T), 0, h->side2, h->dev, t - 1, lpe_src(h, t - 1)); // ... and of the E just drawn
-  // Esum's flag [3] last: it releases the next iteration's draws, which overwrite the P and E the two kernels above read (the sums
-  // themselves were made by launch_side_early on this stream)
-  dbg_delay(h, h->side2);
-  hipLaunchKernelGGL(k_raise_flag, dim3(1), dim3(64), 0, h->side2, h->dFlags + 3, t);
-  hipEventRecord(h->ev_sideP, h->side2);
-  hipStreamWaitEvent(h->side, h->ev_sideP, 0);
-  hipEventRecord(h->ev_side, h->side);
-  h->side_ev_stale = false;
-  h->side_valid = true;
-  if (h->red_pending) { issue_reduce(h, h->red_t, h->red_row, tm); h->red_pending = false; }
-}
-template <typename KernelT, typename ArgT>
-static int launch_z(bnmf_handle* h, uint32_t t, KernelT kern, const ArgT& arg, int zt) {
-  if (h->z_attr_kernel != (const void*)kern) {           // once per handle (per device): allow > 64 KiB of dynamic LDS
-    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    h->z_attr_kernel = (const void*)kern;
-  }
-  hipLaunchKernelGGL(kern, dim3(h->z_grid), dim3(zt), h->z_lds, h->stream, arg, t, h->zg, h->z_ablate);
-  return 0;
-}
-static ZArgs zargs(const bnmf_handle* h) {
-  const Dev& d = h->dev;
-  ZArgs za{d.K, d.G, d.N, d.maxM, d.k0, d.k1, d.M, d.P, d.E, d.A, d.ZsumK, d.ZsumG, d.Z, d.colsse, d.colll, d.colkl, d.lgfact, d.logm, nullptr, nullptr, 0u, nullptr};
-  if (h->z_gate_next) { za.gate0 = h->dFlags + h->gate_f0; za.gate1 = h->dFlags + 3; za.gate_epoch = h->z_gate_next; za.gate_err = h->dErr; }
-  return za;
-}
-template <bool SZ, int ZT_, bool DIAG>
-static int launch_zreg_t(bnmf_handle* h, uint32_t t) {
-  const ZArgs za = zargs(h);
-  switch (h->zg.TR) {
-    case 8: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 8, DIAG>, za, ZT_);
-    case 16: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 16, DIAG>, za, ZT_);
-    case 20: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 20, DIAG>, za, ZT_);
-    default: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 24, DIAG>, za, ZT_);
-  }
-}
-template <bool SZ, int ZT_, bool LEAN_>
-static int launch_ztile(bnmf_handle* h, uint32_t t) {
-  auto kern = k_zalloc_tile<SZ, ZT_, LEAN_>;
-  if (h->z_attr_kernel != (const void*)kern) {
-    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    h->z_attr_kernel = (const void*)kern;
-  }
-  const ZArgs za = zargs(h);
-  hipLaunchKernelGGL(kern, dim3(h->z_grid), dim3(ZT_), h->z_lds, h->stream, za, h->dMhatZ, t, h->ztg);
-  hipLaunchKernelGGL(k_colmetrics<256>, dim3((h->cfg.G + 3) / 4), dim3(256), 0, h->stream, za, (const double*)h->dMhatZ);
-  if (h->ztg.dbg) {                                        // BNMF_ZTDBG: section cycles (100 MHz s_memtime ticks) per launch
-    unsigned long long v[8];
-    hipStreamSynchronize(h->stream);
-    hipMemcpy(v, h->ztg.dbg, sizeof v, hipMemcpyDeviceToHost);
-    hipMemset(h->ztg.dbg, 0, sizeof v);
-    if (v[0]) fprintf(stderr, "[ztile t=%u] waves %llu grid %d w %d lds %zu  per wave: phase1 %.1f  phase2 %.1f  flush %.1f  columns %.1f  kernel %.1f (s_memtime ticks)\n",
-                      t, v[0], h->z_grid, h->z_zw, h->z_lds, (double)v[1] / v[0], (double)v[2] / v[0], (double)v[3] / v[0], (double)v[4] / v[0], (double)v[5] / v[0]);
-  }
-  return 0;
-}
-template <bool SZ, int ZT_>
-static int launch_zalloc_t(bnmf_handle* h, uint32_t t) {
-  if (h->z_tile) return (h->z_lean && ZT_ == 1024) ? launch_ztile<SZ, ZT_, (ZT_ == 1024)>(h, t) : launch_ztile<SZ, ZT_, false>(h, t);
-  if (!h->z_reg) return launch_z(h, t, k_zalloc<SZ, ZT_>, h->dev, ZT_);
-#ifdef BNMF_DIAG
-  if (h->z_ablate) return launch_zreg_t<SZ, ZT_, true>(h, t);   // the DIAG instantiation honours BNMF_ABLATE
-#endif
-  return launch_zreg_t<SZ, ZT_, false>(h, t);
-}
-static int zs_prio() { static const int v = getenv("BNMF_ZSPRIO") ? atoi(getenv("BNMF_ZSPRIO")) : 1; return v; }   // A/B: 0 = the allocation kernel at default issue priority
-// where the item records of iteration t go (save_Z on the sorted schedule): the sample's slot of the record ring, or the one buffer
-static uint32_t* zs_rec_at(const bnmf_handle* h, uint32_t t) {
-  if (!h->dZsRec) return nullptr;
-  return h->dZsRecRing ? h->dZsRecRing + (size_t)((t - 1) % (uint32_t)h->wcap) * h->zs_recwords : h->dZsRec;
-}
-// Z[k, n, g] of iteration t from its records into h->dZ (main stream)
-static void launch_zexpand(bnmf_handle* h, uint32_t t) {
-  const ZSArgs sa{zargs(h), h->dZsItems, h->dZsBlocks, h->dZsCols, h->dZsM, h->zs_it16, h->zs_qmax, zs_rec_at(h, t), nullptr, 0, 0, h->dZsProf};
-  hipLaunchKernelGGL(k_zexpand, dim3(h->zsg.nblocks), dim3(ZX_T), h->zx_lds, h->stream, sa, h->zx_cols);
-  h->z_expanded_iter = (int)t;
-}
-static int ensure_Z(bnmf_handle* h) {
-  if (!h->z_sort || !h->dZsRec || !h->cfg.save_Z || h->iter < 1 || h->z_expanded_iter == h->iter) return 0;
-  HIPCHK(hipSetDevice(h->device));
-  launch_zexpand(h, (uint32_t)h->iter);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-template <int ZT_>
-static int launch_zsort_t(bnmf_handle* h, uint32_t t) {
-  const ZSArgs sa{zargs(h), h->dZsItems, h->dZsBlocks, h->dZsCols, h->dZsM, h->zs_it16, h->zs_qmax, zs_rec_at(h, t), h->dZsMh + (size_t)(t % 3u) * h->cfg.K * h->cfg.G, zs_prio(), h->zs_shared ? 1 : 0, h->dZsProf};
-  auto go = [&](auto kern) -> int {
-    if (h->z_attr_kernel != (const void*)kern) {
-      HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      h->z_attr_kernel = (const void*)kern;
-    }
-    hipLaunchKernelGGL(kern, dim3(h->zsg.nblocks), dim3(ZT_), h->zs_lds, h->stream, sa, t, h->zsg);
-    return 0;
-  };
-#ifdef BNMF_FASTBUILD   /* builder's experiment builds only (one allocation kernel: the metric configuration's): never the product */
-  if (h->zs_nblk != 4) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only N = 16..20");
-  return h->zs_pk ? go(k_zalloc_sort<ZT_, 4, true>) : go(k_zalloc_sort<ZT_, 4, false>);
-#else
-  if (h->zs_pk) switch (h->zs_nblk) {
-    case 1: return go(k_zalloc_sort<ZT_, 1, true>);
-    case 2: return go(k_zalloc_sort<ZT_, 2, true>);
-    case 3: return go(k_zalloc_sort<ZT_, 3, true>);
-    case 4: return go(k_zalloc_sort<ZT_, 4, true>);
-    default: return go(k_zalloc_sort<ZT_, 5, true>);
-  }
-  switch (h->zs_nblk) {
-    case 1: return go(k_zalloc_sort<ZT_, 1, false>);
-    case 2: return go(k_zalloc_sort<ZT_, 2, false>);
-    case 3: return go(k_zalloc_sort<ZT_, 3, false>);
-    case 4: return go(k_zalloc_sort<ZT_, 4, false>);
-    default: return go(k_zalloc_sort<ZT_, 5, false>);
-  }
-#endif
-}
-static int launch_zsort(bnmf_handle* h, uint32_t t) {
-#ifdef BNMF_FASTBUILD
-  if (h->zs_w == 14) return launch_zsort_t<896>(h, t);
-  if (h->zs_w != 12) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only 12 or 14 waves");
-  return launch_zsort_t<768>(h, t);
-#else
-  switch (h->zs_w) {
-    case 16: return launch_zsort_t<1024>(h, t);
-    case 14: return launch_zsort_t<896>(h, t);
-    case 12: return launch_zsort_t<768>(h, t);
-    case 8: return launch_zsort_t<512>(h, t);
-    case 6: return launch_zsort_t<384>(h, t);
-    default: return launch_zsort_t<256>(h, t);
-  }
-#endif
-}
-static int launch_zstep(bnmf_handle* h, uint32_t t) {
-  const ZPArgs pa{zargs(h), h->dZpItems, h->zp_it16 ? 1 : 0, h->dZpWgs, h->dZpBatches, h->dZpSteps, h->dZpCols};
-  auto go = [&](auto kern) -> int {
-    if (h->z_attr_kernel != (const void*)kern) {
-      HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      h->z_attr_kernel = (const void*)kern;
-    }
-    hipLaunchKernelGGL(kern, dim3(h->zpg.nwg), dim3(h->zp_ns * 64), h->zp_lds, h->stream, pa, t, h->zpg);
-    return 0;
-  };
-  return h->zp_gbp == 40 ? go(k_zalloc_step<4, 40, 8>) : go(k_zalloc_step<4, 32, 8>);
-}
-static int launch_zalloc(bnmf_handle* h, uint32_t t) {
-  if (h->z_sort) {
-    if (int rc = launch_zsort(h, t)) return rc;
-    // save_Z: the items' records ARE the sample (zs_rec_at); Z is expanded from them when it is read (ensure_Z, bnmf_window)
-    if (h->cfg.save_Z && h->zs_eager) launch_zexpand(h, t);
-    return 0;
-  }
-  if (h->z_step) return launch_zstep(h, t);
-  const bool sz = h->cfg.save_Z != 0;
-#ifdef BNMF_FASTBUILD
-  if (h->z_zw != 16) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only 16 waves");
-  return sz ? launch_zalloc_t<true, 1024>(h, t) : launch_zalloc_t<false, 1024>(h, t);
-#else
-  switch (h->z_zw) {
-    case 16: return sz ? launch_zalloc_t<true, 1024>(h, t) : launch_zalloc_t<false, 1024>(h, t);
-    case 8: return sz ? launch_zalloc_t<true, 512>(h, t) : launch_zalloc_t<false, 512>(h, t);
-    case 6: return sz ? launch_zalloc_t<true, 384>(h, t) : launch_zalloc_t<false, 384>(h, t);
-    case 4: return sz ? launch_zalloc_t<true, 256>(h, t) : launch_zalloc_t<false, 256>(h, t);
-    case 2: return sz ? launch_zalloc_t<true, 128>(h, t) : launch_zalloc_t<false, 128>(h, t);
-    default: return sz ? launch_zalloc_t<true, 64>(h, t) : launch_zalloc_t<false, 64>(h, t);
-  }
-#endif
-}
-// sample_R then sample_An for n = 1..N (R/sample_params.R:67-74): one persistent launch for the N sequential updates
-// row >= 0 (Gibbs sweep): the kernel also records A, R and sum(A) of the iteration (k_sumA's work)
-static void launch_rank(bnmf_handle* h, uint32_t t, hipEvent_t stop = nullptr, int row = -1) {
-  const int N = h->cfg.N;
-  const int NB = (h->cfg.G + RK_MAXC - 1) / RK_MAXC;
-  const size_t lds = (3 * (size_t)N + 1) * sizeof(double);            // A, sample_R weights, sample_An uniforms
-  const RecDst rr = row >= 0 ? rec_at(h, t, fused_rec(h)) : RecDst{};
-  auto go = [&](auto kern) {
-    hipExtLaunchKernelGGL(kern, dim3(h->rank_grid), dim3(h->rank_half ? RK_TH : RK_T), (uint32_t)lds, h->stream, nullptr, stop, 0, h->dev, t, (unsigned long long*)h->dRankCol, NB, h->dErr + 1, h->dRankMhat, (unsigned long long*)h->dRankDbg, row, rr.A, rr.R);
-  };
-  const bool nrm = h->cfg.likelihood == BNMF_NORMAL;
-  if (h->rank_half) { if (nrm) go(k_rank_sweep<true, true, true>); else go(k_rank_sweep<true, false, true>); }
-  else if (h->rank_reg) { if (nrm) go(k_rank_sweep<true, true>); else go(k_rank_sweep<true, false>); }
-  else { if (nrm) go(k_rank_sweep<false, true>); else go(k_rank_sweep<false, false>); }
-}
-// ids recorded per iteration (names(self$params) + names(self$prior_params), R/bayesNMF_sampler.R:245-252)
-static std::vector<int> recorded_ids(const bnmf_handle* h) {
-  std::vector<int> ids = {BNMF_P, BNMF_E, BNMF_A, BNMF_R};
-  if (h->cfg.prior == BNMF_GAMMA) ids.insert(ids.end(), {BNMF_ALPHA_P, BNMF_BETA_P, BNMF_ALPHA_E, BNMF_BETA_E});
-  else if (h->cfg.prior == BNMF_EXPONENTIAL) ids.insert(ids.end(), {BNMF_LAMBDA_P, BNMF_LAMBDA_E});
-  else ids.insert(ids.end(), {BNMF_MU_P, BNMF_SIGMASQ_P, BNMF_MU_E, BNMF_SIGMASQ_E});
-  if (h->cfg.MH) ids.insert(ids.end(), {BNMF_ACC_P, BNMF_ACC_E});
-  if (h->cfg.likelihood == BNMF_NORMAL) ids.push_back(BNMF_SIGMASQ);
-  return ids;
-}
-static int ensure_rings(bnmf_handle* h) {
-  if (h->cfg.window <= 0) return 0;
-  h->wcap = h->cfg.window + 1;
-  for (int id : recorded_ids(h)) {
-    Arr& a = h->arr[id];
-    if (!a.ring) if (int rc = ring_alloc(h->device, (size_t)h->wcap * id_len(h, id) * sizeof(double), &a.ring)) return rc;
-  }
-  if (h->dZ && h->z_sort && h->dZsRec) {                   // samples$Z on the sorted schedule: a ring of item records (zs_rec_at)
-    if (!h->dZsRecRing) {
-      const double gb = (double)h->wcap * (double)h->zs_recwords * 4.0 / 1e9;
-      const char* e = getenv("BNMF_ZRING_GB");
-      if (gb <= (e ? atof(e) : 32.0)) HIPCHK(dmalloc(&h->dZsRecRing, (size_t)h->wcap * h->zs_recwords * sizeof(uint32_t)));
-    }
-  } else if (h->dZ && !h->zring) {                         // samples$Z (R/bayesNMF_sampler.R:245-252): K*N*G ints per kept sample
-    const double gb = (double)h->wcap * (double)id_len(h, BNMF_Z) * 4.0 / 1e9;
-    const char* e = getenv("BNMF_ZRING_GB");
-    if (gb <= (e ? atof(e) : 32.0)) HIPCHK(dmalloc(&h->zring, (size_t)h->wcap * id_len(h, BNMF_Z) * sizeof(int32_t)));
-  }
-  return 0;
-}
-static void record_Z(bnmf_handle* h, uint32_t t) {
-  if (!h->zring) return;                                   // (sorted schedule: the allocation kernel wrote the sample's records into its ring slot)
-  const size_t len = id_len(h, BNMF_Z);
-  hipMemcpyAsync(h->zring + (size_t)((t - 1) % (uint32_t)h->wcap) * len, h->dZ, len * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream);
-}
-// the Gibbs sweep (Poisson, no MH) records inside its producers: k_pdraw (P, and A, R when the rank is fixed), k_edraw (E),
-// k_side (prior parameters), k_sumA (A, R when the rank is learned).  The MH / Normal sweeps copy with k_record.
-static bool fused_rec(const bnmf_handle* h) { return h->cfg.window > 0 && !h->cfg.MH && h->cfg.likelihood == BNMF_POISSON; }
-static double* ring_at(const bnmf_handle* h, int id, uint32_t t) {
-  const Arr& a = h->arr[id];
-  return a.ring ? a.ring + (size_t)((t - 1) % (uint32_t)h->wcap) * id_len(h, id) : nullptr;
-}
-static RecDst rec_at(const bnmf_handle* h, uint32_t t, bool on) {
-  RecDst r{};
-  if (!on || h->wcap <= 0) return r;
-  r.P = ring_at(h, BNMF_P, t); r.E = ring_at(h, BNMF_E, t); r.A = ring_at(h, BNMF_A, t); r.R = ring_at(h, BNMF_R, t);
-  static const int PP[3][4] = {{BNMF_MU_P, BNMF_SIGMASQ_P, BNMF_MU_E, BNMF_SIGMASQ_E},      // indexed by the prior enum
-                               {BNMF_LAMBDA_P, -1, BNMF_LAMBDA_E, -1},
-                               {BNMF_ALPHA_P, BNMF_BETA_P, BNMF_ALPHA_E, BNMF_BETA_E}};
-  const int* pp = PP[h->cfg.prior];
-  for (int i = 0; i < 4; ++i) r.pp[i] = pp[i] >= 0 ? ring_at(h, pp[i], t) : nullptr;
-  return r;
-}
-static int record_args(bnmf_handle* h, uint32_t t, RecArgs& ra) {
-  ra = RecArgs{}; ra.n = 0; ra.R = nullptr; ra.Rdst = nullptr;
-  const int W = h->cfg.window;
-  if (W <= 0) return 0;
-  const size_t slot = (size_t)((t - 1) % (uint32_t)h->wcap);
-  for (int id : recorded_ids(h)) {
-    Arr& a = h->arr[id];
-    const size_t len = id_len(h, id);
-    if (!a.ring) return fail(BNMF_ESTATE, "record: ring of id %d missing", id);
-    if (id == BNMF_R) { ra.R = h->dR; ra.Rdst = a.ring + slot; continue; }
-    if (!a.d) continue;
-    ra.src[ra.n] = a.d + (is_prior_param(id) ? (size_t)(t & 1u) * len : 0);
-    ra.dst[ra.n] = a.ring + slot * len;
-    ra.len[ra.n] = len;
-    ra.n++;
-  }
-  return 0;
-}
-static int launch_record(bnmf_handle* h, uint32_t t) {
-  RecArgs ra;
-  if (int rc = record_args(h, t, ra)) return rc;
-  if (ra.n > 0 || ra.Rdst) hipLaunchKernelGGL(k_record, dim3(512), dim3(256), 0, h->stream, ra);
-  return 0;
-}
-// k_reduce of iteration t: on the side stream, after the main stream has finished k_zalloc / metrics of t
-// metrics of iteration t: sum(A) now (main stream, right after the rank update); the canonical reductions later
-static void launch_reduce(bnmf_handle* h, uint32_t t, int row, Timer& tm, bool rank_wrote = false) {   // rank_wrote: k_rank_sweep recorded A, R, sum(A)
-  // sum(A) and the A-masked acceptance sum (MH / Normal sweeps, init); the Gibbs sweep's rank kernel writes sum(A), A, R itself
-  if (h->cfg.learning_rank && !rank_wrote) hipLaunchKernelGGL(k_sumA, dim3(1), dim3(64), 0, h->stream, h->dev, row, (const double*)accPn_slot(h, t), rec_at(h, t, fused_rec(h)));
-  h->red_pending = true; h->red_t = t; h->red_row = row;
-}
-// ... or at once (init, end of a run), on the MAIN stream: behind the allocation / metrics kernel of the last iteration in
-// stream order, and behind the log-prior workgroups of that iteration on the side streams through ONE event wait (they ran
-// beside the allocation kernel and are long done).  On the side stream it took two cross-stream hops in a row (side waits
-// for main, main waits for side: ~15 us each) at the end of every bnmf_run.
-static void flush_reduce(bnmf_handle* h, Timer& tm) {
-  if (!h->red_pending) return;
-  if (h->side_ev_stale) hipEventRecord(h->ev_sideP, h->side2);   // fixed-rank sweep: k_lpp / k_lpe workgroups live on side2
-  hipStreamWaitEvent(h->stream, h->ev_sideP, 0);
-  issue_reduce(h, h->red_t, h->red_row, tm, h->stream);
-  h->red_pending = false;
-}
-// P and E updates of the MH models (R/sample_params.R:56-64 with sample_Pn/_En -> *_normal -> MH_*_poisson)
-struct MhPipe { MhETail et; MhPTail pt; };
-static void launch_mh_PE(bnmf_handle* h, uint32_t t, int converged, bool poll = false, const MhPipe* pp = nullptr) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G, S = h->mh_S;
-  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
-  const int mhstep = (h->cfg.MH && converged && !normal) ? 1 : 0;
-  if (pp) {
-    if (!h->mh_pipe_valid) {                                 // first hosted sweep after init / set_array / a sweep of the other form
-      hipMemsetAsync(h->dNzE + 2 * N, 0, 4 * N * sizeof(int), h->stream);
-      hipLaunchKernelGGL(k_mh_nz, dim3(N), dim3(256), 0, h->stream, h->dev, h->dNzE + 2 * N + ((t - 1) & 1u) * N);
-      h->mh_pipe_valid = true; h->mh_prep_valid = false;
-    }
-  } else if (!h->mh_prep_valid) {                            // first sweep after init / set_array; afterwards k_mh_tail prepares them
-    hipMemsetAsync(h->dNzE, 0, 2 * N * sizeof(int), h->stream);         // nzE[N], nzP[N]
-    hipLaunchKernelGGL(k_mh_nz, dim3(N), dim3(256), 0, h->stream, h->dev, h->dNzE);
-    h->mh_prep_valid = true; h->mh_pipe_valid = false;
-  }
-  double* accP = h->arr[BNMF_ACC_P].d; double* accE = h->arr[BNMF_ACC_E].d;
-  const bool regP = S <= MHP_W;                              // one 320-column segment per wave: the row's cells stay in registers
-  const size_t ldsP = (4 * (size_t)S + 2 * N + 2 + (size_t)(PRE_W + 2) * N + ((regP && mhstep) ? (size_t)MH_CPL * MHP_T : 0)) * sizeof(double);
-  const bool pipe = pp != nullptr;                         // hosted form (sweep_mh): parity flag buffers, hosted workgroups behind the rows / the column blocks
-  int* const nzb = h->dNzE + 2 * N;                        // nzE[2][N], nzP[2][N]
-  const int* nzE_in = pipe ? nzb + ((t - 1) & 1u) * N : h->dNzE;
-  int* nzP_io = pipe ? nzb + 2 * N + (t & 1u) * N : h->dNzE + N;
-  const MhETail et = pipe ? pp->et : MhETail{};
-  const int nhostP = pipe ? mh_etail_groups(et, N, MHP_T / ES_T) : 0;
-  const size_t ldsPx = pipe ? std::max<size_t>(ldsP, MHP_T * sizeof(double)) : ldsP;
-  auto goP = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(K + nhostP), dim3(MHP_T), ldsPx, h->stream, h->dev, t, S, nzE_in, nzP_io, accP, h->dMhat, h->dMhat + (size_t)K * h->cfg.G,
-                                                poll ? SideWait{h->dFlags + 1, h->dFlags + 1, t, h->dErr} : SideWait{}, et); };
-  if (normal) { if (regP) goP(k_mh_prow<true, true, false>); else goP(k_mh_prow<true, false, false>); }
-  else if (mhstep) { if (regP) goP(k_mh_prow<false, true, true>); else goP(k_mh_prow<false, false, true>); }
-  else { if (regP) goP(k_mh_prow<false, true, false>); else goP(k_mh_prow<false, false, false>); }
-  int grid = (G + 3) / 4; if (grid > 2048) grid = 2048;
-  if (h->mhe16) {                                          // several columns per wave
-    // lanes per column: 16 for the Gibbs-only sweep, 32 with the MH step (measured at config 3: 117 / 126 us and 276 / 205 us)
-    const int gw = h->mhe_gw ? h->mhe_gw : (mhstep ? 32 : 16), cpw = 64 / gw;
-    int g16 = ((G + cpw - 1) / cpw + 3) / 4; if (g16 > 2048) g16 = 2048;
-    const size_t lds16 = (4 * (size_t)cpw * N * (1 + PRE_W) + 2 * (size_t)N) * sizeof(double);
-    const MhPTail pt = pipe ? pp->pt : MhPTail{};
-    const int nhostE = pipe ? mh_ptail_blocks(pt, N, h->cfg.MH) : 0;
-    const size_t lds16x = pipe ? std::max<size_t>(lds16, RT * sizeof(double)) : lds16;
-    int* nzE_set = pipe ? nzb + (t & 1u) * N : nullptr;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(g16 + nhostE), dim3(MHE_T), lds16x, h->stream, h->dev, t, (const int*)nzP_io, accE, 0, nzE_set, g16, pt); };
-    if (normal) {                                          // the Normal forms: fp64 data in the registers, no MH step
-      if (K <= 96 && !h->mhe_k128) { if (gw == 16) go(k_mh_ecol16<false, false, 16, 96, true>); else go(k_mh_ecol16<false, false, 32, 96, true>); }
-      else if (gw == 16) go(k_mh_ecol16<false, false, 16, MHE16_KMAX, true>);
-      else go(k_mh_ecol16<false, false, 32, MHE16_KMAX, true>);
-    } else if (K <= 96 && !h->mhe_k128) {                  // register arrays for 96 rows (BNMF_MHE_K128=1: the 128-row form)
-      if (gw == 16) { if (mhstep) go(k_mh_ecol16<false, true, 16, 96>); else go(k_mh_ecol16<false, false, 16, 96>); }
-      else { if (mhstep) go(k_mh_ecol16<false, true, 32, 96>); else go(k_mh_ecol16<false, false, 32, 96>); }
-    } else if (gw == 16) { if (mhstep) go(k_mh_ecol16<false, true, 16>); else go(k_mh_ecol16<false, false, 16>); }
-    else { if (mhstep) go(k_mh_ecol16<false, true, 32>); else go(k_mh_ecol16<false, false, 32>); }
-  } else if (normal)
-  hipLaunchKernelGGL((k_mh_ecol<false, true>), dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)(h->dNzE + N), accE, 0);
-  else
-  hipLaunchKernelGGL(k_mh_ecol<false>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, mhstep, (const int*)(h->dNzE + N), accE, 0);
-}
-static int launch_mh_metrics(bnmf_handle* h, uint32_t t, bool cells, bool with_record = false, bool with_side = false) {   // with_record: record_sample inside k_mh_tail; with_side: and the hyper sweep of t + 1
-  const int draw_sig = h->cfg.likelihood == BNMF_NORMAL ? 1 : 0;
-  if (draw_sig) cells = true;                 // sigmasq is drawn after R, A (R/sample_params.R:86-88) in the metrics pass
-  const int N = h->cfg.N, G = h->cfg.G;
-  if (cells) {
-    if (h->mhe16) {
-      const int gw = h->mhe_gw ? h->mhe_gw : 16, cpw = 64 / gw;
-      int g16 = ((G + cpw - 1) / cpw + 3) / 4; if (g16 > 2048) g16 = 2048;
-      const size_t lds16 = (4 * (size_t)cpw * N * (1 + PRE_W) + 2 * (size_t)N) * sizeof(double);
-      const bool k96 = h->cfg.K <= 96 && !h->mhe_k128;
-      auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{}); };
-      if (draw_sig) {                                        // the Normal forms (fp64 data)
-        if (gw == 16 && k96) go(k_mh_ecol16<true, false, 16, 96, true>);
-        else if (gw == 16) go(k_mh_ecol16<true, false, 16, MHE16_KMAX, true>);
-        else if (k96) go(k_mh_ecol16<true, false, 32, 96, true>);
-        else go(k_mh_ecol16<true, false, 32, MHE16_KMAX, true>);
-      } else if (gw == 16 && k96) hipLaunchKernelGGL((k_mh_ecol16<true, false, 16, 96>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
-      else if (gw == 16) hipLaunchKernelGGL((k_mh_ecol16<true, false, 16>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
-      else if (k96) hipLaunchKernelGGL((k_mh_ecol16<true, false, 32, 96>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
-      else hipLaunchKernelGGL((k_mh_ecol16<true, false, 32>), dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
-    } else {
-      int grid = (G + 3) / 4; if (grid > 2048) grid = 2048;
-      if (draw_sig) hipLaunchKernelGGL((k_mh_ecol<true, true>), dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
-      else hipLaunchKernelGGL(k_mh_ecol<true>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
-    }
-  }
-  // log-priors and acceptance sums, (for the next iteration's P sweep) Et, nzE, nzP = 0, and record_sample: one launch
-  RecArgs ra{};
-  if (with_record) { if (int rc = record_args(h, t, ra)) return rc; }
-  const int nrec = (ra.n > 0 || ra.Rdst) ? 256 : 0;
-  // the canonical reductions of the iteration BEFORE ride in this launch when the hyper sweep runs on the main stream (launch_side_main):
-  // as a kernel of their own on the side stream nothing ordered the writers of their slot, three iterations on, behind them
-  RedSlots rs{};
-  if (h->red_pending && h->mh_side_main) {
-    Dev dr = h->dev;
-    set_slot(h, dr, h->red_t);
-    rs = RedSlots{dr.colsse, dr.colll, dr.colkl, dr.lpE_part, dr.lpPn, accPn_slot(h, h->red_t), accEp_slot(h, h->red_t), h->red_row, 1};
-    h->red_pending = false;
-  }
-  SideInTail sx{};
-  if (with_side) {                                           // launch_side_main's kernel as the first blocks of this one
-    const int nbP = (int)(((size_t)h->cfg.K * N + RT - 1) / RT), nbE = (int)(((size_t)N * G + RT - 1) / RT);
-    sx = SideInTail{N + nbP + nbE, nbP, t + 1, rec_at(h, t + 1, fused_rec(h))};
-    h->flags_valid = false; h->side_valid = true; h->side_main = true;
-  }
-  hipLaunchKernelGGL(k_mh_tail, dim3(sx.n + 2 * N + h->nblkE + nrec + (rs.on ? (h->cfg.MH ? 5 : 4) : 0)), dim3(ES_T), 0, h->stream, h->dev, t, (const double*)h->arr[BNMF_ACC_P].d, accPn_slot(h, t),
-                     (const double*)h->arr[BNMF_ACC_E].d, accEp_slot(h, t), h->dNzE, h->dNzE + N, h->nblkE, ra, nrec, rs, sx);
-  h->mh_prep_valid = true;
-  return 0;
-}
-// record_sample's arrays of iteration t in two groups: what the row sweep of t + 1 rewrites (P, its prior parameters of t, its acceptance
-// rates: copied beside the column sweep of t) and the rest (copied beside the row sweep of t + 1)
-static int record_args_split(bnmf_handle* h, uint32_t t, RecArgs& raP, RecArgs& raE) {
-  RecArgs ra;
-  if (int rc = record_args(h, t, ra)) return rc;
-  raP = RecArgs{}; raE = RecArgs{};
-  raE.R = ra.R; raE.Rdst = ra.Rdst;
-  const int pids[] = {BNMF_P, BNMF_ACC_P, BNMF_MU_P, BNMF_SIGMASQ_P, BNMF_LAMBDA_P, BNMF_ALPHA_P, BNMF_BETA_P};
-  for (int j = 0; j < ra.n; ++j) {
-    bool isP = false;
-    for (int id : pids) { const Arr& a = h->arr[id]; if (a.ring && ra.dst[j] >= a.ring && ra.dst[j] < a.ring + (size_t)h->wcap * id_len(h, id)) isP = true; }
-    RecArgs& o = isP ? raP : raE;
-    o.src[o.n] = ra.src[j]; o.dst[o.n] = ra.dst[j]; o.len[o.n] = ra.len[j]; o.n++;
-  }
-  return 0;
-}
-static MhETail mh_etail_args(bnmf_handle* h, uint32_t te, uint32_t t_next, int& rc) {   // the E side of iteration te (0: none pending); t_next: the iteration of the next column sweep
-  const int N = h->cfg.N;
-  MhETail et{};
-  rc = 0;
-  et.nz_zero = h->dNzE + 2 * N + (t_next & 1u) * N;
-  if (!te) return et;
-  RecArgs raP;
-  if ((rc = record_args_split(h, te, raP, et.ra))) return et;
-  et.on = 1; et.t = te;
-  et.nbE = (int)(((size_t)N * h->cfg.G + RT - 1) / RT); et.nblkE = h->nblkE;
-  et.nrec = (et.ra.n > 0 || et.ra.Rdst) ? 128 : 0;
-  et.accE = h->arr[BNMF_ACC_E].d; et.accE_part = accEp_slot(h, te); et.lpE_part = h->dlpE + (size_t)(te % 3u) * h->nblkE;
-  return et;
-}
-// the E side of the last iteration of a call: no row sweep behind it
-static int flush_mh_etail(bnmf_handle* h) {
-  if (!h->mh_etail_pending) return 0;
-  int rc = 0;
-  const MhETail et = mh_etail_args(h, h->mh_etail_pending, h->mh_etail_pending + 1, rc);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_mh_etail, dim3(mh_etail_groups(et, h->cfg.N, 4)), dim3(1024), 0, h->stream, h->dev, et);
-  h->mh_etail_pending = 0;
-  return 0;
-}
-// The hosted form of the sweep (Poisson MH models at fixed rank, k_mh_ecol16): two launches per iteration, k_mh_tail's work inside them (mh.h)
-static int sweep_mh_pipe(bnmf_handle* h, int row, int converged, Timer& tm) {
-  h->iter += 1;
-  const uint32_t t = (uint32_t)h->iter;
-  const int N = h->cfg.N;
-  use_slot(h, t);
-  if (!h->side_valid) launch_side(h, t, tm);              // first sweep after init / set_array: the prior parameters of t on the side streams
-  if (!h->side_main) { refresh_side_events(h); hipStreamWaitEvent(h->stream, h->ev_side, 0); hipStreamWaitEvent(h->stream, h->ev_sideP, 0); }
-  MhPipe pp{};
-  int rc = 0;
-  pp.et = mh_etail_args(h, h->mh_etail_pending, t, rc);
-  if (rc) return rc;
-  MhPTail& pt = pp.pt;
-  pt.on = 1; pt.t = t;
-  pt.nbP = (int)(((size_t)h->cfg.K * N + RT - 1) / RT);
-  RecArgs raE;
-  if ((rc = record_args_split(h, t, pt.ra, raE))) return rc;
-  pt.nrec = pt.ra.n > 0 ? 8 : 0;
-  pt.accP = h->arr[BNMF_ACC_P].d; pt.accPn = accPn_slot(h, t);
-  pt.nblkE = h->nblkE;
-  pt.nz_zero = h->dNzE + 2 * N + 2 * N + ((t + 1) & 1u) * N;
-  if (h->red_pending) {                                    // k_reduce's work for the iteration before: its E-side sums are issued with pp.et above
-    Dev dr = h->dev;
-    set_slot(h, dr, h->red_t);
-    pt.rs = RedSlots{dr.colsse, dr.colll, dr.colkl, dr.lpE_part, dr.lpPn, accPn_slot(h, h->red_t), accEp_slot(h, h->red_t), h->red_row, 1};
-    h->red_pending = false;
-  }
-  dbg_delay_main(h);
-  launch_mh_PE(h, t, converged, false, &pp);
-  dbg_delay_main(h);
-  h->mh_etail_pending = t;
-  h->flags_valid = false; h->side_valid = true; h->side_main = true;
-  launch_reduce(h, t, row, tm);
-  return 0;
-}
-static int sweep_mh(bnmf_handle* h, int row, int converged, Timer& tm) {
-  if (h->mh_pipe && !tm.on) return sweep_mh_pipe(h, row, converged, tm);
-  if (int rc = flush_mh_etail(h)) return rc;
-  h->iter += 1;
-  const uint32_t t = (uint32_t)h->iter;
-  use_slot(h, t);
-  if (!h->side_valid) launch_side(h, t, tm);
-  // prior parameters of iteration t: in the steady state the P-row kernel polls the flag k_side publishes (a stream wait is a
-  // barrier packet: ~16 us of bubble per iteration here); after init / set_array / in profile mode a stream wait
-  const bool on_main = h->side_main;                       // the hyper sweep of t ran on this stream (launch_side_main): nothing to wait for
-  const bool poll = !on_main && h->flags_valid && !tm.on && !h->serial;
-  if (!poll && !on_main) { refresh_side_events(h); hipStreamWaitEvent(h->stream, h->ev_side, 0); hipStreamWaitEvent(h->stream, h->ev_sideP, 0); }
-  dbg_delay_main(h);
-  tm.begin(KN_MH, h->stream); launch_mh_PE(h, t, converged, poll); tm.end(KN_MH, h->stream);
-  dbg_delay_main(h);
-  // the hyper sweep of t + 1: on the main stream — inside k_mh_tail below (its own launch in profile mode, which times it) — or on the side stream
-  const bool side_in_tail = h->mh_side_main && !tm.on && h->mh_side_tail;
-  if (side_in_tail) {} else if (h->mh_side_main) launch_side_main(h, t + 1, tm); else launch_side(h, t + 1, tm, !tm.on);
-  if (h->cfg.learning_rank) { tm.begin(KN_RANK, h->stream); launch_rank(h, t); tm.end(KN_RANK, h->stream); }
-  // record_sample rides in k_mh_tail: after sample_sigmasq, like record_sample (:279) after sample_params (:276)
-  tm.begin(KN_OTHER, h->stream); if (int rc = launch_mh_metrics(h, t, h->cfg.learning_rank != 0, true, side_in_tail)) return rc; tm.end(KN_OTHER, h->stream);
-  launch_reduce(h, t, row, tm);
-  return 0;
-}
-// Merged draw kernel + gate at the end of the allocation kernel (k_draw, zalloc_reg.h): pays when the allocation kernel is long
-// enough to cover the side streams' kernels that its last lane waits for: 107 -> 92.5 us per iteration at K = 96, G = 10,000, 59.4 -> 52.7 at
-// G = 3,000, but 45.2 -> 51.1 us at G = 2,000, where they outlast the kernel and the gate puts them on the main stream's path.
-// BNMF_GATE=0 / 1 forces it off / on (diagnostics).
-static bool gate_enabled(const bnmf_handle* h) {
-  if (h->gate_forced >= 0) return h->gate_forced != 0;
-  // tools/gatesize.py (us per iteration without / with, K = 96, N = 20, recording on).  Round 3: 45.2 / 51.1 at G = 2,000; 59.4 / 52.7 at G = 3,000;
-  // 107 / 92.5 at G = 10,000 -> from 250,000 cells.  Round 5 (the sorted schedule without metric tasks, the two draw kernels' and the side
-  // kernels' chains shortened): 48.3 / 55.4 at G = 3,000; 56.4 / 58.9 at 4,000; 63.6 / 59.3 at 5,000; 72.4 / 67.0 at 7,000; 85.9 / 84.1 at
-  // 10,000 -> the crossover has moved up; with the quads per item chosen per data set (build_zsort): 45.5 / 52.9 at G = 3,000; 49.0 / 54.3 at 4,000;
-  // 59.8 / 60.6 at 5,000; 72.7 / 68.9 at 7,000; 85.6 / 83.5 at 10,000
-  return (size_t)h->cfg.K * h->cfg.G >= 550000;
-}
-static int sweep(bnmf_handle* h, int row, Timer& tm) {
-  h->iter += 1;
-  const uint32_t t = (uint32_t)h->iter;
-  use_slot(h, t);
-  const bool rec = fused_rec(h);
-  if (!h->side_valid) launch_side(h, t, tm);               // first sweep after init / set_array
-  // The log-prior kernel of iteration t-1 (k_lpe, side stream) is ordered only behind its own inputs, not before this
-  // iteration's k_edraw.  With recording on it reads E_{t-1} from the ring; without a ring E is double-buffered: this k_edraw
-  // writes the buffer that held E_{t-2}.  Nothing below reads E_{t-1}: the draws use ZsumK / Psum / Esum, everything after
-  // k_edraw works on E_t.  (The P side needs nothing: k_lpp precedes Esum, whose flag releases k_pdraw.)
-  if (!lpe_from_ring(h)) {
-    if (!h->E_alt) {
-      HIPCHK(dmalloc(&h->E_alt, (size_t)h->cfg.N * h->cfg.G * sizeof(double)));
-      HIPCHK(hipMemsetAsync(h->E_alt, 0, (size_t)h->cfg.N * h->cfg.G * sizeof(double), h->stream));
-    }
-    std::swap(h->arr[BNMF_E].d, h->E_alt);
-    h->dev.E = h->arr[BNMF_E].d;
-  }
-  // prior parameters + Esum of iteration t: in the steady state k_pdraw polls the flags their kernels publish (no barrier
-  // packet on the main stream); after init / set_array / in profile mode a stream wait
-  const bool poll = h->flags_valid && !tm.on && !h->serial;
-  if (!poll) { refresh_side_events(h); hipStreamWaitEvent(h->stream, h->ev_side, 0); }
-  dbg_delay_main(h);
-  if (tm.on) {                                             // profile mode: one kernel at a time
-    flush_colterms(h);
-    tm.begin(KN_PDRAW, h->stream); launch_pdraw(h, t, 0, rec); tm.end(KN_PDRAW, h->stream);
-    tm.begin(KN_EDRAW, h->stream); launch_edraw(h, t, 0, rec); tm.end(KN_EDRAW, h->stream);
-    launch_side(h, t + 1, tm);
-  } else if (gate_enabled(h) && !h->cfg.learning_rank && h->z_reg && !h->z_tile && (!poll || h->z_gated_for == t)) {
-    // merged draw kernel: the allocation kernel of t-1 has waited for this iteration's hyper sweep (its gate), or the main
-    // stream has (the event wait above: first sweep after init / set_array, serial mode)
-    // workgroup width: the E elements spread over (almost) all CUs in ONE round of workgroups — 1,024-lane workgroups left
-    // 60 of 256 CUs idle at N G = 200,000 — while the workgroup count stays small (the gap to the next kernel grows with it)
-    if (!h->draw_bw) {
-      hipDeviceProp_t pr;
-      HIPCHK(hipGetDeviceProperties(&pr, h->device));
-      const size_t per_cu = ((size_t)h->cfg.N * h->cfg.G + pr.multiProcessorCount - 1) / pr.multiProcessorCount;
-      size_t bw = ((per_cu + 63) / 64) * 64 + 64;        // one wave of slack: a few CUs take two small workgroups rather than one a second round
-      h->draw_bw = (int)std::min<size_t>(DW, std::max<size_t>(256, bw));
-      if (const char* e = getenv("BNMF_DRAWBW")) { const int v = atoi(e); if (v >= 64 && v <= DW && v % 64 == 0) h->draw_bw = v; }   // diagnostics
-    }
-    const unsigned bw = (unsigned)h->draw_bw;
-    const unsigned nE = (unsigned)(((size_t)h->cfg.N * h->cfg.G + bw - 1) / bw);
-    hipExtLaunchKernelGGL(k_draw, dim3(h->cfg.N + nE), dim3(bw), 0, h->stream, nullptr, h->ev_draw, 0, h->dev, t, rec_at(h, t, rec),
-                          SideDone{h->dFlags + 5, h->dFlags + 6, (unsigned)h->cfg.N, t}, SideWait{h->dFlags + 6, h->dFlags + 6, t, h->dErr},
-                          rec_at(h, t + 1, rec), SideDone{h->dFlags, h->dFlags + 1, nE, t + 1}, h->dDrawOwn, ++h->draw_seq, h->dbg_draw_no_p);
-
-    launch_side_merged(h, t + 1, tm);
-  } else {
-    // The side work of this iteration may have been issued by launch_side_merged (the sweep before took the merged path without
-    // arming the allocation kernel's gate: first sweep after init / set_array).  Its P-side sweep then runs on `side` under flag
-    // [9], which k_pdraw does not poll ([1] was raised by k_draw, [3] covers side2 only): the main stream waits for it here, and
-    // with it launch_side_P below (released by k_pdraw's stop event) cannot overwrite the slot that sweep still reads.
-    if (poll && h->gate_f0 == 9) { hipEventRecord(h->ev_side, h->side); hipStreamWaitEvent(h->stream, h->ev_side, 0); }
-    if (h->cfg.learning_rank) flush_colterms(h);           // (fixed rank: launch_side_E below takes the column terms of t - 1 along)
-    // completion events ride on the dispatches themselves (stop events): no marker packets on the main stream
-    hipExtLaunchKernelGGL(k_pdraw, dim3(h->cfg.N), dim3(PD_T), (uint32_t)(2 * (size_t)h->cfg.K * sizeof(double)), h->stream,
-                          nullptr, h->ev_p, 0, h->dev, t, 0, 0, rec_pdraw(h, t, rec),
-                          poll ? SideWait{h->dFlags + 1, h->dFlags + 3, t, h->dErr} : SideWait{});
-    h->gate_f0 = 1;
-    if (!h->cfg.learning_rank) {
-      launch_side_P(h, t + 1);
-      hipExtLaunchKernelGGL(k_edraw, dim3(h->nblkE), dim3(ES_T), 0, h->stream, nullptr, h->ev_draw, 0, h->dev, t, 0, 0, rec_at(h, t, rec).E);
-      launch_side_E(h, t + 1, tm);                         // overlaps k_zalloc below
-    } else {
-      // rank learning: every workgroup of the rank sweep waits for all others at every factor, so a kernel sharing a CU
-      // with one of them delays the whole grid: see launch_side_early / launch_side_late
-      hipExtLaunchKernelGGL(k_edraw, dim3(h->nblkE), dim3(ES_T), 0, h->stream, nullptr, h->ev_draw, 0, h->dev, t, 0, 0, rec_at(h, t, rec).E);
-      launch_side_early(h, t + 1);
-      launch_rank(h, t, h->ev_rank, row);
-      launch_side_late(h, t + 1, tm);
-    }
-  }
-  if (h->cfg.learning_rank && tm.on) { tm.begin(KN_RANK, h->stream); launch_rank(h, t, nullptr, row); tm.end(KN_RANK, h->stream); }
-  const bool gate = gate_enabled(h) && !h->cfg.learning_rank && poll && h->z_reg && !h->z_tile;
-  h->z_gate_next = gate ? t + 1 : 0u;
-  dbg_delay_main(h);
-  tm.begin(KN_ZALLOC, h->stream);
-  if (int rc = launch_zalloc(h, t)) return rc;
-  tm.end(KN_ZALLOC, h->stream);
-  if (h->z_sort) {
-    h->ct_pending = t;
-    if (tm.on) { tm.begin(KN_OTHER, h->stream); flush_colterms(h); tm.end(KN_OTHER, h->stream); }   // profile mode: the column terms as a launch of their own ("other")
-  }
-  h->z_gated_for = h->z_gate_next; h->z_gate_next = 0;
-  record_Z(h, t);
-  launch_reduce(h, t, row, tm, h->cfg.learning_rank != 0);
-  return 0;
-}
+#include "sweep.h"   // the scheduler: launch helpers, sweep / sweep_mh / sweep_mh_pipe, run_impl
 
 extern "C" {
 
@@ -2493,22 +1330,26 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
     if (h->dRankCol) HIPCHK(hipMemset(h->dRankCol, 0, (size_t)RK_REP * 4 * 2 * (((size_t)h->cfg.G + RK_MAXC - 1) / RK_MAXC) * sizeof(double)));
     HIPCHK(hipMemset(h->dZsumK, 0, (size_t)h->cfg.N * h->cfg.G * sizeof(int32_t)));
     HIPCHK(hipMemset(h->dZsumG, 0, (size_t)h->cfg.K * h->cfg.N * sizeof(int32_t)));
-    h->side_valid = false; h->side_main = false; h->flags_valid = false; h->z_gate_next = 0; h->z_gated_for = 0; h->gate_f0 = 1;
-    h->side_ev_stale = false; h->red_on_side2 = false; h->red_pending = false; h->red_issued = false; h->mh_prep_valid = false; h->mh_pipe_valid = false; h->mh_etail_pending = 0; h->ct_pending = 0; h->z_expanded_iter = 0;
+    h->pipe = Pipe{};
     h->inited = false;
   }
   const bnmf_config& c = h->cfg;
   const int N = c.N;
   const long KN = (long)c.K * N, NG = (long)N * c.G;
-  struct Spec { int id; uint32_t var; int side; int hs, hr; };
+  // the prior parameters of iteration 1, drawn from their hyper-priors: gamma variates (k_init_gamma, from the hyper-prior pair hs, hr)
+  // or, for the truncated-normal prior, Mu / Sigmasq (k_init_tn)
+  struct Spec { int id; uint32_t var; int side; int hs, hr, is_mu; };   // hs < 0: k_init_tn
   std::vector<Spec> specs;
   if (c.prior == BNMF_GAMMA) {
     if (int rc = need_hyper(h, {BNMF_HA_P, BNMF_HB_P, BNMF_HC_P, BNMF_HD_P, BNMF_HA_E, BNMF_HB_E, BNMF_HC_E, BNMF_HD_E})) return rc;
-    specs = {{BNMF_BETA_P, BNMF_V_BETA_P, 0, BNMF_HA_P, BNMF_HB_P}, {BNMF_ALPHA_P, BNMF_V_ALPHA_P, 0, BNMF_HC_P, BNMF_HD_P},
-             {BNMF_BETA_E, BNMF_V_BETA_E, 1, BNMF_HA_E, BNMF_HB_E}, {BNMF_ALPHA_E, BNMF_V_ALPHA_E, 1, BNMF_HC_E, BNMF_HD_E}};
+    specs = {{BNMF_BETA_P, BNMF_V_BETA_P, 0, BNMF_HA_P, BNMF_HB_P, 0}, {BNMF_ALPHA_P, BNMF_V_ALPHA_P, 0, BNMF_HC_P, BNMF_HD_P, 0},
+             {BNMF_BETA_E, BNMF_V_BETA_E, 1, BNMF_HA_E, BNMF_HB_E, 0}, {BNMF_ALPHA_E, BNMF_V_ALPHA_E, 1, BNMF_HC_E, BNMF_HD_E, 0}};
   } else if (c.prior == BNMF_EXPONENTIAL) {
     if (int rc = need_hyper(h, {BNMF_HA_P, BNMF_HB_P, BNMF_HA_E, BNMF_HB_E})) return rc;
-    specs = {{BNMF_LAMBDA_P, BNMF_V_LAMBDA_P, 0, BNMF_HA_P, BNMF_HB_P}, {BNMF_LAMBDA_E, BNMF_V_LAMBDA_E, 1, BNMF_HA_E, BNMF_HB_E}};
+    specs = {{BNMF_LAMBDA_P, BNMF_V_LAMBDA_P, 0, BNMF_HA_P, BNMF_HB_P, 0}, {BNMF_LAMBDA_E, BNMF_V_LAMBDA_E, 1, BNMF_HA_E, BNMF_HB_E, 0}};
+  } else if (c.prior == BNMF_TRUNCNORMAL) {
+    if (int rc = need_hyper(h, {BNMF_HM_P, BNMF_HS_P, BNMF_HA_P, BNMF_HB_P, BNMF_HM_E, BNMF_HS_E, BNMF_HA_E, BNMF_HB_E})) return rc;
+    specs = {{BNMF_MU_P, BNMF_V_MU_P, 0, -1, -1, 1}, {BNMF_SIGMASQ_P, BNMF_V_SIGSQ_P, 0, -1, -1, 0}, {BNMF_MU_E, BNMF_V_MU_E, 1, -1, -1, 1}, {BNMF_SIGMASQ_E, BNMF_V_SIGSQ_E, 1, -1, -1, 0}};
   }
   for (const Spec& sp : specs) {
     Arr& a = h->arr[sp.id];
@@ -2518,31 +1359,15 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
     refresh_dev(h);
     HIPCHK(hipMemcpyAsync(h->dRedraw, redraw.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
     const long len = sp.side ? NG : KN;
-    const HRef hs{h->arr[sp.hs].d, h->arr[sp.hs].stride}, hr{h->arr[sp.hr].d, h->arr[sp.hr].stride};
     double* slot1 = a.d + (size_t)len;                      // iteration 1 lives in slot 1
-    if (sp.side) hipLaunchKernelGGL(k_init_gamma<1>, dim3((len + 255) / 256), dim3(256), 0, h->stream, h->dev, slot1, hs, hr, sp.var, h->dRedraw);
-    else hipLaunchKernelGGL(k_init_gamma<0>, dim3((len + 255) / 256), dim3(256), 0, h->stream, h->dev, slot1, hs, hr, sp.var, h->dRedraw);
+    auto go = [&](auto kernP, auto kernE, auto... args) {
+      auto kern = sp.side ? kernE : kernP;
+      hipLaunchKernelGGL(kern, dim3((len + 255) / 256), dim3(256), 0, h->stream, h->dev, slot1, args..., sp.var, h->dRedraw);
+    };
+    if (sp.hs >= 0) go(k_init_gamma<0>, k_init_gamma<1>, HRef{h->arr[sp.hs].d, h->arr[sp.hs].stride}, HRef{h->arr[sp.hr].d, h->arr[sp.hr].stride});
+    else go(k_init_tn<0>, k_init_tn<1>, sp.is_mu);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));   // redraw is reused by the next spec
-  }
-  if (c.prior == BNMF_TRUNCNORMAL) {
-    if (int rc = need_hyper(h, {BNMF_HM_P, BNMF_HS_P, BNMF_HA_P, BNMF_HB_P, BNMF_HM_E, BNMF_HS_E, BNMF_HA_E, BNMF_HB_E})) return rc;
-    struct TS { int id; uint32_t var; int side, is_mu; };
-    const TS ts[4] = {{BNMF_MU_P, BNMF_V_MU_P, 0, 1}, {BNMF_SIGMASQ_P, BNMF_V_SIGSQ_P, 0, 0}, {BNMF_MU_E, BNMF_V_MU_E, 1, 1}, {BNMF_SIGMASQ_E, BNMF_V_SIGSQ_E, 1, 0}};
-    for (const TS& sp : ts) {
-      Arr& a = h->arr[sp.id];
-      std::vector<int> redraw(N, 1);
-      if (a.set) redraw = a.redraw.empty() ? std::vector<int>(N, 0) : a.redraw;
-      if (int rc = ensure(h, sp.id)) return rc;
-      refresh_dev(h);
-      HIPCHK(hipMemcpyAsync(h->dRedraw, redraw.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
-      const long len = sp.side ? NG : KN;
-      double* slot1 = a.d + (size_t)len;
-      if (sp.side) hipLaunchKernelGGL(k_init_tn<1>, dim3((len + 255) / 256), dim3(256), 0, h->stream, h->dev, slot1, sp.is_mu, sp.var, h->dRedraw);
-      else hipLaunchKernelGGL(k_init_tn<0>, dim3((len + 255) / 256), dim3(256), 0, h->stream, h->dev, slot1, sp.is_mu, sp.var, h->dRedraw);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(h->stream));
-    }
   }
   const bool haveP = h->arr[BNMF_P].set, haveE = h->arr[BNMF_E].set, haveA = h->arr[BNMF_A].set;
   if (int rc = ensure(h, BNMF_P)) return rc;
@@ -2569,7 +1394,7 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
     hipLaunchKernelGGL(k_rank_Aprior, dim3((N + 63) / 64), dim3(64), 0, h->stream, h->dev, 1u);
   }
   if (c.MH || c.likelihood == BNMF_NORMAL) launch_mh_metrics(h, 1u, true);
-  else { if (int rc = launch_zalloc(h, 1u)) return rc; if (h->z_sort) { h->ct_pending = 1u; flush_colterms(h); } record_Z(h, 1u); }
+  else { if (int rc = launch_zalloc(h, 1u)) return rc; if (h->z_sort) { h->pipe.ct_pending = 1u; flush_colterms(h); } record_Z(h, 1u); }
   if (int rc = launch_record(h, 1u)) return rc;
   launch_reduce(h, 1u, 0, tm);
   flush_reduce(h, tm);
@@ -2587,105 +1412,6 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
   return 0;
 }
 
-// Two handles that learn the rank must not run on one device at the same time: each persistent rank sweep sizes its grid
-// as if it owned the device (one workgroup per CU, every workgroup waits for all others), and two half-resident grids
-// would wait for each other until their bounded spins give up.  Their calls take turns (a call is at most one block of
-// iterations between MAP checks).  Nor may a rank-learning call run beside ANY other chain's call on the device (round 4, found
-// by tools/concurrent_check.py with full-size chains): a workgroup that waits inside a kernel for its chain's side streams (the
-// allocation kernel's gate, the draw kernels' polls) holds a CU the rank sweep's grid needs, while the rank sweep's resident
-// workgroups hold the registers the side-stream kernel needs — a cycle only the time-outs broke.  Rank-learning calls take the
-// device's lock exclusively, all other calls shared.
-static int flock_retry(int fd, int op) { int rc; while ((rc = flock(fd, op)) != 0 && errno == EINTR) {} return rc; }
-static int run_impl(bnmf_handle* h, int n_iter, int converged, double* metrics, Timer& tm) {
-  if (!h) return fail(BNMF_EINVAL, "bnmf_run: null handle");
-  const bool excl = h->cfg.learning_rank != 0;
-  // The rule between the PROCESSES that share the device first (each learns nothing of the others' launches), then the one between the
-  // chains of this process — a call blocked on another process must not hold this process's gate.  Without the lock files a
-  // rank-learning call is refused (two such chains of two processes end in each other's time-outs) unless the caller has said
-  // BNMF_DEVLOCK=0: no other process uses the device.
-  struct FileTurn { int fd; ~FileTurn() { if (fd >= 0) flock(fd, LOCK_UN); } } fturn{-1};
-  if (!h->devlock_off) {
-    if (h->devlock_fd < 0 || h->devgate_fd < 0) {
-      if (excl) return fail(BNMF_ESTATE, "bnmf_run: a rank-learning chain needs its device to itself, and the device's lock files could not be opened "
-                                         "(see the warning at bnmf_create): set BNMF_LOCKDIR, or BNMF_DEVLOCK=0 if no other process uses this GPU");
-    } else {
-      int rc;
-      if (excl) { rc = flock_retry(h->devgate_fd, LOCK_EX); if (!rc) { rc = flock_retry(h->devlock_fd, LOCK_EX); flock(h->devgate_fd, LOCK_UN); } }
-      else { rc = flock_retry(h->devgate_fd, LOCK_SH); if (!rc) { flock(h->devgate_fd, LOCK_UN); rc = flock_retry(h->devlock_fd, LOCK_SH); } }
-      if (rc) return fail(BNMF_ESTATE, "bnmf_run: the device's lock file could not be taken (%s)", strerror(errno));
-      fturn.fd = h->devlock_fd;
-    }
-  }
-  struct GateTurn { DeviceGate* g; bool ex; ~GateTurn() { if (g) { if (ex) g->unlock(); else g->unlock_shared(); } } } gturn{nullptr, excl};
-  if (h->device >= 0 && h->device < 64) {
-    gturn.g = &g_dev_gate[h->device];
-    if (excl) gturn.g->lock(); else gturn.g->lock_shared();
-  }
-  if (!h->inited) return fail(BNMF_ESTATE, "bnmf_run: call bnmf_init first");
-  if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_run: an earlier call timed out inside a kernel; the handle's state is invalid, destroy it");
-  if (n_iter < 0) return fail(BNMF_EINVAL, "bnmf_run: n_iter < 0");
-  if (n_iter == 0) return 0;
-  HIPCHK(hipSetDevice(h->device));
-  if (int rc = ensure_metrics(h, (size_t)n_iter)) return rc;
-  const uint32_t t0 = (uint32_t)h->iter + 1;
-  // BNMF_RUNCLOCK=1 (diagnostics): host time of the call's phases on stderr
-  static const bool runclock = getenv("BNMF_RUNCLOCK") != nullptr;
-  const auto rc0 = std::chrono::steady_clock::now();
-  auto rc_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - rc0).count(); };
-  double rc_first = 0.0, rc_issued = 0.0, rc_tail = 0.0, rc_main = 0.0;
-  for (int i = 0; i < n_iter; ++i) {
-    if (runclock && i == 1) rc_first = rc_us();
-    if (int rc = ((h->cfg.MH || h->cfg.likelihood == BNMF_NORMAL) ? sweep_mh(h, i, h->cfg.MH ? converged : 0, tm) : sweep(h, i, tm))) return rc;
-    HIPCHK(hipGetLastError());                               // a refused launch of this iteration (bad geometry, LDS size)
-    // a bounded in-kernel wait that timed out has set its word (mapped host memory): issue nothing more, so that one stuck
-    // hand-off costs one spin bound and not one per remaining launch
-    if (((volatile int*)h->hErr)[0] | ((volatile int*)h->hErr)[1]) break;
-  }
-  if (runclock) rc_issued = rc_us();
-  const bool reduces_on_side2 = h->red_on_side2;          // fixed-rank sweep: every earlier k_reduce sits on side2, which flush_reduce's wait covers
-  flush_colterms(h);                                       // the last iteration's column terms: no draw kernel behind it in this call
-  if (int rc = flush_mh_etail(h)) return rc;              // (hosted MH sweep) the last iteration's E side: no row sweep behind it in this call
-  // Round 5: the main stream waits for EVERYTHING issued on the two side streams (a fresh event each) in front of the last reduction:
-  // when it is idle so are they, and the two host-side synchronisations of idle streams that stood below (6 us each, at the end of
-  // every call) are gone.  (flush_reduce's own wait for side2 is then a wait for an event that has fired.)
-  hipEventRecord(h->ev_z, h->side); hipStreamWaitEvent(h->stream, h->ev_z, 0);
-  hipEventRecord(h->ev_sideP, h->side2); hipStreamWaitEvent(h->stream, h->ev_sideP, 0);
-  if (h->side_ev_stale) { hipStreamWaitEvent(h->side, h->ev_sideP, 0); hipEventRecord(h->ev_side, h->side); h->side_ev_stale = false; }   // (what refresh_side_events would record)
-  flush_reduce(h, tm);
-  (void)reduces_on_side2;
-  hipLaunchKernelGGL(k_compose, dim3((n_iter + 63) / 64), dim3(64), 0, h->stream, h->dev, n_iter, t0);
-  HIPCHK(hipGetLastError());
-  std::vector<double> own;
-  if (!metrics && h->wcap > 0) { own.resize((size_t)n_iter * BNMF_NMETRIC); metrics = own.data(); }
-  if (runclock) rc_tail = rc_us();
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (runclock) rc_main = rc_us();
-  if (metrics) memcpy(metrics, h->hMetrics, (size_t)n_iter * BNMF_NMETRIC * sizeof(double));
-
-  if (runclock) fprintf(stderr, "[bnmf_run %d] first iteration issued %.1f us, all issued %.1f, tail issued %.1f, main stream idle %.1f, side streams idle %.1f\n",
-                        n_iter, rc_first, rc_issued, rc_tail, rc_main, rc_us());
-  if (h->wcap > 0 && metrics) {                             // loglik / logpost of the recorded iterations (MAP metrics are window means)
-    if (h->hist.size() != (size_t)h->wcap * 4) h->hist.assign((size_t)h->wcap * 4, std::nan(""));
-    for (int i = 0; i < n_iter; ++i) {
-      const double* r = metrics + (size_t)i * BNMF_NMETRIC;
-      double* d = h->hist.data() + (size_t)((t0 + i - 1) % (uint32_t)h->wcap) * 4;
-      d[0] = r[3]; d[1] = r[4]; d[2] = r[9]; d[3] = r[10];
-    }
-  }
-  // all three streams are idle: the time-out words (mapped host memory) are final
-  if (((volatile int*)h->hErr)[0] | ((volatile int*)h->hErr)[1]) {
-    // the kernels behind the time-out ran on inputs that were never published: P, E, the rings and the metric rows of this call
-    // are not the chain's.  The handle stays poisoned (every later call fails with BNMF_ESTATE) until it is destroyed.
-    h->poisoned = true;
-    unsigned fl[16] = {};
-    hipMemcpy(fl, h->dFlags, sizeof fl, hipMemcpyDeviceToHost);
-    if (((volatile int*)h->hErr)[0])
-      return fail(BNMF_EHIP, "bnmf_run: a kernel timed out waiting for the hyper-parameter sweep of its iteration (iteration %d; flags E-side %u, Esum %u, P-side %u, draw %u; "
-                  "serialised dispatch? set BNMF_SERIAL=1); the handle is now invalid", h->iter, fl[1], fl[3], fl[9], fl[6]);
-    return fail(BNMF_EHIP, "bnmf_run: the grid barrier of the rank sweep timed out at iteration %d (workgroups not co-resident?); the handle is now invalid", h->iter);
-  }
-  return 0;
-}
 int bnmf_run(bnmf_handle* h, int n_iter, int converged, double* metrics) {
   Timer tm{h, false};
   return run_impl(h, n_iter, converged, metrics, tm);

@@ -485,10 +485,8 @@ int bnmf_load_state(bnmf_handle* h, const char* path, int* iter_out) {
   if (h->dRankCol) HIPCHK(hipMemset(h->dRankCol, 0, (size_t)RK_REP * 4 * 2 * (((size_t)h->cfg.G + RK_MAXC - 1) / RK_MAXC) * sizeof(double)));
   HIPCHK(hipMemset(h->dDrawOwn, 0, (size_t)h->cfg.N * sizeof(unsigned)));
   h->draw_seq = 0;
-  h->side_valid = false; h->side_main = false; h->flags_valid = false; h->z_gate_next = 0; h->z_gated_for = 0; h->gate_f0 = 1;
-  h->side_ev_stale = false; h->red_on_side2 = false; h->red_pending = false; h->red_issued = false; h->mh_prep_valid = false; h->mh_pipe_valid = false;
-  h->mh_etail_pending = 0; h->ct_pending = 0;
-  h->z_expanded_iter = h->dZ ? h->iter : 0;                   // (the file's Z is the current iteration's)
+  h->pipe = Pipe{};
+  h->pipe.z_expanded_iter = h->dZ ? h->iter : 0;                   // (the file's Z is the current iteration's)
   if (h->wcap > 0 && h->hist.size() != (size_t)h->wcap * 4) h->hist.assign((size_t)h->wcap * 4, std::nan(""));
   refresh_dev(h);
   h->inited = true;

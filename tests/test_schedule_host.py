@@ -1,4 +1,4 @@
-"""CPU tests of the two static allocation schedules (api.hip plan_zsort / plan_zstep, through bnmf_test_zsort_plan /
+"""CPU tests of the two static allocation schedules (csrc/zplan.h plan_zsort / plan_zstep, through bnmf_test_zsort_plan /
 bnmf_test_zstep_plan): the plan the host would upload is decoded with plain numpy and checked against the contract the kernels
 rely on ("Contract of the sorted schedule"), for several CU counts and for the data no chain-level test feeds them:
 all-zero columns, G between one and two times the CU count, blocks without a column, large cells exported into such blocks,
