@@ -102,11 +102,13 @@ static hipError_t dfree(void* p) {
 }
 
 
+#include "zplan.h"   // Switches and the planners of bnmf_create (device-free)
+
 struct Arr { double* d = nullptr; size_t n = 0; int stride = 1; bool set = false; std::vector<int> redraw; double* ring = nullptr;
              bool slab = false; };   // slab: d points into the handle's block of scalars (a broadcast hyper-prior value), not an allocation of its own
 
 // What one sweep hands to the next: the host's record of what is in flight on the three streams (sweep.h is its only writer
-// apart from the two resets below).  Configuration chosen at bnmf_create (mh_pipe, mh_side_main, gate_forced, serial, dbg_*) is
+// apart from the two resets below).  Configuration chosen at bnmf_create (mh.pipe, mh.side_main, gate_forced, serial, dbg_*) is
 // not in here.  The default member initialisers ARE the reset values: a chain starts (bnmf_init on a used handle, bnmf_load_state)
 // with `pipe = Pipe{}` behind drained streams and cleared sync words.  "t" below is the iteration a sweep is about to run.
 //
@@ -157,6 +159,50 @@ struct Pipe {
   void invalidate_prepared() { side_valid = false; side_main = false; mh_prep_valid = false; mh_pipe_valid = false; }
 };
 
+// Which allocation kernel a Poisson handle launches: chosen once, by create_zalloc, in this order — step before tile before the sorted
+// schedule, else the wave-per-column kernel that fits.  launch_zalloc switches on it.  `reg` and `sort` are the two kinds for which
+// the register kernel was eligible (N <= 24 and its LDS fits): what the merged draw kernel asks (merged_draw_ok).  Modifiers, not
+// kinds: ZTile::lean (tile) and, in -DBNMF_DIAG builds, z_ablate (reg: the sorted schedule is then not tried).
+enum class ZKind { none /* Normal: counts are not allocated */, general /* k_zalloc */, reg /* k_zalloc_reg */, tile, step, sort };
+
+// What bnmf_create decides and acquires for one kernel family, each with its device buffers.  All of them: written by bnmf_create only
+// (create_rank, create_mh, create_zalloc, build_zsort, build_zstep below) unless a member says otherwise; a group whose kernel the
+// handle does not launch stays at its defaults (null pointers).  The planners' halves are in zplan.h.
+// The wave-per-column kernels (ZKind::reg, ::general) need no buffers of their own: ZWavePlan zw is the whole group; read by launch_z.
+// k_zalloc_tile (ZKind::tile); read by launch_ztile.  g.dbg (BNMF_ZTDBG) is a device buffer too.
+struct ZTile : ZTilePlan { double* dMhat = nullptr; };
+// k_zalloc_sort (ZKind::sort: stats mode, N <= 24) — the static schedule built from M; read by launch_zsort, launch_zexpand, ensure_Z,
+// zs_rec_at, the column terms (colterms.h launches in sweep.h), bnmf_get_stat and state_io.h (records).
+struct ZSort {
+  bool pk = false, shared = false;     // two factors per word; large cells spread over the blocks: ZsumK is accumulated (atomics), the draw kernels zero it
+  ZSGeom g{}; int nblk = 0, w = 0; size_t lds = 0;
+  int it16 = 0, qmax = ZS_QMAX;        // 2-byte items; quads per item
+  int nempty = 0;                      // blocks without an own column (bnmf_get_stat 7)
+  uint32_t* dItems = nullptr; ZSBlock* dBlocks = nullptr; int* dCols = nullptr; int32_t* dM = nullptr; unsigned long long* dProf = nullptr;
+  double* dMh = nullptr;               // [3][G][K] Mhat left by k_zalloc_sort for the per-column metric terms (colterms.h)
+  // save_Z: Z is kept AS RECORDS (two 16-bit counts per word and item: 44 MB per iteration at the metric configuration against 77 MB of Z)
+  // and expanded when somebody reads it (bnmf_get_array, bnmf_window).  With a window the records of iteration t live in slot
+  // (t - 1) % wcap of dRecRing (samples$Z; made by ensure_rings at bnmf_init); eager (BNMF_ZEAGER=1, measurements): expand every iteration.
+  uint32_t *dRec = nullptr, *dRecRing = nullptr; size_t recwords = 0; bool eager = false;
+  int x_cols = 0; size_t x_lds = 0;    // k_zexpand's columns per pass and LDS bytes
+};
+// k_zalloc_step (ZKind::step: stats mode, 25 <= N <= 100, any K) — the static schedule built from M; read by launch_zstep, bnmf_get_stat.
+struct ZStep {
+  ZPGeom g{}; int ns = 0 /* waves per workgroup */, gbp = 0; size_t lds = 0; bool it16 = false;
+  uint32_t* dItems = nullptr; ZPWg* dWgs = nullptr; ZPBatch* dBatches = nullptr; ZPStep* dSteps = nullptr; int* dCols = nullptr;
+};
+// The rank sweep (learning_rank); read by launch_rank, bnmf_debug_rank; dSync / dCol are cleared where a chain starts.
+struct Rank : RankPlan { double *dCol = nullptr, *dMhat = nullptr; uint32_t* dSync = nullptr; void* dDbg = nullptr; };
+// The MH / Normal sweeps; read by sweep_mh / sweep_mh_pipe and their launch helpers (sweep.h), refresh_dev, bnmf_get_stat.
+struct Mh : MhPlan {
+  bool side_tail = true;               // BNMF_MHSIDETAIL=0 (diagnostics): the main-stream hyper sweep as a launch of its own in front of k_mh_tail
+  bool side_main = true;               // BNMF_MHSIDE=0 (diagnostics / tests): the hyper sweep on the side stream, as in round 3
+  bool e_k128 = false;                 // BNMF_MHE_K128=1 (diagnostics / tests): k_mh_ecol16's 128-row form also where K <= 96
+  int e_gw = 0;                        // BNMF_MHE_GW: lanes per column of k_mh_ecol16 (0 = by mode)
+  double *dMhat = nullptr, *dAccPn = nullptr, *dAccEpart = nullptr, *dEt = nullptr; int* dNzE = nullptr;
+  int32_t* dMt = nullptr; double* dMtf = nullptr;   // the [G][K] transpose of the data: counts, or fp64 on a Normal handle
+};
+
 struct bnmf_handle {
   bnmf_config cfg{};
   int device = 0;
@@ -164,8 +210,10 @@ struct bnmf_handle {
   hipStream_t side = nullptr;          // side stream: k_side (E part) of the next iteration (overlaps k_zalloc), k_reduce
   hipStream_t side2 = nullptr;         // second side stream: k_side P part (starts right after k_pdraw) and Esum
   hipEvent_t ev_draw = nullptr, ev_side = nullptr, ev_sideP = nullptr, ev_p = nullptr, ev_z = nullptr, ev_red = nullptr, ev_rank = nullptr;
-  bool mh_side_tail = true;            // BNMF_MHSIDETAIL=0 (diagnostics): the main-stream hyper sweep as a launch of its own in front of k_mh_tail
-  bool mh_side_main = true;            // BNMF_MHSIDE=0 (diagnostics / tests): the MH / Normal sweeps' hyper sweep on the side stream, as in round 3
+  // Every pooled device block made for the handle (hmalloc), in the order made: bnmf_destroy frees the list, hfree takes a block out
+  // early (one grown on demand that is being replaced).  Not in here, released by name in bnmf_destroy: Arr::d and Arr::ring, the three
+  // hipHostMalloc blocks (hMetrics, hErr, hStage), events, streams, the lock files.
+  std::vector<void*> owned;
   int gate_forced = -1;                // BNMF_GATE at bnmf_create: 0 / 1 forces the merged draw kernel off / on, else by size
   int draw_bw = 0;                     // lanes per workgroup of the merged draw kernel (chosen at the first launch)
   double* dScal = nullptr;              // [BNMF_ID_MAX] broadcast scalars of bnmf_set_array (hyper-prior values given as one number)
@@ -175,10 +223,7 @@ struct bnmf_handle {
   int dbg_main_delay_us = 0;           // BNMF_DEBUG_MAIN_DELAY_US (tests): a delay kernel in front of the main stream's kernels of every sweep
   int dbg_allside_delay_us = 0;        // BNMF_DEBUG_ALLSIDE_DELAY_US (tests): a delay kernel in front of EVERY kernel launched on the two side streams
   int dbg_side_delay_us = 0;           // BNMF_DEBUG_SIDE_DELAY_US (tests): a delay kernel in front of the P-side hyper sweep of launch_side_merged
-  bool mhe_k128 = false;               // BNMF_MHE_K128=1 (diagnostics / tests): k_mh_ecol16's 128-row form also where K <= 96
-  bool mhe16 = false;                  // the MH / Normal column sweep by k_mh_ecol16 (K <= 128 and its LDS fits)
   double* E_alt = nullptr;             // Gibbs sweep: the other E buffer (k_edraw of t+1 does not overwrite what k_lpe of t still reads)
-  bool mh_pipe = false;                // Poisson MH models at fixed rank through k_mh_ecol16: what followed the two sweeps is hosted BY them (mh.h; BNMF_MHPIPE=0: k_mh_tail)
   const void* z_attr_kernel = nullptr;   // allocation kernel whose dynamic-LDS limit has been raised for this handle (raise_lds_limit, sweep.h)
   Pipe pipe;                           // what one sweep hands to the next (above); reset where a chain starts: bnmf_init, bnmf_load_state
   int iter = 0;
@@ -186,40 +231,22 @@ struct bnmf_handle {
   Dev dev{};
   Arr arr[BNMF_ID_MAX];
   int32_t *dM = nullptr, *dZsumK = nullptr, *dZsumG = nullptr, *dZ = nullptr;
+  double* dMf = nullptr;               // Normal handles: the data as fp64, M's layout (dM stays unset)
   int* dR = nullptr; int* dRedraw = nullptr;
   double *dEsum = nullptr, *dPsum = nullptr, *dlpPn = nullptr, *dlpE = nullptr, *dcol = nullptr;
   double* hMetrics = nullptr;          // the metric rows live in mapped host memory (dMetrics is its device address): k_compose writes them
                                        // where the host reads them, no device-to-host copy at the end of a call
-  double *dLut = nullptr, *dTemp = nullptr, *dMetrics = nullptr, *dRaw = nullptr, *dRankCol = nullptr, *dRankMhat = nullptr;
-  uint32_t* dRankSync = nullptr; int rank_grid = 0; bool rank_reg = false, rank_half = false; void* dRankDbg = nullptr;
-  int32_t* dMt = nullptr; double* dEt = nullptr;
-  double *dMf = nullptr, *dMtf = nullptr;   // Normal handles: the data as fp64, M's layout and the [G][K] transpose (dM, dMt stay unset)
+  double *dLut = nullptr, *dTemp = nullptr, *dMetrics = nullptr, *dRaw = nullptr;
   int32_t* zring = nullptr;            // save_Z with a window: samples$Z, [wcap][K*N*G] int32 (only if it fits BNMF_ZRING_GB, default 32)
-  double *dMhat = nullptr, *dAccPn = nullptr, *dAccEpart = nullptr; int* dNzE = nullptr; int mh_S = 1; size_t mhe_lds = 0; int mhe_gw = 0;
   size_t metrics_rows = 0;
   int maxM = 0, nblkE = 0;
+  long colmax = 0;                     // largest column total of M (Poisson)
+  int n_cu = 256;
   int wcap = 0;                        // ring capacity = window + 1: the hyper sweep of iteration t+1 is issued (and, in the
                                        // Gibbs sweep, recorded) during iteration t, one slot ahead of the oldest kept sample
-  int z_grid = 0, z_zw = 8, z_ablate = 0; bool z_reg = false; size_t z_lds = 0; ZGeom zg{};
-  bool z_tile = false, z_lean = false; ZTGeom ztg{}; double* dMhatZ = nullptr;   // k_zalloc_tile (zalloc_tile.h): N > 24 / large K
-  // k_zalloc_sort (zalloc_sort.h): stats mode, N <= 24 — the static schedule built from M at bnmf_create
-  bool z_sort = false, zs_pk = false; ZSGeom zsg{}; int zs_nblk = 0, zs_w = 0; size_t zs_lds = 0; int32_t* dZsM = nullptr;
-  int zs_it16 = 0, zs_qmax = ZS_QMAX;   // 2-byte items; quads per item
-  uint32_t* dZsRec = nullptr; int zx_cols = 0; size_t zx_lds = 0;   // save_Z on the sorted schedule: the items' records, k_zexpand's columns per pass and LDS bytes
-  // Round 5: Z of the sorted schedule is kept AS RECORDS (two 16-bit counts per word and item: 44 MB per iteration at the metric configuration
-  // against 77 MB of Z) and expanded when somebody reads it (bnmf_get_array, bnmf_window): k_zexpand left the loop.  With a window the
-  // records of iteration t live in slot (t - 1) % wcap of dZsRecRing (samples$Z); zs_eager (BNMF_ZEAGER=1, measurements): expand every iteration.
-  uint32_t* dZsRecRing = nullptr; size_t zs_recwords = 0; bool zs_eager = false;
-  uint32_t* dZsItems = nullptr; ZSBlock* dZsBlocks = nullptr; int* dZsCols = nullptr; unsigned long long* dZsProf = nullptr;
-  double* dZsMh = nullptr;              // [G][K] Mhat left by k_zalloc_sort for the per-column metric terms (colterms.h)
-  long colmax = 0;                      // largest column total of M
-  bool zs_shared = false;               // the sorted schedule spreads large cells over the blocks: ZsumK is accumulated (atomics), the draw kernels zero it
-  int n_cu = 256;
-  int zs_nempty = 0;                    // blocks of the sorted schedule without an own column (bnmf_get_stat 7)
-  // k_zalloc_step (zalloc_step.h): stats mode, 25 <= N <= 100, any K — the static schedule built from M at bnmf_create
-  bool z_step = false; ZPGeom zpg{}; int zp_ns = 0 /* waves per workgroup */, zp_gbp = 0; size_t zp_lds = 0;
-  bool zp_it16 = false;                // k_zalloc_step's items as uint16
-  uint32_t* dZpItems = nullptr; ZPWg* dZpWgs = nullptr; ZPBatch* dZpBatches = nullptr; ZPStep* dZpSteps = nullptr; int* dZpCols = nullptr;
+  ZKind zkind = ZKind::none;           // the allocation kernel (above), and the groups of bnmf_create's choices
+  int z_ablate = 0;
+  ZWavePlan zw; ZTile zt; ZSort zs; ZStep zp; Rank rank; Mh mh;
   hipEvent_t ev[2 * BNMF_NKERNEL]{};
   bool have_ev = false;
   double* dMap = nullptr; size_t map_words = 0;   // scratch of bnmf_map (grown on demand)
@@ -239,6 +266,29 @@ struct bnmf_handle {
   uint64_t data_hash = 0;                         // hash of the data as the handle holds it (int32 counts, fp64 for Normal): bnmf_save_state's file header
   unsigned char* hStage = nullptr;                // two pinned halves of bnmf_save_state / bnmf_load_state (state_io.h), made at the first of them
 };
+
+// The one owner of a handle's pooled device memory: make a block and register it; make it zeroed; make it and fill it from the host.
+template <class T> static hipError_t hmalloc(bnmf_handle* h, T** out, size_t bytes) {
+  const hipError_t e = dmalloc(out, bytes);
+  if (e == hipSuccess) h->owned.push_back(*out);
+  return e;
+}
+template <class T> static hipError_t hzeroed(bnmf_handle* h, T** out, size_t bytes) {
+  const hipError_t e = hmalloc(h, out, bytes);
+  return e != hipSuccess ? e : hipMemset(*out, 0, bytes);
+}
+template <class T> static hipError_t hupload(bnmf_handle* h, T** out, const void* src, size_t bytes, size_t alloc_bytes = 0) {
+  const hipError_t e = hmalloc(h, out, alloc_bytes ? alloc_bytes : bytes);
+  return e != hipSuccess ? e : hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice);
+}
+// ... and give one up before the handle goes (a buffer grown on demand, about to be replaced by a larger one)
+template <class T> static hipError_t hfree(bnmf_handle* h, T*& p) {
+  if (!p) return hipSuccess;
+  h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), (void*)p), h->owned.end());
+  const hipError_t e = dfree(p);
+  p = nullptr;
+  return e;
+}
 
 static size_t id_len(const bnmf_handle* h, int id) {
   const size_t K = h->cfg.K, G = h->cfg.G, N = h->cfg.N;
@@ -280,10 +330,10 @@ static void refresh_dev(bnmf_handle* h) {
   d.K = c.K; d.G = c.G; d.N = c.N;
   d.prior = c.prior; d.likelihood = c.likelihood; d.MH = c.MH; d.learning_rank = c.learning_rank;
   d.rank_method = c.rank_method; d.save_Z = c.save_Z;
-  d.zsumk_accum = (h->z_tile || (h->z_sort && h->zs_shared)) ? 1 : 0;
+  d.zsumk_accum = (h->zkind == ZKind::tile || (h->zkind == ZKind::sort && h->zs.shared)) ? 1 : 0;
   d.k0 = (uint32_t)c.seed; d.k1 = (uint32_t)(c.seed >> 32) ^ c.chain_id;
   d.maxM = h->maxM;
-  d.M = h->dM; d.Mt = h->dMt; d.Mf = h->dMf; d.Mtf = h->dMtf; d.Et = h->dEt; d.R = h->dR;
+  d.M = h->dM; d.Mt = h->mh.dMt; d.Mf = h->dMf; d.Mtf = h->mh.dMtf; d.Et = h->mh.dEt; d.R = h->dR;
   d.P = h->arr[BNMF_P].d; d.E = h->arr[BNMF_E].d; d.A = h->arr[BNMF_A].d;
   d.ZsumK = h->dZsumK; d.ZsumG = h->dZsumG; d.Z = h->dZ;
   d.Alpha_p = h->arr[BNMF_ALPHA_P].d; d.Beta_p = h->arr[BNMF_BETA_P].d;
@@ -306,13 +356,12 @@ static void refresh_dev(bnmf_handle* h) {
 }
 
 // BNMF_TIMING=1 (diagnostics): wall-clock marks of bnmf_create on stderr
+static bool timing_on() { return env_set("BNMF_TIMING"); }
 struct CreateClock {
-  bool on = getenv("BNMF_TIMING") != nullptr; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  bool on = timing_on(); std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   void mark(const char* what) { if (!on) return; const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[bnmf_create] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count()); t0 = t; }
 };
 __global__ void k_set_scalar(double* p, double v) { *p = v; }
-
-#include "zplan.h"   // plan_zsort, plan_zstep: the allocation kernels' static schedules (device-free)
 
 extern "C" {
 
@@ -414,102 +463,67 @@ int bnmf_create_f64(const bnmf_config* cfg, const double* M, bnmf_handle** out) 
   return bnmf_create(cfg, mi.data(), out);
 }
 
-// build_zsort uploads what plan_zsort (zplan.h) returns
-static int build_zsort(bnmf_handle* h, const int32_t* M, int n_cu) {
+// build_zsort uploads what plan_zsort (zplan.h) returns; reg_ok: the register kernel is eligible (plan_zwave)
+static int build_zsort(bnmf_handle* h, const int32_t* M, bool reg_ok, const Switches& sw) {
   const bnmf_config& c = h->cfg;
   const size_t K = c.K, G = c.G, N = c.N;
-  h->z_sort = false;
+  ZSort& z = h->zs;
   ZSortPlan p;
-  if (int rc = plan_zsort(M, K, G, N, c.save_Z != 0, h->maxM, h->z_reg, n_cu, p)) return rc;
+  if (int rc = plan_zsort(M, K, G, N, c.save_Z != 0, h->maxM, reg_ok, h->n_cu, sw, p)) return rc;
   if (!p.ok) return 0;
-  const bool it16 = p.it16, pk = p.pk;
-  const int qmax = p.qmax, GBc = p.GBc, KP = p.KP, W = p.W, nblk = p.nblk, nb = p.nb;
-  const std::vector<ZSBlock>& blocks = p.blocks;
-  const std::vector<int>& cols = p.cols;
-  const std::vector<uint32_t>& items = p.items;
-  const std::vector<int32_t>& Mblk = p.Mblk;
-  if (it16) {
-    const std::vector<uint16_t>& i16 = p.items16;
-    HIPCHK(dmalloc(&h->dZsItems, ((i16.size() * sizeof(uint16_t) + 3) & ~(size_t)3)));
-    HIPCHK(hipMemcpy(h->dZsItems, i16.data(), i16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  } else {
-    HIPCHK(dmalloc(&h->dZsItems, items.size() * sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(h->dZsItems, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  h->zs_it16 = it16 ? 1 : 0; h->zs_qmax = qmax;
-  HIPCHK(dmalloc(&h->dZsBlocks, blocks.size() * sizeof(ZSBlock)));
-  HIPCHK(hipMemcpy(h->dZsBlocks, blocks.data(), blocks.size() * sizeof(ZSBlock), hipMemcpyHostToDevice));
-  HIPCHK(dmalloc(&h->dZsCols, cols.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(h->dZsCols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(dmalloc(&h->dZsM, Mblk.size() * sizeof(int32_t)));
-  HIPCHK(hipMemcpy(h->dZsM, Mblk.data(), Mblk.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (p.it16) HIPCHK(hupload(h, &z.dItems, p.items16.data(), p.items16.size() * sizeof(uint16_t), (p.items16.size() * sizeof(uint16_t) + 3) & ~(size_t)3));
+  else HIPCHK(hupload(h, &z.dItems, p.items.data(), p.items.size() * sizeof(uint32_t)));
+  z.it16 = p.it16 ? 1 : 0; z.qmax = p.qmax;
+  HIPCHK(hupload(h, &z.dBlocks, p.blocks.data(), p.blocks.size() * sizeof(ZSBlock)));
+  HIPCHK(hupload(h, &z.dCols, p.cols.data(), p.cols.size() * sizeof(int)));
+  HIPCHK(hupload(h, &z.dM, p.Mblk.data(), p.Mblk.size() * sizeof(int32_t)));
   // three copies, iteration t in copy t % 3 (as the per-column partial sums): the terms of t are summed beside the allocation kernel of t + 1
   // (k_side_lp of t + 2, stream side2), which is known to be over before the draw kernel of t + 3 starts — the allocation kernel of t + 2
   // has waited for the flag of the k_side_lp behind it on that stream
-  HIPCHK(dmalloc(&h->dZsMh, 3 * K * G * sizeof(double)));
-  HIPCHK(hipMemset(h->dZsMh, 0, 3 * K * G * sizeof(double)));
+  HIPCHK(hzeroed(h, &z.dMh, 3 * K * G * sizeof(double)));
   if (c.save_Z) {
     const size_t hw = (N + 1) / 2;
-    h->zs_recwords = items.size() * hw;
-    HIPCHK(dmalloc(&h->dZsRec, h->zs_recwords * sizeof(uint32_t)));
-    h->zs_eager = getenv("BNMF_ZEAGER") && atoi(getenv("BNMF_ZEAGER")) != 0;
+    z.recwords = p.items.size() * hw;
+    HIPCHK(hmalloc(h, &z.dRec, z.recwords * sizeof(uint32_t)));
+    z.eager = sw.z_eager;
     const size_t lds_max = 160 * 1024;
-    h->zx_cols = std::max(1, std::min(GBc, zexpand_cols((int)K, (int)N, lds_max)));
-    h->zx_lds = ((size_t)h->zx_cols * N * ((K + 1) / 2) * 4 + 15) & ~(size_t)15;
-    if (h->zx_lds > lds_max) return fail(BNMF_EINVAL, "bnmf_create: K = %zu, N = %zu: a column of Z does not fit the LDS of k_zexpand", K, N);
+    z.x_cols = std::max(1, std::min(p.GBc, zexpand_cols((int)K, (int)N, lds_max)));
+    z.x_lds = ((size_t)z.x_cols * N * ((K + 1) / 2) * 4 + 15) & ~(size_t)15;
+    if (z.x_lds > lds_max) return fail(BNMF_EINVAL, "bnmf_create: K = %zu, N = %zu: a column of Z does not fit the LDS of k_zexpand", K, N);
     HIPCHK(hipFuncSetAttribute((const void*)k_zexpand, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   }
-  h->zsg = ZSGeom{KP, GBc, (int)nb};
-  h->zs_shared = p.shared;                                 // columns with several writers of ZsumK: atomics + zeroing by the consumer (refresh_dev)
-  h->zs_nblk = nblk; h->zs_w = W; h->zs_pk = pk; h->zs_nempty = p.nempty;
-  h->zs_lds = (zsort_shared_bytes((int)K, (int)N, KP, GBc, pk) + (size_t)W * zsort_wave_bytes(nblk, (int)N) + 15) & ~(size_t)15;
-  h->z_sort = true;
+  z.g = ZSGeom{p.KP, p.GBc, p.nb};
+  z.shared = p.shared;                                     // columns with several writers of ZsumK: atomics + zeroing by the consumer (refresh_dev)
+  z.nblk = p.nblk; z.w = p.W; z.pk = p.pk; z.nempty = p.nempty;
+  z.lds = (zsort_shared_bytes((int)K, (int)N, p.KP, p.GBc, p.pk) + (size_t)p.W * zsort_wave_bytes(p.nblk, (int)N) + 15) & ~(size_t)15;
+  h->zkind = ZKind::sort;
 #ifdef ZSPROF
-  HIPCHK(dmalloc(&h->dZsProf, (8 + 3 * 16 * 8) * sizeof(unsigned long long)));   // section ticks, then the stamps of three blocks' waves (-DZSPROF)
-  HIPCHK(hipMemset(h->dZsProf, 0, (8 + 3 * 16 * 8) * sizeof(unsigned long long)));
+  HIPCHK(hzeroed(h, &z.dProf, (8 + 3 * 16 * 8) * sizeof(unsigned long long)));   // section ticks, then the stamps of three blocks' waves (-DZSPROF)
 #endif
   return 0;
 }
 
 // ... and build_zstep what plan_zstep returns
-static int build_zstep(bnmf_handle* h, const int32_t* M, int n_cu) {
+static int build_zstep(bnmf_handle* h, const int32_t* M, const Switches& sw) {
   const bnmf_config& c = h->cfg;
-  const size_t N = c.N;
-  h->z_step = false;
+  ZStep& z = h->zp;
   ZStepPlan p;
-  if (int rc = plan_zstep(M, c.K, c.G, N, c.save_Z != 0, n_cu, p)) return rc;
+  if (int rc = plan_zstep(M, c.K, c.G, c.N, c.save_Z != 0, h->n_cu, sw, p)) return rc;
   if (!p.ok) return 0;
-  const int nch = p.nch, nwg = p.nwg, W = p.W, GBP = p.GBP, L = p.L;
-  const std::vector<ZPWg>& wgs = p.wgs;
-  const std::vector<ZPBatch>& batches = p.batches;
-  const std::vector<ZPStep>& steps = p.steps;
-  const std::vector<int>& cols = p.cols;
-  const std::vector<uint32_t>& items = p.items;
-  h->zp_it16 = p.it16;
-  if (h->zp_it16) {
-    const std::vector<uint16_t>& i16 = p.items16;
-    HIPCHK(dmalloc(&h->dZpItems, (i16.size() * sizeof(uint16_t) + 3) & ~(size_t)3));
-    HIPCHK(hipMemcpy(h->dZpItems, i16.data(), i16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  } else {
-    HIPCHK(dmalloc(&h->dZpItems, items.size() * sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(h->dZpItems, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  HIPCHK(dmalloc(&h->dZpWgs, wgs.size() * sizeof(ZPWg)));
-  HIPCHK(hipMemcpy(h->dZpWgs, wgs.data(), wgs.size() * sizeof(ZPWg), hipMemcpyHostToDevice));
-  HIPCHK(dmalloc(&h->dZpBatches, batches.size() * sizeof(ZPBatch)));
-  HIPCHK(hipMemcpy(h->dZpBatches, batches.data(), batches.size() * sizeof(ZPBatch), hipMemcpyHostToDevice));
-  HIPCHK(dmalloc(&h->dZpSteps, steps.size() * sizeof(ZPStep)));
-  HIPCHK(hipMemcpy(h->dZpSteps, steps.data(), steps.size() * sizeof(ZPStep), hipMemcpyHostToDevice));
-  HIPCHK(dmalloc(&h->dZpCols, cols.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(h->dZpCols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice));
-  h->zpg = ZPGeom{nch, (int)nwg, nullptr};
+  z.it16 = p.it16;
+  if (p.it16) HIPCHK(hupload(h, &z.dItems, p.items16.data(), p.items16.size() * sizeof(uint16_t), (p.items16.size() * sizeof(uint16_t) + 3) & ~(size_t)3));
+  else HIPCHK(hupload(h, &z.dItems, p.items.data(), p.items.size() * sizeof(uint32_t)));
+  HIPCHK(hupload(h, &z.dWgs, p.wgs.data(), p.wgs.size() * sizeof(ZPWg)));
+  HIPCHK(hupload(h, &z.dBatches, p.batches.data(), p.batches.size() * sizeof(ZPBatch)));
+  HIPCHK(hupload(h, &z.dSteps, p.steps.data(), p.steps.size() * sizeof(ZPStep)));
+  HIPCHK(hupload(h, &z.dCols, p.cols.data(), p.cols.size() * sizeof(int)));
+  z.g = ZPGeom{p.nch, p.nwg, nullptr};
 #ifdef ZPPROF
-  HIPCHK(dmalloc(&h->zpg.prof, 8 * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(h->zpg.prof, 0, 8 * sizeof(unsigned long long)));
+  HIPCHK(hzeroed(h, &z.g.prof, 8 * sizeof(unsigned long long)));
 #endif
-  h->zp_ns = W; h->zp_gbp = GBP;
-  h->zp_lds = (zstep_shared_bytes((int)N, GBP) + W * zstep_wave_bytes(L) + 15) & ~(size_t)15;
-  h->z_step = true;
+  z.ns = p.W; z.gbp = p.GBP;
+  z.lds = (zstep_shared_bytes((int)c.N, p.GBP) + p.W * zstep_wave_bytes(p.L) + 15) & ~(size_t)15;
+  h->zkind = ZKind::step;
   return 0;
 }
 
@@ -704,7 +718,7 @@ extern "C" int bnmf_test_zsort_plan(int K, int G, int N, int save_Z, int n_cu, c
   int mx = 0;
   for (size_t i = 0; i < (size_t)K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_test_zsort_plan: negative count in M"); if (M[i] > mx) mx = M[i]; }
   ZSortPlan p;
-  if (int rc = plan_zsort(M, (size_t)K, (size_t)G, (size_t)N, save_Z != 0, mx, N <= ZNMAX, n_cu, p)) return rc;
+  if (int rc = plan_zsort(M, (size_t)K, (size_t)G, (size_t)N, save_Z != 0, mx, N <= ZNMAX, n_cu, Switches::from_env(), p)) return rc;
   const long long d[14] = {p.ok, p.KP, p.GBc, p.nb, p.W, p.qmax, p.it16, p.pk, p.shared, p.nempty, (long long)p.cols.size(), (long long)p.items.size(),
                            (long long)p.Mblk.size(), p.nblk};
   memcpy(desc, d, sizeof d);
@@ -721,7 +735,7 @@ extern "C" int bnmf_test_zstep_plan(int K, int G, int N, int save_Z, int n_cu, c
   if (!M || !desc || K < 1 || G < 1 || N < 1 || n_cu < 1) return fail(BNMF_EINVAL, "bnmf_test_zstep_plan: bad argument");
   for (size_t i = 0; i < (size_t)K * G; ++i) if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_test_zstep_plan: negative count in M");
   ZStepPlan p;
-  if (int rc = plan_zstep(M, (size_t)K, (size_t)G, (size_t)N, save_Z != 0, n_cu, p)) return rc;
+  if (int rc = plan_zstep(M, (size_t)K, (size_t)G, (size_t)N, save_Z != 0, n_cu, Switches::from_env(), p)) return rc;
   const long long d[11] = {p.ok, p.nch, p.nwg, p.W, p.GBP, p.it16, p.maxfrag, (long long)p.batches.size(), (long long)p.steps.size(), (long long)p.cols.size(),
                            (long long)p.items.size()};
   memcpy(desc, d, sizeof d);
@@ -779,7 +793,7 @@ static int probe_overlap(int device, int* overlap) {
     dfree(w);
     give_stream(device, a); give_stream(device, b);
     g_probe[device] = res[1] == 1u ? 1 : 2;
-    if (getenv("BNMF_TIMING")) fprintf(stderr, "[bnmf] device %d: kernels on two streams %s\n", device, g_probe[device] == 1 ? "overlap" : "do NOT overlap: serial-safe mode");
+    if (timing_on()) fprintf(stderr, "[bnmf] device %d: kernels on two streams %s\n", device, g_probe[device] == 1 ? "overlap" : "do NOT overlap: serial-safe mode");
   }
   *overlap = g_probe[device] == 1;
   return 0;
@@ -801,16 +815,16 @@ extern "C" int bnmf_probe_overlap(int device, int* overlap) {
 }
 
 static uint64_t state_data_hash(const void* p, size_t bytes);   // state_io.h
-static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* Mf, bnmf_handle* h) {
-  const size_t K = cfg->K, G = cfg->G, N = cfg->N;
-  const bool normal = cfg->likelihood == BNMF_NORMAL;
-  CreateClock clk;
+
+// ---- bnmf_create, step by step (create_impl at the end calls them in this order) ----
+// streams, the device's lock files, events
+static int create_streams(bnmf_handle* h, const Switches& sw, CreateClock& clk) {
   if (int rc = take_stream(h->device, &h->stream)) return rc;
   if (int rc = take_stream(h->device, &h->side, 1)) return rc;
   if (int rc = take_stream(h->device, &h->side2, 1)) return rc;
   clk.mark("streams");
   // one open file description per handle: flock() then also separates the handles of ONE process (BNMF_DEVLOCK=0: no file lock)
-  h->devlock_off = getenv("BNMF_DEVLOCK") && atoi(getenv("BNMF_DEVLOCK")) == 0;
+  h->devlock_off = !sw.devlock;
   if (!h->devlock_off) {
     char bus[64] = {0};
     if (hipDeviceGetPCIBusId(bus, (int)sizeof bus - 1, h->device) == hipSuccess) {
@@ -818,47 +832,48 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* M
       devlock_open(bus, &h->devlock_fd, &h->devgate_fd);
     } else (void)hipGetLastError();
   }
-  HIPCHK(hipEventCreateWithFlags(&h->ev_draw, hipEventDisableTiming | hipEventDisableSystemFence));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming | hipEventDisableSystemFence));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_sideP, hipEventDisableTiming | hipEventDisableSystemFence));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_p, hipEventDisableTiming | hipEventDisableSystemFence));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_rank, hipEventDisableTiming | hipEventDisableSystemFence));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_z, hipEventDisableTiming | hipEventDisableSystemFence));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_red, hipEventDisableTiming | hipEventDisableSystemFence));
+  for (hipEvent_t* e : {&h->ev_draw, &h->ev_side, &h->ev_sideP, &h->ev_p, &h->ev_rank, &h->ev_z, &h->ev_red})
+    HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence));
   clk.mark("events");
+  return 0;
+}
+// the data to the device; maxM, colmax, the data's hash.  Mf comes back pointing at the fp64 data of a Normal handle (mconv: its store
+// where the caller gave counts)
+static int create_data(bnmf_handle* h, const int32_t* M, const double*& Mf, std::vector<double>& mconv, CreateClock& clk) {
+  const size_t KG = (size_t)h->cfg.K * h->cfg.G;
   int mx = 0;
-  std::vector<double> mconv;                                  // Normal data given as int32 counts: converted here (exact)
-  if (!normal) {
-    HIPCHK(dmalloc(&h->dM, K * G * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(h->dM, M, K * G * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (h->cfg.likelihood != BNMF_NORMAL) {
+    HIPCHK(hupload(h, &h->dM, M, KG * sizeof(int32_t)));
     clk.mark("M to the device");
-    for (size_t i = 0; i < K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); if (M[i] > mx) mx = M[i]; }
+    for (size_t i = 0; i < KG; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); if (M[i] > mx) mx = M[i]; }
+    const size_t K = h->cfg.K, G = h->cfg.G;                 // (colmax is checked behind build_zsort: the sorted schedule spreads large cells over the blocks and takes more)
+    for (size_t g = 0; g < G; ++g) { long cs = 0; for (size_t k = 0; k < K; ++k) cs += M[k + K * g]; if (cs > h->colmax) h->colmax = cs; }
+    h->data_hash = state_data_hash(M, KG * sizeof(int32_t));
   } else {
     // a Normal handle holds its data as fp64 whichever entry point created it; nothing is sized by counts (maxM = 0: the
-    // one-entry tables below, which no Normal kernel reads)
-    if (M) {
-      mconv.resize(K * G);
-      for (size_t i = 0; i < K * G; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); mconv[i] = (double)M[i]; }
+    // one-entry tables of create_tables, which no Normal kernel reads)
+    if (M) {                                                 // Normal data given as int32 counts: converted here (exact)
+      mconv.resize(KG);
+      for (size_t i = 0; i < KG; ++i) { if (M[i] < 0) return fail(BNMF_EINVAL, "bnmf_create: negative count in M"); mconv[i] = (double)M[i]; }
       Mf = mconv.data();
     }
-    HIPCHK(dmalloc(&h->dMf, K * G * sizeof(double)));
-    HIPCHK(hipMemcpy(h->dMf, Mf, K * G * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hupload(h, &h->dMf, Mf, KG * sizeof(double)));
     clk.mark("M to the device");
+    h->data_hash = state_data_hash(Mf, KG * sizeof(double));
   }
   h->maxM = mx;
-  h->data_hash = normal ? state_data_hash(Mf, K * G * sizeof(double)) : state_data_hash(M, K * G * sizeof(int32_t));
-  HIPCHK(dmalloc(&h->dZsumK, N * G * sizeof(int32_t)));
-  HIPCHK(dmalloc(&h->dZsumG, K * N * sizeof(int32_t)));
-  HIPCHK(hipMemset(h->dZsumK, 0, N * G * sizeof(int32_t)));
-  HIPCHK(hipMemset(h->dZsumG, 0, K * N * sizeof(int32_t)));
-  if (cfg->save_Z) HIPCHK(dmalloc(&h->dZ, K * N * G * sizeof(int32_t)));
-  if (const char* e = getenv("BNMF_GATE")) h->gate_forced = atoi(e) != 0 ? 1 : 0;   // diagnostics / tests
-  if (const char* e = getenv("BNMF_MHSIDE")) h->mh_side_main = atoi(e) != 0;
-  if (const char* e = getenv("BNMF_MHSIDETAIL")) h->mh_side_tail = atoi(e) != 0;
-  if (const char* e = getenv("BNMF_DEBUG_DRAW_NO_P")) h->dbg_draw_no_p = atoi(e) != 0 ? 1 : 0;   // tests only
-  if (const char* e = getenv("BNMF_DEBUG_MAIN_DELAY_US")) h->dbg_main_delay_us = std::max(0, std::min(20000, atoi(e)));   // tests only
-  if (const char* e = getenv("BNMF_DEBUG_ALLSIDE_DELAY_US")) h->dbg_allside_delay_us = std::max(0, std::min(20000, atoi(e)));   // tests only
-  if (const char* e = getenv("BNMF_DEBUG_SIDE_DELAY_US")) h->dbg_side_delay_us = std::max(0, std::min(20000, atoi(e)));   // tests only
+  return 0;
+}
+// the handle's own switches, the serial-safe mode, the small buffers every model needs
+static int create_small(bnmf_handle* h, const Switches& sw) {
+  const size_t K = h->cfg.K, G = h->cfg.G, N = h->cfg.N;
+  HIPCHK(hzeroed(h, &h->dZsumK, N * G * sizeof(int32_t)));
+  HIPCHK(hzeroed(h, &h->dZsumG, K * N * sizeof(int32_t)));
+  if (h->cfg.save_Z) HIPCHK(hmalloc(h, &h->dZ, K * N * G * sizeof(int32_t)));
+  h->gate_forced = sw.gate;
+  h->mh.side_main = sw.mh_side_main; h->mh.side_tail = sw.mh_side_tail;
+  h->dbg_draw_no_p = sw.draw_no_p ? 1 : 0;
+  h->dbg_main_delay_us = sw.main_delay_us; h->dbg_allside_delay_us = sw.allside_delay_us; h->dbg_side_delay_us = sw.side_delay_us;
   {
     // A lane that polls inside a main-stream kernel for a side-stream kernel deadlocks (until its bound) when dispatches cannot
     // overlap: the waited-for kernel only starts once the waiting one has ended.  Where the process is known to serialise its
@@ -867,255 +882,150 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* M
     // profiler's variables; any other serialising tool ended in a time-out): probe_overlap runs a two-stream hand-off once per device.
     int ov = 0;
     if (int rc = probe_overlap(h->device, &ov)) return rc;
-    h->serial = ov == 0;
-    if (const char* e = getenv("BNMF_SERIAL")) h->serial = atoi(e) != 0;      // the caller's explicit choice
+    h->serial = sw.serial >= 0 ? sw.serial != 0 : ov == 0;   // (BNMF_SERIAL: the caller's explicit choice)
   }
-  HIPCHK(dmalloc(&h->dFlags, 64));
-  HIPCHK(hipMemset(h->dFlags, 0, 64));
-  HIPCHK(dmalloc(&h->dScal, BNMF_ID_MAX * sizeof(double)));
-  HIPCHK(dmalloc(&h->dDrawOwn, N * sizeof(unsigned)));
-  HIPCHK(hipMemset(h->dDrawOwn, 0, N * sizeof(unsigned)));
+  HIPCHK(hzeroed(h, &h->dFlags, 64));
+  HIPCHK(hmalloc(h, &h->dScal, BNMF_ID_MAX * sizeof(double)));
+  HIPCHK(hzeroed(h, &h->dDrawOwn, N * sizeof(unsigned)));
   HIPCHK(hipHostMalloc((void**)&h->hErr, 64, hipHostMallocMapped));
   memset(h->hErr, 0, 64);
   HIPCHK(hipHostGetDevicePointer((void**)&h->dErr, h->hErr, 0));
-  HIPCHK(dmalloc(&h->dR, sizeof(int)));
-  int Rinit = (int)N;
-  HIPCHK(hipMemcpy(h->dR, &Rinit, sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(dmalloc(&h->dRedraw, N * sizeof(int)));
-  HIPCHK(dmalloc(&h->dEsum, N * sizeof(double)));
-  HIPCHK(dmalloc(&h->dPsum, N * sizeof(double)));
-  HIPCHK(dmalloc(&h->dlpPn, 3 * N * sizeof(double)));
+  const int Rinit = (int)N;
+  HIPCHK(hupload(h, &h->dR, &Rinit, sizeof(int)));
+  HIPCHK(hmalloc(h, &h->dRedraw, N * sizeof(int)));
+  HIPCHK(hmalloc(h, &h->dEsum, N * sizeof(double)));
+  HIPCHK(hmalloc(h, &h->dPsum, N * sizeof(double)));
+  HIPCHK(hmalloc(h, &h->dlpPn, 3 * N * sizeof(double)));
   h->nblkE = (int)((N * G + ES_T - 1) / ES_T);
-  HIPCHK(dmalloc(&h->dlpE, 3 * (size_t)h->nblkE * sizeof(double)));
-  HIPCHK(dmalloc(&h->dcol, 3 * 3 * G * sizeof(double)));   // per-column partials, 3 slots (t % 3)
-  if (cfg->learning_rank) {
-    const size_t gran_words = (size_t)RK_REP * 4 * 2 * ((G + RK_MAXC - 1) / RK_MAXC);   // [RK_REP copies][4 buffers][2 granules per block sum]
-    HIPCHK(dmalloc(&h->dRankCol, gran_words * sizeof(double)));
-    HIPCHK(hipMemset(h->dRankCol, 0, gran_words * sizeof(double)));           // tag 0 is never used
-    HIPCHK(dmalloc(&h->dRankSync, 32));
-    HIPCHK(hipMemset(h->dRankSync, 0, 32));
-    // grid of the persistent rank sweep: co-resident by construction (one 512-lane workgroup per CU)
-    hipDeviceProp_t prop0;
-    HIPCHK(hipGetDeviceProperties(&prop0, cfg->device));
-    const long NB = ((long)G + RK_MAXC - 1) / RK_MAXC;                 // blocks of 8 columns, one compute wave each
-    const long wg_needed = (NB + RK_CW - 1) / RK_CW;                   // RK_CW compute waves + the decision wave per workgroup
-    // every workgroup of the sweep waits for all others: the grid must be co-resident.  Ask the runtime how many
-    // workgroups of each variant fit a CU (registers, LDS); where the answer is SGPR-limited (>= 6 per CU) the query can
-    // be one high (MI355X_MICROARCH.md), so one is kept in reserve there; never plan more than two per CU.  Should the
-    // grid still not be co-resident, the bounded spins time out and bnmf_run reports it (no hang).
-    const size_t rlds = (3 * (size_t)N + 1) * sizeof(double);
-    auto fit = [&](const void* fn) {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, RK_T, rlds) != hipSuccess || nb < 1) nb = 1;
-      return std::min(1, nb >= 6 ? nb - 1 : nb);          // one per CU: even compute times, and co-resident with margin
-    };
-    const bool nrm0 = cfg->likelihood == BNMF_NORMAL;
-    const long cap_reg = (long)fit(nrm0 ? (const void*)k_rank_sweep<true, true> : (const void*)k_rank_sweep<true, false>) * prop0.multiProcessorCount;
-    const long cap_gen = (long)fit(nrm0 ? (const void*)k_rank_sweep<false, true> : (const void*)k_rank_sweep<false, false>) * prop0.multiProcessorCount;
-    h->rank_reg = K <= 96 && wg_needed <= cap_reg;       // register variant: rows 64..95 of two columns share a register (rank.h)
-    // ... with HALF a block per compute wave where the grid of ten-half-block workgroups is co-resident too (704 lanes, one per CU)
-    const long wg_half = (NB + RK_CWH / 2 - 1) / (RK_CWH / 2);
-    h->rank_half = h->rank_reg && wg_half <= (long)prop0.multiProcessorCount && NB <= 1536;   // (1,536: one round of its decision wave's gather, rank.h)
-    if (const char* e = getenv("BNMF_RANKHALF")) h->rank_half = h->rank_half && atoi(e) != 0;   // diagnostics / tests: 0 = whole blocks
-    // (a wider grid with the blocks dealt wave-major over all CUs was measured: no gain, the sweep is bound by the
-    // per-factor exchange, not by VALU contention)
-    h->rank_grid = h->rank_half ? (int)wg_half : (int)std::min<long>(wg_needed, h->rank_reg ? cap_reg : cap_gen);
-    if (const char* e = getenv("BNMF_RANKGRID")) { const long v = atol(e); if (!h->rank_half && v >= wg_needed && v <= (h->rank_reg ? cap_reg : cap_gen)) h->rank_grid = (int)v; }   // diagnostics only
-    if (!h->rank_reg) HIPCHK(dmalloc(&h->dRankMhat, K * G * sizeof(double)));
-    if (getenv("BNMF_RANKDBG")) { HIPCHK(dmalloc(&h->dRankDbg, (size_t)h->rank_grid * 16 * 8 * 8)); HIPCHK(hipMemset(h->dRankDbg, 0, (size_t)h->rank_grid * 16 * 8 * 8)); }   // diagnostics only
+  HIPCHK(hmalloc(h, &h->dlpE, 3 * (size_t)h->nblkE * sizeof(double)));
+  HIPCHK(hmalloc(h, &h->dcol, 3 * 3 * G * sizeof(double)));   // per-column partials, 3 slots (t % 3)
+  return 0;
+}
+// the persistent rank sweep: its exchange buffers, variant and grid (plan_rank)
+static int create_rank(bnmf_handle* h, const Switches& sw) {
+  const size_t K = h->cfg.K, G = h->cfg.G, N = h->cfg.N;
+  const size_t gran_words = (size_t)RK_REP * 4 * 2 * ((G + RK_MAXC - 1) / RK_MAXC);   // [RK_REP copies][4 buffers][2 granules per block sum]
+  HIPCHK(hzeroed(h, &h->rank.dCol, gran_words * sizeof(double)));           // tag 0 is never used
+  HIPCHK(hzeroed(h, &h->rank.dSync, 32));
+  const size_t rlds = (3 * N + 1) * sizeof(double);
+  auto occ = [&](const void* fn) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, RK_T, rlds) != hipSuccess || nb < 1) nb = 1;
+    return nb;
+  };
+  const bool nrm = h->cfg.likelihood == BNMF_NORMAL;
+  const int occ_reg = occ(nrm ? (const void*)k_rank_sweep<true, true> : (const void*)k_rank_sweep<true, false>);
+  const int occ_gen = occ(nrm ? (const void*)k_rank_sweep<false, true> : (const void*)k_rank_sweep<false, false>);
+  static_cast<RankPlan&>(h->rank) = plan_rank(K, G, h->n_cu, occ_reg, occ_gen, sw);
+  if (!h->rank.reg) HIPCHK(hmalloc(h, &h->rank.dMhat, K * G * sizeof(double)));
+  if (sw.rank_dbg) HIPCHK(hzeroed(h, &h->rank.dDbg, (size_t)h->rank.grid * 16 * 8 * 8));   // diagnostics only
+  return 0;
+}
+// the MH / Normal sweeps: which kernels (plan_mh), their LDS limits, their buffers, the transposed data
+static int create_mh(bnmf_handle* h, const int32_t* M, const double* Mf, const Switches& sw) {
+  const bnmf_config& c = h->cfg;
+  const size_t K = c.K, G = c.G, N = c.N;
+  Mh& m = h->mh;
+  m.e_k128 = sw.mhe_k128; m.e_gw = sw.mhe_gw;
+  if (int rc = plan_mh(K, G, N, c.MH && c.likelihood == BNMF_POISSON && !c.learning_rank, m.side_main, m.side_tail, sw, m)) return rc;
+  auto raise = [](std::initializer_list<const void*> ks) {
+    for (const void* kf : ks) HIPCHK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return 0;
+  };
+  if (m.e_raise)
+    if (int rc = raise({(const void*)k_mh_ecol<false>, (const void*)k_mh_ecol<true>, (const void*)k_mh_ecol<false, true>, (const void*)k_mh_ecol<true, true>})) return rc;
+  if (m.e16_raise)
+    if (int rc = raise({(const void*)k_mh_ecol16<false, false, 16>, (const void*)k_mh_ecol16<false, true, 16>, (const void*)k_mh_ecol16<false, false, 32>,
+                        (const void*)k_mh_ecol16<false, true, 32>, (const void*)k_mh_ecol16<true, false, 16>, (const void*)k_mh_ecol16<true, false, 32>,
+                        (const void*)k_mh_ecol16<false, false, 16, 96>, (const void*)k_mh_ecol16<false, true, 16, 96>, (const void*)k_mh_ecol16<false, false, 32, 96>,
+                        (const void*)k_mh_ecol16<false, true, 32, 96>, (const void*)k_mh_ecol16<true, false, 16, 96>, (const void*)k_mh_ecol16<true, false, 32, 96>,
+                        (const void*)k_mh_ecol16<false, false, 16, MHE16_KMAX, true>, (const void*)k_mh_ecol16<false, false, 32, MHE16_KMAX, true>,
+                        (const void*)k_mh_ecol16<true, false, 16, MHE16_KMAX, true>, (const void*)k_mh_ecol16<true, false, 32, MHE16_KMAX, true>,
+                        (const void*)k_mh_ecol16<false, false, 16, 96, true>, (const void*)k_mh_ecol16<false, false, 32, 96, true>,
+                        (const void*)k_mh_ecol16<true, false, 16, 96, true>, (const void*)k_mh_ecol16<true, false, 32, 96, true>})) return rc;
+  HIPCHK(hmalloc(h, &m.dMhat, 3 * K * G * sizeof(double)));      // rows of Mhat maintained by the P sweep; log(Mhat) and its candidates (MH step)
+  HIPCHK(hmalloc(h, &m.dAccPn, 3 * N * sizeof(double)));
+  HIPCHK(hmalloc(h, &m.dAccEpart, 3 * (size_t)h->nblkE * sizeof(double)));
+  HIPCHK(hmalloc(h, &m.dNzE, 6 * N * sizeof(int)));         // nzE[N], nzP[N] (k_mh_tail's), then the hosted form's nzE[2][N], nzP[2][N] by iteration parity
+  HIPCHK(hmalloc(h, &m.dEt, N * G * sizeof(double)));
+  if (c.likelihood == BNMF_NORMAL) {                        // the [G][K] transpose of the data
+    std::vector<double> mt(K * G);
+    for (size_t g = 0; g < G; ++g) for (size_t k = 0; k < K; ++k) mt[g + G * k] = Mf[k + K * g];
+    HIPCHK(hupload(h, &m.dMtf, mt.data(), K * G * sizeof(double)));
+  } else {
+    std::vector<int32_t> mt(K * G);
+    for (size_t g = 0; g < G; ++g) for (size_t k = 0; k < K; ++k) mt[g + G * k] = M[k + K * g];
+    HIPCHK(hupload(h, &m.dMt, mt.data(), K * G * sizeof(int32_t)));
   }
-  if (cfg->MH || cfg->likelihood == BNMF_NORMAL) {
-    h->mh_S = (int)((G + MH_SEG - 1) / MH_SEG);
-    HIPCHK(dmalloc(&h->dMhat, 3 * K * G * sizeof(double)));      // rows of Mhat maintained by the P sweep; log(Mhat) and its candidates (MH step)
-    if (const char* e = getenv("BNMF_MHE_K128")) h->mhe_k128 = atoi(e) != 0;
-    if (const char* e = getenv("BNMF_MHE_GW")) h->mhe_gw = atoi(e) == 32 ? 32 : atoi(e) == 16 ? 16 : 0;   // diagnostics / tests: lanes per column of k_mh_ecol16 (0 = by mode)
-    h->mhe_lds = 4 * (2 * N + 3 * K) * sizeof(double);             // k_mh_ecol: per wave E column, A, Mhat column, log(Mhat) and candidates
-    if (h->mhe_lds > 64 * 1024) {
-      if (h->mhe_lds > 160 * 1024) return fail(BNMF_EINVAL, "bnmf_create: K = %zu too large for the column kernel of the MH / Normal models (LDS)", K);
-      HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)k_mh_ecol<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    // k_mh_ecol16 (K <= 128: several columns per wave): its LDS grows with N — above 64 KiB it needs the attribute, above the CU's 160 KiB
-    // the sweep takes k_mh_ecol
-    {
-      const size_t lds16_max = (4 * (size_t)4 * N * (1 + PRE_W) + 2 * N) * sizeof(double);   // 16 lanes per column: 4 columns per wave
-      h->mhe16 = K <= (size_t)MHE16_KMAX && lds16_max <= 160 * 1024;
-      if (h->mhe16 && lds16_max > 64 * 1024) {
-        const void* ks[] = {(const void*)k_mh_ecol16<false, false, 16>, (const void*)k_mh_ecol16<false, true, 16>, (const void*)k_mh_ecol16<false, false, 32>,
-                            (const void*)k_mh_ecol16<false, true, 32>, (const void*)k_mh_ecol16<true, false, 16>, (const void*)k_mh_ecol16<true, false, 32>,
-                            (const void*)k_mh_ecol16<false, false, 16, 96>, (const void*)k_mh_ecol16<false, true, 16, 96>, (const void*)k_mh_ecol16<false, false, 32, 96>,
-                            (const void*)k_mh_ecol16<false, true, 32, 96>, (const void*)k_mh_ecol16<true, false, 16, 96>, (const void*)k_mh_ecol16<true, false, 32, 96>,
-                            (const void*)k_mh_ecol16<false, false, 16, MHE16_KMAX, true>, (const void*)k_mh_ecol16<false, false, 32, MHE16_KMAX, true>,
-                            (const void*)k_mh_ecol16<true, false, 16, MHE16_KMAX, true>, (const void*)k_mh_ecol16<true, false, 32, MHE16_KMAX, true>,
-                            (const void*)k_mh_ecol16<false, false, 16, 96, true>, (const void*)k_mh_ecol16<false, false, 32, 96, true>,
-                            (const void*)k_mh_ecol16<true, false, 16, 96, true>, (const void*)k_mh_ecol16<true, false, 32, 96, true>};
-        for (const void* kf : ks) HIPCHK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      }
-    }
-    // Round 5: k_mh_tail's work hosted by the two sweep kernels (mh.h) — the Poisson MH models at fixed rank where the column sweep is k_mh_ecol16
-    h->mh_pipe = h->mhe16 && cfg->MH && cfg->likelihood == BNMF_POISSON && !cfg->learning_rank && h->mh_side_main && h->mh_side_tail && N <= RT;
-    if (const char* e = getenv("BNMF_MHPIPE")) h->mh_pipe = h->mh_pipe && atoi(e) != 0;      // diagnostics / tests: 0 = k_mh_tail between the sweeps
-    HIPCHK(dmalloc(&h->dAccPn, 3 * N * sizeof(double)));
-    HIPCHK(dmalloc(&h->dAccEpart, 3 * (size_t)h->nblkE * sizeof(double)));
-    HIPCHK(dmalloc(&h->dNzE, 6 * N * sizeof(int)));         // nzE[N], nzP[N] (k_mh_tail's), then the hosted form's nzE[2][N], nzP[2][N] by iteration parity
-    HIPCHK(dmalloc(&h->dEt, N * G * sizeof(double)));
-    if (normal) {
-      HIPCHK(dmalloc(&h->dMtf, K * G * sizeof(double)));
-      std::vector<double> mt(K * G);
-      for (size_t g = 0; g < G; ++g) for (size_t k = 0; k < K; ++k) mt[g + G * k] = Mf[k + K * g];
-      HIPCHK(hipMemcpy(h->dMtf, mt.data(), K * G * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-      HIPCHK(dmalloc(&h->dMt, K * G * sizeof(int32_t)));
-      std::vector<int32_t> mt(K * G);
-      for (size_t g = 0; g < G; ++g) for (size_t k = 0; k < K; ++k) mt[g + G * k] = M[k + K * g];
-      HIPCHK(hipMemcpy(h->dMt, mt.data(), K * G * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-  }
-  HIPCHK(dmalloc(&h->dLut, 2 * (size_t)(mx + 1) * sizeof(double)));
+  return 0;
+}
+// the lgamma / log tables of the counts, the temperature schedule, the metric rows
+static int create_tables(bnmf_handle* h, const bnmf_config* cfg, CreateClock& clk) {
+  const int mx = h->maxM;
+  HIPCHK(hmalloc(h, &h->dLut, 2 * (size_t)(mx + 1) * sizeof(double)));
   if (cfg->n_temperature > 0 && cfg->temperature) {
-    HIPCHK(dmalloc(&h->dTemp, cfg->n_temperature * sizeof(double)));
-    HIPCHK(hipMemcpy(h->dTemp, cfg->temperature, cfg->n_temperature * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hupload(h, &h->dTemp, cfg->temperature, cfg->n_temperature * sizeof(double)));
     h->temp_host.assign(cfg->temperature, cfg->temperature + cfg->n_temperature);
   } else h->cfg.n_temperature = 0;
   h->cfg.temperature = nullptr;
   h->metrics_rows = 1024;
   HIPCHK(hipHostMalloc((void**)&h->hMetrics, h->metrics_rows * BNMF_NMETRIC * sizeof(double), hipHostMallocMapped));
   HIPCHK(hipHostGetDevicePointer((void**)&h->dMetrics, h->hMetrics, 0));
-  HIPCHK(dmalloc(&h->dRaw, h->metrics_rows * 8 * sizeof(double)));
+  HIPCHK(hmalloc(h, &h->dRaw, h->metrics_rows * 8 * sizeof(double)));
   hipLaunchKernelGGL(k_luts, dim3((mx + 256) / 256), dim3(256), 0, h->stream, h->dLut, h->dLut + (mx + 1), mx);
   HIPCHK(hipGetLastError());
   clk.mark("small buffers, tables");
-  // wait for the tables now: left to the end of this function, the wait cost 20-25 ms on every bnmf_create after the first of a
+  // wait for the tables now: left to the end of bnmf_create, the wait cost 20-25 ms on every bnmf_create after the first of a
   // process (the launch sat unsubmitted behind the allocations and copies of the schedule)
   HIPCHK(hipStreamSynchronize(h->stream));
   clk.mark("tables kernel done");
-  // Allocation-kernel geometry: independent waves, one LDS slab per wave, zacc (and P) shared per workgroup.
-  // N <= 24 takes k_zalloc_reg (zalloc_reg.h), larger N the general LDS-search kernel k_zalloc (kernels.h).
-  // The Poisson Gibbs sweep alone allocates counts: a Normal handle skips all of it (its data need not be counts).
-  if (!normal) {
-    ZGeom& zg = h->zg;
-    zg.KP = (K % 32 == 0) ? (int)K + 1 : (int)(K | 1);
-    zg.HW = (int)((N + 3) / 4);
-    zg.TR = N <= 8 ? 8 : N <= 16 ? 16 : N <= 20 ? 20 : 24;   // threshold registers of the k_zalloc_reg instantiation
-    h->z_reg = N <= (size_t)ZNMAX;
-    if (const char* e = getenv("BNMF_ZREG")) h->z_reg = h->z_reg && atoi(e) != 0;   // diagnostics only
-    long colmax = 0;
-    for (size_t g = 0; g < G; ++g) { long cs = 0; for (size_t k = 0; k < K; ++k) cs += M[k + K * g]; if (cs > colmax) colmax = cs; }
-    h->colmax = colmax;                                      // (checked behind build_zsort: the sorted schedule spreads large cells over the blocks and takes more)
-    // LDS need of a geometry; the general kernel (k_zalloc) takes the whole column in one row chunk when that
-    // leaves room for at least two waves per workgroup, else row chunks of 64 with ZsumG kept in global memory
-    bool force_chunk = false;
-    if (const char* e = getenv("BNMF_ZCHUNK")) force_chunk = atoi(e) != 0;   // diagnostics / tests
-    size_t slab = 0, shared_words = 0;
-    auto geometry = [&](bool chunked) {
-      if (h->z_reg) {
-        zg.KC = (int)K;
-        slab = (size_t)zg.HW * ZH + (K + 1) * (size_t)zreg_row_words(zg.TR) + 2 * N + N + (cfg->save_Z ? N * (size_t)zg.KP : 0);
-        zg.zacc_words = (int)((N * (size_t)zg.KP + 3) & ~(size_t)3);
-        zg.p_words = (int)((2 * K * N + 3) & ~(size_t)3);                  // workgroup copy of P (fp64)
-      } else {
-        zg.KC = chunked ? 64 : (int)((K + 63) & ~(size_t)63);
-        zg.KP = chunked ? 65 : ((K % 32 == 0) ? (int)K + 1 : (int)(K | 1));
-        const bool loc = chunked || cfg->save_Z;
-        slab = (size_t)zg.HW * ZH + 2 * N + (N - 1) * (size_t)zg.KP + (zg.KC + 1) + zg.KC + N + (loc ? N * (size_t)zg.KP : 0);
-        zg.zacc_words = chunked ? 0 : (int)((N * (size_t)zg.KP + 3) & ~(size_t)3);
-        zg.p_words = 0;
-      }
-      slab = (slab + 3) & ~(size_t)3;
-      zg.slab_words = (int)slab;
-      shared_words = (size_t)zg.zacc_words + zg.p_words;
-    };
-    // workgroup width.  k_zalloc holds 128 VGPRs per lane: at 16 waves/CU it owns the whole register file and
-    // starves k_side (side stream) until its tail.  Measured end to end at the metric config (tools/e2e.py):
-    // 16 waves/CU 178 us/iter, 12: 169, 10: 176, 8: 161, 2x4: 165, 6: 179.  So: at most 8 waves per CU, in one
-    // workgroup when LDS allows.
-    constexpr int Z_MAX_WAVES_PER_CU = 8;
-    int best_w = 0, best_per_cu = 0, best_total = 0;
-    auto pick = [&]() {
-      best_w = best_per_cu = best_total = 0;
-      for (int per_cu = 1; per_cu <= 2; ++per_cu)
-        for (int w : {16, 8, 6, 4, 2, 1}) {
-          const size_t lds = (shared_words + (size_t)w * slab) * 4;
-          if (lds * per_cu <= 160 * 1024 && w * per_cu <= Z_MAX_WAVES_PER_CU && w * per_cu > best_total) { best_total = w * per_cu; best_w = w; best_per_cu = per_cu; }
-        }
-    };
-    geometry(force_chunk && !h->z_reg);
-    pick();
-    // the register path keeps (K+1) threshold rows per wave and a workgroup copy of P: for large K (e.g. K = 1,536
-    // with N <= 24) that exceeds LDS, so fall back to the general kernel, which can walk the rows in chunks
-    if (h->z_reg && best_total < 2) { h->z_reg = false; geometry(force_chunk); pick(); }
-    if (!h->z_reg && best_total < 2 && !force_chunk) { geometry(true); pick(); }
-    if (const char* e = getenv("BNMF_ZW")) { best_w = atoi(e); best_per_cu = (shared_words + (size_t)best_w * slab) * 4 * 2 <= 160 * 1024 ? 2 : 1; }
-    if (best_w == 0) return fail(BNMF_EINVAL, "bnmf_create: K = %zu, N = %zu needs %zu B of LDS per wavefront for the allocation kernel (limit 160 KiB): unsupported", K, N, slab * 4);
-    h->z_zw = best_w;
-    h->z_lds = ((shared_words + (size_t)best_w * slab) * 4 + 15) & ~(size_t)15;
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-    const long resident = (long)prop.multiProcessorCount * best_per_cu;
-    const long want = ((long)G + best_w - 1) / best_w;
-    h->z_grid = (int)(want < resident ? want : resident);
-    if (const char* e = getenv("BNMF_ZGRID")) h->z_grid = atoi(e);          // diagnostics only
-    // N > 24, stats mode: the statically scheduled lane-per-item kernel (zalloc_step.h), where its LDS layout fits
-    if (!h->z_reg) if (int rc = build_zstep(h, M, prop.multiProcessorCount)) return rc;
-    // N > 24 (or K too large for the register kernel): the tile kernel, when at least two waves per CU fit
-    if (!h->z_reg && !h->z_step) {
-      bool want_tile = true;
-      if (const char* e = getenv("BNMF_ZTILE")) want_tile = atoi(e) != 0;   // diagnostics / tests: 0 = k_zalloc
-      ZTGeom& tg = h->ztg;
-      tg.HW = zg.HW;
-      tg.nch = (int)((K + ZTR - 1) / ZTR);
-      tg.p_words = 2 * ztile_np8((int)N) * ZTR;
-      tg.zacc_words = (int)((N * (size_t)ZTR + 3) & ~(size_t)3);
-      tg.slab_words = (int)ztile_slab_words((int)N, tg.HW, cfg->save_Z != 0);
-      const size_t shw = (size_t)tg.p_words + tg.zacc_words;
-      int tw = 0, tper = 0, ttot = 0;
-      for (int per_cu = 1; per_cu <= 2; ++per_cu)
-        for (int w : {8, 6, 4, 2}) {
-          const size_t lds = (shw + (size_t)w * tg.slab_words) * 4;
-          // 8 waves per CU: the kernel holds ~190 VGPRs (double-buffered LDS reads), i.e. two waves per SIMD
-          if (lds * per_cu <= 160 * 1024 && w * per_cu <= 8 && w * per_cu > ttot) { ttot = w * per_cu; tw = w; tper = per_cu; }
-        }
-      // ... or 16 (one workgroup of 1024 lanes) with the register-lean variant, where LDS allows it
-      h->z_lean = false;
-      if ((shw + 16 * (size_t)tg.slab_words) * 4 <= 160 * 1024 && !getenv("BNMF_ZNOLEAN")) { ttot = 16; tw = 16; tper = 1; h->z_lean = true; }
-      if (want_tile && ttot >= 2) {
-        h->z_tile = true;
-        h->z_zw = tw;
-        h->z_lds = ((shw + (size_t)tw * tg.slab_words) * 4 + 15) & ~(size_t)15;
-        // column slices: the fewest rounds (1..4) of resident workgroups that fill >= 97 % of the CUs (the chunk's P rows
-        // are staged and its ZsumG counts flushed once per workgroup); every wave with at least two columns
-        const long res = (long)prop.multiProcessorCount * tper;
-        long ns = 1; double best_util = 0.0;
-        for (long r = 1; r <= 4; ++r) {
-          const long c = (r * res) / tg.nch;
-          if (c < 1) continue;
-          const double util = (double)(c * tg.nch) / (double)(r * res);
-          if (util > best_util + 1e-9) { best_util = util; ns = c; }
-          if (util >= 0.97) break;
-        }
-        const long nsmax = ((long)G + 2 * tw - 1) / (2 * tw);
-        if (ns > nsmax) ns = nsmax;
-        if (ns < 1) ns = 1;
-        tg.nslice = (int)ns;
-        h->z_grid = tg.nch * tg.nslice;
-        HIPCHK(dmalloc(&h->dMhatZ, K * G * sizeof(double)));
-        tg.dbg = nullptr;
-        if (getenv("BNMF_ZTDBG")) { HIPCHK(dmalloc(&tg.dbg, 8 * sizeof(unsigned long long))); HIPCHK(hipMemset(tg.dbg, 0, 8 * sizeof(unsigned long long))); }   // diagnostics only
-      }
+  return 0;
+}
+// Which allocation kernel (ZKind), its geometry or schedule.  The Poisson Gibbs sweep alone allocates counts: a Normal handle skips
+// all of it (its data need not be counts).  N <= 24 takes the sorted schedule or k_zalloc_reg, larger N the step
+// schedule, the tile kernel or the general LDS-search kernel k_zalloc.
+static int create_zalloc(bnmf_handle* h, const int32_t* M, const Switches& sw) {
+  const bnmf_config& c = h->cfg;
+  const size_t K = c.K, G = c.G, N = c.N;
+  if (int rc = plan_zwave(K, G, N, c.save_Z != 0, h->n_cu, sw, h->zw)) return rc;
+  const bool reg_ok = h->zw.reg;
+  // N > 24, stats mode: the statically scheduled lane-per-item kernel (zalloc_step.h), where its LDS layout fits
+  if (!reg_ok) if (int rc = build_zstep(h, M, sw)) return rc;
+  // N > 24 (or K too large for the register kernel): the tile kernel, when at least two waves per CU fit
+  if (!reg_ok && h->zkind != ZKind::step) {
+    static_cast<ZTilePlan&>(h->zt) = plan_ztile(K, G, N, c.save_Z != 0, h->n_cu, sw);
+    if (h->zt.ok) {
+      h->zkind = ZKind::tile;
+      HIPCHK(hmalloc(h, &h->zt.dMhat, K * G * sizeof(double)));
+      if (sw.zt_dbg) HIPCHK(hzeroed(h, &h->zt.g.dbg, 8 * sizeof(unsigned long long)));   // diagnostics only
     }
-#ifdef BNMF_DIAG   /* the builder's diagnostic builds only (tools/bin/, never libbnmf.so): phases of the allocation kernels switched off */
-    if (const char* e = getenv("BNMF_ABLATE")) h->z_ablate = atoi(e);
-#endif
-    h->n_cu = prop.multiProcessorCount;
-    if (!h->z_tile && !h->z_step && !h->z_ablate) if (int rc = build_zsort(h, M, prop.multiProcessorCount)) return rc;
-    // the other allocation kernels take a column whole (k_zalloc_reg: one wave per column; tile / step: a workgroup's batch): 4,000,000 counts
-    // per column is where that stops being a sensible launch.  The sorted schedule (N <= 24, K <= 1,024, no save_Z) spreads the counts of a
-    // large cell over all blocks and is bounded by its item format only (a cell <= 65,534 fragments of 256 counts = 16.7 M counts).
-    if (h->colmax > 4000000 && !(h->z_sort && h->zs_shared))
-      return fail(BNMF_EINVAL, "bnmf_create: a column of M sums to %ld (> 4,000,000 counts): unsupported for this model / shape (N <= 24 and K <= 1,024 without save_Z take up to 16.7 M counts per cell)", h->colmax);
   }
+  h->z_ablate = sw.ablate;
+  if (h->zkind == ZKind::none && !h->z_ablate) if (int rc = build_zsort(h, M, reg_ok, sw)) return rc;
+  if (h->zkind == ZKind::none) h->zkind = reg_ok ? ZKind::reg : ZKind::general;
+  // the other allocation kernels take a column whole (k_zalloc_reg: one wave per column; tile / step: a workgroup's batch): 4,000,000 counts
+  // per column is where that stops being a sensible launch.  The sorted schedule (N <= 24, K <= 1,024, no save_Z) spreads the counts of a
+  // large cell over all blocks and is bounded by its item format only (a cell <= 65,534 fragments of 256 counts = 16.7 M counts).
+  if (h->colmax > 4000000 && !(h->zkind == ZKind::sort && h->zs.shared))
+    return fail(BNMF_EINVAL, "bnmf_create: a column of M sums to %ld (> 4,000,000 counts): unsupported for this model / shape (N <= 24 and K <= 1,024 without save_Z take up to 16.7 M counts per cell)", h->colmax);
+  return 0;
+}
+
+static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* Mf, bnmf_handle* h) {
+  const bool normal = cfg->likelihood == BNMF_NORMAL;
+  const Switches sw = Switches::from_env();
+  CreateClock clk;
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
+  h->n_cu = prop.multiProcessorCount;
+  std::vector<double> mconv;
+  if (int rc = create_streams(h, sw, clk)) return rc;
+  if (int rc = create_data(h, M, Mf, mconv, clk)) return rc;
+  if (int rc = create_small(h, sw)) return rc;
+  if (cfg->learning_rank) if (int rc = create_rank(h, sw)) return rc;
+  if (cfg->MH || normal) if (int rc = create_mh(h, M, Mf, sw)) return rc;
+  if (int rc = create_tables(h, cfg, clk)) return rc;
+  if (!normal) if (int rc = create_zalloc(h, M, sw)) return rc;
   clk.mark("allocation-kernel schedule");
   HIPCHK(hipStreamSynchronize(h->stream));
   refresh_dev(h);
@@ -1126,32 +1036,20 @@ static int create_impl(const bnmf_config* cfg, const int32_t* M, const double* M
 int bnmf_destroy(bnmf_handle* h) {
   if (!h) return 0;
   hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  if (h->side) hipStreamSynchronize(h->side);
-  if (h->side2) hipStreamSynchronize(h->side2);
+  for (hipStream_t st : {h->stream, h->side, h->side2}) if (st) hipStreamSynchronize(st);
   for (int id = 0; id < BNMF_ID_MAX; ++id) {
     Arr& a = h->arr[id];
-    if (a.d && !a.slab) dfree(a.d);
-    if (a.ring) ring_release(h->device, a.ring, (size_t)h->wcap * id_len(h, id) * sizeof(double));
+    if (!a.slab) dfree(a.d);
+    ring_release(h->device, a.ring, (size_t)h->wcap * id_len(h, id) * sizeof(double));
   }
-  dfree(h->dM); dfree(h->dZsumK); dfree(h->dZsumG); if (h->dZ) dfree(h->dZ);
-  dfree(h->dR); dfree(h->dRedraw); dfree(h->dEsum); dfree(h->dPsum); dfree(h->dlpPn);
-  dfree(h->dlpE); dfree(h->dcol); dfree(h->dLut); if (h->dTemp) dfree(h->dTemp); if (h->hMetrics) hipHostFree(h->hMetrics); dfree(h->dRaw); if (h->dRankCol) dfree(h->dRankCol); if (h->dRankMhat) dfree(h->dRankMhat); if (h->dRankSync) dfree(h->dRankSync);
-  if (h->E_alt) dfree(h->E_alt);
-  if (h->dMhatZ) dfree(h->dMhatZ);
-  if (h->zpg.prof) dfree(h->zpg.prof);
-  if (h->dZpItems) dfree(h->dZpItems); if (h->dZpWgs) dfree(h->dZpWgs); if (h->dZpBatches) dfree(h->dZpBatches); if (h->dZpSteps) dfree(h->dZpSteps); if (h->dZpCols) dfree(h->dZpCols);
-  if (h->dZsItems) dfree(h->dZsItems); if (h->dZsBlocks) dfree(h->dZsBlocks); if (h->dZsCols) dfree(h->dZsCols); if (h->dZsProf) dfree(h->dZsProf); if (h->dZsM) dfree(h->dZsM); if (h->dZsRec) dfree(h->dZsRec); if (h->dZsRecRing) dfree(h->dZsRecRing); if (h->dZsMh) dfree(h->dZsMh);
-  if (h->dMhat) dfree(h->dMhat); if (h->dAccPn) dfree(h->dAccPn); if (h->dAccEpart) dfree(h->dAccEpart); if (h->dNzE) dfree(h->dNzE);
-  if (h->dEt) dfree(h->dEt); if (h->dMt) dfree(h->dMt); dfree(h->dMf); dfree(h->dMtf); if (h->zring) dfree(h->zring);
-  if (h->ev_draw) hipEventDestroy(h->ev_draw); if (h->ev_side) hipEventDestroy(h->ev_side); if (h->ev_sideP) hipEventDestroy(h->ev_sideP); if (h->ev_p) hipEventDestroy(h->ev_p); if (h->ev_rank) hipEventDestroy(h->ev_rank); if (h->ev_z) hipEventDestroy(h->ev_z); if (h->ev_red) hipEventDestroy(h->ev_red); give_stream(h->device, h->side, 1); give_stream(h->device, h->side2, 1);
+  dfree(h->E_alt);                                         // (trades places with Arr::d of E every sweep: released like one, not owned)
+  for (void* p : h->owned) dfree(p);                       // every other pooled device block, in the order made
+  for (void* p : {(void*)h->hMetrics, (void*)h->hErr, (void*)h->hStage}) if (p) hipHostFree(p);
+  for (hipEvent_t e : {h->ev_draw, h->ev_side, h->ev_sideP, h->ev_p, h->ev_rank, h->ev_z, h->ev_red}) if (e) hipEventDestroy(e);
   if (h->have_ev) for (auto& e : h->ev) hipEventDestroy(e);
-  if (h->dMap) dfree(h->dMap);
-  if (h->dAsg) dfree(h->dAsg);
   if (h->devlock_fd >= 0) close(h->devlock_fd);
   if (h->devgate_fd >= 0) close(h->devgate_fd);
-  if (h->dFlags) dfree(h->dFlags); if (h->dDrawOwn) dfree(h->dDrawOwn); if (h->dScal) dfree(h->dScal); if (h->hErr) hipHostFree(h->hErr);
-  if (h->hStage) hipHostFree(h->hStage);
+  give_stream(h->device, h->side, 1); give_stream(h->device, h->side2, 1);
   give_stream(h->device, h->stream);                    // synchronised at the top of this function
   delete h;
   return 0;
@@ -1254,20 +1152,20 @@ int bnmf_get_array_i32(bnmf_handle* h, int id, int32_t* out, size_t n) {
 }
 
 int bnmf_debug_rank(bnmf_handle* h, unsigned long long* out, size_t n) {   // diagnostics: phase time stamps of k_rank_sweep
-  if (!h || !h->dRankDbg) return fail(BNMF_ESTATE, "BNMF_RANKDBG not set");
-  HIPCHK(hipMemcpy(out, h->dRankDbg, n * 8, hipMemcpyDeviceToHost));
-  return h->rank_grid;
+  if (!h || !h->rank.dDbg) return fail(BNMF_ESTATE, "BNMF_RANKDBG not set");
+  HIPCHK(hipMemcpy(out, h->rank.dDbg, n * 8, hipMemcpyDeviceToHost));
+  return h->rank.grid;
 }
 #ifdef ZSPROF
 int bnmf_debug_zstamps(bnmf_handle* h, unsigned long long* out) {   // diagnostics (-DZSPROF): [3 blocks][16 waves][8] s_memrealtime stamps of the last k_zalloc_sort
-  if (!h || !h->dZsProf) return fail(BNMF_ESTATE, "not a -DZSPROF build, or the kernel is not in use");
+  if (!h || !h->zs.dProf) return fail(BNMF_ESTATE, "not a -DZSPROF build, or the kernel is not in use");
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(out, h->dZsProf + 8, 3 * 16 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, h->zs.dProf + 8, 3 * 16 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return 0;
 }
 #endif
 int bnmf_debug_zsort(bnmf_handle* h, unsigned long long* out) {   // diagnostics (-DZSPROF / -DZPPROF builds): section ticks of k_zalloc_sort / k_zalloc_step, then reset
-  unsigned long long* src = h ? (h->dZsProf ? h->dZsProf : h->zpg.prof) : nullptr;
+  unsigned long long* src = h ? (h->zs.dProf ? h->zs.dProf : h->zp.g.prof) : nullptr;
   if (!src) return fail(BNMF_ESTATE, "not a -DZSPROF / -DZPPROF build, or the kernel is not in use");
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(out, src, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -1294,14 +1192,14 @@ int bnmf_debug_set_timeout(bnmf_handle* h, int word) {   // tests: what a bounde
 int bnmf_get_stat(bnmf_handle* h, int what, double* out) {   // sizes of the schedule's buffers, for bench.py's byte counts
   if (!h || !out) return fail(BNMF_EINVAL, "bnmf_get_stat: null argument");
   switch (what) {
-    case 0: *out = (double)h->zs_recwords * 4.0; return 0;                                  // bytes of item records per iteration (save_Z, sorted schedule; else 0)
-    case 1: *out = h->dZsMh ? (double)h->cfg.K * h->cfg.G * 8.0 : 0.0; return 0;            // bytes of Mhat left per iteration for the column terms
-    case 2: *out = h->dZsRecRing ? 1.0 : 0.0; return 0;                                     // samples$Z kept as a ring of records
-    case 3: *out = h->zs_eager ? 1.0 : 0.0; return 0;
-    case 5: *out = h->z_sort ? (double)h->zs_qmax : 0.0; return 0;                          // quads per item of the sorted schedule (chosen per data set)
-    case 4: *out = h->mh_pipe ? 1.0 : 0.0; return 0;                                        // MH sweep: k_mh_tail's work hosted by the two sweep kernels
-    case 6: *out = h->z_sort ? (double)h->zsg.nblocks : h->z_step ? (double)h->zpg.nwg : 0.0; return 0;   // blocks (workgroups) of the static schedule
-    case 7: *out = h->z_sort ? (double)h->zs_nempty : 0.0; return 0;                        // ... of them without an own column (k_zalloc_step: never)
+    case 0: *out = (double)h->zs.recwords * 4.0; return 0;                                  // bytes of item records per iteration (save_Z, sorted schedule; else 0)
+    case 1: *out = h->zs.dMh ? (double)h->cfg.K * h->cfg.G * 8.0 : 0.0; return 0;            // bytes of Mhat left per iteration for the column terms
+    case 2: *out = h->zs.dRecRing ? 1.0 : 0.0; return 0;                                     // samples$Z kept as a ring of records
+    case 3: *out = h->zs.eager ? 1.0 : 0.0; return 0;
+    case 5: *out = h->zkind == ZKind::sort ? (double)h->zs.qmax : 0.0; return 0;                          // quads per item of the sorted schedule (chosen per data set)
+    case 4: *out = h->mh.pipe ? 1.0 : 0.0; return 0;                                        // MH sweep: k_mh_tail's work hosted by the two sweep kernels
+    case 6: *out = h->zkind == ZKind::sort ? (double)h->zs.g.nblocks : h->zkind == ZKind::step ? (double)h->zp.g.nwg : 0.0; return 0;   // blocks (workgroups) of the static schedule
+    case 7: *out = h->zkind == ZKind::sort ? (double)h->zs.nempty : 0.0; return 0;                        // ... of them without an own column (k_zalloc_step: never)
     default: return fail(BNMF_EINVAL, "bnmf_get_stat: unknown statistic %d", what);
   }
 }
@@ -1326,8 +1224,8 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
     HIPCHK(hipStreamSynchronize(h->side2));
     HIPCHK(hipMemset(h->dFlags, 0, 64));
     memset(h->hErr, 0, 64);
-    if (h->dRankSync) HIPCHK(hipMemset(h->dRankSync, 0, 32));
-    if (h->dRankCol) HIPCHK(hipMemset(h->dRankCol, 0, (size_t)RK_REP * 4 * 2 * (((size_t)h->cfg.G + RK_MAXC - 1) / RK_MAXC) * sizeof(double)));
+    if (h->rank.dSync) HIPCHK(hipMemset(h->rank.dSync, 0, 32));
+    if (h->rank.dCol) HIPCHK(hipMemset(h->rank.dCol, 0, (size_t)RK_REP * 4 * 2 * (((size_t)h->cfg.G + RK_MAXC - 1) / RK_MAXC) * sizeof(double)));
     HIPCHK(hipMemset(h->dZsumK, 0, (size_t)h->cfg.N * h->cfg.G * sizeof(int32_t)));
     HIPCHK(hipMemset(h->dZsumG, 0, (size_t)h->cfg.K * h->cfg.N * sizeof(int32_t)));
     h->pipe = Pipe{};
@@ -1394,7 +1292,7 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
     hipLaunchKernelGGL(k_rank_Aprior, dim3((N + 63) / 64), dim3(64), 0, h->stream, h->dev, 1u);
   }
   if (c.MH || c.likelihood == BNMF_NORMAL) launch_mh_metrics(h, 1u, true);
-  else { if (int rc = launch_zalloc(h, 1u)) return rc; if (h->z_sort) { h->pipe.ct_pending = 1u; flush_colterms(h); } record_Z(h, 1u); }
+  else { if (int rc = launch_zalloc(h, 1u)) return rc; if (h->zkind == ZKind::sort) { h->pipe.ct_pending = 1u; flush_colterms(h); } record_Z(h, 1u); }
   if (int rc = launch_record(h, 1u)) return rc;
   launch_reduce(h, 1u, 0, tm);
   flush_reduce(h, tm);
@@ -1433,14 +1331,14 @@ int bnmf_window(bnmf_handle* h, int id, int last_n, double* out) {
   if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_window: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
   if (id < 0 || id >= BNMF_ID_MAX) return fail(BNMF_EINVAL, "bnmf_window: unknown id %d", id);
   if (id == BNMF_Z) {
-    if (!h->zring && !h->dZsRecRing) return fail(BNMF_EUNSET, "bnmf_window: Z is not kept per sample (needs save_Z, a window, and the window's samples within BNMF_ZRING_GB)");
+    if (!h->zring && !h->zs.dRecRing) return fail(BNMF_EUNSET, "bnmf_window: Z is not kept per sample (needs save_Z, a window, and the window's samples within BNMF_ZRING_GB)");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t lenz = id_len(h, BNMF_Z);
     std::vector<int32_t> tmp(lenz);
     for (int i = 0; i < last_n; ++i) {
       const size_t slot = (size_t)(h->iter - last_n + i) % (size_t)h->wcap;
-      if (h->dZsRecRing) {                                   // sorted schedule: the sample is its item records; expand them (k_zexpand) and copy
+      if (h->zs.dRecRing) {                                   // sorted schedule: the sample is its item records; expand them (k_zexpand) and copy
         launch_zexpand(h, (uint32_t)(h->iter - last_n + i + 1));
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1540,7 +1438,7 @@ static int map_impl(bnmf_handle* h, int end_iter, int last_n, double ci, double*
   if (want_ci && !qS && (size_t)kt * 2 * 64 * sizeof(double) > 160 * 1024)
     return fail(BNMF_EINVAL, "bnmf_map: credible_interval %.3g over %d samples needs %d order statistics per element (device limit 160): take the window with bnmf_window", ci, nu, kt);
   const size_t words = (size_t)nu * N + 3 * (lenP + lenE) + 2 * (size_t)G + N + ((size_t)nu + 1) / 2 + 8;
-  if (words > h->map_words) { if (h->dMap) HIPCHK(dfree(h->dMap)); h->dMap = nullptr; HIPCHK(dmalloc(&h->dMap, words * sizeof(double))); h->map_words = words; }
+  if (words > h->map_words) { HIPCHK(hfree(h, h->dMap)); HIPCHK(hmalloc(h, &h->dMap, words * sizeof(double))); h->map_words = words; }
   double* cs = h->dMap; double* mP = cs + (size_t)nu * N; double* loP = mP + lenP; double* hiP = loP + lenP;
   double* mE = hiP + lenP; double* loE = mE + lenE; double* hiE = loE + lenE;
   double* colsse = hiE + lenE; double* colkl = colsse + G; double* dA = colkl + G; int* dslots = (int*)(dA + N);
@@ -1744,8 +1642,8 @@ static int assign_impl(bnmf_handle* h, int end_iter, int last_n, const int32_t* 
   const size_t oRef = 0, oN2 = oRef + up(refT.size() * 8), oOut = oN2 + up((size_t)R * 8), oSl = oOut + up(nout * 8), oSig = oSl + up((size_t)nu * sizeof(int)),
                oCol = oSig + up((size_t)nk * sizeof(int)), need = oCol + up((size_t)nu * std::min(nk, R) * sizeof(int32_t));
   if (need > h->asg_bytes) {
-    if (h->dAsg) { HIPCHK(dfree(h->dAsg)); h->dAsg = nullptr; h->asg_bytes = 0; }
-    HIPCHK(dmalloc(&h->dAsg, need));
+    HIPCHK(hfree(h, h->dAsg)); h->asg_bytes = 0;
+    HIPCHK(hmalloc(h, &h->dAsg, need));
     h->asg_bytes = need;
   }
   double *dRef = (double*)(h->dAsg + oRef), *dN2 = (double*)(h->dAsg + oN2), *dOut = (double*)(h->dAsg + oOut);
@@ -1855,8 +1753,8 @@ int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, cons
                oCos = oSig + up((size_t)N * sizeof(int)), oCol = oCos + up((size_t)chunk * per),
                need = oCol + up((size_t)chunk * nrow * sizeof(int32_t));
   if (need > h->asg_bytes) {                                             // bnmf_assign's scratch, grown on demand
-    if (h->dAsg) { HIPCHK(dfree(h->dAsg)); h->dAsg = nullptr; h->asg_bytes = 0; }
-    HIPCHK(dmalloc(&h->dAsg, need));
+    HIPCHK(hfree(h, h->dAsg)); h->asg_bytes = 0;
+    HIPCHK(hmalloc(h, &h->dAsg, need));
     h->asg_bytes = need;
   }
   double *dRef = (double*)(h->dAsg + oRef), *dN2 = (double*)(h->dAsg + oN2), *dCs = (double*)(h->dAsg + oCs);

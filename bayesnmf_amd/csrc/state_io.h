@@ -143,7 +143,7 @@ int plan_record(bnmf_handle* h, int since, std::vector<Sec>& out) {
   if (h->dZ) {
     if (int rc = ensure_Z(h)) return rc;                       // (the sorted schedule keeps Z as records: expanded for the file)
     out.push_back(dev(SEC_Z, BNMF_Z, (int64_t)(K * N * G), 4, h->dZ));
-    if (h->dZsRec && !h->dZsRecRing) out.push_back(dev(SEC_ZREC, 0, (int64_t)h->zs_recwords, 4, h->dZsRec));
+    if (h->zs.dRec && !h->zs.dRecRing) out.push_back(dev(SEC_ZREC, 0, (int64_t)h->zs.recwords, 4, h->zs.dRec));
   }
   int64_t first = 0, ns = 0;
   kept_range(h, since, &first, &ns);
@@ -162,9 +162,9 @@ int plan_record(bnmf_handle* h, int since, std::vector<Sec>& out) {
       ring_runs((size_t)h->wcap, first, ns, len * 4, h->zring, s.run_p, s.run_n);
       out.push_back(s);
     }
-    if (h->dZsRecRing) {
-      Sec s{SEC_ZRECRING, 0, first, ns * (int64_t)h->zs_recwords, 4};
-      ring_runs((size_t)h->wcap, first, ns, h->zs_recwords * 4, h->dZsRecRing, s.run_p, s.run_n);
+    if (h->zs.dRecRing) {
+      Sec s{SEC_ZRECRING, 0, first, ns * (int64_t)h->zs.recwords, 4};
+      ring_runs((size_t)h->wcap, first, ns, h->zs.recwords * 4, h->zs.dRecRing, s.run_p, s.run_n);
       out.push_back(s);
     }
   }
@@ -318,7 +318,7 @@ int sec_dest(bnmf_handle* h, int ri, int iter, uint32_t kind, int id, int64_t fi
     case SEC_ZSUMK: return one(h->dZsumK, N * G, 4);
     case SEC_ZSUMG: return one(h->dZsumG, K * N, 4);
     case SEC_Z: if (!h->dZ) return bad("Z in the file, save_Z off in the handle"); return one(h->dZ, K * N * G, 4);
-    case SEC_ZREC: if (!h->dZsRec || h->dZsRecRing) return bad("Z records the handle does not keep"); return one(h->dZsRec, h->zs_recwords, 4);
+    case SEC_ZREC: if (!h->zs.dRec || h->zs.dRecRing) return bad("Z records the handle does not keep"); return one(h->zs.dRec, h->zs.recwords, 4);
     case SEC_HIST: if (h->wcap <= 0) return bad("a history without a window"); return one(nullptr, (size_t)h->wcap * 4, 8);
     case SEC_RING: case SEC_ZRING: case SEC_ZRECRING: {
       const int64_t lo = std::max<int64_t>(1, (int64_t)iter - h->cfg.window + 1);
@@ -331,8 +331,8 @@ int sec_dest(bnmf_handle* h, int ri, int iter, uint32_t kind, int id, int64_t fi
         if (!h->zring) return bad("a Z ring this handle does not keep");
         slot = id_len(h, BNMF_Z); base = h->zring; wes = 4;
       } else {
-        if (!h->dZsRecRing) return bad("a ring of Z records this handle does not keep");
-        slot = h->zs_recwords; base = h->dZsRecRing; wes = 4;
+        if (!h->zs.dRecRing) return bad("a ring of Z records this handle does not keep");
+        slot = h->zs.recwords; base = h->zs.dRecRing; wes = 4;
       }
       if (es != wes || slot == 0 || count % (int64_t)slot != 0) return bad("ring section size does not match the handle");
       const int64_t ns = count / (int64_t)slot;
@@ -481,8 +481,8 @@ int bnmf_load_state(bnmf_handle* h, const char* path, int* iter_out) {
   // bnmf_init's re-initialisation does it; the sync words are cleared — a handle from the pool may hold another chain's
   HIPCHK(hipMemset(h->dFlags, 0, 64));
   memset(h->hErr, 0, 64);
-  if (h->dRankSync) HIPCHK(hipMemset(h->dRankSync, 0, 32));
-  if (h->dRankCol) HIPCHK(hipMemset(h->dRankCol, 0, (size_t)RK_REP * 4 * 2 * (((size_t)h->cfg.G + RK_MAXC - 1) / RK_MAXC) * sizeof(double)));
+  if (h->rank.dSync) HIPCHK(hipMemset(h->rank.dSync, 0, 32));
+  if (h->rank.dCol) HIPCHK(hipMemset(h->rank.dCol, 0, (size_t)RK_REP * 4 * 2 * (((size_t)h->cfg.G + RK_MAXC - 1) / RK_MAXC) * sizeof(double)));
   HIPCHK(hipMemset(h->dDrawOwn, 0, (size_t)h->cfg.N * sizeof(unsigned)));
   h->draw_seq = 0;
   h->pipe = Pipe{};

@@ -18,8 +18,8 @@ static int ensure_metrics(bnmf_handle* h, size_t rows) {
   h->metrics_rows = rows;
   HIPCHK(hipHostMalloc((void**)&h->hMetrics, rows * BNMF_NMETRIC * sizeof(double), hipHostMallocMapped));
   HIPCHK(hipHostGetDevicePointer((void**)&h->dMetrics, h->hMetrics, 0));
-  HIPCHK(dfree(h->dRaw));
-  HIPCHK(dmalloc(&h->dRaw, rows * 8 * sizeof(double)));
+  HIPCHK(hfree(h, h->dRaw));
+  HIPCHK(hmalloc(h, &h->dRaw, rows * 8 * sizeof(double)));
   refresh_dev(h);
   return 0;
 }
@@ -35,8 +35,8 @@ static void set_slot(const bnmf_handle* h, Dev& d, uint32_t t) {
   d.lpPn = h->dlpPn + sl * N;
 }
 static void use_slot(bnmf_handle* h, uint32_t t) { set_slot(h, h->dev, t); }
-static double* accPn_slot(const bnmf_handle* h, uint32_t t) { return h->dAccPn ? h->dAccPn + (size_t)(t % 3u) * h->cfg.N : nullptr; }
-static double* accEp_slot(const bnmf_handle* h, uint32_t t) { return h->dAccEpart ? h->dAccEpart + (size_t)(t % 3u) * h->nblkE : nullptr; }
+static double* accPn_slot(const bnmf_handle* h, uint32_t t) { return h->mh.dAccPn ? h->mh.dAccPn + (size_t)(t % 3u) * h->cfg.N : nullptr; }
+static double* accEp_slot(const bnmf_handle* h, uint32_t t) { return h->mh.dAccEpart ? h->mh.dAccEpart + (size_t)(t % 3u) * h->nblkE : nullptr; }
 struct Timer {   // optional per-kernel HIP-event bracketing (serialises the two streams: profile mode only)
   bnmf_handle* h; bool on; double acc[BNMF_NKERNEL]{}; int cnt[BNMF_NKERNEL]{};
   void begin(int k, hipStream_t st) { if (on) { hipStreamSynchronize(h->stream); hipStreamSynchronize(h->side); hipStreamSynchronize(h->side2); hipEventRecord(h->ev[2 * k], st); } }
@@ -101,7 +101,7 @@ static RedSlots take_reduce_slots(bnmf_handle* h) {
 static CtArgs ct_args(const bnmf_handle* h, uint32_t t) {
   const size_t G = h->cfg.G;
   double* sse = h->dcol + (size_t)(t % 3u) * 3 * G;
-  return CtArgs{h->dZsMh + (size_t)(t % 3u) * h->cfg.K * G, h->dev.M, h->dev.lgfact, h->dev.logm, sse, sse + G, sse + 2 * G, h->cfg.K, h->cfg.G, h->dev.maxM};
+  return CtArgs{h->zs.dMh + (size_t)(t % 3u) * h->cfg.K * G, h->dev.M, h->dev.lgfact, h->dev.logm, sse, sse + G, sse + 2 * G, h->cfg.K, h->cfg.G, h->dev.maxM};
 }
 // The pending column terms, taken by the launch that will sum them: its arguments and n_ct workgroups (two columns per wavefront; k_colterms
 // and k_side_lp's extra workgroups have the same shape).  Nothing pending: CtArgs{}, 0.
@@ -286,7 +286,7 @@ static int raise_lds_limit(bnmf_handle* h, const void* kern) {
 template <typename KernelT, typename ArgT>
 static int launch_z(bnmf_handle* h, uint32_t t, KernelT kern, const ArgT& arg, int zt) {
   if (int rc = raise_lds_limit(h, (const void*)kern)) return rc;
-  hipLaunchKernelGGL(kern, dim3(h->z_grid), dim3(zt), h->z_lds, h->stream, arg, t, h->zg, h->z_ablate);
+  hipLaunchKernelGGL(kern, dim3(h->zw.grid), dim3(zt), h->zw.lds, h->stream, arg, t, h->zw.g, h->z_ablate);
   return 0;
 }
 static ZArgs zargs(const bnmf_handle* h) {
@@ -298,7 +298,7 @@ static ZArgs zargs(const bnmf_handle* h) {
 template <bool SZ, int ZT_, bool DIAG>
 static int launch_zreg_t(bnmf_handle* h, uint32_t t) {
   const ZArgs za = zargs(h);
-  switch (h->zg.TR) {
+  switch (h->zw.g.TR) {
     case 8: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 8, DIAG>, za, ZT_);
     case 16: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 16, DIAG>, za, ZT_);
     case 20: return launch_z(h, t, k_zalloc_reg<SZ, ZT_, 20, DIAG>, za, ZT_);
@@ -310,22 +310,22 @@ static int launch_ztile(bnmf_handle* h, uint32_t t) {
   auto kern = k_zalloc_tile<SZ, ZT_, LEAN_>;
   if (int rc = raise_lds_limit(h, (const void*)kern)) return rc;
   const ZArgs za = zargs(h);
-  hipLaunchKernelGGL(kern, dim3(h->z_grid), dim3(ZT_), h->z_lds, h->stream, za, h->dMhatZ, t, h->ztg);
-  hipLaunchKernelGGL(k_colmetrics<256>, dim3((h->cfg.G + 3) / 4), dim3(256), 0, h->stream, za, (const double*)h->dMhatZ);
-  if (h->ztg.dbg) {                                        // BNMF_ZTDBG: section cycles (100 MHz s_memtime ticks) per launch
+  hipLaunchKernelGGL(kern, dim3(h->zt.grid), dim3(ZT_), h->zt.lds, h->stream, za, h->zt.dMhat, t, h->zt.g);
+  hipLaunchKernelGGL(k_colmetrics<256>, dim3((h->cfg.G + 3) / 4), dim3(256), 0, h->stream, za, (const double*)h->zt.dMhat);
+  if (h->zt.g.dbg) {                                        // BNMF_ZTDBG: section cycles (100 MHz s_memtime ticks) per launch
     unsigned long long v[8];
     hipStreamSynchronize(h->stream);
-    hipMemcpy(v, h->ztg.dbg, sizeof v, hipMemcpyDeviceToHost);
-    hipMemset(h->ztg.dbg, 0, sizeof v);
+    hipMemcpy(v, h->zt.g.dbg, sizeof v, hipMemcpyDeviceToHost);
+    hipMemset(h->zt.g.dbg, 0, sizeof v);
     if (v[0]) fprintf(stderr, "[ztile t=%u] waves %llu grid %d w %d lds %zu  per wave: phase1 %.1f  phase2 %.1f  flush %.1f  columns %.1f  kernel %.1f (s_memtime ticks)\n",
-                      t, v[0], h->z_grid, h->z_zw, h->z_lds, (double)v[1] / v[0], (double)v[2] / v[0], (double)v[3] / v[0], (double)v[4] / v[0], (double)v[5] / v[0]);
+                      t, v[0], h->zt.grid, h->zt.w, h->zt.lds, (double)v[1] / v[0], (double)v[2] / v[0], (double)v[3] / v[0], (double)v[4] / v[0], (double)v[5] / v[0]);
   }
   return 0;
 }
 template <bool SZ, int ZT_>
 static int launch_zalloc_t(bnmf_handle* h, uint32_t t) {
-  if (h->z_tile) return (h->z_lean && ZT_ == 1024) ? launch_ztile<SZ, ZT_, (ZT_ == 1024)>(h, t) : launch_ztile<SZ, ZT_, false>(h, t);
-  if (!h->z_reg) return launch_z(h, t, k_zalloc<SZ, ZT_>, h->dev, ZT_);
+  if (h->zkind == ZKind::tile) return (h->zt.lean && ZT_ == 1024) ? launch_ztile<SZ, ZT_, (ZT_ == 1024)>(h, t) : launch_ztile<SZ, ZT_, false>(h, t);
+  if (h->zkind == ZKind::general) return launch_z(h, t, k_zalloc<SZ, ZT_>, h->dev, ZT_);
 #ifdef BNMF_DIAG
   if (h->z_ablate) return launch_zreg_t<SZ, ZT_, true>(h, t);   // the DIAG instantiation honours BNMF_ABLATE
 #endif
@@ -334,17 +334,17 @@ static int launch_zalloc_t(bnmf_handle* h, uint32_t t) {
 static int zs_prio() { static const int v = getenv("BNMF_ZSPRIO") ? atoi(getenv("BNMF_ZSPRIO")) : 1; return v; }   // A/B: 0 = the allocation kernel at default issue priority
 // where the item records of iteration t go (save_Z on the sorted schedule): the sample's slot of the record ring, or the one buffer
 static uint32_t* zs_rec_at(const bnmf_handle* h, uint32_t t) {
-  if (!h->dZsRec) return nullptr;
-  return h->dZsRecRing ? h->dZsRecRing + (size_t)((t - 1) % (uint32_t)h->wcap) * h->zs_recwords : h->dZsRec;
+  if (!h->zs.dRec) return nullptr;
+  return h->zs.dRecRing ? h->zs.dRecRing + (size_t)((t - 1) % (uint32_t)h->wcap) * h->zs.recwords : h->zs.dRec;
 }
 // Z[k, n, g] of iteration t from its records into h->dZ (main stream)
 static void launch_zexpand(bnmf_handle* h, uint32_t t) {
-  const ZSArgs sa{zargs(h), h->dZsItems, h->dZsBlocks, h->dZsCols, h->dZsM, h->zs_it16, h->zs_qmax, zs_rec_at(h, t), nullptr, 0, 0, h->dZsProf};
-  hipLaunchKernelGGL(k_zexpand, dim3(h->zsg.nblocks), dim3(ZX_T), h->zx_lds, h->stream, sa, h->zx_cols);
+  const ZSArgs sa{zargs(h), h->zs.dItems, h->zs.dBlocks, h->zs.dCols, h->zs.dM, h->zs.it16, h->zs.qmax, zs_rec_at(h, t), nullptr, 0, 0, h->zs.dProf};
+  hipLaunchKernelGGL(k_zexpand, dim3(h->zs.g.nblocks), dim3(ZX_T), h->zs.x_lds, h->stream, sa, h->zs.x_cols);
   h->pipe.z_expanded_iter = (int)t;
 }
 static int ensure_Z(bnmf_handle* h) {
-  if (!h->z_sort || !h->dZsRec || !h->cfg.save_Z || h->iter < 1 || h->pipe.z_expanded_iter == h->iter) return 0;
+  if (h->zkind != ZKind::sort || !h->zs.dRec || !h->cfg.save_Z || h->iter < 1 || h->pipe.z_expanded_iter == h->iter) return 0;
   HIPCHK(hipSetDevice(h->device));
   launch_zexpand(h, (uint32_t)h->iter);
   HIPCHK(hipGetLastError());
@@ -353,24 +353,24 @@ static int ensure_Z(bnmf_handle* h) {
 }
 template <int ZT_>
 static int launch_zsort_t(bnmf_handle* h, uint32_t t) {
-  const ZSArgs sa{zargs(h), h->dZsItems, h->dZsBlocks, h->dZsCols, h->dZsM, h->zs_it16, h->zs_qmax, zs_rec_at(h, t), h->dZsMh + (size_t)(t % 3u) * h->cfg.K * h->cfg.G, zs_prio(), h->zs_shared ? 1 : 0, h->dZsProf};
+  const ZSArgs sa{zargs(h), h->zs.dItems, h->zs.dBlocks, h->zs.dCols, h->zs.dM, h->zs.it16, h->zs.qmax, zs_rec_at(h, t), h->zs.dMh + (size_t)(t % 3u) * h->cfg.K * h->cfg.G, zs_prio(), h->zs.shared ? 1 : 0, h->zs.dProf};
   auto go = [&](auto kern) -> int {
     if (int rc = raise_lds_limit(h, (const void*)kern)) return rc;
-    hipLaunchKernelGGL(kern, dim3(h->zsg.nblocks), dim3(ZT_), h->zs_lds, h->stream, sa, t, h->zsg);
+    hipLaunchKernelGGL(kern, dim3(h->zs.g.nblocks), dim3(ZT_), h->zs.lds, h->stream, sa, t, h->zs.g);
     return 0;
   };
 #ifdef BNMF_FASTBUILD   /* builder's experiment builds only (one allocation kernel: the metric configuration's): never the product */
-  if (h->zs_nblk != 4) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only N = 16..20");
-  return h->zs_pk ? go(k_zalloc_sort<ZT_, 4, true>) : go(k_zalloc_sort<ZT_, 4, false>);
+  if (h->zs.nblk != 4) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only N = 16..20");
+  return h->zs.pk ? go(k_zalloc_sort<ZT_, 4, true>) : go(k_zalloc_sort<ZT_, 4, false>);
 #else
-  if (h->zs_pk) switch (h->zs_nblk) {
+  if (h->zs.pk) switch (h->zs.nblk) {
     case 1: return go(k_zalloc_sort<ZT_, 1, true>);
     case 2: return go(k_zalloc_sort<ZT_, 2, true>);
     case 3: return go(k_zalloc_sort<ZT_, 3, true>);
     case 4: return go(k_zalloc_sort<ZT_, 4, true>);
     default: return go(k_zalloc_sort<ZT_, 5, true>);
   }
-  switch (h->zs_nblk) {
+  switch (h->zs.nblk) {
     case 1: return go(k_zalloc_sort<ZT_, 1, false>);
     case 2: return go(k_zalloc_sort<ZT_, 2, false>);
     case 3: return go(k_zalloc_sort<ZT_, 3, false>);
@@ -381,11 +381,11 @@ static int launch_zsort_t(bnmf_handle* h, uint32_t t) {
 }
 static int launch_zsort(bnmf_handle* h, uint32_t t) {
 #ifdef BNMF_FASTBUILD
-  if (h->zs_w == 14) return launch_zsort_t<896>(h, t);
-  if (h->zs_w != 12) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only 12 or 14 waves");
+  if (h->zs.w == 14) return launch_zsort_t<896>(h, t);
+  if (h->zs.w != 12) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only 12 or 14 waves");
   return launch_zsort_t<768>(h, t);
 #else
-  switch (h->zs_w) {
+  switch (h->zs.w) {
     case 16: return launch_zsort_t<1024>(h, t);
     case 14: return launch_zsort_t<896>(h, t);
     case 12: return launch_zsort_t<768>(h, t);
@@ -396,28 +396,33 @@ static int launch_zsort(bnmf_handle* h, uint32_t t) {
 #endif
 }
 static int launch_zstep(bnmf_handle* h, uint32_t t) {
-  const ZPArgs pa{zargs(h), h->dZpItems, h->zp_it16 ? 1 : 0, h->dZpWgs, h->dZpBatches, h->dZpSteps, h->dZpCols};
+  const ZPArgs pa{zargs(h), h->zp.dItems, h->zp.it16 ? 1 : 0, h->zp.dWgs, h->zp.dBatches, h->zp.dSteps, h->zp.dCols};
   auto go = [&](auto kern) -> int {
     if (int rc = raise_lds_limit(h, (const void*)kern)) return rc;
-    hipLaunchKernelGGL(kern, dim3(h->zpg.nwg), dim3(h->zp_ns * 64), h->zp_lds, h->stream, pa, t, h->zpg);
+    hipLaunchKernelGGL(kern, dim3(h->zp.g.nwg), dim3(h->zp.ns * 64), h->zp.lds, h->stream, pa, t, h->zp.g);
     return 0;
   };
-  return h->zp_gbp == 40 ? go(k_zalloc_step<4, 40, 8>) : go(k_zalloc_step<4, 32, 8>);
+  return h->zp.gbp == 40 ? go(k_zalloc_step<4, 40, 8>) : go(k_zalloc_step<4, 32, 8>);
 }
 static int launch_zalloc(bnmf_handle* h, uint32_t t) {
-  if (h->z_sort) {
-    if (int rc = launch_zsort(h, t)) return rc;
-    // save_Z: the items' records ARE the sample (zs_rec_at); Z is expanded from them when it is read (ensure_Z, bnmf_window)
-    if (h->cfg.save_Z && h->zs_eager) launch_zexpand(h, t);
-    return 0;
+  int w = 0;                                               // waves per workgroup of the three kernels instantiated by width
+  switch (h->zkind) {
+    case ZKind::none: return fail(BNMF_ESTATE, "launch_zalloc: the handle allocates no counts");
+    case ZKind::sort:
+      if (int rc = launch_zsort(h, t)) return rc;
+      // save_Z: the items' records ARE the sample (zs_rec_at); Z is expanded from them when it is read (ensure_Z, bnmf_window)
+      if (h->cfg.save_Z && h->zs.eager) launch_zexpand(h, t);
+      return 0;
+    case ZKind::step: return launch_zstep(h, t);
+    case ZKind::tile: w = h->zt.w; break;
+    case ZKind::reg: case ZKind::general: w = h->zw.w; break;
   }
-  if (h->z_step) return launch_zstep(h, t);
   const bool sz = h->cfg.save_Z != 0;
 #ifdef BNMF_FASTBUILD
-  if (h->z_zw != 16) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only 16 waves");
+  if (w != 16) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only 16 waves");
   return sz ? launch_zalloc_t<true, 1024>(h, t) : launch_zalloc_t<false, 1024>(h, t);
 #else
-  switch (h->z_zw) {
+  switch (w) {
     case 16: return sz ? launch_zalloc_t<true, 1024>(h, t) : launch_zalloc_t<false, 1024>(h, t);
     case 8: return sz ? launch_zalloc_t<true, 512>(h, t) : launch_zalloc_t<false, 512>(h, t);
     case 6: return sz ? launch_zalloc_t<true, 384>(h, t) : launch_zalloc_t<false, 384>(h, t);
@@ -435,11 +440,11 @@ static void launch_rank(bnmf_handle* h, uint32_t t, hipEvent_t stop = nullptr, i
   const size_t lds = (3 * (size_t)N + 1) * sizeof(double);            // A, sample_R weights, sample_An uniforms
   const RecDst rr = row >= 0 ? rec_at(h, t, fused_rec(h)) : RecDst{};
   auto go = [&](auto kern) {
-    hipExtLaunchKernelGGL(kern, dim3(h->rank_grid), dim3(h->rank_half ? RK_TH : RK_T), (uint32_t)lds, h->stream, nullptr, stop, 0, h->dev, t, (unsigned long long*)h->dRankCol, NB, h->dErr + 1, h->dRankMhat, (unsigned long long*)h->dRankDbg, row, rr.A, rr.R);
+    hipExtLaunchKernelGGL(kern, dim3(h->rank.grid), dim3(h->rank.half ? RK_TH : RK_T), (uint32_t)lds, h->stream, nullptr, stop, 0, h->dev, t, (unsigned long long*)h->rank.dCol, NB, h->dErr + 1, h->rank.dMhat, (unsigned long long*)h->rank.dDbg, row, rr.A, rr.R);
   };
   const bool nrm = h->cfg.likelihood == BNMF_NORMAL;
-  if (h->rank_half) { if (nrm) go(k_rank_sweep<true, true, true>); else go(k_rank_sweep<true, false, true>); }
-  else if (h->rank_reg) { if (nrm) go(k_rank_sweep<true, true>); else go(k_rank_sweep<true, false>); }
+  if (h->rank.half) { if (nrm) go(k_rank_sweep<true, true, true>); else go(k_rank_sweep<true, false, true>); }
+  else if (h->rank.reg) { if (nrm) go(k_rank_sweep<true, true>); else go(k_rank_sweep<true, false>); }
   else { if (nrm) go(k_rank_sweep<false, true>); else go(k_rank_sweep<false, false>); }
 }
 // ids recorded per iteration (names(self$params) + names(self$prior_params), R/bayesNMF_sampler.R:245-252)
@@ -459,16 +464,10 @@ static int ensure_rings(bnmf_handle* h) {
     Arr& a = h->arr[id];
     if (!a.ring) if (int rc = ring_alloc(h->device, (size_t)h->wcap * id_len(h, id) * sizeof(double), &a.ring)) return rc;
   }
-  if (h->dZ && h->z_sort && h->dZsRec) {                   // samples$Z on the sorted schedule: a ring of item records (zs_rec_at)
-    if (!h->dZsRecRing) {
-      const double gb = (double)h->wcap * (double)h->zs_recwords * 4.0 / 1e9;
-      const char* e = getenv("BNMF_ZRING_GB");
-      if (gb <= (e ? atof(e) : 32.0)) HIPCHK(dmalloc(&h->dZsRecRing, (size_t)h->wcap * h->zs_recwords * sizeof(uint32_t)));
-    }
-  } else if (h->dZ && !h->zring) {                         // samples$Z (R/bayesNMF_sampler.R:245-252): K*N*G ints per kept sample
-    const double gb = (double)h->wcap * (double)id_len(h, BNMF_Z) * 4.0 / 1e9;
-    const char* e = getenv("BNMF_ZRING_GB");
-    if (gb <= (e ? atof(e) : 32.0)) HIPCHK(dmalloc(&h->zring, (size_t)h->wcap * id_len(h, BNMF_Z) * sizeof(int32_t)));
+  const bool recs = h->zkind == ZKind::sort && h->zs.dRec;   // samples$Z on the sorted schedule: a ring of item records (zs_rec_at)
+  if (h->dZ && !(recs ? (void*)h->zs.dRecRing : (void*)h->zring)) {   // else (R/bayesNMF_sampler.R:245-252) K*N*G ints per kept sample
+    const size_t bytes = (size_t)h->wcap * (recs ? h->zs.recwords : id_len(h, BNMF_Z)) * 4;
+    if ((double)bytes / 1e9 <= env_real("BNMF_ZRING_GB", 32.0)) HIPCHK(recs ? hmalloc(h, &h->zs.dRecRing, bytes) : hmalloc(h, &h->zring, bytes));
   }
   return 0;
 }
@@ -553,20 +552,20 @@ static MhEcol16 mh_ecol16_kernel(bool mhstep, int gw, bool k96, bool normal) {
   if constexpr (!METRICS) if (mhstep) return mh_ecol16_shape<false, true, false>(gw, k96);
   return mh_ecol16_shape<METRICS, false, false>(gw, k96);
 }
-static bool mh_ecol16_k96(const bnmf_handle* h) { return h->cfg.K <= 96 && !h->mhe_k128; }   // BNMF_MHE_K128=1: the 128-row form also where K <= 96
+static bool mh_ecol16_k96(const bnmf_handle* h) { return h->cfg.K <= 96 && !h->mh.e_k128; }   // BNMF_MHE_K128=1: the 128-row form also where K <= 96
 static void launch_mh_PE(bnmf_handle* h, uint32_t t, int converged, bool poll = false, const MhPipe* pp = nullptr) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G, S = h->mh_S;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G, S = h->mh.S;
   const bool normal = h->cfg.likelihood == BNMF_NORMAL;
   const int mhstep = (h->cfg.MH && converged && !normal) ? 1 : 0;
   if (pp) {
     if (!h->pipe.mh_pipe_valid) {                                 // first hosted sweep after init / set_array / a sweep of the other form
-      hipMemsetAsync(h->dNzE + 2 * N, 0, 4 * N * sizeof(int), h->stream);
-      hipLaunchKernelGGL(k_mh_nz, dim3(N), dim3(256), 0, h->stream, h->dev, h->dNzE + 2 * N + ((t - 1) & 1u) * N);
+      hipMemsetAsync(h->mh.dNzE + 2 * N, 0, 4 * N * sizeof(int), h->stream);
+      hipLaunchKernelGGL(k_mh_nz, dim3(N), dim3(256), 0, h->stream, h->dev, h->mh.dNzE + 2 * N + ((t - 1) & 1u) * N);
       h->pipe.mh_pipe_valid = true; h->pipe.mh_prep_valid = false;
     }
   } else if (!h->pipe.mh_prep_valid) {                            // first sweep after init / set_array; afterwards k_mh_tail prepares them
-    hipMemsetAsync(h->dNzE, 0, 2 * N * sizeof(int), h->stream);         // nzE[N], nzP[N]
-    hipLaunchKernelGGL(k_mh_nz, dim3(N), dim3(256), 0, h->stream, h->dev, h->dNzE);
+    hipMemsetAsync(h->mh.dNzE, 0, 2 * N * sizeof(int), h->stream);         // nzE[N], nzP[N]
+    hipLaunchKernelGGL(k_mh_nz, dim3(N), dim3(256), 0, h->stream, h->dev, h->mh.dNzE);
     h->pipe.mh_prep_valid = true; h->pipe.mh_pipe_valid = false;
   }
   assert(!(h->pipe.mh_prep_valid && h->pipe.mh_pipe_valid));
@@ -574,21 +573,21 @@ static void launch_mh_PE(bnmf_handle* h, uint32_t t, int converged, bool poll = 
   const bool regP = S <= MHP_W;                              // one 320-column segment per wave: the row's cells stay in registers
   const size_t ldsP = (4 * (size_t)S + 2 * N + 2 + (size_t)(PRE_W + 2) * N + ((regP && mhstep) ? (size_t)MH_CPL * MHP_T : 0)) * sizeof(double);
   const bool pipe = pp != nullptr;                         // hosted form (sweep_mh): parity flag buffers, hosted workgroups behind the rows / the column blocks
-  int* const nzb = h->dNzE + 2 * N;                        // nzE[2][N], nzP[2][N]
-  const int* nzE_in = pipe ? nzb + ((t - 1) & 1u) * N : h->dNzE;
-  int* nzP_io = pipe ? nzb + 2 * N + (t & 1u) * N : h->dNzE + N;
+  int* const nzb = h->mh.dNzE + 2 * N;                        // nzE[2][N], nzP[2][N]
+  const int* nzE_in = pipe ? nzb + ((t - 1) & 1u) * N : h->mh.dNzE;
+  int* nzP_io = pipe ? nzb + 2 * N + (t & 1u) * N : h->mh.dNzE + N;
   const MhETail et = pipe ? pp->et : MhETail{};
   const int nhostP = pipe ? mh_etail_groups(et, N, MHP_T / ES_T) : 0;
   const size_t ldsPx = pipe ? std::max<size_t>(ldsP, MHP_T * sizeof(double)) : ldsP;
-  auto goP = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(K + nhostP), dim3(MHP_T), ldsPx, h->stream, h->dev, t, S, nzE_in, nzP_io, accP, h->dMhat, h->dMhat + (size_t)K * h->cfg.G,
+  auto goP = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(K + nhostP), dim3(MHP_T), ldsPx, h->stream, h->dev, t, S, nzE_in, nzP_io, accP, h->mh.dMhat, h->mh.dMhat + (size_t)K * h->cfg.G,
                                                 poll ? SideWait{h->dFlags + 1, h->dFlags + 1, t, h->dErr} : SideWait{}, et); };
   if (normal) { if (regP) goP(k_mh_prow<true, true, false>); else goP(k_mh_prow<true, false, false>); }
   else if (mhstep) { if (regP) goP(k_mh_prow<false, true, true>); else goP(k_mh_prow<false, false, true>); }
   else { if (regP) goP(k_mh_prow<false, true, false>); else goP(k_mh_prow<false, false, false>); }
   int grid = (G + 3) / 4; if (grid > 2048) grid = 2048;
-  if (h->mhe16) {                                          // several columns per wave
+  if (h->mh.e16) {                                          // several columns per wave
     // lanes per column: 16 for the Gibbs-only sweep, 32 with the MH step (measured at config 3: 117 / 126 us and 276 / 205 us)
-    const int gw = h->mhe_gw ? h->mhe_gw : (mhstep ? 32 : 16), cpw = 64 / gw;
+    const int gw = h->mh.e_gw ? h->mh.e_gw : (mhstep ? 32 : 16), cpw = 64 / gw;
     int g16 = ((G + cpw - 1) / cpw + 3) / 4; if (g16 > 2048) g16 = 2048;
     const size_t lds16 = (4 * (size_t)cpw * N * (1 + PRE_W) + 2 * (size_t)N) * sizeof(double);
     const MhPTail pt = pipe ? pp->pt : MhPTail{};
@@ -598,25 +597,25 @@ static void launch_mh_PE(bnmf_handle* h, uint32_t t, int converged, bool poll = 
     const MhEcol16 kern = mh_ecol16_kernel<false>(mhstep != 0, gw, mh_ecol16_k96(h), normal);
     hipLaunchKernelGGL(kern, dim3(g16 + nhostE), dim3(MHE_T), lds16x, h->stream, h->dev, t, (const int*)nzP_io, accE, 0, nzE_set, g16, pt);
   } else if (normal)
-  hipLaunchKernelGGL((k_mh_ecol<false, true>), dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)(h->dNzE + N), accE, 0);
+  hipLaunchKernelGGL((k_mh_ecol<false, true>), dim3(grid), dim3(MHE_T), h->mh.e_lds, h->stream, h->dev, t, 0, (const int*)(h->mh.dNzE + N), accE, 0);
   else
-  hipLaunchKernelGGL(k_mh_ecol<false>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, mhstep, (const int*)(h->dNzE + N), accE, 0);
+  hipLaunchKernelGGL(k_mh_ecol<false>, dim3(grid), dim3(MHE_T), h->mh.e_lds, h->stream, h->dev, t, mhstep, (const int*)(h->mh.dNzE + N), accE, 0);
 }
 static int launch_mh_metrics(bnmf_handle* h, uint32_t t, bool cells, bool with_record = false, bool with_side = false) {   // with_record: record_sample inside k_mh_tail; with_side: and the hyper sweep of t + 1
   const int draw_sig = h->cfg.likelihood == BNMF_NORMAL ? 1 : 0;
   if (draw_sig) cells = true;                 // sigmasq is drawn after R, A (R/sample_params.R:86-88) in the metrics pass
   const int N = h->cfg.N, G = h->cfg.G;
   if (cells) {
-    if (h->mhe16) {
-      const int gw = h->mhe_gw ? h->mhe_gw : 16, cpw = 64 / gw;
+    if (h->mh.e16) {
+      const int gw = h->mh.e_gw ? h->mh.e_gw : 16, cpw = 64 / gw;
       int g16 = ((G + cpw - 1) / cpw + 3) / 4; if (g16 > 2048) g16 = 2048;
       const size_t lds16 = (4 * (size_t)cpw * N * (1 + PRE_W) + 2 * (size_t)N) * sizeof(double);
       const MhEcol16 kern = mh_ecol16_kernel<true>(false, gw, mh_ecol16_k96(h), draw_sig != 0);
       hipLaunchKernelGGL(kern, dim3(g16), dim3(MHE_T), lds16, h->stream, h->dev, t, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig, (int*)nullptr, g16, MhPTail{});
     } else {
       int grid = (G + 3) / 4; if (grid > 2048) grid = 2048;
-      if (draw_sig) hipLaunchKernelGGL((k_mh_ecol<true, true>), dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
-      else hipLaunchKernelGGL(k_mh_ecol<true>, dim3(grid), dim3(MHE_T), h->mhe_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
+      if (draw_sig) hipLaunchKernelGGL((k_mh_ecol<true, true>), dim3(grid), dim3(MHE_T), h->mh.e_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
+      else hipLaunchKernelGGL(k_mh_ecol<true>, dim3(grid), dim3(MHE_T), h->mh.e_lds, h->stream, h->dev, t, 0, (const int*)nullptr, h->arr[BNMF_ACC_E].d, draw_sig);
     }
   }
   // log-priors and acceptance sums, (for the next iteration's P sweep) Et, nzE, nzP = 0, and record_sample: one launch
@@ -625,7 +624,7 @@ static int launch_mh_metrics(bnmf_handle* h, uint32_t t, bool cells, bool with_r
   const int nrec = (ra.n > 0 || ra.Rdst) ? 256 : 0;
   // the canonical reductions of the iteration BEFORE ride in this launch when the hyper sweep runs on the main stream (launch_side_main):
   // as a kernel of their own on the side stream nothing ordered the writers of their slot, three iterations on, behind them
-  const RedSlots rs = h->mh_side_main ? take_reduce_slots(h) : RedSlots{};
+  const RedSlots rs = h->mh.side_main ? take_reduce_slots(h) : RedSlots{};
   SideInTail sx{};
   if (with_side) {                                           // launch_side_main's kernel as the first blocks of this one
     const int nbP = side_nbP(h), nbE = side_nbE(h);
@@ -633,7 +632,7 @@ static int launch_mh_metrics(bnmf_handle* h, uint32_t t, bool cells, bool with_r
     h->pipe.flags_valid = false; h->pipe.side_valid = true; h->pipe.side_main = true;
   }
   hipLaunchKernelGGL(k_mh_tail, dim3(sx.n + 2 * N + h->nblkE + nrec + (rs.on ? (h->cfg.MH ? 5 : 4) : 0)), dim3(ES_T), 0, h->stream, h->dev, t, (const double*)h->arr[BNMF_ACC_P].d, accPn_slot(h, t),
-                     (const double*)h->arr[BNMF_ACC_E].d, accEp_slot(h, t), h->dNzE, h->dNzE + N, h->nblkE, ra, nrec, rs, sx);
+                     (const double*)h->arr[BNMF_ACC_E].d, accEp_slot(h, t), h->mh.dNzE, h->mh.dNzE + N, h->nblkE, ra, nrec, rs, sx);
   h->pipe.mh_prep_valid = true;
   return 0;
 }
@@ -657,7 +656,7 @@ static MhETail mh_etail_args(bnmf_handle* h, uint32_t te, uint32_t t_next, int& 
   const int N = h->cfg.N;
   MhETail et{};
   rc = 0;
-  et.nz_zero = h->dNzE + 2 * N + (t_next & 1u) * N;
+  et.nz_zero = h->mh.dNzE + 2 * N + (t_next & 1u) * N;
   if (!te) return et;
   RecArgs raP;
   if ((rc = record_args_split(h, te, raP, et.ra))) return et;
@@ -698,7 +697,7 @@ static int sweep_mh_pipe(bnmf_handle* h, int row, int converged, Timer& tm) {
   pt.nrec = pt.ra.n > 0 ? 8 : 0;
   pt.accP = h->arr[BNMF_ACC_P].d; pt.accPn = accPn_slot(h, t);
   pt.nblkE = h->nblkE;
-  pt.nz_zero = h->dNzE + 2 * N + 2 * N + ((t + 1) & 1u) * N;
+  pt.nz_zero = h->mh.dNzE + 2 * N + 2 * N + ((t + 1) & 1u) * N;
   pt.rs = take_reduce_slots(h);                            // k_reduce's work for the iteration before: its E-side sums are issued with pp.et above
   dbg_delay_main(h);
   launch_mh_PE(h, t, converged, false, &pp);
@@ -709,7 +708,7 @@ static int sweep_mh_pipe(bnmf_handle* h, int row, int converged, Timer& tm) {
   return 0;
 }
 static int sweep_mh(bnmf_handle* h, int row, int converged, Timer& tm) {
-  if (h->mh_pipe && !tm.on) return sweep_mh_pipe(h, row, converged, tm);
+  if (h->mh.pipe && !tm.on) return sweep_mh_pipe(h, row, converged, tm);
   if (int rc = flush_mh_etail(h)) return rc;
   h->iter += 1;
   const uint32_t t = (uint32_t)h->iter;
@@ -725,8 +724,8 @@ static int sweep_mh(bnmf_handle* h, int row, int converged, Timer& tm) {
   tm.begin(KN_MH, h->stream); launch_mh_PE(h, t, converged, poll); tm.end(KN_MH, h->stream);
   dbg_delay_main(h);
   // the hyper sweep of t + 1: on the main stream — inside k_mh_tail below (its own launch in profile mode, which times it) — or on the side stream
-  const bool side_in_tail = h->mh_side_main && !tm.on && h->mh_side_tail;
-  if (side_in_tail) {} else if (h->mh_side_main) launch_side_main(h, t + 1, tm); else launch_side(h, t + 1, tm, !tm.on);
+  const bool side_in_tail = h->mh.side_main && !tm.on && h->mh.side_tail;
+  if (side_in_tail) {} else if (h->mh.side_main) launch_side_main(h, t + 1, tm); else launch_side(h, t + 1, tm, !tm.on);
   if (h->cfg.learning_rank) { tm.begin(KN_RANK, h->stream); launch_rank(h, t); tm.end(KN_RANK, h->stream); }
   // record_sample rides in k_mh_tail: after sample_sigmasq, like record_sample (:279) after sample_params (:276)
   tm.begin(KN_OTHER, h->stream); if (int rc = launch_mh_metrics(h, t, h->cfg.learning_rank != 0, true, side_in_tail)) return rc; tm.end(KN_OTHER, h->stream);
@@ -747,7 +746,7 @@ static bool gate_enabled(const bnmf_handle* h) {
   return (size_t)h->cfg.K * h->cfg.G >= 550000;
 }
 // ... and what the handle's configuration must allow beside it: fixed rank, the register allocation kernel or a schedule on top of it
-static bool merged_draw_ok(const bnmf_handle* h) { return gate_enabled(h) && !h->cfg.learning_rank && h->z_reg && !h->z_tile; }
+static bool merged_draw_ok(const bnmf_handle* h) { return gate_enabled(h) && !h->cfg.learning_rank && (h->zkind == ZKind::reg || h->zkind == ZKind::sort); }
 // workgroup width of the merged draw kernel: the E elements spread over (almost) all CUs in ONE round of workgroups — 1,024-lane workgroups
 // left 60 of 256 CUs idle at N G = 200,000 — while the workgroup count stays small (the gap to the next kernel grows with it)
 static int ensure_draw_bw(bnmf_handle* h) {
@@ -849,7 +848,7 @@ static int sweep(bnmf_handle* h, int row, Timer& tm) {
   tm.begin(KN_ZALLOC, h->stream);
   if (int rc = launch_zalloc(h, t)) return rc;
   tm.end(KN_ZALLOC, h->stream);
-  if (h->z_sort) {
+  if (h->zkind == ZKind::sort) {
     h->pipe.ct_pending = t;
     if (tm.on) { tm.begin(KN_OTHER, h->stream); flush_colterms(h); tm.end(KN_OTHER, h->stream); }   // profile mode: the column terms as a launch of their own ("other")
   }

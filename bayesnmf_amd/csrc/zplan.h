@@ -1,6 +1,233 @@
-// bayesnmf_amd/csrc/zplan.h — the static schedules of k_zalloc_sort and k_zalloc_step as pure host code: no HIP call, no handle.
-// Included by api.hip (one translation unit); build_zsort / build_zstep there upload what these return, bnmf_test_zsort_plan /
-// bnmf_test_zstep_plan hand it to tests/test_schedule_host.py on any machine.
+// bayesnmf_amd/csrc/zplan.h — everything bnmf_create decides by arithmetic, as pure host code: no HIP call, no handle.
+// The environment switches (Switches), the geometry of the wave-per-column and tile allocation kernels (plan_zwave, plan_ztile), the
+// rank sweep's variant and grid (plan_rank), the MH / Normal sweeps' kernels (plan_mh), and the static schedules of k_zalloc_sort and
+// k_zalloc_step (plan_zsort, plan_zstep).  Included by api.hip (one translation unit): create_impl there calls the planners and
+// allocates / uploads what they return; bnmf_test_zsort_plan / bnmf_test_zstep_plan hand the two schedules to
+// tests/test_schedule_host.py on any machine.  A planner that refuses a shape says so with fail() and returns its code.
+
+// ---- the environment switches of a handle (diagnostics / tests; the table is in tools/README.md) ----
+// Read at EVERY bnmf_create (tests set them per handle in one process), each in exactly one place: Switches::from_env.  The planners
+// take them as values, so a caller decides whether the process environment has a say.
+static const int ENV_UNSET = INT_MIN;
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+static int env_int(const char* name, int unset = ENV_UNSET, int lo = INT_MIN, int hi = INT_MAX) {
+  const char* e = getenv(name);
+  return e ? std::max(lo, std::min(hi, atoi(e))) : unset;
+}
+static bool env_flag(const char* name, bool unset) { const char* e = getenv(name); return e ? atoi(e) != 0 : unset; }
+static double env_real(const char* name, double unset) { const char* e = getenv(name); return e ? atof(e) : unset; }
+struct Switches {
+  // the handle itself (create_impl)
+  bool devlock = true;                 // BNMF_DEVLOCK=0: no lock files
+  int gate = -1, serial = -1;          // BNMF_GATE, BNMF_SERIAL: -1 unset, else 0 / 1
+  bool mh_side_main = true, mh_side_tail = true;   // BNMF_MHSIDE, BNMF_MHSIDETAIL
+  bool draw_no_p = false;              // BNMF_DEBUG_DRAW_NO_P
+  int main_delay_us = 0, allside_delay_us = 0, side_delay_us = 0;   // BNMF_DEBUG_{MAIN,ALLSIDE,SIDE}_DELAY_US, 0..20000
+  bool rank_dbg = false, zt_dbg = false;   // BNMF_RANKDBG, BNMF_ZTDBG (set = on): the diagnostic buffers
+  bool z_eager = false;                // BNMF_ZEAGER
+  int ablate = 0;                      // BNMF_ABLATE (-DBNMF_DIAG builds only)
+  // plan_rank
+  bool rank_half = true; long rank_grid = 0;   // BNMF_RANKHALF=0: whole blocks; BNMF_RANKGRID: workgroups (0 = unset)
+  // plan_mh
+  bool mhe_k128 = false, mh_pipe = true; int mhe_gw = 0;   // BNMF_MHE_K128, BNMF_MHPIPE, BNMF_MHE_GW (16 / 32, else by mode)
+  // plan_zwave, plan_ztile
+  bool z_reg = true, z_chunk = false, z_tile = true, z_nolean = false;   // BNMF_ZREG, BNMF_ZCHUNK, BNMF_ZTILE, BNMF_ZNOLEAN (set = on)
+  int zw = ENV_UNSET, z_grid = ENV_UNSET;   // BNMF_ZW, BNMF_ZGRID
+  // plan_zsort
+  bool zsort = true, zs_spread = true, zs_it16 = true, zs_pk = true;   // BNMF_ZSORT, BNMF_ZSSPREAD, BNMF_ZSIT16, BNMF_ZSPK
+  int zs_lds_kb = ENV_UNSET, zs_w = ENV_UNSET, zs_qmax = 0;             // BNMF_ZSLDS, BNMF_ZSW, BNMF_ZSQMAX
+  // plan_zstep
+  bool zstep = true, zp_it16 = true; int zp_gb = 0;   // BNMF_ZSTEP, BNMF_ZPIT16, BNMF_ZPGB
+  static Switches from_env() {
+    Switches s;
+    s.devlock = env_flag("BNMF_DEVLOCK", true);
+    s.gate = env_set("BNMF_GATE") ? (int)env_flag("BNMF_GATE", false) : -1;
+    s.serial = env_set("BNMF_SERIAL") ? (int)env_flag("BNMF_SERIAL", false) : -1;
+    s.mh_side_main = env_flag("BNMF_MHSIDE", true); s.mh_side_tail = env_flag("BNMF_MHSIDETAIL", true);
+    s.draw_no_p = env_flag("BNMF_DEBUG_DRAW_NO_P", false);
+    s.main_delay_us = env_int("BNMF_DEBUG_MAIN_DELAY_US", 0, 0, 20000);
+    s.allside_delay_us = env_int("BNMF_DEBUG_ALLSIDE_DELAY_US", 0, 0, 20000);
+    s.side_delay_us = env_int("BNMF_DEBUG_SIDE_DELAY_US", 0, 0, 20000);
+    s.rank_dbg = env_set("BNMF_RANKDBG"); s.zt_dbg = env_set("BNMF_ZTDBG");
+    s.z_eager = env_flag("BNMF_ZEAGER", false);
+#ifdef BNMF_DIAG   /* the builder's diagnostic builds only (tools/bin/, never libbnmf.so): phases of the allocation kernels switched off */
+    s.ablate = env_int("BNMF_ABLATE", 0);
+#endif
+    s.rank_half = env_flag("BNMF_RANKHALF", true);
+    if (const char* e = getenv("BNMF_RANKGRID")) s.rank_grid = atol(e);
+    s.mhe_k128 = env_flag("BNMF_MHE_K128", false); s.mh_pipe = env_flag("BNMF_MHPIPE", true);
+    { const int v = env_int("BNMF_MHE_GW", 0); s.mhe_gw = v == 32 ? 32 : v == 16 ? 16 : 0; }
+    s.z_reg = env_flag("BNMF_ZREG", true); s.z_chunk = env_flag("BNMF_ZCHUNK", false);
+    s.z_tile = env_flag("BNMF_ZTILE", true); s.z_nolean = env_set("BNMF_ZNOLEAN");
+    s.zw = env_int("BNMF_ZW"); s.z_grid = env_int("BNMF_ZGRID");
+    s.zsort = env_flag("BNMF_ZSORT", true); s.zs_spread = env_flag("BNMF_ZSSPREAD", true);
+    s.zs_it16 = env_flag("BNMF_ZSIT16", true); s.zs_pk = env_flag("BNMF_ZSPK", true);
+    s.zs_lds_kb = env_int("BNMF_ZSLDS"); s.zs_w = env_int("BNMF_ZSW"); s.zs_qmax = env_int("BNMF_ZSQMAX", 0);
+    s.zstep = env_flag("BNMF_ZSTEP", true); s.zp_it16 = env_flag("BNMF_ZPIT16", true); s.zp_gb = env_int("BNMF_ZPGB", 0);
+    return s;
+  }
+};
+
+// ---- the rank sweep (rank.h): variant and grid ----
+// Every workgroup of the persistent sweep waits for all others: the grid must be co-resident.  occ_reg / occ_gen: how many workgroups
+// of the register / general variant the runtime says fit a CU (registers, LDS); where the answer is SGPR-limited (>= 6 per CU) the
+// query can be one high (MI355X_MICROARCH.md), so one is kept in reserve there; never more than one per CU is planned: even compute
+// times, and co-resident with margin.  Should the grid still not be co-resident, the bounded spins time out and bnmf_run reports it.
+struct RankPlan { bool reg = false, half = false; int grid = 0; };
+static RankPlan plan_rank(size_t K, size_t G, int n_cu, int occ_reg, int occ_gen, const Switches& sw) {
+  RankPlan p;
+  const long NB = ((long)G + RK_MAXC - 1) / RK_MAXC;                 // blocks of 8 columns, one compute wave each
+  const long wg_needed = (NB + RK_CW - 1) / RK_CW;                   // RK_CW compute waves + the decision wave per workgroup
+  auto cap = [&](int occ) { return (long)std::min(1, occ >= 6 ? occ - 1 : occ) * n_cu; };
+  const long cap_reg = cap(occ_reg), cap_gen = cap(occ_gen);
+  p.reg = K <= 96 && wg_needed <= cap_reg;               // register variant: rows 64..95 of two columns share a register (rank.h)
+  // ... with HALF a block per compute wave where the grid of ten-half-block workgroups is co-resident too (704 lanes, one per CU)
+  const long wg_half = (NB + RK_CWH / 2 - 1) / (RK_CWH / 2);
+  p.half = p.reg && wg_half <= (long)n_cu && NB <= 1536 && sw.rank_half;   // (1,536: one round of its decision wave's gather, rank.h)
+  // (a wider grid with the blocks dealt wave-major over all CUs was measured: no gain, the sweep is bound by the
+  // per-factor exchange, not by VALU contention)
+  const long cap_used = p.reg ? cap_reg : cap_gen;
+  p.grid = p.half ? (int)wg_half : (int)std::min<long>(wg_needed, cap_used);
+  if (!p.half && sw.rank_grid >= wg_needed && sw.rank_grid <= cap_used) p.grid = (int)sw.rank_grid;   // diagnostics only
+  return p;
+}
+
+// ---- the MH / Normal sweeps (mh.h): which column kernel, and what it hosts ----
+struct MhPlan {
+  int S = 1;                           // segments of a row of the P sweep
+  size_t e_lds = 0;                    // k_mh_ecol: per wave E column, A, Mhat column, log(Mhat) and candidates
+  bool e16 = false;                    // the column sweep by k_mh_ecol16 (K <= 128 and its LDS fits)
+  bool e_raise = false, e16_raise = false;   // k_mh_ecol / k_mh_ecol16 need more than 64 KiB of dynamic LDS: raise their limit
+  bool pipe = false;                   // Poisson MH models at fixed rank through k_mh_ecol16: what followed the two sweeps is hosted BY them (BNMF_MHPIPE=0: k_mh_tail)
+};
+static int plan_mh(size_t K, size_t G, size_t N, bool poisson_mh_fixed_rank, bool side_main, bool side_tail, const Switches& sw, MhPlan& p) {
+  p = MhPlan();
+  p.S = (int)((G + MH_SEG - 1) / MH_SEG);
+  p.e_lds = 4 * (2 * N + 3 * K) * sizeof(double);
+  if (p.e_lds > 160 * 1024) return fail(BNMF_EINVAL, "bnmf_create: K = %zu too large for the column kernel of the MH / Normal models (LDS)", K);
+  p.e_raise = p.e_lds > 64 * 1024;
+  // k_mh_ecol16 (K <= 128: several columns per wave): its LDS grows with N — above 64 KiB it needs the attribute, above the CU's 160 KiB
+  // the sweep takes k_mh_ecol
+  const size_t lds16_max = (4 * (size_t)4 * N * (1 + PRE_W) + 2 * N) * sizeof(double);   // 16 lanes per column: 4 columns per wave
+  p.e16 = K <= (size_t)MHE16_KMAX && lds16_max <= 160 * 1024;
+  p.e16_raise = p.e16 && lds16_max > 64 * 1024;
+  // k_mh_tail's work hosted by the two sweep kernels (mh.h) — the Poisson MH models at fixed rank where the column sweep is k_mh_ecol16
+  p.pipe = p.e16 && poisson_mh_fixed_rank && side_main && side_tail && N <= RT && sw.mh_pipe;
+  return 0;
+}
+
+// ---- the wave-per-column allocation kernels: k_zalloc_reg (zalloc_reg.h, N <= 24) and the general LDS-search kernel k_zalloc (kernels.h) ----
+// Independent waves, one LDS slab per wave, zacc (and P) shared per workgroup.  The general kernel takes the whole column in one row
+// chunk when that leaves room for at least two waves per workgroup, else row chunks of 64 with ZsumG kept in global memory.
+struct ZWavePlan {
+  bool reg = false;                    // k_zalloc_reg is eligible (N <= ZNMAX and its LDS fits); false: k_zalloc
+  ZGeom g{};
+  int w = 8, per_cu = 0, grid = 0;     // waves per workgroup, workgroups per CU, workgroups
+  size_t lds = 0;
+};
+static int plan_zwave(size_t K, size_t G, size_t N, bool save_Z, int n_cu, const Switches& sw, ZWavePlan& p) {
+  p = ZWavePlan();
+  ZGeom& zg = p.g;
+  zg.KP = (K % 32 == 0) ? (int)K + 1 : (int)(K | 1);
+  zg.HW = (int)((N + 3) / 4);
+  zg.TR = N <= 8 ? 8 : N <= 16 ? 16 : N <= 20 ? 20 : 24;   // threshold registers of the k_zalloc_reg instantiation
+  p.reg = N <= (size_t)ZNMAX && sw.z_reg;
+  size_t slab = 0, shared_words = 0;
+  auto geometry = [&](bool chunked) {
+    if (p.reg) {
+      zg.KC = (int)K;
+      slab = (size_t)zg.HW * ZH + (K + 1) * (size_t)zreg_row_words(zg.TR) + 2 * N + N + (save_Z ? N * (size_t)zg.KP : 0);
+      zg.zacc_words = (int)((N * (size_t)zg.KP + 3) & ~(size_t)3);
+      zg.p_words = (int)((2 * K * N + 3) & ~(size_t)3);                  // workgroup copy of P (fp64)
+    } else {
+      zg.KC = chunked ? 64 : (int)((K + 63) & ~(size_t)63);
+      zg.KP = chunked ? 65 : ((K % 32 == 0) ? (int)K + 1 : (int)(K | 1));
+      const bool loc = chunked || save_Z;
+      slab = (size_t)zg.HW * ZH + 2 * N + (N - 1) * (size_t)zg.KP + (zg.KC + 1) + zg.KC + N + (loc ? N * (size_t)zg.KP : 0);
+      zg.zacc_words = chunked ? 0 : (int)((N * (size_t)zg.KP + 3) & ~(size_t)3);
+      zg.p_words = 0;
+    }
+    slab = (slab + 3) & ~(size_t)3;
+    zg.slab_words = (int)slab;
+    shared_words = (size_t)zg.zacc_words + zg.p_words;
+  };
+  // workgroup width.  k_zalloc holds 128 VGPRs per lane: at 16 waves/CU it owns the whole register file and
+  // starves k_side (side stream) until its tail.  Measured end to end at the metric config (tools/e2e.py):
+  // 16 waves/CU 178 us/iter, 12: 169, 10: 176, 8: 161, 2x4: 165, 6: 179.  So: at most 8 waves per CU, in one
+  // workgroup when LDS allows.
+  constexpr int Z_MAX_WAVES_PER_CU = 8;
+  int best_total = 0;
+  auto pick = [&]() {
+    p.w = p.per_cu = best_total = 0;
+    for (int per_cu = 1; per_cu <= 2; ++per_cu)
+      for (int w : {16, 8, 6, 4, 2, 1}) {
+        const size_t lds = (shared_words + (size_t)w * slab) * 4;
+        if (lds * per_cu <= 160 * 1024 && w * per_cu <= Z_MAX_WAVES_PER_CU && w * per_cu > best_total) { best_total = w * per_cu; p.w = w; p.per_cu = per_cu; }
+      }
+  };
+  geometry(sw.z_chunk && !p.reg);
+  pick();
+  // the register path keeps (K+1) threshold rows per wave and a workgroup copy of P: for large K (e.g. K = 1,536
+  // with N <= 24) that exceeds LDS, so fall back to the general kernel, which can walk the rows in chunks
+  if (p.reg && best_total < 2) { p.reg = false; geometry(sw.z_chunk); pick(); }
+  if (!p.reg && best_total < 2 && !sw.z_chunk) { geometry(true); pick(); }
+  if (sw.zw != ENV_UNSET) { p.w = sw.zw; p.per_cu = (shared_words + (size_t)p.w * slab) * 4 * 2 <= 160 * 1024 ? 2 : 1; }
+  if (p.w == 0) return fail(BNMF_EINVAL, "bnmf_create: K = %zu, N = %zu needs %zu B of LDS per wavefront for the allocation kernel (limit 160 KiB): unsupported", K, N, slab * 4);
+  p.lds = ((shared_words + (size_t)p.w * slab) * 4 + 15) & ~(size_t)15;
+  const long resident = (long)n_cu * p.per_cu;
+  const long want = ((long)G + p.w - 1) / p.w;
+  p.grid = (int)(want < resident ? want : resident);
+  if (sw.z_grid != ENV_UNSET) p.grid = sw.z_grid;          // diagnostics only
+  return 0;
+}
+
+// ---- the tile kernel k_zalloc_tile (zalloc_tile.h): N > 24 (or K too large for the register kernel), when at least two waves per CU fit ----
+struct ZTilePlan {
+  bool ok = false, lean = false;       // lean: the register-lean variant, one workgroup of 1024 lanes
+  ZTGeom g{};
+  int w = 0, grid = 0;                 // waves per workgroup, workgroups
+  size_t lds = 0;
+};
+static ZTilePlan plan_ztile(size_t K, size_t G, size_t N, bool save_Z, int n_cu, const Switches& sw) {
+  ZTilePlan p;
+  ZTGeom& tg = p.g;
+  tg.HW = (int)((N + 3) / 4);
+  tg.nch = (int)((K + ZTR - 1) / ZTR);
+  tg.p_words = 2 * ztile_np8((int)N) * ZTR;
+  tg.zacc_words = (int)((N * (size_t)ZTR + 3) & ~(size_t)3);
+  tg.slab_words = (int)ztile_slab_words((int)N, tg.HW, save_Z);
+  tg.dbg = nullptr;
+  const size_t shw = (size_t)tg.p_words + tg.zacc_words;
+  int tper = 0, ttot = 0;
+  for (int per_cu = 1; per_cu <= 2; ++per_cu)
+    for (int w : {8, 6, 4, 2}) {
+      const size_t lds = (shw + (size_t)w * tg.slab_words) * 4;
+      // 8 waves per CU: the kernel holds ~190 VGPRs (double-buffered LDS reads), i.e. two waves per SIMD
+      if (lds * per_cu <= 160 * 1024 && w * per_cu <= 8 && w * per_cu > ttot) { ttot = w * per_cu; p.w = w; tper = per_cu; }
+    }
+  // ... or 16 (one workgroup of 1024 lanes) with the register-lean variant, where LDS allows it
+  if ((shw + 16 * (size_t)tg.slab_words) * 4 <= 160 * 1024 && !sw.z_nolean) { ttot = 16; p.w = 16; tper = 1; p.lean = true; }
+  if (!sw.z_tile || ttot < 2) return p;                    // (BNMF_ZTILE=0: k_zalloc)
+  p.ok = true;
+  p.lds = ((shw + (size_t)p.w * tg.slab_words) * 4 + 15) & ~(size_t)15;
+  // column slices: the fewest rounds (1..4) of resident workgroups that fill >= 97 % of the CUs (the chunk's P rows
+  // are staged and its ZsumG counts flushed once per workgroup); every wave with at least two columns
+  const long res = (long)n_cu * tper;
+  long ns = 1; double best_util = 0.0;
+  for (long r = 1; r <= 4; ++r) {
+    const long c = (r * res) / tg.nch;
+    if (c < 1) continue;
+    const double util = (double)(c * tg.nch) / (double)(r * res);
+    if (util > best_util + 1e-9) { best_util = util; ns = c; }
+    if (util >= 0.97) break;
+  }
+  const long nsmax = ((long)G + 2 * p.w - 1) / (2 * p.w);
+  if (ns > nsmax) ns = nsmax;
+  if (ns < 1) ns = 1;
+  tg.nslice = (int)ns;
+  p.grid = tg.nch * tg.nslice;
+  return p;
+}
 
 // Static schedule of k_zalloc_sort (zalloc_sort.h): columns dealt into blocks of equal total count (largest column first,
 // to the lightest block that still has room), the non-empty cells of a block as items sorted by their number of quads,
@@ -17,12 +244,12 @@ struct ZSortPlan {
   std::vector<uint16_t> items16;      // 2-byte form of the same items, if it16
   std::vector<int32_t> Mblk;
 };
-static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int maxM, bool z_reg, int n_cu, ZSortPlan& p) {
+static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int maxM, bool z_reg, int n_cu, const Switches& sw, ZSortPlan& p) {
   p = ZSortPlan();
   if (!z_reg || N > (size_t)ZS_NMAX - 1 || K > 1024) return 0;
   // save_Z: a cell's counts per factor meet as 16-bit halves in k_zexpand's slab
   if (save_Z && maxM > 65535) return 0;
-  if (const char* e = getenv("BNMF_ZSORT")) if (atoi(e) == 0) return 0;          // diagnostics / tests: the register kernel
+  if (!sw.zsort) return 0;                                                        // diagnostics / tests: the register kernel
   // an item word holds 16 bits of fragment index (k | gl << 10 | f << 16), and f = 65535 with k = 1023, gl = 63 is the empty-lane
   // sentinel: a cell above 65,534 fragments of 4 ZS_QMAX counts stays with the register kernel
   if ((long long)maxM > 65534LL * 4 * ZS_QMAX16) return 0;
@@ -35,11 +262,11 @@ static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_
   // save_Z (k_zexpand writes whole columns of Z per block).  The per-count work stays O(sum M) — the reference's rmultinom is O(N) per cell
   // (R/sample_params.R:263) — but a 10^7-count cell is 25 % more counts for the whole chip, not a 60-fold longer block.
   constexpr int ZS_BIG = 8192, ZS_HOME = 16, ZS_UNIT = 32;
-  const bool spread = !save_Z && (long long)maxM > ZS_BIG && !(getenv("BNMF_ZSSPREAD") && atoi(getenv("BNMF_ZSSPREAD")) == 0);   // (tests: 0 = every cell at home)
+  const bool spread = !save_Z && (long long)maxM > ZS_BIG && sw.zs_spread;   // (tests: 0 = every cell at home)
   const int nblk = (int)((N + 4) / 5);                                             // threshold blocks per cell
   const int KP = (K % 32 == 0) ? (int)K + 1 : (int)(K | 1);
   size_t budget = 156 * 1024;                                                     // of 160: the side streams' workgroups (2 KB each) keep room on the CU
-  if (const char* e = getenv("BNMF_ZSLDS")) budget = (size_t)atol(e) * 1024;
+  if (sw.zs_lds_kb != ENV_UNSET) budget = (size_t)(long)sw.zs_lds_kb * 1024;
   long nb = std::min<long>((long)G, n_cu);
   int GBc = 0, W = 0;
   for (int tries = 0; tries < 12; ++tries, nb = std::min<long>((long)G, nb * 2)) {
@@ -54,7 +281,7 @@ static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_
     if (nb >= (long)G) break;
   }
   if (!W || GBc > 64) return 0;
-  if (const char* e = getenv("BNMF_ZSW")) { const int w = atoi(e); if (w == 4 || w == 6 || w == 8 || w == 12 || w == 14 || w == 16) W = w; }
+  { const int w = sw.zs_w; if (w == 4 || w == 6 || w == 8 || w == 12 || w == 14 || w == 16) W = w; }
   // columns -> blocks
   const bool it16_pre = K <= 127 && GBc <= 64 && (long long)maxM <= 8LL * 4 * ZS_QMAX16;
   const int qmax_pre = (it16_pre || (long long)maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;   // quads per fragment (the item format is fixed below: the same rule)
@@ -163,11 +390,11 @@ static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_
     }
     double best = 1e300;
     for (int c = 0; c < 5; ++c) if (worst[c] < 0.95 * best) { best = worst[c]; qsel = cand[c]; }
-    if (const char* e = getenv("BNMF_ZSQMAX")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) qsel = v; }
+    { const int v = sw.zs_qmax; if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) qsel = v; }
   }
   // 2-byte items where row, column-in-block and fragment index fit 7 + 6 + 3 bits (and 0xFFFF stays free for the empty lane)
   bool it16 = K <= 127 && GBc <= 64 && (long long)maxM <= 8LL * 4 * (qsel ? qsel : ZS_QMAX16);
-  if (const char* e = getenv("BNMF_ZSIT16")) it16 = it16 && atoi(e) != 0;           // diagnostics / tests: 0 = 4-byte items
+  it16 = it16 && sw.zs_it16;                                                        // diagnostics / tests: 0 = 4-byte items
   // (large cells spread over the blocks: 4-byte items of 128 counts per fragment, 256 where a cell would need more than 65,534 of them)
   const int qmax = qsel ? qsel : (it16 || (long long)maxM > 65534LL * 4 * ZS_QMAX) ? ZS_QMAX16 : ZS_QMAX;
   std::vector<ZSBlock> blocks(nb);
@@ -226,12 +453,12 @@ static int plan_zsort(const int32_t* M, size_t K, size_t G, size_t N, bool save_
     for (auto& th : pool) th.join();
   }
   for (int b = 0; b < nb; ++b) pk = pk && bpk[b];
-  if (const char* e = getenv("BNMF_ZSPK")) pk = pk && atoi(e) != 0;                 // diagnostics / tests: 0 = one factor per word
+  pk = pk && sw.zs_pk;                                                              // diagnostics / tests: 0 = one factor per word
   // the waves per workgroup were sized for one factor per word (the block tables' larger form); with two per word the tables are half as
   // large and, at the metric configuration, 14 waves fit where 12 did.  tools/ablong.py, sixteen processes alternating on one box: 12 waves
   // 80.3 us per iteration in three of eight processes and 81.4-83.0 in the others (the stop-event mode of DESIGN.md 5b), 14 waves 81.3-81.6
   // in seven of eight (80.3 in one): 82.1 against 81.3 us on average
-  if (pk && !getenv("BNMF_ZSW")) {
+  if (pk && sw.zs_w == ENV_UNSET) {
     const size_t sh = zsort_shared_bytes((int)K, (int)N, KP, GBc, true), wv = zsort_wave_bytes(nblk, (int)N);
     for (int w : {16, 14, 12, 8, 6, 4}) if (sh + (size_t)w * wv <= budget) { W = std::max(W, w); break; }
   }
@@ -286,17 +513,17 @@ struct ZStepPlan {
   std::vector<uint32_t> items;        // 4-byte form, always
   std::vector<uint16_t> items16;      // 2-byte form of the same items, if it16
 };
-static int plan_zstep(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int n_cu, ZStepPlan& p) {
+static int plan_zstep(const int32_t* M, size_t K, size_t G, size_t N, bool save_Z, int n_cu, const Switches& sw, ZStepPlan& p) {
   p = ZStepPlan();
   if (save_Z || N <= (size_t)ZNMAX || N > (size_t)ZP_NMAX) return 0;
-  if (const char* e = getenv("BNMF_ZSTEP")) if (atoi(e) == 0) return 0;            // diagnostics / tests: the tile kernel
+  if (!sw.zstep) return 0;                                                         // diagnostics / tests: the tile kernel
   const int L = 4;                                                                 // lanes per cell (with <= 20 included factors the search then skips a level)
   size_t budget = 156 * 1024;                                                      // of 160: the side streams' workgroups keep room on the CU
   int GBP = 0, W = 0;
   // 8 waves (two per SIMD).  12 waves fit the LDS up to N = 60 and were measured at config 4: 114.5 against 121 us per launch, but
   // at the 168 registers three waves per SIMD leave, the kernel spills 16-36 bytes per lane — not kept
   for (int gbp : {40, 32}) if (zstep_shared_bytes((int)N, gbp) + 8 * zstep_wave_bytes(L) <= budget) { GBP = gbp; W = 8; break; }
-  if (const char* e = getenv("BNMF_ZPGB")) { const int v = atoi(e); if (v == 32 || v == 40) GBP = v; }   // diagnostics / tests
+  if (sw.zp_gb == 32 || sw.zp_gb == 40) GBP = sw.zp_gb;                            // diagnostics / tests
   if (!GBP) return 0;
   const int nch = (int)((K + ZP_KC - 1) / ZP_KC);
   const long nwg = std::min<long>((long)G, n_cu);
@@ -374,7 +601,7 @@ static int plan_zstep(const int32_t* M, size_t K, size_t G, size_t N, bool save_
   if (items.empty()) items.push_back(0xFFFFFFFFu);
   // 2-byte items where the fragment index fits 5 bits beside row (5) and column (6), 0xFFFF staying the empty lane (column 63 does not
   // occur): BNMF_ZPIT16=0 keeps the 4-byte form (diagnostics / tests)
-  const bool it16 = maxfrag <= 30 && !(getenv("BNMF_ZPIT16") && atoi(getenv("BNMF_ZPIT16")) == 0);
+  const bool it16 = maxfrag <= 30 && sw.zp_it16;
   if (it16) {
     p.items16.resize(items.size());
     for (size_t i = 0; i < items.size(); ++i) p.items16[i] = items[i] == 0xFFFFFFFFu ? (uint16_t)0xFFFFu : (uint16_t)items[i];
