@@ -197,6 +197,7 @@ struct Rank : RankPlan { double *dCol = nullptr, *dMhat = nullptr; uint32_t* dSy
 struct Mh : MhPlan {
   bool side_tail = true;               // BNMF_MHSIDETAIL=0 (diagnostics): the main-stream hyper sweep as a launch of its own in front of k_mh_tail
   bool side_main = true;               // BNMF_MHSIDE=0 (diagnostics / tests): the hyper sweep on the side stream, as in round 3
+  bool no_reg = false;                 // BNMF_MHREG=0 (tests): the row sweep in the form that keeps Mhat in memory also where its register form fits
   bool e_k128 = false;                 // BNMF_MHE_K128=1 (diagnostics / tests): k_mh_ecol16's 128-row form also where K <= 96
   int e_gw = 0;                        // BNMF_MHE_GW: lanes per column of k_mh_ecol16 (0 = by mode)
   double *dMhat = nullptr, *dAccPn = nullptr, *dAccEpart = nullptr, *dEt = nullptr; int* dNzE = nullptr;
@@ -233,6 +234,8 @@ struct bnmf_handle {
   int32_t *dM = nullptr, *dZsumK = nullptr, *dZsumG = nullptr, *dZ = nullptr;
   double* dMf = nullptr;               // Normal handles: the data as fp64, M's layout (dM stays unset)
   int* dR = nullptr; int* dRedraw = nullptr;
+  std::vector<int32_t> fixedP;         // bnmf_set_fixed: 1 = column n of P is held at its value (empty: never called); n_fixed of them are;
+  int n_fixed = 0; int* dFixedP = nullptr;   // dFixedP [N]: the mask the kernels read (Dev::fixedP; null there while no column is fixed)
   double *dEsum = nullptr, *dPsum = nullptr, *dlpPn = nullptr, *dlpE = nullptr, *dcol = nullptr;
   double* hMetrics = nullptr;          // the metric rows live in mapped host memory (dMetrics is its device address): k_compose writes them
                                        // where the host reads them, no device-to-host copy at the end of a call
@@ -353,6 +356,7 @@ static void refresh_dev(bnmf_handle* h) {
   d.temperature = h->dTemp; d.n_temperature = c.n_temperature;
   d.metrics = h->dMetrics; d.raw = h->dRaw;
   d.lenP = (size_t)c.K * c.N; d.lenE = (size_t)c.N * c.G;
+  d.fixedP = h->n_fixed > 0 ? h->dFixedP : nullptr;
 }
 
 // BNMF_TIMING=1 (diagnostics): wall-clock marks of bnmf_create on stderr
@@ -927,6 +931,7 @@ static int create_mh(bnmf_handle* h, const int32_t* M, const double* Mf, const S
   const size_t K = c.K, G = c.G, N = c.N;
   Mh& m = h->mh;
   m.e_k128 = sw.mhe_k128; m.e_gw = sw.mhe_gw;
+  m.no_reg = env_set("BNMF_MHREG") && !env_flag("BNMF_MHREG", true);
   if (int rc = plan_mh(K, G, N, c.MH && c.likelihood == BNMF_POISSON && !c.learning_rank, m.side_main, m.side_tail, sw, m)) return rc;
   auto raise = [](std::initializer_list<const void*> ks) {
     for (const void* kf : ks) HIPCHK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1130,6 +1135,17 @@ int bnmf_get_array(bnmf_handle* h, int id, double* out, size_t n) {
     for (size_t i = 0; i < n; ++i) out[i] = tmp[i];
     return 0;
   }
+  if (id == BNMF_MHAT) {
+    // the rows of Mhat as the last row sweep of the MH / Normal models left them: P_t diag(A) E_{t-1}, maintained factor by factor
+    if (!h->mh.dMhat || h->iter < 2) return fail(BNMF_EUNSET, "bnmf_get_array: Mhat is maintained by the row sweep of the MH / Normal models, after their first iteration");
+    if (h->mh.S <= MHP_W && !h->mh.no_reg)
+      return fail(BNMF_EUNSET, "bnmf_get_array: this handle's row sweep keeps Mhat in registers; create it with BNMF_MHREG=0 to read it");
+    const size_t K = h->cfg.K, G = h->cfg.G;
+    std::vector<double> rows(K * G);
+    HIPCHK(hipMemcpy(rows.data(), h->mh.dMhat, K * G * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < K; ++k) for (size_t g = 0; g < G; ++g) out[k + K * g] = rows[k * G + g];
+    return 0;
+  }
   const Arr& a = h->arr[id];
   if (!a.d) return fail(BNMF_EUNSET, "bnmf_get_array: id %d has no value", id);
   if (a.stride == 0) { double v; HIPCHK(hipMemcpy(&v, a.d, sizeof(double), hipMemcpyDeviceToHost)); for (size_t i = 0; i < n; ++i) out[i] = v; return 0; }
@@ -1200,10 +1216,68 @@ int bnmf_get_stat(bnmf_handle* h, int what, double* out) {   // sizes of the sch
     case 4: *out = h->mh.pipe ? 1.0 : 0.0; return 0;                                        // MH sweep: k_mh_tail's work hosted by the two sweep kernels
     case 6: *out = h->zkind == ZKind::sort ? (double)h->zs.g.nblocks : h->zkind == ZKind::step ? (double)h->zp.g.nwg : 0.0; return 0;   // blocks (workgroups) of the static schedule
     case 7: *out = h->zkind == ZKind::sort ? (double)h->zs.nempty : 0.0; return 0;                        // ... of them without an own column (k_zalloc_step: never)
+    case 8: *out = (double)h->n_fixed; return 0;                                            // columns of P held fixed (bnmf_set_fixed)
+    case 9: *out = !h->mh.dMhat ? 0.0 : (h->mh.S <= MHP_W && !h->mh.no_reg) ? 1.0 : 2.0; return 0;   // MH / Normal row sweep: 1 its register form, 2 the form with Mhat in memory
+    case 10: *out = (double)h->draw_seq; return 0;                                          // launches of the merged draw kernel so far
+    case 11: *out = h->zkind == ZKind::step ? 1.0 : 0.0; return 0;                          // the allocation kernel is k_zalloc_step
     default: return fail(BNMF_EINVAL, "bnmf_get_stat: unknown statistic %d", what);
   }
 }
 int bnmf_get_iter(bnmf_handle* h, int* iter) { if (!h || !iter) return fail(BNMF_EINVAL, "null"); *iter = h->iter; return 0; }
+
+// the mask of fixed columns on the handle and on the device (bnmf_set_fixed, bnmf_load_state); a mask of zeros leaves Dev::fixedP null:
+// the kernels then run the path they run without a mask
+static int apply_fixed(bnmf_handle* h, const int32_t* fixed) {
+  const size_t N = h->cfg.N;
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->dFixedP) HIPCHK(hmalloc(h, &h->dFixedP, N * sizeof(int)));
+  HIPCHK(hipMemcpy(h->dFixedP, fixed, N * sizeof(int), hipMemcpyHostToDevice));
+  h->fixedP.assign(fixed, fixed + N);
+  h->n_fixed = 0;
+  for (size_t n = 0; n < N; ++n) h->n_fixed += fixed[n] != 0;
+  refresh_dev(h);
+  return 0;
+}
+int bnmf_set_fixed(bnmf_handle* h, int id, const int32_t* fixed, size_t n) {
+  if (!h || !fixed) return fail(BNMF_EINVAL, "bnmf_set_fixed: null argument");
+  if (id != BNMF_P) return fail(BNMF_EMODEL, "bnmf_set_fixed: only columns of P (id %d) can be held fixed, not id %d (fixing rows of E is out of scope)", (int)BNMF_P, id);
+  if (n != (size_t)h->cfg.N) return fail(BNMF_ESIZE, "bnmf_set_fixed: the mask has %zu entries, P has N = %d columns", n, h->cfg.N);
+  for (size_t i = 0; i < n; ++i)
+    if (fixed[i] != 0 && fixed[i] != 1) return fail(BNMF_EINVAL, "bnmf_set_fixed: fixed[%zu] = %d (column %zu) is neither 0 nor 1", i, (int)fixed[i], i);
+  if (h->inited || h->iter != 0)
+    return fail(BNMF_ESTATE, "bnmf_set_fixed: the handle has been initialised, loaded or run (iteration %d); set the mask before bnmf_init / bnmf_load_state", h->iter);
+  return apply_fixed(h, fixed);
+}
+int bnmf_get_fixed(bnmf_handle* h, int id, int32_t* out, size_t n) {
+  if (!h || !out) return fail(BNMF_EINVAL, "bnmf_get_fixed: null argument");
+  if (id != BNMF_P) return fail(BNMF_EMODEL, "bnmf_get_fixed: only columns of P (id %d) can be held fixed, not id %d", (int)BNMF_P, id);
+  if (n != (size_t)h->cfg.N) return fail(BNMF_ESIZE, "bnmf_get_fixed: the mask has N = %d entries, room for %zu given", h->cfg.N, n);
+  for (size_t i = 0; i < n; ++i) out[i] = h->fixedP.empty() ? 0 : h->fixedP[i];
+  return 0;
+}
+// bnmf_init with fixed columns: each must hold a usable value — decided on the host (P is read back, nothing is written)
+static int check_fixed_columns(bnmf_handle* h) {
+  if (h->n_fixed == 0) return 0;
+  const size_t K = h->cfg.K, N = h->cfg.N;
+  const Arr& a = h->arr[BNMF_P];
+  size_t first = 0;
+  while (!h->fixedP[first]) ++first;
+  if (!a.set || !a.d) return fail(BNMF_EUNSET, "bnmf_init: column %zu of P is fixed but P has no value (bnmf_set_array(BNMF_P) first)", first);
+  std::vector<double> P(K * N);
+  HIPCHK(hipMemcpy(P.data(), a.d, K * N * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t n = 0; n < N; ++n) {
+    if (!h->fixedP[n]) continue;
+    double sum = 0.0;
+    for (size_t k = 0; k < K; ++k) {
+      const double v = P[k + K * n];
+      if (v != v) return fail(BNMF_EUNSET, "bnmf_init: fixed column %zu of P has no value at row %zu (NaN)", n, k);
+      if (v < 0.0 || std::isinf(v)) return fail(BNMF_EINVAL, "bnmf_init: fixed column %zu of P holds %g at row %zu (a signature is finite and non-negative)", n, v, k);
+      sum += v;
+    }
+    if (sum == 0.0) return fail(BNMF_EINVAL, "bnmf_init: fixed column %zu of P sums to 0", n);
+  }
+  return 0;
+}
 
 }  // extern "C"
 
@@ -1215,6 +1289,7 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
   if (!h) return fail(BNMF_EINVAL, "bnmf_init: null handle");
   HIPCHK(hipSetDevice(h->device));
   if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_init: the handle timed out inside a kernel; destroy it");
+  if (int rc = check_fixed_columns(h)) return rc;
   if (h->inited) {
     // Re-initialisation restarts the iteration counter at 1, and with it every epoch the kernels compare their sync words
     // against (flags < epoch, the rank sweep's granule tags): stale words from the first life of the handle would satisfy
@@ -1284,7 +1359,18 @@ int bnmf_init(bnmf_handle* h, double* metrics_row1) {
   Timer tm{h, false};
   use_slot(h, 1u);
   if (int rc = ensure_rings(h)) return rc;
-  launch_pdraw(h, 1u, haveP ? 2 : 1, false);                // skip = names(init_params): supplied P / E kept verbatim
+  // skip = names(init_params): supplied P / E kept verbatim.  With fixed columns the OTHER columns of a supplied P that carry a missing
+  // (NaN) entry are drawn from the prior, as missing columns of the prior parameters are: the launch keeps the columns of a mask of its own
+  std::vector<int> keepP;
+  if (haveP && h->n_fixed > 0 && !h->arr[BNMF_P].redraw.empty())
+    for (int n = 0; n < N; ++n) if (h->arr[BNMF_P].redraw[n] && !h->fixedP[n]) { keepP.assign(N, 1); break; }
+  if (!keepP.empty()) {
+    for (int n = 0; n < N; ++n) keepP[n] = (h->arr[BNMF_P].redraw[n] && !h->fixedP[n]) ? 0 : 1;
+    HIPCHK(hipMemcpy(h->dRedraw, keepP.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    launch_pdraw(h, 1u, 1, false, h->dRedraw);
+  } else {
+    launch_pdraw(h, 1u, haveP ? 2 : 1, false);
+  }
   launch_edraw(h, 1u, haveE ? 2 : 1, false);                // (iteration 1 is recorded by k_record below, every model)
   launch_side(h, 2u, tm);
   if (!haveA && c.learning_rank) {                            // R ~ Uniform{0..N}, A[n] ~ Bernoulli(pi(R))

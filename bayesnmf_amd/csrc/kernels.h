@@ -44,7 +44,10 @@ struct Dev {
   double* metrics;                   // device rows [row][BNMF_NMETRIC]
   double* raw;                       // device rows [row][8]: sse, ll, kl, lpE, lpP, sumA (k_reduce -> k_compose)
   size_t lenP, lenE;                 // K*N, N*G: the prior-parameter arrays hold 2 slots, slot(t) = t & 1
+  const int* fixedP;                 // [N] 1: column n of P is held at its value, never drawn (bnmf_set_fixed); null: no column is
 };
+// column n of P is held fixed: uniform over the workgroup (one scalar load); everything a draw site hands on is still produced
+BNMF_DEV bool p_fixed(const Dev& d, int n) { return d.fixedP && d.fixedP[n] != 0; }
 // record_sample fused into the producers (R/bayesNMF_sampler.R:651-672): the ring slot of the iteration whose values a
 // kernel writes, one pointer per recorded array (null = not recorded / window 0).  pp[0..1]: P-side prior parameters in
 // the order (Alpha|Mu|Lambda, Beta|Sigmasq), pp[2..3]: E-side.
@@ -261,7 +264,8 @@ __global__ void k_raise_flag(unsigned* flag, unsigned epoch) {
 // sample_Pn_poisson R/sample_Pn.R:98-120 (dispatch :11-42); Psum[n] and the log-prior of column n
 // are reduced canonically (W = 64) over k.
 constexpr int PD_T = 128;
-__global__ __launch_bounds__(PD_T) void k_pdraw(Dev d, uint32_t t, int from_prior, int with_lp, RecDst rec, SideWait sw) {
+// keep (bnmf_init only, else null): [N] 1 = column n of the supplied P is kept verbatim although from_prior == 1 draws the others
+__global__ __launch_bounds__(PD_T) void k_pdraw(Dev d, uint32_t t, int from_prior, int with_lp, RecDst rec, SideWait sw, const int* keep) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
   side_wait(sw, threadIdx.x);
   double* Pn = (double*)dyn;          // [K]
@@ -269,12 +273,13 @@ __global__ __launch_bounds__(PD_T) void k_pdraw(Dev d, uint32_t t, int from_prio
   const int n = blockIdx.x, tid = threadIdx.x;
   const int K = d.K;
   const double a_n = d.A[n];
+  const bool fx = p_fixed(d, n) || (keep && keep[n] != 0);
   // Esum may have been published while this kernel was already polling: an agent-scope load (never the scalar cache)
   const double Esum = from_prior ? 0.0 : __hip_atomic_load(&d.Esum[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (int k = tid; k < K; k += PD_T) {
     const int e = k + K * n;
     double x;
-    if (from_prior == 2) x = d.P[e];                    // user-supplied initial value kept verbatim
+    if (from_prior == 2 || fx) x = d.P[e];              // user-supplied initial value kept verbatim; a fixed column (also where A[n] == 0)
     else if (from_prior || a_n == 0.0) x = prior_draw<0>(d, e, t);
     else {
       double shape, rate;
@@ -361,10 +366,12 @@ __global__ __launch_bounds__(DW) void k_draw(Dev d, uint32_t t, RecDst rec, Side
   auto p_column = [&](int n) __attribute__((always_inline)) {
     const double a_n = d.A[n];
     const double Esum = d.Esum[n];
+    const bool fx = p_fixed(d, n);
     for (int k = tid; k < K; k += BW) {
       const int e = k + K * n;
       double x;
-      if (a_n == 0.0) x = prior_draw<0>(d, e, t);
+      if (fx) x = d.P[e];                                 // a fixed column: its value instead of a draw, the rest as below
+      else if (a_n == 0.0) x = prior_draw<0>(d, e, t);
       else {
         double shape, rate;
         if (d.prior == BNMF_GAMMA) { shape = slot<0>(d, d.Alpha_p, t)[e] + (double)d.ZsumG[e]; rate = slot<0>(d, d.Beta_p, t)[e] + a_n * Esum; }
@@ -407,11 +414,13 @@ __global__ __launch_bounds__(DW) void k_draw(Dev d, uint32_t t, RecDst rec, Side
   auto p_column_wave = [&](int n) __attribute__((always_inline)) {
     const double a_n = d.A[n];
     const double Esum = d.Esum[n];
+    const bool fx = p_fixed(d, n);
     double acc = 0.0;
     for (int k = lane; k < K; k += 64) {
       const int e = k + K * n;
       double x;
-      if (a_n == 0.0) x = prior_draw<0>(d, e, t);
+      if (fx) x = d.P[e];
+      else if (a_n == 0.0) x = prior_draw<0>(d, e, t);
       else {
         double shape, rate;
         if (d.prior == BNMF_GAMMA) { shape = slot<0>(d, d.Alpha_p, t)[e] + (double)d.ZsumG[e]; rate = slot<0>(d, d.Beta_p, t)[e] + a_n * Esum; }

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
   const MElem<NORMAL>* Mk = m_rows<NORMAL>(d) + (size_t)G * k;   // M[k, g] at Mt[g + G k] (Normal: the fp64 data)
   for (int j = tid; j < N; j += MHP_T) {
     const double pj = d.P[k + (size_t)K * j]; pa[j] = pj * d.A[j]; pcur[j] = pj;
-    anz[j] = d.A[j]; anz[N + j] = nzE[j] == 0 ? 1.0 : 0.0;
+    anz[j] = p_fixed(d, j) ? -1.0 : d.A[j]; anz[N + j] = nzE[j] == 0 ? 1.0 : 0.0;   // -1: a fixed column, whatever its A (A is 0 / 1; pa keeps the true product)
   }
   wg_lds_barrier();                                     // pa, anz are complete
 #ifdef ZSPROF
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
   // the factors' DrawPre by the LAST wave, one factor per lane (one pass for N <= 64; one factor per wave took two rounds at N = 20, with
   // every other lane of the workgroup waiting), while the other waves form the row's Mhat below: the first reader (thread 0, behind the first
   // barrier of the first factor step) finds them complete — every wave passes that barrier only after this code
-  if (wave == MHP_W - 1) for (int j = lane; j < N; j += 64) pre_store(prq + PRE_W * j, draw_pre<0>(d, k + K * j, t, MHSTEP));
+  if (wave == MHP_W - 1) for (int j = lane; j < N; j += 64) if (!p_fixed(d, j)) pre_store(prq + PRE_W * j, draw_pre<0>(d, k + K * j, t, MHSTEP));   // (a fixed column: no proposal, no uniform)
   double mh[REG ? MH_CPL : 1], enr[REG ? MH_CPL : 1], enx[REG ? MH_CPL : 1], sgr[(REG && NORMAL) ? MH_CPL : 1];
   double lg[(REG && MHSTEP) ? MH_CPL : 1];              // log(max(Mhat, 1e-6)) of the lane's cells
   MElem<NORMAL> mr[REG ? MH_CPL : 1];
@@ -351,6 +351,7 @@ __global__ __launch_bounds__(MHP_T) void k_mh_prow(Dev d, uint32_t t, int S, con
         for (int i = 0; i < MH_CPL; ++i) { const int g = g0r + 64 * i; if (wave < S && g < min(G, (wave + 1) * MH_SEG)) enx[i] = d.Et[g + (size_t)G * (n + 1)]; }
       }
     }
+    if (a_n < 0.0) continue;                                // a fixed column: no step; its term stays in Mhat (pa[n]), P[k, n] in pcur, accP[e] as it was
     if (a_n == 0.0) { if (tid == 0) { const double x = prior_draw<0>(d, e, t); d.P[e] = x; pcur[n] = x; } continue; }          // sample_Pn :12
     const bool allzero = anz[N + n] != 0.0;
     const double pold = pa[n];                                                             // P[k,n] * A[n]

@@ -15,7 +15,7 @@ constexpr uint32_t ST_VERSION = 1;
 constexpr size_t ST_HDR = 128, ST_RHDR = 32, ST_SHDR = 32;
 constexpr size_t ST_STAGE = (size_t)32 << 20;        // each of the two pinned staging halves
 enum { SEC_HYPER = 1, SEC_ARRAY = 2, SEC_R = 3, SEC_ZSUMK = 4, SEC_ZSUMG = 5, SEC_Z = 6, SEC_ZREC = 7, SEC_RING = 8, SEC_ZRING = 9,
-       SEC_ZRECRING = 10, SEC_HIST = 11 };
+       SEC_ZRECRING = 10, SEC_HIST = 11, SEC_FIXED = 12 /* the mask of fixed columns of P: base record only, only if a column is fixed */ };
 
 // 64-bit word hash (multiply-xorshift), streamed: the data hash of a handle, the temperature hash and the checksums
 struct Hash64 {
@@ -129,6 +129,11 @@ int plan_record(bnmf_handle* h, int since, std::vector<Sec>& out) {
       if (!is_hyper(id) || !a.d) continue;
       out.push_back(dev(SEC_HYPER, id, a.stride == 0 ? 1 : (int64_t)id_len(h, id), 8, a.d));
     }
+  if (since == 0 && h->n_fixed > 0) {                         // (a chain without fixed columns writes the bytes it always wrote)
+    Sec s{SEC_FIXED, BNMF_P, 0, (int64_t)N, 4};
+    s.host.resize(N * 4); memcpy(s.host.data(), h->fixedP.data(), N * 4);
+    out.push_back(s);
+  }
   for (int id : state_ids(h)) {
     const Arr& a = h->arr[id];
     if (!a.d) return fail(BNMF_ESTATE, "bnmf_save_state: array id %d has no value", id);
@@ -274,7 +279,7 @@ int scan_file(const char* fn, const char* path, FILE* f, const bnmf_handle* h, b
         hs.update(sb, ST_SHDR); left -= ST_SHDR; ++nsec;
         const uint32_t kind = get_at<uint32_t>(sb, 0), es = get_at<uint32_t>(sb, 24);
         const int64_t count = get_at<int64_t>(sb, 16);
-        if (kind < SEC_HYPER || kind > SEC_HIST || (es != 4 && es != 8) || count < 0 || (uint64_t)count * es > left || get_at<uint32_t>(sb, 28) != 0)
+        if (kind < SEC_HYPER || kind > SEC_FIXED || (es != 4 && es != 8) || count < 0 || (uint64_t)count * es > left || get_at<uint32_t>(sb, 28) != 0)
           return fail(BNMF_EINVAL, "%s: %s: record %d (iteration %d) is corrupt (section %u)", fn, path, ri, r.iter, nsec - 1);
         uint64_t n = (uint64_t)count * es;
         left -= n;
@@ -320,6 +325,7 @@ int sec_dest(bnmf_handle* h, int ri, int iter, uint32_t kind, int id, int64_t fi
     case SEC_Z: if (!h->dZ) return bad("Z in the file, save_Z off in the handle"); return one(h->dZ, K * N * G, 4);
     case SEC_ZREC: if (!h->zs.dRec || h->zs.dRecRing) return bad("Z records the handle does not keep"); return one(h->zs.dRec, h->zs.recwords, 4);
     case SEC_HIST: if (h->wcap <= 0) return bad("a history without a window"); return one(nullptr, (size_t)h->wcap * 4, 8);
+    case SEC_FIXED: if (id != BNMF_P || ri != 0) return bad("a mask of fixed columns outside the base record, or not of P"); return one(nullptr, N, 4);
     case SEC_RING: case SEC_ZRING: case SEC_ZRECRING: {
       const int64_t lo = std::max<int64_t>(1, (int64_t)iter - h->cfg.window + 1);
       size_t slot = 0; void* base = nullptr; uint32_t wes = 8;
@@ -349,6 +355,7 @@ int sec_dest(bnmf_handle* h, int ri, int iter, uint32_t kind, int id, int64_t fi
 int check_sections(bnmf_handle* h, const char* path, FILE* f, const std::vector<RecInfo>& recs) {
   const auto ids = state_ids(h);
   std::vector<int> have;
+  std::vector<int32_t> file_mask;
   for (size_t ri = 0; ri < recs.size(); ++ri) {
     long off = recs[ri].off + (long)ST_RHDR;
     for (uint32_t i = 0; i < recs[ri].nsec; ++i) {
@@ -358,6 +365,11 @@ int check_sections(bnmf_handle* h, const char* path, FILE* f, const std::vector<
       const uint32_t kind = get_at<uint32_t>(sb, 0), es = get_at<uint32_t>(sb, 24);
       const int64_t count = get_at<int64_t>(sb, 16);
       if (int rc = sec_dest(h, (int)ri, recs[ri].iter, kind, get_at<int32_t>(sb, 4), get_at<int64_t>(sb, 8), count, es, p, n)) return rc;
+      if (kind == SEC_FIXED) {                                 // a mask given to the handle beforehand must be the file's
+        file_mask.resize((size_t)count);
+        if (fread(file_mask.data(), 4, (size_t)count, f) != (size_t)count) return fail(BNMF_EINVAL, "bnmf_load_state: record %zu: cannot read a section", ri);
+        for (int32_t v : file_mask) if (v != 0 && v != 1) return fail(BNMF_EINVAL, "bnmf_load_state: %s: the mask of fixed columns is corrupt", path);
+      }
       if (kind == SEC_ARRAY && ri == 0) have.push_back(get_at<int32_t>(sb, 4));
       if (kind == SEC_R && ri == 0) have.push_back(BNMF_R);
       off += (long)(ST_SHDR + (size_t)count * es);
@@ -366,6 +378,13 @@ int check_sections(bnmf_handle* h, const char* path, FILE* f, const std::vector<
   for (int id : ids) if (std::find(have.begin(), have.end(), id) == have.end())
     return fail(BNMF_EINVAL, "bnmf_load_state: %s: the full record carries no value of array id %d", path, id);
   if (std::find(have.begin(), have.end(), (int)BNMF_R) == have.end()) return fail(BNMF_EINVAL, "bnmf_load_state: %s: the full record carries no R", path);
+  if (!h->fixedP.empty())
+    for (size_t n = 0; n < h->fixedP.size(); ++n) {
+      const int32_t fv = file_mask.empty() ? 0 : file_mask[n];
+      if (fv != h->fixedP[n])
+        return fail(BNMF_ESTATE, "bnmf_load_state: column %zu of P is %s in %s and %s on the handle (bnmf_set_fixed)", n, fv ? "fixed" : "not fixed", path,
+                    h->fixedP[n] ? "fixed" : "not fixed");
+    }
   return 0;
 }
 
@@ -436,6 +455,7 @@ int bnmf_load_state(bnmf_handle* h, const char* path, int* iter_out) {
   struct IterGuard { bnmf_handle* h; bool done = false; ~IterGuard() { if (!done) h->iter = 0; } } guard{h};   // a replay that fails: not "has run"
   bool have_ev[2] = {false, false};
   size_t half = 0;
+  std::vector<int32_t> file_mask;                              // applied once the replay has succeeded: a failed one leaves the handle's mask alone
   for (size_t ri = 0; ri < recs.size(); ++ri) {
     const int iter = recs[ri].iter;
     h->iter = iter;                                            // (cur_slot: the prior parameters of this record's iteration)
@@ -450,6 +470,11 @@ int bnmf_load_state(bnmf_handle* h, const char* path, int* iter_out) {
       off += (long)(ST_SHDR + nbytes);
       void* p[2]; size_t n[2];
       if (int rc = sec_dest(h, (int)ri, iter, kind, id, get_at<int64_t>(sb, 8), count, es, p, n)) return rc;
+      if (kind == SEC_FIXED) {
+        file_mask.resize((size_t)count);
+        if (fread(file_mask.data(), 1, nbytes, fc.f) != nbytes) return fail(BNMF_EINVAL, "bnmf_load_state: %s: read failed", path);
+        continue;
+      }
       if (kind == SEC_HYPER || kind == SEC_HIST) {             // small: through host memory
         std::vector<double> v((size_t)count);
         if (fread(v.data(), 1, nbytes, fc.f) != nbytes) return fail(BNMF_EINVAL, "bnmf_load_state: %s: read failed", path);
@@ -477,6 +502,7 @@ int bnmf_load_state(bnmf_handle* h, const char* path, int* iter_out) {
     }
   }
   HIPCHK(hipStreamSynchronize(h->stream));
+  if (!file_mask.empty()) if (int rc = apply_fixed(h, file_mask.data())) return rc;
   // What the next bnmf_run recomputes (the hyper sweep of iter + 1, Esum / Psum, Et, nzE, Mhat, the partial sums) is invalidated as
   // bnmf_init's re-initialisation does it; the sync words are cleared — a handle from the pool may hold another chain's
   HIPCHK(hipMemset(h->dFlags, 0, 64));

@@ -53,9 +53,9 @@ static RecDst rec_pdraw(const bnmf_handle* h, uint32_t t, bool on) {   // what k
 // workgroups of the hyper sweep's P part (K N elements) and E part (N G elements), RT lanes each
 static int side_nbP(const bnmf_handle* h) { return (int)(((size_t)h->cfg.K * h->cfg.N + RT - 1) / RT); }
 static int side_nbE(const bnmf_handle* h) { return (int)(((size_t)h->cfg.N * h->cfg.G + RT - 1) / RT); }
-static void launch_pdraw(bnmf_handle* h, uint32_t t, int from_prior, bool rec) {
+static void launch_pdraw(bnmf_handle* h, uint32_t t, int from_prior, bool rec, const int* keep = nullptr) {   // keep: see k_pdraw
   const size_t lds = 2 * (size_t)h->cfg.K * sizeof(double);
-  hipLaunchKernelGGL(k_pdraw, dim3(h->cfg.N), dim3(PD_T), lds, h->stream, h->dev, t, from_prior, 1, rec_pdraw(h, t, rec), SideWait{});
+  hipLaunchKernelGGL(k_pdraw, dim3(h->cfg.N), dim3(PD_T), lds, h->stream, h->dev, t, from_prior, 1, rec_pdraw(h, t, rec), SideWait{}, keep);
 }
 static void launch_edraw(bnmf_handle* h, uint32_t t, int from_prior, bool rec) {
   hipLaunchKernelGGL(k_edraw, dim3(h->nblkE), dim3(ES_T), 0, h->stream, h->dev, t, from_prior, 1, rec_at(h, t, rec).E);
@@ -570,7 +570,7 @@ static void launch_mh_PE(bnmf_handle* h, uint32_t t, int converged, bool poll = 
   }
   assert(!(h->pipe.mh_prep_valid && h->pipe.mh_pipe_valid));
   double* accP = h->arr[BNMF_ACC_P].d; double* accE = h->arr[BNMF_ACC_E].d;
-  const bool regP = S <= MHP_W;                              // one 320-column segment per wave: the row's cells stay in registers
+  const bool regP = S <= MHP_W && !h->mh.no_reg;                              // one 320-column segment per wave: the row's cells stay in registers
   const size_t ldsP = (4 * (size_t)S + 2 * N + 2 + (size_t)(PRE_W + 2) * N + ((regP && mhstep) ? (size_t)MH_CPL * MHP_T : 0)) * sizeof(double);
   const bool pipe = pp != nullptr;                         // hosted form (sweep_mh): parity flag buffers, hosted workgroups behind the rows / the column blocks
   int* const nzb = h->mh.dNzE + 2 * N;                        // nzE[2][N], nzP[2][N]
@@ -770,7 +770,7 @@ static void launch_pdraw_split(bnmf_handle* h, uint32_t t, bool rec, bool poll) 
   if (h->cfg.learning_rank) flush_colterms(h);           // (fixed rank: launch_side_E takes the column terms of t - 1 along)
   hipExtLaunchKernelGGL(k_pdraw, dim3(h->cfg.N), dim3(PD_T), (uint32_t)(2 * (size_t)h->cfg.K * sizeof(double)), h->stream,
                         nullptr, h->ev_p, 0, h->dev, t, 0, 0, rec_pdraw(h, t, rec),
-                        poll ? SideWait{h->dFlags + 1, h->dFlags + 3, t, h->dErr} : SideWait{});
+                        poll ? SideWait{h->dFlags + 1, h->dFlags + 3, t, h->dErr} : SideWait{}, (const int*)nullptr);
   h->pipe.gate_f0 = 1;
 }
 static void launch_edraw_split(bnmf_handle* h, uint32_t t, bool rec) {   // ... and k_edraw, its completion as ev_draw

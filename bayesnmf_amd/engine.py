@@ -78,7 +78,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_assign_at", "bnmf_label_switching", "bnmf_get_iter", "bnmf_profile",
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
-               "bnmf_save_state", "bnmf_load_state", "bnmf_state_info"]
+               "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed"]
 
 
 def lib():
@@ -125,6 +125,8 @@ def lib():
         L.bnmf_save_state.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_size_t)]
         L.bnmf_load_state.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
         L.bnmf_state_info.argtypes = [C.c_char_p, C.POINTER(BnmfStateDesc)]
+        L.bnmf_set_fixed.argtypes = [C.c_void_p, C.c_int, ip, C.c_size_t]
+        L.bnmf_get_fixed.argtypes = [C.c_void_p, C.c_int, ip, C.c_size_t]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -288,6 +290,21 @@ class Engine:
             out = np.empty(n)
             _chk(lib().bnmf_get_array(self._h, IDS[name], _dp(out), n))
         return out.reshape(shp, order="F")
+
+    def set_fixed(self, name, mask):
+        """Hold the columns of P flagged in mask (length N, 0 / 1) at the value set("P", ...) gives them (bnmf_set_fixed); before
+        init() / load_state()."""
+        m = np.asarray(mask)
+        if m.dtype.kind == "f" and not (m == np.floor(m)).all():
+            raise BnmfError(-1, "set_fixed: the mask holds a value that is neither 0 nor 1")
+        m = np.ascontiguousarray(m.ravel(), dtype=np.int32)
+        _chk(lib().bnmf_set_fixed(self._h, IDS[name], m.ctypes.data_as(C.POINTER(C.c_int32)), m.size))
+
+    def get_fixed(self, name):
+        """The mask of fixed columns (bnmf_get_fixed): int32, length N; zeros if none was set."""
+        out = np.empty(self.N, dtype=np.int32)
+        _chk(lib().bnmf_get_fixed(self._h, IDS[name], out.ctypes.data_as(C.POINTER(C.c_int32)), out.size))
+        return out
 
     def init(self):
         row = np.empty(NMETRIC)

@@ -66,7 +66,7 @@ class bayesNMF_sampler:
                  output_dir=None, overwrite=False, hyperprior_params=None, init_prior_params=None,
                  init_params=None, verbosity=1, periodic_save=True, save_all_samples=False,
                  seed=1, chain_id=0, device=0, save_Z=False, engine_factory=None, intermediate_credible_intervals=False,
-                 engine_side_convergence=True, save_engine_state=False):
+                 engine_side_convergence=True, save_engine_state=False, fixed_P=None):
         if MH is None:
             MH = likelihood == "poisson" and prior in ("truncnormal", "exponential")
         cc = dict(convergence_control) if convergence_control is not None else new_convergence_control()
@@ -139,6 +139,11 @@ class bayesNMF_sampler:
         self.log("Setting hyperprior parameters", verbosity=1)
         self._check_model()
         self.log("Model check passed", verbosity=1)
+        fixed = self._check_fixed_P(fixed_P, init_params)
+        if fixed is not None:
+            self.specs["fixed_P"] = fixed                 # (kept by save_object: load_sampler rebuilds the same engine)
+            self.log(f"fixed_P: columns 1..{fixed.shape[1]} of P held fixed" + (" (refit: only E is sampled)" if fixed.shape[1] == self.dims["N"] else ""),
+                     verbosity=1)
 
         factory = engine_factory or Engine
         kw = dict(likelihood=likelihood, prior=prior, MH=bool(MH), learning_rank=learning_rank,
@@ -152,12 +157,24 @@ class bayesNMF_sampler:
         if save_engine_state and not hasattr(self._chain, "save_state"):
             self.close()
             raise ValueError("save_engine_state = TRUE needs an engine that can save its state (save_state); this engine_factory's cannot")
+        if fixed is not None and not hasattr(self._chain, "set_fixed"):
+            self.close()
+            raise ValueError("fixed_P needs an engine that can hold columns of P fixed (set_fixed); this engine_factory's cannot")
         self.hyperprior_params = apply_hyperprior_params(self._chain, prior, data, self.dims["N"], hyperprior_params)
         self.log("Initializing prior parameters and parameters", verbosity=1)
         for name, val in (init_prior_params or {}).items():
             self._chain.set(name, val)
         for name, val in (init_params or {}).items():
             self._chain.set(name, val)
+        if fixed is not None:
+            F = fixed.shape[1]
+            if "P" not in (init_params or {}):                 # the other columns: no value (NaN), drawn from the prior by init()
+                P0 = np.full((self.dims["K"], self.dims["N"]), np.nan)
+                P0[:, :F] = fixed
+                self._chain.set("P", P0)
+            mask = np.zeros(self.dims["N"], dtype=np.int32)
+            mask[:F] = 1
+            self._chain.set_fixed("P", mask)
         self.log("Sampling parameters from priors", verbosity=1)
         row = self._chain.init()
         self.log("Logging initial sample", verbosity=1)
@@ -182,6 +199,36 @@ class bayesNMF_sampler:
                 self._error("gamma prior cannot be used in a MH-within-gibbs sampler")
             if pr == "truncnormal" and not MH:
                 self._error("truncnormal prior can only be used in a MH-within-gibbs sampler")
+
+    def _check_fixed_P(self, fixed_P, init_params):
+        """fixed_P (K x F): known signatures that become columns 1..F of P and are never drawn.  Returns it as a float array, or None."""
+        if fixed_P is None:
+            return None
+        K, N = self.dims["K"], self.dims["N"]
+        fp = np.asarray(fixed_P, dtype=float)
+        if fp.ndim == 1:
+            fp = fp[:, None]
+        if fp.ndim != 2 or fp.shape[0] != K:
+            self._error(f"fixed_P has {fp.shape[0]} rows, but data has {K} rows.")
+        F = fp.shape[1]
+        if F < 1:
+            self._error("fixed_P has no columns")
+        if F > N:
+            self._error(f"fixed_P has {F} columns, but the rank (or the top of the rank range) is {N}; it must be >= {F}")
+        if np.isnan(fp).any():
+            self._error(f"fixed_P has NaN entries (column {int(np.argwhere(np.isnan(fp))[0][1]) + 1})")
+        bad = (fp < 0) | np.isinf(fp)
+        if bad.any():
+            self._error(f"fixed_P must be finite and non-negative (column {int(np.argwhere(bad)[0][1]) + 1})")
+        zero = np.where(fp.sum(axis=0) == 0)[0]
+        if zero.size:
+            self._error(f"fixed_P column {int(zero[0]) + 1} sums to 0")
+        ip = (init_params or {}).get("P")
+        if ip is not None:
+            ip = np.asarray(ip, dtype=float)
+            if ip.shape != (K, N) or not np.array_equal(ip[:, :F], fp):
+                self._error(f"init_params$P contradicts fixed_P: its columns 1..{F} must equal fixed_P")
+        return np.ascontiguousarray(fp)
 
     def _error(self, msg):
         msg = "ERROR: " + msg
@@ -662,6 +709,10 @@ def load_sampler(output_dir, device=None):
                       prior=sp["prior"], MH=sp["MH"], learning_rank=sp["learning_rank"], rank_method=sp["engine_rank_method"],
                       seed=sp["seed"], chain_id=sp["chain_id"], temperature=s.temperature_schedule, save_Z=sp["save_Z"],
                       window=sp["window"], device=dev)
+    if sp.get("fixed_P") is not None:                        # (the state file carries the mask too: load_state checks the two agree)
+        mask = np.zeros(s.dims["N"], dtype=np.int32)
+        mask[:np.asarray(sp["fixed_P"]).shape[1]] = 1
+        s._chain.set_fixed("P", mask)
     it = s._chain.load_state(st)
     if it != int(s.state["iter"]):
         s._chain.close()
@@ -676,13 +727,18 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
              convergence_control=None, prop_temp=0.2, post_warmup=None, output_dir=None, overwrite=False,
              hyperprior_params=None, init_prior_params=None, init_params=None, periodic_save=True,
              save_all_samples=True, seed=1, chain_id=0, device=0, save_Z=False, engine_factory=None,
-             intermediate_credible_intervals=False, n_chains=1, devices=None, engine_side_convergence=True, save_engine_state=False):
+             intermediate_credible_intervals=False, n_chains=1, devices=None, engine_side_convergence=True, save_engine_state=False,
+             fixed_P=None):
     """bayesNMF() (R/bayesNMF.R:24-138): build the sampler and run it; with rank_method = "BIC" run one
     fixed-rank sampler per rank and return dict(results, best_rank, sampler).
 
     New optional trailing arguments: seed, chain_id, device, save_Z, and n_chains / devices:
     n_chains > 1 runs independent replicas (chain_id = 0..n_chains-1 in the Philox key), chain c on
-    devices[c % len(devices)], and returns the list of samplers (multichain.run_chains)."""
+    devices[c % len(devices)], and returns the list of samplers (multichain.run_chains).
+
+    fixed_P (K x F): known signatures held fixed as columns 1..F of P (never drawn); the rank, or the top of a rank range, must
+    be >= F.  F == rank is a refit (only E is sampled); with a rank range SBFI / BFI learn which of the known signatures are
+    present; with rank_method = "BIC" the ranks below F are dropped."""
     if n_chains and n_chains > 1:
         from .multichain import run_chains
         kw = dict(likelihood=likelihood, prior=prior, rank_method=rank_method, MH=MH, convergence_control=convergence_control,
@@ -690,7 +746,7 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
                   hyperprior_params=hyperprior_params, init_prior_params=init_prior_params, init_params=init_params,
                   periodic_save=periodic_save, save_all_samples=save_all_samples, seed=seed, save_Z=save_Z,
                   engine_factory=engine_factory, intermediate_credible_intervals=intermediate_credible_intervals,
-                  engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state)
+                  engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state, fixed_P=fixed_P)
         return run_chains(data, rank, n_chains=n_chains, devices=devices, **kw)
     if output_dir is None:
         output_dir = f"nmf_{likelihood}_{prior}"
@@ -700,9 +756,16 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
                   init_params=init_params, verbosity=1, periodic_save=periodic_save,
                   save_all_samples=save_all_samples, seed=seed, chain_id=chain_id, device=device, save_Z=save_Z,
                   engine_factory=engine_factory, intermediate_credible_intervals=intermediate_credible_intervals,
-                  engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state)
+                  engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state, fixed_P=fixed_P)
     ranks = np.atleast_1d(np.asarray(rank, dtype=int))
     if ranks.size > 1 and rank_method == "BIC":
+        if fixed_P is not None:
+            F = np.asarray(fixed_P).shape[1] if np.ndim(fixed_P) > 1 else 1
+            if (ranks < F).any():
+                print(f"fixed_P has {F} columns: dropping ranks {[int(k) for k in ranks[ranks < F]]} (below {F}) from the BIC sweep")
+                ranks = ranks[ranks >= F]
+            if ranks.size == 0:
+                raise ValueError(f"ERROR: fixed_P has {F} columns, but the top of the rank range is below {F}")
         # One fixed-rank sampler per rank (R/bayesNMF.R:66-126).  The reference runs them one after the other; they are
         # independent, so here they run concurrently, one host thread per sampler, spread over the visible GPUs
         # (SURVEY.md 8 f2); `devices` picks the GPUs, default all of them.

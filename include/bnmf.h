@@ -94,6 +94,24 @@ int bnmf_set_array(bnmf_handle* h, int id, const double* colmajor, size_t n);
 int bnmf_get_array(bnmf_handle* h, int id, double* colmajor_out, size_t n);
 int bnmf_get_array_i32(bnmf_handle* h, int id, int32_t* out, size_t n);   /* Z, ZsumK, ZsumG */
 
+/* Hold chosen columns of P fixed (refit to a known catalogue).  id must be BNMF_P, fixed[N] holds 0 / 1.  Iteration t of
+ * a chain with a mask is the loop body with sample_Pn skipped for every n with fixed[n] = 1, nothing else changed: P[, n] keeps, bit for
+ * bit, the value bnmf_set_array(BNMF_P) gave it (also while A[n] == 0: no prior redraw); every other draw keeps its Philox stream —
+ * the P-side prior parameters of a fixed column go on being drawn, from the fixed P; Psum, the recorded samples, the log-prior and the
+ * metrics are produced as always.  n_params stays sum(A) * (G + K): it is NOT reduced for fixed columns.  The BNMF_ACC_P entries of a
+ * fixed column are never written: they stay as bnmf_init left them (no value, NaN), and P_mean_acceptance_rate averages them as before.
+ * A mask of zeros, or no call, is the chain without the feature, bit for bit.  Call before bnmf_init / bnmf_load_state.
+ *   bnmf_set_fixed refuses: id != BNMF_P with BNMF_EMODEL (fixing rows of E is out of scope), n != N with BNMF_ESIZE, a value other than
+ *   0 / 1 with BNMF_EINVAL, a handle that has been initialised, loaded or run with BNMF_ESTATE (the column or value named).
+ *   bnmf_init then refuses, on the host and before its first device write: a fixed column whose P[, n] was not set or holds NaN with
+ *   BNMF_EUNSET; one with a negative or infinite entry or a column sum of 0 with BNMF_EINVAL.  Columns that are NOT fixed and carry a NaN
+ *   in the supplied P are drawn from the prior at bnmf_init (without a mask a supplied P is kept whole, as before).
+ *   bnmf_save_state writes the mask into the base record (only if a column is fixed: other chains write the bytes they always wrote);
+ *   bnmf_load_state applies it, and refuses a handle that was given another mask with BNMF_ESTATE, the column named.
+ * bnmf_get_fixed returns the mask (zeros if none was set); bnmf_get_stat(h, 8) the number of fixed columns. */
+int bnmf_set_fixed(bnmf_handle* h, int id, const int32_t* fixed, size_t n);
+int bnmf_get_fixed(bnmf_handle* h, int id, int32_t* out, size_t n);
+
 /* constructor draws: prior params from hyper-priors unless supplied, then
  * sample_params(from_prior=TRUE), record iteration 1 and its metrics row
  * (R/bayesNMF_sampler.R:232-257).  metrics_row1 may be NULL. */
@@ -224,7 +242,12 @@ int bnmf_state_info(const char* path, bnmf_state_desc* out);
  * sorted schedule: samples$Z is kept as these records and expanded when read), 1 bytes of Mhat left for the per-column metric terms,
  * 2 whether samples$Z is a ring of records, 3 whether Z is expanded every iteration (BNMF_ZEAGER=1), 4 whether the MH sweep hosts what followed
  * its two kernels inside them (Poisson MH models at fixed rank; BNMF_MHPIPE=0: no), 5 the quads (4 counts) per item of the sorted schedule,
- * 6 the blocks (workgroups) of the static allocation schedule, 7 how many of them have no column of their own (sorted schedule) */
+ * 6 the blocks (workgroups) of the static allocation schedule, 7 how many of them have no column of their own (sorted schedule),
+ * 8 the number of columns of P held fixed (bnmf_set_fixed), 9 the form of the MH / Normal row sweep (1 Mhat in registers, 2 Mhat in memory; 0: no such
+ * sweep), 10 the launches of the merged draw kernel so far, 11 whether the allocation kernel is k_zalloc_step.
+ * BNMF_MHAT (bnmf_get_array; tests): the rows of Mhat as the last row sweep of the MH / Normal models left them, P_t diag(A) E_(t-1),
+ * maintained factor by factor.  Readable where the sweep keeps them in memory (statistic 9 == 2: more than 5,120 columns, or a handle
+ * created under BNMF_MHREG=0, which takes that form whatever G — the same bits, slower); else BNMF_EUNSET. */
 int bnmf_get_stat(bnmf_handle* h, int what, double* out);
 
 /* average device time (ms) of each kernel class over n_iter iterations, measured with HIP

@@ -28,9 +28,11 @@ bayesNMF_sampler_hip <- R6::R6Class(
   "bayesNMF_sampler", inherit = bayesNMF::bayesNMF_sampler,
   public = list(
     handle = NULL,
-    initialize = function(..., seed = 1, chain_id = 0L, device = 0L, save_Z = FALSE, save_engine_state = FALSE) {
+    # fixed_P (K x F): known signatures held fixed as columns 1..F of P, never drawn (bnmf_set_fixed).  The rank, or the top of a rank
+    # range, must be >= F; F == rank is a refit (only E is sampled).  Checked before the reference constructor runs.
+    initialize = function(..., seed = 1, chain_id = 0L, device = 0L, save_Z = FALSE, save_engine_state = FALSE, fixed_P = NULL) {
       private$hip <- list(seed = seed, chain_id = chain_id, device = device, save_Z = save_Z, save_engine_state = save_engine_state,
-                          state_iter = 0L, post_warmup_done = 0)
+                          state_iter = 0L, post_warmup_done = 0, fixed_P = private$check_fixed_P(fixed_P))
       super$initialize(...)     # runs the reference constructor; its prior draws are redirected below
     },
     # save_object (R/bayesNMF_sampler.R:414-416): sampler.rds, then (save_engine_state) the device state beside it — a full record at
@@ -161,6 +163,16 @@ bayesNMF_sampler_hip <- R6::R6Class(
   ),
   private = list(
     hip = NULL,
+    # fixed_P as a double matrix, or NULL; refusals in the reference's ERROR: convention (what needs the dims is checked in sample_params)
+    check_fixed_P = function(fixed_P) {
+      if (is.null(fixed_P)) return(NULL)
+      fp <- as.matrix(fixed_P); storage.mode(fp) <- "double"
+      if (ncol(fp) < 1) stop("ERROR: fixed_P has no columns")
+      if (anyNA(fp)) stop("ERROR: fixed_P has NaN entries")
+      if (any(fp < 0 | is.infinite(fp))) stop("ERROR: fixed_P must be finite and non-negative")
+      if (any(colSums(fp) == 0)) stop(glue::glue("ERROR: fixed_P column {which(colSums(fp) == 0)[1]} sums to 0"))
+      unname(fp)
+    },
     # the constructor's sample_params(from_prior = TRUE) + record_sample + update_sample_metrics
     sample_params = function(skip = c(), from_prior = FALSE) {
       if (!from_prior) stop("per-iteration sampling goes through run_block()")
@@ -174,6 +186,19 @@ bayesNMF_sampler_hip <- R6::R6Class(
       for (nm in names(self$prior_params)) if (nm %in% names(.bnmf_ids) && is.matrix(self$prior_params[[nm]]))
         .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$prior_params[[nm]]))
       for (nm in skip) if (nm %in% names(.bnmf_ids)) .Call("C_bnmf_set_array", self$handle, .bnmf_ids[[nm]], as.double(self$params[[nm]]))
+      fp <- private$hip$fixed_P
+      if (!is.null(fp)) {
+        if (nrow(fp) != self$dims$K) stop(glue::glue("ERROR: fixed_P has {nrow(fp)} rows, but data has {self$dims$K} rows."))
+        if (ncol(fp) > self$dims$N) stop(glue::glue("ERROR: fixed_P has {ncol(fp)} columns, but the rank (or the top of the rank range) is {self$dims$N}; it must be >= {ncol(fp)}"))
+        if ("P" %in% skip) {
+          if (!identical(unname(as.matrix(self$params$P)[, seq_len(ncol(fp)), drop = FALSE]), unname(fp)))
+            stop(glue::glue("ERROR: init_params$P contradicts fixed_P: its columns 1..{ncol(fp)} must equal fixed_P"))
+        } else {                                             # the other columns: no value (NA), drawn from the prior by bnmf_init
+          P0 <- matrix(NA_real_, self$dims$K, self$dims$N); P0[, seq_len(ncol(fp))] <- fp
+          .Call("C_bnmf_set_array", self$handle, .bnmf_ids[["P"]], as.double(P0))
+        }
+        .Call("C_bnmf_set_fixed", self$handle, .bnmf_ids[["P"]], as.integer(seq_len(self$dims$N) <= ncol(fp)))
+      }
       row <- .Call("C_bnmf_init", self$handle)
       private$pull_state(); private$bind_metrics(matrix(row, ncol = 1))
     },
@@ -208,6 +233,8 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (info$last_iter != self$state$iter) stop(glue::glue("{path} ends at iteration {info$last_iter}, sampler.rds at iteration {self$state$iter}"))
       private$hip$device <- as.integer(device)
       private$create_handle()
+      if (!is.null(private$hip$fixed_P))                     # (the file carries the mask too: bnmf_load_state checks that the two agree)
+        .Call("C_bnmf_set_fixed", self$handle, .bnmf_ids[["P"]], as.integer(seq_len(self$dims$N) <= ncol(private$hip$fixed_P)))
       it <- .Call("C_bnmf_load_state", self$handle, path)
       private$hip$state_iter <- as.integer(it)
       self$specs$output_dir <- output_dir

@@ -65,6 +65,31 @@ SEXP C_bnmf_get_array(SEXP ptr, SEXP id, SEXP n) {
   UNPROTECT(1);
   return out;
 }
+/* hold columns of P fixed (bnmf_set_fixed): C_bnmf_set_fixed(ptr, id (.bnmf_ids[["P"]]), mask (integer 0 / 1, length N)), before
+ * C_bnmf_init / C_bnmf_load_state; C_bnmf_get_fixed(ptr, id, n (= N)) -> the mask as an integer vector.  The arguments are checked
+ * before the handle is touched */
+SEXP C_bnmf_set_fixed(SEXP ptr, SEXP id, SEXP mask) {
+  if (XLENGTH(id) != 1) Rf_error("bnmf: id must be one integer");
+  const R_xlen_t n = XLENGTH(mask);
+  if (n < 1) Rf_error("bnmf: the mask of fixed columns is empty");
+  const int* m = INTEGER(mask);
+  int32_t* f = (int32_t*)R_alloc((size_t)n, sizeof(int32_t));
+  for (R_xlen_t i = 0; i < n; ++i) {
+    if (m[i] == NA_INTEGER) Rf_error("bnmf: the mask of fixed columns holds NA (entry %ld)", (long)(i + 1));
+    f[i] = (int32_t)m[i];
+  }
+  chk(bnmf_set_fixed(get_handle(ptr), INTEGER(id)[0], f, (size_t)n));
+  return R_NilValue;
+}
+SEXP C_bnmf_get_fixed(SEXP ptr, SEXP id, SEXP n) {
+  if (XLENGTH(id) != 1 || XLENGTH(n) != 1) Rf_error("bnmf: id and n must be one number each");
+  const double len = REAL(n)[0];
+  if (!(len >= 1.0) || len > 2147483647.0) Rf_error("bnmf: n = %g is not a number of columns", len);
+  SEXP out = PROTECT(Rf_allocVector(INTSXP, (R_xlen_t)len));
+  chk(bnmf_get_fixed(get_handle(ptr), INTEGER(id)[0], (int32_t*)INTEGER(out), (size_t)len));
+  UNPROTECT(1);
+  return out;
+}
 SEXP C_bnmf_init(SEXP ptr) {
   SEXP row = PROTECT(Rf_allocVector(REALSXP, BNMF_NMETRIC));
   chk(bnmf_init(get_handle(ptr), REAL(row)));
@@ -330,6 +355,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_destroy", (DL_FUNC)&C_bnmf_destroy, 1}, {"C_bnmf_device_info", (DL_FUNC)&C_bnmf_device_info, 1},
   {"C_bnmf_save_state", (DL_FUNC)&C_bnmf_save_state, 3}, {"C_bnmf_load_state", (DL_FUNC)&C_bnmf_load_state, 2},
   {"C_bnmf_state_info", (DL_FUNC)&C_bnmf_state_info, 1},
+  {"C_bnmf_set_fixed", (DL_FUNC)&C_bnmf_set_fixed, 3}, {"C_bnmf_get_fixed", (DL_FUNC)&C_bnmf_get_fixed, 3},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
