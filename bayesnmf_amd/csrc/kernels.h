@@ -1418,6 +1418,12 @@ __global__ void k_test_math(int fn, const double* in, double* out, size_t n) {
 __global__ void k_test_sampler(int which, uint32_t k0, uint32_t k1, uint32_t var, uint32_t elem0, uint32_t iter,
                                const double* a, const double* b, const double* c, double* out, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (which == 7) {   // ralpha_fast_wave: every lane of every wave calls it, the lanes past n as helpers without an element
+    const bool act = i < n;
+    const double r = ralpha_fast_wave(act, k0, k1, var, elem0 + (uint32_t)i, iter, act ? a[i] : 0.0, act ? b[i] : 0.0, act ? c[i] : 0.0, g_alut);
+    if (act) out[i] = r;
+    return;
+  }
   if (i >= n) return;
   Stream s(k0, k1, var, elem0 + (uint32_t)i, iter);
   double r;

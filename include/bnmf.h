@@ -264,6 +264,8 @@ int bnmf_ubench(int device, double* philox_words_per_s, double* copy_gbs);
 
 /* device-side unit probes used by the parity tests (tests/test_gpu_*.py) */
 int bnmf_test_math(int device, int fn, const double* in, double* out, size_t n);
+/* which: 0 rgamma(a, b), 1 rtnorm0(a, b), 2 rnorm, 3 ralpha(a, b, c), 4 runif, 5 rexp(a), 6 ralpha_fast(a, b, c), 7 ralpha_fast_wave(a, b, c):
+ * the wave-cooperative form of 6 (every lane of every wave calls it; the lanes past n take part without an element) */
 int bnmf_test_sampler(int device, int which, uint64_t seed, uint32_t chain, uint32_t var,
                       uint32_t elem0, uint32_t iter, const double* a, const double* b,
                       const double* c, double* out, size_t n);

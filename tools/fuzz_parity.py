@@ -18,6 +18,19 @@ rng_big = np.random.default_rng(7919 + int(os.environ.get("FUZZ_SEED", "1")))   
 # from a stream of their own; unset, every case of a seed is what it always was
 fuzz_real = os.environ.get("FUZZ_REAL") == "1"
 rng_real = np.random.default_rng(104729 + int(os.environ.get("FUZZ_SEED", "1")))
+# FUZZ_HYPER=1: upper-case hyper-prior matrices, every entry within a decade around the default scalar; FUZZ_KEY=1: a 64-bit seed and a
+# random chain id (both words of the Philox key in use).  Streams of their own again
+fuzz_hyper, fuzz_key = os.environ.get("FUZZ_HYPER") == "1", os.environ.get("FUZZ_KEY") == "1"
+rng_hyper = np.random.default_rng(1299709 + int(os.environ.get("FUZZ_SEED", "1")))
+rng_key = np.random.default_rng(15485863 + int(os.environ.get("FUZZ_SEED", "1")))
+def hyper_matrices(prior, M, N):
+    from bayesnmf_amd.setup import default_hyperprior_params
+    out = {}
+    for k, v in default_hyperprior_params(prior, M, N).items():
+        shp = (M.shape[0], N) if k.endswith("_p") else (N, M.shape[1])
+        f = 10.0 ** rng_hyper.uniform(-0.5, 0.5, size=shp)
+        out[k[0].upper() + k[1:]] = f * v if v != 0 else rng_hyper.uniform(0.0, 1.0, size=shp)
+    return out
 n_cases = int(os.environ.get("FUZZ_N", "60"))
 bad = 0
 t0 = time.time()
@@ -40,6 +53,7 @@ for case in range(n_cases):
     if real:
         M = np.asfortranarray(M + rng_real.normal(0.0, 1.0 + 0.2 * M.std(), size=M.shape))
     kw = dict(seed=int(rng.integers(1, 1000)), learning_rank=lr)
+    if fuzz_key: kw.update(seed=int(rng_key.integers(0, 2 ** 64, dtype=np.uint64)), chain_id=int(rng_key.integers(0, 2 ** 32)))
     save_Z = bool(rng.random() < 0.4) and model in ("gamma", "exponential")      # full mode of the Gibbs sweep: Z itself is compared
     if save_Z: kw["save_Z"] = True
     only = os.environ.get("FUZZ_ONLY")
@@ -53,7 +67,8 @@ for case in range(n_cases):
     try:
         o = O.Oracle(M, N, nthreads=4, **kw)
         e = Engine(M, N, window=window, **kw)
-        apply_hyperprior_params(o, kw["prior"], M, N); apply_hyperprior_params(e, kw["prior"], M, N)
+        user = hyper_matrices(kw["prior"], M, N) if fuzz_hyper else None
+        apply_hyperprior_params(o, kw["prior"], M, N, user); apply_hyperprior_params(e, kw["prior"], M, N, user)
         r0, r1 = o.init(), e.init()
         ok = same_bits(r0[:9], r1[:9])
         for conv in (False, True):
