@@ -31,6 +31,7 @@
 #include "zalloc_step.h"
 #include "rank.h"
 #include "mh.h"
+#include "waic.h"
 
 using namespace bnmf;
 
@@ -253,6 +254,7 @@ struct bnmf_handle {
   hipEvent_t ev[2 * BNMF_NKERNEL]{};
   bool have_ev = false;
   double* dMap = nullptr; size_t map_words = 0;   // scratch of bnmf_map (grown on demand)
+  double* dWaic = nullptr; size_t waic_words = 0; // scratch of bnmf_waic (grown on demand): column sums, cell values, slot list
   int devlock_fd = -1;                 // the device's lock file (<BNMF_LOCKDIR or /tmp>/bnmf_dev_<PCI bus id>.lock): the device gate's rule across the PROCESSES that share the device
   int devgate_fd = -1;                 // ... and its turnstile (.gate): a process that wants the device exclusively holds it while it waits, new sharers queue behind it
   bool devlock_off = false;            // BNMF_DEVLOCK=0: the caller vouches that no other process uses the device
@@ -1588,6 +1590,71 @@ int bnmf_map_at(bnmf_handle* h, int end_iter, int n_samples, double ci, double* 
   if (int rc = check_recorded(h, "bnmf_map_at")) return rc;
   if (int rc = check_kept(h, "bnmf_map_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
   return map_impl(h, end_iter, n_samples, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
+}
+
+// WAIC over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller): k_waic
+// (waic.h) leaves the per-column sums; the totals are their sequential sums over g, as map_impl sums colsse.
+static int waic_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  std::vector<int> slots;
+  for (int s = 0; s < n_samples; ++s) {
+    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
+    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
+  }
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the log-likelihood needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
+    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  const size_t KG = (size_t)K * G, ncol = (size_t)WA_NCOL * G;
+  const size_t words = ncol + (cell ? 2 * KG : 0) + ((size_t)S + 1) / 2 + 8;
+  if (words > h->waic_words) { HIPCHK(hfree(h, h->dWaic)); HIPCHK(hmalloc(h, &h->dWaic, words * sizeof(double))); h->waic_words = words; }
+  double* dcol = h->dWaic; double* dcell = cell ? dcol + ncol : nullptr; int* dslots = (int*)(dcol + ncol + (cell ? 2 * KG : 0));
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  WaicArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr;
+  a.M = h->dM; a.Mf = h->dMf; a.lgfact = h->dLut; a.slots = dslots; a.col = dcol; a.cell = dcell;
+  a.lenP = (size_t)K * N; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.S = S; a.maxM = h->maxM;
+  size_t lds = waic_lds_bytes(N);
+  a.stage = lds <= 160 * 1024 ? 1 : 0;
+  if (!a.stage) lds = 0;
+  const void* kern = normal ? (const void*)k_waic<true> : (const void*)k_waic<false>;
+  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  const dim3 grid((unsigned)((G + WA_GC - 1) / WA_GC)), block(WA_T);
+  if (normal) hipLaunchKernelGGL(k_waic<true>, grid, block, lds, h->stream, a);
+  else hipLaunchKernelGGL(k_waic<false>, grid, block, lds, h->stream, a);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hc(ncol);
+  HIPCHK(hipMemcpyAsync(hc.data(), dcol, ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (cell) HIPCHK(hipMemcpyAsync(cell, dcell, 2 * KG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  double t[WA_NCOL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < WA_NCOL; ++q) for (int g = 0; g < G; ++g) t[q] += hc[(size_t)q * G + g];
+  if (col) for (int q = 0; q < 3; ++q) std::memcpy(col + (size_t)q * G, hc.data() + (size_t)q * G, (size_t)G * sizeof(double));
+  const double n = (double)K * (double)G;
+  double var = n > 1.0 ? (t[4] - t[3] * (t[3] / n)) / (n - 1.0) : 0.0;   // variance of elpd over the cells from its two sums
+  if (!(var > 0.0)) var = 0.0;
+  info->n_used = S; info->n_high_var = (int32_t)t[5];
+  info->lppd = t[0]; info->p_waic = t[1]; info->mean_loglik = t[2]; info->elpd_waic = t[3]; info->waic = -2.0 * t[3];
+  info->se_elpd = std::sqrt(n * var);
+  return 0;
+}
+int bnmf_waic(bnmf_handle* h, int last_n, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_waic: null argument");
+  if (int rc = check_recorded(h, "bnmf_waic")) return rc;
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_waic: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return waic_impl(h, "bnmf_waic", h->iter, last_n, used, col, cell, info);
+}
+int bnmf_waic_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_waic_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_waic_at")) return rc;
+  if (int rc = check_kept(h, "bnmf_waic_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return waic_impl(h, "bnmf_waic_at", end_iter, n_samples, used, col, cell, info);
 }
 
 // One MAP check (R/bayesNMF_sampler.R:297-321): get_MAP_ over the last min(MAP_over, iter) samples on the device, the

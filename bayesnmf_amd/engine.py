@@ -69,6 +69,11 @@ class BnmfStateDesc(C.Structure):
                 ("n_records", C.c_int32), ("_pad", C.c_int32), ("bytes", C.c_int64)]
 
 
+class BnmfWaicInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_high_var", C.c_int32), ("lppd", C.c_double), ("p_waic", C.c_double),
+                ("elpd_waic", C.c_double), ("waic", C.c_double), ("se_elpd", C.c_double), ("mean_loglik", C.c_double)]
+
+
 NMAPROW = 17
 CC_METRICS = ["loglikelihood", "logposterior", "RMSE", "KL", "BIC"]
 WHY = {0: None, 1: "no change", 2: "no best", 3: "max iters"}
@@ -78,7 +83,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_assign_at", "bnmf_label_switching", "bnmf_get_iter", "bnmf_profile",
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
-               "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed"]
+               "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
+               "bnmf_waic", "bnmf_waic_at"]
 
 
 def lib():
@@ -127,6 +133,8 @@ def lib():
         L.bnmf_state_info.argtypes = [C.c_char_p, C.POINTER(BnmfStateDesc)]
         L.bnmf_set_fixed.argtypes = [C.c_void_p, C.c_int, ip, C.c_size_t]
         L.bnmf_get_fixed.argtypes = [C.c_void_p, C.c_int, ip, C.c_size_t]
+        L.bnmf_waic.argtypes = [C.c_void_p, C.c_int, ip, dp, dp, C.POINTER(BnmfWaicInfo)]
+        L.bnmf_waic_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, C.POINTER(BnmfWaicInfo)]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -395,6 +403,27 @@ class Engine:
                     P_lower=f(Pl, (K, N)), P_upper=f(Pu, (K, N)), E_lower=f(El, (N, G)), E_upper=f(Eu, (N, G)),
                     top_A=top.reshape(5, N)[:npat], top_counts=[int(c) for c in info.top_counts][:npat],
                     n_used=info.n_used, n_patterns=info.n_patterns, rmse=info.rmse, kl=info.kl)
+
+    def waic(self, last_n, used=None, end_iter=None, pointwise=False):
+        """WAIC over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`, or with
+        end_iter of the `last_n` that end at iteration end_iter (bnmf_waic / bnmf_waic_at), on the device.  Returns the info fields;
+        with pointwise also lppd_col, p_waic_col, mean_loglik_col (G) and lppd_cell, p_waic_cell (K x G)."""
+        K, G = self.K, self.G
+        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
+        if u is not None and u.size != last_n:
+            raise BnmfError(-2, f"waic: used has {u.size} entries for {last_n} samples")
+        col = np.empty(3 * G) if pointwise else None
+        cell = np.empty(2 * K * G) if pointwise else None
+        info = BnmfWaicInfo()
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_waic if end_iter is None else lib().bnmf_waic_at)(
+            self._h, *rng, None if u is None else u.ctypes.data_as(C.POINTER(C.c_int32)), None if col is None else _dp(col),
+            None if cell is None else _dp(cell), C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in BnmfWaicInfo._fields_}
+        if pointwise:
+            out.update(lppd_col=col[:G], p_waic_col=col[G:2 * G], mean_loglik_col=col[2 * G:],
+                       lppd_cell=cell[:K * G].reshape((K, G), order="F"), p_waic_cell=cell[K * G:].reshape((K, G), order="F"))
+        return out
 
     def label_switching(self, iters, reference_P):
         """plot_label_switching's per-sample hungarian_assignment diagonal over the recorded iterations `iters`, on the device

@@ -622,6 +622,48 @@ class bayesNMF_sampler:
         self.reference_comparison.update(reference_P=ref, idxs=idx, keep_sigs=keep_sigs, assignments=assignments, votes=votes)
         return dict(assignments=assignments, votes=votes)
 
+    def get_WAIC(self, end_iter=None, n_samples=None, idx="MAP_idx", pointwise=False):
+        """The Watanabe-Akaike criterion over recorded samples, on the device (bnmf_waic_at): over iterations end_iter - n_samples + 1
+        ... end_iter (defaults as get_MAP: the last MAP_over samples), restricted to `idx` — "MAP_idx": those whose A equals the mode
+        of the range, so that the samples are all of one rank; None: every sample of the range; else a vector of recorded iterations.
+        Returns dict(n_used, n_high_var, lppd, p_waic, elpd_waic, waic, se_elpd, mean_loglik); with pointwise also the per-column
+        and per-cell arrays (Engine.waic)."""
+        if not hasattr(self._chain, "waic"):
+            raise ValueError("get_WAIC needs an engine that computes WAIC over its recorded samples (waic); this engine_factory's cannot")
+        cc = self.specs["convergence_control"]
+        it = self.state["iter"]
+        default = end_iter is None and n_samples is None
+        end_iter = it if end_iter is None else int(end_iter)
+        n = min(cc["MAP_over"], it) if n_samples is None else int(n_samples)
+        first_iter = end_iter - n + 1
+        lo, hi = self._kept_range()
+        if n < 1 or first_iter < lo or end_iter > hi:
+            raise ValueError(f"iterations {first_iter}..{end_iter} are not all recorded: the kept samples are iterations {lo}..{hi}")
+        if idx is None:
+            used = None
+        elif isinstance(idx, str):
+            if idx != "MAP_idx":
+                raise ValueError("Parameter `idx` must be 'MAP_idx', None or a vector of recorded iterations")
+            if default and "idx" in self.MAP:
+                ia = np.asarray(self.MAP["idx"], dtype=int)
+                ia = ia[(ia >= first_iter) & (ia <= end_iter)]
+                used = np.zeros(n, dtype=np.int32)
+                used[ia - first_iter] = 1
+            elif hasattr(self._chain, "map"):
+                used = np.asarray(self._chain.map(n, None, end_iter=end_iter)["used"], dtype=np.int32)
+            else:
+                mode = get_mode(self._chain.window("A", it - first_iter + 1)[:n])
+                used = np.zeros(n, dtype=np.int32)
+                used[mode["idx"]] = 1
+        else:
+            ia = np.asarray(idx, dtype=int).ravel()
+            if ia.size and (ia.min() < first_iter or ia.max() > end_iter):
+                raise ValueError(f"idx must lie in the iterations {first_iter}..{end_iter}")
+            used = np.zeros(n, dtype=np.int32)
+            used[ia - first_iter] = 1
+        kw = {} if end_iter == it else dict(end_iter=end_iter)
+        return self._chain.waic(n, used=used, pointwise=pointwise, **kw)
+
     def label_switching(self, reference_P, reference_names=None, idx="all"):
         """The data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below: for every
         recorded iteration in `idx` ("all": every kept sample) the diagonal of hungarian_assignment(P_t, reference_P,
@@ -730,7 +772,9 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
              intermediate_credible_intervals=False, n_chains=1, devices=None, engine_side_convergence=True, save_engine_state=False,
              fixed_P=None):
     """bayesNMF() (R/bayesNMF.R:24-138): build the sampler and run it; with rank_method = "BIC" run one
-    fixed-rank sampler per rank and return dict(results, best_rank, sampler).
+    fixed-rank sampler per rank and return dict(results, best_rank, sampler).  rank_method = "WAIC" (not in the reference) runs the
+    same per-rank sweep, adds elpd_waic, se_elpd, p_waic and n_high_var (get_WAIC over each sampler's final MAP window) to the
+    results beside BIC, and picks the largest elpd_waic.
 
     New optional trailing arguments: seed, chain_id, device, save_Z, and n_chains / devices:
     n_chains > 1 runs independent replicas (chain_id = 0..n_chains-1 in the Philox key), chain c on
@@ -758,11 +802,12 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
                   engine_factory=engine_factory, intermediate_credible_intervals=intermediate_credible_intervals,
                   engine_side_convergence=engine_side_convergence, save_engine_state=save_engine_state, fixed_P=fixed_P)
     ranks = np.atleast_1d(np.asarray(rank, dtype=int))
-    if ranks.size > 1 and rank_method == "BIC":
+    if ranks.size > 1 and rank_method in ("BIC", "WAIC"):
+        waic = rank_method == "WAIC"
         if fixed_P is not None:
             F = np.asarray(fixed_P).shape[1] if np.ndim(fixed_P) > 1 else 1
             if (ranks < F).any():
-                print(f"fixed_P has {F} columns: dropping ranks {[int(k) for k in ranks[ranks < F]]} (below {F}) from the BIC sweep")
+                print(f"fixed_P has {F} columns: dropping ranks {[int(k) for k in ranks[ranks < F]]} (below {F}) from the {rank_method} sweep")
                 ranks = ranks[ranks >= F]
             if ranks.size == 0:
                 raise ValueError(f"ERROR: fixed_P has {F} columns, but the top of the rank range is below {F}")
@@ -781,17 +826,27 @@ def bayesNMF(data, rank, likelihood="poisson", prior="truncnormal", rank_method=
         def one(i_k):
             i, k = i_k
             s = bayesNMF_sampler(data, int(k), output_dir=os.path.join(output_dir, f"rank_{k}"), device=devices[i % len(devices)], **common)
+            if waic and not hasattr(s._chain, "waic"):
+                s.close()
+                raise ValueError("rank_method = 'WAIC' needs an engine that computes WAIC over its recorded samples (waic); this engine_factory's cannot")
             s.run_gibbs_sampler()
             bic = float(s.state["MAP_metrics"].iloc[-1]["BIC"])
-            return dict(rank=int(k), dir=s.specs["output_dir"], BIC=bic, time=s.time["total"], sampler=s)
+            row = dict(rank=int(k), dir=s.specs["output_dir"], BIC=bic, time=s.time["total"], sampler=s)
+            if waic:                                     # over the final MAP window, the samples whose A is its mode (MAP$idx)
+                w = s.get_WAIC()
+                row.update({c: w[c] for c in ("elpd_waic", "se_elpd", "p_waic", "n_high_var")})
+            return row
 
         with cf.ThreadPoolExecutor(max_workers=max(1, min(len(ranks), 4 * len(devices)))) as ex:
             results = list(ex.map(one, enumerate(ranks)))
+        table = pd.DataFrame([{k: v for k, v in r.items() if k != "sampler"} for r in results])
+        if waic:                                         # the largest expected log pointwise predictive density
+            best = max(results, key=lambda r: r["elpd_waic"])
+            return dict(results=table.sort_values("elpd_waic", ascending=False), best_rank=best["rank"], sampler=best["sampler"])
         best = min(results, key=lambda r: r["BIC"])
-        return dict(results=pd.DataFrame([{k: v for k, v in r.items() if k != "sampler"} for r in results]).sort_values("BIC"),
-                    best_rank=best["rank"], sampler=best["sampler"])
+        return dict(results=table.sort_values("BIC"), best_rank=best["rank"], sampler=best["sampler"])
     if ranks.size > 1 and rank_method not in ("SBFI", "BFI"):
-        raise ValueError("Rank method must be SBFI, BFI, or BIC")
+        raise ValueError("Rank method must be SBFI, BFI, BIC, or WAIC")
     sampler = bayesNMF_sampler(data, rank, output_dir=output_dir, **common)
     sampler.run_gibbs_sampler()
     return sampler

@@ -207,6 +207,23 @@ int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, cons
                          int32_t* assigned /* [n_iters][N], 0-based column or -1 */, double* cosine /* [n_iters][N] */,
                          int32_t* included /* [n_iters][N], may be NULL */);
 
+/* WAIC of a recorded range, on the device: over the recorded samples flagged in used[] (oldest first; NULL = all; they
+ * should share one rank, e.g. bnmf_map's used[]) every cell (k, g) of the data gets the log-likelihood l_s of each sample's fit
+ * P_s diag(A_s) E_s (the Poisson cell term of the loglikelihood metric with the 1e-6 clip, or dnorm(m, c, sqrt(sigmasq_s[g]), log = TRUE)),
+ * lppd_kg = log mean_s exp(l_s) and p_kg = var_s(l_s) (n - 1 form).  col [3][G]: the sums over k of lppd, p and mean_s(l_s) per column;
+ * cell [2][K*G] (column-major): lppd_kg, p_kg; either may be NULL.  info: the totals (elpd_waic = lppd - p_waic, waic = -2 elpd_waic,
+ * mean_loglik = the mean over the used samples of the log-likelihood), se_elpd = sqrt(K G var_cells(lppd_kg - p_kg)), n_high_var = the
+ * cells with p_kg > 0.4.  The sums are taken in a fixed order: the same call gives the same bits.  Read-only for the chain.
+ * bnmf_waic_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_waic(h, n, ...) is bnmf_waic_at(h, iter, n, ...).  Refused before any device work: null info and a used[] value other than 0 / 1
+ * (the index named) with BNMF_EINVAL, fewer than 2 used samples with BNMF_ESIZE, window = 0 or a poisoned handle with BNMF_ESTATE. */
+typedef struct { int32_t n_used, n_high_var;
+                 double lppd, p_waic, elpd_waic, waic /* -2 elpd_waic */, se_elpd, mean_loglik; } bnmf_waic_info;
+int bnmf_waic(bnmf_handle*, int last_n, const int32_t* used /* [last_n], NULL = all */,
+              double* col /* [3][G]: lppd, p_waic, mean_loglik per column; may be NULL */,
+              double* cell /* [2][K*G] column-major: lppd_kg, p_kg; may be NULL */, bnmf_waic_info* info);
+int bnmf_waic_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info);
+
 int bnmf_get_iter(bnmf_handle* h, int* iter);
 
 /* A chain's state in a file, and back (checkpoint / resume; the reference's save_object, saveRDS(self), R/bayesNMF_sampler.R:414-416).

@@ -138,6 +138,26 @@ bayesNMF_sampler_hip <- R6::R6Class(
       self$reference_comparison$idxs <- self$MAP$idx
       invisible(self$reference_comparison)
     },
+    # The Watanabe-Akaike criterion over recorded samples, on the device (bnmf_waic_at; not in the reference): iterations
+    # end_iter - n_samples + 1 ... end_iter (defaults as get_MAP: the last MAP_over samples), restricted to idx — "MAP_idx": MAP$idx,
+    # the samples whose A is the mode, all of one rank; NULL: every sample of the range; else a vector of recorded iterations.
+    # list(n_used, n_high_var, lppd, p_waic, elpd_waic, waic, se_elpd, mean_loglik), with pointwise also col (G x 3: lppd, p_waic,
+    # mean_loglik per column), lppd_cell and p_waic_cell (K x G)
+    get_WAIC = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                        idx = "MAP_idx", pointwise = FALSE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      .Call("C_bnmf_waic", self$handle, as.integer(end_iter), as.integer(n_samples), used, as.logical(pointwise), as.logical(pointwise),
+            c(self$dims$K, self$dims$G, self$dims$N))
+    },
     # the data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below, on the device
     # (bnmf_label_switching): per recorded iteration in idx ("all": every kept sample) and latent factor, the reference signature
     # hungarian_assignment(keep_all_est = TRUE) gives it ("None": no partner), that cosine, and whether A includes the factor
@@ -324,4 +344,33 @@ load_bayesNMF_hip <- function(output_dir, device = 0L) {
   sampler <- readRDS(file.path(output_dir, "sampler.rds"))
   sampler$.__enclos_env__$private$reopen(output_dir, device)
   sampler
+}
+
+# bayesNMF(rank = <range>, rank_method = "WAIC") on the HIP engine (not in the reference, whose fixed-rank criterion is "BIC",
+# R/bayesNMF.R:66-126): the same per-rank sweep — one fixed-rank sampler per rank, the ranks below ncol(fixed_P) dropped — with
+# get_WAIC() over each sampler's final MAP window.  The table carries elpd_waic, se_elpd, p_waic, n_high_var and BIC for comparison;
+# best_rank is the largest elpd_waic.  rank_method = "BIC" gives the reference's choice from the same sweep.
+bayesNMF_hip_ranks <- function(data, rank, rank_method = "WAIC", output_dir = "nmf_hip", fixed_P = NULL, ...) {
+  if (!rank_method %in% c("BIC", "WAIC")) stop("Rank method must be BIC or WAIC for a per-rank sweep")
+  if (!is.null(fixed_P)) {
+    nf <- ncol(as.matrix(fixed_P))
+    if (any(rank < nf)) message(glue::glue("fixed_P has {nf} columns: dropping ranks below {nf} from the {rank_method} sweep"))
+    rank <- rank[rank >= nf]
+    if (length(rank) == 0) stop(glue::glue("ERROR: fixed_P has {nf} columns, but the top of the rank range is below {nf}"))
+  }
+  samplers <- list(); rows <- list()
+  for (k in rank) {
+    s <- bayesNMF_sampler_hip$new(data = data, rank = k, output_dir = file.path(output_dir, paste0("rank_", k)), fixed_P = fixed_P, ...)
+    s$run_gibbs_sampler()
+    row <- data.frame(rank = k, dir = s$specs$output_dir, BIC = utils::tail(s$state$MAP_metrics$BIC, 1), time = as.numeric(s$time$total))
+    if (rank_method == "WAIC") {
+      w <- s$get_WAIC()
+      row <- cbind(row, data.frame(elpd_waic = w$elpd_waic, se_elpd = w$se_elpd, p_waic = w$p_waic, n_high_var = w$n_high_var))
+    }
+    samplers[[as.character(k)]] <- s; rows[[length(rows) + 1]] <- row
+  }
+  results <- do.call(rbind, rows)
+  best <- if (rank_method == "WAIC") results$rank[which.max(results$elpd_waic)] else results$rank[which.min(results$BIC)]
+  results <- if (rank_method == "WAIC") results[order(-results$elpd_waic), ] else results[order(results$BIC), ]
+  list(results = results, best_rank = best, sampler = samplers[[as.character(best)]])
 }

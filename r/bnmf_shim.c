@@ -278,6 +278,60 @@ SEXP C_bnmf_assign_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP r
   UNPROTECT(1);
   return out;
 }
+/* WAIC over recorded samples on the device (bnmf_waic / bnmf_waic_at): C_bnmf_waic(ptr, end_iter (integer, or NULL = the current
+ * iteration), n_samples, used (logical length n_samples, or NULL = all), want_col, want_cell (logical), dims c(K,G,N)) ->
+ * list(n_used, n_high_var, lppd, p_waic, elpd_waic, waic, se_elpd, mean_loglik, col (G x 3: lppd, p_waic, mean_loglik per column, or
+ * NULL), lppd_cell, p_waic_cell (K x G each, or NULL)) over iterations end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_waic_at: the same with end_iter required */
+/* the result list with col allocated if wanted, and the flags of used; returned unprotected */
+static SEXP waic_alloc(SEXP n_samples, SEXP used, SEXP want_col, SEXP dims, int32_t** u) {
+  const int n = INTEGER(n_samples)[0], G = INTEGER(dims)[1];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  *u = lgl_flags(used, n);
+  static const char* nms[] = {"n_used", "n_high_var", "lppd", "p_waic", "elpd_waic", "waic", "se_elpd", "mean_loglik", "col", "lppd_cell", "p_waic_cell"};
+  SEXP out = PROTECT(named_list(11, nms));
+  if (LOGICAL(want_col)[0] == TRUE) SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, G, 3));
+  UNPROTECT(1);
+  return out;
+}
+static double* waic_cell_buf(SEXP want_cell, SEXP dims) {
+  const int* d = INTEGER(dims);
+  return LOGICAL(want_cell)[0] == TRUE ? (double*)R_alloc(2 * (size_t)d[0] * (size_t)d[1], sizeof(double)) : NULL;
+}
+static void waic_finish(SEXP out, const double* cell, SEXP dims, const bnmf_waic_info* info) {
+  const int* d = INTEGER(dims); const int K = d[0], G = d[1];
+  if (cell) {
+    for (int i = 0; i < 2; ++i) {
+      SEXP m = Rf_allocMatrix(REALSXP, K, G);
+      SET_VECTOR_ELT(out, 9 + i, m);
+      for (R_xlen_t j = 0; j < (R_xlen_t)K * G; ++j) REAL(m)[j] = cell[(size_t)i * K * G + (size_t)j];
+    }
+  }
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_high_var));
+  const double v[6] = {info->lppd, info->p_waic, info->elpd_waic, info->waic, info->se_elpd, info->mean_loglik};
+  for (int i = 0; i < 6; ++i) SET_VECTOR_ELT(out, 2 + i, Rf_ScalarReal(v[i]));
+}
+SEXP C_bnmf_waic(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP want_col, SEXP want_cell, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(waic_alloc(n_samples, used, want_col, dims, &u));
+  double* cell = waic_cell_buf(want_cell, dims);
+  bnmf_waic_info info;
+  if (end_iter == R_NilValue) chk(bnmf_waic(get_handle(ptr), INTEGER(n_samples)[0], u, map_buf(out, 8), cell, &info));
+  else chk(bnmf_waic_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, map_buf(out, 8), cell, &info));
+  waic_finish(out, cell, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_waic_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP want_col, SEXP want_cell, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(waic_alloc(n_samples, used, want_col, dims, &u));
+  double* cell = waic_cell_buf(want_cell, dims);
+  bnmf_waic_info info;
+  chk(bnmf_waic_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, map_buf(out, 8), cell, &info));
+  waic_finish(out, cell, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* plot_label_switching's per-sample hungarian_assignment diagonal (R/postprocessing_visualizations.R:598-669):
  * C_bnmf_label_switching(ptr, iters (integer iteration numbers), reference_P (K x R), dims c(K,G,N)) ->
  * list(assigned N x n_iters (1-based column of reference_P, NA = "None"), cosine N x n_iters, included N x n_iters logical):
@@ -356,6 +410,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_save_state", (DL_FUNC)&C_bnmf_save_state, 3}, {"C_bnmf_load_state", (DL_FUNC)&C_bnmf_load_state, 2},
   {"C_bnmf_state_info", (DL_FUNC)&C_bnmf_state_info, 1},
   {"C_bnmf_set_fixed", (DL_FUNC)&C_bnmf_set_fixed, 3}, {"C_bnmf_get_fixed", (DL_FUNC)&C_bnmf_get_fixed, 3},
+  {"C_bnmf_waic", (DL_FUNC)&C_bnmf_waic, 7}, {"C_bnmf_waic_at", (DL_FUNC)&C_bnmf_waic_at, 7},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
