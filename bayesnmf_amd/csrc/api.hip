@@ -32,6 +32,7 @@
 #include "rank.h"
 #include "mh.h"
 #include "waic.h"
+#include "mixing.h"
 
 using namespace bnmf;
 
@@ -255,6 +256,7 @@ struct bnmf_handle {
   bool have_ev = false;
   double* dMap = nullptr; size_t map_words = 0;   // scratch of bnmf_map (grown on demand)
   double* dWaic = nullptr; size_t waic_words = 0; // scratch of bnmf_waic (grown on demand): column sums, cell values, slot list
+  double* dMix = nullptr; size_t mix_words = 0;   // scratch of bnmf_mixing (grown on demand): colSums(P) per sample, both outputs, slot list
   int devlock_fd = -1;                 // the device's lock file (<BNMF_LOCKDIR or /tmp>/bnmf_dev_<PCI bus id>.lock): the device gate's rule across the PROCESSES that share the device
   int devgate_fd = -1;                 // ... and its turnstile (.gate): a process that wants the device exclusively holds it while it waits, new sharers queue behind it
   bool devlock_off = false;            // BNMF_DEVLOCK=0: the caller vouches that no other process uses the device
@@ -1655,6 +1657,90 @@ int bnmf_waic_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* use
   if (int rc = check_recorded(h, "bnmf_waic_at")) return rc;
   if (int rc = check_kept(h, "bnmf_waic_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
   return waic_impl(h, "bnmf_waic_at", end_iter, n_samples, used, col, cell, info);
+}
+
+// Mixing diagnostics over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller):
+// k_map_colsum, then k_mixing (mixing.h) per side leaves the per-element rows; the summary is a sequential scan of them on
+// the host, element index ascending, P then E, over the factors that keep[] flags.
+static_assert(BNMF_NMIX == MX_NROW, "bnmf.h and mixing.h disagree on the rows of the per-element output");
+static int mixing_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out,
+                       double* E_out, bnmf_mixing_info* info) {
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  for (int s = 0; s < n_samples; ++s) {
+    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
+    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
+  }
+  if (keep) for (int n = 0; n < N; ++n) if (keep[n] != 0 && keep[n] != 1) return fail(BNMF_EINVAL, "%s: keep[%d] = %d is neither 0 nor 1", fn, n, (int)keep[n]);
+  const int S = (int)slots.size();
+  if (S < 4) return fail(BNMF_ESIZE, "%s: %d used sample%s, split R-hat needs at least 4 (a variance in each half)", fn, S, S == 1 ? "" : "s");
+  static_assert(BNMF_MIXING_MAX_SAMPLES * (sizeof(double) + sizeof(int)) <= MX_LDS, "one element's series and the slot list fit the LDS");
+  if (S > BNMF_MIXING_MAX_SAMPLES)
+    return fail(BNMF_ESIZE, "%s: %d used samples but at most %d fit the device's 160 KB of LDS per element: thin the range with used[]", fn, S, BNMF_MIXING_MAX_SAMPLES);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G;
+  const size_t words = (size_t)S * N + MX_NROW * (lenP + lenE) + ((size_t)S + 1) / 2 + 8;
+  if (words > h->mix_words) { HIPCHK(hfree(h, h->dMix)); HIPCHK(hmalloc(h, &h->dMix, words * sizeof(double))); h->mix_words = words; }
+  double* cs = h->dMix; double* oP = cs + (size_t)S * N; double* oE = oP + MX_NROW * lenP; int* dslots = (int*)(oE + MX_NROW * lenE);
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
+  const int epw = mixing_elements_per_group(S);
+  const size_t lds = mixing_lds_bytes(epw, S);
+  const double tau_min = 1.0 / std::log10((double)S);
+  if (lds > 64 * 1024) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_mixing<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MX_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)k_mixing<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MX_LDS));
+  }
+  hipLaunchKernelGGL(k_mixing<0>, dim3((unsigned)((lenP + epw - 1) / epw)), dim3(64 * epw), lds, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N,
+                     (const int*)dslots, S, (const double*)cs, tau_min, epw, oP);
+  hipLaunchKernelGGL(k_mixing<1>, dim3((unsigned)((lenE + epw - 1) / epw)), dim3(64 * epw), lds, h->stream, (const double*)h->arr[BNMF_E].ring, lenE, K, N,
+                     (const int*)dslots, S, (const double*)cs, tau_min, epw, oE);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hP, hE;                       // the summary needs the rows whether or not the caller wants them
+  if (!P_out) { hP.resize(MX_NROW * lenP); P_out = hP.data(); }
+  if (!E_out) { hE.resize(MX_NROW * lenE); E_out = hE.data(); }
+  HIPCHK(hipMemcpyAsync(P_out, oP, MX_NROW * lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(E_out, oE, MX_NROW * lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  info->n_used = S; info->n_half = S / 2;
+  const double nan = std::nan("");
+  info->min_ess_P = info->min_ess_E = info->max_rhat_P = info->max_rhat_E = nan;
+  info->min_ess_P_at = info->min_ess_E_at = info->max_rhat_P_at = info->max_rhat_E_at = -1;
+  auto scan = [&](const double* o, size_t len, bool sideE, double& mn, int64_t& mn_at, double& mx, int64_t& mx_at) {
+    for (size_t e = 0; e < len; ++e) {
+      const int n = sideE ? (int)(e % (size_t)N) : (int)(e / (size_t)K);
+      if (keep && !keep[n]) continue;
+      const double ess = o[2 * len + e], rhat = o[4 * len + e];
+      if (o[5 * len + e] == 0.0) info->n_const++;
+      if (o[6 * len + e] == 1.0) info->n_ran_out++;
+      if (ess < BNMF_MIXING_LOW_ESS) info->n_low_ess++;
+      if (rhat > BNMF_MIXING_HIGH_RHAT) info->n_high_rhat++;
+      if (!std::isnan(ess) && (mn_at < 0 || ess < mn)) { mn = ess; mn_at = (int64_t)e; }
+      if (!std::isnan(rhat) && (mx_at < 0 || rhat > mx)) { mx = rhat; mx_at = (int64_t)e; }
+    }
+  };
+  scan(P_out, lenP, false, info->min_ess_P, info->min_ess_P_at, info->max_rhat_P, info->max_rhat_P_at);
+  scan(E_out, lenE, true, info->min_ess_E, info->min_ess_E_at, info->max_rhat_E, info->max_rhat_E_at);
+  return 0;
+}
+int bnmf_mixing(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* keep, double* P_out, double* E_out, bnmf_mixing_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_mixing: null argument");
+  if (int rc = check_recorded(h, "bnmf_mixing")) return rc;
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_mixing: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return mixing_impl(h, "bnmf_mixing", h->iter, last_n, used, keep, P_out, E_out, info);
+}
+int bnmf_mixing_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out, double* E_out,
+                   bnmf_mixing_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_mixing_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_mixing_at")) return rc;
+  if (int rc = check_kept(h, "bnmf_mixing_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return mixing_impl(h, "bnmf_mixing_at", end_iter, n_samples, used, keep, P_out, E_out, info);
 }
 
 // One MAP check (R/bayesNMF_sampler.R:297-321): get_MAP_ over the last min(MAP_over, iter) samples on the device, the

@@ -74,6 +74,15 @@ class BnmfWaicInfo(C.Structure):
                 ("elpd_waic", C.c_double), ("waic", C.c_double), ("se_elpd", C.c_double), ("mean_loglik", C.c_double)]
 
 
+class BnmfMixingInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_half", C.c_int32), ("n_const", C.c_int64), ("n_ran_out", C.c_int64), ("n_low_ess", C.c_int64),
+                ("n_high_rhat", C.c_int64), ("min_ess_P_at", C.c_int64), ("min_ess_E_at", C.c_int64), ("max_rhat_P_at", C.c_int64),
+                ("max_rhat_E_at", C.c_int64), ("min_ess_P", C.c_double), ("min_ess_E", C.c_double), ("max_rhat_P", C.c_double),
+                ("max_rhat_E", C.c_double)]
+
+
+NMIX = 11
+MIX_ROWS = ["mean", "var", "ess", "mcse", "rhat", "pairs", "exit", "mean_a", "var_a", "mean_b", "var_b"]
 NMAPROW = 17
 CC_METRICS = ["loglikelihood", "logposterior", "RMSE", "KL", "BIC"]
 WHY = {0: None, 1: "no change", 2: "no best", 3: "max iters"}
@@ -84,7 +93,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
-               "bnmf_waic", "bnmf_waic_at"]
+               "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at"]
 
 
 def lib():
@@ -135,6 +144,8 @@ def lib():
         L.bnmf_get_fixed.argtypes = [C.c_void_p, C.c_int, ip, C.c_size_t]
         L.bnmf_waic.argtypes = [C.c_void_p, C.c_int, ip, dp, dp, C.POINTER(BnmfWaicInfo)]
         L.bnmf_waic_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, C.POINTER(BnmfWaicInfo)]
+        L.bnmf_mixing.argtypes = [C.c_void_p, C.c_int, ip, ip, dp, dp, C.POINTER(BnmfMixingInfo)]
+        L.bnmf_mixing_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, dp, dp, C.POINTER(BnmfMixingInfo)]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -423,6 +434,33 @@ class Engine:
         if pointwise:
             out.update(lppd_col=col[:G], p_waic_col=col[G:2 * G], mean_loglik_col=col[2 * G:],
                        lppd_cell=cell[:K * G].reshape((K, G), order="F"), p_waic_cell=cell[K * G:].reshape((K, G), order="F"))
+        return out
+
+    def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
+        """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,
+        or with end_iter of the `last_n` that end at iteration end_iter (bnmf_mixing / bnmf_mixing_at), on the device.  A lag counts used
+        samples: a used with gaps is treated as one contiguous series.  keep (length N, None = all): the factors that enter the summary.
+        Returns the info fields; with arrays also, for every name in MIX_ROWS, name_P (K x N) and name_E (N x G)."""
+        K, G, N = self.K, self.G, self.N
+        ip = C.POINTER(C.c_int32)
+        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
+        if u is not None and u.size != last_n:
+            raise BnmfError(-2, f"mixing: used has {u.size} entries for {last_n} samples")
+        kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.int32)
+        if kp is not None and kp.size != N:
+            raise BnmfError(-2, f"mixing: keep has {kp.size} entries for {N} factors")
+        oP = np.empty((NMIX, K * N)) if arrays else None
+        oE = np.empty((NMIX, N * G)) if arrays else None
+        info = BnmfMixingInfo()
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_mixing if end_iter is None else lib().bnmf_mixing_at)(
+            self._h, *rng, None if u is None else u.ctypes.data_as(ip), None if kp is None else kp.ctypes.data_as(ip),
+            None if oP is None else _dp(oP), None if oE is None else _dp(oE), C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in BnmfMixingInfo._fields_}
+        if arrays:
+            for i, name in enumerate(MIX_ROWS):
+                out[name + "_P"] = oP[i].reshape((K, N), order="F")
+                out[name + "_E"] = oE[i].reshape((N, G), order="F")
         return out
 
     def label_switching(self, iters, reference_P):

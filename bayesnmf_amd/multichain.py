@@ -9,7 +9,8 @@ differs by `chain_id`.  There is no data-path collective.  Two ways to run them:
   the ranks all-gather (i) the block's metric rows and their convergence flags and, (ii) when a chain has just made a MAP
   check, every chain's window statistics — mode of A, renormalised window means of P and E: N + K N + N G doubles per
   chain (SURVEY.md 8e ii; get_MAP_ R/utils.R:194-288) — (`ChainSync`), on GPUs over RCCL (backend "nccl"), in the CPU
-  tests over "gloo"; (iii) `gather_window` collects the chains' last recorded samples at the end.  Ranks that finish early
+  tests over "gloo"; (iii) `gather_window` collects the chains' last recorded samples at the end, `gather_mixing` the moments of
+  their split halves, from which `combine_rhat` forms the between-chain R-hat on the host.  Ranks that finish early
   keep answering the collectives until every rank is done, so their number is the same on every rank.
 """
 import os
@@ -55,6 +56,66 @@ def gather_window(sampler, dist, what=("P", "E"), last_n=None, device=None):
     for name in what:
         w = np.stack([np.asarray(x, dtype=np.float64) for x in sampler._chain.window(name, n)])
         out[name] = gather_rows(w.reshape(n, -1), dist, device).reshape((dist.get_world_size(),) + w.shape)
+    return out
+
+
+HALF_ROWS = ("mean_a", "var_a", "mean_b", "var_b")        # rows 8 to 11 of bnmf_mixing's per-element output
+
+
+def gather_mixing(sampler, dist, device=None, **kw):
+    """The halves' moments of every chain's get_mixing(**kw) on every rank, as gather_window gathers samples: one all-gather of
+    1 + 4 (K N + N G) doubles per chain.  Returns the list, by chain, of dict(n_half, mean_a_P, ..., var_b_E) that combine_rhat takes."""
+    m = sampler.get_mixing(**kw)
+    K, N, G = sampler.dims["K"], sampler.dims["N"], sampler.dims["G"]
+    v = np.concatenate([[float(m["n_half"])]] + [np.asarray(m[f"{r}_{side}"], dtype=np.float64).ravel(order="F") for side in "PE" for r in HALF_ROWS])
+    g = gather_rows(v.reshape(1, -1), dist, device)[:, 0]
+    out = []
+    for c in range(g.shape[0]):
+        d, at = dict(n_half=int(g[c, 0])), 1
+        for side, shp in (("P", (K, N)), ("E", (N, G))):
+            for r in HALF_ROWS:
+                d[f"{r}_{side}"] = g[c, at:at + shp[0] * shp[1]].reshape(shp, order="F").copy()
+                at += shp[0] * shp[1]
+        out.append(d)
+    return out
+
+
+def combine_rhat(per_chain, perm=None):
+    """Between-chain R-hat of every element of P and E from the replicas' split halves (host only, numpy): per_chain[c] is chain c's
+    Engine.mixing / get_mixing result (or gather_mixing's entry): n_half and mean_a, var_a, mean_b, var_b of each side.  The 2 C
+    half-chains of n = n_half samples give the standard statistic (Gelman et al., BDA3 11.4; Vehtari et al. 2021 without the rank
+    normalisation):  W = mean of the 2 C variances,  B / n = variance (2 C - 1 form) of the 2 C means,
+    rhat = sqrt(((n - 1) / n W + B / n) / W), NaN where W is not positive.  Chains whose n_half differ raise ValueError.
+    perm[c] (optional) is a permutation of chain c's factors that aligns its labels with the others': element j of the aligned
+    chain is factor perm[c][j].  Taken from bnmf_assign against a common catalogue of N columns (say chain 0's MAP P):
+        a = chain_c.assign(n, P_map_of_chain_0)["assigned"]     # assigned_ref: factor -> column of the catalogue
+        perm_c = np.argsort(a)                                  # where a is a permutation of 0 .. N-1
+    Returns dict(rhat_P K x N, rhat_E N x G, n_half, n_chains)."""
+    if len(per_chain) < 1:
+        raise ValueError("combine_rhat needs at least one chain")
+    nh = [int(c["n_half"]) for c in per_chain]
+    if len(set(nh)) != 1:
+        raise ValueError(f"the chains' halves differ in length (n_half = {nh}): R-hat needs equal half-chains")
+    n = float(nh[0])
+    if perm is not None and len(perm) != len(per_chain):
+        raise ValueError(f"perm has {len(perm)} entries for {len(per_chain)} chains")
+    out = dict(n_half=nh[0], n_chains=len(per_chain))
+    for side in "PE":
+        means, vars_ = [], []
+        for c, m in enumerate(per_chain):
+            for half in "ab":
+                mu, va = np.asarray(m[f"mean_{half}_{side}"], dtype=np.float64), np.asarray(m[f"var_{half}_{side}"], dtype=np.float64)
+                if perm is not None:
+                    p = np.asarray(perm[c], dtype=int)
+                    if sorted(p.tolist()) != list(range(len(p))):
+                        raise ValueError(f"perm[{c}] is not a permutation of the factors")
+                    mu, va = (mu[:, p], va[:, p]) if side == "P" else (mu[p, :], va[p, :])
+                means.append(mu); vars_.append(va)
+        means, vars_ = np.stack(means), np.stack(vars_)
+        W = vars_.mean(axis=0)
+        Bn = means.var(axis=0, ddof=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[f"rhat_{side}"] = np.where(W > 0, np.sqrt(((n - 1.0) / n * W + Bn) / W), np.nan)
     return out
 
 

@@ -478,6 +478,7 @@ class bayesNMF_sampler:
         else:
             self.get_MAP(final=True)
             self.log("Final MAP computed", verbosity=1)
+        self._log_mixing()
         self._sync_state()
         self.log("Sampler done", verbosity=1)
         self.time["total"] = (time.time() - start) / 60.0
@@ -630,6 +631,12 @@ class bayesNMF_sampler:
         and per-cell arrays (Engine.waic)."""
         if not hasattr(self._chain, "waic"):
             raise ValueError("get_WAIC needs an engine that computes WAIC over its recorded samples (waic); this engine_factory's cannot")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        return self._chain.waic(n, used=used, pointwise=pointwise, **kw)
+
+    def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
+        """The range and sample selection of get_WAIC / get_mixing: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]
         default = end_iter is None and n_samples is None
@@ -639,30 +646,69 @@ class bayesNMF_sampler:
         lo, hi = self._kept_range()
         if n < 1 or first_iter < lo or end_iter > hi:
             raise ValueError(f"iterations {first_iter}..{end_iter} are not all recorded: the kept samples are iterations {lo}..{hi}")
+        N = self.dims["N"]
+        mode_used = mode_A = None
+        have_map = default and "idx" in self.MAP
+        if (isinstance(idx, str) and idx == "MAP_idx" and not have_map) or (want_mode and not (default and "keep_sigs" in self.MAP)):
+            if hasattr(self._chain, "map"):
+                r = self._chain.map(n, None, end_iter=end_iter)
+                mode_used, mode_A = np.asarray(r["used"], dtype=np.int32), (np.ravel(r["A"]) != 0).astype(np.int32)
+            else:
+                mode = get_mode(self._chain.window("A", it - first_iter + 1)[:n])
+                mode_used = np.zeros(n, dtype=np.int32)
+                mode_used[mode["idx"]] = 1
+                mode_A = (np.ravel(mode["matrix"]) != 0).astype(np.int32)
+        if want_mode and mode_A is None:                   # the last MAP's: its kept factors, or those its A includes
+            A, ks = np.ravel(self.MAP["A"]), np.asarray(self.MAP["keep_sigs"], dtype=int)
+            mode_A = np.zeros(N, dtype=np.int32)
+            mode_A[ks[A != 0] if len(ks) == len(A) else ks] = 1
         if idx is None:
             used = None
         elif isinstance(idx, str):
             if idx != "MAP_idx":
                 raise ValueError("Parameter `idx` must be 'MAP_idx', None or a vector of recorded iterations")
-            if default and "idx" in self.MAP:
+            if have_map:
                 ia = np.asarray(self.MAP["idx"], dtype=int)
                 ia = ia[(ia >= first_iter) & (ia <= end_iter)]
                 used = np.zeros(n, dtype=np.int32)
                 used[ia - first_iter] = 1
-            elif hasattr(self._chain, "map"):
-                used = np.asarray(self._chain.map(n, None, end_iter=end_iter)["used"], dtype=np.int32)
             else:
-                mode = get_mode(self._chain.window("A", it - first_iter + 1)[:n])
-                used = np.zeros(n, dtype=np.int32)
-                used[mode["idx"]] = 1
+                used = mode_used
         else:
             ia = np.asarray(idx, dtype=int).ravel()
             if ia.size and (ia.min() < first_iter or ia.max() > end_iter):
                 raise ValueError(f"idx must lie in the iterations {first_iter}..{end_iter}")
             used = np.zeros(n, dtype=np.int32)
             used[ia - first_iter] = 1
-        kw = {} if end_iter == it else dict(end_iter=end_iter)
-        return self._chain.waic(n, used=used, pointwise=pointwise, **kw)
+        return n, used, mode_A, ({} if end_iter == it else dict(end_iter=end_iter))
+
+    def get_mixing(self, end_iter=None, n_samples=None, idx="MAP_idx", arrays=True):
+        """Mixing diagnostics of the recorded samples, on the device (bnmf_mixing_at; not in the reference): for every element of the
+        renormalised P and E over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last MAP_over samples),
+        restricted to `idx` ("MAP_idx": those whose A equals the mode of the range; None: every sample; else a vector of recorded
+        iterations) — the mean and variance, Geyer's effective sample size, the Monte-Carlo standard error of the mean, split R-hat and
+        the halves' moments (Engine.mixing: name_P is K x N, name_E is N x G, over all N factors), with a summary over the factors of
+        the mode of A: n_const, n_ran_out, n_low_ess (< 100), n_high_rhat (> 1.01), the smallest ESS and largest R-hat of each side.
+        Caveat: a lag counts USED samples, not iterations.  Where `idx` leaves gaps in the range (samples whose A is not the mode),
+        the samples that remain are treated as one contiguous series, as get_MAP's idx is; autocorrelations across a gap are then
+        those of the thinned series."""
+        if not hasattr(self._chain, "mixing"):
+            raise ValueError("get_mixing needs an engine that computes mixing diagnostics over its recorded samples (mixing); this engine_factory's cannot")
+        n, used, keep, kw = self._recorded_range(end_iter, n_samples, idx, want_mode=True)
+        return self._chain.mixing(n, used=used, keep=keep, arrays=arrays, **kw)
+
+    def _log_mixing(self):
+        """one line after the final MAP: how many independent draws the summaries rest on"""
+        if not hasattr(self._chain, "mixing"):
+            return
+        try:
+            m = self.get_mixing(arrays=False)
+        except Exception as ex:  # noqa: BLE001  (e.g. fewer than 4 samples share the mode of A)
+            self.log(f"Mixing not computed: {ex}", verbosity=1)
+            return
+        self.log(f"Mixing over {m['n_used']} samples: min ESS P {m['min_ess_P']:.1f} E {m['min_ess_E']:.1f} | max split R-hat P {m['max_rhat_P']:.4f} "
+                 f"E {m['max_rhat_E']:.4f} | {m['n_low_ess']} ESS < 100 | {m['n_high_rhat']} R-hat > 1.01 | {m['n_const']} constant | "
+                 f"{m['n_ran_out']} ran out of lags", verbosity=1)
 
     def label_switching(self, reference_P, reference_names=None, idx="all"):
         """The data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below: for every

@@ -224,6 +224,37 @@ int bnmf_waic(bnmf_handle*, int last_n, const int32_t* used /* [last_n], NULL = 
               double* cell /* [2][K*G] column-major: lppd_kg, p_kg; may be NULL */, bnmf_waic_info* info);
 int bnmf_waic_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info);
 
+/* Mixing diagnostics of a recorded range, on the device: for every element of the renormalised P (K x N: P / colSums(P))
+ * and E (N x G: E * colSums(P)), over the recorded samples flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1.  A lag
+ * counts used samples, not iterations: a used[] with gaps is treated as one contiguous series, as get_MAP_'s idx is.
+ * P_out [BNMF_NMIX][K*N], E_out [BNMF_NMIX][N*G] (each row column-major as P and E; either may be NULL), the rows:
+ *   0 mean   1 var (S - 1 form)   2 ess (Geyer's initial monotone sequence over the autocorrelations; tau floored at 1 / log10(S))
+ *   3 mcse = sqrt(var / ess)   4 rhat (split R-hat: halves of S / 2 samples, an odd middle sample dropped)
+ *   5 pairs (the Gammas summed; 0 for a series without variance)   6 exit (0: a Gamma was not positive; 1: the lags ran out)
+ *   7 mean_a   8 var_a   9 mean_b   10 var_b (the halves' moments, from which a between-chain R-hat is combined on the host)
+ * An element whose series is constant (every sample equal to the first: a fixed_P column, an MH element that never moved), has no
+ * variance or holds a NaN gets ess = mcse = rhat = NaN, pairs = exit = 0 (its mean and var are still the formulas': rounding noise).  info: a sequential scan, element index ascending, P then E, over the elements of the factors with keep[n] != 0
+ * (NULL = all): the counts, and the smallest ess / largest rhat of each side with the element index (column-major position in P / E;
+ * the first index wins a tie, NaN entries are skipped, -1 and NaN if there is none).  The sums are taken in a fixed order: the same
+ * call gives the same bits.  Read-only for the chain.
+ * bnmf_mixing_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_mixing(h, n, ...) is bnmf_mixing_at(h, iter, n, ...).  Refused before any device work: null info and a used[] / keep[] value other
+ * than 0 / 1 (the index named) with BNMF_EINVAL; fewer than 4 used samples (each half needs a variance) and more than
+ * BNMF_MIXING_MAX_SAMPLES (one element's series must fit the 160 KB of LDS; never truncated) with BNMF_ESIZE; window = 0 or a poisoned
+ * handle with BNMF_ESTATE. */
+#define BNMF_NMIX 11
+#define BNMF_MIXING_MAX_SAMPLES 13653     /* 160 KB / (8 B of the series + 4 B of the slot list) per sample */
+#define BNMF_MIXING_LOW_ESS 100.0         /* n_low_ess counts ess < this; n_high_rhat counts rhat > the next: the published conventions */
+#define BNMF_MIXING_HIGH_RHAT 1.01        /* (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) */
+typedef struct { int32_t n_used, n_half;
+                 int64_t n_const, n_ran_out /* exit == 1 */, n_low_ess, n_high_rhat;
+                 int64_t min_ess_P_at, min_ess_E_at, max_rhat_P_at, max_rhat_E_at;
+                 double min_ess_P, min_ess_E, max_rhat_P, max_rhat_E; } bnmf_mixing_info;
+int bnmf_mixing(bnmf_handle*, int last_n, const int32_t* used /* [last_n], NULL = all */, const int32_t* keep /* [N], NULL = all */,
+                double* P_out /* [BNMF_NMIX][K*N], may be NULL */, double* E_out /* [BNMF_NMIX][N*G], may be NULL */, bnmf_mixing_info* info);
+int bnmf_mixing_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out, double* E_out,
+                   bnmf_mixing_info* info);
+
 int bnmf_get_iter(bnmf_handle* h, int* iter);
 
 /* A chain's state in a file, and back (checkpoint / resume; the reference's save_object, saveRDS(self), R/bayesNMF_sampler.R:414-416).

@@ -158,6 +158,32 @@ bayesNMF_sampler_hip <- R6::R6Class(
       .Call("C_bnmf_waic", self$handle, as.integer(end_iter), as.integer(n_samples), used, as.logical(pointwise), as.logical(pointwise),
             c(self$dims$K, self$dims$G, self$dims$N))
     },
+    # Mixing diagnostics of the recorded samples, on the device (bnmf_mixing_at; not in the reference): for every element of the
+    # renormalised P and E over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, the mean,
+    # variance, Geyer's effective sample size, Monte-Carlo standard error, split R-hat and the halves' moments: P (K N x 11) and
+    # E (N G x 11), columns mean, var, ess, mcse, rhat, pairs, exit, mean_a, var_a, mean_b, var_b; and the summary over the factors of
+    # MAP$keep_sigs (counts, smallest ESS and largest R-hat of each side with their 1-based positions, 0 = none).  A lag counts USED samples:
+    # where idx leaves gaps in the range the remaining samples are treated as one contiguous series, as get_MAP's idx is.
+    get_mixing = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                          idx = "MAP_idx", arrays = TRUE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      keep <- NULL
+      if (!is.null(self$MAP$keep_sigs)) { keep <- rep(FALSE, self$dims$N); keep[self$MAP$keep_sigs] <- TRUE }
+      r <- .Call("C_bnmf_mixing", self$handle, as.integer(end_iter), as.integer(n_samples), used, keep, as.logical(arrays),
+                 c(self$dims$K, self$dims$G, self$dims$N))
+      cols <- c("mean", "var", "ess", "mcse", "rhat", "pairs", "exit", "mean_a", "var_a", "mean_b", "var_b")
+      if (!is.null(r$P)) { colnames(r$P) <- cols; colnames(r$E) <- cols }
+      r
+    },
     # the data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below, on the device
     # (bnmf_label_switching): per recorded iteration in idx ("all": every kept sample) and latent factor, the reference signature
     # hungarian_assignment(keep_all_est = TRUE) gives it ("None": no partner), that cosine, and whether A includes the factor

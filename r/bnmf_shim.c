@@ -332,6 +332,56 @@ SEXP C_bnmf_waic_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP wan
   UNPROTECT(1);
   return out;
 }
+/* Mixing diagnostics over recorded samples on the device (bnmf_mixing / bnmf_mixing_at): C_bnmf_mixing(ptr, end_iter (integer, or NULL =
+ * the current iteration), n_samples, used (logical length n_samples, or NULL = all), keep (logical length N, or NULL = all), want_arrays
+ * (logical), dims c(K,G,N)) -> list(n_used, n_half, n_const, n_ran_out, n_low_ess, n_high_rhat, min_ess_P, min_ess_E, max_rhat_P,
+ * max_rhat_E, min_ess_P_at, min_ess_E_at, max_rhat_P_at, max_rhat_E_at (1-based positions in P / E as doubles, 0 = none), P (K N x 11), E (N G x 11):
+ * one column per row of the C output — mean, var, ess, mcse, rhat, pairs, exit, mean_a, var_a, mean_b, var_b — or NULL) over iterations
+ * end_iter - n_samples + 1 ... end_iter.  C_bnmf_mixing_at: the same with end_iter required */
+/* the result list with P and E allocated if wanted, and the flags of used and keep; returned unprotected */
+static SEXP mixing_alloc(SEXP n_samples, SEXP used, SEXP keep, SEXP want_arrays, SEXP dims, int32_t** u, int32_t** kp) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (keep != R_NilValue && XLENGTH(keep) != (R_xlen_t)d[2]) Rf_error("bnmf: keep has %ld entries for %d factors", (long)XLENGTH(keep), d[2]);
+  *u = lgl_flags(used, n); *kp = lgl_flags(keep, d[2]);
+  static const char* nms[] = {"n_used", "n_half", "n_const", "n_ran_out", "n_low_ess", "n_high_rhat", "min_ess_P", "min_ess_E", "max_rhat_P", "max_rhat_E",
+                              "min_ess_P_at", "min_ess_E_at", "max_rhat_P_at", "max_rhat_E_at", "P", "E"};
+  SEXP out = PROTECT(named_list(16, nms));
+  if (LOGICAL(want_arrays)[0] == TRUE) {
+    SET_VECTOR_ELT(out, 14, Rf_allocMatrix(REALSXP, d[0] * d[2], BNMF_NMIX));
+    SET_VECTOR_ELT(out, 15, Rf_allocMatrix(REALSXP, d[2] * d[1], BNMF_NMIX));
+  }
+  UNPROTECT(1);
+  return out;
+}
+static void mixing_finish(SEXP out, const bnmf_mixing_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_half));
+  const double v[12] = {(double)info->n_const, (double)info->n_ran_out, (double)info->n_low_ess, (double)info->n_high_rhat,
+                        info->min_ess_P, info->min_ess_E, info->max_rhat_P, info->max_rhat_E,
+                        (double)info->min_ess_P_at, (double)info->min_ess_E_at, (double)info->max_rhat_P_at, (double)info->max_rhat_E_at};
+  for (int i = 0; i < 8; ++i) SET_VECTOR_ELT(out, 2 + i, Rf_ScalarReal(v[i]));
+  for (int i = 8; i < 12; ++i) SET_VECTOR_ELT(out, 2 + i, Rf_ScalarReal(v[i] + 1.0)   /* 1-based; 0 = none */);
+}
+SEXP C_bnmf_mixing(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP keep, SEXP want_arrays, SEXP dims) {
+  int32_t *u = NULL, *kp = NULL;
+  SEXP out = PROTECT(mixing_alloc(n_samples, used, keep, want_arrays, dims, &u, &kp));
+  bnmf_mixing_info info;
+  if (end_iter == R_NilValue) chk(bnmf_mixing(get_handle(ptr), INTEGER(n_samples)[0], u, kp, map_buf(out, 14), map_buf(out, 15), &info));
+  else chk(bnmf_mixing_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, kp, map_buf(out, 14), map_buf(out, 15), &info));
+  mixing_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_mixing_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP keep, SEXP want_arrays, SEXP dims) {
+  int32_t *u = NULL, *kp = NULL;
+  SEXP out = PROTECT(mixing_alloc(n_samples, used, keep, want_arrays, dims, &u, &kp));
+  bnmf_mixing_info info;
+  chk(bnmf_mixing_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, kp, map_buf(out, 14), map_buf(out, 15), &info));
+  mixing_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* plot_label_switching's per-sample hungarian_assignment diagonal (R/postprocessing_visualizations.R:598-669):
  * C_bnmf_label_switching(ptr, iters (integer iteration numbers), reference_P (K x R), dims c(K,G,N)) ->
  * list(assigned N x n_iters (1-based column of reference_P, NA = "None"), cosine N x n_iters, included N x n_iters logical):
@@ -411,6 +461,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_state_info", (DL_FUNC)&C_bnmf_state_info, 1},
   {"C_bnmf_set_fixed", (DL_FUNC)&C_bnmf_set_fixed, 3}, {"C_bnmf_get_fixed", (DL_FUNC)&C_bnmf_get_fixed, 3},
   {"C_bnmf_waic", (DL_FUNC)&C_bnmf_waic, 7}, {"C_bnmf_waic_at", (DL_FUNC)&C_bnmf_waic_at, 7},
+  {"C_bnmf_mixing", (DL_FUNC)&C_bnmf_mixing, 7}, {"C_bnmf_mixing_at", (DL_FUNC)&C_bnmf_mixing_at, 7},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
