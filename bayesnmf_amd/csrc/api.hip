@@ -32,6 +32,7 @@
 #include "rank.h"
 #include "mh.h"
 #include "waic.h"
+#include "ppc.h"
 #include "mixing.h"
 
 using namespace bnmf;
@@ -256,6 +257,7 @@ struct bnmf_handle {
   bool have_ev = false;
   double* dMap = nullptr; size_t map_words = 0;   // scratch of bnmf_map (grown on demand)
   double* dWaic = nullptr; size_t waic_words = 0; // scratch of bnmf_waic (grown on demand): column sums, cell values, slot list
+  double* dPpc = nullptr; size_t ppc_words = 0;   // scratch of bnmf_ppc (grown on demand): T[4][S][G], column rows, series, cell values, slot and iteration lists
   double* dMix = nullptr; size_t mix_words = 0;   // scratch of bnmf_mixing (grown on demand): colSums(P) per sample, both outputs, slot list
   int devlock_fd = -1;                 // the device's lock file (<BNMF_LOCKDIR or /tmp>/bnmf_dev_<PCI bus id>.lock): the device gate's rule across the PROCESSES that share the device
   int devgate_fd = -1;                 // ... and its turnstile (.gate): a process that wants the device exclusively holds it while it waits, new sharers queue behind it
@@ -1659,6 +1661,90 @@ int bnmf_waic_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* use
   return waic_impl(h, "bnmf_waic_at", end_iter, n_samples, used, col, cell, info);
 }
 
+// Posterior predictive checks over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the
+// caller): k_ppc leaves T[4][S][G], the tail cells per column and the cell values, k_ppc_totals the per-column rows and the series
+// (ppc.h); the info fields are sequential scans of the series on the host.
+static_assert(PP_NCOL == BNMF_PPC_NCOL && PP_VAR == (uint32_t)BNMF_V_YREP, "ppc.h and bnmf.h disagree");
+static int ppc_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series,
+                    bnmf_ppc_info* info) {
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  std::vector<int> sl;                              // slots, then iterations
+  for (int s = 0; s < n_samples; ++s) {
+    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
+    if (!used || used[s]) sl.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
+  }
+  const int S = (int)sl.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the replicates needs at least 2", fn, S, S == 1 ? "" : "s");
+  for (int s = 0; s < n_samples; ++s) if (!used || used[s]) sl.push_back(end_iter - n_samples + 1 + s);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
+    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  const size_t KG = (size_t)K * G, SG = (size_t)S * G, ncol = (size_t)(PP_NCOL + 1) * G;
+  const size_t words = 4 * SG + ncol + 4 * (size_t)S + (cell ? 4 * KG : 0) + (size_t)S + 8;
+  if (words > h->ppc_words) {
+    HIPCHK(hfree(h, h->dPpc)); h->dPpc = nullptr; h->ppc_words = 0;
+    HIPCHK(hmalloc(h, &h->dPpc, words * sizeof(double))); h->ppc_words = words;
+  }
+  double* dT = h->dPpc; double* dcol = dT + 4 * SG; double* dser = dcol + ncol; double* dcell = cell ? dser + 4 * (size_t)S : nullptr;
+  int* dsl = (int*)(dser + 4 * (size_t)S + (cell ? 4 * KG : 0));
+  HIPCHK(hipMemcpyAsync(dsl, sl.data(), 2 * (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  PpcArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr;
+  a.M = h->dM; a.Mf = h->dMf; a.slots = dsl; a.iters = dsl + S; a.T = dT; a.tail = dcol + (size_t)PP_NCOL * G; a.cell = dcell;
+  a.lenP = (size_t)K * N; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.S = S;
+  a.k0 = (uint32_t)h->cfg.seed; a.k1 = (uint32_t)(h->cfg.seed >> 32) ^ h->cfg.chain_id;
+  size_t lds = ppc_lds_bytes(N);
+  a.stage = lds <= 160 * 1024 ? 1 : 0;
+  if (!a.stage) lds = 0;
+  const void* kern = normal ? (const void*)k_ppc<true> : (const void*)k_ppc<false>;
+  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  const dim3 grid((unsigned)((G + PP_GC - 1) / PP_GC)), block(PP_T);
+  const dim3 tgrid((unsigned)(4 * S + (G + PP_TT - 1) / PP_TT)), tblock(PP_TT);
+  if (normal) {
+    hipLaunchKernelGGL(k_ppc<true>, grid, block, lds, h->stream, a);
+    hipLaunchKernelGGL(k_ppc_totals<true>, tgrid, tblock, 0, h->stream, (const double*)dT, S, G, dser, dcol);
+  } else {
+    hipLaunchKernelGGL(k_ppc<false>, grid, block, lds, h->stream, a);
+    hipLaunchKernelGGL(k_ppc_totals<false>, tgrid, tblock, 0, h->stream, (const double*)dT, S, G, dser, dcol);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<double> hs(4 * (size_t)S), ht((size_t)G);
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, 4 * (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(ht.data(), dcol + (size_t)PP_NCOL * G, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (col) HIPCHK(hipMemcpyAsync(col, dcol, (size_t)PP_NCOL * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (cell) HIPCHK(hipMemcpyAsync(cell, dcell, 4 * KG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), 4 * (size_t)S * sizeof(double));
+  double t[4] = {0.0, 0.0, 0.0, 0.0}; int n1 = 0, n2 = 0;
+  for (int s = 0; s < S; ++s) {
+    for (int q = 0; q < 4; ++q) t[q] += hs[(size_t)q * S + s];
+    n1 += hs[(size_t)S + s] >= hs[s] ? 1 : 0; n2 += hs[3 * (size_t)S + s] >= hs[2 * (size_t)S + s] ? 1 : 0;
+  }
+  int64_t nt = 0;
+  for (int g = 0; g < G; ++g) nt += (int64_t)ht[g];
+  info->n_used = S; info->n_tail_cells = nt;
+  info->p_T1 = (double)n1 / (double)S; info->p_T2 = (double)n2 / (double)S;
+  info->mean_T1_obs = t[0] / (double)S; info->mean_T1_rep = t[1] / (double)S; info->mean_T2_obs = t[2] / (double)S; info->mean_T2_rep = t[3] / (double)S;
+  return 0;
+}
+int bnmf_ppc(bnmf_handle* h, int last_n, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_ppc: null argument");
+  if (int rc = check_recorded(h, "bnmf_ppc")) return rc;
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_ppc: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return ppc_impl(h, "bnmf_ppc", h->iter, last_n, used, col, cell, series, info);
+}
+int bnmf_ppc_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_ppc_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_ppc_at")) return rc;
+  if (int rc = check_kept(h, "bnmf_ppc_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return ppc_impl(h, "bnmf_ppc_at", end_iter, n_samples, used, col, cell, series, info);
+}
+
 // Mixing diagnostics over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller):
 // k_map_colsum, then k_mixing (mixing.h) per side leaves the per-element rows; the summary is a sequential scan of them on
 // the host, element index ascending, P then E, over the factors that keep[] flags.
@@ -2102,6 +2188,18 @@ int bnmf_test_math(int device, int fn, const double* in, double* out, size_t n) 
 int bnmf_test_sampler(int device, int which, uint64_t seed, uint32_t chain, uint32_t var, uint32_t elem0, uint32_t iter,
                       const double* a, const double* b, const double* c, double* out, size_t n) {
   HIPCHK(hipSetDevice(device));
+  if (which == 8) {                                 // rpois(a): k_test_rpois
+    if (!a || !out) return fail(BNMF_EINVAL, "bnmf_test_sampler: probe 8 needs a and out");
+    double *da8, *do8;
+    HIPCHK(dmalloc(&da8, n * sizeof(double))); HIPCHK(dmalloc(&do8, n * sizeof(double)));
+    HIPCHK(hipMemcpy(da8, a, n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_test_rpois, dim3((n + 255) / 256), dim3(256), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32) ^ chain, var, elem0, iter,
+                       (const double*)da8, do8, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, do8, n * sizeof(double), hipMemcpyDeviceToHost));
+    dfree(da8); dfree(do8);
+    return 0;
+  }
   if (int rc = ensure_alut(device)) return rc;
   double *da, *db, *dc, *dou;
   HIPCHK(dmalloc(&da, n * sizeof(double))); HIPCHK(dmalloc(&db, n * sizeof(double)));

@@ -7,6 +7,8 @@
 //                  R/sample_Pn.R:14,59,79; R/sample_En.R:14,59,78)
 //   Alpha        : exact 3-tangent rejection for the log-concave ARMS target of
 //                  R/sample_priors.R:356-397
+//   Poisson      : inversion by sequential search below lambda = 10, Hoermann's transformed rejection with squeeze (PTRS, 1993)
+//                  from there (the replicates of bnmf_ppc; not a draw of the reference's sweep)
 #pragma once
 #include "dmath.h"
 
@@ -17,6 +19,44 @@ constexpr int MAX_ATTEMPTS = 2000;
 BNMF_DEV double rnorm_std(Stream& s) { const u32x4 w = s.next(); return dqnorm(u52(w.x, w.y)); }
 BNMF_DEV double runif(Stream& s) { const u32x4 w = s.next(); return u52(w.x, w.y); }
 BNMF_DEV double rexp(Stream& s, double rate) { const u32x4 w = s.next(); return -dlog(u52(w.x, w.y)) / rate; }
+
+// Poisson(lam), 1e-6 <= lam <= 2^24, as a whole number in a double.  One Philox block per attempt.
+//   lam < 10 : one attempt.  u = u52(w.x, w.y); p = dexp(-lam), F = p, x = 0; while u > F and x < RPOIS_CAP: x = x + 1,
+//              p = (p * lam) / x, F = F + p.  The cap ends the search for a uniform above the rounded sum of the masses.
+//   lam >= 10: PTRS.  Per attempt U = u52(w.x, w.y) - 0.5, V = u52(w.z, w.w), us = 0.5 - |U|,
+//              k = floor((((2 a) / us + b) U + lam) + 0.43); accept by the squeeze (us >= 0.07 and V <= vr), reject k < 0 and
+//              (us < 0.013 and V > us), else accept iff (dlog(V) + lia) - dlog(a / (us us) + b) <= (k ll - lam) - dlgamma(k + 1).
+//              MAX_ATTEMPTS rejections in a row (probability below 1e-1000) give floor(lam).
+constexpr double RPOIS_CAP = 128.0;
+BNMF_DEV double rpois(Stream& s, double lam, int* n_attempts = nullptr) {
+  if (lam < 10.0) {
+    const u32x4 w = s.next();
+    const double u = u52(w.x, w.y);
+    double p = dexp(-lam), F = p, x = 0.0;
+    while (u > F && x < RPOIS_CAP) { x = x + 1.0; p = (p * lam) / x; F = F + p; }
+    if (n_attempts) *n_attempts = 1;
+    return x;
+  }
+  const double sl = dsqrt(lam), ll = dlog(lam);
+  const double b = 0.931 + 2.53 * sl;
+  const double a = -0.059 + 0.02483 * b;
+  const double lia = dlog(1.1239 + 1.1328 / (b - 3.4));
+  const double vr = 0.9277 - 3.6224 / (b - 2.0);
+  double res = __builtin_floor(lam);
+  int it = 0;
+  for (; it < MAX_ATTEMPTS; ++it) {
+    const u32x4 w = s.next();
+    const double U = u52(w.x, w.y) - 0.5;
+    const double V = u52(w.z, w.w);
+    const double us = 0.5 - dabs(U);
+    const double k = __builtin_floor((((2.0 * a) / us + b) * U + lam) + 0.43);
+    if (us >= 0.07 && V <= vr) { res = k; break; }
+    if (k < 0.0 || (us < 0.013 && V > us)) continue;
+    if ((dlog(V) + lia) - dlog(a / (us * us) + b) <= (k * ll - lam) - dlgamma(k + 1.0)) { res = k; break; }
+  }
+  if (n_attempts) *n_attempts = it < MAX_ATTEMPTS ? it + 1 : MAX_ATTEMPTS;
+  return res;
+}
 
 #ifdef ZSPROF
 constexpr int DRPROF_W = 4096;

@@ -1439,6 +1439,13 @@ __global__ void k_test_sampler(int which, uint32_t k0, uint32_t k1, uint32_t var
   }
   out[i] = r;
 }
+// probe 8 of bnmf_test_sampler: rpois(a).  A kernel of its own, so that k_test_sampler stays the code it was.
+__global__ void k_test_rpois(uint32_t k0, uint32_t k1, uint32_t var, uint32_t elem0, uint32_t iter, const double* a, double* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Stream s(k0, k1, var, elem0 + (uint32_t)i, iter);
+  out[i] = rpois(s, a[i]);
+}
 __global__ void k_test_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out, int rounds) {
   const u32x4 w = rounds == 7 ? philox4x32_7(c0, c1, c2, c3, k0, k1) : philox4x32_10(c0, c1, c2, c3, k0, k1);
   out[0] = w.x; out[1] = w.y; out[2] = w.z; out[3] = w.w;

@@ -26,7 +26,7 @@ LIKELIHOOD = dict(poisson=0, normal=1)
 PRIOR = dict(truncnormal=0, exponential=1, gamma=2)
 RANK_METHOD = dict(SBFI=0, BFI=1)
 MATH_FN = dict(log=0, exp=1, lgamma=2, digamma=3, qnorm=4, log_pnorm=5, sqrt=6, recip=7)
-SAMPLER = dict(rgamma=0, rtnorm0=1, rnorm=2, ralpha=3, runif=4, rexp=5, ralpha_fast=6, ralpha_fast_wave=7)
+SAMPLER = dict(rgamma=0, rtnorm0=1, rnorm=2, ralpha=3, runif=4, rexp=5, ralpha_fast=6, ralpha_fast_wave=7, rpois=8)
 
 
 class BnmfError(RuntimeError):
@@ -81,6 +81,14 @@ class BnmfMixingInfo(C.Structure):
                 ("max_rhat_E", C.c_double)]
 
 
+class BnmfPpcInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_tail_cells", C.c_int64), ("p_T1", C.c_double), ("p_T2", C.c_double),
+                ("mean_T1_obs", C.c_double), ("mean_T1_rep", C.c_double), ("mean_T2_obs", C.c_double), ("mean_T2_rep", C.c_double)]
+
+
+PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
+PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
+PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
 NMIX = 11
 MIX_ROWS = ["mean", "var", "ess", "mcse", "rhat", "pairs", "exit", "mean_a", "var_a", "mean_b", "var_b"]
 NMAPROW = 17
@@ -93,7 +101,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
-               "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at"]
+               "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at"]
 
 
 def lib():
@@ -146,6 +154,8 @@ def lib():
         L.bnmf_waic_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, C.POINTER(BnmfWaicInfo)]
         L.bnmf_mixing.argtypes = [C.c_void_p, C.c_int, ip, ip, dp, dp, C.POINTER(BnmfMixingInfo)]
         L.bnmf_mixing_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, dp, dp, C.POINTER(BnmfMixingInfo)]
+        L.bnmf_ppc.argtypes = [C.c_void_p, C.c_int, ip, dp, dp, dp, C.POINTER(BnmfPpcInfo)]
+        L.bnmf_ppc_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, dp, C.POINTER(BnmfPpcInfo)]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -434,6 +444,34 @@ class Engine:
         if pointwise:
             out.update(lppd_col=col[:G], p_waic_col=col[G:2 * G], mean_loglik_col=col[2 * G:],
                        lppd_cell=cell[:K * G].reshape((K, G), order="F"), p_waic_cell=cell[K * G:].reshape((K, G), order="F"))
+        return out
+
+    def ppc(self, last_n, used=None, end_iter=None, pointwise=False):
+        """Posterior predictive checks over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_ppc / bnmf_ppc_at), on the device.  Returns the
+        info fields, col (6 x G) with its rows also by name (PPC_COL_ROWS: the mean over the used samples of T on the data and on the
+        replicate and p = #(T_rep >= T_obs) / S, for T1 and T2), series (4 x S) with its rows by name (PPC_SERIES_ROWS: the whole-matrix
+        values per used sample); with pointwise also mean_cell, var_cell, p_less_cell, p_equal_cell and pit = p_less + 0.5 p_equal (K x G)."""
+        K, G = self.K, self.G
+        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
+        if u is not None and u.size != last_n:
+            raise BnmfError(-2, f"ppc: used has {u.size} entries for {last_n} samples")
+        S = int(last_n) if u is None else int((u != 0).sum())
+        col = np.empty((6, G))
+        series = np.empty((4, max(S, 0)))
+        cell = np.empty((4, K * G)) if pointwise else None
+        info = BnmfPpcInfo()
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_ppc if end_iter is None else lib().bnmf_ppc_at)(
+            self._h, *rng, None if u is None else u.ctypes.data_as(C.POINTER(C.c_int32)), _dp(col), None if cell is None else _dp(cell),
+            _dp(series), C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in BnmfPpcInfo._fields_}
+        out.update(col=col, series=series)
+        out.update({name: col[i] for i, name in enumerate(PPC_COL_ROWS)})
+        out.update({name: series[i] for i, name in enumerate(PPC_SERIES_ROWS)})
+        if pointwise:
+            out.update({name: cell[i].reshape((K, G), order="F") for i, name in enumerate(PPC_CELL_ROWS)})
+            out["pit"] = out["p_less_cell"] + 0.5 * out["p_equal_cell"]
         return out
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):

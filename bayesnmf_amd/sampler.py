@@ -634,8 +634,29 @@ class bayesNMF_sampler:
         n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
         return self._chain.waic(n, used=used, pointwise=pointwise, **kw)
 
+    def get_PPC(self, end_iter=None, n_samples=None, idx="MAP_idx", pointwise=False):
+        """Posterior predictive checks of the recorded samples, on the device (bnmf_ppc_at; not in the reference): over iterations
+        end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last MAP_over samples), restricted to `idx` ("MAP_idx": those
+        whose A equals the mode of the range; None: every sample; else a vector of recorded iterations), a replicate of the data is
+        drawn from every sample's own fit and compared with the data through two discrepancies (Poisson: Freeman-Tukey and the number
+        of zero cells; Normal: the sum of squared standardised residuals and the largest one).
+        Returns dict(n_used, n_tail_cells, p_T1, p_T2, mean_T1_obs, mean_T1_rep, mean_T2_obs, mean_T2_rep; col: a data frame with one
+        row per column of the data — T1_obs, T1_rep, p_T1, T2_obs, T2_rep, p_T2: a p_T1 near 0 marks a column the model reconstructs
+        worse than its own replicates; series: a data frame with one row per used sample — T1_obs, T1_rep, T2_obs, T2_rep over the
+        whole matrix); with pointwise also mean_cell, var_cell, p_less_cell, p_equal_cell and pit = p_less + 0.5 p_equal (K x G)."""
+        if not hasattr(self._chain, "ppc"):
+            raise ValueError("get_PPC needs an engine that computes posterior predictive checks over its recorded samples (ppc); this engine_factory's cannot")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.ppc(n, used=used, pointwise=pointwise, **kw)
+        out = {k: r[k] for k in ("n_used", "n_tail_cells", "p_T1", "p_T2", "mean_T1_obs", "mean_T1_rep", "mean_T2_obs", "mean_T2_rep")}
+        out["col"] = pd.DataFrame({k[:-4]: r[k] for k in ("T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col")})
+        out["series"] = pd.DataFrame({k: r[k] for k in ("T1_obs", "T1_rep", "T2_obs", "T2_rep")})
+        if pointwise:
+            out.update({k: r[k] for k in ("mean_cell", "var_cell", "p_less_cell", "p_equal_cell", "pit")})
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

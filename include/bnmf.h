@@ -54,7 +54,8 @@ enum {
 enum { BNMF_V_Z = 1, BNMF_V_P = 2, BNMF_V_E = 3, BNMF_V_BETA_P = 4, BNMF_V_ALPHA_P = 5,
        BNMF_V_BETA_E = 6, BNMF_V_ALPHA_E = 7, BNMF_V_MU_P = 8, BNMF_V_SIGSQ_P = 9,
        BNMF_V_MU_E = 10, BNMF_V_SIGSQ_E = 11, BNMF_V_LAMBDA_P = 12, BNMF_V_LAMBDA_E = 13,
-       BNMF_V_A = 14, BNMF_V_R = 15, BNMF_V_MHU_P = 16, BNMF_V_MHU_E = 17, BNMF_V_SIGMASQ = 18 };
+       BNMF_V_A = 14, BNMF_V_R = 15, BNMF_V_MHU_P = 16, BNMF_V_MHU_E = 17, BNMF_V_SIGMASQ = 18,
+       BNMF_V_YREP = 19 /* the replicates of bnmf_ppc: no draw of the chain */ };
 
 typedef struct bnmf_handle bnmf_handle;
 
@@ -255,6 +256,32 @@ int bnmf_mixing(bnmf_handle*, int last_n, const int32_t* used /* [last_n], NULL 
 int bnmf_mixing_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out, double* E_out,
                    bnmf_mixing_info* info);
 
+/* Posterior predictive checks of a recorded range, on the device: for every recorded sample flagged in used[] (oldest first;
+ * NULL = all) a replicate y_s of the data is drawn from the sample's own fit c_s = P_s diag(A_s) E_s — Poisson(max(c_s, 1e-6)) by the
+ * stream spec's rpois, or c_s + sqrt(sigmasq_s[g]) * a standard normal — on the stream (BNMF_V_YREP, element k + K g, the sample's
+ * iteration) under the handle's key: the replicate of a cell and iteration is the same whichever range, used[] or call asks for it, and
+ * the chain's own streams are not consumed.  Two discrepancies, each evaluated on the data and on the replicate against the same fit:
+ *   Poisson  T1 = sum_k (sqrt(x) - sqrt(lambda))^2 (Freeman-Tukey)   T2 = the number of cells with x == 0
+ *   Normal   T1 = sum_k z^2, z = (x - c_s) / sd                       T2 = max_k |z|
+ * col [BNMF_PPC_NCOL][G]: per column the mean over the used samples of T on the data, of T on the replicate, and p = #(T_rep >= T_obs) / S,
+ *   T1 in rows 0-2, T2 in rows 3-5 (a p near 0: the data of that column fit better than the model's own replicates do, near 1 the reverse;
+ *   for T1 a column the model reconstructs badly has p near 0).
+ * cell [4][K*G] (column-major): the mean and variance (S - 1 form) of the replicates, p_less = #(y < m) / S, p_equal = #(y == m) / S; the
+ *   mid-PIT of a cell is p_less + 0.5 p_equal.
+ * series [4][S]: the whole-matrix T1_obs, T1_rep, T2_obs, T2_rep of every used sample (sums over the columns; the maximum for the Normal T2).
+ * info: p_T1 / p_T2 = the fraction of used samples whose whole-matrix T_rep >= T_obs, the means of the four series, n_tail_cells = the
+ *   cells whose mid-PIT lies outside [0.025, 0.975].  col, cell and series may each be NULL.  Every sum is taken in a fixed order: the same
+ *   call gives the same bits.  Read-only for the chain.
+ * bnmf_ppc_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_ppc(h, n, ...) is bnmf_ppc_at(h, iter, n, ...).  Refused before any device work: null info and a used[] value other than 0 / 1
+ * (the index named) with BNMF_EINVAL, fewer than 2 used samples with BNMF_ESIZE, window = 0 or a poisoned handle with BNMF_ESTATE. */
+#define BNMF_PPC_NCOL 6   /* per T: mean T_obs, mean T_rep, p = #(T_rep >= T_obs)/S; T1 rows 0-2, T2 rows 3-5 */
+typedef struct { int32_t n_used; int64_t n_tail_cells;   /* mid-PIT outside [0.025, 0.975] */
+                 double p_T1, p_T2, mean_T1_obs, mean_T1_rep, mean_T2_obs, mean_T2_rep; } bnmf_ppc_info;
+int bnmf_ppc(bnmf_handle*, int last_n, const int32_t* used, double* col /* [6][G] */, double* cell /* [4][K*G]: mean, var, p_less, p_equal */,
+             double* series /* [4][S]: whole-matrix T1_obs, T1_rep, T2_obs, T2_rep per used sample */, bnmf_ppc_info* info);
+int bnmf_ppc_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info);
+
 int bnmf_get_iter(bnmf_handle* h, int* iter);
 
 /* A chain's state in a file, and back (checkpoint / resume; the reference's save_object, saveRDS(self), R/bayesNMF_sampler.R:414-416).
@@ -313,7 +340,8 @@ int bnmf_ubench(int device, double* philox_words_per_s, double* copy_gbs);
 /* device-side unit probes used by the parity tests (tests/test_gpu_*.py) */
 int bnmf_test_math(int device, int fn, const double* in, double* out, size_t n);
 /* which: 0 rgamma(a, b), 1 rtnorm0(a, b), 2 rnorm, 3 ralpha(a, b, c), 4 runif, 5 rexp(a), 6 ralpha_fast(a, b, c), 7 ralpha_fast_wave(a, b, c):
- * the wave-cooperative form of 6 (every lane of every wave calls it; the lanes past n take part without an element) */
+ * the wave-cooperative form of 6 (every lane of every wave calls it; the lanes past n take part without an element), 8 rpois(a): a whole
+ * number in a double, 1e-6 <= a <= 2^24 (b and c are not read) */
 int bnmf_test_sampler(int device, int which, uint64_t seed, uint32_t chain, uint32_t var,
                       uint32_t elem0, uint32_t iter, const double* a, const double* b,
                       const double* c, double* out, size_t n);

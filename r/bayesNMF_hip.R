@@ -184,6 +184,32 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (!is.null(r$P)) { colnames(r$P) <- cols; colnames(r$E) <- cols }
       r
     },
+    # Posterior predictive checks of the recorded samples, on the device (bnmf_ppc_at; not in the reference): over iterations
+    # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, a replicate of the data is drawn from every
+    # sample's own fit and compared with the data through two discrepancies (Poisson: Freeman-Tukey and the number of zero cells;
+    # Normal: the sum of squared standardised residuals and the largest one).  list(n_used, n_tail_cells, p_T1, p_T2, mean_T1_obs,
+    # mean_T1_rep, mean_T2_obs, mean_T2_rep, col (G x 6: T1_obs, T1_rep, p_T1, T2_obs, T2_rep, p_T2 per column of the data; a p_T1 near 0
+    # marks a column the model reconstructs worse than its own replicates), series (S x 4 per used sample, over the whole matrix)), with
+    # pointwise also mean_cell, var_cell, p_less_cell, p_equal_cell and pit = p_less_cell + 0.5 p_equal_cell (K x G)
+    get_PPC = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                       idx = "MAP_idx", pointwise = FALSE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      r <- .Call("C_bnmf_ppc", self$handle, as.integer(end_iter), as.integer(n_samples), used, as.logical(pointwise),
+                 c(self$dims$K, self$dims$G, self$dims$N))
+      colnames(r$col) <- c("T1_obs", "T1_rep", "p_T1", "T2_obs", "T2_rep", "p_T2")
+      colnames(r$series) <- c("T1_obs", "T1_rep", "T2_obs", "T2_rep")
+      if (pointwise) r$pit <- r$p_less_cell + 0.5 * r$p_equal_cell
+      r
+    },
     # the data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below, on the device
     # (bnmf_label_switching): per recorded iteration in idx ("all": every kept sample) and latent factor, the reference signature
     # hungarian_assignment(keep_all_est = TRUE) gives it ("None": no partner), that cosine, and whether A includes the factor

@@ -382,6 +382,65 @@ SEXP C_bnmf_mixing_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP k
   UNPROTECT(1);
   return out;
 }
+/* Posterior predictive checks over recorded samples on the device (bnmf_ppc / bnmf_ppc_at): C_bnmf_ppc(ptr, end_iter (integer, or NULL =
+ * the current iteration), n_samples, used (logical length n_samples, or NULL = all), want_cell (logical), dims c(K,G,N)) ->
+ * list(n_used, n_tail_cells, p_T1, p_T2, mean_T1_obs, mean_T1_rep, mean_T2_obs, mean_T2_rep, col (G x 6: T1_obs, T1_rep, p_T1, T2_obs,
+ * T2_rep, p_T2 per column), series (S x 4: the whole-matrix T1_obs, T1_rep, T2_obs, T2_rep per used sample), mean_cell, var_cell,
+ * p_less_cell, p_equal_cell (K x G each, or NULL)) over iterations end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_ppc_at: the same with end_iter required */
+/* the result list with col and series allocated, and the flags of used; returned unprotected */
+static SEXP ppc_alloc(SEXP n_samples, SEXP used, SEXP dims, int32_t** u) {
+  const int n = INTEGER(n_samples)[0], G = INTEGER(dims)[1];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  *u = lgl_flags(used, n);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_tail_cells", "p_T1", "p_T2", "mean_T1_obs", "mean_T1_rep", "mean_T2_obs", "mean_T2_rep", "col", "series",
+                              "mean_cell", "var_cell", "p_less_cell", "p_equal_cell"};
+  SEXP out = PROTECT(named_list(14, nms));
+  SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, G, BNMF_PPC_NCOL));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, S, 4));
+  UNPROTECT(1);
+  return out;
+}
+static double* ppc_cell_buf(SEXP want_cell, SEXP dims) {
+  const int* d = INTEGER(dims);
+  return LOGICAL(want_cell)[0] == TRUE ? (double*)R_alloc(4 * (size_t)d[0] * (size_t)d[1], sizeof(double)) : NULL;
+}
+static void ppc_finish(SEXP out, const double* cell, SEXP dims, const bnmf_ppc_info* info) {
+  const int* d = INTEGER(dims); const int K = d[0], G = d[1];
+  if (cell) {
+    for (int i = 0; i < 4; ++i) {
+      SEXP m = Rf_allocMatrix(REALSXP, K, G);
+      SET_VECTOR_ELT(out, 10 + i, m);
+      for (R_xlen_t j = 0; j < (R_xlen_t)K * G; ++j) REAL(m)[j] = cell[(size_t)i * K * G + (size_t)j];
+    }
+  }
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarReal((double)info->n_tail_cells));
+  const double v[6] = {info->p_T1, info->p_T2, info->mean_T1_obs, info->mean_T1_rep, info->mean_T2_obs, info->mean_T2_rep};
+  for (int i = 0; i < 6; ++i) SET_VECTOR_ELT(out, 2 + i, Rf_ScalarReal(v[i]));
+}
+SEXP C_bnmf_ppc(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP want_cell, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(ppc_alloc(n_samples, used, dims, &u));
+  double* cell = ppc_cell_buf(want_cell, dims);
+  bnmf_ppc_info info;
+  if (end_iter == R_NilValue) chk(bnmf_ppc(get_handle(ptr), INTEGER(n_samples)[0], u, map_buf(out, 8), cell, map_buf(out, 9), &info));
+  else chk(bnmf_ppc_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, map_buf(out, 8), cell, map_buf(out, 9), &info));
+  ppc_finish(out, cell, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_ppc_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP want_cell, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(ppc_alloc(n_samples, used, dims, &u));
+  double* cell = ppc_cell_buf(want_cell, dims);
+  bnmf_ppc_info info;
+  chk(bnmf_ppc_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, map_buf(out, 8), cell, map_buf(out, 9), &info));
+  ppc_finish(out, cell, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* plot_label_switching's per-sample hungarian_assignment diagonal (R/postprocessing_visualizations.R:598-669):
  * C_bnmf_label_switching(ptr, iters (integer iteration numbers), reference_P (K x R), dims c(K,G,N)) ->
  * list(assigned N x n_iters (1-based column of reference_P, NA = "None"), cosine N x n_iters, included N x n_iters logical):
@@ -462,6 +521,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_set_fixed", (DL_FUNC)&C_bnmf_set_fixed, 3}, {"C_bnmf_get_fixed", (DL_FUNC)&C_bnmf_get_fixed, 3},
   {"C_bnmf_waic", (DL_FUNC)&C_bnmf_waic, 7}, {"C_bnmf_waic_at", (DL_FUNC)&C_bnmf_waic_at, 7},
   {"C_bnmf_mixing", (DL_FUNC)&C_bnmf_mixing, 7}, {"C_bnmf_mixing_at", (DL_FUNC)&C_bnmf_mixing_at, 7},
+  {"C_bnmf_ppc", (DL_FUNC)&C_bnmf_ppc, 6}, {"C_bnmf_ppc_at", (DL_FUNC)&C_bnmf_ppc_at, 6},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
