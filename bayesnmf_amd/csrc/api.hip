@@ -33,6 +33,7 @@
 #include "mh.h"
 #include "waic.h"
 #include "ppc.h"
+#include "attribution.h"
 #include "mixing.h"
 
 using namespace bnmf;
@@ -257,6 +258,7 @@ struct bnmf_handle {
   bool have_ev = false;
   double* dMap = nullptr; size_t map_words = 0;   // scratch of bnmf_map (grown on demand)
   double* dWaic = nullptr; size_t waic_words = 0; // scratch of bnmf_waic (grown on demand): column sums, cell values, slot list
+  double* dAttr = nullptr; size_t attr_words = 0; // scratch of bnmf_attribution (grown on demand): a batch of a_s and u, the running statistics, load rows, series, prob, slot list
   double* dPpc = nullptr; size_t ppc_words = 0;   // scratch of bnmf_ppc (grown on demand): T[4][S][G], column rows, series, cell values, slot and iteration lists
   double* dMix = nullptr; size_t mix_words = 0;   // scratch of bnmf_mixing (grown on demand): colSums(P) per sample, both outputs, slot list
   int devlock_fd = -1;                 // the device's lock file (<BNMF_LOCKDIR or /tmp>/bnmf_dev_<PCI bus id>.lock): the device gate's rule across the PROCESSES that share the device
@@ -1743,6 +1745,92 @@ int bnmf_ppc_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used
   if (int rc = check_recorded(h, "bnmf_ppc_at")) return rc;
   if (int rc = check_kept(h, "bnmf_ppc_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
   return ppc_impl(h, "bnmf_ppc_at", end_iter, n_samples, used, col, cell, series, info);
+}
+
+// Signature attribution over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller):
+// per batch of samples k_attr leaves a_s[n,g] in the scratch, k_attr_share the reciprocal column totals, k_attr_stats continues the
+// per-(n, g) statistics and reduces the series (attribution.h); total and n_present are sequential scans on the host.
+static_assert(AT_NLOAD == BNMF_ATTR_NLOAD, "attribution.h and bnmf.h disagree");
+static constexpr size_t ATTR_SCRATCH_CAP = (size_t)256 << 20;   // bytes of a_s and u per batch
+static int attr_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, double min_load, double* load, double* prob,
+                     double* series, bnmf_attr_info* info) {
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
+  std::vector<int> slots;
+  for (int s = 0; s < n_samples; ++s) {
+    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
+    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
+  }
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the loads needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  const size_t NG = (size_t)N * G, KNG = (size_t)K * NG, per = (NG + (size_t)G) * sizeof(double);   // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, ATTR_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_ATTR_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>(want, S);
+  const size_t words = (size_t)Sb * (NG + G) + 2 * AT_NLOAD * NG + (size_t)S * N + (prob ? KNG : 0) + ((size_t)S + 1) / 2 + 8;
+  if (words > h->attr_words) {
+    HIPCHK(hfree(h, h->dAttr)); h->dAttr = nullptr; h->attr_words = 0;
+    HIPCHK(hmalloc(h, &h->dAttr, words * sizeof(double))); h->attr_words = words;
+  }
+  double* dscr = h->dAttr; double* du = dscr + (size_t)Sb * NG; double* dst = du + (size_t)Sb * G; double* dload = dst + AT_NLOAD * NG;
+  double* dser = dload + AT_NLOAD * NG; double* dprob = prob ? dser + (size_t)S * N : nullptr;
+  int* dslots = (int*)(dser + (size_t)S * N + (prob ? KNG : 0));
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  AttrArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.M = h->dM; a.scr = dscr; a.prob = dprob;
+  a.lenP = (size_t)K * N; a.lenE = NG; a.K = K; a.N = N; a.G = G; a.S = S;
+  size_t lds = attr_lds_bytes(N);
+  a.stage = lds <= 160 * 1024 ? 1 : 0;
+  if (!a.stage) lds = 0;
+  const void* kern = normal ? (prob ? (const void*)k_attr<true, true> : (const void*)k_attr<true, false>)
+                            : (prob ? (const void*)k_attr<false, true> : (const void*)k_attr<false, false>);
+  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  const dim3 grid((unsigned)((G + AT_GC - 1) / AT_GC)), block(AT_T);
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0), last = s0 + nb == S ? 1 : 0;
+    a.slots = dslots + s0; a.Sb = nb; a.first = s0 == 0 ? 1 : 0; a.last = last;
+    if (normal) { if (prob) hipLaunchKernelGGL((k_attr<true, true>), grid, block, lds, h->stream, a); else hipLaunchKernelGGL((k_attr<true, false>), grid, block, lds, h->stream, a); }
+    else { if (prob) hipLaunchKernelGGL((k_attr<false, true>), grid, block, lds, h->stream, a); else hipLaunchKernelGGL((k_attr<false, false>), grid, block, lds, h->stream, a); }
+    const size_t nsg = (size_t)nb * G;
+    hipLaunchKernelGGL(k_attr_share, dim3((unsigned)((nsg + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, G, du);
+    hipLaunchKernelGGL(k_attr_stats, dim3((unsigned)((size_t)nb * N + (NG + AT_TT - 1) / AT_TT)), dim3(AT_TT), 0, h->stream, (const double*)dscr,
+                       (const double*)du, nb, N, G, S, s0, last, min_load, dst, dser, dload);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> hs((size_t)S * N), hp(NG);
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, (size_t)S * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hp.data(), dload + 3 * NG, NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (load) HIPCHK(hipMemcpyAsync(load, dload, AT_NLOAD * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (prob) HIPCHK(hipMemcpyAsync(prob, dprob, KNG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), (size_t)S * N * sizeof(double));
+  double t = 0.0;
+  for (size_t i = 0; i < (size_t)S * N; ++i) t += hs[i];
+  int64_t np = 0;
+  for (size_t i = 0; i < NG; ++i) np += hp[i] >= 0.5 ? 1 : 0;
+  info->n_used = S; info->_pad = 0; info->n_present = np; info->min_load = min_load; info->total = t / (double)S;
+  return 0;
+}
+int bnmf_attribution(bnmf_handle* h, int last_n, const int32_t* used, double min_load, double* load, double* prob, double* series, bnmf_attr_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_attribution: null argument");
+  if (int rc = check_recorded(h, "bnmf_attribution")) return rc;
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter)
+    return fail(BNMF_ESIZE, "bnmf_attribution: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return attr_impl(h, "bnmf_attribution", h->iter, last_n, used, min_load, load, prob, series, info);
+}
+int bnmf_attribution_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double min_load, double* load, double* prob, double* series,
+                        bnmf_attr_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_attribution_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_attribution_at")) return rc;
+  if (int rc = check_kept(h, "bnmf_attribution_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return attr_impl(h, "bnmf_attribution_at", end_iter, n_samples, used, min_load, load, prob, series, info);
 }
 
 // Mixing diagnostics over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller):

@@ -86,6 +86,11 @@ class BnmfPpcInfo(C.Structure):
                 ("mean_T1_obs", C.c_double), ("mean_T1_rep", C.c_double), ("mean_T2_obs", C.c_double), ("mean_T2_rep", C.c_double)]
 
 
+class BnmfAttrInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("_pad", C.c_int32), ("n_present", C.c_int64), ("min_load", C.c_double), ("total", C.c_double)]
+
+
+ATTR_LOAD_ROWS = ["load_mean", "load_var", "share", "p_present"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -101,7 +106,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_kernel_name", "bnmf_ubench", "bnmf_test_math", "bnmf_test_sampler", "bnmf_test_philox", "bnmf_test_philox7",
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
-               "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at"]
+               "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
+               "bnmf_attribution", "bnmf_attribution_at"]
 
 
 def lib():
@@ -156,6 +162,8 @@ def lib():
         L.bnmf_mixing_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, dp, dp, C.POINTER(BnmfMixingInfo)]
         L.bnmf_ppc.argtypes = [C.c_void_p, C.c_int, ip, dp, dp, dp, C.POINTER(BnmfPpcInfo)]
         L.bnmf_ppc_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, dp, C.POINTER(BnmfPpcInfo)]
+        L.bnmf_attribution.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
+        L.bnmf_attribution_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -472,6 +480,33 @@ class Engine:
         if pointwise:
             out.update({name: cell[i].reshape((K, G), order="F") for i, name in enumerate(PPC_CELL_ROWS)})
             out["pit"] = out["p_less_cell"] + 0.5 * out["p_equal_cell"]
+        return out
+
+    def attribution(self, last_n, used=None, end_iter=None, min_load=1.0, prob=False):
+        """Signature attribution over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_attribution / bnmf_attribution_at), on the
+        device.  Returns the info fields, load (4 x N x G) with its rows also by name (ATTR_LOAD_ROWS: the mean and variance over the
+        used samples of the mutations of tumour g attributed to factor n, the mean share of the tumour's load, and the fraction of
+        samples whose load is >= min_load), series (S x N: the cohort's load per used sample and factor); with prob also prob
+        (K x N x G: the probability that a mutation of type k in tumour g came from factor n)."""
+        K, G, N = self.K, self.G, self.N
+        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
+        if u is not None and u.size != last_n:
+            raise BnmfError(-2, f"attribution: used has {u.size} entries for {last_n} samples")
+        S = int(last_n) if u is None else int((u != 0).sum())
+        load = np.empty((4, N * G))
+        series = np.empty((max(S, 0), N))
+        pr = np.empty(K * N * G) if prob else None
+        info = BnmfAttrInfo()
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_attribution if end_iter is None else lib().bnmf_attribution_at)(
+            self._h, *rng, None if u is None else u.ctypes.data_as(C.POINTER(C.c_int32)), float(min_load), _dp(load),
+            None if pr is None else _dp(pr), _dp(series), C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in BnmfAttrInfo._fields_ if name != "_pad"}
+        out.update(load=np.stack([row.reshape((N, G), order="F") for row in load]), series=series)
+        out.update({name: out["load"][i] for i, name in enumerate(ATTR_LOAD_ROWS)})
+        if prob:
+            out["prob"] = pr.reshape((K, N, G), order="F")
         return out
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):

@@ -655,8 +655,33 @@ class bayesNMF_sampler:
             out.update({k: r[k] for k in ("mean_cell", "var_cell", "p_less_cell", "p_equal_cell", "pit")})
         return out
 
+    def get_attribution(self, end_iter=None, n_samples=None, idx="MAP_idx", min_load=1.0, credible_interval=0.95, prob=False):
+        """Which signature produced the mutations of which tumour, on the device (bnmf_attribution_at; not in the reference): over
+        iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last MAP_over samples), restricted to `idx`
+        ("MAP_idx": those whose A equals the mode of the range; None: every sample; else a vector of recorded iterations), every
+        sample allocates the count of every cell to the factors in proportion to their parts of the fit.
+        Returns dict(load_mean, load_sd, share, p_present: N x G arrays — the mean and standard deviation over the samples of the
+        mutations of tumour g attributed to signature n, its mean share of the tumour, and the fraction of samples in which it
+        carries at least min_load mutations; cohort: a data frame with one row per signature — the mean and the credible_interval
+        bounds (quantile type 7) of its load over the whole cohort; n_used, n_present: the (n, g) with p_present >= 0.5, total: the
+        mean load of the cohort); with prob also prob (K x N x G), the probability that a mutation of type k in tumour g came from
+        signature n.  Factor n is taken to be the same signature in every sample, as get_MAP takes it."""
+        if not hasattr(self._chain, "attribution"):
+            raise ValueError("get_attribution needs an engine that computes the attribution over its recorded samples (attribution); this engine_factory's cannot")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.attribution(n, used=used, min_load=min_load, prob=prob, **kw)
+        ser = np.asarray(r["series"], dtype=float)
+        a = (1.0 - float(credible_interval)) / 2.0
+        out = dict(load_mean=r["load_mean"], load_sd=np.sqrt(r["load_var"]), share=r["share"], p_present=r["p_present"],
+                   cohort=pd.DataFrame(dict(signature=np.arange(1, ser.shape[1] + 1), mean=ser.mean(axis=0),
+                                            lower=np.quantile(ser, a, axis=0), upper=np.quantile(ser, 1.0 - a, axis=0))),
+                   n_used=r["n_used"], n_present=r["n_present"], total=r["total"])
+        if prob:
+            out["prob"] = r["prob"]
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

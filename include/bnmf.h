@@ -282,6 +282,33 @@ int bnmf_ppc(bnmf_handle*, int last_n, const int32_t* used, double* col /* [6][G
              double* series /* [4][S]: whole-matrix T1_obs, T1_rep, T2_obs, T2_rep per used sample */, bnmf_ppc_info* info);
 int bnmf_ppc_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info);
 
+/* Signature attribution of a recorded range, on the device: for every recorded sample flagged in used[] (oldest first;
+ * NULL = all) the share of factor n in cell (k, g) is r_n = f_n / sum_n' f_n', f_n = P_s[k,n] A_s[n] E_s[n,g] (0 where the fit of the
+ * cell is 0), and the mutations of the cell attributed to it x_n = m_kg r_n, the mean of the allocation Z given the sample (Normal
+ * likelihood: x_n = f_n, the component of the fit; real-valued data are not allocated).  a_s[n,g] = sum_k x_n is the load of signature n
+ * in tumour g under sample s.
+ * load [BNMF_ATTR_NLOAD][N*G], each row laid out as E (n + N g): over the used samples the mean and the variance (S - 1 form) of a_s, the
+ *   mean of a_s[n,g] / sum_n' a_s[n',g], and #(a_s >= min_load) / S: the probability that the signature is present in the tumour.
+ * prob [K*N*G], laid out as Z (k + K (n + N g)): the mean over the used samples of r_n, the probability that a mutation of type k in
+ *   tumour g came from signature n.
+ * series [S][N] row-major: the cohort's load of every signature per used sample (a_s summed over the tumours).
+ * info: total = the mean over the samples of the whole cohort's load (Poisson: close to the sum of the data), n_present = the (n, g)
+ *   whose probability of presence is >= 0.5.  load, prob and series may each be NULL.  Factor n is taken to be the same signature in
+ *   every sample, as bnmf_map takes it when it averages P and E element-wise.  Every sum is taken in a fixed order: the same call
+ *   gives the same bits.  Read-only for the chain.
+ * bnmf_attribution_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_attribution(h, n, ...) is bnmf_attribution_at(h, iter, n, ...).  Refused before any device work: null info, a used[] value other
+ * than 0 / 1 (the index named) and a min_load that is NaN, infinite or negative with BNMF_EINVAL, fewer than 2 used samples with
+ * BNMF_ESIZE, window = 0 or a poisoned handle with BNMF_ESTATE. */
+#define BNMF_ATTR_NLOAD 4   /* load rows: mean, variance, mean share, probability of presence */
+typedef struct { int32_t n_used, _pad; int64_t n_present; double min_load, total; } bnmf_attr_info;
+int bnmf_attribution(bnmf_handle*, int last_n, const int32_t* used, double min_load,
+                     double* load   /* [BNMF_ATTR_NLOAD][N*G], each row laid out as E (n + N g); may be NULL */,
+                     double* prob   /* [K*N*G], laid out as Z (k + K (n + N g)); may be NULL */,
+                     double* series /* [S][N] row-major; may be NULL */, bnmf_attr_info* info);
+int bnmf_attribution_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double min_load,
+                        double* load, double* prob, double* series, bnmf_attr_info* info);
+
 int bnmf_get_iter(bnmf_handle* h, int* iter);
 
 /* A chain's state in a file, and back (checkpoint / resume; the reference's save_object, saveRDS(self), R/bayesNMF_sampler.R:414-416).

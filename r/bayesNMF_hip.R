@@ -210,6 +210,39 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (pointwise) r$pit <- r$p_less_cell + 0.5 * r$p_equal_cell
       r
     },
+    # Which signature produced the mutations of which tumour, on the device (bnmf_attribution_at; not in the reference): over iterations
+    # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample allocates the count of every cell to
+    # the factors in proportion to their parts of the fit.  list(load_mean, load_sd, share, p_present (N x G: the mean and standard
+    # deviation over the samples of the mutations of tumour g attributed to signature n, its mean share of the tumour, the fraction of
+    # samples in which it carries at least min_load mutations), cohort (a data frame with one row per signature: the mean and the
+    # credible_interval bounds, quantile type 7, of its load over the whole cohort), n_used, n_present (the (n, g) with p_present >= 0.5),
+    # total), with prob also prob (K x N x G: the probability that a mutation of type k in tumour g came from signature n).  Factor n is
+    # taken to be the same signature in every sample, as get_MAP takes it.
+    get_attribution = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                               idx = "MAP_idx", min_load = 1, credible_interval = 0.95, prob = FALSE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      r <- .Call("C_bnmf_attribution", self$handle, as.integer(end_iter), as.integer(n_samples), used, as.double(min_load),
+                 as.logical(prob), c(K, G, N))
+      a <- (1 - credible_interval) / 2
+      out <- list(load_mean = matrix(r$load[, 1], N, G), load_sd = sqrt(matrix(r$load[, 2], N, G)), share = matrix(r$load[, 3], N, G),
+                  p_present = matrix(r$load[, 4], N, G),
+                  cohort = data.frame(signature = seq_len(N), mean = rowMeans(r$series),
+                                      lower = apply(r$series, 1, quantile, probs = a, type = 7, names = FALSE),
+                                      upper = apply(r$series, 1, quantile, probs = 1 - a, type = 7, names = FALSE)),
+                  n_used = r$n_used, n_present = r$n_present, total = r$total)
+      if (prob) out$prob <- array(r$prob, c(K, N, G))
+      out
+    },
     # the data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below, on the device
     # (bnmf_label_switching): per recorded iteration in idx ("all": every kept sample) and latent factor, the reference signature
     # hungarian_assignment(keep_all_est = TRUE) gives it ("None": no partner), that cosine, and whether A includes the factor

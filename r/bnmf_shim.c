@@ -441,6 +441,55 @@ SEXP C_bnmf_ppc_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP want
   UNPROTECT(1);
   return out;
 }
+/* Signature attribution over recorded samples on the device (bnmf_attribution / bnmf_attribution_at): C_bnmf_attribution(ptr, end_iter
+ * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), min_load, want_prob (logical),
+ * dims c(K,G,N)) -> list(n_used, n_present, min_load, total, load (N G x 4: one column per row of the C output — mean, variance, mean
+ * share, probability of presence — each laid out as E), series (N x S: the cohort's load of every signature per used sample), prob
+ * (K N x G, laid out as Z: k + K (n + N g); or NULL)) over iterations end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_attribution_at: the same with end_iter required */
+/* the result list with load, series and (if wanted) prob allocated, and the flags of used; returned unprotected */
+static SEXP attr_alloc(SEXP n_samples, SEXP used, SEXP want_prob, SEXP dims, int32_t** u) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  *u = lgl_flags(used, n);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_present", "min_load", "total", "load", "series", "prob"};
+  SEXP out = PROTECT(named_list(7, nms));
+  SET_VECTOR_ELT(out, 4, Rf_allocMatrix(REALSXP, d[2] * d[1], BNMF_ATTR_NLOAD));
+  SET_VECTOR_ELT(out, 5, Rf_allocMatrix(REALSXP, d[2], S));
+  if (LOGICAL(want_prob)[0] == TRUE) SET_VECTOR_ELT(out, 6, Rf_allocMatrix(REALSXP, d[0] * d[2], d[1]));
+  UNPROTECT(1);
+  return out;
+}
+static void attr_finish(SEXP out, const bnmf_attr_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarReal((double)info->n_present));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarReal(info->min_load)); SET_VECTOR_ELT(out, 3, Rf_ScalarReal(info->total));
+}
+SEXP C_bnmf_attribution(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP min_load, SEXP want_prob, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(attr_alloc(n_samples, used, want_prob, dims, &u));
+  bnmf_attr_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_attribution(get_handle(ptr), INTEGER(n_samples)[0], u, REAL(min_load)[0], map_buf(out, 4), map_buf(out, 6), map_buf(out, 5), &info));
+  else
+    chk(bnmf_attribution_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(min_load)[0], map_buf(out, 4), map_buf(out, 6),
+                            map_buf(out, 5), &info));
+  attr_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_attribution_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP min_load, SEXP want_prob, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(attr_alloc(n_samples, used, want_prob, dims, &u));
+  bnmf_attr_info info;
+  chk(bnmf_attribution_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(min_load)[0], map_buf(out, 4), map_buf(out, 6),
+                          map_buf(out, 5), &info));
+  attr_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* plot_label_switching's per-sample hungarian_assignment diagonal (R/postprocessing_visualizations.R:598-669):
  * C_bnmf_label_switching(ptr, iters (integer iteration numbers), reference_P (K x R), dims c(K,G,N)) ->
  * list(assigned N x n_iters (1-based column of reference_P, NA = "None"), cosine N x n_iters, included N x n_iters logical):
@@ -522,6 +571,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_waic", (DL_FUNC)&C_bnmf_waic, 7}, {"C_bnmf_waic_at", (DL_FUNC)&C_bnmf_waic_at, 7},
   {"C_bnmf_mixing", (DL_FUNC)&C_bnmf_mixing, 7}, {"C_bnmf_mixing_at", (DL_FUNC)&C_bnmf_mixing_at, 7},
   {"C_bnmf_ppc", (DL_FUNC)&C_bnmf_ppc, 6}, {"C_bnmf_ppc_at", (DL_FUNC)&C_bnmf_ppc_at, 6},
+  {"C_bnmf_attribution", (DL_FUNC)&C_bnmf_attribution, 7}, {"C_bnmf_attribution_at", (DL_FUNC)&C_bnmf_attribution_at, 7},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
