@@ -35,6 +35,7 @@
 #include "ppc.h"
 #include "attribution.h"
 #include "mixing.h"
+#include "relabel.h"
 
 using namespace bnmf;
 
@@ -261,6 +262,7 @@ struct bnmf_handle {
   double* dAttr = nullptr; size_t attr_words = 0; // scratch of bnmf_attribution (grown on demand): a batch of a_s and u, the running statistics, load rows, series, prob, slot list
   double* dPpc = nullptr; size_t ppc_words = 0;   // scratch of bnmf_ppc (grown on demand): T[4][S][G], column rows, series, cell values, slot and iteration lists
   double* dMix = nullptr; size_t mix_words = 0;   // scratch of bnmf_mixing (grown on demand): colSums(P) per sample, both outputs, slot list
+  unsigned char* dRel = nullptr; size_t rel_bytes = 0;   // scratch of bnmf_relabel (grown on demand): pivot, colSums(P), permutations, cosines, both outputs, lists, a batch of aligned samples
   int devlock_fd = -1;                 // the device's lock file (<BNMF_LOCKDIR or /tmp>/bnmf_dev_<PCI bus id>.lock): the device gate's rule across the PROCESSES that share the device
   int devgate_fd = -1;                 // ... and its turnstile (.gate): a process that wants the device exclusively holds it while it waits, new sharers queue behind it
   bool devlock_off = false;            // BNMF_DEVLOCK=0: the caller vouches that no other process uses the device
@@ -2207,6 +2209,197 @@ int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, cons
   for (int i = 0; i < n_iters; ++i)
     if (assigned[(size_t)i * N] == -2 && N > 0) return fail(BNMF_ESTATE, "bnmf_label_switching: iteration %d has no assignment (a cosine is not finite)", iters[i]);
   return 0;
+}
+
+// Label-switching correction over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the
+// caller): per round k_rl_pivot, the matching (k_rl_match, or past the LDS k_ref_cosine + k_hungarian + k_rl_finish over chunks of samples),
+// k_rl_compact, then the two counts come to the host; between rounds k_rl_accum leaves the next pivot, after the last round the aligned
+// mean and variance of both sides (relabel.h).  confusion and the summary are sequential scans on the host.
+static_assert(BNMF_NREL == RL_NROW, "bnmf.h and relabel.h disagree on the rows of the output");
+static constexpr size_t REL_SCRATCH_CAP = (size_t)256 << 20;    // bytes of aligned samples per batch
+static int relabel_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds,
+                        int32_t* perm, double* cosine, int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E,
+                        bnmf_relabel_info* info) {
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  for (int s = 0; s < n_samples; ++s) {
+    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
+    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
+  }
+  if (max_rounds < 1) return fail(BNMF_EINVAL, "%s: max_rounds = %d, at least 1 round is needed", fn, max_rounds);
+  if (pivot_P)
+    for (int j = 0; j < N; ++j) {
+      bool zero = true;
+      for (int k = 0; k < K; ++k) {
+        const double v = pivot_P[(size_t)k + (size_t)K * j];
+        if (!std::isfinite(v)) return fail(BNMF_EINVAL, "%s: column %d of pivot_P holds a value that is not finite (row %d)", fn, j, k);
+        zero = zero && v == 0.0;
+      }
+      if (zero) return fail(BNMF_EINVAL, "%s: column %d of pivot_P is all zero: it has no cosine", fn, j);
+    }
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, an aligned variance needs at least 2", fn, S, S == 1 ? "" : "s");
+  const size_t hung_lds = relabel_hung_lds(N), match_lds = relabel_match_lds(N);
+  const bool fused = match_lds <= RL_LDS;
+  if (!fused && hung_lds > RL_LDS) return fail(BNMF_ESIZE, "%s: the %d x %d assignment problem exceeds the LDS of one workgroup", fn, N, N);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G, SN = (size_t)S * N, per = (size_t)N * N * sizeof(double);
+  const int chunk = fused ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)S, LS_CHUNK_BYTES / per));
+  // the aligned samples leave in batches of whole samples, P then E through the same scratch
+  const int bP = aligned_P ? (int)std::min<size_t>({(size_t)S, (size_t)65535, std::max<size_t>(1, REL_SCRATCH_CAP / (lenP * sizeof(double)))}) : 0;
+  const int bE = aligned_E ? (int)std::min<size_t>({(size_t)S, (size_t)65535, std::max<size_t>(1, REL_SCRATCH_CAP / (lenE * sizeof(double)))}) : 0;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t oRef = 0, oN2 = oRef + up(lenP * 8), oPiv = oN2 + up((size_t)N * 8), oCs = oPiv + up(lenP * 8), oOP = oCs + up(SN * 8),
+               oOE = oOP + up(RL_NROW * lenP * 8), oCos = oOE + up(RL_NROW * lenE * 8), oPerm = oCos + up(SN * 8), oInv = oPerm + up(SN * 4),
+               oFlag = oInv + up(SN * 4), oAl = oFlag + up((size_t)S * 4), oSl = oAl + up((size_t)S * 4), oCnt = oSl + up((size_t)S * 4),
+               oSig = oCnt + up(16), oCv = oSig + up((size_t)N * 4), oCol = oCv + up((size_t)chunk * per),
+               oBat = oCol + up((size_t)chunk * N * 4), need = oBat + up(std::max((size_t)bP * lenP, (size_t)bE * lenE) * 8);
+  if (need > h->rel_bytes) {
+    HIPCHK(hfree(h, h->dRel)); h->rel_bytes = 0;
+    HIPCHK(hmalloc(h, &h->dRel, need));
+    h->rel_bytes = need;
+  }
+  unsigned char* b = h->dRel;
+  double *dRef = (double*)(b + oRef), *dN2 = (double*)(b + oN2), *dPiv = (double*)(b + oPiv), *cs = (double*)(b + oCs), *oP = (double*)(b + oOP),
+         *oE = (double*)(b + oOE), *dCs = (double*)(b + oCos), *dCv = (double*)(b + oCv), *dBat = (double*)(b + oBat);
+  int32_t *dPerm = (int32_t*)(b + oPerm), *dInv = (int32_t*)(b + oInv), *dFlag = (int32_t*)(b + oFlag), *dCol = (int32_t*)(b + oCol);
+  int *dAl = (int*)(b + oAl), *dSl = (int*)(b + oSl), *dCnt = (int*)(b + oCnt), *dSig = (int*)(b + oSig);
+  const double* ringP = h->arr[BNMF_P].ring;
+  const double* ringE = h->arr[BNMF_E].ring;
+  HIPCHK(hipMemcpyAsync(dSl, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (pivot_P) HIPCHK(hipMemcpyAsync(dPiv, pivot_P, lenP * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (!fused) {
+    std::vector<int> sig(N);
+    for (int n = 0; n < N; ++n) sig[n] = n;
+    HIPCHK(hipMemcpy(dSig, sig.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipFuncSetAttribute((const void*)k_hungarian, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hung_lds));
+  } else if (match_lds > 64 * 1024) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_rl_match, hipFuncAttributeMaxDynamicSharedMemorySize, (int)match_lds));
+  }
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, ringP, lenP, K, N, (const int*)dSl, cs);
+  const size_t tab = relabel_tab_bytes(S, N);
+  const bool stage = tab <= RL_TAB_LDS;
+  if (stage && tab > 64 * 1024) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_rl_accum<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RL_TAB_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)k_rl_accum<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RL_TAB_LDS));
+  }
+  auto accum = [&](int side, int want_var) {
+    const double* ring = side ? ringE : ringP;
+    const size_t len = side ? lenE : lenP;
+    double* o = side ? oE : oP;
+    const dim3 grid((unsigned)((len + (size_t)RL_E * (RL_AT / 64) - 1) / ((size_t)RL_E * (RL_AT / 64)))), block(RL_AT);
+    const size_t lds = stage ? tab : 0;
+    if (side == 0) {
+      if (stage) hipLaunchKernelGGL((k_rl_accum<0, true>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
+      else hipLaunchKernelGGL((k_rl_accum<0, false>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
+    } else {
+      if (stage) hipLaunchKernelGGL((k_rl_accum<1, true>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
+      else hipLaunchKernelGGL((k_rl_accum<1, false>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
+    }
+  };
+  const double* piv = pivot_P ? dPiv : ringP + (size_t)slots[S - 1] * lenP;      // NULL: the newest used sample's P
+  int rounds = 0, converged = 0, cnt[2] = {0, 0};
+  for (int r = 1; r <= max_rounds; ++r) {
+    const int first = r == 1 ? 1 : 0;
+    hipLaunchKernelGGL(k_rl_pivot, dim3((N + 63) / 64), dim3(64), 0, h->stream, piv, K, N, dRef, dN2);
+    if (fused) {
+      hipLaunchKernelGGL(k_rl_match, dim3(S), dim3(64), match_lds, h->stream, ringP, K, N, (const int*)dSl, (const double*)dRef, (const double*)dN2, first,
+                         dPerm, dInv, dCs, dFlag);
+    } else {
+      for (int s0 = 0; s0 < S; s0 += chunk) {
+        const int ns = std::min(chunk, S - s0);
+        hipLaunchKernelGGL(k_ref_cosine, dim3(ns, N), dim3(128), 0, h->stream, ringP, lenP, K, (const int*)dSl + s0, (const int*)dSig, N,
+                           (const double*)dRef, (const double*)dN2, N, dCv);
+        HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)ns * N * sizeof(int32_t), h->stream));
+        hipLaunchKernelGGL(k_hungarian, dim3(ns), dim3(64), hung_lds, h->stream, (const double*)dCv, N, N, 0, dCol);
+        hipLaunchKernelGGL(k_rl_finish, dim3((ns + 63) / 64), dim3(64), 0, h->stream, (const double*)dCv, (const int32_t*)dCol, N, ns, first,
+                           dPerm + (size_t)s0 * N, dInv + (size_t)s0 * N, dCs + (size_t)s0 * N, dFlag + s0);
+      }
+    }
+    hipLaunchKernelGGL(k_rl_compact, dim3(1), dim3(64), 0, h->stream, (const int32_t*)dFlag, S, dAl, dCnt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cnt, dCnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rounds = r;
+    if (cnt[0] < 2)
+      return fail(BNMF_ESIZE, "%s: %d of the %d used samples could be aligned in round %d (a cosine that is not finite leaves a sample unmatched), at least 2 are needed",
+                  fn, cnt[0], S, r);
+    if (cnt[1] == 0) { converged = 1; break; }
+    if (r == max_rounds) break;
+    accum(0, 0);                                           // the next pivot: the aligned mean of the renormalised P
+    piv = oP;
+  }
+  accum(0, 1);
+  accum(1, 1);
+  HIPCHK(hipGetLastError());
+  std::vector<int32_t> hperm(SN);
+  std::vector<double> hcos(SN);
+  HIPCHK(hipMemcpyAsync(hperm.data(), dPerm, SN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hcos.data(), dCs, SN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (P_out) HIPCHK(hipMemcpyAsync(P_out, oP, RL_NROW * lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (E_out) HIPCHK(hipMemcpyAsync(E_out, oE, RL_NROW * lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  auto gather = [&](int side, int nbmax, double* dst) -> int {
+    const size_t len = side ? lenE : lenP;
+    for (int s0 = 0; s0 < S; s0 += nbmax) {
+      const int nb = std::min(nbmax, S - s0);
+      const dim3 grid((unsigned)((len + 255) / 256), (unsigned)nb), block(256);
+      if (side) hipLaunchKernelGGL(k_rl_gather<1>, grid, block, 0, h->stream, ringE, len, K, N, (const int*)dSl, (const int32_t*)dInv, (const int32_t*)dFlag, (const double*)cs, s0, dBat);
+      else hipLaunchKernelGGL(k_rl_gather<0>, grid, block, 0, h->stream, ringP, len, K, N, (const int*)dSl, (const int32_t*)dInv, (const int32_t*)dFlag, (const double*)cs, s0, dBat);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(dst + (size_t)s0 * len, dBat, (size_t)nb * len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));               // the next batch overwrites the scratch
+    }
+    return 0;
+  };
+  if (aligned_P) if (int rc = gather(0, bP, aligned_P)) return rc;
+  if (aligned_E) if (int rc = gather(1, bE, aligned_E)) return rc;
+  if (perm) std::memcpy(perm, hperm.data(), SN * sizeof(int32_t));
+  if (cosine) std::memcpy(cosine, hcos.data(), SN * sizeof(double));
+  if (confusion) for (size_t i = 0; i < (size_t)N * N; ++i) confusion[i] = 0;
+  std::memset(info, 0, sizeof *info);
+  info->n_used = S; info->n_aligned = cnt[0]; info->n_unmatched = S - cnt[0]; info->rounds = rounds; info->converged = converged;
+  info->n_changed_last = cnt[1];
+  double acc[64], mn = std::nan("");
+  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
+  int64_t mn_at = -1;
+  size_t t = 0;                                            // place in the (s, n) sequence of the aligned samples' cosines
+  for (int s = 0; s < S; ++s) {
+    const int32_t* pm = hperm.data() + (size_t)s * N;
+    if (N > 0 && pm[0] < 0) continue;                      // unmatched
+    bool ident = true;
+    for (int n = 0; n < N; ++n) {
+      const double c = hcos[(size_t)s * N + n];
+      ident = ident && pm[n] == n;
+      if (confusion) confusion[(size_t)n * N + pm[n]] += 1;
+      acc[t & 63] = acc[t & 63] + c; ++t;
+      if (mn_at < 0 || c < mn) { mn = c; mn_at = (int64_t)s * N + n; }
+    }
+    if (!ident) info->n_switched++;
+  }
+  for (int hh = 32; hh >= 1; hh >>= 1) for (int l = 0; l < hh; ++l) acc[l] = acc[l] + acc[l + hh];   // wave_tree64's order
+  info->mean_cosine = acc[0] / (double)((size_t)cnt[0] * (size_t)N);
+  info->min_cosine = mn; info->min_cosine_at = mn_at;
+  return 0;
+}
+int bnmf_relabel(bnmf_handle* h, int last_n, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine, int64_t* confusion,
+                 double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_relabel: null argument");
+  if (int rc = check_recorded(h, "bnmf_relabel")) return rc;
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_relabel: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  return relabel_impl(h, "bnmf_relabel", h->iter, last_n, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
+}
+int bnmf_relabel_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine,
+                    int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
+  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_relabel_at: null argument");
+  if (int rc = check_recorded(h, "bnmf_relabel_at")) return rc;
+  if (int rc = check_kept(h, "bnmf_relabel_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
+  return relabel_impl(h, "bnmf_relabel_at", end_iter, n_samples, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
 }
 
 // ---- measured ceilings for bench.py's roofline: Philox4x32-7 words per second (the count-allocation stream's generator) with

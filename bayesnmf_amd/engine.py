@@ -90,6 +90,12 @@ class BnmfAttrInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("_pad", C.c_int32), ("n_present", C.c_int64), ("min_load", C.c_double), ("total", C.c_double)]
 
 
+class BnmfRelabelInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
+                ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
+                ("min_cosine", C.c_double), ("min_cosine_at", C.c_int64)]
+
+
 ATTR_LOAD_ROWS = ["load_mean", "load_var", "share", "p_present"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
@@ -107,7 +113,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
-               "bnmf_attribution", "bnmf_attribution_at"]
+               "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at"]
 
 
 def lib():
@@ -164,6 +170,9 @@ def lib():
         L.bnmf_ppc_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, dp, C.POINTER(BnmfPpcInfo)]
         L.bnmf_attribution.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
         L.bnmf_attribution_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
+        lp = C.POINTER(C.c_int64)
+        L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
+        L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
         L.bnmf_version.restype = C.c_int
         _LIB = L
@@ -534,6 +543,43 @@ class Engine:
             for i, name in enumerate(MIX_ROWS):
                 out[name + "_P"] = oP[i].reshape((K, N), order="F")
                 out[name + "_E"] = oE[i].reshape((N, G), order="F")
+        return out
+
+    def relabel(self, last_n, used=None, end_iter=None, pivot_P=None, max_rounds=10, aligned=False):
+        """Label-switching correction over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_relabel / bnmf_relabel_at), on the device: every
+        sample's factors are permuted to the labels of a pivot (pivot_P, K x N; None = the newest used sample's P) so that the total
+        cosine is largest, and the pivot is iterated to the aligned mean for at most max_rounds rounds.  Returns the info fields, perm
+        (S x N int32: the label factor n of sample s receives; -1 = the sample is unmatched), cosine (S x N), confusion (N x N int64),
+        P_mean, P_var (K x N) and E_mean, E_var (N x G) of the aligned, renormalised samples; with aligned also aligned_P (S x K x N)
+        and aligned_E (S x N x G), the aligned samples themselves (NaN for an unmatched one)."""
+        K, G, N = self.K, self.G, self.N
+        ip = C.POINTER(C.c_int32)
+        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
+        if u is not None and u.size != last_n:
+            raise BnmfError(-2, f"relabel: used has {u.size} entries for {last_n} samples")
+        S = max(int(last_n) if u is None else int((u != 0).sum()), 0)
+        pv = None
+        if pivot_P is not None:
+            pv = np.asarray(pivot_P, dtype=np.float64)
+            if pv.shape != (K, N):
+                raise BnmfError(-2, f"relabel: pivot_P is {pv.shape}, not {(K, N)}")
+            pv = np.ascontiguousarray(pv.ravel(order="F"))
+        perm, cos, conf = np.empty((S, N), dtype=np.int32), np.empty((S, N)), np.empty((N, N), dtype=np.int64)
+        oP, oE = np.empty((2, K * N)), np.empty((2, N * G))
+        aP = np.empty((S, K * N)) if aligned else None
+        aE = np.empty((S, N * G)) if aligned else None
+        info = BnmfRelabelInfo()
+        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
+        _chk((lib().bnmf_relabel if end_iter is None else lib().bnmf_relabel_at)(
+            self._h, *rng, None if u is None else u.ctypes.data_as(ip), None if pv is None else _dp(pv), int(max_rounds), perm.ctypes.data_as(ip),
+            _dp(cos), conf.ctypes.data_as(C.POINTER(C.c_int64)), _dp(oP), _dp(oE), None if aP is None else _dp(aP),
+            None if aE is None else _dp(aE), C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in BnmfRelabelInfo._fields_ if name != "_pad"}
+        out.update(perm=perm, cosine=cos, confusion=conf, P_mean=oP[0].reshape((K, N), order="F"), P_var=oP[1].reshape((K, N), order="F"),
+                   E_mean=oE[0].reshape((N, G), order="F"), E_var=oE[1].reshape((N, G), order="F"))
+        if aligned:
+            out.update(aligned_P=aP.reshape((S, N, K)).transpose(0, 2, 1), aligned_E=aE.reshape((S, G, N)).transpose(0, 2, 1))
         return out
 
     def label_switching(self, iters, reference_P):

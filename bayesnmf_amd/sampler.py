@@ -479,6 +479,7 @@ class bayesNMF_sampler:
             self.get_MAP(final=True)
             self.log("Final MAP computed", verbosity=1)
         self._log_mixing()
+        self._log_relabelling()
         self._sync_state()
         self.log("Sampler done", verbosity=1)
         self.time["total"] = (time.time() - start) / 60.0
@@ -755,6 +756,55 @@ class bayesNMF_sampler:
         self.log(f"Mixing over {m['n_used']} samples: min ESS P {m['min_ess_P']:.1f} E {m['min_ess_E']:.1f} | max split R-hat P {m['max_rhat_P']:.4f} "
                  f"E {m['max_rhat_E']:.4f} | {m['n_low_ess']} ESS < 100 | {m['n_high_rhat']} R-hat > 1.01 | {m['n_const']} constant | "
                  f"{m['n_ran_out']} ran out of lags", verbosity=1)
+
+    def get_relabelling(self, end_iter=None, n_samples=None, idx="MAP_idx", pivot="MAP", max_rounds=10, aligned=False):
+        """Label-switching correction of the recorded samples, on the device (bnmf_relabel_at; not in the reference): over iterations
+        end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last MAP_over samples), restricted to `idx` ("MAP_idx": those
+        whose A equals the mode of the range; None: every sample; else a vector of recorded iterations), every sample's factors are
+        permuted to the labels of a pivot so that the total cosine between its signatures and the pivot's is largest, and the pivot
+        is iterated to the aligned mean (at most max_rounds rounds).  pivot: "MAP" — the MAP's P, the factors it dropped put back
+        from the last sample; "last" — the newest used sample's P; or a K x N matrix.
+        Returns Engine.relabel's dict over all N factors (perm: S x N, the label factor n of sample s receives, -1 for a sample that
+        could not be matched; cosine; confusion; P_mean, P_var, E_mean, E_var of the aligned, renormalised samples; rounds, converged,
+        n_switched, n_unmatched, mean_cosine, min_cosine, min_cosine_at; with aligned also aligned_P, aligned_E), plus P (K x kept) and
+        E (kept x G): the aligned means restricted to the MAP's kept factors, and keep_sigs, their indices."""
+        if not hasattr(self._chain, "relabel"):
+            raise ValueError("get_relabelling needs an engine that aligns its recorded samples (relabel); this engine_factory's cannot")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        K, N = self.dims["K"], self.dims["N"]
+        ks = np.asarray(self.MAP["keep_sigs"], dtype=int) if "keep_sigs" in self.MAP else np.arange(N)
+        if isinstance(pivot, str):
+            if pivot == "last":
+                piv = None
+            elif pivot == "MAP":
+                if "P" not in self.MAP:
+                    raise ValueError("get_relabelling(pivot = 'MAP') needs a MAP: call get_MAP first, or pass pivot = 'last' or a matrix")
+                piv = np.array(self._chain.get("P"), dtype=float)          # the dropped factors: the last sample's columns
+                MP = np.asarray(self.MAP["P"], dtype=float)
+                piv[:, ks] = MP if MP.shape[1] == len(ks) else MP[:, ks]
+            else:
+                raise ValueError("Parameter `pivot` must be 'MAP', 'last' or a K x N matrix")
+        else:
+            piv = np.asarray(pivot, dtype=float)
+            if piv.shape != (K, N):
+                raise ValueError(f"pivot is {piv.shape}, but P is {(K, N)}")
+        r = self._chain.relabel(n, used=used, pivot_P=piv, max_rounds=max_rounds, aligned=aligned, **kw)
+        out = dict(r)
+        out.update(P=r["P_mean"][:, ks], E=r["E_mean"][ks, :], keep_sigs=ks)
+        return out
+
+    def _log_relabelling(self):
+        """one line after the mixing line: whether the labels moved inside the range the summaries rest on"""
+        if not hasattr(self._chain, "relabel"):
+            return
+        try:
+            r = self.get_relabelling()
+        except Exception as ex:  # noqa: BLE001  (e.g. fewer than 2 samples share the mode of A)
+            self.log(f"Relabelling not computed: {ex}", verbosity=1)
+            return
+        self.log(f"Relabelling over {r['n_used']} samples: {r['rounds']} round{'' if r['rounds'] == 1 else 's'}"
+                 f"{'' if r['converged'] else ' (not converged)'} | {r['n_switched']} samples switched | {r['n_unmatched']} unmatched | "
+                 f"smallest cosine {r['min_cosine']:.4f}", verbosity=1)
 
     def label_switching(self, reference_P, reference_names=None, idx="all"):
         """The data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below: for every

@@ -309,6 +309,45 @@ int bnmf_attribution(bnmf_handle*, int last_n, const int32_t* used, double min_l
 int bnmf_attribution_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double min_load,
                         double* load, double* prob, double* series, bnmf_attr_info* info);
 
+/* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
+ * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
+ * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and
+ * iterates the pivot to the aligned mean.  All N factors take part, included or not, as in bnmf_label_switching.  Round r = 1, 2, ...:
+ *   pivot: K x N.  Round 1: pivot_P (column-major), or with NULL the newest used sample's P; later the aligned mean of the last round.
+ *   C_s[n][j] = dot / sqrt(nn * refnorm2[j]), dot = sum_k P_s[k,n] pivot[k,j], nn = sum_k P_s[k,n]^2, refnorm2[j] = sum_k pivot[k,j]^2: the
+ *     cosine of the raw P_s[, n] with pivot column j, the sums over k ascending from +0.0 (the operations bnmf_assign votes with).
+ *   perm[s][.] = the assignment n -> j that maximises sum_n C_s[n][perm[s][n]] (shortest augmenting paths with potentials, rows in order,
+ *     the lowest column among equal reduced costs): perm[s][n] is the label factor n of sample s receives; cosine[s][n] = C_s[n][perm[s][n]].
+ *   A sample without an assignment (a cosine that is not finite: a zero column of P_s) is unmatched: perm[s][.] = -1, cosine[s][.] = NaN, it
+ *     enters no sum and its aligned_* rows are NaN.  The others are the S' aligned samples, in order.  Fewer than 2 of them: BNMF_ESIZE.
+ *   x_s[k,n] = P_s[k,n] / cs_s[n], e_s[n,g] = E_s[n,g] * cs_s[n], cs_s = colSums(P_s): bnmf_map's renormalisation.  With inv_s the inverse of
+ *     perm[s][.], the aligned series of element (k, j) of P is x_s[k, inv_s(j)] and of element (j, g) of E e_s[inv_s(j), g], over the aligned
+ *     samples;  mean = canon(series) / S',  var = canon((series - mean)^2) / (S' - 1),  canon the canonical W = 64 sum of bnmf_mixing.
+ *   The next pivot is the aligned mean of P.  The rounds stop after the first in which no aligned sample's permutation differs from the round
+ *   before (round 1: from the identity) — converged = 1 — or after max_rounds.
+ * perm [S][N] and cosine [S][N] row-major, of the last round;  confusion [N][N] row-major: the aligned samples with perm[s][n] == j;
+ * P_out [BNMF_NREL][K*N], E_out [BNMF_NREL][N*G]: mean and variance, each row column-major as P and E;  aligned_P [S][K*N], aligned_E [S][N*G]:
+ * the aligned samples themselves (caller-sized: S times the matrix; they leave the device in batches of at most 256 MB).  Every output but
+ * info may be NULL.  info: mean_cosine = canon over the S' N final cosines in (s, n) order / (S' N), min_cosine the smallest of them and
+ * min_cosine_at = s * N + n its place (the first wins a tie).  Only + - * /, sqrt and comparisons in a fixed order: the same call gives
+ * the same bits, whatever the batches.  Read-only for the chain.
+ * bnmf_relabel_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_relabel(h, n, ...) is bnmf_relabel_at(h, iter, n, ...).  Refused before any device work: null info, a used[] value other than 0 / 1
+ * (the index named), max_rounds < 1 and a pivot_P with a NaN, an infinite value or an all-zero column (the column named) with BNMF_EINVAL,
+ * fewer than 2 used samples with BNMF_ESIZE, window = 0 or a poisoned handle with BNMF_ESTATE. */
+#define BNMF_NREL 2   /* rows of P_out / E_out: mean, variance (S' - 1 form) */
+typedef struct { int32_t n_used, n_aligned /* S' */, n_unmatched, rounds, converged /* the last round changed no permutation */,
+                 n_switched /* aligned samples whose final permutation is not the identity */, n_changed_last, _pad;
+                 double mean_cosine, min_cosine; int64_t min_cosine_at /* s * N + n */; } bnmf_relabel_info;
+int bnmf_relabel(bnmf_handle*, int last_n, const int32_t* used /* [last_n], NULL = all */,
+                 const double* pivot_P /* K x N column-major, NULL: the newest used sample's P */, int max_rounds,
+                 int32_t* perm /* [S][N] */, double* cosine /* [S][N] */, int64_t* confusion /* [N][N] row-major */,
+                 double* P_out /* [BNMF_NREL][K*N] */, double* E_out /* [BNMF_NREL][N*G] */,
+                 double* aligned_P /* [S][K*N] */, double* aligned_E /* [S][N*G] */, bnmf_relabel_info* info);
+int bnmf_relabel_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds,
+                    int32_t* perm, double* cosine, int64_t* confusion, double* P_out, double* E_out,
+                    double* aligned_P, double* aligned_E, bnmf_relabel_info* info);
+
 int bnmf_get_iter(bnmf_handle* h, int* iter);
 
 /* A chain's state in a file, and back (checkpoint / resume; the reference's save_object, saveRDS(self), R/bayesNMF_sampler.R:414-416).

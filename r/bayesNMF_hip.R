@@ -243,6 +243,49 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (prob) out$prob <- array(r$prob, c(K, N, G))
       out
     },
+    # Label-switching correction of the recorded samples, on the device (bnmf_relabel_at; not in the reference): over iterations
+    # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample's factors are permuted to the labels
+    # of a pivot so that the total cosine is largest, and the pivot is iterated to the aligned mean (at most max_rounds rounds).
+    # pivot: "MAP" (the MAP's P, the factors it dropped put back from the last sample), "last" (the newest used sample's P) or a K x N
+    # matrix.  list(perm (N x S: the label of every factor per used sample, NA = no assignment), cosine (N x S), confusion (N x N),
+    # P_mean, P_var (K x N), E_mean, E_var (N x G) over all N factors, P and E: the aligned means of the MAP's kept factors, n_used,
+    # n_aligned, n_unmatched, rounds, converged, n_switched, n_changed_last, mean_cosine, min_cosine, min_cosine_at), with aligned also
+    # aligned_P (K x N x S) and aligned_E (N x G x S)
+    get_relabelling = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                               idx = "MAP_idx", pivot = "MAP", max_rounds = 10, aligned = FALSE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      ks <- if (is.null(self$MAP$keep_sigs)) seq_len(N) else self$MAP$keep_sigs
+      if (is.character(pivot)) {
+        if (pivot == "last") piv <- NULL
+        else if (pivot == "MAP") {
+          piv <- self$params$P
+          piv[, ks] <- self$MAP$P
+        } else stop("Parameter `pivot` must be 'MAP', 'last' or a K x N matrix")
+      } else {
+        piv <- as.matrix(pivot)
+        if (!all(dim(piv) == c(K, N))) stop("pivot must be a K x N matrix")
+      }
+      if (!is.null(piv)) storage.mode(piv) <- "double"
+      r <- .Call("C_bnmf_relabel", self$handle, as.integer(end_iter), as.integer(n_samples), used, piv, as.integer(max_rounds),
+                 as.logical(aligned), c(K, G, N))
+      out <- r[c("n_used", "n_aligned", "n_unmatched", "rounds", "converged", "n_switched", "n_changed_last", "mean_cosine", "min_cosine",
+                 "min_cosine_at", "perm", "cosine", "confusion")]
+      out$P_mean <- matrix(r$P[, 1], K, N); out$P_var <- matrix(r$P[, 2], K, N)
+      out$E_mean <- matrix(r$E[, 1], N, G); out$E_var <- matrix(r$E[, 2], N, G)
+      out$P <- out$P_mean[, ks, drop = FALSE]; out$E <- out$E_mean[ks, , drop = FALSE]
+      if (aligned) { out$aligned_P <- array(r$aligned_P, c(K, N, ncol(r$perm))); out$aligned_E <- array(r$aligned_E, c(N, G, ncol(r$perm))) }
+      out
+    },
     # the data frame plot_label_switching (R/postprocessing_visualizations.R:598-669) builds before combine_below, on the device
     # (bnmf_label_switching): per recorded iteration in idx ("all": every kept sample) and latent factor, the reference signature
     # hungarian_assignment(keep_all_est = TRUE) gives it ("None": no partner), that cosine, and whether A includes the factor

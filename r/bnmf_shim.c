@@ -490,6 +490,82 @@ SEXP C_bnmf_attribution_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, S
   UNPROTECT(1);
   return out;
 }
+/* Label-switching correction over recorded samples on the device (bnmf_relabel / bnmf_relabel_at): C_bnmf_relabel(ptr, end_iter (integer,
+ * or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), pivot_P (K x N, or NULL = the newest used
+ * sample's P), max_rounds, want_aligned (logical), dims c(K,G,N)) -> list(n_used, n_aligned, n_unmatched, rounds, converged, n_switched,
+ * n_changed_last, mean_cosine, min_cosine, min_cosine_at (1-based position in perm as a double, 0 = none), perm (N x S: one column per used
+ * sample, the 1-based label of every factor, NA for a sample without an assignment), cosine (N x S), confusion (N x N: samples in which
+ * factor [row] received label [column]), P (K N x 2) and E (N G x 2): mean and variance of the aligned samples, each column laid out as P /
+ * E, aligned_P (K N x S) and aligned_E (N G x S) or NULL) over iterations end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_relabel_at: the same with end_iter required */
+/* the result list with its buffers allocated, the flags of used and the pivot; returned unprotected */
+static SEXP relabel_alloc(SEXP n_samples, SEXP used, SEXP pivot_P, SEXP want_aligned, SEXP dims, int32_t** u, const double** piv) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (pivot_P != R_NilValue && XLENGTH(pivot_P) != (R_xlen_t)d[0] * d[2])
+    Rf_error("bnmf: pivot_P has %ld entries, K x N = %d x %d are needed", (long)XLENGTH(pivot_P), d[0], d[2]);
+  *u = lgl_flags(used, n);
+  *piv = pivot_P == R_NilValue ? NULL : REAL(pivot_P);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_aligned", "n_unmatched", "rounds", "converged", "n_switched", "n_changed_last", "mean_cosine",
+                              "min_cosine", "min_cosine_at", "perm", "cosine", "confusion", "P", "E", "aligned_P", "aligned_E"};
+  SEXP out = PROTECT(named_list(17, nms));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(INTSXP, d[2], S));
+  SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, d[2], S));
+  SET_VECTOR_ELT(out, 12, Rf_allocMatrix(REALSXP, d[2], d[2]));
+  SET_VECTOR_ELT(out, 13, Rf_allocMatrix(REALSXP, d[0] * d[2], BNMF_NREL));
+  SET_VECTOR_ELT(out, 14, Rf_allocMatrix(REALSXP, d[2] * d[1], BNMF_NREL));
+  if (LOGICAL(want_aligned)[0] == TRUE) {
+    SET_VECTOR_ELT(out, 15, Rf_allocMatrix(REALSXP, d[0] * d[2], S));
+    SET_VECTOR_ELT(out, 16, Rf_allocMatrix(REALSXP, d[2] * d[1], S));
+  }
+  UNPROTECT(1);
+  return out;
+}
+static void relabel_finish(SEXP out, const int64_t* conf, SEXP dims, const bnmf_relabel_info* info) {
+  const int N = INTEGER(dims)[2];
+  const int v[7] = {info->n_used, info->n_aligned, info->n_unmatched, info->rounds, info->converged, info->n_switched, info->n_changed_last};
+  for (int i = 0; i < 7; ++i) SET_VECTOR_ELT(out, i, Rf_ScalarInteger(v[i]));
+  SET_VECTOR_ELT(out, 7, Rf_ScalarReal(info->mean_cosine)); SET_VECTOR_ELT(out, 8, Rf_ScalarReal(info->min_cosine));
+  SET_VECTOR_ELT(out, 9, Rf_ScalarReal((double)info->min_cosine_at + 1.0));   /* 1-based; 0 = none */
+  SEXP pm = VECTOR_ELT(out, 10);
+  int* a = INTEGER(pm);
+  for (R_xlen_t i = 0; i < XLENGTH(pm); ++i) a[i] = a[i] < 0 ? NA_INTEGER : a[i] + 1;
+  double* c = REAL(VECTOR_ELT(out, 12));
+  for (int n = 0; n < N; ++n) for (int j = 0; j < N; ++j) c[n + (size_t)N * j] = (double)conf[(size_t)n * N + j];
+}
+SEXP C_bnmf_relabel(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP pivot_P, SEXP max_rounds, SEXP want_aligned, SEXP dims) {
+  int32_t* u = NULL;
+  const double* piv = NULL;
+  SEXP out = PROTECT(relabel_alloc(n_samples, used, pivot_P, want_aligned, dims, &u, &piv));
+  const int N = INTEGER(dims)[2];
+  int64_t* conf = (int64_t*)R_alloc((size_t)N * N, sizeof(int64_t));
+  bnmf_relabel_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_relabel(get_handle(ptr), INTEGER(n_samples)[0], u, piv, INTEGER(max_rounds)[0], INTEGER(VECTOR_ELT(out, 10)), map_buf(out, 11), conf,
+                     map_buf(out, 13), map_buf(out, 14), map_buf(out, 15), map_buf(out, 16), &info));
+  else
+    chk(bnmf_relabel_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, piv, INTEGER(max_rounds)[0], INTEGER(VECTOR_ELT(out, 10)),
+                        map_buf(out, 11), conf, map_buf(out, 13), map_buf(out, 14), map_buf(out, 15), map_buf(out, 16), &info));
+  relabel_finish(out, conf, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_relabel_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP pivot_P, SEXP max_rounds, SEXP want_aligned, SEXP dims) {
+  int32_t* u = NULL;
+  const double* piv = NULL;
+  SEXP out = PROTECT(relabel_alloc(n_samples, used, pivot_P, want_aligned, dims, &u, &piv));
+  const int N = INTEGER(dims)[2];
+  int64_t* conf = (int64_t*)R_alloc((size_t)N * N, sizeof(int64_t));
+  bnmf_relabel_info info;
+  chk(bnmf_relabel_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, piv, INTEGER(max_rounds)[0], INTEGER(VECTOR_ELT(out, 10)),
+                      map_buf(out, 11), conf, map_buf(out, 13), map_buf(out, 14), map_buf(out, 15), map_buf(out, 16), &info));
+  relabel_finish(out, conf, dims, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* plot_label_switching's per-sample hungarian_assignment diagonal (R/postprocessing_visualizations.R:598-669):
  * C_bnmf_label_switching(ptr, iters (integer iteration numbers), reference_P (K x R), dims c(K,G,N)) ->
  * list(assigned N x n_iters (1-based column of reference_P, NA = "None"), cosine N x n_iters, included N x n_iters logical):
@@ -572,6 +648,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_mixing", (DL_FUNC)&C_bnmf_mixing, 7}, {"C_bnmf_mixing_at", (DL_FUNC)&C_bnmf_mixing_at, 7},
   {"C_bnmf_ppc", (DL_FUNC)&C_bnmf_ppc, 6}, {"C_bnmf_ppc_at", (DL_FUNC)&C_bnmf_ppc_at, 6},
   {"C_bnmf_attribution", (DL_FUNC)&C_bnmf_attribution, 7}, {"C_bnmf_attribution_at", (DL_FUNC)&C_bnmf_attribution_at, 7},
+  {"C_bnmf_relabel", (DL_FUNC)&C_bnmf_relabel, 8}, {"C_bnmf_relabel_at", (DL_FUNC)&C_bnmf_relabel_at, 8},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
