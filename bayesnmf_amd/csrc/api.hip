@@ -2032,7 +2032,8 @@ static double quantile7(std::vector<double> x, double prob) {
   const double hq = (x.size() - 1) * prob;
   const size_t j = (size_t)std::floor(hq);
   const double g = hq - (double)j;
-  return (1.0 - g) * x[j] + g * x[std::min(j + 1, x.size() - 1)];
+  const double a = x[j], b = x[std::min(j + 1, x.size() - 1)];
+  return a == b ? a : (1.0 - g) * a + g * b;              // k_map_quant's map_interp
 }
 
 // assign_signatures_ensemble_ over the last_n samples that end at iteration end_iter (checked by the caller)

@@ -958,6 +958,9 @@ BNMF_DEV void lane_sort(double* a, int n) {           // insertion sort of a[0],
     a[(j + 1) * 64] = x;
   }
 }
+// quantile type 7 between two neighbouring order statistics; equal neighbours give that value itself, as stats::quantile leaves it
+// ((1 - g) a + g a can round to a neighbour of a)
+BNMF_DEV double map_interp(double a, double b, double g) { return a == b ? a : (1.0 - g) * a + g * b; }
 template <int SIDE>
 __global__ __launch_bounds__(64) void k_map_stats(const double* ring, size_t len, int K, int N, const int* slots, int n_used,
                                                   const double* cs, int kt, int jlo, double glo, int jhi, double ghi,
@@ -971,7 +974,8 @@ __global__ __launch_bounds__(64) void k_map_stats(const double* ring, size_t len
   double* hi = (double*)smem + (size_t)kt * 64 + tid;   // hi[i * 64]: the kt largest so far
   int cnt = 0, lop = 0, hip = 0;
   double lov = 0.0, hiv = 0.0;                          // largest of the small set / smallest of the large set
-  double sum = 0.0;
+  double sum = 0.0, first = 0.0;
+  bool same = true;                                     // every sample so far holds the first one's value
   for (int s0 = 0; s0 < n_used; s0 += 8) {
     double v[8], c[8];
 #pragma unroll
@@ -985,6 +989,8 @@ __global__ __launch_bounds__(64) void k_map_stats(const double* ring, size_t len
       if (s0 + j >= n_used) break;
       const double x = SIDE ? v[j] * c[j] : v[j] / c[j];
       sum = sum + x;
+      if (s0 + j == 0) first = x;
+      same = same && x == first;
       if (kt == 0) continue;
       if (cnt < kt) {                                   // filling: both sets hold everything seen so far
         lo[cnt * 64] = x; hi[cnt * 64] = x;
@@ -1007,13 +1013,13 @@ __global__ __launch_bounds__(64) void k_map_stats(const double* ring, size_t len
       }
     }
   }
-  mean[e] = sum / (double)n_used;
+  mean[e] = same ? first : sum / (double)n_used;        // a constant series: the constant itself, not its sum / n rounded
   if (kt) {
     lane_sort(lo, cnt); lane_sort(hi, cnt);
     const int base = n_used - cnt;                      // hi[i] is order statistic base + i
     const int jl1 = min(jlo + 1, n_used - 1), jh1 = min(jhi + 1, n_used - 1);
-    lower[e] = (1.0 - glo) * lo[jlo * 64] + glo * lo[jl1 * 64];
-    upper[e] = (1.0 - ghi) * hi[(jhi - base) * 64] + ghi * hi[(jh1 - base) * 64];
+    lower[e] = map_interp(lo[jlo * 64], lo[jl1 * 64], glo);
+    upper[e] = map_interp(hi[(jhi - base) * 64], hi[(jh1 - base) * 64], ghi);
   }
 }
 // ---- k_map_quant: the credible bounds of get_MAP_ (R/utils.R:269-284, quantile type 7) by a wave per element (round 4) ----
@@ -1118,6 +1124,8 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
   static_assert(EW >= 1 && NIOK, "a wave takes whole elements");
   // the means (get_MAP_: the sum in sample order, as k_map_stats forms it) while the samples still lie in sample order: lane q of the
   // wave walks element q of the wave — 2 lanes for a few microseconds against a second pass over the window by another kernel
+  // (the mean is stored at the end: a series whose smallest and largest order statistic are equal has that value as its mean)
+  double msum = 0.0;
   if (mean && lane < EW) {
     const double* x = tile + (size_t)(wave * EW + lane) * S;
     double sum = 0.0;
@@ -1130,8 +1138,7 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
       for (int b = 0; b < 8; ++b) sum = sum + v[b];
     }
     for (; s0 < n_used; ++s0) sum = sum + x[s0];
-    const size_t e = e0 + (size_t)(wave * EW + lane);
-    if (e < len) mean[e] = sum / (double)n_used;
+    msum = sum;
   }
   double* col[EW];
 #pragma unroll
@@ -1147,7 +1154,7 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
   wave_lds_fence();
   // the column heads (lov / hiv), the values behind them (lon / hin: loaded when the head moves, a whole reduction before they are
   // needed) and their positions; no branch in a step, so that the chains of a wave interleave
-  double x0[EW] = {}, x1[EW] = {}, y0[EW] = {}, y1[EW] = {}, lov[EW], hiv[EW], lon[EW], hin[EW];
+  double x0[EW] = {}, x1[EW] = {}, y0[EW] = {}, y1[EW] = {}, gmin[EW] = {}, gmax[EW] = {}, lov[EW], hiv[EW], lon[EW], hin[EW];
   int pl[EW], ph[EW];
   const double INF = __builtin_inf();
 #pragma unroll
@@ -1163,6 +1170,7 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
 #pragma unroll
     for (int q = 0; q < EW; ++q) {
       const double m = wave_min_all(lov[q]);
+      if (c == 0) gmin[q] = m;
       if (c == jlo) x0[q] = m;
       if (c == jl1) x1[q] = m;
       const unsigned long long eq = __builtin_amdgcn_ballot_w64(lov[q] == m);
@@ -1178,6 +1186,7 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
 #pragma unroll
     for (int q = 0; q < EW; ++q) {
       const double m = wave_max_all(hiv[q]);
+      if (c == 0) gmax[q] = m;
       if (os == jh1) y1[q] = m;
       if (os == jhi) y0[q] = m;
       const unsigned long long eq = __builtin_amdgcn_ballot_w64(hiv[q] == m);
@@ -1192,13 +1201,18 @@ __global__ __launch_bounds__(MQ_T) void k_map_quant(const double* ring, size_t l
   for (int c = 0; c < nboth; ++c) { low_step(c); high_step(c); }
   for (int c = nboth; c < nlo; ++c) low_step(c);
   for (int c = nboth; c < nhi; ++c) high_step(c);
+#pragma unroll
+  for (int q = 0; q < EW; ++q) {                          // lane q holds the sum of element q of the wave
+    const size_t e = e0 + (size_t)(wave * EW + q);
+    if (mean && lane == q && e < len) mean[e] = gmin[q] == gmax[q] ? gmin[q] : msum / (double)n_used;
+  }
   if (lane == 0) {
 #pragma unroll
     for (int q = 0; q < EW; ++q) {
       const size_t e = e0 + (size_t)(wave * EW + q);
       if (e < len) {
-        lower[e] = (1.0 - glo) * x0[q] + glo * x1[q];
-        upper[e] = (1.0 - ghi) * y0[q] + ghi * y1[q];
+        lower[e] = map_interp(x0[q], x1[q], glo);
+        upper[e] = map_interp(y0[q], y1[q], ghi);
       }
     }
   }

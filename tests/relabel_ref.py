@@ -12,10 +12,12 @@ INFO = ("n_used", "n_aligned", "n_unmatched", "rounds", "converged", "n_switched
 
 
 def cosine_matrix(P, pivot):
-    """C[n][j] = dot / sqrt(nn * refnorm2[j]) of the raw P (K x N) against the pivot (K x N): k ascending from +0.0 (k_ref_cosine)"""
+    """C[n][j] = dot / sqrt(nn * refnorm2[j]) of the raw P (K x N) against the pivot (K x N; or a catalogue, K x R: bnmf_assign's cosines,
+    tests/map_ref.py): k ascending from +0.0 (k_ref_cosine; refnorm2 as the host sums it)"""
     P, pivot = np.asarray(P, dtype=np.float64), np.asarray(pivot, dtype=np.float64)
     K, N = P.shape
-    dot, nn, rn2 = np.zeros((N, N)), np.zeros(N), np.zeros(N)
+    R = pivot.shape[1]
+    dot, nn, rn2 = np.zeros((N, R)), np.zeros(N), np.zeros(R)
     for k in range(K):
         dot = dot + P[k][:, None] * pivot[k][None, :]
         nn = nn + P[k] * P[k]
@@ -25,11 +27,12 @@ def cosine_matrix(P, pivot):
 
 
 def hungarian(C):
-    """The assignment row -> column of the square C that maximises the total (cost = -C): rows inserted in order, shortest augmenting
-    path with potentials, strict comparisons over ascending columns, so the lowest column wins among equals.  None when no finite
-    reduced cost is left (a NaN in C)."""
+    """The assignment row -> column of C (n rows <= m columns) that maximises the total (cost = -C): rows inserted in order, shortest
+    augmenting path with potentials, strict comparisons over ascending columns, so the lowest column wins among equals.  None when no
+    finite reduced cost is left (a NaN in C).  With more rows than columns hungarian_wave takes the transposed matrix: so does the caller."""
     C = np.asarray(C, dtype=np.float64)
-    n = m = C.shape[0]
+    n, m = C.shape
+    assert n <= m
     u, v = np.zeros(n + 1), np.zeros(m + 1)
     p, way = np.zeros(m + 1, dtype=int), np.zeros(m + 1, dtype=int)
     for i in range(1, n + 1):
@@ -67,14 +70,16 @@ def hungarian(C):
             p[j0] = p[jn]
             j0 = jn
     perm = np.empty(n, dtype=np.int32)
-    perm[p[1:] - 1] = np.arange(m, dtype=np.int32)
+    matched = p[1:] > 0                                        # (m - n columns stay free)
+    perm[p[1:][matched] - 1] = np.arange(m, dtype=np.int32)[matched]
     return perm
 
 
 def hungarian_scalar(C):
     """the same algorithm with a Python loop over the columns (the text-book form): the vectorised one above must agree with it"""
     C = np.asarray(C, dtype=np.float64)
-    n = m = C.shape[0]
+    n, m = C.shape
+    assert n <= m
     u, v, p, way = [0.0] * (n + 1), [0.0] * (m + 1), [0] * (m + 1), [0] * (m + 1)
     for i in range(1, n + 1):
         p[0] = i
@@ -106,7 +111,8 @@ def hungarian_scalar(C):
             j0 = jn
     perm = np.empty(n, dtype=np.int32)
     for j in range(1, m + 1):
-        perm[p[j] - 1] = j - 1
+        if p[j]:
+            perm[p[j] - 1] = j - 1
     return perm
 
 
