@@ -1,7 +1,7 @@
 // bayesnmf_amd/csrc/api.hip — C ABI of libbnmf.so (include/bnmf.h) over the gfx950 kernels.
 // Host side: device memory, three HIP streams per handle, the constructor draws (R/bayesNMF_sampler.R:232-257).  The launch sequencing of
-// the sweep (:273-285) is in sweep.h, the allocation kernels' static schedules in zplan.h, the state file in state_io.h: all three are
-// included here (one translation unit).  There is no CPU path.
+// the sweep (:273-285) is in sweep.h, the allocation kernels' static schedules in zplan.h, the posterior calls on a recorded range in
+// posterior.h, the state file in state_io.h: all four are included here (one translation unit).  There is no CPU path.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <chrono>
@@ -209,6 +209,8 @@ struct Mh : MhPlan {
   int32_t* dMt = nullptr; double* dMtf = nullptr;   // the [G][K] transpose of the data: counts, or fp64 on a Normal handle
 };
 
+struct Scratch { unsigned char* p = nullptr; size_t bytes = 0; };   // a device block and its size (scratch_reserve, posterior.h)
+
 struct bnmf_handle {
   bnmf_config cfg{};
   int device = 0;
@@ -257,16 +259,10 @@ struct bnmf_handle {
   ZWavePlan zw; ZTile zt; ZSort zs; ZStep zp; Rank rank; Mh mh;
   hipEvent_t ev[2 * BNMF_NKERNEL]{};
   bool have_ev = false;
-  double* dMap = nullptr; size_t map_words = 0;   // scratch of bnmf_map (grown on demand)
-  double* dWaic = nullptr; size_t waic_words = 0; // scratch of bnmf_waic (grown on demand): column sums, cell values, slot list
-  double* dAttr = nullptr; size_t attr_words = 0; // scratch of bnmf_attribution (grown on demand): a batch of a_s and u, the running statistics, load rows, series, prob, slot list
-  double* dPpc = nullptr; size_t ppc_words = 0;   // scratch of bnmf_ppc (grown on demand): T[4][S][G], column rows, series, cell values, slot and iteration lists
-  double* dMix = nullptr; size_t mix_words = 0;   // scratch of bnmf_mixing (grown on demand): colSums(P) per sample, both outputs, slot list
-  unsigned char* dRel = nullptr; size_t rel_bytes = 0;   // scratch of bnmf_relabel (grown on demand): pivot, colSums(P), permutations, cosines, both outputs, lists, a batch of aligned samples
+  Scratch scratch;                     // of the posterior calls (posterior.h): grown on demand, carved by one call at a time, nothing in it outlives a call
   int devlock_fd = -1;                 // the device's lock file (<BNMF_LOCKDIR or /tmp>/bnmf_dev_<PCI bus id>.lock): the device gate's rule across the PROCESSES that share the device
   int devgate_fd = -1;                 // ... and its turnstile (.gate): a process that wants the device exclusively holds it while it waits, new sharers queue behind it
   bool devlock_off = false;            // BNMF_DEVLOCK=0: the caller vouches that no other process uses the device
-  unsigned char* dAsg = nullptr; size_t asg_bytes = 0;   // scratch of bnmf_assign (grown on demand): catalogue, norms, cosines, slot / signature lists
   unsigned* dFlags = nullptr;                     // [0] counter, [1] flag of the E-side hyper sweep; [2], [3] of P part + Esum; [5], [6] P inside k_draw;
                                                   // [8], [9] P-side sweep on its own stream
   int* hErr = nullptr; int* dErr = nullptr;       // time-out words of the bounded in-kernel waits, in mapped host memory (read without a copy):
@@ -1419,12 +1415,16 @@ int bnmf_profile(bnmf_handle* h, int n_iter, int converged, double* out_ms) {
   for (int k = 0; k < BNMF_NKERNEL; ++k) out_ms[k] = tm.cnt[k] ? tm.acc[k] / tm.cnt[k] : 0.0;
   return 0;
 }
+}  // extern "C"
+
+#include "posterior.h"   // the posterior calls on a recorded range and the layer they share
+
+extern "C" {
+
 int bnmf_window(bnmf_handle* h, int id, int last_n, double* out) {
   if (!h || !out) return fail(BNMF_EINVAL, "bnmf_window: null argument");
-  const int W = h->cfg.window;
-  if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_window: the handle timed out inside a kernel; its state is invalid");
-  if (W <= 0) return fail(BNMF_ESTATE, "bnmf_window: the handle was created with window = 0");
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_window: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
+  if (int rc = check_recorded(h, "bnmf_window")) return rc;
+  if (int rc = check_last(h, "bnmf_window", last_n)) return rc;
   if (id < 0 || id >= BNMF_ID_MAX) return fail(BNMF_EINVAL, "bnmf_window: unknown id %d", id);
   if (id == BNMF_Z) {
     if (!h->zring && !h->zs.dRecRing) return fail(BNMF_EUNSET, "bnmf_window: Z is not kept per sample (needs save_Z, a window, and the window's samples within BNMF_ZRING_GB)");
@@ -1445,479 +1445,12 @@ int bnmf_window(bnmf_handle* h, int id, int last_n, double* out) {
     }
     return 0;
   }
-  const Arr& a = h->arr[id];
-  const size_t len = id_len(h, id);
-  if (!a.ring || len == 0) return fail(BNMF_EUNSET, "bnmf_window: id %d is not recorded for this model", id);
+  if (!h->arr[id].ring || id_len(h, id) == 0) return fail(BNMF_EUNSET, "bnmf_window: id %d is not recorded for this model", id);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  // sample `it` lives in slot (it-1) % (W+1): the last_n samples, oldest first, are at most two contiguous runs of the ring
-  const size_t C = (size_t)h->wcap, s0 = (size_t)(h->iter - last_n) % C;
-  const size_t n1 = (s0 + (size_t)last_n <= C) ? (size_t)last_n : C - s0;
-  HIPCHK(hipMemcpy(out, a.ring + s0 * len, n1 * len * sizeof(double), hipMemcpyDeviceToHost));
-  if (n1 < (size_t)last_n) HIPCHK(hipMemcpy(out + n1 * len, a.ring, ((size_t)last_n - n1) * len * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return ring_read(h, id, h->iter, last_n, out);
 }
 
-
-// copy the `last_n` consecutive samples that end at iteration `end_iter` (oldest first) of a ring to the host: at most two contiguous runs
-static int ring_read(const bnmf_handle* h, int id, int end_iter, int last_n, double* out) {
-  const Arr& a = h->arr[id];
-  const size_t len = id_len(h, id), C = (size_t)h->wcap, s0 = (size_t)(end_iter - last_n) % C;
-  const size_t n1 = (s0 + (size_t)last_n <= C) ? (size_t)last_n : C - s0;
-  HIPCHK(hipMemcpy(out, a.ring + s0 * len, n1 * len * sizeof(double), hipMemcpyDeviceToHost));
-  if (n1 < (size_t)last_n) HIPCHK(hipMemcpy(out + n1 * len, a.ring, ((size_t)last_n - n1) * len * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// Iterations first..last must be recorded and still kept: [max(1, iter - window + 1), iter] (the ring holds window + 1 slots, the
-// slot ahead of the oldest kept sample belongs to the iteration in flight).
-static int check_kept(const bnmf_handle* h, const char* fn, long long first, long long last) {
-  const int lo = std::max(1, h->iter - h->cfg.window + 1);
-  if (first > last || first < lo || last > h->iter)
-    return fail(BNMF_ESIZE, "%s: iterations %lld..%lld requested but only iterations %d..%d are kept (window = %d, iter = %d)", fn, first, last, lo,
-                h->iter, h->cfg.window, h->iter);
-  return 0;
-}
-static int check_recorded(const bnmf_handle* h, const char* fn) {
-  if (h->poisoned) return fail(BNMF_ESTATE, "%s: the handle timed out inside a kernel; its state is invalid", fn);
-  if (h->cfg.window <= 0) return fail(BNMF_ESTATE, "%s: the handle was created with window = 0", fn);
-  return 0;
-}
-
-// get_MAP_ over the last_n samples that end at iteration end_iter (checked by the caller)
-static int map_impl(bnmf_handle* h, int end_iter, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
-                    double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
-  if (ci >= 1.0) return fail(BNMF_EINVAL, "bnmf_map: credible_interval must be below 1");
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
-  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G;
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "bnmf_map: nothing recorded yet");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  // i. mode of A (get_mode): patterns as strings, most frequent first, ties in alphabetical order
-  std::vector<double> Aw((size_t)last_n * N);
-  if (int rc = ring_read(h, BNMF_A, end_iter, last_n, Aw.data())) return rc;
-  std::vector<std::string> keys(last_n, std::string(N, '0'));
-  std::map<std::string, int> tab;
-  for (int s = 0; s < last_n; ++s) { for (int n = 0; n < N; ++n) if (Aw[(size_t)s * N + n] != 0.0) keys[s][n] = '1'; tab[keys[s]]++; }
-  std::vector<std::pair<std::string, int>> ord(tab.begin(), tab.end());        // std::map iterates alphabetically
-  std::stable_sort(ord.begin(), ord.end(), [](const auto& a, const auto& b) { return a.second > b.second; });
-  const std::string& mode = ord[0].first;
-  info->n_patterns = (int)ord.size();
-  for (int i = 0; i < 5; ++i) {
-    info->top_counts[i] = i < (int)ord.size() ? ord[i].second : 0;
-    if (top_A) for (int n = 0; n < N; ++n) top_A[(size_t)i * N + n] = i < (int)ord.size() ? (ord[i].first[n] == '1' ? 1.0 : 0.0) : std::nan("");
-  }
-  std::vector<int> slots;
-  for (int s = 0; s < last_n; ++s) {
-    const bool u = keys[s] == mode;
-    if (used) used[s] = u ? 1 : 0;
-    if (u) slots.push_back((int)((size_t)(end_iter - last_n + s) % (size_t)h->wcap));
-  }
-  const int nu = (int)slots.size();
-  info->n_used = nu; info->_pad = 0;
-  std::vector<double> Am(N);
-  for (int n = 0; n < N; ++n) Am[n] = A_mode[n] = mode[n] == '1' ? 1.0 : 0.0;
-  // ii-iii. renormalised means (and quantiles) on the device
-  const bool want_ci = ci > 0.0 && (P_lower || P_upper || E_lower || E_upper);
-  int kt = 0, jlo = 0, jhi = 0; double glo = 0.0, ghi = 0.0;
-  if (want_ci) {                                    // quantile type 7: h = (n-1) p, j = floor(h), g = h - j
-    const double plo = 0.5 - ci / 2.0, phi = 0.5 + ci / 2.0;
-    const double hl = (nu - 1) * plo, hh = (nu - 1) * phi;
-    jlo = (int)std::floor(hl); glo = hl - jlo; jhi = (int)std::floor(hh); ghi = hh - jhi;
-    kt = std::min(nu, std::max(jlo + 2, nu - jhi));
-  }
-  // the bounds by sorting (k_map_quant) when the samples of 8 elements fit the LDS; else by the kt smallest / largest per lane
-  int qS = 0;
-  if (want_ci) { qS = ((nu + 63) / 64) * 64; if (qS > 2048) qS = 0; }
-  if (want_ci && !qS && (size_t)kt * 2 * 64 * sizeof(double) > 160 * 1024)
-    return fail(BNMF_EINVAL, "bnmf_map: credible_interval %.3g over %d samples needs %d order statistics per element (device limit 160): take the window with bnmf_window", ci, nu, kt);
-  const size_t words = (size_t)nu * N + 3 * (lenP + lenE) + 2 * (size_t)G + N + ((size_t)nu + 1) / 2 + 8;
-  if (words > h->map_words) { HIPCHK(hfree(h, h->dMap)); HIPCHK(hmalloc(h, &h->dMap, words * sizeof(double))); h->map_words = words; }
-  double* cs = h->dMap; double* mP = cs + (size_t)nu * N; double* loP = mP + lenP; double* hiP = loP + lenP;
-  double* mE = hiP + lenP; double* loE = mE + lenE; double* hiE = loE + lenE;
-  double* colsse = hiE + lenE; double* colkl = colsse + G; double* dA = colkl + G; int* dslots = (int*)(dA + N);
-  HIPCHK(hipMemcpyAsync(dslots, slots.data(), nu * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dA, Am.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_map_colsum, dim3(nu, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
-  if (!qS) {                                              // means (and, beyond 2,048 samples, the bounds) by a lane per element
-    const size_t lds = (size_t)kt * 2 * 64 * sizeof(double);
-    if (lds > 64 * 1024) {
-      HIPCHK(hipFuncSetAttribute((const void*)k_map_stats<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)k_map_stats<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    hipLaunchKernelGGL(k_map_stats<0>, dim3((unsigned)((lenP + 63) / 64)), dim3(64), lds, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N,
-                       (const int*)dslots, nu, (const double*)cs, kt, jlo, glo, jhi, ghi, mP, loP, hiP);
-    hipLaunchKernelGGL(k_map_stats<1>, dim3((unsigned)((lenE + 63) / 64)), dim3(64), lds, h->stream, (const double*)h->arr[BNMF_E].ring, lenE, K, N,
-                       (const int*)dslots, nu, (const double*)cs, kt, jlo, glo, jhi, ghi, mE, loE, hiE);
-  }
-  if (qS) {
-    const bool r16 = qS <= 1024;                           // 16 or 32 samples per lane column
-    const size_t qS2 = r16 ? 1024 : 2048, qlds = qS2 * MQ_E * sizeof(double) + qS2 * sizeof(int);
-    auto go = [&](auto kern, const double* ring, size_t len, double* mn, double* lo, double* hi) {
-      if (qlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qlds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)((len + MQ_E - 1) / MQ_E)), dim3(MQ_T), qlds, h->stream, ring, len, K, N, (const int*)dslots, nu,
-                         (const double*)cs, jlo, glo, jhi, ghi, mn, lo, hi);
-      return 0;
-    };
-    if (r16) { if (int rc = go(k_map_quant<0, 16>, h->arr[BNMF_P].ring, lenP, mP, loP, hiP)) return rc; if (int rc = go(k_map_quant<1, 16>, h->arr[BNMF_E].ring, lenE, mE, loE, hiE)) return rc; }
-    else { if (int rc = go(k_map_quant<0, 32>, h->arr[BNMF_P].ring, lenP, mP, loP, hiP)) return rc; if (int rc = go(k_map_quant<1, 32>, h->arr[BNMF_E].ring, lenE, mE, loE, hiE)) return rc; }
-  }
-  if (h->dMf) hipLaunchKernelGGL(k_map_fit<double>, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const double*)h->dMf, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
-  else hipLaunchKernelGGL(k_map_fit<int32_t>, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
-  HIPCHK(hipGetLastError());
-  if (P_mean) HIPCHK(hipMemcpyAsync(P_mean, mP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (E_mean) HIPCHK(hipMemcpyAsync(E_mean, mE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (want_ci) {
-    if (P_lower) HIPCHK(hipMemcpyAsync(P_lower, loP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (P_upper) HIPCHK(hipMemcpyAsync(P_upper, hiP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (E_lower) HIPCHK(hipMemcpyAsync(E_lower, loE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (E_upper) HIPCHK(hipMemcpyAsync(E_upper, hiE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  std::vector<double> col(2 * (size_t)G);
-  HIPCHK(hipMemcpyAsync(col.data(), colsse, 2 * (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  double sse = 0.0, kl = 0.0;
-  for (int g = 0; g < G; ++g) { sse += col[g]; kl += col[(size_t)G + g]; }
-  info->rmse = std::sqrt(sse / ((double)K * (double)G));
-  info->kl = kl;
-  return 0;
-}
-int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
-             double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
-  if (!h || !A_mode || !info) return fail(BNMF_EINVAL, "bnmf_map: null argument");
-  if (int rc = check_recorded(h, "bnmf_map")) return rc;
-  const int W = h->cfg.window;
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_map: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return map_impl(h, h->iter, last_n, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
-}
-int bnmf_map_at(bnmf_handle* h, int end_iter, int n_samples, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
-                double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
-  if (!h || !A_mode || !info) return fail(BNMF_EINVAL, "bnmf_map_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_map_at")) return rc;
-  if (int rc = check_kept(h, "bnmf_map_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return map_impl(h, end_iter, n_samples, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
-}
-
-// WAIC over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller): k_waic
-// (waic.h) leaves the per-column sums; the totals are their sequential sums over g, as map_impl sums colsse.
-static int waic_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
-  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
-  std::vector<int> slots;
-  for (int s = 0; s < n_samples; ++s) {
-    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
-    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
-  }
-  const int S = (int)slots.size();
-  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the log-likelihood needs at least 2", fn, S, S == 1 ? "" : "s");
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
-    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  const size_t KG = (size_t)K * G, ncol = (size_t)WA_NCOL * G;
-  const size_t words = ncol + (cell ? 2 * KG : 0) + ((size_t)S + 1) / 2 + 8;
-  if (words > h->waic_words) { HIPCHK(hfree(h, h->dWaic)); HIPCHK(hmalloc(h, &h->dWaic, words * sizeof(double))); h->waic_words = words; }
-  double* dcol = h->dWaic; double* dcell = cell ? dcol + ncol : nullptr; int* dslots = (int*)(dcol + ncol + (cell ? 2 * KG : 0));
-  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  WaicArgs a{};
-  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr;
-  a.M = h->dM; a.Mf = h->dMf; a.lgfact = h->dLut; a.slots = dslots; a.col = dcol; a.cell = dcell;
-  a.lenP = (size_t)K * N; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.S = S; a.maxM = h->maxM;
-  size_t lds = waic_lds_bytes(N);
-  a.stage = lds <= 160 * 1024 ? 1 : 0;
-  if (!a.stage) lds = 0;
-  const void* kern = normal ? (const void*)k_waic<true> : (const void*)k_waic<false>;
-  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  const dim3 grid((unsigned)((G + WA_GC - 1) / WA_GC)), block(WA_T);
-  if (normal) hipLaunchKernelGGL(k_waic<true>, grid, block, lds, h->stream, a);
-  else hipLaunchKernelGGL(k_waic<false>, grid, block, lds, h->stream, a);
-  HIPCHK(hipGetLastError());
-  std::vector<double> hc(ncol);
-  HIPCHK(hipMemcpyAsync(hc.data(), dcol, ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (cell) HIPCHK(hipMemcpyAsync(cell, dcell, 2 * KG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  double t[WA_NCOL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int q = 0; q < WA_NCOL; ++q) for (int g = 0; g < G; ++g) t[q] += hc[(size_t)q * G + g];
-  if (col) for (int q = 0; q < 3; ++q) std::memcpy(col + (size_t)q * G, hc.data() + (size_t)q * G, (size_t)G * sizeof(double));
-  const double n = (double)K * (double)G;
-  double var = n > 1.0 ? (t[4] - t[3] * (t[3] / n)) / (n - 1.0) : 0.0;   // variance of elpd over the cells from its two sums
-  if (!(var > 0.0)) var = 0.0;
-  info->n_used = S; info->n_high_var = (int32_t)t[5];
-  info->lppd = t[0]; info->p_waic = t[1]; info->mean_loglik = t[2]; info->elpd_waic = t[3]; info->waic = -2.0 * t[3];
-  info->se_elpd = std::sqrt(n * var);
-  return 0;
-}
-int bnmf_waic(bnmf_handle* h, int last_n, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_waic: null argument");
-  if (int rc = check_recorded(h, "bnmf_waic")) return rc;
-  const int W = h->cfg.window;
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_waic: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return waic_impl(h, "bnmf_waic", h->iter, last_n, used, col, cell, info);
-}
-int bnmf_waic_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_waic_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_waic_at")) return rc;
-  if (int rc = check_kept(h, "bnmf_waic_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return waic_impl(h, "bnmf_waic_at", end_iter, n_samples, used, col, cell, info);
-}
-
-// Posterior predictive checks over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the
-// caller): k_ppc leaves T[4][S][G], the tail cells per column and the cell values, k_ppc_totals the per-column rows and the series
-// (ppc.h); the info fields are sequential scans of the series on the host.
-static_assert(PP_NCOL == BNMF_PPC_NCOL && PP_VAR == (uint32_t)BNMF_V_YREP, "ppc.h and bnmf.h disagree");
-static int ppc_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series,
-                    bnmf_ppc_info* info) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
-  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
-  std::vector<int> sl;                              // slots, then iterations
-  for (int s = 0; s < n_samples; ++s) {
-    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
-    if (!used || used[s]) sl.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
-  }
-  const int S = (int)sl.size();
-  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the replicates needs at least 2", fn, S, S == 1 ? "" : "s");
-  for (int s = 0; s < n_samples; ++s) if (!used || used[s]) sl.push_back(end_iter - n_samples + 1 + s);
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
-    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  const size_t KG = (size_t)K * G, SG = (size_t)S * G, ncol = (size_t)(PP_NCOL + 1) * G;
-  const size_t words = 4 * SG + ncol + 4 * (size_t)S + (cell ? 4 * KG : 0) + (size_t)S + 8;
-  if (words > h->ppc_words) {
-    HIPCHK(hfree(h, h->dPpc)); h->dPpc = nullptr; h->ppc_words = 0;
-    HIPCHK(hmalloc(h, &h->dPpc, words * sizeof(double))); h->ppc_words = words;
-  }
-  double* dT = h->dPpc; double* dcol = dT + 4 * SG; double* dser = dcol + ncol; double* dcell = cell ? dser + 4 * (size_t)S : nullptr;
-  int* dsl = (int*)(dser + 4 * (size_t)S + (cell ? 4 * KG : 0));
-  HIPCHK(hipMemcpyAsync(dsl, sl.data(), 2 * (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  PpcArgs a{};
-  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr;
-  a.M = h->dM; a.Mf = h->dMf; a.slots = dsl; a.iters = dsl + S; a.T = dT; a.tail = dcol + (size_t)PP_NCOL * G; a.cell = dcell;
-  a.lenP = (size_t)K * N; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.S = S;
-  a.k0 = (uint32_t)h->cfg.seed; a.k1 = (uint32_t)(h->cfg.seed >> 32) ^ h->cfg.chain_id;
-  size_t lds = ppc_lds_bytes(N);
-  a.stage = lds <= 160 * 1024 ? 1 : 0;
-  if (!a.stage) lds = 0;
-  const void* kern = normal ? (const void*)k_ppc<true> : (const void*)k_ppc<false>;
-  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  const dim3 grid((unsigned)((G + PP_GC - 1) / PP_GC)), block(PP_T);
-  const dim3 tgrid((unsigned)(4 * S + (G + PP_TT - 1) / PP_TT)), tblock(PP_TT);
-  if (normal) {
-    hipLaunchKernelGGL(k_ppc<true>, grid, block, lds, h->stream, a);
-    hipLaunchKernelGGL(k_ppc_totals<true>, tgrid, tblock, 0, h->stream, (const double*)dT, S, G, dser, dcol);
-  } else {
-    hipLaunchKernelGGL(k_ppc<false>, grid, block, lds, h->stream, a);
-    hipLaunchKernelGGL(k_ppc_totals<false>, tgrid, tblock, 0, h->stream, (const double*)dT, S, G, dser, dcol);
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<double> hs(4 * (size_t)S), ht((size_t)G);
-  HIPCHK(hipMemcpyAsync(hs.data(), dser, 4 * (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(ht.data(), dcol + (size_t)PP_NCOL * G, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (col) HIPCHK(hipMemcpyAsync(col, dcol, (size_t)PP_NCOL * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (cell) HIPCHK(hipMemcpyAsync(cell, dcell, 4 * KG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (series) std::memcpy(series, hs.data(), 4 * (size_t)S * sizeof(double));
-  double t[4] = {0.0, 0.0, 0.0, 0.0}; int n1 = 0, n2 = 0;
-  for (int s = 0; s < S; ++s) {
-    for (int q = 0; q < 4; ++q) t[q] += hs[(size_t)q * S + s];
-    n1 += hs[(size_t)S + s] >= hs[s] ? 1 : 0; n2 += hs[3 * (size_t)S + s] >= hs[2 * (size_t)S + s] ? 1 : 0;
-  }
-  int64_t nt = 0;
-  for (int g = 0; g < G; ++g) nt += (int64_t)ht[g];
-  info->n_used = S; info->n_tail_cells = nt;
-  info->p_T1 = (double)n1 / (double)S; info->p_T2 = (double)n2 / (double)S;
-  info->mean_T1_obs = t[0] / (double)S; info->mean_T1_rep = t[1] / (double)S; info->mean_T2_obs = t[2] / (double)S; info->mean_T2_rep = t[3] / (double)S;
-  return 0;
-}
-int bnmf_ppc(bnmf_handle* h, int last_n, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_ppc: null argument");
-  if (int rc = check_recorded(h, "bnmf_ppc")) return rc;
-  const int W = h->cfg.window;
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_ppc: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return ppc_impl(h, "bnmf_ppc", h->iter, last_n, used, col, cell, series, info);
-}
-int bnmf_ppc_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_ppc_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_ppc_at")) return rc;
-  if (int rc = check_kept(h, "bnmf_ppc_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return ppc_impl(h, "bnmf_ppc_at", end_iter, n_samples, used, col, cell, series, info);
-}
-
-// Signature attribution over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller):
-// per batch of samples k_attr leaves a_s[n,g] in the scratch, k_attr_share the reciprocal column totals, k_attr_stats continues the
-// per-(n, g) statistics and reduces the series (attribution.h); total and n_present are sequential scans on the host.
-static_assert(AT_NLOAD == BNMF_ATTR_NLOAD, "attribution.h and bnmf.h disagree");
-static constexpr size_t ATTR_SCRATCH_CAP = (size_t)256 << 20;   // bytes of a_s and u per batch
-static int attr_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, double min_load, double* load, double* prob,
-                     double* series, bnmf_attr_info* info) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
-  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
-  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
-  std::vector<int> slots;
-  for (int s = 0; s < n_samples; ++s) {
-    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
-    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
-  }
-  const int S = (int)slots.size();
-  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the loads needs at least 2", fn, S, S == 1 ? "" : "s");
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  const size_t NG = (size_t)N * G, KNG = (size_t)K * NG, per = (NG + (size_t)G) * sizeof(double);   // scratch bytes of one sample
-  long long want = (long long)std::max<size_t>(1, ATTR_SCRATCH_CAP / per);
-  if (const char* e = getenv("BNMF_ATTR_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
-  const int Sb = (int)std::min<long long>(want, S);
-  const size_t words = (size_t)Sb * (NG + G) + 2 * AT_NLOAD * NG + (size_t)S * N + (prob ? KNG : 0) + ((size_t)S + 1) / 2 + 8;
-  if (words > h->attr_words) {
-    HIPCHK(hfree(h, h->dAttr)); h->dAttr = nullptr; h->attr_words = 0;
-    HIPCHK(hmalloc(h, &h->dAttr, words * sizeof(double))); h->attr_words = words;
-  }
-  double* dscr = h->dAttr; double* du = dscr + (size_t)Sb * NG; double* dst = du + (size_t)Sb * G; double* dload = dst + AT_NLOAD * NG;
-  double* dser = dload + AT_NLOAD * NG; double* dprob = prob ? dser + (size_t)S * N : nullptr;
-  int* dslots = (int*)(dser + (size_t)S * N + (prob ? KNG : 0));
-  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  AttrArgs a{};
-  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.M = h->dM; a.scr = dscr; a.prob = dprob;
-  a.lenP = (size_t)K * N; a.lenE = NG; a.K = K; a.N = N; a.G = G; a.S = S;
-  size_t lds = attr_lds_bytes(N);
-  a.stage = lds <= 160 * 1024 ? 1 : 0;
-  if (!a.stage) lds = 0;
-  const void* kern = normal ? (prob ? (const void*)k_attr<true, true> : (const void*)k_attr<true, false>)
-                            : (prob ? (const void*)k_attr<false, true> : (const void*)k_attr<false, false>);
-  if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  const dim3 grid((unsigned)((G + AT_GC - 1) / AT_GC)), block(AT_T);
-  for (int s0 = 0; s0 < S; s0 += Sb) {
-    const int nb = std::min(Sb, S - s0), last = s0 + nb == S ? 1 : 0;
-    a.slots = dslots + s0; a.Sb = nb; a.first = s0 == 0 ? 1 : 0; a.last = last;
-    if (normal) { if (prob) hipLaunchKernelGGL((k_attr<true, true>), grid, block, lds, h->stream, a); else hipLaunchKernelGGL((k_attr<true, false>), grid, block, lds, h->stream, a); }
-    else { if (prob) hipLaunchKernelGGL((k_attr<false, true>), grid, block, lds, h->stream, a); else hipLaunchKernelGGL((k_attr<false, false>), grid, block, lds, h->stream, a); }
-    const size_t nsg = (size_t)nb * G;
-    hipLaunchKernelGGL(k_attr_share, dim3((unsigned)((nsg + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, G, du);
-    hipLaunchKernelGGL(k_attr_stats, dim3((unsigned)((size_t)nb * N + (NG + AT_TT - 1) / AT_TT)), dim3(AT_TT), 0, h->stream, (const double*)dscr,
-                       (const double*)du, nb, N, G, S, s0, last, min_load, dst, dser, dload);
-    HIPCHK(hipGetLastError());
-  }
-  std::vector<double> hs((size_t)S * N), hp(NG);
-  HIPCHK(hipMemcpyAsync(hs.data(), dser, (size_t)S * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(hp.data(), dload + 3 * NG, NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (load) HIPCHK(hipMemcpyAsync(load, dload, AT_NLOAD * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (prob) HIPCHK(hipMemcpyAsync(prob, dprob, KNG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (series) std::memcpy(series, hs.data(), (size_t)S * N * sizeof(double));
-  double t = 0.0;
-  for (size_t i = 0; i < (size_t)S * N; ++i) t += hs[i];
-  int64_t np = 0;
-  for (size_t i = 0; i < NG; ++i) np += hp[i] >= 0.5 ? 1 : 0;
-  info->n_used = S; info->_pad = 0; info->n_present = np; info->min_load = min_load; info->total = t / (double)S;
-  return 0;
-}
-int bnmf_attribution(bnmf_handle* h, int last_n, const int32_t* used, double min_load, double* load, double* prob, double* series, bnmf_attr_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_attribution: null argument");
-  if (int rc = check_recorded(h, "bnmf_attribution")) return rc;
-  const int W = h->cfg.window;
-  if (last_n < 1 || last_n > W || last_n > h->iter)
-    return fail(BNMF_ESIZE, "bnmf_attribution: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return attr_impl(h, "bnmf_attribution", h->iter, last_n, used, min_load, load, prob, series, info);
-}
-int bnmf_attribution_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double min_load, double* load, double* prob, double* series,
-                        bnmf_attr_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_attribution_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_attribution_at")) return rc;
-  if (int rc = check_kept(h, "bnmf_attribution_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return attr_impl(h, "bnmf_attribution_at", end_iter, n_samples, used, min_load, load, prob, series, info);
-}
-
-// Mixing diagnostics over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the caller):
-// k_map_colsum, then k_mixing (mixing.h) per side leaves the per-element rows; the summary is a sequential scan of them on
-// the host, element index ascending, P then E, over the factors that keep[] flags.
-static_assert(BNMF_NMIX == MX_NROW, "bnmf.h and mixing.h disagree on the rows of the per-element output");
-static int mixing_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out,
-                       double* E_out, bnmf_mixing_info* info) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
-  std::vector<int> slots;
-  for (int s = 0; s < n_samples; ++s) {
-    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
-    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
-  }
-  if (keep) for (int n = 0; n < N; ++n) if (keep[n] != 0 && keep[n] != 1) return fail(BNMF_EINVAL, "%s: keep[%d] = %d is neither 0 nor 1", fn, n, (int)keep[n]);
-  const int S = (int)slots.size();
-  if (S < 4) return fail(BNMF_ESIZE, "%s: %d used sample%s, split R-hat needs at least 4 (a variance in each half)", fn, S, S == 1 ? "" : "s");
-  static_assert(BNMF_MIXING_MAX_SAMPLES * (sizeof(double) + sizeof(int)) <= MX_LDS, "one element's series and the slot list fit the LDS");
-  if (S > BNMF_MIXING_MAX_SAMPLES)
-    return fail(BNMF_ESIZE, "%s: %d used samples but at most %d fit the device's 160 KB of LDS per element: thin the range with used[]", fn, S, BNMF_MIXING_MAX_SAMPLES);
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G;
-  const size_t words = (size_t)S * N + MX_NROW * (lenP + lenE) + ((size_t)S + 1) / 2 + 8;
-  if (words > h->mix_words) { HIPCHK(hfree(h, h->dMix)); HIPCHK(hmalloc(h, &h->dMix, words * sizeof(double))); h->mix_words = words; }
-  double* cs = h->dMix; double* oP = cs + (size_t)S * N; double* oE = oP + MX_NROW * lenP; int* dslots = (int*)(oE + MX_NROW * lenE);
-  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
-  const int epw = mixing_elements_per_group(S);
-  const size_t lds = mixing_lds_bytes(epw, S);
-  const double tau_min = 1.0 / std::log10((double)S);
-  if (lds > 64 * 1024) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_mixing<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MX_LDS));
-    HIPCHK(hipFuncSetAttribute((const void*)k_mixing<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MX_LDS));
-  }
-  hipLaunchKernelGGL(k_mixing<0>, dim3((unsigned)((lenP + epw - 1) / epw)), dim3(64 * epw), lds, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N,
-                     (const int*)dslots, S, (const double*)cs, tau_min, epw, oP);
-  hipLaunchKernelGGL(k_mixing<1>, dim3((unsigned)((lenE + epw - 1) / epw)), dim3(64 * epw), lds, h->stream, (const double*)h->arr[BNMF_E].ring, lenE, K, N,
-                     (const int*)dslots, S, (const double*)cs, tau_min, epw, oE);
-  HIPCHK(hipGetLastError());
-  std::vector<double> hP, hE;                       // the summary needs the rows whether or not the caller wants them
-  if (!P_out) { hP.resize(MX_NROW * lenP); P_out = hP.data(); }
-  if (!E_out) { hE.resize(MX_NROW * lenE); E_out = hE.data(); }
-  HIPCHK(hipMemcpyAsync(P_out, oP, MX_NROW * lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(E_out, oE, MX_NROW * lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  std::memset(info, 0, sizeof *info);
-  info->n_used = S; info->n_half = S / 2;
-  const double nan = std::nan("");
-  info->min_ess_P = info->min_ess_E = info->max_rhat_P = info->max_rhat_E = nan;
-  info->min_ess_P_at = info->min_ess_E_at = info->max_rhat_P_at = info->max_rhat_E_at = -1;
-  auto scan = [&](const double* o, size_t len, bool sideE, double& mn, int64_t& mn_at, double& mx, int64_t& mx_at) {
-    for (size_t e = 0; e < len; ++e) {
-      const int n = sideE ? (int)(e % (size_t)N) : (int)(e / (size_t)K);
-      if (keep && !keep[n]) continue;
-      const double ess = o[2 * len + e], rhat = o[4 * len + e];
-      if (o[5 * len + e] == 0.0) info->n_const++;
-      if (o[6 * len + e] == 1.0) info->n_ran_out++;
-      if (ess < BNMF_MIXING_LOW_ESS) info->n_low_ess++;
-      if (rhat > BNMF_MIXING_HIGH_RHAT) info->n_high_rhat++;
-      if (!std::isnan(ess) && (mn_at < 0 || ess < mn)) { mn = ess; mn_at = (int64_t)e; }
-      if (!std::isnan(rhat) && (mx_at < 0 || rhat > mx)) { mx = rhat; mx_at = (int64_t)e; }
-    }
-  };
-  scan(P_out, lenP, false, info->min_ess_P, info->min_ess_P_at, info->max_rhat_P, info->max_rhat_P_at);
-  scan(E_out, lenE, true, info->min_ess_E, info->min_ess_E_at, info->max_rhat_E, info->max_rhat_E_at);
-  return 0;
-}
-int bnmf_mixing(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* keep, double* P_out, double* E_out, bnmf_mixing_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_mixing: null argument");
-  if (int rc = check_recorded(h, "bnmf_mixing")) return rc;
-  const int W = h->cfg.window;
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_mixing: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return mixing_impl(h, "bnmf_mixing", h->iter, last_n, used, keep, P_out, E_out, info);
-}
-int bnmf_mixing_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out, double* E_out,
-                   bnmf_mixing_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_mixing_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_mixing_at")) return rc;
-  if (int rc = check_kept(h, "bnmf_mixing_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return mixing_impl(h, "bnmf_mixing_at", end_iter, n_samples, used, keep, P_out, E_out, info);
-}
 
 // One MAP check (R/bayesNMF_sampler.R:297-321): get_MAP_ over the last min(MAP_over, iter) samples on the device, the
 // state$MAP_metrics row (update_MAP_metrics_, R/utils.R:356-397) and check_convergence_ (R/convergence.R:60-154) into mr.
@@ -2025,382 +1558,6 @@ int bnmf_run_post_warmup(bnmf_handle* h, const bnmf_convergence_control* cc, bnm
     *n_checks += 1; st->n_checks += 1;
   }
   return 0;
-}
-
-static double quantile7(std::vector<double> x, double prob) {
-  std::sort(x.begin(), x.end());
-  const double hq = (x.size() - 1) * prob;
-  const size_t j = (size_t)std::floor(hq);
-  const double g = hq - (double)j;
-  const double a = x[j], b = x[std::min(j + 1, x.size() - 1)];
-  return a == b ? a : (1.0 - g) * a + g * b;              // k_map_quant's map_interp
-}
-
-// assign_signatures_ensemble_ over the last_n samples that end at iteration end_iter (checked by the caller)
-static int assign_impl(bnmf_handle* h, int end_iter, int last_n, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
-                       double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
-  if (R < 1) return fail(BNMF_EINVAL, "bnmf_assign: empty reference");
-  const int K = h->cfg.K, N = h->cfg.N;
-  std::vector<int> slots, sig;
-  for (int s = 0; s < last_n; ++s) if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - last_n + s) % (size_t)h->wcap));
-  for (int n = 0; n < N; ++n) if (!keep || keep[n]) sig.push_back(n);
-  const int nu = (int)slots.size(), nk = (int)sig.size();
-  for (int i = 0; i < N * R; ++i) votes[i] = 0.0;
-  for (int n = 0; n < N; ++n) { assigned[n] = -1; if (MAP_cosine) MAP_cosine[n] = std::nan(""); if (lower) lower[n] = std::nan(""); if (upper) upper[n] = std::nan(""); }
-  if (nu == 0 || nk == 0) return 0;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  std::vector<double> refT((size_t)K * R), rn2(R, 0.0);
-  for (int j = 0; j < R; ++j) for (int k = 0; k < K; ++k) { const double v = ref[k + (size_t)K * j]; refT[(size_t)k * R + j] = v; rn2[j] += v * v; }
-  const size_t nout = (size_t)nu * nk * R;
-  // one scratch allocation per handle, grown on demand (the ensemble assignment is called once per result, but BIC sweeps call it per rank)
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t oRef = 0, oN2 = oRef + up(refT.size() * 8), oOut = oN2 + up((size_t)R * 8), oSl = oOut + up(nout * 8), oSig = oSl + up((size_t)nu * sizeof(int)),
-               oCol = oSig + up((size_t)nk * sizeof(int)), need = oCol + up((size_t)nu * std::min(nk, R) * sizeof(int32_t));
-  if (need > h->asg_bytes) {
-    HIPCHK(hfree(h, h->dAsg)); h->asg_bytes = 0;
-    HIPCHK(hmalloc(h, &h->dAsg, need));
-    h->asg_bytes = need;
-  }
-  double *dRef = (double*)(h->dAsg + oRef), *dN2 = (double*)(h->dAsg + oN2), *dOut = (double*)(h->dAsg + oOut);
-  int *dSl = (int*)(h->dAsg + oSl), *dSig = (int*)(h->dAsg + oSig);
-  int32_t* dCol = (int32_t*)(h->dAsg + oCol);
-  HIPCHK(hipMemcpy(dRef, refT.data(), refT.size() * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dN2, rn2.data(), R * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dSl, slots.data(), nu * sizeof(int), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dSig, sig.data(), nk * sizeof(int), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_ref_cosine, dim3(nu, nk), dim3(128), 0, h->stream, (const double*)h->arr[BNMF_P].ring, (size_t)K * N, K, (const int*)dSl,
-                     (const int*)dSig, nk, (const double*)dRef, (const double*)dN2, R, dOut);
-  HIPCHK(hipGetLastError());
-  // one Hungarian assignment per sample (maximise the total cosine), one wave each; with more signatures than references the
-  // references are the rows
-  const bool tr = nk > R;
-  const int nrow = tr ? R : nk, ncol = tr ? nk : R;
-  const size_t hung_lds = (size_t)(ncol + 1) * (16 + 12) + (size_t)(nrow + 1) * 8;
-  if (hung_lds > 160 * 1024) return fail(BNMF_ESIZE, "bnmf_assign: %d x %d assignment problem exceeds the LDS of one workgroup", nrow, ncol);
-  HIPCHK(hipFuncSetAttribute((const void*)k_hungarian, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hung_lds));
-  HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)nu * nrow * sizeof(int32_t), h->stream));
-  hipLaunchKernelGGL(k_hungarian, dim3(nu), dim3(64), hung_lds, h->stream, (const double*)dOut, nk, R, tr ? 1 : 0, dCol);
-  HIPCHK(hipGetLastError());
-  std::vector<double> cosv(nout);
-  std::vector<int32_t> col((size_t)nu * nrow);
-  HIPCHK(hipMemcpyAsync(cosv.data(), dOut, nout * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(col.data(), dCol, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  // the cosine of a chosen pair is its vote; the votes are summed in sample order
-  for (int s = 0; s < nu; ++s) {
-    const double* c = cosv.data() + (size_t)s * nk * R;
-    const int32_t* a = col.data() + (size_t)s * nrow;
-    for (int r = 0; r < nrow; ++r) if (a[r] < 0 || a[r] >= ncol) return fail(BNMF_ESTATE, "bnmf_assign: sample %d has no assignment (a cosine is not finite)", s);
-    if (!tr) for (int i = 0; i < nk; ++i) votes[sig[i] + (size_t)N * a[i]] += c[(size_t)i * R + a[i]];
-    else for (int j = 0; j < R; ++j) votes[sig[a[j]] + (size_t)N * j] += c[(size_t)a[j] * R + j];
-  }
-  for (int i = 0; i < nk; ++i) {                           // which.max(prop_votes): first maximum
-    const int n = sig[i];
-    int best = -1; double bv = 0.0;
-    for (int j = 0; j < R; ++j) if (votes[n + (size_t)N * j] > bv) { bv = votes[n + (size_t)N * j]; best = j; }
-    assigned[n] = best;
-    if (best < 0) continue;
-    if (MAP_P && MAP_cosine) {
-      double dot = 0.0, nn = 0.0;
-      for (int k = 0; k < K; ++k) { const double p = MAP_P[k + (size_t)K * n]; dot += p * ref[k + (size_t)K * best]; nn += p * p; }
-      MAP_cosine[n] = dot / std::sqrt(nn * rn2[best]);
-    }
-    if (ci > 0.0 && ci < 1.0 && (lower || upper)) {
-      std::vector<double> x(nu);
-      for (int s = 0; s < nu; ++s) x[s] = cosv[((size_t)s * nk + i) * R + best];
-      if (lower) lower[n] = quantile7(x, (1.0 - ci) / 2.0);
-      if (upper) upper[n] = quantile7(x, 1.0 - (1.0 - ci) / 2.0);
-    }
-  }
-  return 0;
-}
-int bnmf_assign(bnmf_handle* h, int last_n, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
-                double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
-  if (!h || !ref || !votes || !assigned) return fail(BNMF_EINVAL, "bnmf_assign: null argument");
-  const int W = h->cfg.window;
-  if (h->poisoned) return fail(BNMF_ESTATE, "bnmf_assign: the handle timed out inside a kernel; its state is invalid");
-  if (W <= 0 || !h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign: no recorded samples (window = 0)");
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_assign: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return assign_impl(h, h->iter, last_n, used, ref, R, keep, MAP_P, ci, votes, assigned, MAP_cosine, lower, upper);
-}
-int bnmf_assign_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
-                   double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
-  if (!h || !ref || !votes || !assigned) return fail(BNMF_EINVAL, "bnmf_assign_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_assign_at")) return rc;
-  if (!h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign_at: nothing recorded yet");
-  if (int rc = check_kept(h, "bnmf_assign_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return assign_impl(h, end_iter, n_samples, used, ref, R, keep, MAP_P, ci, votes, assigned, MAP_cosine, lower, upper);
-}
-
-// plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:
-// 598-669) over the recorded iterations iters[]: k_label_switch, one wave per sample with the cosine matrix in the LDS; past the LDS,
-// k_ref_cosine + k_hungarian (what bnmf_assign runs) over chunks of samples whose cosines stay within LS_CHUNK_BYTES, then k_label_gather.
-static const size_t LS_CHUNK_BYTES = (size_t)256 << 20;
-int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, const double* ref, int R, int32_t* assigned, double* cosine,
-                         int32_t* included) {
-  if (!h || !iters || !ref || !assigned || !cosine) return fail(BNMF_EINVAL, "bnmf_label_switching: null argument");
-  if (int rc = check_recorded(h, "bnmf_label_switching")) return rc;
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "bnmf_label_switching: nothing recorded yet");
-  if (n_iters < 0) return fail(BNMF_EINVAL, "bnmf_label_switching: n_iters < 0");
-  if (R < 1) return fail(BNMF_EINVAL, "bnmf_label_switching: empty reference");
-  const int K = h->cfg.K, N = h->cfg.N;
-  std::vector<int> slots(n_iters);
-  for (int i = 0; i < n_iters; ++i) {
-    if (int rc = check_kept(h, "bnmf_label_switching", iters[i], iters[i])) return rc;
-    slots[i] = (int)((size_t)(iters[i] - 1) % (size_t)h->wcap);
-  }
-  if (n_iters == 0) return 0;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  std::vector<double> refT((size_t)K * R), rn2(R, 0.0);                 // as bnmf_assign: the catalogue row-major [k][j], its squared norms
-  for (int j = 0; j < R; ++j) for (int k = 0; k < K; ++k) { const double v = ref[k + (size_t)K * j]; refT[(size_t)k * R + j] = v; rn2[j] += v * v; }
-  const int tr = N > R ? 1 : 0, nrow = tr ? R : N, ncol = tr ? N : R;
-  const size_t hung_lds = (size_t)(ncol + 1) * (16 + 12) + (size_t)(nrow + 1) * 8;
-  const size_t ls_lds = (size_t)N * R * sizeof(double) + hung_lds;
-  const bool fused = ls_lds <= 160 * 1024;
-  if (!fused && hung_lds > 160 * 1024) return fail(BNMF_ESIZE, "bnmf_label_switching: %d x %d assignment problem exceeds the LDS of one workgroup", nrow, ncol);
-  const size_t per = (size_t)N * R * sizeof(double);
-  const int chunk = fused ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)n_iters, LS_CHUNK_BYTES / per));
-  const size_t out_n = (size_t)n_iters * N;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t oRef = 0, oN2 = oRef + up(refT.size() * 8), oSl = oN2 + up((size_t)R * 8), oAs = oSl + up((size_t)n_iters * sizeof(int)),
-               oCs = oAs + up(out_n * sizeof(int32_t)), oInc = oCs + up(out_n * sizeof(double)), oSig = oInc + up(out_n * sizeof(int32_t)),
-               oCos = oSig + up((size_t)N * sizeof(int)), oCol = oCos + up((size_t)chunk * per),
-               need = oCol + up((size_t)chunk * nrow * sizeof(int32_t));
-  if (need > h->asg_bytes) {                                             // bnmf_assign's scratch, grown on demand
-    HIPCHK(hfree(h, h->dAsg)); h->asg_bytes = 0;
-    HIPCHK(hmalloc(h, &h->dAsg, need));
-    h->asg_bytes = need;
-  }
-  double *dRef = (double*)(h->dAsg + oRef), *dN2 = (double*)(h->dAsg + oN2), *dCs = (double*)(h->dAsg + oCs);
-  int *dSl = (int*)(h->dAsg + oSl), *dSig = (int*)(h->dAsg + oSig);
-  int32_t *dAs = (int32_t*)(h->dAsg + oAs), *dInc = (int32_t*)(h->dAsg + oInc);
-  HIPCHK(hipMemcpy(dRef, refT.data(), refT.size() * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dN2, rn2.data(), R * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dSl, slots.data(), (size_t)n_iters * sizeof(int), hipMemcpyHostToDevice));
-  const double* ringP = h->arr[BNMF_P].ring;
-  const double* ringA = h->arr[BNMF_A].ring;
-  if (fused) {
-    if (ls_lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_label_switch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls_lds));
-    hipLaunchKernelGGL(k_label_switch, dim3(n_iters), dim3(64), ls_lds, h->stream, ringP, ringA, K, N, (const int*)dSl, (const double*)dRef,
-                       (const double*)dN2, R, dAs, dCs, dInc);
-    HIPCHK(hipGetLastError());
-  } else {
-    std::vector<int> sig(N);
-    for (int n = 0; n < N; ++n) sig[n] = n;
-    HIPCHK(hipMemcpy(dSig, sig.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
-    double* dCos = (double*)(h->dAsg + oCos);
-    int32_t* dCol = (int32_t*)(h->dAsg + oCol);
-    HIPCHK(hipFuncSetAttribute((const void*)k_hungarian, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hung_lds));
-    for (int s0 = 0; s0 < n_iters; s0 += chunk) {
-      const int ns = std::min(chunk, n_iters - s0);
-      hipLaunchKernelGGL(k_ref_cosine, dim3(ns, N), dim3(128), 0, h->stream, ringP, (size_t)K * N, K, (const int*)dSl + s0, (const int*)dSig, N,
-                         (const double*)dRef, (const double*)dN2, R, dCos);
-      HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)ns * nrow * sizeof(int32_t), h->stream));
-      hipLaunchKernelGGL(k_hungarian, dim3(ns), dim3(64), hung_lds, h->stream, (const double*)dCos, N, R, tr, dCol);
-      hipLaunchKernelGGL(k_label_gather, dim3((ns + 63) / 64), dim3(64), 0, h->stream, (const double*)dCos, (const int32_t*)dCol, N, R, ns, ringA,
-                         (const int*)dSl + s0, dAs + (size_t)s0 * N, dCs + (size_t)s0 * N, dInc + (size_t)s0 * N);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  HIPCHK(hipMemcpyAsync(assigned, dAs, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(cosine, dCs, out_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (included) HIPCHK(hipMemcpyAsync(included, dInc, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < n_iters; ++i)
-    if (assigned[(size_t)i * N] == -2 && N > 0) return fail(BNMF_ESTATE, "bnmf_label_switching: iteration %d has no assignment (a cosine is not finite)", iters[i]);
-  return 0;
-}
-
-// Label-switching correction over the samples flagged in used[n_samples] of the range that ends at iteration end_iter (checked by the
-// caller): per round k_rl_pivot, the matching (k_rl_match, or past the LDS k_ref_cosine + k_hungarian + k_rl_finish over chunks of samples),
-// k_rl_compact, then the two counts come to the host; between rounds k_rl_accum leaves the next pivot, after the last round the aligned
-// mean and variance of both sides (relabel.h).  confusion and the summary are sequential scans on the host.
-static_assert(BNMF_NREL == RL_NROW, "bnmf.h and relabel.h disagree on the rows of the output");
-static constexpr size_t REL_SCRATCH_CAP = (size_t)256 << 20;    // bytes of aligned samples per batch
-static int relabel_impl(bnmf_handle* h, const char* fn, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds,
-                        int32_t* perm, double* cosine, int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E,
-                        bnmf_relabel_info* info) {
-  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
-  std::vector<int> slots;
-  for (int s = 0; s < n_samples; ++s) {
-    if (used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
-    if (!used || used[s]) slots.push_back((int)((size_t)(end_iter - n_samples + s) % (size_t)h->wcap));
-  }
-  if (max_rounds < 1) return fail(BNMF_EINVAL, "%s: max_rounds = %d, at least 1 round is needed", fn, max_rounds);
-  if (pivot_P)
-    for (int j = 0; j < N; ++j) {
-      bool zero = true;
-      for (int k = 0; k < K; ++k) {
-        const double v = pivot_P[(size_t)k + (size_t)K * j];
-        if (!std::isfinite(v)) return fail(BNMF_EINVAL, "%s: column %d of pivot_P holds a value that is not finite (row %d)", fn, j, k);
-        zero = zero && v == 0.0;
-      }
-      if (zero) return fail(BNMF_EINVAL, "%s: column %d of pivot_P is all zero: it has no cosine", fn, j);
-    }
-  const int S = (int)slots.size();
-  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, an aligned variance needs at least 2", fn, S, S == 1 ? "" : "s");
-  const size_t hung_lds = relabel_hung_lds(N), match_lds = relabel_match_lds(N);
-  const bool fused = match_lds <= RL_LDS;
-  if (!fused && hung_lds > RL_LDS) return fail(BNMF_ESIZE, "%s: the %d x %d assignment problem exceeds the LDS of one workgroup", fn, N, N);
-  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipStreamSynchronize(h->side));
-  HIPCHK(hipStreamSynchronize(h->side2));
-  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G, SN = (size_t)S * N, per = (size_t)N * N * sizeof(double);
-  const int chunk = fused ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)S, LS_CHUNK_BYTES / per));
-  // the aligned samples leave in batches of whole samples, P then E through the same scratch
-  const int bP = aligned_P ? (int)std::min<size_t>({(size_t)S, (size_t)65535, std::max<size_t>(1, REL_SCRATCH_CAP / (lenP * sizeof(double)))}) : 0;
-  const int bE = aligned_E ? (int)std::min<size_t>({(size_t)S, (size_t)65535, std::max<size_t>(1, REL_SCRATCH_CAP / (lenE * sizeof(double)))}) : 0;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t oRef = 0, oN2 = oRef + up(lenP * 8), oPiv = oN2 + up((size_t)N * 8), oCs = oPiv + up(lenP * 8), oOP = oCs + up(SN * 8),
-               oOE = oOP + up(RL_NROW * lenP * 8), oCos = oOE + up(RL_NROW * lenE * 8), oPerm = oCos + up(SN * 8), oInv = oPerm + up(SN * 4),
-               oFlag = oInv + up(SN * 4), oAl = oFlag + up((size_t)S * 4), oSl = oAl + up((size_t)S * 4), oCnt = oSl + up((size_t)S * 4),
-               oSig = oCnt + up(16), oCv = oSig + up((size_t)N * 4), oCol = oCv + up((size_t)chunk * per),
-               oBat = oCol + up((size_t)chunk * N * 4), need = oBat + up(std::max((size_t)bP * lenP, (size_t)bE * lenE) * 8);
-  if (need > h->rel_bytes) {
-    HIPCHK(hfree(h, h->dRel)); h->rel_bytes = 0;
-    HIPCHK(hmalloc(h, &h->dRel, need));
-    h->rel_bytes = need;
-  }
-  unsigned char* b = h->dRel;
-  double *dRef = (double*)(b + oRef), *dN2 = (double*)(b + oN2), *dPiv = (double*)(b + oPiv), *cs = (double*)(b + oCs), *oP = (double*)(b + oOP),
-         *oE = (double*)(b + oOE), *dCs = (double*)(b + oCos), *dCv = (double*)(b + oCv), *dBat = (double*)(b + oBat);
-  int32_t *dPerm = (int32_t*)(b + oPerm), *dInv = (int32_t*)(b + oInv), *dFlag = (int32_t*)(b + oFlag), *dCol = (int32_t*)(b + oCol);
-  int *dAl = (int*)(b + oAl), *dSl = (int*)(b + oSl), *dCnt = (int*)(b + oCnt), *dSig = (int*)(b + oSig);
-  const double* ringP = h->arr[BNMF_P].ring;
-  const double* ringE = h->arr[BNMF_E].ring;
-  HIPCHK(hipMemcpyAsync(dSl, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (pivot_P) HIPCHK(hipMemcpyAsync(dPiv, pivot_P, lenP * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (!fused) {
-    std::vector<int> sig(N);
-    for (int n = 0; n < N; ++n) sig[n] = n;
-    HIPCHK(hipMemcpy(dSig, sig.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipFuncSetAttribute((const void*)k_hungarian, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hung_lds));
-  } else if (match_lds > 64 * 1024) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_rl_match, hipFuncAttributeMaxDynamicSharedMemorySize, (int)match_lds));
-  }
-  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, ringP, lenP, K, N, (const int*)dSl, cs);
-  const size_t tab = relabel_tab_bytes(S, N);
-  const bool stage = tab <= RL_TAB_LDS;
-  if (stage && tab > 64 * 1024) {
-    HIPCHK(hipFuncSetAttribute((const void*)k_rl_accum<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RL_TAB_LDS));
-    HIPCHK(hipFuncSetAttribute((const void*)k_rl_accum<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RL_TAB_LDS));
-  }
-  auto accum = [&](int side, int want_var) {
-    const double* ring = side ? ringE : ringP;
-    const size_t len = side ? lenE : lenP;
-    double* o = side ? oE : oP;
-    const dim3 grid((unsigned)((len + (size_t)RL_E * (RL_AT / 64) - 1) / ((size_t)RL_E * (RL_AT / 64)))), block(RL_AT);
-    const size_t lds = stage ? tab : 0;
-    if (side == 0) {
-      if (stage) hipLaunchKernelGGL((k_rl_accum<0, true>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
-      else hipLaunchKernelGGL((k_rl_accum<0, false>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
-    } else {
-      if (stage) hipLaunchKernelGGL((k_rl_accum<1, true>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
-      else hipLaunchKernelGGL((k_rl_accum<1, false>), grid, block, lds, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt, (const int32_t*)dInv, (const double*)cs, want_var, o);
-    }
-  };
-  const double* piv = pivot_P ? dPiv : ringP + (size_t)slots[S - 1] * lenP;      // NULL: the newest used sample's P
-  int rounds = 0, converged = 0, cnt[2] = {0, 0};
-  for (int r = 1; r <= max_rounds; ++r) {
-    const int first = r == 1 ? 1 : 0;
-    hipLaunchKernelGGL(k_rl_pivot, dim3((N + 63) / 64), dim3(64), 0, h->stream, piv, K, N, dRef, dN2);
-    if (fused) {
-      hipLaunchKernelGGL(k_rl_match, dim3(S), dim3(64), match_lds, h->stream, ringP, K, N, (const int*)dSl, (const double*)dRef, (const double*)dN2, first,
-                         dPerm, dInv, dCs, dFlag);
-    } else {
-      for (int s0 = 0; s0 < S; s0 += chunk) {
-        const int ns = std::min(chunk, S - s0);
-        hipLaunchKernelGGL(k_ref_cosine, dim3(ns, N), dim3(128), 0, h->stream, ringP, lenP, K, (const int*)dSl + s0, (const int*)dSig, N,
-                           (const double*)dRef, (const double*)dN2, N, dCv);
-        HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)ns * N * sizeof(int32_t), h->stream));
-        hipLaunchKernelGGL(k_hungarian, dim3(ns), dim3(64), hung_lds, h->stream, (const double*)dCv, N, N, 0, dCol);
-        hipLaunchKernelGGL(k_rl_finish, dim3((ns + 63) / 64), dim3(64), 0, h->stream, (const double*)dCv, (const int32_t*)dCol, N, ns, first,
-                           dPerm + (size_t)s0 * N, dInv + (size_t)s0 * N, dCs + (size_t)s0 * N, dFlag + s0);
-      }
-    }
-    hipLaunchKernelGGL(k_rl_compact, dim3(1), dim3(64), 0, h->stream, (const int32_t*)dFlag, S, dAl, dCnt);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cnt, dCnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    rounds = r;
-    if (cnt[0] < 2)
-      return fail(BNMF_ESIZE, "%s: %d of the %d used samples could be aligned in round %d (a cosine that is not finite leaves a sample unmatched), at least 2 are needed",
-                  fn, cnt[0], S, r);
-    if (cnt[1] == 0) { converged = 1; break; }
-    if (r == max_rounds) break;
-    accum(0, 0);                                           // the next pivot: the aligned mean of the renormalised P
-    piv = oP;
-  }
-  accum(0, 1);
-  accum(1, 1);
-  HIPCHK(hipGetLastError());
-  std::vector<int32_t> hperm(SN);
-  std::vector<double> hcos(SN);
-  HIPCHK(hipMemcpyAsync(hperm.data(), dPerm, SN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(hcos.data(), dCs, SN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (P_out) HIPCHK(hipMemcpyAsync(P_out, oP, RL_NROW * lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (E_out) HIPCHK(hipMemcpyAsync(E_out, oE, RL_NROW * lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  auto gather = [&](int side, int nbmax, double* dst) -> int {
-    const size_t len = side ? lenE : lenP;
-    for (int s0 = 0; s0 < S; s0 += nbmax) {
-      const int nb = std::min(nbmax, S - s0);
-      const dim3 grid((unsigned)((len + 255) / 256), (unsigned)nb), block(256);
-      if (side) hipLaunchKernelGGL(k_rl_gather<1>, grid, block, 0, h->stream, ringE, len, K, N, (const int*)dSl, (const int32_t*)dInv, (const int32_t*)dFlag, (const double*)cs, s0, dBat);
-      else hipLaunchKernelGGL(k_rl_gather<0>, grid, block, 0, h->stream, ringP, len, K, N, (const int*)dSl, (const int32_t*)dInv, (const int32_t*)dFlag, (const double*)cs, s0, dBat);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(dst + (size_t)s0 * len, dBat, (size_t)nb * len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));               // the next batch overwrites the scratch
-    }
-    return 0;
-  };
-  if (aligned_P) if (int rc = gather(0, bP, aligned_P)) return rc;
-  if (aligned_E) if (int rc = gather(1, bE, aligned_E)) return rc;
-  if (perm) std::memcpy(perm, hperm.data(), SN * sizeof(int32_t));
-  if (cosine) std::memcpy(cosine, hcos.data(), SN * sizeof(double));
-  if (confusion) for (size_t i = 0; i < (size_t)N * N; ++i) confusion[i] = 0;
-  std::memset(info, 0, sizeof *info);
-  info->n_used = S; info->n_aligned = cnt[0]; info->n_unmatched = S - cnt[0]; info->rounds = rounds; info->converged = converged;
-  info->n_changed_last = cnt[1];
-  double acc[64], mn = std::nan("");
-  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
-  int64_t mn_at = -1;
-  size_t t = 0;                                            // place in the (s, n) sequence of the aligned samples' cosines
-  for (int s = 0; s < S; ++s) {
-    const int32_t* pm = hperm.data() + (size_t)s * N;
-    if (N > 0 && pm[0] < 0) continue;                      // unmatched
-    bool ident = true;
-    for (int n = 0; n < N; ++n) {
-      const double c = hcos[(size_t)s * N + n];
-      ident = ident && pm[n] == n;
-      if (confusion) confusion[(size_t)n * N + pm[n]] += 1;
-      acc[t & 63] = acc[t & 63] + c; ++t;
-      if (mn_at < 0 || c < mn) { mn = c; mn_at = (int64_t)s * N + n; }
-    }
-    if (!ident) info->n_switched++;
-  }
-  for (int hh = 32; hh >= 1; hh >>= 1) for (int l = 0; l < hh; ++l) acc[l] = acc[l] + acc[l + hh];   // wave_tree64's order
-  info->mean_cosine = acc[0] / (double)((size_t)cnt[0] * (size_t)N);
-  info->min_cosine = mn; info->min_cosine_at = mn_at;
-  return 0;
-}
-int bnmf_relabel(bnmf_handle* h, int last_n, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine, int64_t* confusion,
-                 double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_relabel: null argument");
-  if (int rc = check_recorded(h, "bnmf_relabel")) return rc;
-  const int W = h->cfg.window;
-  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "bnmf_relabel: last_n = %d but only min(window = %d, iter = %d) samples are kept", last_n, W, h->iter);
-  return relabel_impl(h, "bnmf_relabel", h->iter, last_n, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
-}
-int bnmf_relabel_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine,
-                    int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
-  if (!h || !info) return fail(BNMF_EINVAL, "bnmf_relabel_at: null argument");
-  if (int rc = check_recorded(h, "bnmf_relabel_at")) return rc;
-  if (int rc = check_kept(h, "bnmf_relabel_at", (long long)end_iter - n_samples + 1, end_iter)) return rc;
-  return relabel_impl(h, "bnmf_relabel_at", end_iter, n_samples, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
 }
 
 // ---- measured ceilings for bench.py's roofline: Philox4x32-7 words per second (the count-allocation stream's generator) with

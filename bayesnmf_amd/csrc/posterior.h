@@ -1,0 +1,819 @@
+// bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
+// bnmf_mixing, bnmf_assign, bnmf_relabel (each with its _at form) and bnmf_label_switching.  Host code only: the kernels are in kernels.h,
+// waic.h, ppc.h, attribution.h, mixing.h and relabel.h.  Included by api.hip (one translation unit) behind sweep.h.
+// The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
+// and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
+// its host reduction.
+#pragma once
+
+// copy the `last_n` consecutive samples that end at iteration `end_iter` (oldest first) of a ring to the host: sample `it` lives in slot
+// (it - 1) % (window + 1), so they are at most two contiguous runs
+static int ring_read(const bnmf_handle* h, int id, int end_iter, int last_n, double* out) {
+  const Arr& a = h->arr[id];
+  const size_t len = id_len(h, id), C = (size_t)h->wcap, s0 = (size_t)(end_iter - last_n) % C;
+  const size_t n1 = (s0 + (size_t)last_n <= C) ? (size_t)last_n : C - s0;
+  HIPCHK(hipMemcpy(out, a.ring + s0 * len, n1 * len * sizeof(double), hipMemcpyDeviceToHost));
+  if (n1 < (size_t)last_n) HIPCHK(hipMemcpy(out + n1 * len, a.ring, ((size_t)last_n - n1) * len * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- the range ----
+// bnmf_X names the last n samples (at = false), bnmf_X_at the n samples that end at iteration end_iter.
+struct Range { bool at; int end_iter, n; };
+
+static int check_alive(const bnmf_handle* h, const char* fn) {
+  if (h->poisoned) return fail(BNMF_ESTATE, "%s: the handle timed out inside a kernel; its state is invalid", fn);
+  return 0;
+}
+static int check_recorded(const bnmf_handle* h, const char* fn) {
+  if (int rc = check_alive(h, fn)) return rc;
+  if (h->cfg.window <= 0) return fail(BNMF_ESTATE, "%s: the handle was created with window = 0", fn);
+  return 0;
+}
+static int check_last(const bnmf_handle* h, const char* fn, int last_n) {
+  const int W = h->cfg.window;
+  if (last_n < 1 || last_n > W || last_n > h->iter) return fail(BNMF_ESIZE, "%s: last_n = %d but only min(window = %d, iter = %d) samples are kept", fn, last_n, W, h->iter);
+  return 0;
+}
+// Iterations first..last must be recorded and still kept: [max(1, iter - window + 1), iter] (the ring holds window + 1 slots, the
+// slot ahead of the oldest kept sample belongs to the iteration in flight).
+static int check_kept(const bnmf_handle* h, const char* fn, long long first, long long last) {
+  const int lo = std::max(1, h->iter - h->cfg.window + 1);
+  if (first > last || first < lo || last > h->iter)
+    return fail(BNMF_ESIZE, "%s: iterations %lld..%lld requested but only iterations %d..%d are kept (window = %d, iter = %d)", fn, first, last, lo,
+                h->iter, h->cfg.window, h->iter);
+  return 0;
+}
+// check `r` and make it explicit: afterwards r.end_iter is the range's last iteration in both forms
+static int range_resolve(const bnmf_handle* h, const char* fn, Range& r) {
+  if (r.at) return check_kept(h, fn, (long long)r.end_iter - r.n + 1, r.end_iter);
+  r.end_iter = h->iter;
+  return check_last(h, fn, r.n);
+}
+// what every call does first: `args_ok` is the call's null check (it includes h), then the handle, then the range
+static int range_enter(const bnmf_handle* h, const char* fn, bool args_ok, Range& r) {
+  if (!args_ok) return fail(BNMF_EINVAL, "%s: null argument", fn);
+  if (int rc = check_recorded(h, fn)) return rc;
+  return range_resolve(h, fn, r);
+}
+// The ring slots of the samples of `r` that used[] flags (null: all of them), oldest first; with `iters` their iterations behind them
+// in the same vector.  strict: a used[s] outside {0, 1} is refused; else any non-zero value flags a sample (bnmf_assign).
+static int range_slots(const bnmf_handle* h, const char* fn, const Range& r, const int32_t* used, bool strict, std::vector<int>& slots, bool iters = false) {
+  slots.clear();
+  for (int s = 0; s < r.n; ++s) {
+    if (strict && used && used[s] != 0 && used[s] != 1) return fail(BNMF_EINVAL, "%s: used[%d] = %d is neither 0 nor 1", fn, s, (int)used[s]);
+    if (!used || used[s]) slots.push_back((int)((size_t)(r.end_iter - r.n + s) % (size_t)h->wcap));
+  }
+  if (iters) for (int s = 0; s < r.n; ++s) if (!used || used[s]) slots.push_back(r.end_iter - r.n + 1 + s);
+  return 0;
+}
+
+// ---- quiesce: nothing of the chain is in flight while a posterior call reads the rings ----
+static int post_sync(const bnmf_handle* h) {
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->side));
+  HIPCHK(hipStreamSynchronize(h->side2));
+  return 0;
+}
+
+// ---- scratch: one buffer per handle, grown on demand; a call carves it and leaves nothing in it that a later call reads ----
+static int scratch_reserve(bnmf_handle* h, size_t need) {
+  Scratch& s = h->scratch;
+  if (need <= s.bytes) return 0;
+  s.bytes = 0;                                            // first: a failed replacement leaves an empty scratch, not a stale size
+  HIPCHK(hfree(h, s.p));
+  HIPCHK(hmalloc(h, &s.p, need));
+  s.bytes = need;
+  return 0;
+}
+// bump carver: typed sub-blocks in the order taken, each aligned to 256 bytes
+struct Carve {
+  uintptr_t base; size_t off = 0;
+  template <class T> T* take(size_t n) { T* p = (T*)(base + off); off += (n * sizeof(T) + 255) & ~(size_t)255; return p; }
+};
+// run a call's carve list twice: once to measure, then, the scratch reserved, to hand out the blocks
+template <class List> static int carve(bnmf_handle* h, List list) {
+  Carve measure{0};
+  list(measure);
+  if (int rc = scratch_reserve(h, measure.off)) return rc;
+  Carve c{(uintptr_t)h->scratch.p};
+  list(c);
+  return 0;
+}
+
+// ---- the reference catalogue of bnmf_assign and bnmf_label_switching, and the assignment problem's LDS ----
+// dRef: the catalogue row-major [k][j]; dN2 and rn2: its squared column norms, summed over k ascending (MAP_cosine is pinned bit for bit)
+static int catalogue_upload(const double* ref, int K, int R, double* dRef, double* dN2, std::vector<double>& rn2) {
+  std::vector<double> refT((size_t)K * R);
+  rn2.assign(R, 0.0);
+  for (int j = 0; j < R; ++j) for (int k = 0; k < K; ++k) { const double v = ref[k + (size_t)K * j]; refT[(size_t)k * R + j] = v; rn2[j] += v * v; }
+  HIPCHK(hipMemcpy(dRef, refT.data(), refT.size() * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dN2, rn2.data(), R * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+static size_t hungarian_lds_bytes(int nrow, int ncol) { return (size_t)(ncol + 1) * (16 + 12) + (size_t)(nrow + 1) * 8; }
+
+// ---- dynamic LDS above the 64 KB a kernel may use unasked: raise the kernel's limit to `limit` ----
+static constexpr size_t LDS_CAP = 160 * 1024;
+template <class Kern> static int opt_in_lds(Kern* kernel, size_t bytes, size_t limit = LDS_CAP) {
+  if (bytes <= 64 * 1024) return 0;
+  HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
+  return 0;
+}
+
+// ---- the calls ----
+
+// get_MAP_ over the samples of r
+static int map_impl(bnmf_handle* h, const char* fn, Range r, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
+                    double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
+  if (int rc = range_enter(h, fn, h && A_mode && info, r)) return rc;
+  const int end_iter = r.end_iter, last_n = r.n;
+  if (ci >= 1.0) return fail(BNMF_EINVAL, "bnmf_map: credible_interval must be below 1");
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G;
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "bnmf_map: nothing recorded yet");
+  if (int rc = post_sync(h)) return rc;
+  // i. mode of A (get_mode): patterns as strings, most frequent first, ties in alphabetical order
+  std::vector<double> Aw((size_t)last_n * N);
+  if (int rc = ring_read(h, BNMF_A, end_iter, last_n, Aw.data())) return rc;
+  std::vector<std::string> keys(last_n, std::string(N, '0'));
+  std::map<std::string, int> tab;
+  for (int s = 0; s < last_n; ++s) { for (int n = 0; n < N; ++n) if (Aw[(size_t)s * N + n] != 0.0) keys[s][n] = '1'; tab[keys[s]]++; }
+  std::vector<std::pair<std::string, int>> ord(tab.begin(), tab.end());        // std::map iterates alphabetically
+  std::stable_sort(ord.begin(), ord.end(), [](const auto& a, const auto& b) { return a.second > b.second; });
+  const std::string& mode = ord[0].first;
+  info->n_patterns = (int)ord.size();
+  for (int i = 0; i < 5; ++i) {
+    info->top_counts[i] = i < (int)ord.size() ? ord[i].second : 0;
+    if (top_A) for (int n = 0; n < N; ++n) top_A[(size_t)i * N + n] = i < (int)ord.size() ? (ord[i].first[n] == '1' ? 1.0 : 0.0) : std::nan("");
+  }
+  std::vector<int32_t> is_mode(last_n);
+  for (int s = 0; s < last_n; ++s) is_mode[s] = keys[s] == mode ? 1 : 0;
+  if (used) std::copy(is_mode.begin(), is_mode.end(), used);
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, is_mode.data(), false, slots)) return rc;
+  const int nu = (int)slots.size();
+  info->n_used = nu; info->_pad = 0;
+  std::vector<double> Am(N);
+  for (int n = 0; n < N; ++n) Am[n] = A_mode[n] = mode[n] == '1' ? 1.0 : 0.0;
+  // ii-iii. renormalised means (and quantiles) on the device
+  const bool want_ci = ci > 0.0 && (P_lower || P_upper || E_lower || E_upper);
+  int kt = 0, jlo = 0, jhi = 0; double glo = 0.0, ghi = 0.0;
+  if (want_ci) {                                    // quantile type 7: h = (n-1) p, j = floor(h), g = h - j
+    const double plo = 0.5 - ci / 2.0, phi = 0.5 + ci / 2.0;
+    const double hl = (nu - 1) * plo, hh = (nu - 1) * phi;
+    jlo = (int)std::floor(hl); glo = hl - jlo; jhi = (int)std::floor(hh); ghi = hh - jhi;
+    kt = std::min(nu, std::max(jlo + 2, nu - jhi));
+  }
+  // the bounds by sorting (k_map_quant) when the samples of 8 elements fit the LDS; else by the kt smallest / largest per lane
+  int qS = 0;
+  if (want_ci) { qS = ((nu + 63) / 64) * 64; if (qS > 2048) qS = 0; }
+  if (want_ci && !qS && (size_t)kt * 2 * 64 * sizeof(double) > LDS_CAP)
+    return fail(BNMF_EINVAL, "bnmf_map: credible_interval %.3g over %d samples needs %d order statistics per element (device limit 160): take the window with bnmf_window", ci, nu, kt);
+  double *cs, *mP, *loP, *hiP, *mE, *loE, *hiE, *colsse, *dA; int* dslots;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)nu * N);
+        mP = c.take<double>(lenP); loP = c.take<double>(lenP); hiP = c.take<double>(lenP);
+        mE = c.take<double>(lenE); loE = c.take<double>(lenE); hiE = c.take<double>(lenE);
+        colsse = c.take<double>(2 * (size_t)G);         // colsse, then colkl
+        dA = c.take<double>(N); dslots = c.take<int>(nu);
+      })) return rc;
+  double* colkl = colsse + G;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), nu * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dA, Am.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(nu, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
+  if (!qS) {                                              // means (and, beyond 2,048 samples, the bounds) by a lane per element
+    const size_t lds = (size_t)kt * 2 * 64 * sizeof(double);
+    if (int rc = opt_in_lds(k_map_stats<0>, lds)) return rc;
+    if (int rc = opt_in_lds(k_map_stats<1>, lds)) return rc;
+    hipLaunchKernelGGL(k_map_stats<0>, dim3((unsigned)((lenP + 63) / 64)), dim3(64), lds, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N,
+                       (const int*)dslots, nu, (const double*)cs, kt, jlo, glo, jhi, ghi, mP, loP, hiP);
+    hipLaunchKernelGGL(k_map_stats<1>, dim3((unsigned)((lenE + 63) / 64)), dim3(64), lds, h->stream, (const double*)h->arr[BNMF_E].ring, lenE, K, N,
+                       (const int*)dslots, nu, (const double*)cs, kt, jlo, glo, jhi, ghi, mE, loE, hiE);
+  }
+  if (qS) {
+    const bool r16 = qS <= 1024;                           // 16 or 32 samples per lane column
+    const size_t qS2 = r16 ? 1024 : 2048, qlds = qS2 * MQ_E * sizeof(double) + qS2 * sizeof(int);
+    using QuantKernel = decltype(&k_map_quant<0, 16>);
+    const QuantKernel q16[2] = {k_map_quant<0, 16>, k_map_quant<1, 16>}, q32[2] = {k_map_quant<0, 32>, k_map_quant<1, 32>};
+    const QuantKernel* kquant = r16 ? q16 : q32;           // [side]
+    auto go = [&](int side, const double* ring, size_t len, double* mn, double* lo, double* hi) {
+      if (int rc = opt_in_lds(kquant[side], qlds, qlds)) return rc;
+      hipLaunchKernelGGL(kquant[side], dim3((unsigned)((len + MQ_E - 1) / MQ_E)), dim3(MQ_T), qlds, h->stream, ring, len, K, N, (const int*)dslots, nu,
+                         (const double*)cs, jlo, glo, jhi, ghi, mn, lo, hi);
+      return 0;
+    };
+    if (int rc = go(0, h->arr[BNMF_P].ring, lenP, mP, loP, hiP)) return rc;
+    if (int rc = go(1, h->arr[BNMF_E].ring, lenE, mE, loE, hiE)) return rc;
+  }
+  if (h->dMf) hipLaunchKernelGGL(k_map_fit<double>, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const double*)h->dMf, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
+  else hipLaunchKernelGGL(k_map_fit<int32_t>, dim3((G + 3) / 4), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)mP, (const double*)dA, (const double*)mE, K, N, G, colsse, colkl);
+  HIPCHK(hipGetLastError());
+  if (P_mean) HIPCHK(hipMemcpyAsync(P_mean, mP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (E_mean) HIPCHK(hipMemcpyAsync(E_mean, mE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (want_ci) {
+    if (P_lower) HIPCHK(hipMemcpyAsync(P_lower, loP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (P_upper) HIPCHK(hipMemcpyAsync(P_upper, hiP, lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (E_lower) HIPCHK(hipMemcpyAsync(E_lower, loE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (E_upper) HIPCHK(hipMemcpyAsync(E_upper, hiE, lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  std::vector<double> col(2 * (size_t)G);
+  HIPCHK(hipMemcpyAsync(col.data(), colsse, 2 * (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  double sse = 0.0, kl = 0.0;
+  for (int g = 0; g < G; ++g) { sse += col[g]; kl += col[(size_t)G + g]; }
+  info->rmse = std::sqrt(sse / ((double)K * (double)G));
+  info->kl = kl;
+  return 0;
+}
+
+// WAIC over the samples of r that used[] flags: k_waic (waic.h) leaves the per-column sums; the totals are their
+// sequential sums over g, as map_impl sums colsse.
+static int waic_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the log-likelihood needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
+    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t KG = (size_t)K * G, ncol = (size_t)WA_NCOL * G;
+  double *dcol, *dcell; int* dslots;
+  if (int rc = carve(h, [&](Carve& c) { dcol = c.take<double>(ncol); dcell = cell ? c.take<double>(2 * KG) : nullptr; dslots = c.take<int>(S); })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  WaicArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr;
+  a.M = h->dM; a.Mf = h->dMf; a.lgfact = h->dLut; a.slots = dslots; a.col = dcol; a.cell = dcell;
+  a.lenP = (size_t)K * N; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.S = S; a.maxM = h->maxM;
+  size_t lds = waic_lds_bytes(N);
+  a.stage = lds <= LDS_CAP ? 1 : 0;
+  if (!a.stage) lds = 0;
+  const auto kern = normal ? k_waic<true> : k_waic<false>;
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((G + WA_GC - 1) / WA_GC)), dim3(WA_T), lds, h->stream, a);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hc(ncol);
+  HIPCHK(hipMemcpyAsync(hc.data(), dcol, ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (cell) HIPCHK(hipMemcpyAsync(cell, dcell, 2 * KG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  double t[WA_NCOL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < WA_NCOL; ++q) for (int g = 0; g < G; ++g) t[q] += hc[(size_t)q * G + g];
+  if (col) for (int q = 0; q < 3; ++q) std::memcpy(col + (size_t)q * G, hc.data() + (size_t)q * G, (size_t)G * sizeof(double));
+  const double n = (double)K * (double)G;
+  double var = n > 1.0 ? (t[4] - t[3] * (t[3] / n)) / (n - 1.0) : 0.0;   // variance of elpd over the cells from its two sums
+  if (!(var > 0.0)) var = 0.0;
+  info->n_used = S; info->n_high_var = (int32_t)t[5];
+  info->lppd = t[0]; info->p_waic = t[1]; info->mean_loglik = t[2]; info->elpd_waic = t[3]; info->waic = -2.0 * t[3];
+  info->se_elpd = std::sqrt(n * var);
+  return 0;
+}
+
+// Posterior predictive checks over the samples of r that used[] flags: k_ppc leaves T[4][S][G], the tail cells per column and the cell
+// values, k_ppc_totals the per-column rows and the series (ppc.h); the info fields are sequential scans of the series
+// on the host.
+static_assert(PP_NCOL == BNMF_PPC_NCOL && PP_VAR == (uint32_t)BNMF_V_YREP, "ppc.h and bnmf.h disagree");
+static int ppc_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  std::vector<int> sl;                              // slots, then iterations
+  if (int rc = range_slots(h, fn, r, used, true, sl, true)) return rc;
+  const int S = (int)sl.size() / 2;
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the replicates needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
+    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t KG = (size_t)K * G, SG = (size_t)S * G, ncol = (size_t)(PP_NCOL + 1) * G;
+  double *dT, *dcol, *dser, *dcell; int* dsl;
+  if (int rc = carve(h, [&](Carve& c) {
+        dT = c.take<double>(4 * SG); dcol = c.take<double>(ncol); dser = c.take<double>(4 * (size_t)S);
+        dcell = cell ? c.take<double>(4 * KG) : nullptr; dsl = c.take<int>(2 * (size_t)S);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dsl, sl.data(), 2 * (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  PpcArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr;
+  a.M = h->dM; a.Mf = h->dMf; a.slots = dsl; a.iters = dsl + S; a.T = dT; a.tail = dcol + (size_t)PP_NCOL * G; a.cell = dcell;
+  a.lenP = (size_t)K * N; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.S = S;
+  a.k0 = (uint32_t)h->cfg.seed; a.k1 = (uint32_t)(h->cfg.seed >> 32) ^ h->cfg.chain_id;
+  size_t lds = ppc_lds_bytes(N);
+  a.stage = lds <= LDS_CAP ? 1 : 0;
+  if (!a.stage) lds = 0;
+  const auto kern = normal ? k_ppc<true> : k_ppc<false>;
+  const auto ktot = normal ? k_ppc_totals<true> : k_ppc_totals<false>;
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((G + PP_GC - 1) / PP_GC)), dim3(PP_T), lds, h->stream, a);
+  hipLaunchKernelGGL(ktot, dim3((unsigned)(4 * S + (G + PP_TT - 1) / PP_TT)), dim3(PP_TT), 0, h->stream, (const double*)dT, S, G, dser, dcol);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hs(4 * (size_t)S), ht((size_t)G);
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, 4 * (size_t)S * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(ht.data(), dcol + (size_t)PP_NCOL * G, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (col) HIPCHK(hipMemcpyAsync(col, dcol, (size_t)PP_NCOL * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (cell) HIPCHK(hipMemcpyAsync(cell, dcell, 4 * KG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), 4 * (size_t)S * sizeof(double));
+  double t[4] = {0.0, 0.0, 0.0, 0.0}; int n1 = 0, n2 = 0;
+  for (int s = 0; s < S; ++s) {
+    for (int q = 0; q < 4; ++q) t[q] += hs[(size_t)q * S + s];
+    n1 += hs[(size_t)S + s] >= hs[s] ? 1 : 0; n2 += hs[3 * (size_t)S + s] >= hs[2 * (size_t)S + s] ? 1 : 0;
+  }
+  int64_t nt = 0;
+  for (int g = 0; g < G; ++g) nt += (int64_t)ht[g];
+  info->n_used = S; info->n_tail_cells = nt;
+  info->p_T1 = (double)n1 / (double)S; info->p_T2 = (double)n2 / (double)S;
+  info->mean_T1_obs = t[0] / (double)S; info->mean_T1_rep = t[1] / (double)S; info->mean_T2_obs = t[2] / (double)S; info->mean_T2_rep = t[3] / (double)S;
+  return 0;
+}
+
+// Signature attribution over the samples of r that used[] flags: per batch of samples k_attr leaves a_s[n,g] in the scratch,
+// k_attr_share the reciprocal column totals, k_attr_stats continues the per-(n, g) statistics (zeroed by the first batch: a.first)
+// and reduces the series (attribution.h); total and n_present are sequential scans on the host.
+static_assert(AT_NLOAD == BNMF_ATTR_NLOAD, "attribution.h and bnmf.h disagree");
+static constexpr size_t ATTR_SCRATCH_CAP = (size_t)256 << 20;   // bytes of a_s and u per batch
+static int attr_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, double min_load, double* load, double* prob, double* series,
+                     bnmf_attr_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the loads needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t NG = (size_t)N * G, KNG = (size_t)K * NG, per = (NG + (size_t)G) * sizeof(double);   // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, ATTR_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_ATTR_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>(want, S);
+  double *dscr, *du, *dst, *dload, *dser, *dprob; int* dslots;
+  if (int rc = carve(h, [&](Carve& c) {
+        dscr = c.take<double>((size_t)Sb * NG); du = c.take<double>((size_t)Sb * G); dst = c.take<double>(AT_NLOAD * NG);
+        dload = c.take<double>(AT_NLOAD * NG); dser = c.take<double>((size_t)S * N); dprob = prob ? c.take<double>(KNG) : nullptr;
+        dslots = c.take<int>(S);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  AttrArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.M = h->dM; a.scr = dscr; a.prob = dprob;
+  a.lenP = (size_t)K * N; a.lenE = NG; a.K = K; a.N = N; a.G = G; a.S = S;
+  size_t lds = attr_lds_bytes(N);
+  a.stage = lds <= LDS_CAP ? 1 : 0;
+  if (!a.stage) lds = 0;
+  const auto kern = normal ? (prob ? k_attr<true, true> : k_attr<true, false>) : (prob ? k_attr<false, true> : k_attr<false, false>);
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  const dim3 grid((unsigned)((G + AT_GC - 1) / AT_GC)), block(AT_T);
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0), last = s0 + nb == S ? 1 : 0;
+    a.slots = dslots + s0; a.Sb = nb; a.first = s0 == 0 ? 1 : 0; a.last = last;
+    hipLaunchKernelGGL(kern, grid, block, lds, h->stream, a);
+    const size_t nsg = (size_t)nb * G;
+    hipLaunchKernelGGL(k_attr_share, dim3((unsigned)((nsg + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, G, du);
+    hipLaunchKernelGGL(k_attr_stats, dim3((unsigned)((size_t)nb * N + (NG + AT_TT - 1) / AT_TT)), dim3(AT_TT), 0, h->stream, (const double*)dscr,
+                       (const double*)du, nb, N, G, S, s0, last, min_load, dst, dser, dload);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> hs((size_t)S * N), hp(NG);
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, (size_t)S * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hp.data(), dload + 3 * NG, NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (load) HIPCHK(hipMemcpyAsync(load, dload, AT_NLOAD * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (prob) HIPCHK(hipMemcpyAsync(prob, dprob, KNG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), (size_t)S * N * sizeof(double));
+  double t = 0.0;
+  for (size_t i = 0; i < (size_t)S * N; ++i) t += hs[i];
+  int64_t np = 0;
+  for (size_t i = 0; i < NG; ++i) np += hp[i] >= 0.5 ? 1 : 0;
+  info->n_used = S; info->_pad = 0; info->n_present = np; info->min_load = min_load; info->total = t / (double)S;
+  return 0;
+}
+
+// Mixing diagnostics over the samples of r that used[] flags: k_map_colsum, then k_mixing (mixing.h) per side leaves the
+// per-element rows; the summary is a sequential scan of them on the host, element index ascending, P then E, over the factors that
+// keep[] flags.
+static_assert(BNMF_NMIX == MX_NROW, "bnmf.h and mixing.h disagree on the rows of the per-element output");
+static int mixing_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* keep, double* P_out, double* E_out,
+                       bnmf_mixing_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  if (keep) for (int n = 0; n < N; ++n) if (keep[n] != 0 && keep[n] != 1) return fail(BNMF_EINVAL, "%s: keep[%d] = %d is neither 0 nor 1", fn, n, (int)keep[n]);
+  const int S = (int)slots.size();
+  if (S < 4) return fail(BNMF_ESIZE, "%s: %d used sample%s, split R-hat needs at least 4 (a variance in each half)", fn, S, S == 1 ? "" : "s");
+  static_assert(BNMF_MIXING_MAX_SAMPLES * (sizeof(double) + sizeof(int)) <= MX_LDS, "one element's series and the slot list fit the LDS");
+  if (S > BNMF_MIXING_MAX_SAMPLES)
+    return fail(BNMF_ESIZE, "%s: %d used samples but at most %d fit the device's 160 KB of LDS per element: thin the range with used[]", fn, S, BNMF_MIXING_MAX_SAMPLES);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G;
+  double *cs, *oP, *oE; int* dslots;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); oP = c.take<double>(MX_NROW * lenP); oE = c.take<double>(MX_NROW * lenE); dslots = c.take<int>(S);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
+  const int epw = mixing_elements_per_group(S);
+  const size_t lds = mixing_lds_bytes(epw, S);
+  const double tau_min = 1.0 / std::log10((double)S);
+  if (int rc = opt_in_lds(k_mixing<0>, lds, MX_LDS)) return rc;
+  if (int rc = opt_in_lds(k_mixing<1>, lds, MX_LDS)) return rc;
+  hipLaunchKernelGGL(k_mixing<0>, dim3((unsigned)((lenP + epw - 1) / epw)), dim3(64 * epw), lds, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N,
+                     (const int*)dslots, S, (const double*)cs, tau_min, epw, oP);
+  hipLaunchKernelGGL(k_mixing<1>, dim3((unsigned)((lenE + epw - 1) / epw)), dim3(64 * epw), lds, h->stream, (const double*)h->arr[BNMF_E].ring, lenE, K, N,
+                     (const int*)dslots, S, (const double*)cs, tau_min, epw, oE);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hP, hE;                       // the summary needs the rows whether or not the caller wants them
+  if (!P_out) { hP.resize(MX_NROW * lenP); P_out = hP.data(); }
+  if (!E_out) { hE.resize(MX_NROW * lenE); E_out = hE.data(); }
+  HIPCHK(hipMemcpyAsync(P_out, oP, MX_NROW * lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(E_out, oE, MX_NROW * lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  info->n_used = S; info->n_half = S / 2;
+  const double nan = std::nan("");
+  info->min_ess_P = info->min_ess_E = info->max_rhat_P = info->max_rhat_E = nan;
+  info->min_ess_P_at = info->min_ess_E_at = info->max_rhat_P_at = info->max_rhat_E_at = -1;
+  auto scan = [&](const double* o, size_t len, bool sideE, double& mn, int64_t& mn_at, double& mx, int64_t& mx_at) {
+    for (size_t e = 0; e < len; ++e) {
+      const int n = sideE ? (int)(e % (size_t)N) : (int)(e / (size_t)K);
+      if (keep && !keep[n]) continue;
+      const double ess = o[2 * len + e], rhat = o[4 * len + e];
+      if (o[5 * len + e] == 0.0) info->n_const++;
+      if (o[6 * len + e] == 1.0) info->n_ran_out++;
+      if (ess < BNMF_MIXING_LOW_ESS) info->n_low_ess++;
+      if (rhat > BNMF_MIXING_HIGH_RHAT) info->n_high_rhat++;
+      if (!std::isnan(ess) && (mn_at < 0 || ess < mn)) { mn = ess; mn_at = (int64_t)e; }
+      if (!std::isnan(rhat) && (mx_at < 0 || rhat > mx)) { mx = rhat; mx_at = (int64_t)e; }
+    }
+  };
+  scan(P_out, lenP, false, info->min_ess_P, info->min_ess_P_at, info->max_rhat_P, info->max_rhat_P_at);
+  scan(E_out, lenE, true, info->min_ess_E, info->min_ess_E_at, info->max_rhat_E, info->max_rhat_E_at);
+  return 0;
+}
+
+static double quantile7(std::vector<double> x, double prob) {
+  std::sort(x.begin(), x.end());
+  const double hq = (x.size() - 1) * prob;
+  const size_t j = (size_t)std::floor(hq);
+  const double g = hq - (double)j;
+  const double a = x[j], b = x[std::min(j + 1, x.size() - 1)];
+  return a == b ? a : (1.0 - g) * a + g * b;              // k_map_quant's map_interp
+}
+
+// assign_signatures_ensemble_ over the samples of r that used[] flags (any non-zero value).  Its preconditions have their own wording:
+// bnmf_assign refuses a handle without a P ring as one without a window, before it looks at last_n.
+static int assign_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
+                       double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
+  if (!h || !ref || !votes || !assigned) return fail(BNMF_EINVAL, "%s: null argument", fn);
+  if (int rc = check_alive(h, fn)) return rc;
+  if (!r.at) {
+    if (h->cfg.window <= 0 || !h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign: no recorded samples (window = 0)");
+  } else {
+    if (int rc = check_recorded(h, fn)) return rc;
+    if (!h->arr[BNMF_P].ring) return fail(BNMF_ESTATE, "bnmf_assign_at: nothing recorded yet");
+  }
+  if (int rc = range_resolve(h, fn, r)) return rc;
+  if (R < 1) return fail(BNMF_EINVAL, "bnmf_assign: empty reference");
+  const int K = h->cfg.K, N = h->cfg.N;
+  std::vector<int> slots, sig;
+  if (int rc = range_slots(h, fn, r, used, false, slots)) return rc;
+  for (int n = 0; n < N; ++n) if (!keep || keep[n]) sig.push_back(n);
+  const int nu = (int)slots.size(), nk = (int)sig.size();
+  for (int i = 0; i < N * R; ++i) votes[i] = 0.0;
+  for (int n = 0; n < N; ++n) { assigned[n] = -1; if (MAP_cosine) MAP_cosine[n] = std::nan(""); if (lower) lower[n] = std::nan(""); if (upper) upper[n] = std::nan(""); }
+  if (nu == 0 || nk == 0) return 0;
+  if (int rc = post_sync(h)) return rc;
+  const size_t nout = (size_t)nu * nk * R;
+  // one Hungarian assignment per sample (maximise the total cosine), one wave each; with more signatures than references the
+  // references are the rows
+  const bool tr = nk > R;
+  const int nrow = tr ? R : nk, ncol = tr ? nk : R;
+  double *dRef, *dN2, *dOut; int *dSl, *dSig; int32_t* dCol;
+  if (int rc = carve(h, [&](Carve& c) {
+        dRef = c.take<double>((size_t)K * R); dN2 = c.take<double>(R); dOut = c.take<double>(nout);
+        dSl = c.take<int>(nu); dSig = c.take<int>(nk); dCol = c.take<int32_t>((size_t)nu * nrow);
+      })) return rc;
+  std::vector<double> rn2;
+  if (int rc = catalogue_upload(ref, K, R, dRef, dN2, rn2)) return rc;
+  HIPCHK(hipMemcpy(dSl, slots.data(), nu * sizeof(int), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dSig, sig.data(), nk * sizeof(int), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_ref_cosine, dim3(nu, nk), dim3(128), 0, h->stream, (const double*)h->arr[BNMF_P].ring, (size_t)K * N, K, (const int*)dSl,
+                     (const int*)dSig, nk, (const double*)dRef, (const double*)dN2, R, dOut);
+  HIPCHK(hipGetLastError());
+  const size_t hung_lds = hungarian_lds_bytes(nrow, ncol);
+  if (hung_lds > LDS_CAP) return fail(BNMF_ESIZE, "bnmf_assign: %d x %d assignment problem exceeds the LDS of one workgroup", nrow, ncol);
+  if (int rc = opt_in_lds(k_hungarian, hung_lds, hung_lds)) return rc;
+  HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)nu * nrow * sizeof(int32_t), h->stream));
+  hipLaunchKernelGGL(k_hungarian, dim3(nu), dim3(64), hung_lds, h->stream, (const double*)dOut, nk, R, tr ? 1 : 0, dCol);
+  HIPCHK(hipGetLastError());
+  std::vector<double> cosv(nout);
+  std::vector<int32_t> col((size_t)nu * nrow);
+  HIPCHK(hipMemcpyAsync(cosv.data(), dOut, nout * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(col.data(), dCol, col.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the cosine of a chosen pair is its vote; the votes are summed in sample order
+  for (int s = 0; s < nu; ++s) {
+    const double* c = cosv.data() + (size_t)s * nk * R;
+    const int32_t* a = col.data() + (size_t)s * nrow;
+    for (int i = 0; i < nrow; ++i) if (a[i] < 0 || a[i] >= ncol) return fail(BNMF_ESTATE, "bnmf_assign: sample %d has no assignment (a cosine is not finite)", s);
+    if (!tr) for (int i = 0; i < nk; ++i) votes[sig[i] + (size_t)N * a[i]] += c[(size_t)i * R + a[i]];
+    else for (int j = 0; j < R; ++j) votes[sig[a[j]] + (size_t)N * j] += c[(size_t)a[j] * R + j];
+  }
+  for (int i = 0; i < nk; ++i) {                           // which.max(prop_votes): first maximum
+    const int n = sig[i];
+    int best = -1; double bv = 0.0;
+    for (int j = 0; j < R; ++j) if (votes[n + (size_t)N * j] > bv) { bv = votes[n + (size_t)N * j]; best = j; }
+    assigned[n] = best;
+    if (best < 0) continue;
+    if (MAP_P && MAP_cosine) {
+      double dot = 0.0, nn = 0.0;
+      for (int k = 0; k < K; ++k) { const double p = MAP_P[k + (size_t)K * n]; dot += p * ref[k + (size_t)K * best]; nn += p * p; }
+      MAP_cosine[n] = dot / std::sqrt(nn * rn2[best]);
+    }
+    if (ci > 0.0 && ci < 1.0 && (lower || upper)) {
+      std::vector<double> x(nu);
+      for (int s = 0; s < nu; ++s) x[s] = cosv[((size_t)s * nk + i) * R + best];
+      if (lower) lower[n] = quantile7(x, (1.0 - ci) / 2.0);
+      if (upper) upper[n] = quantile7(x, 1.0 - (1.0 - ci) / 2.0);
+    }
+  }
+  return 0;
+}
+
+// Label-switching correction over the samples of r that used[] flags: per round k_rl_pivot, the matching (k_rl_match, or past the LDS
+// k_ref_cosine + k_hungarian + k_rl_finish over chunks of samples), k_rl_compact, then the two counts come to the host; between rounds
+// k_rl_accum leaves the next pivot, after the last round the aligned mean and variance of both sides (relabel.h).
+// confusion and the summary are sequential scans on the host.
+static_assert(BNMF_NREL == RL_NROW, "bnmf.h and relabel.h disagree on the rows of the output");
+static const size_t LS_CHUNK_BYTES = (size_t)256 << 20;         // bytes of cosines per chunk of samples, past the LDS (also bnmf_label_switching)
+static constexpr size_t REL_SCRATCH_CAP = (size_t)256 << 20;    // bytes of aligned samples per batch
+static int relabel_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm,
+                        double* cosine, int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  if (max_rounds < 1) return fail(BNMF_EINVAL, "%s: max_rounds = %d, at least 1 round is needed", fn, max_rounds);
+  if (pivot_P)
+    for (int j = 0; j < N; ++j) {
+      bool zero = true;
+      for (int k = 0; k < K; ++k) {
+        const double v = pivot_P[(size_t)k + (size_t)K * j];
+        if (!std::isfinite(v)) return fail(BNMF_EINVAL, "%s: column %d of pivot_P holds a value that is not finite (row %d)", fn, j, k);
+        zero = zero && v == 0.0;
+      }
+      if (zero) return fail(BNMF_EINVAL, "%s: column %d of pivot_P is all zero: it has no cosine", fn, j);
+    }
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, an aligned variance needs at least 2", fn, S, S == 1 ? "" : "s");
+  const size_t hung_lds = relabel_hung_lds(N), match_lds = relabel_match_lds(N);
+  const bool fused = match_lds <= RL_LDS;
+  if (!fused && hung_lds > RL_LDS) return fail(BNMF_ESIZE, "%s: the %d x %d assignment problem exceeds the LDS of one workgroup", fn, N, N);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t lenP = (size_t)K * N, lenE = (size_t)N * G, SN = (size_t)S * N, per = (size_t)N * N * sizeof(double);
+  const int chunk = fused ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)S, LS_CHUNK_BYTES / per));
+  // the aligned samples leave in batches of whole samples, P then E through the same scratch
+  const int bP = aligned_P ? (int)std::min<size_t>({(size_t)S, (size_t)65535, std::max<size_t>(1, REL_SCRATCH_CAP / (lenP * sizeof(double)))}) : 0;
+  const int bE = aligned_E ? (int)std::min<size_t>({(size_t)S, (size_t)65535, std::max<size_t>(1, REL_SCRATCH_CAP / (lenE * sizeof(double)))}) : 0;
+  double *dRef, *dN2, *dPiv, *cs, *oP, *oE, *dCs, *dCv, *dBat; int32_t *dPerm, *dInv, *dFlag, *dCol; int *dAl, *dSl, *dCnt, *dSig;
+  if (int rc = carve(h, [&](Carve& c) {
+        dRef = c.take<double>(lenP); dN2 = c.take<double>(N); dPiv = c.take<double>(lenP); cs = c.take<double>(SN);
+        oP = c.take<double>(RL_NROW * lenP); oE = c.take<double>(RL_NROW * lenE); dCs = c.take<double>(SN);
+        dPerm = c.take<int32_t>(SN); dInv = c.take<int32_t>(SN); dFlag = c.take<int32_t>(S);
+        dAl = c.take<int>(S); dSl = c.take<int>(S); dCnt = c.take<int>(4); dSig = c.take<int>(N);
+        dCv = c.take<double>((size_t)chunk * N * N); dCol = c.take<int32_t>((size_t)chunk * N);
+        dBat = c.take<double>(std::max((size_t)bP * lenP, (size_t)bE * lenE));
+      })) return rc;
+  const double* ringP = h->arr[BNMF_P].ring;
+  const double* ringE = h->arr[BNMF_E].ring;
+  HIPCHK(hipMemcpyAsync(dSl, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (pivot_P) HIPCHK(hipMemcpyAsync(dPiv, pivot_P, lenP * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (!fused) {
+    std::vector<int> sig(N);
+    for (int n = 0; n < N; ++n) sig[n] = n;
+    HIPCHK(hipMemcpy(dSig, sig.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = opt_in_lds(k_hungarian, hung_lds, hung_lds)) return rc;
+  } else if (int rc = opt_in_lds(k_rl_match, match_lds, match_lds)) return rc;
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, ringP, lenP, K, N, (const int*)dSl, cs);
+  const size_t tab = relabel_tab_bytes(S, N);
+  const bool stage = tab <= RL_TAB_LDS;
+  using AccumKernel = decltype(&k_rl_accum<0, true>);
+  const AccumKernel staged[2] = {k_rl_accum<0, true>, k_rl_accum<1, true>}, direct[2] = {k_rl_accum<0, false>, k_rl_accum<1, false>};
+  const AccumKernel* kaccum = stage ? staged : direct;     // [side]
+  if (stage) for (int side = 0; side < 2; ++side) if (int rc = opt_in_lds(kaccum[side], tab, RL_TAB_LDS)) return rc;
+  auto accum = [&](int side, int want_var) {
+    const double* ring = side ? ringE : ringP;
+    const size_t len = side ? lenE : lenP;
+    const dim3 grid((unsigned)((len + (size_t)RL_E * (RL_AT / 64) - 1) / ((size_t)RL_E * (RL_AT / 64)))), block(RL_AT);
+    hipLaunchKernelGGL(kaccum[side], grid, block, stage ? tab : 0, h->stream, ring, len, K, N, (const int*)dSl, (const int*)dAl, (const int*)dCnt,
+                       (const int32_t*)dInv, (const double*)cs, want_var, side ? oE : oP);
+  };
+  const double* piv = pivot_P ? dPiv : ringP + (size_t)slots[S - 1] * lenP;      // NULL: the newest used sample's P
+  int rounds = 0, converged = 0, cnt[2] = {0, 0};
+  for (int rd = 1; rd <= max_rounds; ++rd) {
+    const int first = rd == 1 ? 1 : 0;
+    hipLaunchKernelGGL(k_rl_pivot, dim3((N + 63) / 64), dim3(64), 0, h->stream, piv, K, N, dRef, dN2);
+    if (fused) {
+      hipLaunchKernelGGL(k_rl_match, dim3(S), dim3(64), match_lds, h->stream, ringP, K, N, (const int*)dSl, (const double*)dRef, (const double*)dN2, first,
+                         dPerm, dInv, dCs, dFlag);
+    } else {
+      for (int s0 = 0; s0 < S; s0 += chunk) {
+        const int ns = std::min(chunk, S - s0);
+        hipLaunchKernelGGL(k_ref_cosine, dim3(ns, N), dim3(128), 0, h->stream, ringP, lenP, K, (const int*)dSl + s0, (const int*)dSig, N,
+                           (const double*)dRef, (const double*)dN2, N, dCv);
+        HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)ns * N * sizeof(int32_t), h->stream));
+        hipLaunchKernelGGL(k_hungarian, dim3(ns), dim3(64), hung_lds, h->stream, (const double*)dCv, N, N, 0, dCol);
+        hipLaunchKernelGGL(k_rl_finish, dim3((ns + 63) / 64), dim3(64), 0, h->stream, (const double*)dCv, (const int32_t*)dCol, N, ns, first,
+                           dPerm + (size_t)s0 * N, dInv + (size_t)s0 * N, dCs + (size_t)s0 * N, dFlag + s0);
+      }
+    }
+    hipLaunchKernelGGL(k_rl_compact, dim3(1), dim3(64), 0, h->stream, (const int32_t*)dFlag, S, dAl, dCnt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cnt, dCnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rounds = rd;
+    if (cnt[0] < 2)
+      return fail(BNMF_ESIZE, "%s: %d of the %d used samples could be aligned in round %d (a cosine that is not finite leaves a sample unmatched), at least 2 are needed",
+                  fn, cnt[0], S, rd);
+    if (cnt[1] == 0) { converged = 1; break; }
+    if (rd == max_rounds) break;
+    accum(0, 0);                                           // the next pivot: the aligned mean of the renormalised P
+    piv = oP;
+  }
+  accum(0, 1);
+  accum(1, 1);
+  HIPCHK(hipGetLastError());
+  std::vector<int32_t> hperm(SN);
+  std::vector<double> hcos(SN);
+  HIPCHK(hipMemcpyAsync(hperm.data(), dPerm, SN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hcos.data(), dCs, SN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (P_out) HIPCHK(hipMemcpyAsync(P_out, oP, RL_NROW * lenP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (E_out) HIPCHK(hipMemcpyAsync(E_out, oE, RL_NROW * lenE * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  auto gather = [&](int side, int nbmax, double* dst) -> int {
+    const size_t len = side ? lenE : lenP;
+    const auto kern = side ? k_rl_gather<1> : k_rl_gather<0>;
+    for (int s0 = 0; s0 < S; s0 += nbmax) {
+      const int nb = std::min(nbmax, S - s0);
+      hipLaunchKernelGGL(kern, dim3((unsigned)((len + 255) / 256), (unsigned)nb), dim3(256), 0, h->stream, side ? ringE : ringP, len, K, N, (const int*)dSl,
+                         (const int32_t*)dInv, (const int32_t*)dFlag, (const double*)cs, s0, dBat);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(dst + (size_t)s0 * len, dBat, (size_t)nb * len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));               // the next batch overwrites the scratch
+    }
+    return 0;
+  };
+  if (aligned_P) if (int rc = gather(0, bP, aligned_P)) return rc;
+  if (aligned_E) if (int rc = gather(1, bE, aligned_E)) return rc;
+  if (perm) std::memcpy(perm, hperm.data(), SN * sizeof(int32_t));
+  if (cosine) std::memcpy(cosine, hcos.data(), SN * sizeof(double));
+  if (confusion) for (size_t i = 0; i < (size_t)N * N; ++i) confusion[i] = 0;
+  std::memset(info, 0, sizeof *info);
+  info->n_used = S; info->n_aligned = cnt[0]; info->n_unmatched = S - cnt[0]; info->rounds = rounds; info->converged = converged;
+  info->n_changed_last = cnt[1];
+  double acc[64], mn = std::nan("");
+  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
+  int64_t mn_at = -1;
+  size_t t = 0;                                            // place in the (s, n) sequence of the aligned samples' cosines
+  for (int s = 0; s < S; ++s) {
+    const int32_t* pm = hperm.data() + (size_t)s * N;
+    if (N > 0 && pm[0] < 0) continue;                      // unmatched
+    bool ident = true;
+    for (int n = 0; n < N; ++n) {
+      const double c = hcos[(size_t)s * N + n];
+      ident = ident && pm[n] == n;
+      if (confusion) confusion[(size_t)n * N + pm[n]] += 1;
+      acc[t & 63] = acc[t & 63] + c; ++t;
+      if (mn_at < 0 || c < mn) { mn = c; mn_at = (int64_t)s * N + n; }
+    }
+    if (!ident) info->n_switched++;
+  }
+  for (int hh = 32; hh >= 1; hh >>= 1) for (int l = 0; l < hh; ++l) acc[l] = acc[l] + acc[l + hh];   // wave_tree64's order
+  info->mean_cosine = acc[0] / (double)((size_t)cnt[0] * (size_t)N);
+  info->min_cosine = mn; info->min_cosine_at = mn_at;
+  return 0;
+}
+
+extern "C" {
+
+int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
+             double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
+  return map_impl(h, "bnmf_map", {false, 0, last_n}, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
+}
+int bnmf_map_at(bnmf_handle* h, int end_iter, int n_samples, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
+                double* P_lower, double* P_upper, double* E_lower, double* E_upper, int32_t* used, bnmf_map_info* info) {
+  return map_impl(h, "bnmf_map_at", {true, end_iter, n_samples}, ci, P_mean, E_mean, A_mode, top_A, P_lower, P_upper, E_lower, E_upper, used, info);
+}
+int bnmf_waic(bnmf_handle* h, int last_n, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
+  return waic_impl(h, "bnmf_waic", {false, 0, last_n}, used, col, cell, info);
+}
+int bnmf_waic_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, bnmf_waic_info* info) {
+  return waic_impl(h, "bnmf_waic_at", {true, end_iter, n_samples}, used, col, cell, info);
+}
+int bnmf_ppc(bnmf_handle* h, int last_n, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
+  return ppc_impl(h, "bnmf_ppc", {false, 0, last_n}, used, col, cell, series, info);
+}
+int bnmf_ppc_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double* col, double* cell, double* series, bnmf_ppc_info* info) {
+  return ppc_impl(h, "bnmf_ppc_at", {true, end_iter, n_samples}, used, col, cell, series, info);
+}
+int bnmf_attribution(bnmf_handle* h, int last_n, const int32_t* used, double min_load, double* load, double* prob, double* series, bnmf_attr_info* info) {
+  return attr_impl(h, "bnmf_attribution", {false, 0, last_n}, used, min_load, load, prob, series, info);
+}
+int bnmf_attribution_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double min_load, double* load, double* prob, double* series,
+                        bnmf_attr_info* info) {
+  return attr_impl(h, "bnmf_attribution_at", {true, end_iter, n_samples}, used, min_load, load, prob, series, info);
+}
+int bnmf_mixing(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* keep, double* P_out, double* E_out, bnmf_mixing_info* info) {
+  return mixing_impl(h, "bnmf_mixing", {false, 0, last_n}, used, keep, P_out, E_out, info);
+}
+int bnmf_mixing_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* keep, double* P_out, double* E_out,
+                   bnmf_mixing_info* info) {
+  return mixing_impl(h, "bnmf_mixing_at", {true, end_iter, n_samples}, used, keep, P_out, E_out, info);
+}
+int bnmf_assign(bnmf_handle* h, int last_n, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
+                double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
+  return assign_impl(h, "bnmf_assign", {false, 0, last_n}, used, ref, R, keep, MAP_P, ci, votes, assigned, MAP_cosine, lower, upper);
+}
+int bnmf_assign_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* ref, int R, const int32_t* keep, const double* MAP_P,
+                   double ci, double* votes, int32_t* assigned, double* MAP_cosine, double* lower, double* upper) {
+  return assign_impl(h, "bnmf_assign_at", {true, end_iter, n_samples}, used, ref, R, keep, MAP_P, ci, votes, assigned, MAP_cosine, lower, upper);
+}
+int bnmf_relabel(bnmf_handle* h, int last_n, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine, int64_t* confusion,
+                 double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
+  return relabel_impl(h, "bnmf_relabel", {false, 0, last_n}, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
+}
+int bnmf_relabel_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine,
+                    int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
+  return relabel_impl(h, "bnmf_relabel_at", {true, end_iter, n_samples}, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
+}
+
+// plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:
+// 598-669) over the recorded iterations iters[]: k_label_switch, one wave per sample with the cosine matrix in the LDS; past the LDS,
+// k_ref_cosine + k_hungarian (what bnmf_assign runs) over chunks of samples whose cosines stay within LS_CHUNK_BYTES, then k_label_gather.
+int bnmf_label_switching(bnmf_handle* h, const int32_t* iters, int n_iters, const double* ref, int R, int32_t* assigned, double* cosine,
+                         int32_t* included) {
+  if (!h || !iters || !ref || !assigned || !cosine) return fail(BNMF_EINVAL, "bnmf_label_switching: null argument");
+  if (int rc = check_recorded(h, "bnmf_label_switching")) return rc;
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "bnmf_label_switching: nothing recorded yet");
+  if (n_iters < 0) return fail(BNMF_EINVAL, "bnmf_label_switching: n_iters < 0");
+  if (R < 1) return fail(BNMF_EINVAL, "bnmf_label_switching: empty reference");
+  const int K = h->cfg.K, N = h->cfg.N;
+  std::vector<int> slots(n_iters);
+  for (int i = 0; i < n_iters; ++i) {
+    if (int rc = check_kept(h, "bnmf_label_switching", iters[i], iters[i])) return rc;
+    slots[i] = (int)((size_t)(iters[i] - 1) % (size_t)h->wcap);
+  }
+  if (n_iters == 0) return 0;
+  if (int rc = post_sync(h)) return rc;
+  const int tr = N > R ? 1 : 0, nrow = tr ? R : N, ncol = tr ? N : R;
+  const size_t hung_lds = hungarian_lds_bytes(nrow, ncol);
+  const size_t ls_lds = (size_t)N * R * sizeof(double) + hung_lds;
+  const bool fused = ls_lds <= LDS_CAP;
+  if (!fused && hung_lds > LDS_CAP) return fail(BNMF_ESIZE, "bnmf_label_switching: %d x %d assignment problem exceeds the LDS of one workgroup", nrow, ncol);
+  const size_t per = (size_t)N * R * sizeof(double);
+  const int chunk = fused ? 0 : (int)std::max<size_t>(1, std::min<size_t>((size_t)n_iters, LS_CHUNK_BYTES / per));
+  const size_t out_n = (size_t)n_iters * N;
+  double *dRef, *dN2, *dCs, *dCos; int *dSl, *dSig; int32_t *dAs, *dInc, *dCol;
+  if (int rc = carve(h, [&](Carve& c) {
+        dRef = c.take<double>((size_t)K * R); dN2 = c.take<double>(R); dSl = c.take<int>(n_iters);
+        dAs = c.take<int32_t>(out_n); dCs = c.take<double>(out_n); dInc = c.take<int32_t>(out_n); dSig = c.take<int>(N);
+        dCos = c.take<double>((size_t)chunk * N * R); dCol = c.take<int32_t>((size_t)chunk * nrow);
+      })) return rc;
+  std::vector<double> rn2;
+  if (int rc = catalogue_upload(ref, K, R, dRef, dN2, rn2)) return rc;
+  HIPCHK(hipMemcpy(dSl, slots.data(), (size_t)n_iters * sizeof(int), hipMemcpyHostToDevice));
+  const double* ringP = h->arr[BNMF_P].ring;
+  const double* ringA = h->arr[BNMF_A].ring;
+  if (fused) {
+    if (int rc = opt_in_lds(k_label_switch, ls_lds, ls_lds)) return rc;
+    hipLaunchKernelGGL(k_label_switch, dim3(n_iters), dim3(64), ls_lds, h->stream, ringP, ringA, K, N, (const int*)dSl, (const double*)dRef,
+                       (const double*)dN2, R, dAs, dCs, dInc);
+    HIPCHK(hipGetLastError());
+  } else {
+    std::vector<int> sig(N);
+    for (int n = 0; n < N; ++n) sig[n] = n;
+    HIPCHK(hipMemcpy(dSig, sig.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = opt_in_lds(k_hungarian, hung_lds, hung_lds)) return rc;
+    for (int s0 = 0; s0 < n_iters; s0 += chunk) {
+      const int ns = std::min(chunk, n_iters - s0);
+      hipLaunchKernelGGL(k_ref_cosine, dim3(ns, N), dim3(128), 0, h->stream, ringP, (size_t)K * N, K, (const int*)dSl + s0, (const int*)dSig, N,
+                         (const double*)dRef, (const double*)dN2, R, dCos);
+      HIPCHK(hipMemsetAsync(dCol, 0xff, (size_t)ns * nrow * sizeof(int32_t), h->stream));
+      hipLaunchKernelGGL(k_hungarian, dim3(ns), dim3(64), hung_lds, h->stream, (const double*)dCos, N, R, tr, dCol);
+      hipLaunchKernelGGL(k_label_gather, dim3((ns + 63) / 64), dim3(64), 0, h->stream, (const double*)dCos, (const int32_t*)dCol, N, R, ns, ringA,
+                         (const int*)dSl + s0, dAs + (size_t)s0 * N, dCs + (size_t)s0 * N, dInc + (size_t)s0 * N);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  HIPCHK(hipMemcpyAsync(assigned, dAs, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(cosine, dCs, out_n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (included) HIPCHK(hipMemcpyAsync(included, dInc, out_n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n_iters; ++i)
+    if (assigned[(size_t)i * N] == -2 && N > 0) return fail(BNMF_ESTATE, "bnmf_label_switching: iteration %d has no assignment (a cosine is not finite)", iters[i]);
+  return 0;
+}
+
+}  // extern "C"

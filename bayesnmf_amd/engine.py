@@ -196,8 +196,12 @@ def _chk(rc):
         raise BnmfError(rc, lib().bnmf_last_error().decode())
 
 
+_IP = C.POINTER(C.c_int32)
+
+
 def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    """Pointer to a float64 array's data; None stays None (an optional argument of the ABI)."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def device_count():
@@ -402,6 +406,27 @@ class Engine:
                                         cap_checks, C.byref(nc)))
         return rows[:nr.value].copy(), maps[:nc.value].copy(), state
 
+    # ---- the posterior calls on a recorded range: three helpers, then one method per call ----
+    def _used(self, name, used, last_n):
+        """The used argument of call `name`: (pointer to its int32 copy or None, S = the number of used samples)."""
+        if used is None:
+            return None, max(int(last_n), 0)
+        u = np.ascontiguousarray(used, dtype=np.int32)
+        if u.size != last_n:
+            raise BnmfError(-2, f"{name}: used has {u.size} entries for {last_n} samples")
+        return u.ctypes.data_as(_IP), int((u != 0).sum())       # (the pointer keeps u alive)
+
+    def _range_call(self, name, last_n, end_iter, *args):
+        """bnmf_<name> over the last `last_n` samples, or with end_iter bnmf_<name>_at over the `last_n` that end at iteration end_iter."""
+        if end_iter is None:
+            _chk(getattr(lib(), "bnmf_" + name)(self._h, last_n, *args))
+        else:
+            _chk(getattr(lib(), "bnmf_" + name + "_at")(self._h, int(end_iter), last_n, *args))
+
+    @staticmethod
+    def _info(info):
+        return {name: getattr(info, name) for name, _ in info._fields_ if name != "_pad"}
+
     def assign(self, last_n, reference_P, used=None, keep=None, MAP_P=None, credible_interval=0.95, end_iter=None):
         """assign_signatures_ensemble_ over recorded samples: votes (N x R), assigned reference per signature (-1 = not
         kept), cosine of the MAP estimate and credible bounds of the per-sample cosines.  The samples are the last `last_n`
@@ -409,17 +434,14 @@ class Engine:
         N = self.N
         ref = np.asfortranarray(reference_P, dtype=np.float64)
         R = ref.shape[1]
-        ip = C.POINTER(C.c_int32)
         u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
         kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.int32)
         mp = None if MAP_P is None else np.asfortranarray(MAP_P, dtype=np.float64)
         votes, asg = np.zeros(N * R), np.empty(N, dtype=np.int32)
         mc, lo, hi = np.empty(N), np.empty(N), np.empty(N)
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_assign if end_iter is None else lib().bnmf_assign_at)(
-            self._h, *rng, None if u is None else u.ctypes.data_as(ip), _dp(ref.ravel(order="F")), R,
-            None if kp is None else kp.ctypes.data_as(ip), None if mp is None else _dp(mp.ravel(order="F")),
-            float(credible_interval), _dp(votes), asg.ctypes.data_as(ip), _dp(mc), _dp(lo), _dp(hi)))
+        self._range_call("assign", last_n, end_iter, None if u is None else u.ctypes.data_as(_IP), _dp(ref.ravel(order="F")), R,
+                         None if kp is None else kp.ctypes.data_as(_IP), None if mp is None else _dp(mp.ravel(order="F")),
+                         float(credible_interval), _dp(votes), asg.ctypes.data_as(_IP), _dp(mc), _dp(lo), _dp(hi))
         return dict(votes=votes.reshape((N, R), order="F"), assigned=asg, MAP_cosine=mc, lower_cosine=lo, upper_cosine=hi)
 
     def map(self, last_n, credible_interval=0.95, end_iter=None):
@@ -431,10 +453,8 @@ class Engine:
         Pl, Pu, El, Eu = (np.empty(K * N), np.empty(K * N), np.empty(N * G), np.empty(N * G)) if ci else (None,) * 4
         used = np.empty(last_n, dtype=np.int32)
         info = BnmfMapInfo()
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_map if end_iter is None else lib().bnmf_map_at)(
-            self._h, *rng, float(credible_interval) if ci else 0.0, _dp(Pm), _dp(Em), _dp(Am), _dp(top),
-            *[_dp(a) if a is not None else None for a in (Pl, Pu, El, Eu)], used.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)))
+        self._range_call("map", last_n, end_iter, float(credible_interval) if ci else 0.0, _dp(Pm), _dp(Em), _dp(Am), _dp(top),
+                         _dp(Pl), _dp(Pu), _dp(El), _dp(Eu), used.ctypes.data_as(_IP), C.byref(info))
         f = lambda a, shp: None if a is None else a.reshape(shp, order="F")   # noqa: E731
         npat = min(info.n_patterns, 5)
         return dict(P=f(Pm, (K, N)), E=f(Em, (N, G)), A=Am.reshape(1, N), used=used.astype(bool),
@@ -447,17 +467,12 @@ class Engine:
         end_iter of the `last_n` that end at iteration end_iter (bnmf_waic / bnmf_waic_at), on the device.  Returns the info fields;
         with pointwise also lppd_col, p_waic_col, mean_loglik_col (G) and lppd_cell, p_waic_cell (K x G)."""
         K, G = self.K, self.G
-        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
-        if u is not None and u.size != last_n:
-            raise BnmfError(-2, f"waic: used has {u.size} entries for {last_n} samples")
+        u, _ = self._used("waic", used, last_n)
         col = np.empty(3 * G) if pointwise else None
         cell = np.empty(2 * K * G) if pointwise else None
         info = BnmfWaicInfo()
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_waic if end_iter is None else lib().bnmf_waic_at)(
-            self._h, *rng, None if u is None else u.ctypes.data_as(C.POINTER(C.c_int32)), None if col is None else _dp(col),
-            None if cell is None else _dp(cell), C.byref(info)))
-        out = {name: getattr(info, name) for name, _ in BnmfWaicInfo._fields_}
+        self._range_call("waic", last_n, end_iter, u, _dp(col), _dp(cell), C.byref(info))
+        out = self._info(info)
         if pointwise:
             out.update(lppd_col=col[:G], p_waic_col=col[G:2 * G], mean_loglik_col=col[2 * G:],
                        lppd_cell=cell[:K * G].reshape((K, G), order="F"), p_waic_cell=cell[K * G:].reshape((K, G), order="F"))
@@ -470,19 +485,13 @@ class Engine:
         replicate and p = #(T_rep >= T_obs) / S, for T1 and T2), series (4 x S) with its rows by name (PPC_SERIES_ROWS: the whole-matrix
         values per used sample); with pointwise also mean_cell, var_cell, p_less_cell, p_equal_cell and pit = p_less + 0.5 p_equal (K x G)."""
         K, G = self.K, self.G
-        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
-        if u is not None and u.size != last_n:
-            raise BnmfError(-2, f"ppc: used has {u.size} entries for {last_n} samples")
-        S = int(last_n) if u is None else int((u != 0).sum())
+        u, S = self._used("ppc", used, last_n)
         col = np.empty((6, G))
-        series = np.empty((4, max(S, 0)))
+        series = np.empty((4, S))
         cell = np.empty((4, K * G)) if pointwise else None
         info = BnmfPpcInfo()
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_ppc if end_iter is None else lib().bnmf_ppc_at)(
-            self._h, *rng, None if u is None else u.ctypes.data_as(C.POINTER(C.c_int32)), _dp(col), None if cell is None else _dp(cell),
-            _dp(series), C.byref(info)))
-        out = {name: getattr(info, name) for name, _ in BnmfPpcInfo._fields_}
+        self._range_call("ppc", last_n, end_iter, u, _dp(col), _dp(cell), _dp(series), C.byref(info))
+        out = self._info(info)
         out.update(col=col, series=series)
         out.update({name: col[i] for i, name in enumerate(PPC_COL_ROWS)})
         out.update({name: series[i] for i, name in enumerate(PPC_SERIES_ROWS)})
@@ -499,19 +508,13 @@ class Engine:
         samples whose load is >= min_load), series (S x N: the cohort's load per used sample and factor); with prob also prob
         (K x N x G: the probability that a mutation of type k in tumour g came from factor n)."""
         K, G, N = self.K, self.G, self.N
-        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
-        if u is not None and u.size != last_n:
-            raise BnmfError(-2, f"attribution: used has {u.size} entries for {last_n} samples")
-        S = int(last_n) if u is None else int((u != 0).sum())
+        u, S = self._used("attribution", used, last_n)
         load = np.empty((4, N * G))
-        series = np.empty((max(S, 0), N))
+        series = np.empty((S, N))
         pr = np.empty(K * N * G) if prob else None
         info = BnmfAttrInfo()
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_attribution if end_iter is None else lib().bnmf_attribution_at)(
-            self._h, *rng, None if u is None else u.ctypes.data_as(C.POINTER(C.c_int32)), float(min_load), _dp(load),
-            None if pr is None else _dp(pr), _dp(series), C.byref(info)))
-        out = {name: getattr(info, name) for name, _ in BnmfAttrInfo._fields_ if name != "_pad"}
+        self._range_call("attribution", last_n, end_iter, u, float(min_load), _dp(load), _dp(pr), _dp(series), C.byref(info))
+        out = self._info(info)
         out.update(load=np.stack([row.reshape((N, G), order="F") for row in load]), series=series)
         out.update({name: out["load"][i] for i, name in enumerate(ATTR_LOAD_ROWS)})
         if prob:
@@ -524,21 +527,15 @@ class Engine:
         samples: a used with gaps is treated as one contiguous series.  keep (length N, None = all): the factors that enter the summary.
         Returns the info fields; with arrays also, for every name in MIX_ROWS, name_P (K x N) and name_E (N x G)."""
         K, G, N = self.K, self.G, self.N
-        ip = C.POINTER(C.c_int32)
-        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
-        if u is not None and u.size != last_n:
-            raise BnmfError(-2, f"mixing: used has {u.size} entries for {last_n} samples")
+        u, _ = self._used("mixing", used, last_n)
         kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.int32)
         if kp is not None and kp.size != N:
             raise BnmfError(-2, f"mixing: keep has {kp.size} entries for {N} factors")
         oP = np.empty((NMIX, K * N)) if arrays else None
         oE = np.empty((NMIX, N * G)) if arrays else None
         info = BnmfMixingInfo()
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_mixing if end_iter is None else lib().bnmf_mixing_at)(
-            self._h, *rng, None if u is None else u.ctypes.data_as(ip), None if kp is None else kp.ctypes.data_as(ip),
-            None if oP is None else _dp(oP), None if oE is None else _dp(oE), C.byref(info)))
-        out = {name: getattr(info, name) for name, _ in BnmfMixingInfo._fields_}
+        self._range_call("mixing", last_n, end_iter, u, None if kp is None else kp.ctypes.data_as(_IP), _dp(oP), _dp(oE), C.byref(info))
+        out = self._info(info)
         if arrays:
             for i, name in enumerate(MIX_ROWS):
                 out[name + "_P"] = oP[i].reshape((K, N), order="F")
@@ -554,11 +551,7 @@ class Engine:
         P_mean, P_var (K x N) and E_mean, E_var (N x G) of the aligned, renormalised samples; with aligned also aligned_P (S x K x N)
         and aligned_E (S x N x G), the aligned samples themselves (NaN for an unmatched one)."""
         K, G, N = self.K, self.G, self.N
-        ip = C.POINTER(C.c_int32)
-        u = None if used is None else np.ascontiguousarray(used, dtype=np.int32)
-        if u is not None and u.size != last_n:
-            raise BnmfError(-2, f"relabel: used has {u.size} entries for {last_n} samples")
-        S = max(int(last_n) if u is None else int((u != 0).sum()), 0)
+        u, S = self._used("relabel", used, last_n)
         pv = None
         if pivot_P is not None:
             pv = np.asarray(pivot_P, dtype=np.float64)
@@ -570,12 +563,9 @@ class Engine:
         aP = np.empty((S, K * N)) if aligned else None
         aE = np.empty((S, N * G)) if aligned else None
         info = BnmfRelabelInfo()
-        rng = (last_n,) if end_iter is None else (int(end_iter), last_n)
-        _chk((lib().bnmf_relabel if end_iter is None else lib().bnmf_relabel_at)(
-            self._h, *rng, None if u is None else u.ctypes.data_as(ip), None if pv is None else _dp(pv), int(max_rounds), perm.ctypes.data_as(ip),
-            _dp(cos), conf.ctypes.data_as(C.POINTER(C.c_int64)), _dp(oP), _dp(oE), None if aP is None else _dp(aP),
-            None if aE is None else _dp(aE), C.byref(info)))
-        out = {name: getattr(info, name) for name, _ in BnmfRelabelInfo._fields_ if name != "_pad"}
+        self._range_call("relabel", last_n, end_iter, u, _dp(pv), int(max_rounds), perm.ctypes.data_as(_IP), _dp(cos),
+                         conf.ctypes.data_as(C.POINTER(C.c_int64)), _dp(oP), _dp(oE), _dp(aP), _dp(aE), C.byref(info))
+        out = self._info(info)
         out.update(perm=perm, cosine=cos, confusion=conf, P_mean=oP[0].reshape((K, N), order="F"), P_var=oP[1].reshape((K, N), order="F"),
                    E_mean=oE[0].reshape((N, G), order="F"), E_var=oE[1].reshape((N, G), order="F"))
         if aligned:
