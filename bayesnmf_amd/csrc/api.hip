@@ -36,6 +36,7 @@
 #include "attribution.h"
 #include "mixing.h"
 #include "relabel.h"
+#include "project.h"
 
 using namespace bnmf;
 

@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel (each with its _at form) and bnmf_label_switching.  Host code only: the kernels are in kernels.h,
-// waic.h, ppc.h, attribution.h, mixing.h and relabel.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project (each with its _at form) and bnmf_label_switching.  Host code only: the kernels are
+// in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h and project.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -696,6 +696,112 @@ static int relabel_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* 
   return 0;
 }
 
+// Exposures of new tumours over the samples of r that used[] flags: k_map_colsum once, then per batch of samples k_proj_x (the columns
+// of x that take part, side by side), k_project (the refit: a_s[n,j] and the fit values in the scratch), attribution.h's k_attr_share
+// and k_attr_stats with G := J, k_proj_fit (project.h); the info fields are sequential scans on the host.
+static_assert(BNMF_PROJ_NLOAD == AT_NLOAD && BNMF_PROJ_NFIT == PJ_NFIT && BNMF_PROJ_MAX_N == PJ_MAX_N, "project.h, attribution.h and bnmf.h disagree");
+static constexpr size_t PROJ_SCRATCH_CAP = (size_t)256 << 20;   // bytes of a batch's blocks of the scratch
+static int project_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const double* X, int J, int n_steps, double min_load, double* load,
+                        double* fit, double* series, double* exposures, bnmf_project_info* info) {
+  if (int rc = range_enter(h, fn, h && info && X, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N;
+  if (h->cfg.likelihood == BNMF_NORMAL)
+    return fail(BNMF_EMODEL, "%s: the handle has the Normal likelihood; its refit is a different algorithm (least squares, not the KL update) and is out of scope", fn);
+  if (J < 1) return fail(BNMF_EINVAL, "%s: J = %d, at least 1 new tumour is needed", fn, J);
+  if (n_steps < 1 || n_steps > 100000) return fail(BNMF_EINVAL, "%s: n_steps = %d is not in 1..100000", fn, n_steps);
+  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<double> Xt((size_t)K * J), tX(J);            // X k-major, and t_j = sum_k X[k,j], k ascending from +0.0
+  for (int j = 0; j < J; ++j) {
+    double t = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double v = X[(size_t)k + (size_t)K * j];
+      if (!(v >= 0.0) || std::isinf(v)) return fail(BNMF_EINVAL, "%s: X[%d, %d] = %g is not a finite number >= 0", fn, k, j, v);
+      Xt[(size_t)k * J + j] = v;
+      t = t + v;
+    }
+    tX[j] = t;
+  }
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the exposures needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (N > PJ_MAX_N) return fail(BNMF_ESIZE, "%s: N = %d factors but at most BNMF_PROJ_MAX_N = %d fit a lane's columns of the LDS", fn, N, PJ_MAX_N);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const int NS = proj_row_stride(N);
+  const size_t NJ = (size_t)N * J, KNS = (size_t)K * NS, lenP = (size_t)K * N;
+  const size_t per = ((exposures ? 2 : 1) * NJ + (size_t)(1 + PJ_NFIT) * J + KNS + N) * sizeof(double);   // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, PROJ_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_PROJ_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>({want, (long long)S, 65535LL});                                  // (a batch is the grid's y)
+  // x staged in the LDS only beside e and g there; with e and g in registers the wave-uniform reads through the caches measured faster
+  const bool fits = proj_lds_bytes(K, N, true) <= LDS_CAP;
+  bool stage = fits && N > PJ_MAX_NT;
+  if (const char* e = getenv("BNMF_PROJ_STAGE")) stage = fits && atoi(e) != 0;                             // tests, tools: the other form
+  const size_t lds = proj_lds_bytes(K, N, stage);
+  if (lds > LDS_CAP) return fail(BNMF_ESIZE, "%s: N = %d factors need %zu bytes of LDS", fn, N, lds);      // (unreachable for N <= BNMF_PROJ_MAX_N)
+  double *cs, *dXt, *dtX, *dxg, *dscr, *dfs, *du, *dst, *dload, *dser, *dfst, *dfit, *dexp; int *dslots, *dnin, *didx;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); dXt = c.take<double>((size_t)K * J); dtX = c.take<double>(J); dxg = c.take<double>((size_t)Sb * KNS);
+        dscr = c.take<double>((size_t)Sb * NJ); dfs = c.take<double>((size_t)Sb * PJ_NFIT * J); du = c.take<double>((size_t)Sb * J);
+        dst = c.take<double>(AT_NLOAD * NJ); dload = c.take<double>(AT_NLOAD * NJ); dser = c.take<double>((size_t)S * N);
+        dfst = c.take<double>((size_t)PJ_NFIT * J); dfit = c.take<double>((size_t)PJ_NFIT * J);
+        dexp = exposures ? c.take<double>((size_t)Sb * NJ) : nullptr;
+        dslots = c.take<int>(S); dnin = c.take<int>(Sb); didx = c.take<int>((size_t)Sb * N);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dXt, Xt.data(), Xt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dtX, tX.data(), tX.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  const double* ringP = h->arr[BNMF_P].ring;
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, ringP, lenP, K, N, (const int*)dslots, cs);
+  using ProjKernel = decltype(&k_project<8, true>);
+  const ProjKernel staged[5] = {k_project<0, true>, k_project<8, true>, k_project<16, true>, k_project<24, true>, k_project<32, true>};
+  const ProjKernel direct[5] = {k_project<0, false>, k_project<8, false>, k_project<16, false>, k_project<24, false>, k_project<32, false>};
+  const ProjKernel kern = (stage ? staged : direct)[N <= PJ_MAX_NT ? NS / 8 : 0];
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  const int T = N <= PJ_MAX_NT ? PJ_T : PJ_TL;
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0), first = s0 == 0 ? 1 : 0, last = s0 + nb == S ? 1 : 0;
+    hipLaunchKernelGGL(k_proj_x, dim3(nb), dim3(256), 0, h->stream, ringP, (const double*)h->arr[BNMF_A].ring, lenP, K, N, NS, (const int*)dslots + s0,
+                       (const double*)cs + (size_t)s0 * N, dxg, dnin, didx);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((J + T - 1) / T), (unsigned)nb), dim3(T), lds, h->stream, (const double*)dxg, (const int*)dnin, (const int*)didx,
+                       (const double*)dXt, (const double*)dtX, K, N, J, n_steps, dscr, dfs);
+    const size_t nsj = (size_t)nb * J;
+    hipLaunchKernelGGL(k_attr_share, dim3((unsigned)((nsj + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, J, du);
+    hipLaunchKernelGGL(k_attr_stats, dim3((unsigned)((size_t)nb * N + (NJ + AT_TT - 1) / AT_TT)), dim3(AT_TT), 0, h->stream, (const double*)dscr,
+                       (const double*)du, nb, N, J, S, s0, last, min_load, dst, dser, dload);
+    hipLaunchKernelGGL(k_proj_fit, dim3((unsigned)((J + 255) / 256)), dim3(256), 0, h->stream, (const double*)dfs, nb, J, S, first, last, dfst, dfit);
+    HIPCHK(hipGetLastError());
+    if (exposures) {
+      hipLaunchKernelGGL(k_proj_exposures, dim3((unsigned)(((size_t)nb * NJ + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, J, dexp);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(exposures + (size_t)s0 * NJ, dexp, (size_t)nb * NJ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));             // the next batch overwrites the scratch
+    }
+  }
+  std::vector<double> hs((size_t)S * N), hp(NJ), hf((size_t)PJ_NFIT * J);
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, (size_t)S * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hp.data(), dload + 3 * NJ, NJ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hf.data(), dfit, hf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (load) HIPCHK(hipMemcpyAsync(load, dload, AT_NLOAD * NJ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), hs.size() * sizeof(double));
+  if (fit) std::memcpy(fit, hf.data(), hf.size() * sizeof(double));
+  double t = 0.0;
+  for (size_t i = 0; i < (size_t)S * N; ++i) t += hs[i];
+  int64_t np = 0;
+  for (size_t i = 0; i < NJ; ++i) np += hp[i] >= 0.5 ? 1 : 0;
+  double mx = 0.0, mn = std::nan(""); int64_t mn_at = -1;
+  for (int j = 0; j < J; ++j) {
+    const double c = hf[j], v = hf[2 * (size_t)J + j];
+    if (v > mx) mx = v;
+    if (!std::isnan(c) && (mn_at < 0 || c < mn)) { mn = c; mn_at = j; }
+  }
+  info->n_used = S; info->n_steps = n_steps; info->n_present = np; info->min_load = min_load; info->total = t / (double)S;
+  info->max_rel_change = mx; info->min_cosine = mn; info->min_cosine_at = mn_at;
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -747,6 +853,15 @@ int bnmf_relabel(bnmf_handle* h, int last_n, const int32_t* used, const double* 
 int bnmf_relabel_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* pivot_P, int max_rounds, int32_t* perm, double* cosine,
                     int64_t* confusion, double* P_out, double* E_out, double* aligned_P, double* aligned_E, bnmf_relabel_info* info) {
   return relabel_impl(h, "bnmf_relabel_at", {true, end_iter, n_samples}, used, pivot_P, max_rounds, perm, cosine, confusion, P_out, E_out, aligned_P, aligned_E, info);
+}
+
+int bnmf_project(bnmf_handle* h, int last_n, const int32_t* used, const double* X, int J, int n_steps, double min_load, double* load, double* fit,
+                 double* series, double* exposures, bnmf_project_info* info) {
+  return project_impl(h, "bnmf_project", {false, 0, last_n}, used, X, J, n_steps, min_load, load, fit, series, exposures, info);
+}
+int bnmf_project_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* X, int J, int n_steps, double min_load, double* load,
+                    double* fit, double* series, double* exposures, bnmf_project_info* info) {
+  return project_impl(h, "bnmf_project_at", {true, end_iter, n_samples}, used, X, J, n_steps, min_load, load, fit, series, exposures, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

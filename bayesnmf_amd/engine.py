@@ -90,6 +90,11 @@ class BnmfAttrInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("_pad", C.c_int32), ("n_present", C.c_int64), ("min_load", C.c_double), ("total", C.c_double)]
 
 
+class BnmfProjectInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_steps", C.c_int32), ("n_present", C.c_int64), ("min_load", C.c_double), ("total", C.c_double),
+                ("max_rel_change", C.c_double), ("min_cosine", C.c_double), ("min_cosine_at", C.c_int64)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -97,6 +102,7 @@ class BnmfRelabelInfo(C.Structure):
 
 
 ATTR_LOAD_ROWS = ["load_mean", "load_var", "share", "p_present"]
+PROJ_FIT_ROWS = ["cosine", "rel_l1", "rel_change"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -113,7 +119,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
-               "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at"]
+               "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at"]
 
 
 def lib():
@@ -170,6 +176,8 @@ def lib():
         L.bnmf_ppc_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, dp, dp, C.POINTER(BnmfPpcInfo)]
         L.bnmf_attribution.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
         L.bnmf_attribution_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
+        L.bnmf_project.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfProjectInfo)]
+        L.bnmf_project_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfProjectInfo)]
         lp = C.POINTER(C.c_int64)
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
@@ -519,6 +527,34 @@ class Engine:
         out.update({name: out["load"][i] for i, name in enumerate(ATTR_LOAD_ROWS)})
         if prob:
             out["prob"] = pr.reshape((K, N, G), order="F")
+        return out
+
+    def project(self, last_n, X, used=None, end_iter=None, n_steps=200, min_load=1.0, exposures=False):
+        """Exposures of the new tumours X (K x J, not negative) under the signatures of the recorded samples flagged in used (length
+        last_n, oldest first; None = all) of the last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter
+        (bnmf_project / bnmf_project_at), on the device: every column is refitted to every sample's renormalised signatures by n_steps
+        steps of the KL multiplicative update.  Returns the info fields, load (4 x N x J) with its rows also by name (ATTR_LOAD_ROWS:
+        the mean and variance over the used samples of the exposure of tumour j to factor n, its mean share of the tumour, and the
+        fraction of samples whose exposure is >= min_load), fit (3 x J) with its rows by name (PROJ_FIT_ROWS: the mean cosine and mean
+        relative L1 error of the fit, the largest relative change of the last step), series (S x N: the exposures summed over the new
+        tumours); with exposures also exposures (S x N x J), every used sample's own."""
+        K, N = self.K, self.N
+        Xf = np.asfortranarray(X, dtype=np.float64)
+        if Xf.ndim != 2 or Xf.shape[0] != K:
+            raise BnmfError(-2, f"project: X has shape {Xf.shape}, K = {K} rows are needed")
+        J = Xf.shape[1]
+        u, S = self._used("project", used, last_n)
+        load, fit, series = np.empty((4, N * J)), np.empty((3, J)), np.empty((S, N))
+        ex = np.empty((S, N * J)) if exposures else None
+        info = BnmfProjectInfo()
+        self._range_call("project", last_n, end_iter, u, _dp(Xf.ravel(order="F")), J, int(n_steps), float(min_load), _dp(load), _dp(fit), _dp(series),
+                         _dp(ex), C.byref(info))
+        out = self._info(info)
+        out.update(load=np.stack([row.reshape((N, J), order="F") for row in load]), fit=fit, series=series)
+        out.update({name: out["load"][i] for i, name in enumerate(ATTR_LOAD_ROWS)})
+        out.update({name: fit[i] for i, name in enumerate(PROJ_FIT_ROWS)})
+        if exposures:
+            out["exposures"] = np.stack([row.reshape((N, J), order="F") for row in ex]) if S else np.empty((0, N, J))
         return out
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):

@@ -681,8 +681,35 @@ class bayesNMF_sampler:
             out["prob"] = r["prob"]
         return out
 
+    def get_projection(self, new_data, end_iter=None, n_samples=None, idx="MAP_idx", n_steps=200, min_load=1.0, credible_interval=0.95):
+        """Exposures of new tumours under the recorded signatures, on the device (bnmf_project_at; not in the reference): new_data is
+        a K x J matrix of counts (or other non-negative values) of tumours the chain has not seen — a validation cohort, one patient,
+        a bootstrap.  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last MAP_over samples),
+        restricted to `idx` ("MAP_idx": those whose A equals the mode of the range; None: every sample; else a vector of recorded
+        iterations), every column is refitted to every sample's renormalised signatures by n_steps steps of the KL multiplicative
+        update, so the uncertainty of the signatures reaches the exposures.
+        Returns dict(exposure_mean, exposure_sd, share, p_present, lower, upper: N x J arrays — the mean and standard deviation over
+        the samples of the exposure of tumour j to signature n, its mean share of the tumour, the fraction of samples in which it
+        carries at least min_load mutations, and the credible_interval bounds (quantile type 7, computed here from the per-sample
+        exposures); fit: a data frame with one row per new tumour — cosine, rel_l1 (the means over the samples of the cosine and the
+        relative L1 error of the fit) and max_rel_change (how far the last step still moved the exposures, relative to the tumour's
+        total); n_used, n_steps, n_present, total, max_rel_change, min_cosine, min_cosine_at).  n_steps = 200 is a convention;
+        max_rel_change is how to judge it.  Factor n is taken to be the same signature in every sample, as get_MAP takes it."""
+        if not hasattr(self._chain, "project"):
+            raise ValueError("get_projection needs an engine that refits new data to its recorded samples (project); this engine_factory's cannot")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.project(n, np.asarray(new_data, dtype=float), used=used, n_steps=n_steps, min_load=min_load, exposures=True, **kw)
+        ex = np.asarray(r["exposures"], dtype=float)
+        a = (1.0 - float(credible_interval)) / 2.0
+        out = dict(exposure_mean=r["load_mean"], exposure_sd=np.sqrt(r["load_var"]), share=r["share"], p_present=r["p_present"],
+                   lower=np.quantile(ex, a, axis=0), upper=np.quantile(ex, 1.0 - a, axis=0),
+                   fit=pd.DataFrame(dict(cosine=r["cosine"], rel_l1=r["rel_l1"], max_rel_change=r["rel_change"])))
+        out.update({k: r[k] for k in ("n_used", "n_steps", "n_present", "total", "max_rel_change", "min_cosine", "min_cosine_at")})
+        self.log(f"Projection: J = {ex.shape[2]}, {r['n_steps']} steps, max_rel_change {r['max_rel_change']:.3g}, min_cosine {r['min_cosine']:.4f}", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

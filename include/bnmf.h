@@ -309,6 +309,39 @@ int bnmf_attribution(bnmf_handle*, int last_n, const int32_t* used, double min_l
 int bnmf_attribution_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double min_load,
                         double* load, double* prob, double* series, bnmf_attr_info* info);
 
+/* Exposures of new tumours under the recorded signatures, on the device: X (K x J, column-major; counts or any
+ * non-negative real values) is a second set of tumours — a validation cohort, one patient, a bootstrap of the data.  For every recorded
+ * sample flagged in used[] (oldest first; NULL = all) every column of X is refitted to the sample's renormalised signatures
+ * x[k,n] = P_s[k,n] / colSums(P_s)[n] by n_steps steps of the KL multiplicative update (EM), started from equal exposures that sum to the
+ * column's total; a factor with A_s[n] == 0 or an all-zero column takes no part and has exposure +0.0.  No random number is drawn.
+ * load [BNMF_PROJ_NLOAD][N*J], each row laid out as E (n + N j): over the used samples the mean and the variance (S - 1 form) of the
+ *   exposure e_s[n,j], the mean of e_s[n,j] / sum_n' e_s[n',j], and #(e_s >= min_load) / S: bnmf_attribution's four rows.
+ * fit [BNMF_PROJ_NFIT][J]: per new tumour the mean over the used samples of the cosine between the column and its fit x e (NaN where a
+ *   sample's cosine is: an all-zero column, or a sample without factors), the mean of sum_k |X - x e| / sum_k X, and the largest over
+ *   the samples of max_n |e_n(last step) - e_n(the step before)| / sum_k X: how far from converged n_steps left the refit.
+ * series [S][N] row-major: the exposures summed over the new tumours, per used sample.
+ * exposures [S][N*J]: every used sample's exposures, each laid out as E (caller-sized; they leave the device in batches).
+ * info: total and n_present as bnmf_attribution's; max_rel_change the largest entry of fit row 2; min_cosine the smallest entry of fit
+ *   row 0 that is not NaN and min_cosine_at its j (the first wins a tie; NaN and -1 if there is none).
+ * load, fit, series and exposures may each be NULL.  Only + * /, sqrt and comparisons in a fixed order: the same call gives the same
+ * bits, whatever the batches and wherever a tumour stands in X.  Read-only for the chain; none of its streams is consumed.
+ * bnmf_project_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_project(h, n, ...) is bnmf_project_at(h, iter, n, ...).  Refused before any device work: null info or X, a used[] value other than
+ * 0 / 1 (the index named), J < 1, n_steps outside 1..100000, a min_load that is NaN, infinite or negative, a cell of X that is NaN,
+ * infinite or negative (the first bad cell [k, j] named) with BNMF_EINVAL; the Normal likelihood with BNMF_EMODEL (its refit is a
+ * different algorithm); fewer than 2 used samples or N > BNMF_PROJ_MAX_N with BNMF_ESIZE; window = 0 or a poisoned handle with
+ * BNMF_ESTATE. */
+#define BNMF_PROJ_NLOAD 4      /* load rows: mean, variance (S - 1 form), mean share, probability of presence: bnmf_attribution's */
+#define BNMF_PROJ_NFIT  3      /* fit rows per new tumour: mean cosine, mean relative L1 error, largest last-step change */
+#define BNMF_PROJ_MAX_N 128
+typedef struct { int32_t n_used, n_steps; int64_t n_present; double min_load, total, max_rel_change, min_cosine;
+                 int64_t min_cosine_at /* j; -1 if none */; } bnmf_project_info;
+int bnmf_project(bnmf_handle*, int last_n, const int32_t* used, const double* X /* K x J column-major */, int J, int n_steps,
+                 double min_load, double* load /* [4][N*J], rows laid out as E: n + N j */, double* fit /* [3][J] */,
+                 double* series /* [S][N] */, double* exposures /* [S][N*J], each sample laid out as E */, bnmf_project_info* info);
+int bnmf_project_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const double* X, int J, int n_steps,
+                    double min_load, double* load, double* fit, double* series, double* exposures, bnmf_project_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

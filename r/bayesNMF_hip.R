@@ -243,6 +243,42 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (prob) out$prob <- array(r$prob, c(K, N, G))
       out
     },
+    # Exposures of new tumours under the recorded signatures, on the device (bnmf_project_at; not in the reference): new_data is a
+    # K x J matrix of counts (or other non-negative values) of tumours the chain has not seen.  Over iterations end_iter - n_samples + 1
+    # ... end_iter (defaults as get_WAIC), restricted to idx, every column is refitted to every sample's renormalised signatures by
+    # n_steps steps of the KL multiplicative update, so the uncertainty of the signatures reaches the exposures.  list(exposure_mean,
+    # exposure_sd, share, p_present, lower, upper (N x J: moments over the samples, the mean share of the tumour, the fraction of samples
+    # with at least min_load mutations, the credible_interval bounds, quantile type 7, computed here from the per-sample exposures), fit
+    # (a data frame with one row per new tumour: cosine, rel_l1, max_rel_change), n_used, n_steps, n_present, total, max_rel_change,
+    # min_cosine, min_cosine_at (1-based; NA if none)).  n_steps = 200 is a convention: max_rel_change says how far the refit still moved.
+    get_projection = function(new_data, end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                              idx = "MAP_idx", n_steps = 200, min_load = 1, credible_interval = 0.95) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      X <- as.matrix(new_data)
+      if (nrow(X) != K) stop("new_data must have K = ", K, " rows")
+      storage.mode(X) <- "double"
+      J <- ncol(X)
+      r <- .Call("C_bnmf_project", self$handle, as.integer(end_iter), as.integer(n_samples), used, X, as.integer(n_steps),
+                 as.double(min_load), TRUE, c(K, G, N))
+      a <- (1 - credible_interval) / 2
+      q <- apply(r$exposures, 1, quantile, probs = c(a, 1 - a), type = 7, names = FALSE)
+      fit <- data.frame(cosine = r$fit[, 1], rel_l1 = r$fit[, 2], max_rel_change = r$fit[, 3])
+      message(sprintf("Projection: J = %d, %d steps, max_rel_change %.3g, min_cosine %.4f", J, r$n_steps, r$max_rel_change, r$min_cosine))
+      list(exposure_mean = matrix(r$load[, 1], N, J), exposure_sd = sqrt(matrix(r$load[, 2], N, J)), share = matrix(r$load[, 3], N, J),
+           p_present = matrix(r$load[, 4], N, J), lower = matrix(q[1, ], N, J), upper = matrix(q[2, ], N, J), fit = fit,
+           n_used = r$n_used, n_steps = r$n_steps, n_present = r$n_present, total = r$total, max_rel_change = r$max_rel_change,
+           min_cosine = r$min_cosine, min_cosine_at = if (r$min_cosine_at < 0) NA_integer_ else as.integer(r$min_cosine_at) + 1L)
+    },
     # Label-switching correction of the recorded samples, on the device (bnmf_relabel_at; not in the reference): over iterations
     # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample's factors are permuted to the labels
     # of a pivot so that the total cosine is largest, and the pivot is iterated to the aligned mean (at most max_rounds rounds).

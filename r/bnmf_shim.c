@@ -490,6 +490,64 @@ SEXP C_bnmf_attribution_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, S
   UNPROTECT(1);
   return out;
 }
+/* Exposures of new tumours under the recorded signatures on the device (bnmf_project / bnmf_project_at): C_bnmf_project(ptr, end_iter
+ * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), X (K x J real matrix, not
+ * negative), n_steps, min_load, want_exposures (logical), dims c(K,G,N)) -> list(n_used, n_steps, n_present, min_load, total,
+ * max_rel_change, min_cosine, min_cosine_at (0-based j; -1 if none), load (N J x 4: one column per row of the C output — mean, variance,
+ * mean share, probability of presence — each laid out as E), fit (J x 3: mean cosine, mean relative L1 error, largest last-step
+ * change), series (N x S), exposures (N J x S: one column per used sample, laid out as E; or NULL)) over iterations
+ * end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_project_at: the same with end_iter required */
+/* the result list with load, fit, series and (if wanted) exposures allocated, the flags of used and J; returned unprotected */
+static SEXP project_alloc(SEXP n_samples, SEXP used, SEXP X, SEXP want_exposures, SEXP dims, int32_t** u, int* J) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  if (d[0] < 1 || XLENGTH(X) % (R_xlen_t)d[0] != 0) Rf_error("bnmf: X has %ld values, not a multiple of K = %d rows", (long)XLENGTH(X), d[0]);
+  *J = (int)(XLENGTH(X) / (R_xlen_t)d[0]);
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  *u = lgl_flags(used, n);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_steps", "n_present", "min_load", "total", "max_rel_change", "min_cosine", "min_cosine_at", "load", "fit",
+                              "series", "exposures"};
+  SEXP out = PROTECT(named_list(12, nms));
+  SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, d[2] * *J, BNMF_PROJ_NLOAD));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, *J, BNMF_PROJ_NFIT));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, d[2], S));
+  if (LOGICAL(want_exposures)[0] == TRUE) SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, d[2] * *J, S));
+  UNPROTECT(1);
+  return out;
+}
+static void project_finish(SEXP out, const bnmf_project_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_steps));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarReal((double)info->n_present)); SET_VECTOR_ELT(out, 3, Rf_ScalarReal(info->min_load));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarReal(info->total)); SET_VECTOR_ELT(out, 5, Rf_ScalarReal(info->max_rel_change));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarReal(info->min_cosine)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal((double)info->min_cosine_at));
+}
+SEXP C_bnmf_project(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP X, SEXP n_steps, SEXP min_load, SEXP want_exposures, SEXP dims) {
+  int32_t* u = NULL; int J = 0;
+  SEXP out = PROTECT(project_alloc(n_samples, used, X, want_exposures, dims, &u, &J));
+  bnmf_project_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_project(get_handle(ptr), INTEGER(n_samples)[0], u, REAL(X), J, INTEGER(n_steps)[0], REAL(min_load)[0], map_buf(out, 8), map_buf(out, 9),
+                     map_buf(out, 10), map_buf(out, 11), &info));
+  else
+    chk(bnmf_project_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(X), J, INTEGER(n_steps)[0], REAL(min_load)[0],
+                        map_buf(out, 8), map_buf(out, 9), map_buf(out, 10), map_buf(out, 11), &info));
+  project_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_project_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP X, SEXP n_steps, SEXP min_load, SEXP want_exposures, SEXP dims) {
+  int32_t* u = NULL; int J = 0;
+  SEXP out = PROTECT(project_alloc(n_samples, used, X, want_exposures, dims, &u, &J));
+  bnmf_project_info info;
+  chk(bnmf_project_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(X), J, INTEGER(n_steps)[0], REAL(min_load)[0],
+                      map_buf(out, 8), map_buf(out, 9), map_buf(out, 10), map_buf(out, 11), &info));
+  project_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Label-switching correction over recorded samples on the device (bnmf_relabel / bnmf_relabel_at): C_bnmf_relabel(ptr, end_iter (integer,
  * or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), pivot_P (K x N, or NULL = the newest used
  * sample's P), max_rounds, want_aligned (logical), dims c(K,G,N)) -> list(n_used, n_aligned, n_unmatched, rounds, converged, n_switched,
@@ -648,6 +706,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_mixing", (DL_FUNC)&C_bnmf_mixing, 7}, {"C_bnmf_mixing_at", (DL_FUNC)&C_bnmf_mixing_at, 7},
   {"C_bnmf_ppc", (DL_FUNC)&C_bnmf_ppc, 6}, {"C_bnmf_ppc_at", (DL_FUNC)&C_bnmf_ppc_at, 6},
   {"C_bnmf_attribution", (DL_FUNC)&C_bnmf_attribution, 7}, {"C_bnmf_attribution_at", (DL_FUNC)&C_bnmf_attribution_at, 7},
+  {"C_bnmf_project", (DL_FUNC)&C_bnmf_project, 9}, {"C_bnmf_project_at", (DL_FUNC)&C_bnmf_project_at, 9},
   {"C_bnmf_relabel", (DL_FUNC)&C_bnmf_relabel, 8}, {"C_bnmf_relabel_at", (DL_FUNC)&C_bnmf_relabel_at, 8},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
