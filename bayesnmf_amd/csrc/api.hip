@@ -37,6 +37,7 @@
 #include "mixing.h"
 #include "relabel.h"
 #include "project.h"
+#include "decompose.h"
 
 using namespace bnmf;
 

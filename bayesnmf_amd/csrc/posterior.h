@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project (each with its _at form) and bnmf_label_switching.  Host code only: the kernels are
-// in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h and project.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h and decompose.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -802,6 +802,115 @@ static int project_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* 
   return 0;
 }
 
+// Decomposition of the recorded signatures into a reference catalogue over the samples of r that used[] flags: the normalised catalogue
+// once, k_map_colsum once, then per batch of samples k_dec_y (the flags and the renormalised columns, k-major), k_decompose (the two-stage
+// refit: w_s[r,n], the fit values and nactive), attribution.h's k_attr_share and k_attr_stats with N := R, G := N, project.h's k_proj_fit
+// with J := N (decompose.h); the info fields are sequential scans on the host.
+static_assert(BNMF_DEC_NW == AT_NLOAD && BNMF_DEC_NFIT == DC_NFIT && BNMF_DEC_MAX_R == DC_MAX_R && DC_MAX_R <= 128, "decompose.h, attribution.h and bnmf.h disagree");
+static constexpr size_t DEC_SCRATCH_CAP = (size_t)256 << 20;    // bytes of a batch's blocks of the scratch
+static int decompose_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const double* ref, int R, const int32_t* keep, int n_steps,
+                          double min_share, double* weight, double* fit, int32_t* nactive, int32_t* included, double* weights, bnmf_decompose_info* info) {
+  if (int rc = range_enter(h, fn, h && info && ref, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  if (keep) for (int n = 0; n < N; ++n) if (keep[n] != 0 && keep[n] != 1) return fail(BNMF_EINVAL, "%s: keep[%d] = %d is neither 0 nor 1", fn, n, (int)keep[n]);
+  if (R < 1 || R > DC_MAX_R) return fail(BNMF_EINVAL, "%s: R = %d references, 1..BNMF_DEC_MAX_R = %d are possible", fn, R, DC_MAX_R);
+  if (n_steps < 1 || n_steps > 100000) return fail(BNMF_EINVAL, "%s: n_steps = %d is not in 1..100000", fn, n_steps);
+  if (!(min_share >= 0.0) || !(min_share < 1.0)) return fail(BNMF_EINVAL, "%s: min_share = %g is not a number in [0, 1)", fn, min_share);
+  const int RS = proj_row_stride(R);
+  std::vector<double> z((size_t)K * RS, 0.0);               // z[k][r] = ref[k,r] / rs[r], rs[r] = sum_k ref[k,r], k ascending from +0.0
+  for (int j = 0; j < R; ++j)
+    for (int k = 0; k < K; ++k) {
+      const double v = ref[(size_t)k + (size_t)K * j];
+      if (!(v >= 0.0) || std::isinf(v)) return fail(BNMF_EINVAL, "%s: reference_P[%d, %d] = %g is not a finite number >= 0", fn, k, j, v);
+    }
+  for (int j = 0; j < R; ++j) {
+    double rs = 0.0;
+    for (int k = 0; k < K; ++k) rs = rs + ref[(size_t)k + (size_t)K * j];
+    if (!(rs > 0.0)) return fail(BNMF_EINVAL, "%s: column %d of reference_P is all zero: it has no share", fn, j);
+    for (int k = 0; k < K; ++k) z[(size_t)k * RS + j] = ref[(size_t)k + (size_t)K * j] / rs;
+  }
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the weights needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t RN = (size_t)R * N, lenP = (size_t)K * N;
+  const size_t per = ((weights ? 2 : 1) * RN + (size_t)(1 + DC_NFIT + K) * N) * sizeof(double) + (size_t)N * sizeof(int);   // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, DEC_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_DEC_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }     // tests: the batch size
+  const int Sb = (int)std::min<long long>({want, (long long)S, (long long)(INT_MAX / 2) / ((long long)K * N)});   // (K Sb N stays an int)
+  // the catalogue through the caches at wave-uniform addresses: measured at the headline shape the staged catalogue beside
+  // w and g in the LDS leaves one wave per CU where two fit without it and takes 1.8 times as long; with w and g in registers it is the
+  // form bnmf_project measured faster.  Staged on request, while it fits 160 KB.
+  const bool fits = proj_lds_bytes(K, R, true) <= LDS_CAP;
+  bool stage = false;
+  if (const char* e = getenv("BNMF_DEC_STAGE")) stage = fits && atoi(e) != 0;                               // tests, tools: the other form
+  const size_t lds = proj_lds_bytes(K, R, stage);
+  if (lds > LDS_CAP) return fail(BNMF_ESIZE, "%s: R = %d references need %zu bytes of LDS", fn, R, lds);    // (unreachable for R <= BNMF_DEC_MAX_R)
+  double *cs, *dz, *dyt, *dscr, *dfs, *du, *dst, *dload, *dser, *dfst, *dfit, *dw; int *dslots, *dkeep, *dpart, *dnact;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); dz = c.take<double>((size_t)K * RS); dyt = c.take<double>((size_t)K * Sb * N);
+        dscr = c.take<double>((size_t)Sb * RN); dfs = c.take<double>((size_t)Sb * DC_NFIT * N); du = c.take<double>((size_t)Sb * N);
+        dst = c.take<double>(AT_NLOAD * RN); dload = c.take<double>(AT_NLOAD * RN); dser = c.take<double>((size_t)S * R);
+        dfst = c.take<double>((size_t)DC_NFIT * N); dfit = c.take<double>((size_t)DC_NFIT * N);
+        dw = weights ? c.take<double>((size_t)Sb * RN) : nullptr;
+        dslots = c.take<int>(S); dkeep = c.take<int>(N); dpart = c.take<int>((size_t)Sb * N); dnact = c.take<int>((size_t)S * N);
+      })) return rc;
+  std::vector<int> hkeep(N, 1);
+  if (keep) for (int n = 0; n < N; ++n) hkeep[n] = keep[n];
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dkeep, hkeep.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dz, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  const double* ringP = h->arr[BNMF_P].ring;
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, ringP, lenP, K, N, (const int*)dslots, cs);
+  using DecKernel = decltype(&k_decompose<8, true>);
+  const DecKernel staged[5] = {k_decompose<0, true>, k_decompose<8, true>, k_decompose<16, true>, k_decompose<24, true>, k_decompose<32, true>};
+  const DecKernel direct[5] = {k_decompose<0, false>, k_decompose<8, false>, k_decompose<16, false>, k_decompose<24, false>, k_decompose<32, false>};
+  const DecKernel kern = (stage ? staged : direct)[R <= PJ_MAX_NT ? RS / 8 : 0];
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  const int T = R <= PJ_MAX_NT ? PJ_T : PJ_TL;
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0), first = s0 == 0 ? 1 : 0, last = s0 + nb == S ? 1 : 0, Pn = nb * N;
+    hipLaunchKernelGGL(k_dec_y, dim3((unsigned)(((size_t)K * Pn + 255) / 256)), dim3(256), 0, h->stream, ringP, (const double*)h->arr[BNMF_A].ring, lenP, K, N,
+                       Pn, (const int*)dslots + s0, (const double*)cs + (size_t)s0 * N, (const int*)dkeep, dyt, dpart);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((Pn + T - 1) / T)), dim3(T), lds, h->stream, (const double*)dz, (const double*)dyt, (const int*)dpart, K, R, N, Pn,
+                       n_steps, min_share, dscr, dfs, dnact + (size_t)s0 * N);
+    hipLaunchKernelGGL(k_attr_share, dim3((unsigned)((Pn + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, R, N, du);
+    hipLaunchKernelGGL(k_attr_stats, dim3((unsigned)((size_t)nb * R + (RN + AT_TT - 1) / AT_TT)), dim3(AT_TT), 0, h->stream, (const double*)dscr,
+                       (const double*)du, nb, R, N, S, s0, last, min_share, dst, dser, dload);
+    hipLaunchKernelGGL(k_proj_fit, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, (const double*)dfs, nb, N, S, first, last, dfst, dfit);
+    HIPCHK(hipGetLastError());
+    if (weights) {
+      hipLaunchKernelGGL(k_proj_exposures, dim3((unsigned)(((size_t)nb * RN + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, R, N, dw);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(weights + (size_t)s0 * RN, dw, (size_t)nb * RN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));               // the next batch overwrites the scratch
+    }
+  }
+  std::vector<double> hp(RN), hf((size_t)DC_NFIT * N);
+  std::vector<int32_t> hn((size_t)S * N);
+  HIPCHK(hipMemcpyAsync(hp.data(), dload + 3 * RN, RN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hf.data(), dfit, hf.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hn.data(), dnact, hn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (weight) HIPCHK(hipMemcpyAsync(weight, dload, AT_NLOAD * RN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (fit) std::memcpy(fit, hf.data(), hf.size() * sizeof(double));
+  if (nactive) std::memcpy(nactive, hn.data(), hn.size() * sizeof(int32_t));
+  if (included) for (int n = 0; n < N; ++n) { int32_t c = 0; for (int s = 0; s < S; ++s) c += hn[(size_t)s * N + n] > 0 ? 1 : 0; included[n] = c; }
+  int64_t np = 0;
+  for (size_t i = 0; i < RN; ++i) np += hp[i] >= 0.5 ? 1 : 0;
+  double mx = 0.0, mn = std::nan(""); int64_t mn_at = -1;
+  for (int n = 0; n < N; ++n) {
+    const double c = hf[n], v = hf[2 * (size_t)N + n];
+    if (v > mx) mx = v;
+    if (!std::isnan(c) && (mn_at < 0 || c < mn)) { mn = c; mn_at = n; }
+  }
+  info->n_used = S; info->n_steps = n_steps; info->R = R; info->_pad = 0; info->n_present = np; info->min_share = min_share;
+  info->max_rel_change = mx; info->min_cosine = mn; info->min_cosine_at = mn_at;
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -862,6 +971,16 @@ int bnmf_project(bnmf_handle* h, int last_n, const int32_t* used, const double* 
 int bnmf_project_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* X, int J, int n_steps, double min_load, double* load,
                     double* fit, double* series, double* exposures, bnmf_project_info* info) {
   return project_impl(h, "bnmf_project_at", {true, end_iter, n_samples}, used, X, J, n_steps, min_load, load, fit, series, exposures, info);
+}
+
+int bnmf_decompose(bnmf_handle* h, int last_n, const int32_t* used, const double* reference_P, int R, const int32_t* keep, int n_steps, double min_share,
+                   double* weight, double* fit, int32_t* nactive, int32_t* included, double* weights, bnmf_decompose_info* info) {
+  return decompose_impl(h, "bnmf_decompose", {false, 0, last_n}, used, reference_P, R, keep, n_steps, min_share, weight, fit, nactive, included, weights, info);
+}
+int bnmf_decompose_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* reference_P, int R, const int32_t* keep, int n_steps,
+                      double min_share, double* weight, double* fit, int32_t* nactive, int32_t* included, double* weights, bnmf_decompose_info* info) {
+  return decompose_impl(h, "bnmf_decompose_at", {true, end_iter, n_samples}, used, reference_P, R, keep, n_steps, min_share, weight, fit, nactive, included,
+                        weights, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

@@ -47,6 +47,24 @@ inline size_t proj_lds_bytes(int K, int N, bool stage) {
   return ((N <= PJ_MAX_NT ? 0 : 2 * (size_t)N * PJ_TL) + (stage ? (size_t)K * proj_row_stride(N) : 0)) * sizeof(double);
 }
 
+// The KL update over one row k, shared with decompose.h (where the roles of x and X are exchanged): the places 0 .. ni - 1 of the row xk
+// against the lane's E and G.  kl_fitted: c = sum_i xk[i] * E(i), i ascending from +0.0.  kl_row: that c, q = c > 0 ? X / c : 0.0,
+// G(i) = G(i) + xk[i] * q.  NT > 0: ni = NT is a constant and the loops unroll over registers.
+template <int NT, class FE> __device__ __forceinline__ double kl_fitted(const double* __restrict__ xk, int m, FE&& E) {
+  const int ni = NT > 0 ? NT : m;
+  double c = 0.0;
+#pragma unroll
+  for (int i = 0; i < ni; ++i) c = c + xk[i] * E(i);
+  return c;
+}
+template <int NT, class FE, class FG> __device__ __forceinline__ void kl_row(const double* __restrict__ xk, double X, int m, FE&& E, FG&& G) {
+  const int ni = NT > 0 ? NT : m;
+  const double c = kl_fitted<NT>(xk, m, E);
+  const double q = c > 0.0 ? X / c : 0.0;
+#pragma unroll
+  for (int i = 0; i < ni; ++i) G(i) = G(i) + xk[i] * q;
+}
+
 // One workgroup per sample of the batch: nin[s], idx[s][0 .. nin) ascending, xg[s][k][i] = P_s[k, idx[i]] / cs[idx[i]] (i < nin), +0.0
 // up to the row stride NS.
 __global__ __launch_bounds__(256) void k_proj_x(const double* ringP, const double* ringA, size_t lenP, int K, int N, int NS, const int* slots,
@@ -115,14 +133,7 @@ __global__ __launch_bounds__(NT > 0 ? PJ_T : PJ_TL) void k_project(const double*
 #pragma unroll
     for (int i = 0; i < ni; ++i) G(i) = 0.0;
     for (int k = 0; k < K; ++k) {
-      const double* xk = xs + (size_t)k * NS;
-      const double X = Xj[(size_t)k * J];
-      double c = 0.0;
-#pragma unroll
-      for (int i = 0; i < ni; ++i) c = c + xk[i] * E(i);
-      const double q = c > 0.0 ? X / c : 0.0;
-#pragma unroll
-      for (int i = 0; i < ni; ++i) G(i) = G(i) + xk[i] * q;
+      kl_row<NT>(xs + (size_t)k * NS, Xj[(size_t)k * J], m, E, G);
     }
     d = 0.0;
 #pragma unroll
@@ -135,11 +146,8 @@ __global__ __launch_bounds__(NT > 0 ? PJ_T : PJ_TL) void k_project(const double*
   }
   double dot = 0.0, xx = 0.0, cc = 0.0, l1 = 0.0;
   for (int k = 0; k < K; ++k) {
-    const double* xk = xs + (size_t)k * NS;
     const double X = Xj[(size_t)k * J];
-    double c = 0.0;
-#pragma unroll
-    for (int i = 0; i < ni; ++i) c = c + xk[i] * E(i);
+    const double c = kl_fitted<NT>(xs + (size_t)k * NS, m, E);
     dot = dot + X * c; xx = xx + X * X; cc = cc + c * c; l1 = l1 + fabs(X - c);
   }
   if (!ok) return;

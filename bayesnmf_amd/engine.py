@@ -95,6 +95,11 @@ class BnmfProjectInfo(C.Structure):
                 ("max_rel_change", C.c_double), ("min_cosine", C.c_double), ("min_cosine_at", C.c_int64)]
 
 
+class BnmfDecomposeInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_steps", C.c_int32), ("R", C.c_int32), ("_pad", C.c_int32), ("n_present", C.c_int64),
+                ("min_share", C.c_double), ("max_rel_change", C.c_double), ("min_cosine", C.c_double), ("min_cosine_at", C.c_int64)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -103,6 +108,7 @@ class BnmfRelabelInfo(C.Structure):
 
 ATTR_LOAD_ROWS = ["load_mean", "load_var", "share", "p_present"]
 PROJ_FIT_ROWS = ["cosine", "rel_l1", "rel_change"]
+DEC_WEIGHT_ROWS = ["weight_mean", "weight_var", "share", "p_present"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -119,7 +125,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_device_info", "bnmf_device_count", "bnmf_last_error", "bnmf_version", "bnmf_probe_overlap", "bnmf_trim", "bnmf_get_stat",
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
-               "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at"]
+               "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
+               "bnmf_decompose", "bnmf_decompose_at"]
 
 
 def lib():
@@ -178,6 +185,9 @@ def lib():
         L.bnmf_attribution_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, dp, dp, dp, C.POINTER(BnmfAttrInfo)]
         L.bnmf_project.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfProjectInfo)]
         L.bnmf_project_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, C.c_int, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfProjectInfo)]
+        L.bnmf_decompose.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, C.c_int, C.c_double, dp, dp, ip, ip, dp, C.POINTER(BnmfDecomposeInfo)]
+        L.bnmf_decompose_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, C.c_int, C.c_double, dp, dp, ip, ip, dp,
+                                        C.POINTER(BnmfDecomposeInfo)]
         lp = C.POINTER(C.c_int64)
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
@@ -555,6 +565,40 @@ class Engine:
         out.update({name: fit[i] for i, name in enumerate(PROJ_FIT_ROWS)})
         if exposures:
             out["exposures"] = np.stack([row.reshape((N, J), order="F") for row in ex]) if S else np.empty((0, N, J))
+        return out
+
+    def decompose(self, last_n, reference_P, used=None, end_iter=None, keep=None, n_steps=200, min_share=0.05, weights=False):
+        """The recorded signatures as mixtures of the references reference_P (K x R, not negative, no all-zero column), over the recorded
+        samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`, or with end_iter of the `last_n` that end
+        at iteration end_iter (bnmf_decompose / bnmf_decompose_at), on the device: every renormalised column of every sample's P is
+        refitted to the normalised catalogue by n_steps steps of the KL multiplicative update, the references below min_share of the
+        column are dropped and n_steps more steps refit the rest (min_share = 0: no pruning, one stage).  keep (length N, None = all):
+        the factors to decompose.  Returns the info fields, weight (4 x R x N) with its rows also by name (DEC_WEIGHT_ROWS: the mean and
+        variance over the used samples of the weight of reference r in factor n, its mean share of the factor, and the fraction of
+        samples whose weight is >= min_share), fit (3 x N) with its rows by name (PROJ_FIT_ROWS), nactive (S x N: the references left
+        per sample and factor) and included (N: the samples in which the factor took part); with weights also weights (S x R x N),
+        every used sample's own."""
+        K, N = self.K, self.N
+        ref = np.asfortranarray(reference_P, dtype=np.float64)
+        if ref.ndim != 2 or ref.shape[0] != K:
+            raise BnmfError(-2, f"decompose: reference_P has shape {ref.shape}, K = {K} rows are needed")
+        R = ref.shape[1]
+        u, S = self._used("decompose", used, last_n)
+        kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.int32)
+        if kp is not None and kp.size != N:
+            raise BnmfError(-2, f"decompose: keep has {kp.size} entries for {N} factors")
+        weight, fit = np.empty((4, R * N)), np.empty((3, N))
+        nact, inc = np.empty((S, N), dtype=np.int32), np.empty(N, dtype=np.int32)
+        ws = np.empty((S, R * N)) if weights else None
+        info = BnmfDecomposeInfo()
+        self._range_call("decompose", last_n, end_iter, u, _dp(ref.ravel(order="F")), R, None if kp is None else kp.ctypes.data_as(_IP), int(n_steps),
+                         float(min_share), _dp(weight), _dp(fit), nact.ctypes.data_as(_IP), inc.ctypes.data_as(_IP), _dp(ws), C.byref(info))
+        out = self._info(info)
+        out.update(weight=np.stack([row.reshape((R, N), order="F") for row in weight]), fit=fit, nactive=nact, included=inc)
+        out.update({name: out["weight"][i] for i, name in enumerate(DEC_WEIGHT_ROWS)})
+        out.update({name: fit[i] for i, name in enumerate(PROJ_FIT_ROWS)})
+        if weights:
+            out["weights"] = np.stack([row.reshape((R, N), order="F") for row in ws]) if S else np.empty((0, R, N))
         return out
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):

@@ -708,8 +708,50 @@ class bayesNMF_sampler:
         self.log(f"Projection: J = {ex.shape[2]}, {r['n_steps']} steps, max_rel_change {r['max_rel_change']:.3g}, min_cosine {r['min_cosine']:.4f}", verbosity=1)
         return out
 
+    def get_decomposition(self, reference_P, end_iter=None, n_samples=None, idx="MAP_idx", n_steps=200, min_share=0.05, keep=None,
+                          credible_interval=0.95, reference_names=None):
+        """Is a discovered signature a mixture of known ones?  On the device (bnmf_decompose_at; not in the reference): reference_P is
+        a K x R catalogue (a data frame's column names become the reference names unless reference_names is given).  Over iterations
+        end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last MAP_over samples), restricted to `idx` ("MAP_idx": those
+        whose A equals the mode of the range, so that the samples are all of one rank pattern — a sample that excludes a factor enters
+        its means with 0; None: every sample; else a vector of recorded iterations), every renormalised column of every sample's P is
+        refitted to the normalised catalogue by n_steps steps of the KL multiplicative update, the references below min_share of the
+        column are dropped, and n_steps more steps refit the rest: the uncertainty of the signatures reaches the mixture weights.
+        keep: the factors to decompose (0 / 1 flags of length N; None = all).
+        Returns dict(weight_mean, weight_sd, share, p_present, lower, upper: R x N arrays — the mean and standard deviation over the
+        samples of the weight of reference r in signature n (a signature's weights sum to 1), its mean share, the fraction of samples
+        in which it holds at least min_share, and the credible_interval bounds (quantile type 7, computed here from the per-sample
+        weights); fit: a data frame with one row per signature — cosine, rel_l1 (the means over the samples of the cosine and the
+        relative L1 error of the mixture) and max_rel_change; nactive (S x N), included (N); components: per signature the list of
+        (reference, p_present, weight_mean) with p_present >= 0.5, the largest weight first, the reference by name when names are
+        known, else by 0-based column; n_used, n_steps, R, n_present, min_share, max_rel_change, min_cosine, min_cosine_at)."""
+        if not hasattr(self._chain, "decompose"):
+            raise ValueError("get_decomposition needs an engine that decomposes its recorded samples into a catalogue (decompose); this engine_factory's cannot")
+        if reference_names is None and hasattr(reference_P, "columns"):
+            reference_names = [str(c) for c in reference_P.columns]
+        ref = np.asarray(reference_P, dtype=float)
+        if reference_names is not None and len(reference_names) != ref.shape[1]:
+            raise ValueError(f"reference_names has {len(reference_names)} entries for {ref.shape[1]} references")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.decompose(n, ref, used=used, keep=keep, n_steps=n_steps, min_share=min_share, weights=True, **kw)
+        ws = np.asarray(r["weights"], dtype=float)
+        a = (1.0 - float(credible_interval)) / 2.0
+        out = dict(weight_mean=r["weight_mean"], weight_sd=np.sqrt(r["weight_var"]), share=r["share"], p_present=r["p_present"],
+                   lower=np.quantile(ws, a, axis=0), upper=np.quantile(ws, 1.0 - a, axis=0),
+                   fit=pd.DataFrame(dict(cosine=r["cosine"], rel_l1=r["rel_l1"], max_rel_change=r["rel_change"])),
+                   nactive=r["nactive"], included=r["included"])
+        comp = []
+        for j in range(ws.shape[2]):
+            rs = [i for i in np.argsort(-r["weight_mean"][:, j], kind="stable") if r["p_present"][i, j] >= 0.5]
+            comp.append([(reference_names[i] if reference_names is not None else int(i), float(r["p_present"][i, j]), float(r["weight_mean"][i, j])) for i in rs])
+        out["components"] = comp
+        out.update({k: r[k] for k in ("n_used", "n_steps", "R", "n_present", "min_share", "max_rel_change", "min_cosine", "min_cosine_at")})
+        self.log(f"Decomposition: R = {r['R']}, {r['n_steps']} steps, min_share {r['min_share']:g}, min_cosine {r['min_cosine']:.4f}, "
+                 f"max_rel_change {r['max_rel_change']:.3g}", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

@@ -342,6 +342,50 @@ int bnmf_project(bnmf_handle*, int last_n, const int32_t* used, const double* X 
 int bnmf_project_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const double* X, int J, int n_steps,
                     double min_load, double* load, double* fit, double* series, double* exposures, bnmf_project_info* info);
 
+/* Decomposition of the recorded signatures into a reference catalogue, on the device: is factor n a mixture of known
+ * signatures?  reference_P (K x R, column-major; finite, not negative, no all-zero column) is normalised to unit column sums on the host.
+ * For every recorded sample flagged in used[] (oldest first; NULL = all) and every factor n with keep[n] != 0 (NULL = all), A_s[n] != 0 and
+ * a positive column sum, the renormalised column y = P_s[, n] / colSums(P_s)[n] is refitted to the catalogue by n_steps steps of the KL
+ * multiplicative update (EM) from equal weights; then every reference whose weight is below min_share of the column's total is dropped
+ * for good (the largest stays if none reaches it) and n_steps more steps refit the rest.  min_share == 0 skips the pruning and the second
+ * stage.  A factor that takes no part in a sample has every weight +0.0 there, a NaN cosine and nactive 0; its column is never read.  No
+ * random number is drawn.
+ * weight [BNMF_DEC_NW][R*N], each row laid out r + R n: over the used samples the mean and the variance (S - 1 form) of the weight
+ *   w_s[r,n], the mean of w_s[r,n] / sum_r' w_s[r',n], and #(w_s >= min_share) / S: the probability that reference r is part of factor n.
+ * fit [BNMF_DEC_NFIT][N]: per factor the mean over the used samples of the cosine between y and its fit z w (NaN where a sample's is:
+ *   a sample in which the factor takes no part), the mean of sum_k |y - z w| / sum_k y, and the largest over the samples of
+ *   max_r |w_r(last step) - w_r(the step before)| / sum_k y: how far from converged n_steps left the refit.
+ * nactive [S][N] row-major: the references left after the pruning, per used sample and factor.
+ * included [N]: the used samples in which the factor took part.  A sample that excludes a factor enters its means with +0.0: flag in
+ *   used[] the samples of one rank pattern (bnmf_map's used[]), as for bnmf_waic.
+ * weights [S][R*N]: every used sample's weights, each laid out r + R n (caller-sized; they leave the device in batches).
+ * info: n_present the (r, n) whose probability is >= 0.5; max_rel_change the largest entry of fit row 2; min_cosine the smallest entry of
+ *   fit row 0 that is not NaN and min_cosine_at its n (the first wins a tie; NaN and -1 if there is none).
+ * weight, fit, nactive, included and weights may each be NULL.  Only + * /, sqrt and comparisons in a fixed order: the same call gives the
+ * same bits, whatever the batches.  Any likelihood: only P and A are read.  Read-only for the chain; none of its streams is consumed.
+ * bnmf_decompose_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_map_at;
+ * bnmf_decompose(h, n, ...) is bnmf_decompose_at(h, iter, n, ...).  Refused before any device work: null info or reference_P, a used[] or
+ * keep[] value other than 0 / 1 (the index named), R outside 1..BNMF_DEC_MAX_R, n_steps outside 1..100000, a min_share that is NaN,
+ * infinite, negative or >= 1, a cell of reference_P that is NaN, infinite or negative (the first bad cell [k, r] named), an all-zero column
+ * of it (the column named) with BNMF_EINVAL; fewer than 2 used samples with BNMF_ESIZE; window = 0, a poisoned handle or nothing recorded
+ * with BNMF_ESTATE. */
+#define BNMF_DEC_NW 4        /* weight rows: mean, variance (S - 1), mean share, P(w >= min_share) */
+#define BNMF_DEC_NFIT 3      /* per factor: mean cosine, mean relative L1, largest last-step change */
+#define BNMF_DEC_MAX_R 128
+typedef struct { int32_t n_used, n_steps, R, _pad; int64_t n_present /* (r, n) with P >= 0.5 */;
+                 double min_share, max_rel_change, min_cosine; int64_t min_cosine_at /* n; -1 if none */; } bnmf_decompose_info;
+int bnmf_decompose(bnmf_handle*, int last_n, const int32_t* used, const double* reference_P /* K x R column-major */, int R, const int32_t* keep,
+                   int n_steps, double min_share,
+                   double* weight   /* [4][R*N], each row r + R n; may be NULL */,
+                   double* fit      /* [3][N]; may be NULL */,
+                   int32_t* nactive /* [S][N] row-major; may be NULL */,
+                   int32_t* included/* [N]; may be NULL */,
+                   double* weights  /* [S][R*N], every sample's weights, r + R n; may be NULL; leaves the device in batches */,
+                   bnmf_decompose_info* info);
+int bnmf_decompose_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const double* reference_P, int R, const int32_t* keep,
+                      int n_steps, double min_share, double* weight, double* fit, int32_t* nactive, int32_t* included, double* weights,
+                      bnmf_decompose_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

@@ -279,6 +279,56 @@ bayesNMF_sampler_hip <- R6::R6Class(
            n_used = r$n_used, n_steps = r$n_steps, n_present = r$n_present, total = r$total, max_rel_change = r$max_rel_change,
            min_cosine = r$min_cosine, min_cosine_at = if (r$min_cosine_at < 0) NA_integer_ else as.integer(r$min_cosine_at) + 1L)
     },
+    # Is a discovered signature a mixture of known ones?  On the device (bnmf_decompose_at; not in the reference): reference_P is a K x R
+    # catalogue (its column names name the references).  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC),
+    # restricted to idx (the default keeps the samples of one rank pattern: a sample that excludes a factor enters its means with 0), every
+    # renormalised column of every sample's P is refitted to the normalised catalogue by n_steps steps of the KL multiplicative update,
+    # the references below min_share of the column are dropped and n_steps more steps refit the rest, so the uncertainty of the
+    # signatures reaches the mixture weights.  keep: the factors to decompose (logical length N, NULL = all).  list(weight_mean, weight_sd,
+    # share, p_present, lower, upper (R x N: moments over the samples, the mean share of the signature, the fraction of samples with a
+    # weight of at least min_share, the credible_interval bounds, quantile type 7, computed here from the per-sample weights), fit (a data
+    # frame with one row per signature: cosine, rel_l1, max_rel_change), nactive (N x S), included (N), components (per signature a data
+    # frame of the references with p_present >= 0.5, the largest mean weight first), n_used, n_steps, R, n_present, min_share,
+    # max_rel_change, min_cosine, min_cosine_at (1-based; NA if none)).
+    get_decomposition = function(reference_P, end_iter = self$state$iter,
+                                 n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx", n_steps = 200,
+                                 min_share = 0.05, keep = NULL, credible_interval = 0.95, reference_names = colnames(reference_P)) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      ref <- as.matrix(reference_P)
+      if (nrow(ref) != K) stop("reference_P must have K = ", K, " rows")
+      storage.mode(ref) <- "double"
+      R <- ncol(ref)
+      if (is.null(reference_names)) reference_names <- seq_len(R)
+      if (length(reference_names) != R) stop("reference_names must have one entry per column of reference_P")
+      if (!is.null(keep)) keep <- as.logical(keep)
+      r <- .Call("C_bnmf_decompose", self$handle, as.integer(end_iter), as.integer(n_samples), used, ref, keep, as.double(min_share),
+                 c(as.integer(n_steps), 1L), c(K, G, N))
+      a <- (1 - credible_interval) / 2
+      q <- apply(r$weights, 1, quantile, probs = c(a, 1 - a), type = 7, names = FALSE)
+      fit <- data.frame(cosine = r$fit[, 1], rel_l1 = r$fit[, 2], max_rel_change = r$fit[, 3])
+      wm <- matrix(r$weight[, 1], R, N); pp <- matrix(r$weight[, 4], R, N)
+      components <- lapply(seq_len(N), function(n) {
+        i <- order(-wm[, n]); i <- i[pp[i, n] >= 0.5]
+        data.frame(reference = reference_names[i], p_present = pp[i, n], weight_mean = wm[i, n])
+      })
+      message(sprintf("Decomposition: R = %d, %d steps, min_share %g, min_cosine %.4f, max_rel_change %.3g", R, r$n_steps, r$min_share,
+                      r$min_cosine, r$max_rel_change))
+      list(weight_mean = wm, weight_sd = sqrt(matrix(r$weight[, 2], R, N)), share = matrix(r$weight[, 3], R, N), p_present = pp,
+           lower = matrix(q[1, ], R, N), upper = matrix(q[2, ], R, N), fit = fit, nactive = r$nactive, included = r$included,
+           components = components, n_used = r$n_used, n_steps = r$n_steps, R = r$R, n_present = r$n_present, min_share = r$min_share,
+           max_rel_change = r$max_rel_change, min_cosine = r$min_cosine,
+           min_cosine_at = if (r$min_cosine_at < 0) NA_integer_ else as.integer(r$min_cosine_at) + 1L)
+    },
     # Label-switching correction of the recorded samples, on the device (bnmf_relabel_at; not in the reference): over iterations
     # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample's factors are permuted to the labels
     # of a pivot so that the total cosine is largest, and the pivot is iterated to the aligned mean (at most max_rounds rounds).

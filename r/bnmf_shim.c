@@ -548,6 +548,72 @@ SEXP C_bnmf_project_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP 
   UNPROTECT(1);
   return out;
 }
+/* Decomposition of the recorded signatures into a reference catalogue on the device (bnmf_decompose / bnmf_decompose_at):
+ * C_bnmf_decompose(ptr, end_iter (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all),
+ * reference_P (K x R real matrix, not negative, no all-zero column), keep (logical length N, or NULL = all), min_share, opts (integer
+ * c(n_steps, want_weights as 0 / 1): .Call routines here take at most 9 arguments), dims c(K,G,N)) -> list(n_used, n_steps, R, n_present, min_share, max_rel_change, min_cosine, min_cosine_at
+ * (0-based n; -1 if none), weight (R N x 4: one column per row of the C output — mean, variance, mean share, probability of presence —
+ * each laid out r + R n), fit (N x 3: mean cosine, mean relative L1 error, largest last-step change), nactive (N x S integer), included
+ * (N integer), weights (R N x S: one column per used sample, laid out r + R n; or NULL)) over iterations
+ * end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_decompose_at: the same with end_iter required */
+/* the result list with weight, fit, nactive, included and (if wanted) weights allocated, the flags of used and keep, and R; returned
+ * unprotected */
+static SEXP decompose_alloc(SEXP n_samples, SEXP used, SEXP ref, SEXP keep, SEXP opts, SEXP dims, int32_t** u, int32_t** kp, int* R) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  if (XLENGTH(opts) != 2) Rf_error("bnmf: opts has %ld entries, c(n_steps, want_weights) is needed", (long)XLENGTH(opts));
+  if (d[0] < 1 || XLENGTH(ref) % (R_xlen_t)d[0] != 0) Rf_error("bnmf: reference_P has %ld values, not a multiple of K = %d rows", (long)XLENGTH(ref), d[0]);
+  *R = (int)(XLENGTH(ref) / (R_xlen_t)d[0]);
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (keep != R_NilValue && XLENGTH(keep) != (R_xlen_t)d[2]) Rf_error("bnmf: keep has %ld entries for %d factors", (long)XLENGTH(keep), d[2]);
+  *u = lgl_flags(used, n);
+  *kp = lgl_flags(keep, d[2]);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_steps", "R", "n_present", "min_share", "max_rel_change", "min_cosine", "min_cosine_at", "weight", "fit",
+                              "nactive", "included", "weights"};
+  SEXP out = PROTECT(named_list(13, nms));
+  SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, *R * d[2], BNMF_DEC_NW));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, d[2], BNMF_DEC_NFIT));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(INTSXP, d[2], S));
+  SET_VECTOR_ELT(out, 11, Rf_allocVector(INTSXP, d[2]));
+  if (INTEGER(opts)[1] != 0) SET_VECTOR_ELT(out, 12, Rf_allocMatrix(REALSXP, *R * d[2], S));
+  UNPROTECT(1);
+  return out;
+}
+static void decompose_finish(SEXP out, const bnmf_decompose_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_steps));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarInteger(info->R)); SET_VECTOR_ELT(out, 3, Rf_ScalarReal((double)info->n_present));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarReal(info->min_share)); SET_VECTOR_ELT(out, 5, Rf_ScalarReal(info->max_rel_change));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarReal(info->min_cosine)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal((double)info->min_cosine_at));
+}
+SEXP C_bnmf_decompose(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP ref, SEXP keep, SEXP min_share, SEXP opts, SEXP dims) {
+  int32_t *u = NULL, *kp = NULL; int R = 0;
+  SEXP out = PROTECT(decompose_alloc(n_samples, used, ref, keep, opts, dims, &u, &kp, &R));
+  bnmf_decompose_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_decompose(get_handle(ptr), INTEGER(n_samples)[0], u, REAL(ref), R, kp, INTEGER(opts)[0], REAL(min_share)[0], map_buf(out, 8),
+                       map_buf(out, 9), (int32_t*)INTEGER(VECTOR_ELT(out, 10)), (int32_t*)INTEGER(VECTOR_ELT(out, 11)), map_buf(out, 12), &info));
+  else
+    chk(bnmf_decompose_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(ref), R, kp, INTEGER(opts)[0], REAL(min_share)[0],
+                          map_buf(out, 8), map_buf(out, 9), (int32_t*)INTEGER(VECTOR_ELT(out, 10)), (int32_t*)INTEGER(VECTOR_ELT(out, 11)),
+                          map_buf(out, 12), &info));
+  decompose_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_decompose_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP ref, SEXP keep, SEXP min_share, SEXP opts, SEXP dims) {
+  int32_t *u = NULL, *kp = NULL; int R = 0;
+  SEXP out = PROTECT(decompose_alloc(n_samples, used, ref, keep, opts, dims, &u, &kp, &R));
+  bnmf_decompose_info info;
+  chk(bnmf_decompose_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(ref), R, kp, INTEGER(opts)[0], REAL(min_share)[0],
+                        map_buf(out, 8), map_buf(out, 9), (int32_t*)INTEGER(VECTOR_ELT(out, 10)), (int32_t*)INTEGER(VECTOR_ELT(out, 11)),
+                        map_buf(out, 12), &info));
+  decompose_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Label-switching correction over recorded samples on the device (bnmf_relabel / bnmf_relabel_at): C_bnmf_relabel(ptr, end_iter (integer,
  * or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), pivot_P (K x N, or NULL = the newest used
  * sample's P), max_rounds, want_aligned (logical), dims c(K,G,N)) -> list(n_used, n_aligned, n_unmatched, rounds, converged, n_switched,
@@ -707,6 +773,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_ppc", (DL_FUNC)&C_bnmf_ppc, 6}, {"C_bnmf_ppc_at", (DL_FUNC)&C_bnmf_ppc_at, 6},
   {"C_bnmf_attribution", (DL_FUNC)&C_bnmf_attribution, 7}, {"C_bnmf_attribution_at", (DL_FUNC)&C_bnmf_attribution_at, 7},
   {"C_bnmf_project", (DL_FUNC)&C_bnmf_project, 9}, {"C_bnmf_project_at", (DL_FUNC)&C_bnmf_project_at, 9},
+  {"C_bnmf_decompose", (DL_FUNC)&C_bnmf_decompose, 9}, {"C_bnmf_decompose_at", (DL_FUNC)&C_bnmf_decompose_at, 9},
   {"C_bnmf_relabel", (DL_FUNC)&C_bnmf_relabel, 8}, {"C_bnmf_relabel_at", (DL_FUNC)&C_bnmf_relabel_at, 8},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
