@@ -38,6 +38,7 @@
 #include "relabel.h"
 #include "project.h"
 #include "decompose.h"
+#include "contrast.h"
 
 using namespace bnmf;
 

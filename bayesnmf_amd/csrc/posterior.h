@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h and decompose.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h and contrast.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -911,6 +911,124 @@ static int decompose_impl(bnmf_handle* h, const char* fn, Range r, const int32_t
   return 0;
 }
 
+// ---- bnmf_contrast's host reduction; no device and no handle, so that a stand-alone host program can run it ----
+// the canonical W = 64 sum of v[0], v[stride], ..., v[(m - 1) stride]: accumulator l adds elements l, l + 64, ... from +0.0, then wave_tree64's halving tree
+static double con_canon64(const double* v, size_t m, size_t stride) {
+  double acc[64];
+  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
+  for (size_t i = 0; i < m; ++i) acc[i & 63] = acc[i & 63] + v[i * stride];
+  for (int hh = 32; hh >= 1; hh >>= 1) for (int l = 0; l < hh; ++l) acc[l] = acc[l] + acc[l + hh];
+  return acc[0];
+}
+// mean, variance (S - 1 form) and the two type-7 quantiles of x[0 .. S) into row[0], row[stride], row[2 stride], row[3 stride]; tmp: S doubles.
+// The quantiles are quantile7's expression on one sort (a NaN sorts last, as numpy's does); ci <= 0: NaN.
+static void con_rows(const double* x, int S, double ci, double* tmp, double* row, size_t stride) {
+  const double mean = con_canon64(x, S, 1) / (double)S;
+  for (int s = 0; s < S; ++s) { const double d = x[s] - mean; tmp[s] = d * d; }
+  row[0] = mean; row[stride] = con_canon64(tmp, S, 1) / (double)(S - 1);
+  if (!(ci > 0.0)) { row[2 * stride] = row[3 * stride] = std::nan(""); return; }
+  std::copy(x, x + S, tmp);
+  std::sort(tmp, tmp + S, [](double a, double b) { return a < b || (std::isnan(b) && !std::isnan(a)); });
+  auto q = [&](double prob) {
+    const double hq = (double)(S - 1) * prob;
+    const size_t j = (size_t)std::floor(hq);
+    const double g = hq - (double)j, a = tmp[j], b = tmp[std::min(j + 1, (size_t)S - 1)];
+    return a == b ? a : (1.0 - g) * a + g * b;             // k_map_quant's map_interp
+  };
+  row[2 * stride] = q((1.0 - ci) / 2.0); row[3 * stride] = q((1.0 + ci) / 2.0);
+}
+// ser [3][S][N*C] -> group [3][4][N*C], pair [3][6][N*NP] (each may be null), n_credible[3]
+static void contrast_reduce(const double* ser, int S, int N, int C, double ci, double* group, double* pair, int64_t* n_credible) {
+  const size_t NC = (size_t)N * C, NP = (size_t)C * (C - 1) / 2, NNP = (size_t)N * NP;
+  std::vector<double> x(S), tmp(S);
+  double prow[BNMF_CON_NPROW];
+  for (int q = 0; q < BNMF_CON_NSTAT; ++q) {
+    const double* v = ser + (size_t)q * S * NC;
+    n_credible[q] = 0;
+    if (group)
+      for (size_t e = 0; e < NC; ++e) {
+        for (int s = 0; s < S; ++s) x[s] = v[(size_t)s * NC + e];
+        con_rows(x.data(), S, ci, tmp.data(), group + (size_t)q * BNMF_CON_NGROW * NC + e, NC);
+      }
+    size_t p = 0;
+    for (int a = 0; a < C; ++a)
+      for (int b = a + 1; b < C; ++b, ++p)
+        for (int n = 0; n < N; ++n) {
+          int gt = 0, lt = 0;
+          for (int s = 0; s < S; ++s) {
+            const double d = v[(size_t)s * NC + n + (size_t)N * a] - v[(size_t)s * NC + n + (size_t)N * b];
+            x[s] = d; gt += d > 0.0 ? 1 : 0; lt += d < 0.0 ? 1 : 0;
+          }
+          con_rows(x.data(), S, ci, tmp.data(), prow, 1);
+          prow[4] = (double)gt / (double)S; prow[5] = (double)lt / (double)S;
+          if (prow[2] > 0.0 || prow[3] < 0.0) n_credible[q]++;
+          if (pair) for (int i = 0; i < BNMF_CON_NPROW; ++i) pair[((size_t)q * BNMF_CON_NPROW + i) * NNP + n + (size_t)N * p] = prow[i];
+        }
+  }
+}
+
+// Group contrasts over the samples of r that used[] flags: k_map_colsum, then k_contrast (contrast.h) leaves the per-sample
+// group values [3][S][N*C] in the scratch, a wave per (group, sample) over member lists built here; the statistics over the samples and
+// the pairs are contrast_reduce's.
+static_assert(CT_NSTAT == BNMF_CON_NSTAT, "contrast.h and bnmf.h disagree");
+static int contrast_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* groups, double min_load, double ci, double* group,
+                         double* pair, double* series, int32_t* sizes, bnmf_contrast_info* info) {
+  if (int rc = range_enter(h, fn, h && info && groups, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  int C = 0, left = 0;
+  for (int g = 0; g < G; ++g) {
+    if (groups[g] < -1 || groups[g] >= BNMF_CON_MAX_GROUPS)
+      return fail(BNMF_EINVAL, "%s: groups[%d] = %d is not a label in -1..%d", fn, g, (int)groups[g], BNMF_CON_MAX_GROUPS - 1);
+    if (groups[g] < 0) ++left; else C = std::max(C, (int)groups[g] + 1);
+  }
+  std::vector<int> goff(C + 1, 0), members(G - left);
+  for (int g = 0; g < G; ++g) if (groups[g] >= 0) goff[groups[g] + 1]++;
+  for (int c = 0; c < C; ++c) if (!goff[c + 1]) return fail(BNMF_EINVAL, "%s: group %d has no member (the labels run to %d)", fn, c, C - 1);
+  if (C == 0) return fail(BNMF_EINVAL, "%s: no tumour is in any group", fn);
+  for (int c = 0; c < C; ++c) goff[c + 1] += goff[c];
+  { std::vector<int> at(goff.begin(), goff.end() - 1); for (int g = 0; g < G; ++g) if (groups[g] >= 0) members[at[groups[g]]++] = g; }   // ascending inside a group
+  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
+  if (!(ci < 1.0)) return fail(BNMF_EINVAL, "%s: credible_interval = %g must be below 1", fn, ci);
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const size_t NC = (size_t)N * C, nser = (size_t)CT_NSTAT * S * NC, lenP = (size_t)K * N;
+  double *cs, *dser; int *dslots, *dmem, *doff;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); dser = c.take<double>(nser); dslots = c.take<int>(S); dmem = c.take<int>(members.size()); doff = c.take<int>(C + 1);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), members.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(doff, goff.data(), goff.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
+  ConArgs a{};
+  a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.cs = cs; a.slots = dslots; a.members = dmem; a.goff = doff; a.out = dser;
+  a.lenE = (size_t)N * G; a.N = N; a.C = C; a.S = S; a.min_load = min_load;
+  bool reg = N <= CT_MAX_REG;
+  if (const char* e = getenv("BNMF_CON_FORM")) reg = reg && atoi(e) == 0;                                  // tests, tools: the tiled form
+  using ConKernel = decltype(&k_contrast<8, true>);
+  const ConKernel regs[4] = {k_contrast<8, true>, k_contrast<16, true>, k_contrast<24, true>, k_contrast<32, true>};
+  for (int s0 = 0; s0 < S; s0 += 65535) {                                                                  // (the samples are the grid's y)
+    const int nb = std::min(65535, S - s0);
+    ConArgs b = a; b.cs = cs + (size_t)s0 * N; b.slots = dslots + s0; b.out = dser + (size_t)s0 * NC;
+    if (reg) hipLaunchKernelGGL(regs[(N - 1) / 8], dim3(C, nb), dim3(64), 0, h->stream, b);
+    else hipLaunchKernelGGL((k_contrast<CT_TN, false>), dim3(C, nb, (N + CT_TN - 1) / CT_TN), dim3(64), 0, h->stream, b);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<double> hs(nser);
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, nser * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), nser * sizeof(double));
+  if (sizes) for (int c = 0; c < C; ++c) sizes[c] = goff[c + 1] - goff[c];
+  std::memset(info, 0, sizeof *info);
+  contrast_reduce(hs.data(), S, N, C, ci, group, C > 1 ? pair : nullptr, info->n_credible);
+  info->n_used = S; info->n_groups = C; info->n_pairs = C * (C - 1) / 2; info->n_left_out = left; info->min_load = min_load; info->credible_interval = ci;
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -981,6 +1099,15 @@ int bnmf_decompose_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t
                       double min_share, double* weight, double* fit, int32_t* nactive, int32_t* included, double* weights, bnmf_decompose_info* info) {
   return decompose_impl(h, "bnmf_decompose_at", {true, end_iter, n_samples}, used, reference_P, R, keep, n_steps, min_share, weight, fit, nactive, included,
                         weights, info);
+}
+
+int bnmf_contrast(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* groups, double min_load, double credible_interval, double* group, double* pair,
+                  double* series, int32_t* sizes, bnmf_contrast_info* info) {
+  return contrast_impl(h, "bnmf_contrast", {false, 0, last_n}, used, groups, min_load, credible_interval, group, pair, series, sizes, info);
+}
+int bnmf_contrast_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* groups, double min_load, double credible_interval,
+                     double* group, double* pair, double* series, int32_t* sizes, bnmf_contrast_info* info) {
+  return contrast_impl(h, "bnmf_contrast_at", {true, end_iter, n_samples}, used, groups, min_load, credible_interval, group, pair, series, sizes, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

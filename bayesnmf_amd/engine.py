@@ -100,6 +100,11 @@ class BnmfDecomposeInfo(C.Structure):
                 ("min_share", C.c_double), ("max_rel_change", C.c_double), ("min_cosine", C.c_double), ("min_cosine_at", C.c_int64)]
 
 
+class BnmfContrastInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_groups", C.c_int32), ("n_pairs", C.c_int32), ("n_left_out", C.c_int32), ("n_credible", C.c_int64 * 3),
+                ("min_load", C.c_double), ("credible_interval", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -109,6 +114,10 @@ class BnmfRelabelInfo(C.Structure):
 ATTR_LOAD_ROWS = ["load_mean", "load_var", "share", "p_present"]
 PROJ_FIT_ROWS = ["cosine", "rel_l1", "rel_change"]
 DEC_WEIGHT_ROWS = ["weight_mean", "weight_var", "share", "p_present"]
+CON_STATS = ["load", "share", "prevalence"]
+CON_GROUP_ROWS = ["mean", "var", "lower", "upper"]
+CON_PAIR_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less"]
+CON_MAX_GROUPS = 64
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -126,7 +135,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
-               "bnmf_decompose", "bnmf_decompose_at"]
+               "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at"]
 
 
 def lib():
@@ -188,6 +197,8 @@ def lib():
         L.bnmf_decompose.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, C.c_int, C.c_double, dp, dp, ip, ip, dp, C.POINTER(BnmfDecomposeInfo)]
         L.bnmf_decompose_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, C.c_int, C.c_double, dp, dp, ip, ip, dp,
                                         C.POINTER(BnmfDecomposeInfo)]
+        L.bnmf_contrast.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, dp, ip, C.POINTER(BnmfContrastInfo)]
+        L.bnmf_contrast_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, dp, ip, C.POINTER(BnmfContrastInfo)]
         lp = C.POINTER(C.c_int64)
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
@@ -599,6 +610,38 @@ class Engine:
         out.update({name: fit[i] for i, name in enumerate(PROJ_FIT_ROWS)})
         if weights:
             out["weights"] = np.stack([row.reshape((R, N), order="F") for row in ws]) if S else np.empty((0, R, N))
+        return out
+
+    def contrast(self, last_n, groups, used=None, end_iter=None, min_load=1.0, credible_interval=0.95, series=False):
+        """Group contrasts of exposures over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_contrast / bnmf_contrast_at), on the device.
+        groups (length G): the label 0 .. C-1 of every tumour, -1 = left out.  Per used sample, group and factor the group's mean
+        renormalised exposure (load), mean share of the tumour's total and prevalence (the fraction of its tumours with a load >=
+        min_load) are one draw each from the posterior of that group statistic.  Returns the info fields (n_credible a list per
+        statistic), sizes (C), group (3 x 4 x N x C: per statistic of CON_STATS the rows CON_GROUP_ROWS) and pair (3 x 6 x N x NP: the
+        rows CON_PAIR_ROWS of the difference a - b of the pairs a < b, a ascending, then b; p_greater / p_less the fraction of samples
+        with a positive / negative difference), pairs (the NP pairs (a, b)); with series also series (3 x S x N x C), every used
+        sample's values.  credible_interval None or <= 0: no interval, lower / upper are NaN."""
+        N, G = self.N, self.G
+        gl = np.ascontiguousarray(groups, dtype=np.int32)
+        if gl.ndim != 1 or gl.size != G:
+            raise BnmfError(-2, f"contrast: groups has shape {gl.shape}, G = {G} labels are needed")
+        u, S = self._used("contrast", used, last_n)
+        Cn = min(max(int(gl.max(initial=-1)) + 1, 1), CON_MAX_GROUPS)      # (a label the library refuses sizes nothing)
+        NP = Cn * (Cn - 1) // 2
+        grp, pr = np.empty((3, 4, N * Cn)), np.empty((3, 6, N * NP))
+        ser = np.empty((3, S, N * Cn)) if series else None
+        sizes = np.empty(Cn, dtype=np.int32)
+        ci = 0.0 if credible_interval is None else float(credible_interval)
+        info = BnmfContrastInfo()
+        self._range_call("contrast", last_n, end_iter, u, gl.ctypes.data_as(_IP), float(min_load), ci, _dp(grp), _dp(pr), _dp(ser),
+                         sizes.ctypes.data_as(_IP), C.byref(info))
+        out = self._info(info)
+        out["n_credible"] = [int(v) for v in info.n_credible]
+        out.update(sizes=sizes, group=grp.reshape((3, 4, Cn, N)).transpose(0, 1, 3, 2), pair=pr.reshape((3, 6, NP, N)).transpose(0, 1, 3, 2),
+                   pairs=[(a, b) for a in range(Cn) for b in range(a + 1, Cn)])
+        if series:
+            out["series"] = ser.reshape((3, S, Cn, N)).transpose(0, 1, 3, 2)
         return out
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):

@@ -58,6 +58,20 @@ def get_mode(matrix_list):
     return dict(matrix=matrix_list[idx[0]], top_counts=counts[:5], idx=idx)
 
 
+def contrast_labels(groups, G):
+    """get_contrast's labels: groups (G labels of any hashable kind; None / NaN = left out) -> (int32 labels 0 .. C-1 in order of first
+    appearance, -1 = left out; the C names)"""
+    gl = list(groups.tolist()) if hasattr(groups, "tolist") else list(groups)
+    if len(gl) != G:
+        raise ValueError(f"groups has {len(gl)} labels for {G} tumours")
+    number, labels = {}, np.full(G, -1, dtype=np.int32)
+    for g, v in enumerate(gl):
+        if v is None or v is pd.NA or (isinstance(v, float) and v != v):
+            continue
+        labels[g] = number.setdefault(v, len(number))
+    return labels, list(number)
+
+
 class bayesNMF_sampler:
     """Python mirror of the R6 class `bayesNMF_sampler` (public fields of R/bayesNMF_sampler.R:11-67)."""
 
@@ -750,8 +764,39 @@ class bayesNMF_sampler:
                  f"max_rel_change {r['max_rel_change']:.3g}", verbosity=1)
         return out
 
+    def get_contrast(self, groups, end_iter=None, n_samples=None, idx="MAP_idx", min_load=1.0, credible_interval=0.95, series=False):
+        """Does the activity of a signature differ between groups of tumours?  On the device (bnmf_contrast_at; not in the reference):
+        groups is a vector of G labels of any hashable kind, one per tumour (None / NaN: the tumour is left out); they are numbered
+        0 .. C-1 in order of first appearance.  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC: the last
+        MAP_over samples), restricted to `idx` ("MAP_idx": those whose A equals the mode of the range; None: every sample; else a
+        vector of recorded iterations), every sample gives one draw of each group's mean load of every signature (the renormalised
+        exposure of get_MAP), mean share of the tumour's total and prevalence (the fraction of the group's tumours in which the
+        signature carries at least min_load mutations); the difference of two groups then has a posterior of its own.
+        Returns dict(names: the C group names, pair_names: the NP pairs (a, b) of names, a before b; per statistic "load", "share",
+        "prevalence" a dict(mean, var, lower, upper: N x C arrays over the samples, quantile type 7 at credible_interval;
+        diff_mean, diff_var, diff_lower, diff_upper, p_greater, p_less: N x NP arrays of the difference a - b); sizes (C),
+        n_used, n_groups, n_pairs, n_left_out, n_credible: per statistic the (signature, pair) whose interval excludes 0, min_load,
+        credible_interval); with series also series (3 x S x N x C), every sample's values.  Factor n is taken to be the same signature in
+        every sample, as get_MAP takes it; no multiple-testing adjustment is made."""
+        if not hasattr(self._chain, "contrast"):
+            raise ValueError("get_contrast needs an engine that contrasts groups over its recorded samples (contrast); this engine_factory's cannot")
+        labels, names = contrast_labels(groups, self.dims["G"])
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.contrast(n, labels, used=used, min_load=min_load, credible_interval=credible_interval, series=series, **kw)
+        out = dict(names=names, pair_names=[(names[a], names[b]) for a, b in r["pairs"]])
+        for q, stat in enumerate(("load", "share", "prevalence")):
+            out[stat] = dict(zip(("mean", "var", "lower", "upper"), r["group"][q]))
+            out[stat].update(zip(("diff_mean", "diff_var", "diff_lower", "diff_upper", "p_greater", "p_less"), r["pair"][q]))
+        out.update({k: r[k] for k in ("sizes", "n_used", "n_groups", "n_pairs", "n_left_out", "n_credible", "min_load", "credible_interval")})
+        if series:
+            out["series"] = r["series"]
+        self.log(f"Contrast: groups {', '.join(f'{nm} ({int(m)})' for nm, m in zip(names, r['sizes']))}; {r['n_pairs']} pair"
+                 f"{'' if r['n_pairs'] == 1 else 's'} {', '.join(f'{a} - {b}' for a, b in out['pair_names'])}; n_credible load {r['n_credible'][0]}, "
+                 f"share {r['n_credible'][1]}, prevalence {r['n_credible'][2]}", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

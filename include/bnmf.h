@@ -386,6 +386,45 @@ int bnmf_decompose_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* 
                       int n_steps, double min_share, double* weight, double* fit, int32_t* nactive, int32_t* included, double* weights,
                       bnmf_decompose_info* info);
 
+/* Group contrasts of exposures over a recorded range, on the device: does the activity of a signature differ between groups
+ * of tumours?  groups [G] labels every tumour 0 .. C-1 (C = 1 + the largest label, every label in between with a member) or -1 = left
+ * out.  For every recorded sample flagged in used[] (oldest first; NULL = all), s = 0 .. S-1, with cs_s = colSums(P_s):
+ *   x_s[n,g] = A_s[n] != 0 ? E_s[n,g] cs_s[n] : +0.0, bnmf_map's renormalised exposure: the mutations of tumour g expected from signature n;
+ *   t = sum_n x_s[n,g];  the share r = x / t (0 where t is not positive);  the presence flag b = (x >= min_load).
+ *   Per group c of m_c tumours and factor n: v0 = the mean load (the group mean of x), v1 = the mean share (of r), v2 = the prevalence
+ *   #(b) / m_c, each sum in the canonical W = 64 order of bnmf_mixing over the members in ascending tumour order.
+ * The S values of v_q[n,c] are draws from the posterior of that group statistic; the difference of two groups then has a posterior too.
+ * group [BNMF_CON_NSTAT][BNMF_CON_NGROW][N*C], each row laid out n + N c: per statistic q over the used samples the mean, the variance
+ *   (S - 1 form) and the type-7 quantiles at (1 -+ credible_interval) / 2 of v_q[n,c].
+ * pair [BNMF_CON_NSTAT][BNMF_CON_NPROW][N*NP], each row n + N p: NP = C (C - 1) / 2 pairs (a, b), a < b, numbered with a ascending, then b
+ *   ascending; the same four rows of d_s = v_q[n,a] - v_q[n,b], then p_greater = #(d_s > 0) / S and p_less = #(d_s < 0) / S.  With C = 1
+ *   there is no pair and pair is not written.
+ * series [BNMF_CON_NSTAT][S][N*C]: v_q per used sample, each laid out n + N c.   sizes [C]: m_c.
+ * info: n_credible[q] = the (n, p) whose interval excludes 0 (lower > 0 or upper < 0); n_left_out = the tumours labelled -1.
+ * credible_interval <= 0 means no interval: the rows lower / upper are NaN and n_credible is 0.  group, pair, series and sizes may each be
+ * NULL.  Factor n is taken to be the same signature in every sample, as bnmf_map takes it.  Only + - * /, comparisons and integer counts
+ * in a fixed order: the same call gives the same bits; renumbering the groups permutes the outputs.  Any likelihood and prior: only P (its
+ * column sums), E and A are read.  Read-only for the chain; none of its streams is consumed and no random number is drawn.
+ * bnmf_contrast_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_waic_at;
+ * bnmf_contrast(h, n, ...) is bnmf_contrast_at(h, iter, n, ...).  Refused before any device work: null info or groups, a used[] value other
+ * than 0 / 1 (the index named), a label below -1 or >= BNMF_CON_MAX_GROUPS (the tumour named), a group 0 .. C-1 without a member (the group
+ * named), no tumour in any group, a min_load that is NaN, infinite or negative, a credible_interval that is NaN or >= 1 with BNMF_EINVAL;
+ * fewer than 2 used samples with BNMF_ESIZE; window = 0, a poisoned handle or nothing recorded with BNMF_ESTATE. */
+#define BNMF_CON_MAX_GROUPS 64
+#define BNMF_CON_NSTAT 3    /* 0 load, 1 share, 2 prevalence */
+#define BNMF_CON_NGROW 4    /* group rows: mean, variance (S - 1 form), lower, upper */
+#define BNMF_CON_NPROW 6    /* pair rows: mean, variance, lower, upper, p_greater, p_less */
+typedef struct { int32_t n_used, n_groups, n_pairs, n_left_out; int64_t n_credible[BNMF_CON_NSTAT];
+                 double min_load, credible_interval; } bnmf_contrast_info;
+int bnmf_contrast(bnmf_handle*, int last_n, const int32_t* used, const int32_t* groups /* [G]: 0..C-1, -1 = left out */,
+                  double min_load, double credible_interval,
+                  double* group  /* [3][4][N*C], each row laid out n + N c; may be NULL */,
+                  double* pair   /* [3][6][N*NP], each row n + N p; may be NULL */,
+                  double* series /* [3][S][N*C]; may be NULL */,
+                  int32_t* sizes /* [C]; may be NULL */, bnmf_contrast_info* info);
+int bnmf_contrast_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* groups, double min_load,
+                     double credible_interval, double* group, double* pair, double* series, int32_t* sizes, bnmf_contrast_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

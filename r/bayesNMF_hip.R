@@ -243,6 +243,54 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (prob) out$prob <- array(r$prob, c(K, N, G))
       out
     },
+    # Does the activity of a signature differ between groups of tumours?  On the device (bnmf_contrast_at; not in the reference): groups
+    # is a vector of G labels, one per tumour (NA: the tumour is left out), numbered in order of first appearance.  Over iterations
+    # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample gives one draw of each group's mean
+    # load of every signature (the renormalised exposure of get_MAP), mean share of the tumour's total and prevalence (the fraction of
+    # the group's tumours in which the signature carries at least min_load mutations), so the difference of two groups has a posterior.
+    # list(names, pair_names (NP x 2: a before b), load, share, prevalence (each a list: mean, var, lower, upper (N x C, quantile type 7
+    # at credible_interval) and diff_mean, diff_var, diff_lower, diff_upper, p_greater, p_less (N x NP) of the difference a - b), sizes,
+    # n_used, n_groups, n_pairs, n_left_out, n_credible (per statistic the (signature, pair) whose interval excludes 0), min_load,
+    # credible_interval), with series also series (N x C x S x 3).  No multiple-testing adjustment is made.
+    get_contrast = function(groups, end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                            idx = "MAP_idx", min_load = 1, credible_interval = 0.95, series = FALSE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      if (length(groups) != G) stop("groups must have one label per tumour (G = ", G, ")")
+      names <- unique(groups[!is.na(groups)])
+      labels <- match(groups, names) - 1L
+      r <- .Call("C_bnmf_contrast", self$handle, as.integer(end_iter), as.integer(n_samples), used, as.integer(labels), as.double(min_load),
+                 as.double(credible_interval), as.logical(series), c(K, G, N))
+      C <- r$n_groups; NP <- r$n_pairs
+      pairs <- if (NP > 0) t(utils::combn(C, 2)) else matrix(integer(0), 0, 2)
+      pair_names <- matrix(as.character(names)[pairs], NP, 2)
+      stat <- function(q) {
+        o <- list(mean = matrix(r$group[, 4 * q + 1], N, C), var = matrix(r$group[, 4 * q + 2], N, C),
+                  lower = matrix(r$group[, 4 * q + 3], N, C), upper = matrix(r$group[, 4 * q + 4], N, C))
+        if (NP > 0) {
+          rows <- c("diff_mean", "diff_var", "diff_lower", "diff_upper", "p_greater", "p_less")
+          for (i in seq_along(rows)) o[[rows[i]]] <- matrix(r$pair[, 6 * q + i], N, NP)
+        }
+        o
+      }
+      out <- list(names = names, pair_names = pair_names, load = stat(0), share = stat(1), prevalence = stat(2), sizes = r$sizes,
+                  n_used = r$n_used, n_groups = C, n_pairs = NP, n_left_out = r$n_left_out, n_credible = r$n_credible, min_load = r$min_load,
+                  credible_interval = r$credible_interval)
+      if (series) out$series <- array(r$series, c(N, C, r$n_used, 3))
+      message(sprintf("Contrast: groups %s; %d pair(s) %s; n_credible load %g, share %g, prevalence %g",
+                      paste(sprintf("%s (%d)", names, r$sizes), collapse = ", "), NP, paste(pair_names[, 1], pair_names[, 2], sep = " - ", collapse = ", "),
+                      r$n_credible[1], r$n_credible[2], r$n_credible[3]))
+      out
+    },
     # Exposures of new tumours under the recorded signatures, on the device (bnmf_project_at; not in the reference): new_data is a
     # K x J matrix of counts (or other non-negative values) of tumours the chain has not seen.  Over iterations end_iter - n_samples + 1
     # ... end_iter (defaults as get_WAIC), restricted to idx, every column is refitted to every sample's renormalised signatures by

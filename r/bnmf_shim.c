@@ -490,6 +490,75 @@ SEXP C_bnmf_attribution_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, S
   UNPROTECT(1);
   return out;
 }
+/* Group contrasts of exposures over recorded samples on the device (bnmf_contrast / bnmf_contrast_at): C_bnmf_contrast(ptr, end_iter
+ * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), groups (integer length G: the
+ * 0-based label of every tumour, -1 or NA = left out), min_load, credible_interval (<= 0: no interval), want_series (logical),
+ * dims c(K,G,N)) -> list(n_used, n_groups, n_pairs, n_left_out, n_credible (3: load, share, prevalence), min_load, credible_interval,
+ * sizes (C), group (N C x 12: column 4 q + i = row i — mean, variance, lower, upper — of statistic q, each laid out n + N c), pair
+ * (N NP x 18: column 6 q + i = row i — mean, variance, lower, upper, p_greater, p_less — of statistic q, each laid out n + N p; NULL
+ * with one group), series (N C x 3 S: column S q + s; or NULL)) over iterations end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_contrast_at: the same with end_iter required */
+/* the result list with sizes, group, pair and (if wanted) series allocated, the flags of used and the labels; returned unprotected */
+static SEXP con_alloc(SEXP n_samples, SEXP used, SEXP groups, SEXP want_series, SEXP dims, int32_t** u, int32_t** lab) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  const int G = d[1], N = d[2];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (XLENGTH(groups) != (R_xlen_t)G) Rf_error("bnmf: groups has %ld labels for %d tumours", (long)XLENGTH(groups), G);
+  *u = lgl_flags(used, n);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  int32_t* l = (int32_t*)R_alloc(G, sizeof(int32_t));
+  int C = 1;                                                              /* (a label the library refuses sizes nothing) */
+  for (int g = 0; g < G; ++g) {
+    const int v = INTEGER(groups)[g];
+    l[g] = v == NA_INTEGER ? -1 : v;
+    if (l[g] >= C && l[g] < BNMF_CON_MAX_GROUPS) C = l[g] + 1;
+  }
+  *lab = l;
+  const int NP = C * (C - 1) / 2;
+  static const char* nms[] = {"n_used", "n_groups", "n_pairs", "n_left_out", "n_credible", "min_load", "credible_interval", "sizes", "group", "pair", "series"};
+  SEXP out = PROTECT(named_list(11, nms));
+  SET_VECTOR_ELT(out, 7, Rf_allocVector(INTSXP, C));
+  SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, N * C, BNMF_CON_NSTAT * BNMF_CON_NGROW));
+  if (NP > 0) SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, N * NP, BNMF_CON_NSTAT * BNMF_CON_NPROW));
+  if (LOGICAL(want_series)[0] == TRUE) SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, N * C, BNMF_CON_NSTAT * S));
+  UNPROTECT(1);
+  return out;
+}
+static void con_finish(SEXP out, const bnmf_contrast_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_groups));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarInteger(info->n_pairs)); SET_VECTOR_ELT(out, 3, Rf_ScalarInteger(info->n_left_out));
+  SEXP nc = PROTECT(Rf_allocVector(REALSXP, BNMF_CON_NSTAT));
+  for (int q = 0; q < BNMF_CON_NSTAT; ++q) REAL(nc)[q] = (double)info->n_credible[q];
+  SET_VECTOR_ELT(out, 4, nc);
+  UNPROTECT(1);
+  SET_VECTOR_ELT(out, 5, Rf_ScalarReal(info->min_load)); SET_VECTOR_ELT(out, 6, Rf_ScalarReal(info->credible_interval));
+}
+SEXP C_bnmf_contrast(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP groups, SEXP min_load, SEXP ci, SEXP want_series, SEXP dims) {
+  int32_t *u = NULL, *lab = NULL;
+  SEXP out = PROTECT(con_alloc(n_samples, used, groups, want_series, dims, &u, &lab));
+  bnmf_contrast_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_contrast(get_handle(ptr), INTEGER(n_samples)[0], u, lab, REAL(min_load)[0], REAL(ci)[0], map_buf(out, 8), map_buf(out, 9), map_buf(out, 10),
+                      INTEGER(VECTOR_ELT(out, 7)), &info));
+  else
+    chk(bnmf_contrast_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, lab, REAL(min_load)[0], REAL(ci)[0], map_buf(out, 8),
+                         map_buf(out, 9), map_buf(out, 10), INTEGER(VECTOR_ELT(out, 7)), &info));
+  con_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_contrast_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP groups, SEXP min_load, SEXP ci, SEXP want_series, SEXP dims) {
+  int32_t *u = NULL, *lab = NULL;
+  SEXP out = PROTECT(con_alloc(n_samples, used, groups, want_series, dims, &u, &lab));
+  bnmf_contrast_info info;
+  chk(bnmf_contrast_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, lab, REAL(min_load)[0], REAL(ci)[0], map_buf(out, 8),
+                       map_buf(out, 9), map_buf(out, 10), INTEGER(VECTOR_ELT(out, 7)), &info));
+  con_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Exposures of new tumours under the recorded signatures on the device (bnmf_project / bnmf_project_at): C_bnmf_project(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), X (K x J real matrix, not
  * negative), n_steps, min_load, want_exposures (logical), dims c(K,G,N)) -> list(n_used, n_steps, n_present, min_load, total,
@@ -775,6 +844,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_project", (DL_FUNC)&C_bnmf_project, 9}, {"C_bnmf_project_at", (DL_FUNC)&C_bnmf_project_at, 9},
   {"C_bnmf_decompose", (DL_FUNC)&C_bnmf_decompose, 9}, {"C_bnmf_decompose_at", (DL_FUNC)&C_bnmf_decompose_at, 9},
   {"C_bnmf_relabel", (DL_FUNC)&C_bnmf_relabel, 8}, {"C_bnmf_relabel_at", (DL_FUNC)&C_bnmf_relabel_at, 8},
+  {"C_bnmf_contrast", (DL_FUNC)&C_bnmf_contrast, 9}, {"C_bnmf_contrast_at", (DL_FUNC)&C_bnmf_contrast_at, 9},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
