@@ -39,6 +39,7 @@
 #include "project.h"
 #include "decompose.h"
 #include "contrast.h"
+#include "regress.h"
 
 using namespace bnmf;
 

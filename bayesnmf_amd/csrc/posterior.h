@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h and contrast.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h and regress.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1029,6 +1029,171 @@ static int contrast_impl(bnmf_handle* h, const char* fn, Range r, const int32_t*
   return 0;
 }
 
+// ---- bnmf_regress's host parts; no device and no handle, so that a stand-alone host program can run them ----
+// canonB: the blocked canonical sum of v[0 .. m): blocks of BNMF_REG_BLOCK, each con_canon64, added with b ascending from +0.0
+static double reg_canonB(const double* v, size_t m) {
+  double t = 0.0;
+  for (size_t i0 = 0; i0 < m; i0 += BNMF_REG_BLOCK) t = t + con_canon64(v + i0, std::min((size_t)BNMF_REG_BLOCK, m - i0), 1);
+  return t;
+}
+// D [m][Q] row-major in member order -> L [Q][Q] row-major, the Cholesky factor of the Gram matrix (the upper triangle 0).  Returns -1, or
+// the first column j whose pivot d_j is not > 0 or not finite.  ratio = min_j d_j / Gm[j][j] and at = its j (the first wins a tie).
+static int regress_factor(const double* D, size_t m, int Q, double* L, double& ratio, int& at) {
+  std::vector<double> Gm((size_t)Q * Q), v(m);
+  for (int j = 0; j < Q; ++j)
+    for (int k = 0; k <= j; ++k) {
+      for (size_t i = 0; i < m; ++i) v[i] = D[i * Q + j] * D[i * Q + k];
+      Gm[(size_t)j * Q + k] = Gm[(size_t)k * Q + j] = reg_canonB(v.data(), m);
+    }
+  std::fill(L, L + (size_t)Q * Q, 0.0);
+  at = -1;
+  for (int j = 0; j < Q; ++j) {
+    double d = Gm[(size_t)j * Q + j];
+    for (int t = 0; t < j; ++t) d = d - L[j * Q + t] * L[j * Q + t];
+    if (!(d > 0.0) || std::isinf(d)) return j;
+    const double rj = d / Gm[(size_t)j * Q + j];
+    if (at < 0 || rj < ratio) { ratio = rj; at = j; }
+    L[j * Q + j] = std::sqrt(d);
+    for (int i = j + 1; i < Q; ++i) {
+      double w = Gm[(size_t)i * Q + j];
+      for (int t = 0; t < j; ++t) w = w - L[i * Q + t] * L[j * Q + t];
+      L[i * Q + j] = w / L[j * Q + j];
+    }
+  }
+  return -1;
+}
+// cser [3][S][N*Q], r2 and s2 [3][S][N] -> coef [3][6][N*Q], fit [3][5][N] (each may be null), n_credible [3][BNMF_REG_MAX_Q].  Every
+// (q, n, j) and (q, n) is a series of its own with its own sort: they are dealt to up to 16 threads (zplan.h's way); the counts are taken
+// from the finished rows, so the result does not depend on the threads.
+static void regress_reduce(const double* cser, const double* r2, const double* s2, int S, int N, int Q, double ci, double* coef, double* fit,
+                           int64_t (*n_credible)[BNMF_REG_MAX_Q]) {
+  const size_t NQ = (size_t)N * Q;
+  const long ncoef = (long)(BNMF_REG_NSTAT * NQ), nfit = (long)BNMF_REG_NSTAT * N;
+  std::vector<double> bounds(2 * (size_t)ncoef);            // lower, upper per (q, e): what n_credible counts, also without coef
+  auto work = [&](long lo, long hi) {
+    std::vector<double> x(S), tmp(S);
+    double row[4];
+    for (long i = lo; i < hi; ++i) {
+      if (i < ncoef) {                                      // a coefficient's series
+        const size_t q = (size_t)i / NQ, e = (size_t)i % NQ;
+        const double* v = cser + q * S * NQ + e;
+        int gt = 0, lt = 0;
+        for (int s = 0; s < S; ++s) { const double b = v[(size_t)s * NQ]; x[s] = b; gt += b > 0.0 ? 1 : 0; lt += b < 0.0 ? 1 : 0; }
+        con_rows(x.data(), S, ci, tmp.data(), row, 1);
+        bounds[2 * i] = row[2]; bounds[2 * i + 1] = row[3];
+        if (!coef) continue;
+        double* o = coef + q * BNMF_REG_NCROW * NQ + e;
+        for (int k = 0; k < 4; ++k) o[(size_t)k * NQ] = row[k];
+        o[4 * NQ] = (double)gt / (double)S; o[5 * NQ] = (double)lt / (double)S;
+      } else if (fit) {                                     // a factor's r2 and sigma2 series
+        const size_t q = (size_t)(i - ncoef) / N, n = (size_t)(i - ncoef) % N;
+        double* o = fit + q * BNMF_REG_NFIT * N + n;
+        int nv = 0;
+        for (int s = 0; s < S; ++s) { const double r = r2[(q * S + s) * N + n]; if (!std::isnan(r)) x[nv++] = r; }
+        row[0] = row[2] = row[3] = std::nan("");
+        if (nv) con_rows(x.data(), nv, ci, tmp.data(), row, 1);
+        o[0] = row[0]; o[(size_t)N] = row[2]; o[2 * (size_t)N] = row[3]; o[3 * (size_t)N] = (double)nv;
+        for (int s = 0; s < S; ++s) x[s] = s2[(q * S + s) * N + n];
+        o[4 * (size_t)N] = con_canon64(x.data(), S, 1) / (double)S;
+      }
+    }
+  };
+  const long nwork = ncoef + nfit;
+  const long nthr = std::max<long>(1, std::min<long>({(long)std::thread::hardware_concurrency(), 16L, nwork / 16}));          // at least 16 series each
+  std::vector<std::thread> pool;
+  for (long t = 1; t < nthr; ++t) pool.emplace_back(work, nwork * t / nthr, nwork * (t + 1) / nthr);
+  work(0, nwork / nthr);
+  for (auto& th : pool) th.join();
+  for (int q = 0; q < BNMF_REG_NSTAT; ++q) {
+    for (int j = 0; j < BNMF_REG_MAX_Q; ++j) n_credible[q][j] = 0;
+    for (size_t e = 0; e < NQ; ++e) if (bounds[2 * (q * NQ + e)] > 0.0 || bounds[2 * (q * NQ + e) + 1] < 0.0) n_credible[q][e / N]++;
+  }
+}
+
+// Regression of exposures on tumour covariates over the samples of r that used[] flags (regress.h): the member list, the
+// design in member order and its Cholesky factor are made here; k_map_colsum, then k_regress_total, k_regress_moments, k_regress_solve,
+// k_regress_resid and k_regress_fit leave the coefficients, r2 and sigma2 of every used sample in the scratch; the statistics over the samples are
+// regress_reduce's.
+static_assert(RG_BLOCK == BNMF_REG_BLOCK && RG_MAX_Q == BNMF_REG_MAX_Q && RG_NSTAT == BNMF_REG_NSTAT, "regress.h and bnmf.h disagree");
+static int regress_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const double* design, int Q, const int32_t* include, double ci,
+                        double* coef, double* fit, double* coef_series, double* r2_series, bnmf_regress_info* info) {
+  if (int rc = range_enter(h, fn, h && info && design, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members;
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) members.push_back(g);
+  }
+  const int m = (int)members.size();
+  if (Q < 1 || Q > BNMF_REG_MAX_Q) return fail(BNMF_EINVAL, "%s: Q = %d design columns, 1..%d are possible", fn, Q, BNMF_REG_MAX_Q);
+  std::vector<double> D((size_t)m * Q);                     // row-major in member order
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < Q; ++j) {
+      const double v = design[(size_t)members[i] + (size_t)G * j];
+      if (std::isnan(v) || std::isinf(v)) return fail(BNMF_EINVAL, "%s: design[%d, %d] = %g of an included tumour is not finite", fn, members[i], j, v);
+      D[(size_t)i * Q + j] = v;
+    }
+  if (!(ci < 1.0)) return fail(BNMF_EINVAL, "%s: credible_interval = %g must be below 1", fn, ci);
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (m <= Q) return fail(BNMF_ESIZE, "%s: %d included tumour%s for Q = %d design columns, more than Q are needed", fn, m, m == 1 ? "" : "s", Q);
+  std::vector<double> L((size_t)Q * Q);
+  double ratio = 0.0; int ratio_at = -1;
+  const int bad = regress_factor(D.data(), (size_t)m, Q, L.data(), ratio, ratio_at);
+  if (bad >= 0) return fail(BNMF_EINVAL, "%s: design is not of full column rank (column %d is a combination of the columns before it)", fn, bad);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const int nb = (m + RG_BLOCK - 1) / RG_BLOCK;
+  const size_t SN = (size_t)RG_NSTAT * S * N, NQ = (size_t)N * Q, lenP = (size_t)K * N;
+  RegArgs a{};
+  double* cs; int *dslots, *dmem; double *dD, *dL;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); a.part = c.take<double>(SN * nb * (Q + 1)); a.part2 = c.take<double>(SN * nb * 2);
+        a.coef = c.take<double>(SN * Q); a.ybar = c.take<double>(SN); a.r2 = c.take<double>(SN); a.sigma2 = c.take<double>(SN);
+        a.u = c.take<double>((size_t)S * m);
+        dD = c.take<double>(D.size()); dL = c.take<double>(L.size()); dslots = c.take<int>(S); dmem = c.take<int>(m);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dD, D.data(), D.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dL, L.data(), L.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
+  a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.cs = cs; a.slots = dslots; a.members = dmem; a.D = dD; a.L = dL;
+  a.lenE = (size_t)N * G; a.N = N; a.Q = Q; a.S = S; a.m = m; a.nb = nb;
+  int form = 0;
+  if (const char* e = getenv("BNMF_REG_FORM")) form = atoi(e) != 0;                                        // tests, tools: the narrow tiles
+  const int TN = form ? 2 : 4, TQ = form ? 2 : 4;
+  const int ntn = (N + TN - 1) / TN, ntq = (Q + TQ - 1) / TQ; const unsigned nlane = (unsigned)((SN + 63) / 64);
+  auto passes = [&](auto kern, unsigned units) {                                                           // (the samples are the grid's y)
+    for (int s0 = 0; s0 < S; s0 += 65535) {
+      RegArgs b = a; b.cs = cs + (size_t)s0 * N; b.slots = dslots + s0;
+      b.part = a.part + (size_t)s0 * nb * RG_NSTAT * N * (Q + 1); b.part2 = a.part2 + (size_t)s0 * nb * RG_NSTAT * N * 2;
+      b.coef = a.coef + (size_t)s0 * NQ; b.ybar = a.ybar + (size_t)s0 * N; b.u = a.u + (size_t)s0 * m;
+      hipLaunchKernelGGL(kern, dim3(units, std::min(65535, S - s0)), dim3(64), 0, h->stream, b);
+    }
+  };
+  passes(k_regress_total<RG_TC>, (unsigned)((m + 63) / 64));
+  if (form) passes(k_regress_moments<2, 2>, reg_units(ntn * ntq, nb)); else passes(k_regress_moments<4, 4>, reg_units(ntn * ntq, nb));
+  hipLaunchKernelGGL(k_regress_solve<RG_MAX_Q>, dim3(nlane), dim3(64), 0, h->stream, a);
+  if (form) passes(k_regress_resid<2>, reg_units(ntn, nb)); else passes(k_regress_resid<4>, reg_units(ntn, nb));
+  hipLaunchKernelGGL(k_regress_fit<RG_NSTAT>, dim3(nlane), dim3(64), 0, h->stream, a);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hc(SN * Q), hr(SN), hs2(SN);
+  HIPCHK(hipMemcpyAsync(hc.data(), a.coef, hc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hr.data(), a.r2, SN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hs2.data(), a.sigma2, SN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (coef_series) std::memcpy(coef_series, hc.data(), hc.size() * sizeof(double));
+  if (r2_series) std::memcpy(r2_series, hr.data(), SN * sizeof(double));
+  std::memset(info, 0, sizeof *info);
+  regress_reduce(hc.data(), hr.data(), hs2.data(), S, N, Q, ci, coef, fit, info->n_credible);
+  info->n_used = S; info->Q = Q; info->n_included = m; info->n_left_out = G - m; info->n_blocks = nb; info->min_pivot_at = ratio_at;
+  info->credible_interval = ci; info->min_pivot_ratio = ratio;
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1108,6 +1273,15 @@ int bnmf_contrast(bnmf_handle* h, int last_n, const int32_t* used, const int32_t
 int bnmf_contrast_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* groups, double min_load, double credible_interval,
                      double* group, double* pair, double* series, int32_t* sizes, bnmf_contrast_info* info) {
   return contrast_impl(h, "bnmf_contrast_at", {true, end_iter, n_samples}, used, groups, min_load, credible_interval, group, pair, series, sizes, info);
+}
+
+int bnmf_regress(bnmf_handle* h, int last_n, const int32_t* used, const double* design, int Q, const int32_t* include, double credible_interval, double* coef,
+                 double* fit, double* coef_series, double* r2_series, bnmf_regress_info* info) {
+  return regress_impl(h, "bnmf_regress", {false, 0, last_n}, used, design, Q, include, credible_interval, coef, fit, coef_series, r2_series, info);
+}
+int bnmf_regress_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* design, int Q, const int32_t* include,
+                    double credible_interval, double* coef, double* fit, double* coef_series, double* r2_series, bnmf_regress_info* info) {
+  return regress_impl(h, "bnmf_regress_at", {true, end_iter, n_samples}, used, design, Q, include, credible_interval, coef, fit, coef_series, r2_series, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

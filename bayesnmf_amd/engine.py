@@ -105,6 +105,11 @@ class BnmfContrastInfo(C.Structure):
                 ("min_load", C.c_double), ("credible_interval", C.c_double)]
 
 
+class BnmfRegressInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("Q", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32), ("n_blocks", C.c_int32),
+                ("min_pivot_at", C.c_int32), ("n_credible", (C.c_int64 * 16) * 3), ("credible_interval", C.c_double), ("min_pivot_ratio", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -118,6 +123,10 @@ CON_STATS = ["load", "share", "prevalence"]
 CON_GROUP_ROWS = ["mean", "var", "lower", "upper"]
 CON_PAIR_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less"]
 CON_MAX_GROUPS = 64
+REG_STATS = ["load", "share", "sqrt_load"]
+REG_COEF_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less"]
+REG_FIT_ROWS = ["r2_mean", "r2_lower", "r2_upper", "r2_samples", "sigma2_mean"]
+REG_MAX_Q = 16
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -135,7 +144,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
-               "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at"]
+               "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at"]
 
 
 def lib():
@@ -199,6 +208,8 @@ def lib():
                                         C.POINTER(BnmfDecomposeInfo)]
         L.bnmf_contrast.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, dp, ip, C.POINTER(BnmfContrastInfo)]
         L.bnmf_contrast_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, dp, ip, C.POINTER(BnmfContrastInfo)]
+        L.bnmf_regress.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfRegressInfo)]
+        L.bnmf_regress_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfRegressInfo)]
         lp = C.POINTER(C.c_int64)
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
@@ -642,6 +653,38 @@ class Engine:
                    pairs=[(a, b) for a in range(Cn) for b in range(a + 1, Cn)])
         if series:
             out["series"] = ser.reshape((3, S, Cn, N)).transpose(0, 1, 3, 2)
+        return out
+
+    def regress(self, last_n, design, include=None, used=None, end_iter=None, credible_interval=0.95, series=False):
+        """Regression of exposures on tumour covariates over the recorded samples flagged in used (length last_n, oldest first; None =
+        all) of the last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_regress / bnmf_regress_at), on
+        the device.  design (G x Q, Q <= REG_MAX_Q) is taken as given: the caller supplies the column of ones.  include (length G of
+        0 / 1, None = all): the tumours that enter the fit.  Per used sample, response (REG_STATS: the load, its share of the tumour's
+        total, its square root) and factor the least-squares coefficients are one draw from the posterior of the cohort's own
+        coefficient (the tumours' sampling error is not added).  Returns the info fields (n_credible 3 x Q: the factors whose interval
+        for a column excludes 0), coef (3 x 6 x N x Q: the rows REG_COEF_ROWS) and fit (3 x 5 x N: the rows REG_FIT_ROWS); with series
+        also coef_series (3 x S x N x Q) and r2_series (3 x S x N).  credible_interval None or <= 0: no interval, lower / upper are NaN."""
+        N, G = self.N, self.G
+        D = np.asfortranarray(design, dtype=np.float64)
+        if D.ndim != 2 or D.shape[0] != G:
+            raise BnmfError(-2, f"regress: design has shape {D.shape}, G = {G} rows are needed")
+        Q = D.shape[1]
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"regress: include has shape {inc.shape}, G = {G} flags are needed")
+        u, S = self._used("regress", used, last_n)
+        coef, fit = np.empty((3, 6, N * Q)), np.empty((3, 5, N))
+        cser = np.empty((3, S, N * Q)) if series else None
+        rser = np.empty((3, S, N)) if series else None
+        ci = 0.0 if credible_interval is None else float(credible_interval)
+        info = BnmfRegressInfo()
+        self._range_call("regress", last_n, end_iter, u, _dp(D.ravel(order="F")), Q, None if inc is None else inc.ctypes.data_as(_IP), ci, _dp(coef),
+                         _dp(fit), _dp(cser), _dp(rser), C.byref(info))
+        out = self._info(info)
+        out["n_credible"] = np.array([[int(v) for v in row][:max(Q, 0)] for row in info.n_credible], dtype=np.int64)
+        out.update(coef=coef.reshape((3, 6, Q, N)).transpose(0, 1, 3, 2), fit=fit)
+        if series:
+            out.update(coef_series=cser.reshape((3, S, Q, N)).transpose(0, 1, 3, 2), r2_series=rser)
         return out
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):

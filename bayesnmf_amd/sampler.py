@@ -72,6 +72,41 @@ def contrast_labels(groups, G):
     return labels, list(number)
 
 
+def regression_design(covariates, G, intercept=True, standardize=False):
+    """get_regression's design: covariates (a G x Q0 array, or a mapping name -> column of G values; None / NaN = missing) ->
+    (design G x Q float64, include: int32 0 / 1 flags of the tumours without a missing value or None when every tumour is complete,
+    the Q column names).  intercept prepends the column of ones, "(Intercept)"; standardize centres and scales every other column by
+    the mean and the standard deviation (n - 1 form) of the included rows."""
+    def column(col):
+        vals = list(col.tolist()) if hasattr(col, "tolist") else list(col)
+        return np.array([np.nan if v is None or v is pd.NA else float(v) for v in vals], dtype=np.float64)
+    if hasattr(covariates, "items"):
+        names, cols = [str(k) for k, _ in covariates.items()], [column(c) for _, c in covariates.items()]
+    else:
+        arr = np.asarray(covariates, dtype=object)
+        if arr.ndim == 1:
+            arr = arr[:, None]
+        if arr.ndim != 2:
+            raise ValueError(f"covariates has {arr.ndim} dimensions: a G x Q array or a mapping name -> column is needed")
+        cols = [column(arr[:, j]) for j in range(arr.shape[1])]
+        names = [f"x{j + 1}" for j in range(len(cols))]
+    for nm, c in zip(names, cols):
+        if c.size != G:
+            raise ValueError(f"covariate {nm} has {c.size} values for {G} tumours")
+    X = np.stack(cols, axis=1) if cols else np.empty((G, 0))
+    complete = ~np.isnan(X).any(axis=1)
+    if standardize:
+        for j, nm in enumerate(names):
+            v = X[complete, j]
+            sd = v.std(ddof=1) if v.size > 1 else 0.0
+            if not sd > 0:
+                raise ValueError(f"covariate {nm} is constant over the included tumours: it cannot be standardized")
+            X[:, j] = (X[:, j] - v.mean()) / sd
+    if intercept:
+        X, names = np.concatenate([np.ones((G, 1)), X], axis=1), ["(Intercept)"] + names
+    return np.asfortranarray(X), (None if complete.all() else complete.astype(np.int32)), names
+
+
 class bayesNMF_sampler:
     """Python mirror of the R6 class `bayesNMF_sampler` (public fields of R/bayesNMF_sampler.R:11-67)."""
 
@@ -795,8 +830,41 @@ class bayesNMF_sampler:
                  f"share {r['n_credible'][1]}, prevalence {r['n_credible'][2]}", verbosity=1)
         return out
 
+    def get_regression(self, covariates, end_iter=None, n_samples=None, idx="MAP_idx", intercept=True, standardize=False, credible_interval=0.95,
+                       series=False):
+        """Does the activity of a signature follow a covariate of the tumours (age, dose, purity), and is a group difference still
+        there once other covariates are in the model?  On the device (bnmf_regress_at; not in the reference): covariates is a G x Q0
+        array or a mapping name -> column of G values (a data frame); a tumour with a None / NaN is left out; intercept prepends the
+        column of ones; standardize centres and scales the other columns by the included tumours' mean and standard deviation.  Over
+        iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as get_contrast), every sample
+        gives one least-squares fit per signature of its load (the renormalised exposure of get_MAP), of its share of the tumour's total
+        and of the square root of its load on the design: the coefficients over the samples are draws from the posterior of the
+        cohort's own coefficient (the tumours' sampling error as a sample of a population is not added).
+        Returns dict(names: the Q column names; per response "load", "share", "sqrt_load" a dict(mean, var, lower, upper, p_greater,
+        p_less: N x Q arrays over the samples, quantile type 7 at credible_interval; r2_mean, r2_lower, r2_upper, r2_samples,
+        sigma2_mean: N); include (G flags, None = all), n_used, Q, n_included, n_left_out, n_blocks, min_pivot_ratio, min_pivot_at (how
+        close to collinear the design is), n_credible (3 x Q: the signatures whose interval for a column excludes 0),
+        credible_interval); with series also coef_series (3 x S x N x Q) and r2_series (3 x S x N).  No multiple-testing adjustment."""
+        if not hasattr(self._chain, "regress"):
+            raise ValueError("get_regression needs an engine that regresses over its recorded samples (regress); this engine_factory's cannot")
+        design, include, names = regression_design(covariates, self.dims["G"], intercept=intercept, standardize=standardize)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.regress(n, design, include=include, used=used, credible_interval=credible_interval, series=series, **kw)
+        out = dict(names=names, include=include)
+        for q, stat in enumerate(("load", "share", "sqrt_load")):
+            out[stat] = dict(zip(("mean", "var", "lower", "upper", "p_greater", "p_less"), r["coef"][q]))
+            out[stat].update(zip(("r2_mean", "r2_lower", "r2_upper", "r2_samples", "sigma2_mean"), r["fit"][q]))
+        out.update({k: r[k] for k in ("n_used", "Q", "n_included", "n_left_out", "n_blocks", "min_pivot_ratio", "min_pivot_at", "n_credible",
+                                      "credible_interval")})
+        if series:
+            out.update(coef_series=r["coef_series"], r2_series=r["r2_series"])
+        self.log(f"Regression: {r['n_included']} tumours included, {r['n_left_out']} left out; Q = {r['Q']}, min_pivot_ratio "
+                 f"{r['min_pivot_ratio']:.3g} (column {names[r['min_pivot_at']]}); n_credible for the load "
+                 f"{', '.join(f'{nm} {int(c)}' for nm, c in zip(names, r['n_credible'][0]))}", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

@@ -425,6 +425,55 @@ int bnmf_contrast(bnmf_handle*, int last_n, const int32_t* used, const int32_t* 
 int bnmf_contrast_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* groups, double min_load,
                      double credible_interval, double* group, double* pair, double* series, int32_t* sizes, bnmf_contrast_info* info);
 
+/* Regression of exposures on tumour covariates over a recorded range, on the device: does the activity of a signature follow
+ * age, dose or purity, and is a group difference still there once other covariates are in the model?  design [G x Q] column-major, one row
+ * per tumour, Q in 1 .. BNMF_REG_MAX_Q; it is taken as given: the caller supplies the column of ones.  include [G] holds 0 / 1 (NULL = all):
+ * the m included tumours g_0 < g_1 < ...; the design cells of the others are not read.  For every recorded sample flagged in used[] (oldest
+ * first; NULL = all), s = 0 .. S-1, with x_s[n,g], t and u = t > 0 ? 1 / t : 0.0 as for bnmf_contrast, the three responses are
+ *   y0 = x the load,   y1 = x u the share,   y2 = sqrt(x) the variance-stabilised load,
+ * and per (s, response q, factor n) the call solves the least-squares problem min_beta sum_i (y_i - sum_j design[g_i,j] beta_j)^2 by the
+ * normal equations: canonB is the blocked canonical sum over the included tumours in ascending order (blocks of BNMF_REG_BLOCK members, a
+ * block the canonical W = 64 sum of bnmf_mixing, the blocks added in order from +0.0);  Gm[j][k] = canonB(design[g_i,j] design[g_i,k]) and its
+ * Cholesky factor L (on the host, once per call);  w_j = canonB(y_i design[g_i,j]),  sy = canonB(y_i);  L z = w,  L' beta = z;  yhat_i = sum_j
+ * design[g_i,j] beta_j;  rss = canonB((y_i - yhat_i)^2),  tss = canonB((y_i - sy / m)^2),  r2 = tss > 0 ? 1 - rss / tss : NaN,  sigma2 = rss / (m - Q).
+ * A factor the sample excludes has y = +0.0: beta = 0, r2 = NaN.  sqrt of a negative load (real-valued data) is NaN by IEEE and stays one.
+ * The S values of beta_j are draws from the posterior of the cohort's own least-squares coefficient, the finite-population quantity, as
+ * bnmf_contrast's group means are: the sampling error of the tumours as a sample of a population is NOT added.
+ * coef [BNMF_REG_NSTAT][BNMF_REG_NCROW][N*Q], each row laid out n + N j: over the used samples the mean, the variance (S - 1 form), the type-7
+ *   quantiles at (1 -+ credible_interval) / 2 of beta_j, p_greater = #(beta_j > 0) / S and p_less = #(beta_j < 0) / S.
+ * fit [BNMF_REG_NSTAT][BNMF_REG_NFIT][N]: the mean and the two quantiles of r2 over the samples whose r2 is not NaN, their number (NaN, NaN,
+ *   NaN, 0 without one), and the mean of sigma2 over all used samples.
+ * coef_series [BNMF_REG_NSTAT][S][N*Q]: beta per used sample, each n + N j.   r2_series [BNMF_REG_NSTAT][S][N].
+ * info: n_credible[q][j] = the factors whose interval for column j excludes 0 (lower > 0 or upper < 0), per column so that the intercept
+ *   does not drown the covariates;  min_pivot_ratio = min_j d_j / Gm[j][j] over the Cholesky pivots d_j and min_pivot_at its j: how close to
+ *   collinear the design is (1 for orthogonal columns, towards 0 for a nearly dependent one);  n_blocks = ceil(m / BNMF_REG_BLOCK).
+ * credible_interval <= 0 means no interval: lower / upper are NaN and n_credible is 0.  coef, fit, coef_series and r2_series may each be
+ * NULL.  Only + - * /, sqrt, comparisons and integer counts in a fixed order: the bits depend on the recorded samples, used, design,
+ * include and credible_interval alone; scaling a design column by a power of two divides its beta by it exactly; leaving tumours out
+ * through include gives the bits of a chain and design without them.  Read-only for the chain; no random number is drawn.
+ * bnmf_regress_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_waic_at;
+ * bnmf_regress(h, n, ...) is bnmf_regress_at(h, iter, n, ...).  Refused before any device work: null info or design, a used[] or include[]
+ * value other than 0 / 1 (the index named), Q outside 1 .. BNMF_REG_MAX_Q, a NaN or infinite design cell of an included tumour (the cell
+ * named), a credible_interval that is NaN or >= 1 with BNMF_EINVAL; fewer than 2 used samples or m <= Q with BNMF_ESIZE; a design not of
+ * full column rank (a pivot d_j that is not > 0 or not finite; the column named, no threshold) with BNMF_EINVAL; window = 0, a poisoned
+ * handle or nothing recorded with BNMF_ESTATE. */
+#define BNMF_REG_MAX_Q 16
+#define BNMF_REG_BLOCK 1024
+#define BNMF_REG_NSTAT 3   /* 0 load, 1 share, 2 sqrt(load) */
+#define BNMF_REG_NCROW 6   /* coef rows: mean, variance (S - 1), lower, upper, p_greater, p_less */
+#define BNMF_REG_NFIT  5   /* fit rows per factor: mean r2, lower r2, upper r2, samples with an r2, mean sigma2 */
+typedef struct { int32_t n_used, Q, n_included, n_left_out, n_blocks, min_pivot_at;
+                 int64_t n_credible[BNMF_REG_NSTAT][BNMF_REG_MAX_Q];
+                 double credible_interval, min_pivot_ratio; } bnmf_regress_info;
+int bnmf_regress(bnmf_handle*, int last_n, const int32_t* used, const double* design /* G x Q column-major */, int Q,
+                 const int32_t* include /* [G] 0 / 1, NULL = all */, double credible_interval,
+                 double* coef        /* [3][6][N*Q], each row n + N j; may be NULL */,
+                 double* fit         /* [3][5][N]; may be NULL */,
+                 double* coef_series /* [3][S][N*Q]; may be NULL */,
+                 double* r2_series   /* [3][S][N]; may be NULL */, bnmf_regress_info* info);
+int bnmf_regress_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const double* design, int Q, const int32_t* include,
+                    double credible_interval, double* coef, double* fit, double* coef_series, double* r2_series, bnmf_regress_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

@@ -291,6 +291,61 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       r$n_credible[1], r$n_credible[2], r$n_credible[3]))
       out
     },
+    # Does the activity of a signature follow a covariate of the tumours (age, dose, purity), and is a group difference still there once
+    # other covariates are in the model?  On the device (bnmf_regress_at; not in the reference): covariates is a G x Q0 numeric matrix or
+    # a data frame of numeric columns, one row per tumour (a row with an NA is left out); intercept prepends the column of ones;
+    # standardize centres and scales the other columns by the included rows' mean and sd.  Over iterations end_iter - n_samples + 1 ...
+    # end_iter (defaults as get_WAIC), restricted to idx, every sample gives one least-squares fit per signature of its load (the
+    # renormalised exposure of get_MAP), of its share of the tumour's total and of the square root of its load: the coefficients over the
+    # samples are draws from the posterior of the cohort's own coefficient (the tumours' sampling error is not added).
+    # list(names, load, share, sqrt_load (each a list: mean, var, lower, upper, p_greater, p_less (N x Q, quantile type 7 at
+    # credible_interval) and r2_mean, r2_lower, r2_upper, r2_samples, sigma2_mean (N)), include, n_used, Q, n_included, n_left_out, n_blocks,
+    # min_pivot_ratio, min_pivot_at (the column closest to a combination of those before it), n_credible (Q x 3: the signatures whose
+    # interval for a column excludes 0), credible_interval), with series also coef_series (N x Q x S x 3) and r2_series (N x S x 3).
+    get_regression = function(covariates, end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                              idx = "MAP_idx", intercept = TRUE, standardize = FALSE, credible_interval = 0.95, series = FALSE) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      X <- as.matrix(covariates)
+      if (!is.numeric(X) || nrow(X) != G) stop("covariates must be numeric with one row per tumour (G = ", G, ")")
+      names <- if (is.null(colnames(X))) paste0("x", seq_len(ncol(X))) else colnames(X)
+      include <- stats::complete.cases(X)
+      if (standardize) for (j in seq_len(ncol(X))) {
+        v <- X[include, j]
+        if (!(stats::sd(v) > 0)) stop("covariate ", names[j], " is constant over the included tumours: it cannot be standardized")
+        X[, j] <- (X[, j] - mean(v)) / stats::sd(v)
+      }
+      if (intercept) { X <- cbind(1, X); names <- c("(Intercept)", names) }
+      storage.mode(X) <- "double"
+      r <- .Call("C_bnmf_regress", self$handle, as.integer(end_iter), as.integer(n_samples), used, X, if (all(include)) NULL else include,
+                 as.double(credible_interval), as.logical(series), c(K, G, N))
+      Q <- r$Q
+      stat <- function(q) {
+        rows <- c("mean", "var", "lower", "upper", "p_greater", "p_less")
+        o <- list()
+        for (i in seq_along(rows)) o[[rows[i]]] <- matrix(r$coef[, 6 * q + i], N, Q, dimnames = list(NULL, names))
+        frows <- c("r2_mean", "r2_lower", "r2_upper", "r2_samples", "sigma2_mean")
+        for (i in seq_along(frows)) o[[frows[i]]] <- r$fit[, 5 * q + i]
+        o
+      }
+      out <- list(names = names, load = stat(0), share = stat(1), sqrt_load = stat(2), include = include, n_used = r$n_used, Q = Q,
+                  n_included = r$n_included, n_left_out = r$n_left_out, n_blocks = r$n_blocks, min_pivot_ratio = r$min_pivot_ratio,
+                  min_pivot_at = r$min_pivot_at + 1L, n_credible = r$n_credible, credible_interval = r$credible_interval)
+      if (series) { out$coef_series <- array(r$coef_series, c(N, Q, r$n_used, 3)); out$r2_series <- array(r$r2_series, c(N, r$n_used, 3)) }
+      message(sprintf("Regression: %d tumours included, %d left out; Q = %d, min_pivot_ratio %.3g (column %s); n_credible for the load %s",
+                      r$n_included, r$n_left_out, Q, r$min_pivot_ratio, names[r$min_pivot_at + 1L],
+                      paste(sprintf("%s %g", names, r$n_credible[, 1]), collapse = ", ")))
+      out
+    },
     # Exposures of new tumours under the recorded signatures, on the device (bnmf_project_at; not in the reference): new_data is a
     # K x J matrix of counts (or other non-negative values) of tumours the chain has not seen.  Over iterations end_iter - n_samples + 1
     # ... end_iter (defaults as get_WAIC), restricted to idx, every column is refitted to every sample's renormalised signatures by

@@ -559,6 +559,73 @@ SEXP C_bnmf_contrast_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP
   UNPROTECT(1);
   return out;
 }
+/* Regression of exposures on tumour covariates over recorded samples on the device (bnmf_regress / bnmf_regress_at): C_bnmf_regress(ptr,
+ * end_iter (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), design (G x Q real
+ * matrix, taken as given: the caller supplies the column of ones), include (logical length G, or NULL = all), credible_interval (<= 0: no
+ * interval), want_series (logical), dims c(K,G,N)) -> list(n_used, Q, n_included, n_left_out, n_blocks, min_pivot_at (0-based column),
+ * n_credible (Q x 3: column q = response q), credible_interval, min_pivot_ratio, coef (N Q x 18: column 6 q + i = row i — mean, variance,
+ * lower, upper, p_greater, p_less — of response q, each laid out n + N j), fit (N x 15: column 5 q + i = row i — mean r2, lower r2, upper
+ * r2, samples with an r2, mean sigma2), coef_series (N Q x 3 S: column S q + s; or NULL), r2_series (N x 3 S; or NULL)) over iterations
+ * end_iter - n_samples + 1 ... end_iter.  C_bnmf_regress_at: the same with end_iter required */
+/* the result list with coef, fit and (if wanted) the series allocated, the flags of used and include; returned unprotected */
+static SEXP reg_alloc(SEXP n_samples, SEXP used, SEXP design, SEXP include, SEXP want_series, SEXP dims, int32_t** u, int32_t** inc, int* Q) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  const int G = d[1], N = d[2];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (Rf_nrows(design) != G) Rf_error("bnmf: design has %d rows for %d tumours", Rf_nrows(design), G);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  *u = lgl_flags(used, n);
+  *inc = lgl_flags(include, G);
+  *Q = Rf_ncols(design);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "Q", "n_included", "n_left_out", "n_blocks", "min_pivot_at", "n_credible", "credible_interval", "min_pivot_ratio",
+                              "coef", "fit", "coef_series", "r2_series"};
+  SEXP out = PROTECT(named_list(13, nms));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, N * *Q, BNMF_REG_NSTAT * BNMF_REG_NCROW));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, N, BNMF_REG_NSTAT * BNMF_REG_NFIT));
+  if (LOGICAL(want_series)[0] == TRUE) {
+    SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, N * *Q, BNMF_REG_NSTAT * S));
+    SET_VECTOR_ELT(out, 12, Rf_allocMatrix(REALSXP, N, BNMF_REG_NSTAT * S));
+  }
+  UNPROTECT(1);
+  return out;
+}
+static void reg_finish(SEXP out, const bnmf_regress_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->Q));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarInteger(info->n_included)); SET_VECTOR_ELT(out, 3, Rf_ScalarInteger(info->n_left_out));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarInteger(info->n_blocks)); SET_VECTOR_ELT(out, 5, Rf_ScalarInteger(info->min_pivot_at));
+  SEXP nc = PROTECT(Rf_allocMatrix(REALSXP, info->Q, BNMF_REG_NSTAT));
+  for (int q = 0; q < BNMF_REG_NSTAT; ++q) for (int j = 0; j < info->Q; ++j) REAL(nc)[j + info->Q * q] = (double)info->n_credible[q][j];
+  SET_VECTOR_ELT(out, 6, nc);
+  UNPROTECT(1);
+  SET_VECTOR_ELT(out, 7, Rf_ScalarReal(info->credible_interval)); SET_VECTOR_ELT(out, 8, Rf_ScalarReal(info->min_pivot_ratio));
+}
+SEXP C_bnmf_regress(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP design, SEXP include, SEXP ci, SEXP want_series, SEXP dims) {
+  int32_t *u = NULL, *inc = NULL; int Q = 0;
+  SEXP out = PROTECT(reg_alloc(n_samples, used, design, include, want_series, dims, &u, &inc, &Q));
+  bnmf_regress_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_regress(get_handle(ptr), INTEGER(n_samples)[0], u, REAL(design), Q, inc, REAL(ci)[0], map_buf(out, 9), map_buf(out, 10), map_buf(out, 11),
+                     map_buf(out, 12), &info));
+  else
+    chk(bnmf_regress_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(design), Q, inc, REAL(ci)[0], map_buf(out, 9),
+                        map_buf(out, 10), map_buf(out, 11), map_buf(out, 12), &info));
+  reg_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_regress_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP design, SEXP include, SEXP ci, SEXP want_series, SEXP dims) {
+  int32_t *u = NULL, *inc = NULL; int Q = 0;
+  SEXP out = PROTECT(reg_alloc(n_samples, used, design, include, want_series, dims, &u, &inc, &Q));
+  bnmf_regress_info info;
+  chk(bnmf_regress_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(design), Q, inc, REAL(ci)[0], map_buf(out, 9),
+                      map_buf(out, 10), map_buf(out, 11), map_buf(out, 12), &info));
+  reg_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Exposures of new tumours under the recorded signatures on the device (bnmf_project / bnmf_project_at): C_bnmf_project(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), X (K x J real matrix, not
  * negative), n_steps, min_load, want_exposures (logical), dims c(K,G,N)) -> list(n_used, n_steps, n_present, min_load, total,
@@ -845,6 +912,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_decompose", (DL_FUNC)&C_bnmf_decompose, 9}, {"C_bnmf_decompose_at", (DL_FUNC)&C_bnmf_decompose_at, 9},
   {"C_bnmf_relabel", (DL_FUNC)&C_bnmf_relabel, 8}, {"C_bnmf_relabel_at", (DL_FUNC)&C_bnmf_relabel_at, 8},
   {"C_bnmf_contrast", (DL_FUNC)&C_bnmf_contrast, 9}, {"C_bnmf_contrast_at", (DL_FUNC)&C_bnmf_contrast_at, 9},
+  {"C_bnmf_regress", (DL_FUNC)&C_bnmf_regress, 9}, {"C_bnmf_regress_at", (DL_FUNC)&C_bnmf_regress_at, 9},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
