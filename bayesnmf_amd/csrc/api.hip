@@ -40,6 +40,7 @@
 #include "decompose.h"
 #include "contrast.h"
 #include "regress.h"
+#include "coactivity.h"
 
 using namespace bnmf;
 

@@ -1,10 +1,11 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h and regress.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h and coactivity.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
 #pragma once
+#include "reduce_host.h"   // the device-free reductions over the samples
 
 // copy the `last_n` consecutive samples that end at iteration `end_iter` (oldest first) of a ring to the host: sample `it` lives in slot
 // (it - 1) % (window + 1), so they are at most two contiguous runs
@@ -912,31 +913,7 @@ static int decompose_impl(bnmf_handle* h, const char* fn, Range r, const int32_t
 }
 
 // ---- bnmf_contrast's host reduction; no device and no handle, so that a stand-alone host program can run it ----
-// the canonical W = 64 sum of v[0], v[stride], ..., v[(m - 1) stride]: accumulator l adds elements l, l + 64, ... from +0.0, then wave_tree64's halving tree
-static double con_canon64(const double* v, size_t m, size_t stride) {
-  double acc[64];
-  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
-  for (size_t i = 0; i < m; ++i) acc[i & 63] = acc[i & 63] + v[i * stride];
-  for (int hh = 32; hh >= 1; hh >>= 1) for (int l = 0; l < hh; ++l) acc[l] = acc[l] + acc[l + hh];
-  return acc[0];
-}
-// mean, variance (S - 1 form) and the two type-7 quantiles of x[0 .. S) into row[0], row[stride], row[2 stride], row[3 stride]; tmp: S doubles.
-// The quantiles are quantile7's expression on one sort (a NaN sorts last, as numpy's does); ci <= 0: NaN.
-static void con_rows(const double* x, int S, double ci, double* tmp, double* row, size_t stride) {
-  const double mean = con_canon64(x, S, 1) / (double)S;
-  for (int s = 0; s < S; ++s) { const double d = x[s] - mean; tmp[s] = d * d; }
-  row[0] = mean; row[stride] = con_canon64(tmp, S, 1) / (double)(S - 1);
-  if (!(ci > 0.0)) { row[2 * stride] = row[3 * stride] = std::nan(""); return; }
-  std::copy(x, x + S, tmp);
-  std::sort(tmp, tmp + S, [](double a, double b) { return a < b || (std::isnan(b) && !std::isnan(a)); });
-  auto q = [&](double prob) {
-    const double hq = (double)(S - 1) * prob;
-    const size_t j = (size_t)std::floor(hq);
-    const double g = hq - (double)j, a = tmp[j], b = tmp[std::min(j + 1, (size_t)S - 1)];
-    return a == b ? a : (1.0 - g) * a + g * b;             // k_map_quant's map_interp
-  };
-  row[2 * stride] = q((1.0 - ci) / 2.0); row[3 * stride] = q((1.0 + ci) / 2.0);
-}
+// (con_canon64 and con_rows: reduce_host.h)
 // ser [3][S][N*C] -> group [3][4][N*C], pair [3][6][N*NP] (each may be null), n_credible[3]
 static void contrast_reduce(const double* ser, int S, int N, int C, double ci, double* group, double* pair, int64_t* n_credible) {
   const size_t NC = (size_t)N * C, NP = (size_t)C * (C - 1) / 2, NNP = (size_t)N * NP;
@@ -1099,11 +1076,7 @@ static void regress_reduce(const double* cser, const double* r2, const double* s
     }
   };
   const long nwork = ncoef + nfit;
-  const long nthr = std::max<long>(1, std::min<long>({(long)std::thread::hardware_concurrency(), 16L, nwork / 16}));          // at least 16 series each
-  std::vector<std::thread> pool;
-  for (long t = 1; t < nthr; ++t) pool.emplace_back(work, nwork * t / nthr, nwork * (t + 1) / nthr);
-  work(0, nwork / nthr);
-  for (auto& th : pool) th.join();
+  deal_threads(nwork, work);
   for (int q = 0; q < BNMF_REG_NSTAT; ++q) {
     for (int j = 0; j < BNMF_REG_MAX_Q; ++j) n_credible[q][j] = 0;
     for (size_t e = 0; e < NQ; ++e) if (bounds[2 * (q * NQ + e)] > 0.0 || bounds[2 * (q * NQ + e) + 1] < 0.0) n_credible[q][e / N]++;
@@ -1191,6 +1164,104 @@ static int regress_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* 
   regress_reduce(hc.data(), hr.data(), hs2.data(), S, N, Q, ci, coef, fit, info->n_credible);
   info->n_used = S; info->Q = Q; info->n_included = m; info->n_left_out = G - m; info->n_blocks = nb; info->min_pivot_at = ratio_at;
   info->credible_interval = ci; info->min_pivot_ratio = ratio;
+  return 0;
+}
+
+// Co-activity of signatures over the samples of r that used[] flags (coactivity.h): the member list is made here;
+// k_map_colsum and k_coa_cosine run once over the range; then per batch of samples (their ranks are S N m int32: the batch keeps the
+// scratch under COA_SCRATCH_CAP, as attr_impl's does) k_coa_mean, k_coa_mu, k_coa_pairs, the rank transform (k_coa_rank, or k_coa_sort +
+// k_coa_search through sorted chunks), k_coa_rsum and k_coa_tail leave the four values of every pair in the series; the statistics over
+// the samples are coactivity_reduce's.
+static_assert(CO_NSTAT == BNMF_COA_NSTAT, "coactivity.h and bnmf.h disagree");
+static constexpr size_t COA_SCRATCH_CAP = (size_t)256 << 20;    // bytes of ranks, sorted chunks and block partials per batch
+static constexpr int COA_CHUNK = 16384, COA_WIDTH = 1024;       // doubles of a sorted chunk, threads of the sorting workgroup (measured)
+static int coactivity_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, double min_load, double ci,
+                           double* pair, double* series, bnmf_coactivity_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members;
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) members.push_back(g);
+  }
+  const int m = (int)members.size();
+  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
+  if (!(ci < 1.0)) return fail(BNMF_EINVAL, "%s: credible_interval = %g must be below 1", fn, ci);
+  if (N < 2) return fail(BNMF_ESIZE, "%s: N = %d factor%s, a pair needs at least 2", fn, N, N == 1 ? "" : "s");
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (m < 3) return fail(BNMF_ESIZE, "%s: %d included tumour%s, a correlation needs at least 3", fn, m, m == 1 ? "" : "s");
+  if (m > BNMF_COA_MAX_M) return fail(BNMF_ESIZE, "%s: %d included tumours, at most %d keep the rank sums inside int64", fn, m, BNMF_COA_MAX_M);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  auto env_int = [](const char* name, long long dflt) { const char* e = getenv(name); const long long v = e ? atoll(e) : 0; return v >= 1 ? v : dflt; };
+  int form = 0;
+  if (const char* e = getenv("BNMF_COA_FORM")) form = atoi(e) != 0;                                        // tests, tools: narrow tiles, ranks through the scratch
+  int chunk = CO_MIN_CHUNK;                                                                                // a power of two in 64 .. 16,384
+  { const long long want = std::min<long long>(env_int("BNMF_COA_CHUNK", COA_CHUNK), CO_MAX_CHUNK); while ((long long)chunk * 2 <= want) chunk *= 2; }
+  const int width = (int)env_int("BNMF_COA_WIDTH", COA_WIDTH);                                            // tools: 256, 512 or 1,024 threads
+  const int nchunk = (m + chunk - 1) / chunk;
+  const bool general = form || nchunk > 1;
+  int n2 = CO_MIN_CHUNK;                                                                                   // keys of the one-chunk form
+  while (n2 < m && n2 < chunk) n2 *= 2;
+  const int nb = (m + RG_BLOCK - 1) / RG_BLOCK, NP = N * (N - 1) / 2;
+  const size_t NN = (size_t)N * N, lenP = (size_t)K * N;
+  const size_t per = (size_t)N * m * 4 + (general ? (size_t)N * nchunk * chunk * 8 : 0) + (size_t)nb * (N * 8 + NN * 12) + NN * 8 + (size_t)N * 12 + 6 * 256;
+  const int Sb = (int)std::min<long long>({env_int("BNMF_COA_BATCH", (long long)std::max<size_t>(1, COA_SCRATCH_CAP / per)), (long long)S, 65535LL});
+  CoaArgs a{};
+  double* cs; int *dslots, *dmem;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); a.ser = c.take<double>((size_t)CO_NSTAT * S * NP);
+        a.partM = c.take<double>((size_t)Sb * nb * N); a.mu = c.take<double>((size_t)Sb * N); a.partS = c.take<double>((size_t)Sb * nb * NN);
+        a.partC = c.take<int>((size_t)Sb * nb * NN); a.c = c.take<int>((size_t)Sb * N * m);
+        a.sorted = general ? c.take<double>((size_t)Sb * N * nchunk * chunk) : nullptr;
+        a.flag = c.take<int>((size_t)Sb * N); a.T = c.take<long long>((size_t)Sb * NN);
+        dslots = c.take<int>(S); dmem = c.take<int>(m);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, lenP, K, N, (const int*)dslots, cs);
+  a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.ringP = h->arr[BNMF_P].ring; a.cs = cs; a.slots = dslots; a.members = dmem;
+  a.lenE = (size_t)N * G; a.lenP = lenP; a.N = N; a.K = K; a.S = S; a.m = m; a.nb = nb; a.chunk = chunk; a.nchunk = nchunk; a.min_load = min_load;
+  const int T = form ? 2 : 4, nt = (N + T - 1) / T, ntp = nt * (nt + 1) / 2;
+  const size_t lds = (size_t)(general ? chunk : n2) * sizeof(double);
+  using RankKernel = decltype(&k_coa_rank<1024>);
+  using SortKernel = decltype(&k_coa_sort<1024>);
+  const int wi = width <= 256 ? 0 : width <= 512 ? 1 : 2, wt = 256 << wi;
+  const RankKernel krank[3] = {k_coa_rank<256>, k_coa_rank<512>, k_coa_rank<1024>};
+  const SortKernel ksort[3] = {k_coa_sort<256>, k_coa_sort<512>, k_coa_sort<1024>};
+  if (int rc = general ? opt_in_lds(ksort[wi], lds, lds) : opt_in_lds(krank[wi], lds, lds)) return rc;   // (the workgroup vote keeps a static word of its own: ask for the keys only)
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int ns = std::min(Sb, S - s0);
+    a.s0 = s0;
+    hipLaunchKernelGGL(k_coa_cosine<CO_NSTAT>, dim3((unsigned)((NP + 63) / 64), ns), dim3(64), 0, h->stream, a);
+    if (form) hipLaunchKernelGGL(k_coa_mean<2>, dim3(reg_units(nt, nb), ns), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_coa_mean<4>, dim3(reg_units(nt, nb), ns), dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL(k_coa_mu<CO_NSTAT>, dim3((unsigned)(((size_t)ns * N + 63) / 64)), dim3(64), 0, h->stream, a, ns);
+    if (form) hipLaunchKernelGGL(k_coa_pairs<2>, dim3(reg_units(ntp, nb), ns), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_coa_pairs<4>, dim3(reg_units(ntp, nb), ns), dim3(64), 0, h->stream, a);
+    if (!general) hipLaunchKernelGGL(krank[wi], dim3(N, ns), dim3(wt), lds, h->stream, a, n2);
+    else {
+      HIPCHK(hipMemsetAsync(a.flag, 0, (size_t)ns * N * sizeof(int), h->stream));
+      hipLaunchKernelGGL(ksort[wi], dim3((unsigned)N * nchunk, ns), dim3(wt), lds, h->stream, a);
+      hipLaunchKernelGGL(k_coa_search<256>, dim3((unsigned)((m + 255) / 256), N, ns), dim3(256), 0, h->stream, a);
+    }
+    if (form) hipLaunchKernelGGL(k_coa_rsum<2>, dim3(ntp, ns), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_coa_rsum<4>, dim3(ntp, ns), dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL(k_coa_tail<CO_NSTAT>, dim3((unsigned)(((size_t)ns * NP + 63) / 64)), dim3(64), 0, h->stream, a, ns);
+    HIPCHK(hipGetLastError());
+  }
+  const size_t nser = (size_t)CO_NSTAT * S * NP;
+  std::vector<double> hs(nser);
+  HIPCHK(hipMemcpyAsync(hs.data(), a.ser, nser * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (series) std::memcpy(series, hs.data(), nser * sizeof(double));
+  std::memset(info, 0, sizeof *info);
+  coactivity_reduce(hs.data(), S, NP, ci, pair, info->n_credible, &info->max_cosine_at, &info->max_cosine);
+  info->n_used = S; info->n_included = m; info->n_left_out = G - m; info->n_pairs = NP; info->n_blocks = nb; info->min_load = min_load;
+  info->credible_interval = ci;
   return 0;
 }
 
@@ -1282,6 +1353,15 @@ int bnmf_regress(bnmf_handle* h, int last_n, const int32_t* used, const double* 
 int bnmf_regress_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const double* design, int Q, const int32_t* include,
                     double credible_interval, double* coef, double* fit, double* coef_series, double* r2_series, bnmf_regress_info* info) {
   return regress_impl(h, "bnmf_regress_at", {true, end_iter, n_samples}, used, design, Q, include, credible_interval, coef, fit, coef_series, r2_series, info);
+}
+
+int bnmf_coactivity(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, double min_load, double credible_interval, double* pair,
+                    double* series, bnmf_coactivity_info* info) {
+  return coactivity_impl(h, "bnmf_coactivity", {false, 0, last_n}, used, include, min_load, credible_interval, pair, series, info);
+}
+int bnmf_coactivity_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, double min_load, double credible_interval,
+                       double* pair, double* series, bnmf_coactivity_info* info) {
+  return coactivity_impl(h, "bnmf_coactivity_at", {true, end_iter, n_samples}, used, include, min_load, credible_interval, pair, series, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

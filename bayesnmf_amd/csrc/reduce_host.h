@@ -1,0 +1,86 @@
+// bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
+// the mean / variance / type-7 rows of a series, the dealing of independent series to threads, and bnmf_coactivity's reduction
+// (DESIGN.md 21).  No device and no handle: posterior.h includes it, and a stand-alone host program can (tools/coactivity_reduce_check.cpp,
+// built with -fsanitize=address,undefined by tests/test_coactivity_host.py).  Compile with -ffp-contract=off, as the library is.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <thread>
+#include <vector>
+#include "bnmf.h"
+
+// the canonical W = 64 sum of v[0], v[stride], ..., v[(m - 1) stride]: accumulator l adds elements l, l + 64, ... from +0.0, then wave_tree64's halving tree
+static double con_canon64(const double* v, size_t m, size_t stride) {
+  double acc[64];
+  for (int l = 0; l < 64; ++l) acc[l] = 0.0;
+  for (size_t i = 0; i < m; ++i) acc[i & 63] = acc[i & 63] + v[i * stride];
+  for (int hh = 32; hh >= 1; hh >>= 1) for (int l = 0; l < hh; ++l) acc[l] = acc[l] + acc[l + hh];
+  return acc[0];
+}
+// mean, variance (S - 1 form) and the two type-7 quantiles of x[0 .. S) into row[0], row[stride], row[2 stride], row[3 stride]; tmp: S doubles.
+// The quantiles are quantile7's expression on one sort (a NaN sorts last, as numpy's does); ci <= 0: NaN.
+static void con_rows(const double* x, int S, double ci, double* tmp, double* row, size_t stride) {
+  const double mean = con_canon64(x, S, 1) / (double)S;
+  for (int s = 0; s < S; ++s) { const double d = x[s] - mean; tmp[s] = d * d; }
+  row[0] = mean; row[stride] = con_canon64(tmp, S, 1) / (double)(S - 1);
+  if (!(ci > 0.0)) { row[2 * stride] = row[3 * stride] = std::nan(""); return; }
+  std::copy(x, x + S, tmp);
+  std::sort(tmp, tmp + S, [](double a, double b) { return a < b || (std::isnan(b) && !std::isnan(a)); });
+  auto q = [&](double prob) {
+    const double hq = (double)(S - 1) * prob;
+    const size_t j = (size_t)std::floor(hq);
+    const double g = hq - (double)j, a = tmp[j], b = tmp[std::min(j + 1, (size_t)S - 1)];
+    return a == b ? a : (1.0 - g) * a + g * b;             // k_map_quant's map_interp
+  };
+  row[2 * stride] = q((1.0 - ci) / 2.0); row[3 * stride] = q((1.0 + ci) / 2.0);
+}
+// work(lo, hi) over [0, nwork) dealt to up to 16 threads (zplan.h's way), at least 16 items each; the caller's items are independent
+template <class Work> static void deal_threads(long nwork, Work work) {
+  const long nthr = std::max<long>(1, std::min<long>({(long)std::thread::hardware_concurrency(), 16L, nwork / 16}));
+  std::vector<std::thread> pool;
+  for (long t = 1; t < nthr; ++t) pool.emplace_back(work, nwork * t / nthr, nwork * (t + 1) / nthr);
+  work(0, nwork / nthr);
+  for (auto& th : pool) th.join();
+}
+
+// ---- bnmf_coactivity's reduction over the samples ----
+// ser [4][S][NP] -> pair [4][7][NP] (may be null): per (q, p) over the S' samples whose value is not NaN the rows of con_rows, p_greater,
+// p_less and S'; n_credible[q] for q < 3 and the pair of the largest mean cosine are taken from the finished rows, so the result does not
+// depend on the threads.
+static void coactivity_reduce(const double* ser, int S, long NP, double ci, double* pair, int64_t* n_credible, int64_t* max_at, double* max_cosine) {
+  const long nwork = (long)BNMF_COA_NSTAT * NP;
+  std::vector<double> rows((size_t)nwork * BNMF_COA_NPROW);
+  auto work = [&](long lo, long hi) {
+    std::vector<double> x(S), tmp(S);
+    for (long i = lo; i < hi; ++i) {
+      const long q = i / NP, p = i % NP;
+      const double* v = ser + (size_t)q * S * NP + p;
+      double* row = rows.data() + (size_t)i * BNMF_COA_NPROW;
+      int nv = 0, gt = 0, lt = 0;
+      for (int s = 0; s < S; ++s) {
+        const double d = v[(size_t)s * NP];
+        if (std::isnan(d)) continue;
+        x[nv++] = d; gt += d > 0.0 ? 1 : 0; lt += d < 0.0 ? 1 : 0;
+      }
+      for (int k = 0; k < 6; ++k) row[k] = std::nan("");
+      row[6] = (double)nv;
+      if (!nv) continue;
+      con_rows(x.data(), nv, ci, tmp.data(), row, 1);
+      if (nv < 2) row[1] = std::nan("");
+      row[4] = (double)gt / (double)nv; row[5] = (double)lt / (double)nv;
+    }
+  };
+  deal_threads(nwork, work);
+  *max_at = -1; *max_cosine = std::nan("");
+  for (long q = 0; q < BNMF_COA_NSTAT; ++q) {
+    if (q < 3) n_credible[q] = 0;
+    for (long p = 0; p < NP; ++p) {
+      const double* row = rows.data() + (size_t)(q * NP + p) * BNMF_COA_NPROW;
+      if (q < 3 && (row[2] > 0.0 || row[3] < 0.0)) n_credible[q]++;
+      if (q == 3 && !std::isnan(row[0]) && (*max_at < 0 || row[0] > *max_cosine)) { *max_cosine = row[0]; *max_at = p; }
+      if (pair) for (int k = 0; k < BNMF_COA_NPROW; ++k) pair[((size_t)q * BNMF_COA_NPROW + k) * NP + p] = row[k];
+    }
+  }
+}

@@ -110,6 +110,12 @@ class BnmfRegressInfo(C.Structure):
                 ("min_pivot_at", C.c_int32), ("n_credible", (C.c_int64 * 16) * 3), ("credible_interval", C.c_double), ("min_pivot_ratio", C.c_double)]
 
 
+class BnmfCoactivityInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32), ("n_pairs", C.c_int32), ("n_blocks", C.c_int32),
+                ("_pad", C.c_int32), ("n_credible", C.c_int64 * 3), ("max_cosine_at", C.c_int64), ("max_cosine", C.c_double),
+                ("min_load", C.c_double), ("credible_interval", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -127,6 +133,8 @@ REG_STATS = ["load", "share", "sqrt_load"]
 REG_COEF_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less"]
 REG_FIT_ROWS = ["r2_mean", "r2_lower", "r2_upper", "r2_samples", "sigma2_mean"]
 REG_MAX_Q = 16
+COA_STATS = ["pearson", "spearman", "copresence", "cosine"]
+COA_PAIR_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less", "n_valid"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -144,7 +152,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_save_state", "bnmf_load_state", "bnmf_state_info", "bnmf_set_fixed", "bnmf_get_fixed",
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
-               "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at"]
+               "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
+               "bnmf_coactivity", "bnmf_coactivity_at"]
 
 
 def lib():
@@ -210,6 +219,8 @@ def lib():
         L.bnmf_contrast_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, dp, ip, C.POINTER(BnmfContrastInfo)]
         L.bnmf_regress.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfRegressInfo)]
         L.bnmf_regress_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfRegressInfo)]
+        L.bnmf_coactivity.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, C.POINTER(BnmfCoactivityInfo)]
+        L.bnmf_coactivity_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, C.POINTER(BnmfCoactivityInfo)]
         lp = C.POINTER(C.c_int64)
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
@@ -686,6 +697,38 @@ class Engine:
         if series:
             out.update(coef_series=cser.reshape((3, S, Q, N)).transpose(0, 1, 3, 2), r2_series=rser)
         return out
+
+    def coactivity(self, last_n, include=None, used=None, end_iter=None, min_load=1.0, credible_interval=0.95, series=False):
+        """Co-activity of the signatures over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_coactivity / bnmf_coactivity_at), on the device.
+        include (length G of 0 / 1, None = all): the tumours that enter.  Per used sample and pair of factors a < b the Pearson and the
+        Spearman (midrank) correlation of their loads across the included tumours, the phi coefficient of their presence (load >=
+        min_load) and the cosine of their two columns of P are one draw each from the posterior of that statistic.  Returns the info
+        fields (n_credible a list for the first three statistics), pairs (the NP pairs (a, b), a ascending, then b) and pair (4 x 7 x
+        NP: per statistic of COA_STATS the rows COA_PAIR_ROWS over the samples whose value is not NaN); with series also series (4 x S
+        x NP), every used sample's values.  credible_interval None or <= 0: no interval, lower / upper are NaN."""
+        N, G = self.N, self.G
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"coactivity: include has shape {inc.shape}, G = {G} flags are needed")
+        u, S = self._used("coactivity", used, last_n)
+        NP = N * (N - 1) // 2
+        pr = np.empty((4, 7, NP))
+        ser = np.empty((4, S, NP)) if series else None
+        ci = 0.0 if credible_interval is None else float(credible_interval)
+        info = BnmfCoactivityInfo()
+        self._range_call("coactivity", last_n, end_iter, u, None if inc is None else inc.ctypes.data_as(_IP), float(min_load), ci, _dp(pr), _dp(ser),
+                         C.byref(info))
+        out = self._info(info)
+        out["n_credible"] = [int(v) for v in info.n_credible]
+        out.update(pair=pr, pairs=[(a, b) for a in range(N) for b in range(a + 1, N)])
+        if series:
+            out["series"] = ser
+        return out
+
+    def coactivity_at(self, end_iter, n_samples, **kw):
+        """coactivity over the n_samples iterations that end at end_iter (bnmf_coactivity_at)."""
+        return self.coactivity(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

@@ -863,8 +863,53 @@ class bayesNMF_sampler:
                  f"{', '.join(f'{nm} {int(c)}' for nm, c in zip(names, r['n_credible'][0]))}", verbosity=1)
         return out
 
+    def get_coactivity(self, include=None, min_load=1.0, credible_interval=0.95, series=False, end_iter=None, n_samples=None, idx="MAP_idx"):
+        """Do two signatures act in the same tumours or exclude each other, and is a signature split into two factors (a high cosine of
+        two columns of P whose exposures are negatively correlated)?  On the device (bnmf_coactivity_at; not in the reference): over
+        iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as get_contrast), every sample
+        gives per pair of signatures the Pearson and the Spearman (midrank) correlation of their loads (the renormalised exposures of
+        get_MAP) across the included tumours, the phi coefficient of their presence (load >= min_load) and the cosine of their two
+        columns of P.  include (G flags; None = all): a tumour with a 0, None or NaN is left out, as get_regression leaves out a tumour
+        with a missing covariate.
+        Returns dict(per statistic "pearson", "spearman", "copresence", "cosine" a dict(mean, lower, upper, p_greater, n_valid: N x N
+        symmetric matrices with a NaN diagonal, over the samples whose value is not NaN; quantile type 7 at credible_interval); pairs
+        (the NP pairs (a, b)), pair (4 x 7 x NP: every row of the call), include, n_used, n_included, n_left_out, n_pairs, n_blocks,
+        n_credible (per statistic but the cosine: the pairs whose interval excludes 0), max_cosine, max_cosine_at, min_load,
+        credible_interval); with series also series (4 x S x NP).  No multiple-testing adjustment."""
+        if not hasattr(self._chain, "coactivity"):
+            raise ValueError("get_coactivity needs an engine that correlates over its recorded samples (coactivity); this engine_factory's cannot")
+        G, N = self.dims["G"], self.dims["N"]
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.coactivity(n, include=inc, used=used, min_load=min_load, credible_interval=credible_interval, series=series, **kw)
+        out = dict(pairs=r["pairs"], pair=r["pair"], include=inc)
+        ia, ib = [a for a, _ in r["pairs"]], [b for _, b in r["pairs"]]
+        for q, stat in enumerate(("pearson", "spearman", "copresence", "cosine")):
+            out[stat] = {}
+            for row, name in ((0, "mean"), (2, "lower"), (3, "upper"), (4, "p_greater"), (6, "n_valid")):
+                mat = np.full((N, N), np.nan)
+                mat[ia, ib] = mat[ib, ia] = r["pair"][q, row]
+                out[stat][name] = mat
+        out.update({k: r[k] for k in ("n_used", "n_included", "n_left_out", "n_pairs", "n_blocks", "n_credible", "max_cosine", "max_cosine_at",
+                                      "min_load", "credible_interval")})
+        if series:
+            out["series"] = r["series"]
+        at = r["max_cosine_at"]
+        self.log(f"Co-activity: {r['n_included']} tumours included, {r['n_left_out']} left out; {r['n_pairs']} pairs, n_credible pearson "
+                 f"{r['n_credible'][0]}, spearman {r['n_credible'][1]}, copresence {r['n_credible'][2]}; largest mean cosine "
+                 f"{r['max_cosine']:.3g}" + (f" (pair {r['pairs'][at]})" if at >= 0 else ""), verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

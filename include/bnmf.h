@@ -474,6 +474,49 @@ int bnmf_regress(bnmf_handle*, int last_n, const int32_t* used, const double* de
 int bnmf_regress_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const double* design, int Q, const int32_t* include,
                     double credible_interval, double* coef, double* fit, double* coef_series, double* r2_series, bnmf_regress_info* info);
 
+/* Co-activity of signatures over a recorded range, on the device: do two signatures act in the same tumours or exclude each
+ * other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are negatively correlated)?  include
+ * [G] holds 0 / 1 (NULL = all): the m included tumours g_0 < g_1 < ..., the member list of bnmf_regress.  NP = N (N - 1) / 2 pairs (a, b),
+ * a < b, numbered with a ascending, then b ascending (bnmf_contrast's numbering of its pairs of groups).  For every recorded sample flagged
+ * in used[] (oldest first; NULL = all), s = 0 .. S-1, with x_s[n,g] as for bnmf_contrast and canonB the blocked canonical sum of
+ * bnmf_regress over the members, four statistics per pair:
+ *   v0 Pearson:   mu_n = canonB(x[n,g_i]) / m;  d_n,i = x[n,g_i] - mu_n;  S_ab = canonB(d_a,i d_b,i);
+ *                 v0 = S_aa S_bb > 0 ? S_ab / sqrt(S_aa S_bb) : NaN.
+ *   v1 Spearman:  c_n,i = 2 #(x_j < x_i) + #(x_j == x_i) - m  (twice the midrank less m + 1; values compared as doubles, -0.0 == +0.0);
+ *                 T_ab = sum_i c_a,i c_b,i in int64;  v1 = T_aa > 0 && T_bb > 0 ? (double)T_ab / sqrt((double)T_aa (double)T_bb) : NaN;
+ *                 a factor with a load that is not finite among its included tumours has v1 = NaN in that sample.
+ *   v2 co-presence: with b_n,i = (x[n,g_i] >= min_load) and the 2 x 2 counts n11, n10, n01, n00 the phi coefficient
+ *                 ((double)n11 n00 - (double)n10 n01) / sqrt(((double)n1. n0.) ((double)n.1 n.0)), NaN when a margin is 0.
+ *   v3 cosine:    of the raw columns P_s[, a] and P_s[, b]: dot, nn_a, nn_b summed over k ascending from +0.0, dot / sqrt(nn_a nn_b); NaN
+ *                 when A_s excludes a or b.
+ * pair [BNMF_COA_NSTAT][BNMF_COA_NPROW][NP]: per statistic and pair over the S' samples whose value is not NaN the mean, the variance
+ *   (S' - 1 form, NaN with S' < 2), the type-7 quantiles at (1 -+ credible_interval) / 2, p_greater = #(v > 0) / S', p_less = #(v < 0) / S'
+ *   and n_valid = S'; with S' = 0 the first six rows are NaN.   series [BNMF_COA_NSTAT][S][NP]: every v, NaN included.
+ * info: n_credible[q] (q < 3) = the pairs whose interval excludes 0 (lower > 0 or upper < 0; unadjusted for the number of pairs);
+ *   max_cosine and max_cosine_at = the largest mean cosine and its pair (the first wins a tie; NaN and -1 without one);
+ *   n_blocks = ceil(m / BNMF_REG_BLOCK).
+ * credible_interval <= 0 means no interval: lower / upper are NaN and n_credible is 0.  pair and series may each be NULL.  Only + - * /,
+ * sqrt, comparisons and whole numbers in a fixed order: the bits depend on the recorded samples, used, include, min_load and
+ * credible_interval alone.  Works for every likelihood and prior; read-only for the chain; no random number is drawn.
+ * bnmf_coactivity_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as for bnmf_waic_at;
+ * bnmf_coactivity(h, n, ...) is bnmf_coactivity_at(h, iter, n, ...).  Refused before any device work: null info, a used[] or include[]
+ * value other than 0 / 1 (the index named), a min_load that is NaN, infinite or negative, a credible_interval that is NaN or >= 1 with
+ * BNMF_EINVAL; N < 2, fewer than 2 used samples, m < 3 or m > BNMF_COA_MAX_M (4 m^3 stays inside int64) with BNMF_ESIZE; window = 0, a
+ * poisoned handle or nothing recorded with BNMF_ESTATE. */
+#define BNMF_COA_NSTAT 4         /* 0 pearson, 1 spearman, 2 co-presence (phi), 3 cosine of the columns of P */
+#define BNMF_COA_NPROW 7         /* pair rows: mean, variance, lower, upper, p_greater, p_less, n_valid */
+#define BNMF_COA_MAX_M 1000000
+typedef struct { int32_t n_used, n_included, n_left_out, n_pairs, n_blocks, _pad;
+                 int64_t n_credible[3];      /* q0..q2: pairs whose interval excludes 0 (unadjusted) */
+                 int64_t max_cosine_at;      /* pair with the largest mean cosine; first wins a tie; -1 if none */
+                 double max_cosine, min_load, credible_interval; } bnmf_coactivity_info;
+int bnmf_coactivity(bnmf_handle*, int last_n, const int32_t* used, const int32_t* include /* [G] 0 / 1, NULL = all */,
+                    double min_load, double credible_interval,
+                    double* pair   /* [BNMF_COA_NSTAT][BNMF_COA_NPROW][NP]; may be NULL */,
+                    double* series /* [BNMF_COA_NSTAT][S][NP]; may be NULL */, bnmf_coactivity_info* info);
+int bnmf_coactivity_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, double min_load,
+                       double credible_interval, double* pair, double* series, bnmf_coactivity_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

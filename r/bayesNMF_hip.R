@@ -346,6 +346,57 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       paste(sprintf("%s %g", names, r$n_credible[, 1]), collapse = ", ")))
       out
     },
+    # Co-activity of the signatures, on the device (bnmf_coactivity_at; not in the reference): do two signatures act in the same tumours
+    # or exclude each other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are
+    # negatively correlated)?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every
+    # sample gives per pair of signatures the Pearson and the Spearman (midrank) correlation of their loads across the included tumours,
+    # the phi coefficient of their presence (load >= min_load) and the cosine of their two columns of P.  include: a logical of G flags
+    # (NULL = all); a tumour with FALSE or NA is left out.  list(pearson, spearman, copresence, cosine (each a list of N x N symmetric
+    # matrices with an NA diagonal: mean, lower, upper, p_greater, n_valid, over the samples whose value is not NaN; quantile type 7),
+    # pairs (NP x 2, 1-based), pair (NP x 7 x 4: every row of the call), include, n_used, n_included, n_left_out, n_pairs, n_blocks,
+    # n_credible (pearson, spearman, copresence: the pairs whose interval excludes 0), max_cosine, max_cosine_at (1-based; NA if none),
+    # min_load, credible_interval), with series also series (NP x S x 4).  No multiple-testing adjustment.
+    get_coactivity = function(include = NULL, min_load = 1, credible_interval = 0.95, series = FALSE, end_iter = self$state$iter,
+                              n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      r <- .Call("C_bnmf_coactivity", self$handle, as.integer(end_iter), as.integer(n_samples), used, include, as.double(min_load),
+                 as.double(credible_interval), as.logical(series), c(K, G, N))
+      pairs <- t(utils::combn(N, 2))
+      stat <- function(q) {
+        rows <- c(mean = 1, lower = 3, upper = 4, p_greater = 5, n_valid = 7)
+        o <- list()
+        for (nm in names(rows)) {
+          m <- matrix(NA_real_, N, N)
+          m[pairs] <- r$pair[, 7 * q + rows[[nm]]]; m[pairs[, 2:1, drop = FALSE]] <- r$pair[, 7 * q + rows[[nm]]]
+          o[[nm]] <- m
+        }
+        o
+      }
+      out <- list(pearson = stat(0), spearman = stat(1), copresence = stat(2), cosine = stat(3), pairs = pairs,
+                  pair = array(r$pair, c(nrow(pairs), 7, 4)), include = include, n_used = r$n_used, n_included = r$n_included,
+                  n_left_out = r$n_left_out, n_pairs = r$n_pairs, n_blocks = r$n_blocks,
+                  n_credible = stats::setNames(r$n_credible, c("pearson", "spearman", "copresence")), max_cosine = r$max_cosine,
+                  max_cosine_at = if (r$max_cosine_at < 0) NA_integer_ else r$max_cosine_at + 1L, min_load = r$min_load,
+                  credible_interval = r$credible_interval)
+      if (series) out$series <- array(r$series, c(nrow(pairs), r$n_used, 4))
+      message(sprintf("Co-activity: %d tumours included, %d left out; %d pairs, n_credible pearson %g, spearman %g, copresence %g; largest mean cosine %.3g",
+                      r$n_included, r$n_left_out, r$n_pairs, r$n_credible[1], r$n_credible[2], r$n_credible[3], r$max_cosine))
+      out
+    },
     # Exposures of new tumours under the recorded signatures, on the device (bnmf_project_at; not in the reference): new_data is a
     # K x J matrix of counts (or other non-negative values) of tumours the chain has not seen.  Over iterations end_iter - n_samples + 1
     # ... end_iter (defaults as get_WAIC), restricted to idx, every column is refitted to every sample's renormalised signatures by

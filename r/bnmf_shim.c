@@ -626,6 +626,66 @@ SEXP C_bnmf_regress_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP 
   UNPROTECT(1);
   return out;
 }
+/* Co-activity of signatures over recorded samples on the device (bnmf_coactivity / bnmf_coactivity_at): C_bnmf_coactivity(ptr, end_iter
+ * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or
+ * NULL = all), min_load, credible_interval (<= 0: no interval), want_series (logical), dims c(K,G,N)) -> list(n_used, n_included,
+ * n_left_out, n_pairs, n_blocks, n_credible (3: pearson, spearman, co-presence), max_cosine_at (0-based pair, -1 = none), max_cosine,
+ * min_load, credible_interval, pair (NP x 28: column 7 q + i = row i — mean, variance, lower, upper, p_greater, p_less, n_valid — of
+ * statistic q; the pairs a < b numbered with a ascending, then b), series (NP x 4 S: column S q + s; or NULL)) over iterations
+ * end_iter - n_samples + 1 ... end_iter.  C_bnmf_coactivity_at: the same with end_iter required */
+/* the result list with pair and (if wanted) series allocated, the flags of used and include; returned unprotected */
+static SEXP coa_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP want_series, SEXP dims, int32_t** u, int32_t** inc) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  const int G = d[1], N = d[2], NP = N * (N - 1) / 2;
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  *u = lgl_flags(used, n);
+  *inc = lgl_flags(include, G);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_included", "n_left_out", "n_pairs", "n_blocks", "n_credible", "max_cosine_at", "max_cosine", "min_load",
+                              "credible_interval", "pair", "series"};
+  SEXP out = PROTECT(named_list(12, nms));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, NP, BNMF_COA_NSTAT * BNMF_COA_NPROW));
+  if (LOGICAL(want_series)[0] == TRUE) SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, NP, BNMF_COA_NSTAT * S));
+  UNPROTECT(1);
+  return out;
+}
+static void coa_finish(SEXP out, const bnmf_coactivity_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_included));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarInteger(info->n_left_out)); SET_VECTOR_ELT(out, 3, Rf_ScalarInteger(info->n_pairs));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarInteger(info->n_blocks));
+  SEXP nc = PROTECT(Rf_allocVector(REALSXP, 3));
+  for (int q = 0; q < 3; ++q) REAL(nc)[q] = (double)info->n_credible[q];
+  SET_VECTOR_ELT(out, 5, nc);
+  UNPROTECT(1);
+  SET_VECTOR_ELT(out, 6, Rf_ScalarInteger((int)info->max_cosine_at)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal(info->max_cosine));
+  SET_VECTOR_ELT(out, 8, Rf_ScalarReal(info->min_load)); SET_VECTOR_ELT(out, 9, Rf_ScalarReal(info->credible_interval));
+}
+SEXP C_bnmf_coactivity(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP min_load, SEXP ci, SEXP want_series, SEXP dims) {
+  int32_t *u = NULL, *inc = NULL;
+  SEXP out = PROTECT(coa_alloc(n_samples, used, include, want_series, dims, &u, &inc));
+  bnmf_coactivity_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_coactivity(get_handle(ptr), INTEGER(n_samples)[0], u, inc, REAL(min_load)[0], REAL(ci)[0], map_buf(out, 10), map_buf(out, 11), &info));
+  else
+    chk(bnmf_coactivity_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, inc, REAL(min_load)[0], REAL(ci)[0], map_buf(out, 10),
+                           map_buf(out, 11), &info));
+  coa_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_coactivity_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP min_load, SEXP ci, SEXP want_series, SEXP dims) {
+  int32_t *u = NULL, *inc = NULL;
+  SEXP out = PROTECT(coa_alloc(n_samples, used, include, want_series, dims, &u, &inc));
+  bnmf_coactivity_info info;
+  chk(bnmf_coactivity_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, inc, REAL(min_load)[0], REAL(ci)[0], map_buf(out, 10),
+                         map_buf(out, 11), &info));
+  coa_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Exposures of new tumours under the recorded signatures on the device (bnmf_project / bnmf_project_at): C_bnmf_project(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), X (K x J real matrix, not
  * negative), n_steps, min_load, want_exposures (logical), dims c(K,G,N)) -> list(n_used, n_steps, n_present, min_load, total,
@@ -913,6 +973,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_relabel", (DL_FUNC)&C_bnmf_relabel, 8}, {"C_bnmf_relabel_at", (DL_FUNC)&C_bnmf_relabel_at, 8},
   {"C_bnmf_contrast", (DL_FUNC)&C_bnmf_contrast, 9}, {"C_bnmf_contrast_at", (DL_FUNC)&C_bnmf_contrast_at, 9},
   {"C_bnmf_regress", (DL_FUNC)&C_bnmf_regress, 9}, {"C_bnmf_regress_at", (DL_FUNC)&C_bnmf_regress_at, 9},
+  {"C_bnmf_coactivity", (DL_FUNC)&C_bnmf_coactivity, 9}, {"C_bnmf_coactivity_at", (DL_FUNC)&C_bnmf_coactivity_at, 9},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
