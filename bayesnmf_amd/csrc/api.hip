@@ -41,6 +41,7 @@
 #include "contrast.h"
 #include "regress.h"
 #include "coactivity.h"
+#include "stability.h"
 
 using namespace bnmf;
 

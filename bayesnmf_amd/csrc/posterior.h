@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h and coactivity.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h and stability.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1265,6 +1265,108 @@ static int coactivity_impl(bnmf_handle* h, const char* fn, Range r, const int32_
   return 0;
 }
 
+// Silhouette stability of the recorded signatures over the samples of r that used[] flags (stability.h): k_stab_norm leaves
+// the squared norm of every ring point, from which the members and the packed order (cluster by cluster, member-list order) are made here;
+// k_stab_gather packs the columns, k_stab_pairs leaves the block partials of D, the blocks are added in order here and everything from D
+// on is stability_reduce's.
+static_assert(BNMF_REG_BLOCK == RG_BLOCK, "regress.h and bnmf.h disagree");
+static int stability_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* labels, const double* extra_P,
+                          const int32_t* extra_label, int X, double* point, double* factor, double* between, double* medoid, int64_t* medoid_at,
+                          bnmf_stability_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  const int S = (int)slots.size();
+  std::vector<int> rows;                                                     // the row of the range of used sample s
+  for (int s = 0; s < r.n; ++s) if (!used || used[s]) rows.push_back(s);
+  if (labels)
+    for (int s : rows) for (int n = 0; n < N; ++n) {
+      const int v = labels[(size_t)s * N + n];
+      if (v < -1 || v >= N) return fail(BNMF_EINVAL, "%s: labels[%d][%d] = %d is outside -1 .. %d (sample %d of the range, factor %d)", fn, s, n, v, N - 1, s, n);
+    }
+  if (X < 0) return fail(BNMF_EINVAL, "%s: X = %d extra columns", fn, X);
+  if (X > 0 && (!extra_P || !extra_label)) return fail(BNMF_EINVAL, "%s: X = %d extra columns but extra_P or extra_label is null", fn, X);
+  for (int x = 0; x < X; ++x) {
+    if (extra_label[x] < 0 || extra_label[x] >= N) return fail(BNMF_EINVAL, "%s: extra_label[%d] = %d is outside 0 .. %d", fn, x, (int)extra_label[x], N - 1);
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      const double v = extra_P[(size_t)K * x + k];
+      if (!std::isfinite(v)) return fail(BNMF_EINVAL, "%s: extra_P[%d, %d] = %g is not finite", fn, k, x, v);
+      any = any || v != 0.0;
+    }
+    if (!any) return fail(BNMF_EINVAL, "%s: extra column %d is all zero", fn, x);
+  }
+  if (N < 2) return fail(BNMF_ESIZE, "%s: N = %d factor%s, a silhouette needs at least 2 clusters", fn, N, N == 1 ? "" : "s");
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, a cluster of draws needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const long SN = (long)S * N, NPT = SN + X;
+  StabArgs a{};
+  a.ringP = h->arr[BNMF_P].ring; a.ringA = h->arr[BNMF_A].ring; a.lenP = (size_t)K * N; a.N = N; a.K = K; a.S = S;
+  int* dslots;
+  if (int rc = carve(h, [&](Carve& c) { a.ok = c.take<int>((size_t)SN); dslots = c.take<int>(S); })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  a.slots = dslots;
+  // (k_stab_norm and k_stab_gather use no template parameter: they are templates only for their place in the code object)
+  hipLaunchKernelGGL(k_stab_norm<BNMF_STAB_NPOINT>, dim3((unsigned)((SN + 63) / 64)), dim3(64), 0, h->stream, a);
+  HIPCHK(hipGetLastError());
+  std::vector<int> ok((size_t)SN);
+  HIPCHK(hipMemcpyAsync(ok.data(), a.ok, (size_t)SN * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the member lists: ring members by ascending index, then the extras by ascending x
+  std::vector<int32_t> off(N + 1, 0);
+  std::vector<int> lab((size_t)NPT, -1);
+  for (int s = 0; s < S; ++s) for (int n = 0; n < N; ++n) {
+    const int j = labels ? labels[(size_t)rows[s] * N + n] : n;
+    if (j != -1 && ok[(size_t)s * N + n]) { lab[(size_t)s * N + n] = j; ++off[j + 1]; }
+  }
+  for (int x = 0; x < X; ++x) { lab[(size_t)SN + x] = extra_label[x]; ++off[extra_label[x] + 1]; }
+  for (int j = 0; j < N; ++j) off[j + 1] += off[j];
+  const long M = off[N];
+  if (M < 2) return fail(BNMF_ESIZE, "%s: %ld member%s in all, a silhouette needs at least 2", fn, M, M == 1 ? "" : "s");
+  if (M > BNMF_STAB_MAX_POINTS) return fail(BNMF_ESIZE, "%s: %ld members, at most %d are taken", fn, M, BNMF_STAB_MAX_POINTS);
+  const int Mp = (int)((M + ST_ROWS - 1) / ST_ROWS) * ST_ROWS;
+  std::vector<int> src(Mp, -1), fill(off.begin(), off.end() - 1), ustart, uend, ucl;
+  std::vector<int64_t> pt((size_t)M);
+  for (long i = 0; i < NPT; ++i) if (lab[i] >= 0) { const int q = fill[lab[i]]++; src[q] = (int)i; pt[q] = i; }
+  for (int j = 0; j < N; ++j)
+    for (int q = off[j]; q < off[j + 1]; q += RG_BLOCK) { ustart.push_back(q); uend.push_back(std::min<int>(q + RG_BLOCK, off[j + 1])); ucl.push_back(j); }
+  const int U = (int)ustart.size();
+  double* dextra; int *dsrc, *dus, *due;
+  if (int rc = carve(h, [&](Carve& c) {
+        dslots = c.take<int>(S); dextra = c.take<double>((size_t)K * std::max(X, 1)); dsrc = c.take<int>(Mp); dus = c.take<int>(U); due = c.take<int>(U);
+        a.packed = c.take<double>((size_t)K * Mp); a.nn = c.take<double>(Mp); a.part = c.take<double>((size_t)M * U);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (X > 0) HIPCHK(hipMemcpyAsync(dextra, extra_P, (size_t)K * X * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dsrc, src.data(), (size_t)Mp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dus, ustart.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(due, uend.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  a.slots = dslots; a.extra = dextra; a.src = dsrc; a.ustart = dus; a.uend = due; a.ok = nullptr; a.M = (int)M; a.Mp = Mp; a.U = U;
+  hipLaunchKernelGGL(k_stab_gather<BNMF_STAB_NPOINT>, dim3((unsigned)((Mp + 63) / 64)), dim3(64), 0, h->stream, a);
+  const int per = ST_ROWS * ST_WAVES;
+  hipLaunchKernelGGL(k_stab_pairs<ST_ROWS>, dim3((unsigned)U, (unsigned)((M + per - 1) / per)), dim3(64 * ST_WAVES), 0, h->stream, a);
+  HIPCHK(hipGetLastError());
+  std::vector<double> part((size_t)M * U), D((size_t)M * N, 0.0);
+  HIPCHK(hipMemcpyAsync(part.data(), a.part, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (long q = 0; q < M; ++q) for (int u = 0; u < U; ++u) D[(size_t)q * N + ucl[u]] = D[(size_t)q * N + ucl[u]] + part[(size_t)q * U + u];   // the blocks in order from +0.0
+  std::memset(info, 0, sizeof *info);
+  std::vector<int64_t> mpos(N);
+  stability_reduce(D.data(), M, N, off.data(), pt.data(), NPT, point, factor, between, medoid_at, mpos.data(), info);
+  info->n_used = S; info->n_extra = X; info->n_left_out = (int32_t)(NPT - M);
+  if (medoid) {
+    std::vector<double> col(K);
+    for (int j = 0; j < N; ++j) {
+      if (mpos[j] < 0) { for (int k = 0; k < K; ++k) medoid[(size_t)K * j + k] = std::nan(""); continue; }
+      HIPCHK(hipMemcpy2D(col.data(), sizeof(double), a.packed + mpos[j], (size_t)Mp * sizeof(double), sizeof(double), (size_t)K, hipMemcpyDeviceToHost));
+      stability_medoid(col.data(), 1, K, medoid + (size_t)K * j);
+    }
+  }
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1362,6 +1464,16 @@ int bnmf_coactivity(bnmf_handle* h, int last_n, const int32_t* used, const int32
 int bnmf_coactivity_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, double min_load, double credible_interval,
                        double* pair, double* series, bnmf_coactivity_info* info) {
   return coactivity_impl(h, "bnmf_coactivity_at", {true, end_iter, n_samples}, used, include, min_load, credible_interval, pair, series, info);
+}
+
+int bnmf_stability(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* labels, const double* extra_P, const int32_t* extra_label, int X,
+                   double* point, double* factor, double* between, double* medoid, int64_t* medoid_at, bnmf_stability_info* info) {
+  return stability_impl(h, "bnmf_stability", {false, 0, last_n}, used, labels, extra_P, extra_label, X, point, factor, between, medoid, medoid_at, info);
+}
+int bnmf_stability_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* labels, const double* extra_P,
+                      const int32_t* extra_label, int X, double* point, double* factor, double* between, double* medoid, int64_t* medoid_at,
+                      bnmf_stability_info* info) {
+  return stability_impl(h, "bnmf_stability_at", {true, end_iter, n_samples}, used, labels, extra_P, extra_label, X, point, factor, between, medoid, medoid_at, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

@@ -1,7 +1,8 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
-// the mean / variance / type-7 rows of a series, the dealing of independent series to threads, and bnmf_coactivity's reduction
-// (DESIGN.md 21).  No device and no handle: posterior.h includes it, and a stand-alone host program can (tools/coactivity_reduce_check.cpp,
-// built with -fsanitize=address,undefined by tests/test_coactivity_host.py).  Compile with -ffp-contract=off, as the library is.
+// the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
+//  and bnmf_stability's finish.  No device and no handle: posterior.h includes it, and a stand-alone host
+// program can (tools/coactivity_reduce_check.cpp and tools/stability_reduce_check.cpp, built with -fsanitize=address,undefined by
+// tests/test_coactivity_host.py and tests/test_stability_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -49,7 +50,7 @@ template <class Work> static void deal_threads(long nwork, Work work) {
 // ser [4][S][NP] -> pair [4][7][NP] (may be null): per (q, p) over the S' samples whose value is not NaN the rows of con_rows, p_greater,
 // p_less and S'; n_credible[q] for q < 3 and the pair of the largest mean cosine are taken from the finished rows, so the result does not
 // depend on the threads.
-static void coactivity_reduce(const double* ser, int S, long NP, double ci, double* pair, int64_t* n_credible, int64_t* max_at, double* max_cosine) {
+[[maybe_unused]] static void coactivity_reduce(const double* ser, int S, long NP, double ci, double* pair, int64_t* n_credible, int64_t* max_at, double* max_cosine) {
   const long nwork = (long)BNMF_COA_NSTAT * NP;
   std::vector<double> rows((size_t)nwork * BNMF_COA_NPROW);
   auto work = [&](long lo, long hi) {
@@ -83,4 +84,101 @@ static void coactivity_reduce(const double* ser, int S, long NP, double ci, doub
       if (pair) for (int k = 0; k < BNMF_COA_NPROW; ++k) pair[((size_t)q * BNMF_COA_NPROW + k) * NP + p] = row[k];
     }
   }
+}
+
+// ---- bnmf_stability's finish: from the distance sums to every output ----
+// The M members are numbered in the packed order: cluster by cluster (off[j] .. off[j + 1] of cluster j, N clusters), each in member-list
+// order; pt[q] is the point index of member q among the NPT points.  D [M][N]: D[q][j] = canonB over the member list of j of d(q, .).
+// point [4][NPT], factor [6][N], between [N][N], med_at [N] (point index) may each be null; med_pos [N] (the member q of the medoid, -1:
+// an empty cluster) is always written.  Of info the fields n_points, n_clusters, n_negative, mean_silhouette, min_stability and
+// min_stability_at are set.
+[[maybe_unused]] static void stability_reduce(const double* D, long M, int N, const int32_t* off, const int64_t* pt, long NPT, double* point, double* factor,
+                             double* between, int64_t* med_at, int64_t* med_pos, bnmf_stability_info* info) {
+  const double nan = std::nan("");
+  std::vector<double> sil(M), aa(M), bb(M), tmp(M);
+  std::vector<int32_t> nearest(M);
+  int64_t nneg = 0;
+  for (int c = 0; c < N; ++c) {
+    const long mc = off[c + 1] - off[c];
+    for (long q = off[c]; q < off[c + 1]; ++q) {
+      const double* Dq = D + (size_t)q * N;
+      const double a = mc >= 2 ? Dq[c] / (double)(mc - 1) : 0.0;
+      double b = nan; int near = -1;
+      for (int j = 0; j < N; ++j) {
+        const long mj = off[j + 1] - off[j];
+        if (j == c || mj < 1) continue;
+        const double v = Dq[j] / (double)mj;
+        if (near < 0 || v < b) { b = v; near = j; }
+      }
+      double s;
+      if (mc < 2) s = 0.0;
+      else if (near < 0) s = nan;
+      else { const double mx = a > b ? a : b; s = mx > 0.0 ? (b - a) / mx : 0.0; }
+      sil[q] = s; aa[q] = a; bb[q] = b; nearest[q] = near;
+      nneg += s < 0.0 ? 1 : 0;
+    }
+  }
+  if (point) {
+    for (long i = 0; i < NPT; ++i) { point[i] = point[NPT + i] = point[2 * NPT + i] = nan; point[3 * NPT + i] = -1.0; }
+    for (long q = 0; q < M; ++q) { const long i = (long)pt[q]; point[i] = sil[q]; point[NPT + i] = aa[q]; point[2 * NPT + i] = bb[q]; point[3 * NPT + i] = (double)nearest[q]; }
+  }
+  std::vector<double> frow((size_t)BNMF_STAB_NFROW * N);
+  int nclus = 0;
+  for (int j = 0; j < N; ++j) {
+    const long o = off[j], mj = off[j + 1] - o;
+    double* f = frow.data() + j;
+    f[0] = (double)mj;
+    for (int k = 1; k < BNMF_STAB_NFROW; ++k) f[(size_t)k * N] = nan;
+    med_pos[j] = -1;
+    if (med_at) med_at[j] = -1;
+    if (mj < 1) continue;
+    ++nclus;
+    f[(size_t)1 * N] = con_canon64(sil.data() + o, mj, 1) / (double)mj;
+    f[(size_t)3 * N] = con_canon64(aa.data() + o, mj, 1) / (double)mj;
+    f[(size_t)4 * N] = con_canon64(bb.data() + o, mj, 1) / (double)mj;
+    double mn = sil[o]; long neg = 0, best = o; bool anynan = false;
+    for (long q = o; q < o + mj; ++q) {
+      anynan = anynan || std::isnan(sil[q]);
+      if (sil[q] < mn) mn = sil[q];
+      neg += sil[q] < 0.0 ? 1 : 0;
+      if (D[(size_t)q * N + j] < D[(size_t)best * N + j]) best = q;
+    }
+    f[(size_t)2 * N] = anynan ? nan : mn;
+    f[(size_t)5 * N] = (double)neg / (double)mj;
+    med_pos[j] = best;
+    if (med_at) med_at[j] = pt[best];
+  }
+  if (factor) std::memcpy(factor, frow.data(), frow.size() * sizeof(double));
+  if (between)
+    for (int a = 0; a < N; ++a)
+      for (int b = 0; b < N; ++b) {
+        const long oa = off[a], ma = off[a + 1] - oa, mb = off[b + 1] - off[b];
+        double v = nan;
+        if (ma >= 1 && mb >= 1) {
+          if (a == b) v = frow[(size_t)3 * N + a];
+          else {
+            for (long q = 0; q < ma; ++q) tmp[q] = D[(size_t)(oa + q) * N + b] / (double)mb;
+            v = con_canon64(tmp.data(), ma, 1) / (double)ma;
+          }
+        }
+        between[(size_t)a * N + b] = v;
+      }
+  // the mean over all members in index order
+  std::vector<long> at(NPT, -1);
+  for (long q = 0; q < M; ++q) at[pt[q]] = q;
+  long n = 0;
+  for (long i = 0; i < NPT; ++i) if (at[i] >= 0) tmp[n++] = sil[at[i]];
+  info->n_points = (int32_t)M; info->n_clusters = nclus; info->n_negative = nneg;
+  info->mean_silhouette = con_canon64(tmp.data(), n, 1) / (double)M;
+  info->min_stability = nan; info->min_stability_at = -1;
+  for (int j = 0; j < N; ++j) {
+    const double v = frow[(size_t)1 * N + j];
+    if (!std::isnan(v) && (info->min_stability_at < 0 || v < info->min_stability)) { info->min_stability = v; info->min_stability_at = j; }
+  }
+}
+// the consensus signature of a cluster: the medoid's column col[0], col[stride], ... divided by its sum over k ascending from +0.0
+[[maybe_unused]] static void stability_medoid(const double* col, size_t stride, int K, double* out) {
+  double sum = 0.0;
+  for (int k = 0; k < K; ++k) sum = sum + col[(size_t)k * stride];
+  for (int k = 0; k < K; ++k) out[k] = col[(size_t)k * stride] / sum;
 }

@@ -116,6 +116,11 @@ class BnmfCoactivityInfo(C.Structure):
                 ("min_load", C.c_double), ("credible_interval", C.c_double)]
 
 
+class BnmfStabilityInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_points", C.c_int32), ("n_extra", C.c_int32), ("n_left_out", C.c_int32), ("n_clusters", C.c_int32),
+                ("min_stability_at", C.c_int32), ("n_negative", C.c_int64), ("mean_silhouette", C.c_double), ("min_stability", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -135,6 +140,8 @@ REG_FIT_ROWS = ["r2_mean", "r2_lower", "r2_upper", "r2_samples", "sigma2_mean"]
 REG_MAX_Q = 16
 COA_STATS = ["pearson", "spearman", "copresence", "cosine"]
 COA_PAIR_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less", "n_valid"]
+STAB_POINT_ROWS = ["silhouette", "a", "b", "nearest"]
+STAB_FACTOR_ROWS = ["members", "stability", "min_silhouette", "mean_a", "mean_b", "share_negative"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -153,7 +160,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
                "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
-               "bnmf_coactivity", "bnmf_coactivity_at"]
+               "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at"]
 
 
 def lib():
@@ -222,6 +229,8 @@ def lib():
         L.bnmf_coactivity.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, C.POINTER(BnmfCoactivityInfo)]
         L.bnmf_coactivity_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp, dp, C.POINTER(BnmfCoactivityInfo)]
         lp = C.POINTER(C.c_int64)
+        L.bnmf_stability.argtypes = [C.c_void_p, C.c_int, ip, ip, dp, ip, C.c_int, dp, dp, dp, dp, lp, C.POINTER(BnmfStabilityInfo)]
+        L.bnmf_stability_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, dp, ip, C.c_int, dp, dp, dp, dp, lp, C.POINTER(BnmfStabilityInfo)]
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -729,6 +738,46 @@ class Engine:
     def coactivity_at(self, end_iter, n_samples, **kw):
         """coactivity over the n_samples iterations that end at end_iter (bnmf_coactivity_at)."""
         return self.coactivity(n_samples, end_iter=end_iter, **kw)
+
+    def stability(self, last_n, labels=None, used=None, end_iter=None, extra_P=None, extra_label=None):
+        """Silhouette stability of the recorded signatures over the samples flagged in used (length last_n, oldest first; None = all) of
+        the last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_stability / bnmf_stability_at), on the
+        device: every recorded column of P is a point, its cluster is labels[row of the sample][n] (last_n x N over the whole range, -1
+        = left out; None = the factor), the distance is the cosine distance, and extra_P (K x X) with extra_label (X values in 0 .. N-1)
+        adds further columns (other chains, a catalogue).  Returns the info fields, point (4 x (S N + X): STAB_POINT_ROWS; NaN, NaN, NaN,
+        -1 at a left-out position), factor (6 x N: STAB_FACTOR_ROWS), between (N x N mean distances between clusters), medoid (K x N:
+        the consensus signatures, columns summing to 1) and medoid_at (N point indices, -1 = empty cluster)."""
+        K, N = self.K, self.N
+        u, S = self._used("stability", used, last_n)
+        lb = None
+        if labels is not None:
+            lb = np.ascontiguousarray(labels, dtype=np.int32)
+            if lb.shape != (last_n, N):
+                raise BnmfError(-2, f"stability: labels is {lb.shape}, not {(last_n, N)}")
+        X, ex, el = 0, None, None
+        if extra_P is not None:
+            ex = np.asarray(extra_P, dtype=np.float64)
+            if ex.ndim != 2 or ex.shape[0] != K:
+                raise BnmfError(-2, f"stability: extra_P is {ex.shape}, K = {K} rows are needed")
+            X = ex.shape[1]
+            el = np.ascontiguousarray(extra_label if extra_label is not None else [], dtype=np.int32)
+            if el.shape != (X,):
+                raise BnmfError(-2, f"stability: extra_label has shape {el.shape} for {X} extra columns")
+            ex = np.ascontiguousarray(ex.ravel(order="F"))
+        NPT = S * N + X
+        point, factor, between, medoid = np.empty((4, NPT)), np.empty((6, N)), np.empty((N, N)), np.empty(K * N)
+        mat = np.empty(N, dtype=np.int64)
+        info = BnmfStabilityInfo()
+        self._range_call("stability", last_n, end_iter, u, None if lb is None else lb.ctypes.data_as(_IP), _dp(ex) if X else None,
+                         el.ctypes.data_as(_IP) if X else None, X, _dp(point), _dp(factor), _dp(between), _dp(medoid),
+                         mat.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(info))
+        out = self._info(info)
+        out.update(point=point, factor=factor, between=between, medoid=medoid.reshape((K, N), order="F"), medoid_at=mat)
+        return out
+
+    def stability_at(self, end_iter, n_samples, **kw):
+        """stability over the n_samples iterations that end at end_iter (bnmf_stability_at)."""
+        return self.stability(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

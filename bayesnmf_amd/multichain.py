@@ -199,6 +199,39 @@ class ChainSync:
         return np.concatenate(self.history[c]) if self.history[c] else np.zeros((0, NMETRIC))
 
 
+def pooled_stability(samplers, end_iter=None, n_samples=None, idx="MAP_idx"):
+    """The across-replicate stability that NMF-based extractors report, over the recorded ranges of several replicas on this host: the
+    first replica is aligned by bnmf_relabel, every replica (the first too) is then aligned to that aligned mean (as pivot_P),
+    and the other replicas' aligned samples go to the first handle's bnmf_stability as extra columns, the label of each being
+    the one it received.  A column of another replica enters as a ring point would: only where that sample's A includes its factor
+    and the column is finite and not all zero (a rank-learning replica's excluded factors stay out; an unmatched sample is left out
+    whole).  Host glue only.  Returns Engine.stability's dict of the first handle, with n_replicas."""
+    first = samplers[0]
+    n, used, _, kw = first._recorded_range(end_iter, n_samples, idx)
+    pivot = first._chain.relabel(n, used=used, **kw)["P_mean"]
+    perm = np.asarray(first._chain.relabel(n, used=used, pivot_P=pivot, **kw)["perm"], dtype=np.int32)
+    N = perm.shape[1]
+    labels = np.full((n, N), -1, dtype=np.int32)
+    labels[slice(None) if used is None else np.asarray(used) != 0] = perm
+    cols, labs = [], []
+    for s in samplers[1:]:
+        m, u, _, k = s._recorded_range(end_iter, n_samples, idx)
+        r = s._chain.relabel(m, used=u, pivot_P=pivot, aligned=True, **k)
+        back = s._chain.iter - k.get("end_iter", s._chain.iter) + m     # the range's oldest sample, counted back from the newest kept
+        A = np.stack([np.ravel(a) for a in s._chain.window("A", back)[:m]])[slice(None) if u is None else np.asarray(u) != 0]
+        for P, pm, inc in zip(r["aligned_P"], r["perm"], A):
+            if pm[0] < 0:                                               # (an unmatched sample is NaN: left out)
+                continue
+            own = P[:, pm]                                              # column n: factor n of the sample, which received label pm[n]
+            ok = (inc != 0) & np.isfinite(own).all(axis=0) & (own != 0).any(axis=0)
+            cols.append(own[:, ok])
+            labs.append(np.asarray(pm, dtype=np.int32)[ok])
+    ex = np.asfortranarray(np.concatenate(cols, axis=1)) if cols else None
+    out = first._chain.stability(n, labels=labels, used=used, extra_P=ex, extra_label=None if ex is None else np.concatenate(labs), **kw)
+    out["n_replicas"] = len(samplers)
+    return out
+
+
 def run_rank(data, rank, dist, device=None, tensor_device=None, **kw):
     """One chain on this rank (chain_id = dist rank).  Returns (sampler, sync): `sync.metrics(c)` holds every chain's
     metric rows (from iteration 2 on), `sync.converged` every chain's convergence flag, `sync.maps[c]` every chain's MAP at

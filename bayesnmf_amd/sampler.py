@@ -908,8 +908,40 @@ class bayesNMF_sampler:
                  f"{r['max_cosine']:.3g}" + (f" (pair {r['pairs'][at]})" if at >= 0 else ""), verbosity=1)
         return out
 
+    def get_stability(self, end_iter=None, n_samples=None, relabel=True, extra_P=None, extra_label=None, idx="MAP_idx"):
+        """Are the N signatures well-separated, reproducible objects?  On the device (bnmf_stability_at; not in the reference): over
+        iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as get_contrast), every recorded
+        column of P is a point, the distance is the cosine distance and the cluster of a point is its factor; the silhouette of each
+        point and the mean silhouette of each cluster (the "stability" of NMF-based extractors) follow.  With relabel the range is
+        first aligned by get_relabelling() and every point's cluster is the label it received; an unmatched sample is left out.
+        extra_P (K x X) with extra_label (X labels) adds further columns, e.g. the aligned samples of other chains.
+        Returns dict(stability, min_silhouette, members, mean_a, mean_b, share_negative (length N), silhouette, a, b, nearest (S x N
+        over the used samples; NaN / -1 where a point is left out), extra (4 x X: the same rows for the extra columns), between (N x
+        N), medoid (K x N consensus signatures), medoid_at, n_used, n_points, n_extra, n_left_out, n_clusters, n_negative,
+        mean_silhouette, min_stability, min_stability_at)."""
+        if not hasattr(self._chain, "stability"):
+            raise ValueError("get_stability needs an engine that takes distances over its recorded samples (stability); this engine_factory's cannot")
+        N = self.dims["N"]
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        labels = None
+        if relabel:
+            perm = np.asarray(self.get_relabelling(end_iter=end_iter, n_samples=n_samples, idx=idx)["perm"], dtype=np.int32)
+            labels = np.full((n, N), -1, dtype=np.int32)                 # perm has a row per used sample: scattered into the range's rows
+            labels[slice(None) if used is None else np.asarray(used) != 0] = perm
+        r = self._chain.stability(n, labels=labels, used=used, extra_P=extra_P, extra_label=extra_label, **kw)
+        S = r["n_used"]
+        out = {name: r["factor"][i] for i, name in enumerate(("members", "stability", "min_silhouette", "mean_a", "mean_b", "share_negative"))}
+        out.update({name: r["point"][i, :S * N].reshape(S, N) for i, name in enumerate(("silhouette", "a", "b", "nearest"))})
+        out.update(extra=r["point"][:, S * N:], labels=labels, between=r["between"], medoid=r["medoid"], medoid_at=r["medoid_at"])
+        out.update({k: r[k] for k in ("n_used", "n_points", "n_extra", "n_left_out", "n_clusters", "n_negative", "mean_silhouette", "min_stability",
+                                      "min_stability_at")})
+        self.log(f"Stability: {r['n_points']} points in {r['n_clusters']} clusters, {r['n_left_out']} left out; mean silhouette "
+                 f"{r['mean_silhouette']:.3g}, least stable signature {r['min_stability_at']} at {r['min_stability']:.3g}, "
+                 f"{r['n_negative']} points nearer to another cluster", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

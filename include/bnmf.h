@@ -517,6 +517,58 @@ int bnmf_coactivity(bnmf_handle*, int last_n, const int32_t* used, const int32_t
 int bnmf_coactivity_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, double min_load,
                        double credible_interval, double* pair, double* series, bnmf_coactivity_info* info);
 
+/* Silhouette stability of the recorded signatures, on the device: are the N signatures well-separated, reproducible objects,
+ * or do two factors keep sharing one signature, or does a signature dissolve between samples?  The points are the columns of P of every
+ * recorded sample flagged in used[] (oldest first; NULL = all), s = 0 .. S-1: ring point (s, n) has index s N + n and the label
+ * labels[row of s][n] (labels NULL: n), and extra column x (other chains, a catalogue) has index S N + x and the label extra_label[x].
+ * labels has one row per sample of the whole range, so with gaps in used[] it is not bnmf_relabel's perm (one row per used sample): a
+ * caller scatters those rows.  A ring point is a member when its label is not -1, A_s[n] != 0 and nn = sum_k P_s[k,n]^2 (k ascending from
+ * +0.0) is finite and > 0; any other ring position is left out (n_left_out).  An extra column is always a member.  The member list of
+ * cluster j: its ring members by ascending index, then its extras by ascending x; m_j its length.
+ *   dot(i, i') = sum_k p_i[k] p_i'[k], k ascending from +0.0, multiply and add rounded separately;
+ *   d(i, i') = 1 - dot / sqrt(nn_i nn_i')  (bitwise symmetric);
+ *   D[i][j] = canonB over the member list of j of d(i, i'), the self term entered as +0.0  (canonB: bnmf_regress's blocked canonical sum).
+ * Per member i of cluster c:  a = m_c >= 2 ? D[i][c] / (m_c - 1) : +0.0;  b = the smallest D[i][j] / m_j over j != c with m_j >= 1 (j
+ * ascending, the first wins a tie), nearest = that j;  the silhouette is +0.0 when m_c < 2, NaN when no other cluster has a member (b NaN,
+ * nearest -1), else with mx = max(a, b): mx > 0 ? (b - a) / mx : +0.0.
+ * point [BNMF_STAB_NPOINT][S N + X]: silhouette, a, b, nearest; a left-out position has NaN, NaN, NaN, -1.
+ * factor [BNMF_STAB_NFROW][N]: m_j; the canonical W = 64 sum of the members' silhouettes in list order / m_j (the stability; NaN if any is
+ *   NaN or m_j = 0); the smallest silhouette (NaN likewise); the same mean of a and of b; #(silhouette < 0) / m_j.
+ * between [N][N]: the canonical W = 64 sum over the members i of cluster a (list order) of D[i][b] / m_b, divided by m_a; on the diagonal
+ *   the mean of a_i (factor row 3); NaN where a or b is empty.
+ * medoid [K*N], medoid_at [N]: per cluster the member with the smallest D[i][j] (list order, the first wins a tie), its column divided by
+ *   its sum over k ascending: the consensus signature; NaN and -1 for an empty cluster.
+ * info: n_points = the members, n_clusters = #(m_j >= 1), n_negative = #(silhouette < 0), mean_silhouette = the canonical W = 64 sum of all
+ *   members' silhouettes in index order / n_points, min_stability and min_stability_at = the smallest non-NaN factor row 1 and its label
+ *   (the first wins a tie; NaN and -1 without one).
+ * Only + - * /, sqrt, comparisons and whole numbers in a fixed order: the bits depend on the recorded samples, used, labels and the extras
+ * alone; renumbering the labels permutes the outputs.  Works for every likelihood and prior (only P and A are read); read-only for the
+ * chain; no random number is drawn.  bnmf_stability_at: the n_samples iterations that end at end_iter; the range rule and BNMF_ESIZE as
+ * for bnmf_waic_at; bnmf_stability(h, n, ...) is bnmf_stability_at(h, iter, n, ...).  Refused before any device work: null info, a used[]
+ * value other than 0 / 1 (the index named), a label outside -1 .. N-1 (sample and factor named), X < 0, X > 0 with a null extra_P or
+ * extra_label, an extra label outside 0 .. N-1, an extra cell that is not finite (named) or an extra column that is all zero (named) with
+ * BNMF_EINVAL; N < 2 or fewer than 2 used samples with BNMF_ESIZE; window = 0, a poisoned handle or nothing recorded with BNMF_ESTATE.
+ * Refused after the pass that takes the norms of the ring points, which decides the members: fewer than 2 members in all or more than
+ * BNMF_STAB_MAX_POINTS with BNMF_ESIZE. */
+#define BNMF_STAB_NPOINT 4       /* point rows: silhouette, a (own cluster), b (nearest other), nearest (label as a double, -1: none) */
+#define BNMF_STAB_NFROW  6       /* factor rows: members, mean silhouette (the stability), min silhouette, mean a, mean b, share with silhouette < 0 */
+#define BNMF_STAB_MAX_POINTS 65536
+typedef struct { int32_t n_used, n_points, n_extra, n_left_out, n_clusters, min_stability_at /* label; -1 if none */;
+                 int64_t n_negative; double mean_silhouette, min_stability; } bnmf_stability_info;
+int bnmf_stability(bnmf_handle*, int last_n, const int32_t* used,
+                   const int32_t* labels   /* [n_samples][N] row-major over the whole range, rows of unused samples not read: the cluster of factor n of that sample, -1 = left out; NULL: n */,
+                   const double* extra_P   /* K x X column-major: further columns (other chains, a catalogue); may be NULL with X = 0 */,
+                   const int32_t* extra_label /* [X], 0 .. N-1 */, int X,
+                   double* point   /* [BNMF_STAB_NPOINT][S*N + X]; may be NULL */,
+                   double* factor  /* [BNMF_STAB_NFROW][N]; may be NULL */,
+                   double* between /* [N][N] row-major; may be NULL */,
+                   double* medoid  /* [K*N] column-major; may be NULL */,
+                   int64_t* medoid_at /* [N] point index, -1: empty cluster; may be NULL */,
+                   bnmf_stability_info* info);
+int bnmf_stability_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* labels, const double* extra_P,
+                      const int32_t* extra_label, int X, double* point, double* factor, double* between, double* medoid, int64_t* medoid_at,
+                      bnmf_stability_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

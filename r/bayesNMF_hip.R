@@ -397,6 +397,50 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       r$n_included, r$n_left_out, r$n_pairs, r$n_credible[1], r$n_credible[2], r$n_credible[3], r$max_cosine))
       out
     },
+    # Silhouette stability of the recorded signatures, on the device (bnmf_stability_at; not in the reference): over iterations
+    # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every recorded column of P is a point, the
+    # distance is the cosine distance and the cluster of a point is its factor - with relabel the label get_relabelling() gave it, an
+    # unmatched sample being left out.  extra_P (K x X) with extra_label (1-based) adds further columns.  list(stability, min_silhouette,
+    # members, mean_a, mean_b, share_negative (length N), silhouette, a, b, nearest (S x N; nearest 1-based, NA = none), between (N x
+    # N), medoid (K x N consensus signatures), medoid_at (1-based points, NA = empty), n_used, n_points, n_extra, n_left_out,
+    # n_clusters, n_negative, mean_silhouette, min_stability, min_stability_at (1-based; NA if none)).
+    get_stability = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                             relabel = TRUE, extra_P = NULL, extra_label = NULL, idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      labels <- NULL
+      if (relabel) {
+        perm <- self$get_relabelling(end_iter = end_iter, n_samples = n_samples, idx = if (is.null(idx)) NULL else idx)$perm
+        perm <- t(matrix(as.integer(perm), nrow = N))                 # get_relabelling's is N x S: here S x N, 1-based labels, NA = unmatched
+        labels <- matrix(-1L, n_samples, N)
+        labels[if (is.null(used)) seq_len(n_samples) else which(used), ] <- ifelse(is.na(perm), -1L, perm - 1L)
+      }
+      if (!is.null(extra_P)) {
+        extra_P <- matrix(as.double(extra_P), nrow = K)
+        extra_label <- as.integer(extra_label) - 1L
+      }
+      r <- .Call("C_bnmf_stability", self$handle, as.integer(end_iter), as.integer(n_samples), used, labels, extra_P, extra_label, c(K, G, N))
+      S <- r$n_used
+      ring <- function(j) matrix(r$point[seq_len(S * N), j], S, N, byrow = TRUE)
+      one <- function(v) ifelse(v < 0, NA_integer_, as.integer(v) + 1L)
+      out <- list(members = r$factor[, 1], stability = r$factor[, 2], min_silhouette = r$factor[, 3], mean_a = r$factor[, 4], mean_b = r$factor[, 5],
+                  share_negative = r$factor[, 6], silhouette = ring(1), a = ring(2), b = ring(3), nearest = matrix(one(ring(4)), S, N),
+                  between = t(r$between), medoid = r$medoid, medoid_at = one(r$medoid_at), n_used = r$n_used, n_points = r$n_points,
+                  n_extra = r$n_extra, n_left_out = r$n_left_out, n_clusters = r$n_clusters, n_negative = r$n_negative,
+                  mean_silhouette = r$mean_silhouette, min_stability = r$min_stability, min_stability_at = one(r$min_stability_at))
+      message(sprintf("Stability: %d points in %d clusters, %d left out; mean silhouette %.3g, least stable signature %s at %.3g", r$n_points,
+                      r$n_clusters, r$n_left_out, r$mean_silhouette, format(out$min_stability_at), r$min_stability))
+      out
+    },
     # Exposures of new tumours under the recorded signatures, on the device (bnmf_project_at; not in the reference): new_data is a
     # K x J matrix of counts (or other non-negative values) of tumours the chain has not seen.  Over iterations end_iter - n_samples + 1
     # ... end_iter (defaults as get_WAIC), restricted to idx, every column is refitted to every sample's renormalised signatures by

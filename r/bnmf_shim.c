@@ -686,6 +686,83 @@ SEXP C_bnmf_coactivity_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SE
   UNPROTECT(1);
   return out;
 }
+/* Silhouette stability of the recorded signatures on the device (bnmf_stability / bnmf_stability_at): C_bnmf_stability(ptr, end_iter
+ * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), labels (integer n_samples x N
+ * matrix of 0-based clusters, -1 / NA = left out; or NULL = the factor), extra_P (K x X real matrix, or NULL), extra_label (integer X,
+ * 0-based; or NULL), dims c(K,G,N)) -> list(n_used, n_points, n_extra, n_left_out, n_clusters, min_stability_at (0-based label, -1 =
+ * none), n_negative, mean_silhouette, min_stability, point ((S N + X) x 4: silhouette, a, b, nearest (0-based, -1 = none); row s N + n
+ * is factor n of used sample s, then the extras), factor (N x 6: members, stability, min silhouette, mean a, mean b, share negative),
+ * between (N x N, column a = the distances from cluster a), medoid (K x N), medoid_at (N 0-based points, -1 = empty)) over iterations
+ * end_iter - n_samples + 1 ... end_iter.  C_bnmf_stability_at: the same with end_iter required */
+/* the result list with its arrays allocated, the flags of used, the labels row-major and X; returned unprotected */
+static SEXP stab_alloc(SEXP n_samples, SEXP used, SEXP labels, SEXP extra_P, SEXP extra_label, SEXP dims, int32_t** u, int32_t** lab, int* X) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  const int K = d[0], N = d[2];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (labels != R_NilValue && XLENGTH(labels) != (R_xlen_t)n * N) Rf_error("bnmf: labels has %ld entries for %d samples of %d factors", (long)XLENGTH(labels), n, N);
+  *X = 0;
+  if (extra_P != R_NilValue) {
+    if (K < 1 || XLENGTH(extra_P) % (R_xlen_t)K != 0) Rf_error("bnmf: extra_P has %ld values, not a multiple of K = %d rows", (long)XLENGTH(extra_P), K);
+    *X = (int)(XLENGTH(extra_P) / (R_xlen_t)K);
+    if (extra_label == R_NilValue || XLENGTH(extra_label) != (R_xlen_t)*X) Rf_error("bnmf: extra_label must hold one label per extra column (%d)", *X);
+  }
+  *u = lgl_flags(used, n);
+  *lab = NULL;
+  if (labels != R_NilValue) {                                             /* column-major n x N -> row-major, NA = left out */
+    *lab = (int32_t*)R_alloc((size_t)n * N, sizeof(int32_t));
+    for (int s = 0; s < n; ++s) for (int f = 0; f < N; ++f) { const int v = INTEGER(labels)[s + (size_t)n * f]; (*lab)[(size_t)s * N + f] = v == NA_INTEGER ? -1 : v; }
+  }
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_points", "n_extra", "n_left_out", "n_clusters", "min_stability_at", "n_negative", "mean_silhouette",
+                              "min_stability", "point", "factor", "between", "medoid", "medoid_at"};
+  SEXP out = PROTECT(named_list(14, nms));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, S * N + *X, BNMF_STAB_NPOINT));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, N, BNMF_STAB_NFROW));
+  SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, N, N));
+  SET_VECTOR_ELT(out, 12, Rf_allocMatrix(REALSXP, K, N));
+  SET_VECTOR_ELT(out, 13, Rf_allocVector(REALSXP, N));
+  UNPROTECT(1);
+  return out;
+}
+static void stab_finish(SEXP out, const bnmf_stability_info* info, const int64_t* at, int N) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_points));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarInteger(info->n_extra)); SET_VECTOR_ELT(out, 3, Rf_ScalarInteger(info->n_left_out));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarInteger(info->n_clusters)); SET_VECTOR_ELT(out, 5, Rf_ScalarInteger(info->min_stability_at));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarReal((double)info->n_negative)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal(info->mean_silhouette));
+  SET_VECTOR_ELT(out, 8, Rf_ScalarReal(info->min_stability));
+  for (int j = 0; j < N; ++j) REAL(VECTOR_ELT(out, 13))[j] = (double)at[j];
+}
+SEXP C_bnmf_stability(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP labels, SEXP extra_P, SEXP extra_label, SEXP dims) {
+  int32_t *u = NULL, *lab = NULL; int X = 0;
+  const int N = INTEGER(dims)[2];
+  SEXP out = PROTECT(stab_alloc(n_samples, used, labels, extra_P, extra_label, dims, &u, &lab, &X));
+  int64_t* at = (int64_t*)R_alloc((size_t)(N > 0 ? N : 1), sizeof(int64_t));
+  const double* ex = X > 0 ? REAL(extra_P) : NULL;
+  const int32_t* el = X > 0 ? (const int32_t*)INTEGER(extra_label) : NULL;
+  bnmf_stability_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_stability(get_handle(ptr), INTEGER(n_samples)[0], u, lab, ex, el, X, map_buf(out, 9), map_buf(out, 10), map_buf(out, 11), map_buf(out, 12), at, &info));
+  else
+    chk(bnmf_stability_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, lab, ex, el, X, map_buf(out, 9), map_buf(out, 10), map_buf(out, 11),
+                          map_buf(out, 12), at, &info));
+  stab_finish(out, &info, at, N);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_stability_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP labels, SEXP extra_P, SEXP extra_label, SEXP dims) {
+  int32_t *u = NULL, *lab = NULL; int X = 0;
+  const int N = INTEGER(dims)[2];
+  SEXP out = PROTECT(stab_alloc(n_samples, used, labels, extra_P, extra_label, dims, &u, &lab, &X));
+  int64_t* at = (int64_t*)R_alloc((size_t)(N > 0 ? N : 1), sizeof(int64_t));
+  bnmf_stability_info info;
+  chk(bnmf_stability_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, lab, X > 0 ? REAL(extra_P) : NULL,
+                        X > 0 ? (const int32_t*)INTEGER(extra_label) : NULL, X, map_buf(out, 9), map_buf(out, 10), map_buf(out, 11), map_buf(out, 12), at, &info));
+  stab_finish(out, &info, at, N);
+  UNPROTECT(1);
+  return out;
+}
 /* Exposures of new tumours under the recorded signatures on the device (bnmf_project / bnmf_project_at): C_bnmf_project(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), X (K x J real matrix, not
  * negative), n_steps, min_load, want_exposures (logical), dims c(K,G,N)) -> list(n_used, n_steps, n_present, min_load, total,
@@ -974,6 +1051,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_contrast", (DL_FUNC)&C_bnmf_contrast, 9}, {"C_bnmf_contrast_at", (DL_FUNC)&C_bnmf_contrast_at, 9},
   {"C_bnmf_regress", (DL_FUNC)&C_bnmf_regress, 9}, {"C_bnmf_regress_at", (DL_FUNC)&C_bnmf_regress_at, 9},
   {"C_bnmf_coactivity", (DL_FUNC)&C_bnmf_coactivity, 9}, {"C_bnmf_coactivity_at", (DL_FUNC)&C_bnmf_coactivity_at, 9},
+  {"C_bnmf_stability", (DL_FUNC)&C_bnmf_stability, 8}, {"C_bnmf_stability_at", (DL_FUNC)&C_bnmf_stability_at, 8},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
