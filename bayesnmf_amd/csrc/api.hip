@@ -188,6 +188,7 @@ struct ZSort {
   bool pk = false, shared = false;     // two factors per word; large cells spread over the blocks: ZsumK is accumulated (atomics), the draw kernels zero it
   ZSGeom g{}; int nblk = 0, w = 0; size_t lds = 0;
   int it16 = 0, qmax = ZS_QMAX;        // 2-byte items; quads per item
+  int fixed = 0;                       // the geometry-fixed instantiation the schedule fits (zsort_fixed_form; 0: none, or BNMF_ZSFIXED=0)
   int nempty = 0;                      // blocks without an own column (bnmf_get_stat 7)
   uint32_t* dItems = nullptr; ZSBlock* dBlocks = nullptr; int* dCols = nullptr; int32_t* dM = nullptr; unsigned long long* dProf = nullptr;
   double* dMh = nullptr;               // [3][G][K] Mhat left by k_zalloc_sort for the per-column metric terms (colterms.h)
@@ -511,6 +512,7 @@ static int build_zsort(bnmf_handle* h, const int32_t* M, bool reg_ok, const Swit
   z.g = ZSGeom{p.KP, p.GBc, p.nb};
   z.shared = p.shared;                                     // columns with several writers of ZsumK: atomics + zeroing by the consumer (refresh_dev)
   z.nblk = p.nblk; z.w = p.W; z.pk = p.pk; z.nempty = p.nempty;
+  z.fixed = sw.zs_fixed ? zsort_fixed_form((int)K, (int)N, p.KP, p.GBc, z.it16, p.qmax, p.W, p.nblk, p.pk, p.shared, c.save_Z != 0) : 0;
   z.lds = (zsort_shared_bytes((int)K, (int)N, p.KP, p.GBc, p.pk) + (size_t)p.W * zsort_wave_bytes(p.nblk, (int)N) + 15) & ~(size_t)15;
   h->zkind = ZKind::sort;
 #ifdef ZSPROF

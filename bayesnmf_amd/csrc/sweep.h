@@ -359,6 +359,15 @@ static int launch_zsort_t(bnmf_handle* h, uint32_t t) {
     hipLaunchKernelGGL(kern, dim3(h->zs.g.nblocks), dim3(ZT_), h->zs.lds, h->stream, sa, t, h->zs.g);
     return 0;
   };
+  // the geometry-fixed instantiations (zalloc_sort.h ZSFixed; chosen by build_zsort, BNMF_ZSFIXED=0: never): 14 waves, two factors per word,
+  // raised issue priority, no record, no shared column.  Every other handle takes the dynamic form below, as before round 6.
+  if constexpr (ZT_ == ZSFIX_ZT) {
+    if (h->zs.fixed && sa.prio != 0 && !sa.rec && !sa.shared) switch (h->zs.fixed) {
+      case 1: return go(k_zalloc_sort<ZSFIX_ZT, ZSFIX_NBLK, true, ZSFix10k>);
+      case 2: return go(k_zalloc_sort<ZSFIX_ZT, ZSFIX_NBLK, true, ZSFix2k>);
+      default: break;
+    }
+  }
 #ifdef BNMF_FASTBUILD   /* builder's experiment builds only (one allocation kernel: the metric configuration's): never the product */
   if (h->zs.nblk != 4) return fail(BNMF_EMODEL, "BNMF_FASTBUILD: only N = 16..20");
   return h->zs.pk ? go(k_zalloc_sort<ZT_, 4, true>) : go(k_zalloc_sort<ZT_, 4, false>);

@@ -73,17 +73,59 @@ BNMF_HD size_t zsort_shared_bytes(int K, int N, int KP, int GBc, bool pk) {
 }
 BNMF_HD size_t zsort_wave_bytes(int NBLK, int N) { return (size_t)NBLK * 64 * 16 + (size_t)(2 * ((N + 1) / 2)) * 64 * 4; }   // threshold blocks + one histogram word per factor and lane
 
+// What an instantiation knows of its geometry at compile time (round 6).  ZSDyn: nothing — K, N, KP, GBc, the item format, the quads per
+// item and the prio / shared / rec switches are read from ZSArgs / ZSGeom at run time, as in rounds 3-5.  ZSFixed: all of them are constants
+// of the instantiation (the headline family of shapes: zsort_fixed_form below, sweep.h launch_zsort_t): no scalar register holds them, the strides of the
+// threshold pass fold into the LDS instructions' offsets, the flush has a constant trip count.  The same body, the same bits.
+struct ZSDyn {
+  static constexpr bool fixed = false, prio = false, shared = false, rec = false;
+  static constexpr int K = 0, N = 0, KP = 0, GBc = 0, IT16 = 0, QMAX = 0;
+};
+template <int K_, int N_, int KP_, int GBc_, int IT16_, int QMAX_, bool PRIO_ = true, bool SHARED_ = false, bool REC_ = false>
+struct ZSFixed {
+  static constexpr bool fixed = true, prio = PRIO_, shared = SHARED_, rec = REC_;
+  static constexpr int K = K_, N = N_, KP = KP_, GBc = GBc_, IT16 = IT16_, QMAX = QMAX_;
+};
+// The instantiated geometries: what plan_zsort (zplan.h) yields for K = 96, N = 20 on 256 blocks of 14 waves at G = 10,000 (the metric
+// configuration: 40 columns per block, 2-byte items of 64 quads) and at G = 2,000 (BASELINE's configuration 2: 8 columns per block, 4-byte
+// items of 16 quads — its cells reach 900 counts, beyond eight 2-byte fragments of 64).  tests/test_zsort_fixed_host.py pins the planner to them.
+constexpr int ZSFIX_ZT = 896, ZSFIX_NBLK = 4;
+using ZSFix10k = ZSFixed<96, 20, 97, 40, 1, 64>;
+using ZSFix2k = ZSFixed<96, 20, 97, 8, 0, 16>;
+template <class FX>
+inline bool zsort_fixed_is(int K, int N, int KP, int GBc, int it16, int qmax) {
+  return K == FX::K && N == FX::N && KP == FX::KP && GBc == FX::GBc && (it16 != 0) == (FX::IT16 != 0) && qmax == FX::QMAX;
+}
+// which of them a schedule can take (0: none, the dynamic form): two factors per word, 14 waves, no shared column, no record
+inline int zsort_fixed_form(int K, int N, int KP, int GBc, int it16, int qmax, int W, int nblk, bool pk, bool shared, bool rec) {
+  if (!pk || shared || rec || W * 64 != ZSFIX_ZT || nblk != ZSFIX_NBLK) return 0;
+  return zsort_fixed_is<ZSFix10k>(K, N, KP, GBc, it16, qmax) ? 1 : zsort_fixed_is<ZSFix2k>(K, N, KP, GBc, it16, qmax) ? 2 : 0;
+}
+// the smallest value of the 64 lanes, in every lane's scalar copy: DPP inside the rows of 16, the four rows by readlane.  All lanes active.
+BNMF_DEV int wave_min_i32(int v) {
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));     // quad_perm:[1,0,3,2]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));     // quad_perm:[2,3,0,1]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));    // row_half_mirror
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));    // row_mirror
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
 // <= 128 VGPRs (4 waves per SIMD by registers): three waves per SIMD of this kernel then leave the side streams' kernels
 // (128 VGPRs) a wave slot on every SIMD — at 133 VGPRs they could not start before the first workgroups here had ended
-template <int ZT, int NBLK /* threshold blocks per cell: covers N <= 5 NBLK */, bool PK>
+template <int ZT, int NBLK /* threshold blocks per cell: covers N <= 5 NBLK */, bool PK, class FX = ZSDyn /* ZSFixed<...>: the geometry at compile time */>
 __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_zalloc_sort(ZSArgs s, uint32_t t, ZSGeom zg) {
+  constexpr bool FIX = FX::fixed;
+  static_assert(!FIX || (NBLK == (FX::N + 4) / 5 && FX::N >= 1 && FX::N < ZS_NMAX && FX::K >= 1 && FX::GBc >= 1 && FX::GBc <= 64 && FX::QMAX >= 1), "ZSFixed: geometry");
   constexpr int NPV = NBLK - 1;                           // pivots: threshold 5j + 4 closes block j
   constexpr int NC = 5 * NBLK;                            // factors covered
   constexpr int NMIN = NBLK == 1 ? 1 : 5 * (NBLK - 1) + 1; // smallest N routed here
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const ZArgs& d = s.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = d.K, N = d.N, KP = zg.KP, GBc = zg.GBc;
+  const int K = FIX ? FX::K : d.K, N = FIX ? FX::N : d.N, KP = FIX ? FX::KP : zg.KP, GBc = FIX ? FX::GBc : zg.GBc;
+  const int qmax = FIX ? FX::QMAX : s.qmax;
+  const bool it16 = FIX ? FX::IT16 != 0 : s.it16 != 0, prio = FIX ? FX::prio : s.prio != 0, shared = FIX ? FX::shared : s.shared != 0;
+  const bool rec = FIX ? FX::rec : s.rec != nullptr;
   const int HW = (N + 1) >> 1;
   const int ZR = PK ? HW : N;                              // rows of zG / zK
   const ZSBlock bk = s.blocks[blockIdx.x];
@@ -151,7 +193,7 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
   ZSSTAMP(2);
   // The kernel is bound by instruction issue and the side streams' kernels run beside it on the same SIMDs: its waves take the issue
   // priority (timing only).  Small side launches raise theirs to 3 (kernels.h side_body): they are few and the next draw kernel waits for them.
-  if (s.prio) __builtin_amdgcn_s_setprio(2);
+  if (prio) __builtin_amdgcn_s_setprio(2);
   const int nthr = N - 1;
   const int ntot = bk.ntask;
   const uint32_t hlb = lds_off(hist + lane);
@@ -172,13 +214,13 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     // ---------------- item task: lane = item
     ZSTIC(1);
     uint32_t it;
-    if (s.it16) {                                          // wave-uniform: the same fields from half the bytes
+    if (it16) {                                            // wave-uniform: the same fields from half the bytes
       const uint32_t r = ((const uint16_t*)s.items)[(size_t)bk.item0 + (size_t)task * 64 + lane];
       it = r == 0xFFFFu ? 0xFFFFFFFFu : ((r & 127u) | (((r >> 7) & 63u) << 10) | ((r >> 13) << 16));
     } else it = s.items[(size_t)bk.item0 + (size_t)task * 64 + lane];
     const bool valid = it != 0xFFFFFFFFu;
     const int k = valid ? (int)(it & 1023u) : 0, gl = valid ? (int)((it >> 10) & 63u) : 0;
-    const int q0 = valid ? (int)(it >> 16) * s.qmax : 0;
+    const int q0 = valid ? (int)(it >> 16) * qmax : 0;
     const int m = Mb[k + (size_t)K * gl];
     const int g = colid[gl];
     int nq = 0, npad = 0;
@@ -197,7 +239,7 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
       for (int n = 0; n < NC; ++n) { if (n < NMIN || n < N) c = c + Pk[(size_t)K * n] * ag[(size_t)n * GBc]; cs[n] = c; }
       if (valid && c > 0.0 && m > 0) {
         const int qt = (m + 3) >> 2;
-        nq = min(s.qmax, qt - q0);
+        nq = min(qmax, qt - q0);
         npad = (q0 + nq == qt) ? ((4 - (m & 3)) & 3) : 0;
       }
       if (valid && q0 == 0) s.mh[(size_t)k + (size_t)K * (size_t)g] = c;
@@ -220,7 +262,8 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     }
     const uint32_t celem = (uint32_t)k + (uint32_t)K * (uint32_t)g;
     // one quad: Philox block q of the cell's stream -> 4 words -> 4 buckets -> 4 histogram increments (inc: 1, or 0 for a pad)
-    auto quad = [&](int qidx, uint32_t inc0, uint32_t inc1, uint32_t inc2, uint32_t inc3) {
+    // (find: the histogram words of the quad's four counts; quad: ... and their increments)
+    auto find = [&](int qidx, uint32_t& a0, uint32_t& a1, uint32_t& a2, uint32_t& a3) {
       const u32x4 w = philox4x32_7((uint32_t)qidx, celem, t, BNMF_V_Z, d.k0, d.k1);
       const uint32_t u0 = min(w.x, 0xFFFFFFFEu), u1 = min(w.y, 0xFFFFFFFEu), u2 = min(w.z, 0xFFFFFFFEu), u3 = min(w.w, 0xFFFFFFFEu);
       uint32_t j0 = 0, j1 = 0, j2 = 0, j3 = 0;
@@ -231,10 +274,15 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
       const uint32_t b1 = 5 * j1 + (k1.x <= u1) + (k1.y <= u1) + (k1.z <= u1) + (k1.w <= u1);
       const uint32_t b2 = 5 * j2 + (k2.x <= u2) + (k2.y <= u2) + (k2.z <= u2) + (k2.w <= u2);
       const uint32_t b3 = 5 * j3 + (k3.x <= u3) + (k3.y <= u3) + (k3.z <= u3) + (k3.w <= u3);
-      lds_add(mad24(b0, 256, hlb), inc0);
-      lds_add(mad24(b1, 256, hlb), inc1);
-      lds_add(mad24(b2, 256, hlb), inc2);
-      lds_add(mad24(b3, 256, hlb), inc3);
+      a0 = mad24(b0, 256, hlb); a1 = mad24(b1, 256, hlb); a2 = mad24(b2, 256, hlb); a3 = mad24(b3, 256, hlb);
+    };
+    auto quad = [&](int qidx, uint32_t inc0, uint32_t inc1, uint32_t inc2, uint32_t inc3) {
+      uint32_t a0, a1, a2, a3;
+      find(qidx, a0, a1, a2, a3);
+      lds_add(a0, inc0);
+      lds_add(a1, inc1);
+      lds_add(a2, inc2);
+      lds_add(a3, inc3);
     };
     wave_lds_fence();
     ZSTOC(1);
@@ -243,7 +291,26 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
 #endif
     ZSTIC(2);
     // full quads, then each lane's last quad (the only one that can hold pads)
-    if (any) for (int i = 0; __builtin_amdgcn_ballot_w64(i < nq - 1) != 0; ++i)
+    int i = 0;
+    if constexpr (FIX) {
+      // Round 6: the items of a task are sorted by their quads, so in nearly every task all 64 lanes hold an item with counts and differ by
+      // a quad or two.  The full quads that EVERY lane has (the wave's smallest nq - 1: one DPP reduction per task) run in a wave-uniform
+      // loop without a ballot or a predicate per trip, two quads per trip with the searches of both ahead of their eight increments; the
+      // loop below follows it for the ragged rest, and alone in the tail tasks (an empty lane, or a cell without counts).  The Philox
+      // counters, the words, the buckets and the increments are the same; the histogram takes integer adds, whatever their order.
+      if (__builtin_amdgcn_ballot_w64(nq > 0) == ~0ull) {
+        const int nfull = wave_min_i32(nq - 1);
+        for (; i + 1 < nfull; i += 2) {
+          uint32_t a0, a1, a2, a3, c0, c1, c2, c3;
+          find(q0 + i, a0, a1, a2, a3);
+          find(q0 + i + 1, c0, c1, c2, c3);
+          lds_add(a0, 1u); lds_add(a1, 1u); lds_add(a2, 1u); lds_add(a3, 1u);
+          lds_add(c0, 1u); lds_add(c1, 1u); lds_add(c2, 1u); lds_add(c3, 1u);
+        }
+        if (i < nfull) { quad(q0 + i, 1u, 1u, 1u, 1u); ++i; }
+      }
+    }
+    if (any) for (; __builtin_amdgcn_ballot_w64(i < nq - 1) != 0; ++i)
       if (i < nq - 1) quad(q0 + i, 1u, 1u, 1u, 1u);
     if (nq > 0) quad(q0 + nq - 1, 1u, npad > 2 ? 0u : 1u, npad > 1 ? 0u : 1u, npad > 0 ? 0u : 1u);
     wave_lds_fence();
@@ -254,11 +321,26 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
 #endif
     ZSTIC(3);
     // flush the lane's histogram into the block's tables
-    if (s.rec) {                       // save_Z: the item's record (lanes without counts write zeros: their histogram is clear)
+    if (rec) {                         // save_Z: the item's record (lanes without counts write zeros: their histogram is clear)
       uint32_t* rt = s.rec + ((size_t)(bk.item0 >> 6) + (size_t)task) * (size_t)HW * 64 + lane;
       for (int w = 0; w < HW; ++w) rt[(size_t)w * 64] = hist[(2 * w) * 64 + lane] | (hist[(2 * w + 1) * 64 + lane] << 16);
     }
-    if (nq > 0) {
+    if constexpr (FIX && PK) {
+      // Round 6: HW is a constant — all the item's histogram words are requested before the first is used (one LDS round trip instead
+      // of HW dependent ones); then the same zeroing and the same adds of the same packed values for the non-zero pairs
+      if (nq > 0) {
+        constexpr int HWC = (FX::N + 1) >> 1;
+        const uint32_t zgb = lds_off(zG) + ((uint32_t)k << 2), zkb = lds_off(zK) + ((uint32_t)gl << 2);
+        uint32_t v[HWC];
+#pragma unroll
+        for (int w = 0; w < HWC; ++w) v[w] = hist[(2 * w) * 64 + lane] | (hist[(2 * w + 1) * 64 + lane] << 16);
+#pragma unroll
+        for (int w = 0; w < HWC; ++w) if (v[w]) {
+          hist[(2 * w) * 64 + lane] = 0; hist[(2 * w + 1) * 64 + lane] = 0;
+          lds_add(zgb + (uint32_t)w * (uint32_t)FX::KP * 4u, v[w]); lds_add(zkb + (uint32_t)w * (uint32_t)FX::GBc * 4u, v[w]);
+        }
+      }
+    } else if (nq > 0) {
       const uint32_t zgb = lds_off(zG) + ((uint32_t)k << 2), zkb = lds_off(zK) + ((uint32_t)gl << 2);
       for (int w = 0; w < HW; ++w) {
         const uint32_t v0 = hist[(2 * w) * 64 + lane], v1 = hist[(2 * w + 1) * 64 + lane];
@@ -290,7 +372,7 @@ __global__ __launch_bounds__(ZT) __attribute__((amdgpu_waves_per_eu(4))) void k_
   for (int i = tid; i < N * bk.ncols; i += ZT) {
     const int gl = i / N, n = i - gl * N;
     const uint32_t v = PK ? (zK[(size_t)(n >> 1) * GBc + gl] >> ((n & 1) << 4)) & 0xFFFFu : zK[(size_t)n * GBc + gl];
-    if (s.shared) { if (v) atomicAdd(&d.ZsumK[n + (size_t)N * colid[gl]], (int32_t)v); }   // (zeroed by the draw kernel that consumed the last one)
+    if (shared) { if (v) atomicAdd(&d.ZsumK[n + (size_t)N * colid[gl]], (int32_t)v); }   // (zeroed by the draw kernel that consumed the last one)
     else d.ZsumK[n + (size_t)N * colid[gl]] = (int32_t)v;
   }
   for (int i = tid; i < K * N; i += ZT) {

@@ -35,6 +35,7 @@ struct Switches {
   int zw = ENV_UNSET, z_grid = ENV_UNSET;   // BNMF_ZW, BNMF_ZGRID
   // plan_zsort
   bool zsort = true, zs_spread = true, zs_it16 = true, zs_pk = true;   // BNMF_ZSORT, BNMF_ZSSPREAD, BNMF_ZSIT16, BNMF_ZSPK
+  bool zs_fixed = true;                // BNMF_ZSFIXED=0: never a geometry-fixed instantiation of k_zalloc_sort (build_zsort; the planner does not read it)
   int zs_lds_kb = ENV_UNSET, zs_w = ENV_UNSET, zs_qmax = 0;             // BNMF_ZSLDS, BNMF_ZSW, BNMF_ZSQMAX
   // plan_zstep
   bool zstep = true, zp_it16 = true; int zp_gb = 0;   // BNMF_ZSTEP, BNMF_ZPIT16, BNMF_ZPGB
@@ -61,7 +62,7 @@ struct Switches {
     s.z_tile = env_flag("BNMF_ZTILE", true); s.z_nolean = env_set("BNMF_ZNOLEAN");
     s.zw = env_int("BNMF_ZW"); s.z_grid = env_int("BNMF_ZGRID");
     s.zsort = env_flag("BNMF_ZSORT", true); s.zs_spread = env_flag("BNMF_ZSSPREAD", true);
-    s.zs_it16 = env_flag("BNMF_ZSIT16", true); s.zs_pk = env_flag("BNMF_ZSPK", true);
+    s.zs_it16 = env_flag("BNMF_ZSIT16", true); s.zs_pk = env_flag("BNMF_ZSPK", true); s.zs_fixed = env_flag("BNMF_ZSFIXED", true);
     s.zs_lds_kb = env_int("BNMF_ZSLDS"); s.zs_w = env_int("BNMF_ZSW"); s.zs_qmax = env_int("BNMF_ZSQMAX", 0);
     s.zstep = env_flag("BNMF_ZSTEP", true); s.zp_it16 = env_flag("BNMF_ZPIT16", true); s.zp_gb = env_int("BNMF_ZPGB", 0);
     return s;
