@@ -42,6 +42,7 @@
 #include "regress.h"
 #include "coactivity.h"
 #include "stability.h"
+#include "reconstruction.h"
 
 using namespace bnmf;
 

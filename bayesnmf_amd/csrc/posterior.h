@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h and stability.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h and reconstruction.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1367,6 +1367,76 @@ static int stability_impl(bnmf_handle* h, const char* fn, Range r, const int32_t
   return 0;
 }
 
+// Reconstruction quality per tumour over the samples of r that used[] flags (reconstruction.h): k_rec_data once (the data
+// k-major as doubles, mm and t per tumour), then per batch of samples k_rec_x (the rows P_s diag(A_s)), k_rec (a lane per (s, g): the
+// per-sample values in the scratch) and k_rec_stats (the statistics continued in sample order, the series); the series' division, the
+// signature rows and the info fields are reconstruction_reduce's.
+static_assert(RC_NTUM == BNMF_REC_NTUM && RC_NDROP == BNMF_REC_NDROP, "reconstruction.h and bnmf.h disagree");
+static constexpr size_t REC_SCRATCH_CAP = (size_t)256 << 20;    // bytes of a batch's blocks of the scratch
+static int reconstruction_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, double min_cosine, double min_drop, double* tumour,
+                               double* drop, double* series, double* signature, bnmf_reconstruction_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  if (!std::isfinite(min_cosine)) return fail(BNMF_EINVAL, "%s: min_cosine = %g is not a finite number", fn, min_cosine);
+  if (!std::isfinite(min_drop)) return fail(BNMF_EINVAL, "%s: min_drop = %g is not a finite number", fn, min_drop);
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the cosines needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  bool reg = N <= RC_MAX_NT;
+  if (const char* e = getenv("BNMF_REC_FORM")) if (atoi(e) == 1) reg = false;                              // tests, tools: the tiled form
+  const int NS = reg ? rec_row_stride(N) : N;
+  const size_t NG = (size_t)N * G, KNS = (size_t)K * NS, rows = (size_t)(N + 3) * G;
+  const size_t per = (rows + KNS) * sizeof(double);                                                        // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, REC_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_REC_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>({want, (long long)S, 65535LL});                                  // (a batch is the grid's y)
+  // x staged in the LDS while it fits: measured faster than the wave-uniform reads through the caches in the register form too
+  // (DESIGN.md 23), unlike bnmf_project's refit
+  const bool fits = rec_lds_bytes(K, NS) <= LDS_CAP;
+  bool stage = fits;
+  if (const char* e = getenv("BNMF_REC_STAGE")) stage = fits && atoi(e) != 0;                              // tests, tools: the other choice
+  const size_t lds = stage ? rec_lds_bytes(K, NS) : 0;
+  double *dMt, *dmm, *dtt, *dxg, *dscr, *dst, *dsd, *dser, *dtum, *ddrop; int* dslots;
+  if (int rc = carve(h, [&](Carve& c) {
+        dMt = c.take<double>((size_t)K * G); dmm = c.take<double>(G); dtt = c.take<double>(G); dxg = c.take<double>((size_t)Sb * KNS);
+        dscr = c.take<double>((size_t)Sb * rows); dst = c.take<double>((size_t)RC_NTUM * G); dsd = c.take<double>(RC_NDROP * NG);
+        dser = c.take<double>(S); dtum = c.take<double>((size_t)RC_NTUM * G); ddrop = c.take<double>(RC_NDROP * NG); dslots = c.take<int>(S);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_rec_data<RC_NTUM>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)h->dMf, K, G, dMt, dmm, dtt);
+  using RecKernel = decltype(&k_rec<8, true>);
+  const RecKernel staged[5] = {k_rec<0, true>, k_rec<8, true>, k_rec<16, true>, k_rec<24, true>, k_rec<32, true>};
+  const RecKernel direct[5] = {k_rec<0, false>, k_rec<8, false>, k_rec<16, false>, k_rec<24, false>, k_rec<32, false>};
+  const RecKernel kern = (stage ? staged : direct)[reg ? NS / 8 : 0];
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  const double *ringP = h->arr[BNMF_P].ring, *ringE = h->arr[BNMF_E].ring, *ringA = h->arr[BNMF_A].ring;
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0), last = s0 + nb == S ? 1 : 0;
+    hipLaunchKernelGGL(k_rec_x<RC_NTUM>, dim3(nb), dim3(256), 0, h->stream, ringP, ringA, (size_t)K * N, K, N, NS, (const int*)dslots + s0, dxg);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((G + RC_T - 1) / RC_T), (unsigned)nb), dim3(RC_T), lds, h->stream, (const double*)dxg, ringE, NG,
+                       (const int*)dslots + s0, (const double*)dMt, (const double*)dmm, (const double*)dtt, K, N, G, dscr);
+    hipLaunchKernelGGL(k_rec_stats<RC_NTUM>, dim3((unsigned)((size_t)nb + (NG + (size_t)G + RC_TT - 1) / RC_TT)), dim3(RC_TT), 0, h->stream, (const double*)dscr, ringA,
+                       (const int*)dslots + s0, (const double*)dmm, nb, N, G, S, s0, last, min_cosine, min_drop, dst, dsd, dser, dtum, ddrop);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> ht, hd, hs(S), hm(G);                      // the info fields need the rows whether or not the caller wants them
+  if (!tumour) { ht.resize((size_t)RC_NTUM * G); tumour = ht.data(); }
+  if (!drop) { hd.resize(RC_NDROP * NG); drop = hd.data(); }
+  HIPCHK(hipMemcpyAsync(tumour, dtum, (size_t)RC_NTUM * G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(drop, ddrop, RC_NDROP * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hs.data(), dser, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hm.data(), dmm, hm.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  reconstruction_reduce(tumour, drop, hm.data(), hs.data(), S, N, G, min_cosine, signature, info);
+  info->n_used = S; info->min_cosine = min_cosine; info->min_drop = min_drop;
+  if (series) std::memcpy(series, hs.data(), hs.size() * sizeof(double));
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1474,6 +1544,15 @@ int bnmf_stability_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t
                       const int32_t* extra_label, int X, double* point, double* factor, double* between, double* medoid, int64_t* medoid_at,
                       bnmf_stability_info* info) {
   return stability_impl(h, "bnmf_stability_at", {true, end_iter, n_samples}, used, labels, extra_P, extra_label, X, point, factor, between, medoid, medoid_at, info);
+}
+
+int bnmf_reconstruction(bnmf_handle* h, int last_n, const int32_t* used, double min_cosine, double min_drop, double* tumour, double* drop, double* series,
+                        double* signature, bnmf_reconstruction_info* info) {
+  return reconstruction_impl(h, "bnmf_reconstruction", {false, 0, last_n}, used, min_cosine, min_drop, tumour, drop, series, signature, info);
+}
+int bnmf_reconstruction_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double min_cosine, double min_drop, double* tumour, double* drop,
+                           double* series, double* signature, bnmf_reconstruction_info* info) {
+  return reconstruction_impl(h, "bnmf_reconstruction_at", {true, end_iter, n_samples}, used, min_cosine, min_drop, tumour, drop, series, signature, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

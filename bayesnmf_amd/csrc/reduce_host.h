@@ -1,8 +1,9 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
-//  and bnmf_stability's finish.  No device and no handle: posterior.h includes it, and a stand-alone host
-// program can (tools/coactivity_reduce_check.cpp and tools/stability_reduce_check.cpp, built with -fsanitize=address,undefined by
-// tests/test_coactivity_host.py and tests/test_stability_host.py).  Compile with -ffp-contract=off, as the library is.
+// (DESIGN.md 21), bnmf_stability's finish and bnmf_reconstruction's.  No device and no handle: posterior.h
+// includes it, and a stand-alone host program can (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp and
+// tools/reconstruction_reduce_check.cpp, built with -fsanitize=address,undefined by tests/test_coactivity_host.py,
+// tests/test_stability_host.py and tests/test_reconstruction_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -181,4 +182,42 @@ template <class Work> static void deal_threads(long nwork, Work work) {
   double sum = 0.0;
   for (int k = 0; k < K; ++k) sum = sum + col[(size_t)k * stride];
   for (int k = 0; k < K; ++k) out[k] = col[(size_t)k * stride] / sum;
+}
+
+// ---- bnmf_reconstruction's finish: from the finished rows to the series, the signature rows and the info fields ----
+// tumour [6][G] and drop [4][N*G] (each row n + N g) as the device left them, mm [G] (a tumour is defined iff mm > 0), ser [S]: in, the
+// sums of cos over the defined tumours; out, divided by their number (NaN without one).  signature [3][N] may be null.  Of info every
+// field but n_used, min_cosine and min_drop is set; min_cosine is the threshold of n_poor.
+[[maybe_unused]] static void reconstruction_reduce(const double* tumour, const double* drop, const double* mm, double* ser, int S, int N, long G, double min_cosine,
+                                                   double* signature, bnmf_reconstruction_info* info) {
+  const double nan = std::nan("");
+  const size_t NG = (size_t)N * (size_t)G;
+  long ndef = 0;
+  for (long g = 0; g < G; ++g) ndef += mm[g] > 0.0 ? 1 : 0;
+  for (int s = 0; s < S; ++s) ser[s] = ndef > 0 ? ser[s] / (double)ndef : nan;
+  int64_t npoor = 0, nneed = 0, at = -1; double worst = nan;
+  for (long g = 0; g < G; ++g) {
+    if (!(mm[g] > 0.0)) continue;
+    const double v = tumour[g];
+    npoor += v < min_cosine ? 1 : 0;
+    if (!std::isnan(v) && (at < 0 || v < worst)) { worst = v; at = g; }
+  }
+  for (size_t i = 0; i < NG; ++i) nneed += drop[3 * NG + i] >= 0.5 ? 1 : 0;
+  info->n_undefined = (int32_t)(G - ndef); info->n_poor = npoor; info->n_needed = nneed; info->worst_cosine = worst; info->worst_at = at;
+  if (!signature) return;
+  std::vector<double> tmp((size_t)std::max<long>(ndef, 1));
+  for (int n = 0; n < N; ++n) {
+    long cnt = 0, j = 0; double mx = nan;
+    for (long g = 0; g < G; ++g) {
+      const size_t i = (size_t)n + (size_t)N * (size_t)g;
+      cnt += drop[3 * NG + i] >= 0.5 ? 1 : 0;
+      if (!(mm[g] > 0.0)) continue;
+      const double v = drop[i];
+      if (j == 0 || v > mx) mx = v;
+      tmp[(size_t)j++] = v;
+    }
+    signature[n] = (double)cnt;
+    signature[(size_t)N + n] = ndef > 0 ? con_canon64(tmp.data(), (size_t)ndef, 1) / (double)ndef : nan;
+    signature[2 * (size_t)N + n] = mx;
+  }
 }

@@ -121,6 +121,11 @@ class BnmfStabilityInfo(C.Structure):
                 ("min_stability_at", C.c_int32), ("n_negative", C.c_int64), ("mean_silhouette", C.c_double), ("min_stability", C.c_double)]
 
 
+class BnmfReconstructionInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_undefined", C.c_int32), ("n_poor", C.c_int64), ("n_needed", C.c_int64), ("worst_at", C.c_int64),
+                ("min_cosine", C.c_double), ("min_drop", C.c_double), ("worst_cosine", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -142,6 +147,9 @@ COA_STATS = ["pearson", "spearman", "copresence", "cosine"]
 COA_PAIR_ROWS = ["mean", "var", "lower", "upper", "p_greater", "p_less", "n_valid"]
 STAB_POINT_ROWS = ["silhouette", "a", "b", "nearest"]
 STAB_FACTOR_ROWS = ["members", "stability", "min_silhouette", "mean_a", "mean_b", "share_negative"]
+REC_TUMOUR_ROWS = ["cosine", "cosine_var", "min_cosine_sample", "rel_l1", "rmse", "p_good"]
+REC_DROP_ROWS = ["drop_mean", "drop_var", "loo_cosine", "p_needed"]
+REC_SIGNATURE_ROWS = ["n_tumours", "mean_drop", "max_drop"]
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -160,7 +168,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_waic", "bnmf_waic_at", "bnmf_mixing", "bnmf_mixing_at", "bnmf_ppc", "bnmf_ppc_at",
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
                "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
-               "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at"]
+               "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
+               "bnmf_reconstruction", "bnmf_reconstruction_at"]
 
 
 def lib():
@@ -231,6 +240,8 @@ def lib():
         lp = C.POINTER(C.c_int64)
         L.bnmf_stability.argtypes = [C.c_void_p, C.c_int, ip, ip, dp, ip, C.c_int, dp, dp, dp, dp, lp, C.POINTER(BnmfStabilityInfo)]
         L.bnmf_stability_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, dp, ip, C.c_int, dp, dp, dp, dp, lp, C.POINTER(BnmfStabilityInfo)]
+        L.bnmf_reconstruction.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfReconstructionInfo)]
+        L.bnmf_reconstruction_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfReconstructionInfo)]
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -778,6 +789,33 @@ class Engine:
     def stability_at(self, end_iter, n_samples, **kw):
         """stability over the n_samples iterations that end at end_iter (bnmf_stability_at)."""
         return self.stability(n_samples, end_iter=end_iter, **kw)
+
+    def reconstruction(self, last_n, used=None, end_iter=None, min_cosine=0.9, min_drop=0.01, drop=True):
+        """Reconstruction quality per tumour over the recorded samples flagged in used (length last_n, oldest first; None = all) of the
+        last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_reconstruction / bnmf_reconstruction_at), on
+        the device.  Returns the info fields, tumour (6 x G) with its rows also by name (REC_TUMOUR_ROWS: the mean, variance and smallest
+        value over the used samples of the cosine between the tumour's data and its fit, the mean relative L1 error and RMSE, the
+        fraction of samples whose cosine is >= min_cosine; NaN for an all-zero tumour), series (S: the cohort's mean cosine per used
+        sample) and signature (3 x N, REC_SIGNATURE_ROWS: the tumours that need the signature, the mean and the largest mean drop); with
+        drop also drop (4 x N x G) and its rows by name (REC_DROP_ROWS: the mean and variance of the loss of cosine when factor n is
+        left out of the fit without a refit, the mean leave-one-out cosine, the fraction of samples whose drop is >= min_drop)."""
+        G, N = self.G, self.N
+        u, S = self._used("reconstruction", used, last_n)
+        tum, series, sig = np.empty((6, G)), np.empty(S), np.empty((3, N))
+        dr = np.empty((4, N * G)) if drop else None
+        info = BnmfReconstructionInfo()
+        self._range_call("reconstruction", last_n, end_iter, u, float(min_cosine), float(min_drop), _dp(tum), _dp(dr), _dp(series), _dp(sig), C.byref(info))
+        out = self._info(info)
+        out.update(tumour=tum, series=series, signature=sig)
+        out.update({name: tum[i] for i, name in enumerate(REC_TUMOUR_ROWS)})
+        if drop:
+            out["drop"] = np.stack([row.reshape((N, G), order="F") for row in dr])
+            out.update({name: out["drop"][i] for i, name in enumerate(REC_DROP_ROWS)})
+        return out
+
+    def reconstruction_at(self, end_iter, n_samples, **kw):
+        """reconstruction over the n_samples iterations that end at end_iter (bnmf_reconstruction_at)."""
+        return self.reconstruction(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

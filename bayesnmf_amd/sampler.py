@@ -940,8 +940,36 @@ class bayesNMF_sampler:
                  f"{r['n_negative']} points nearer to another cluster", verbosity=1)
         return out
 
+    def get_reconstruction(self, end_iter=None, n_samples=None, idx="MAP_idx", min_cosine=0.9, min_drop=0.01):
+        """How well is every tumour of the cohort reconstructed, and which signatures does it need?  On the device
+        (bnmf_reconstruction_at; not in the reference): over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC:
+        the last MAP_over samples), restricted to `idx` ("MAP_idx": those whose A equals the mode of the range; None: every sample;
+        else a vector of recorded iterations), every sample gives per tumour the cosine between its data and its fit, the relative L1
+        error and the RMSE, and per signature the cosine of the fit without it.  The remaining exposures are not refitted after the
+        removal, so the drop is an upper bound of what removing the signature costs the tumour.
+        Returns dict(tumour (6 x G: the mean, variance and smallest value over the samples of the cosine, the mean relative L1 error,
+        the mean RMSE, the fraction of samples with cosine >= min_cosine; NaN for an all-zero tumour) with its rows also as cosine,
+        cosine_var, min_cosine_sample, rel_l1, rmse, p_good; drop (4 x N x G: the mean and variance of the drop, the mean
+        leave-one-out cosine, the fraction of samples with drop >= min_drop: the probability that the tumour needs the signature)
+        with its rows as drop_mean, drop_var, loo_cosine, p_needed; series (S: the cohort's mean cosine per used sample); signature
+        (3 x N: the tumours that need the signature, the mean and the largest mean drop); n_used, n_undefined, n_poor, n_needed,
+        min_cosine, min_drop, worst_cosine, worst_at)."""
+        if not hasattr(self._chain, "reconstruction"):
+            raise ValueError("get_reconstruction needs an engine that computes the fit over its recorded samples (reconstruction); this engine_factory's cannot")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.reconstruction(n, used=used, min_cosine=min_cosine, min_drop=min_drop, **kw)
+        G, N = self.dims["G"], self.dims["N"]
+        tum, drop = np.asarray(r["tumour"]).reshape(6, G), np.asarray(r["drop"]).reshape(4, N, G)
+        out = dict(tumour=tum, drop=drop, series=np.asarray(r["series"]).reshape(-1), signature=np.asarray(r["signature"]).reshape(3, N))
+        out.update({name: tum[i] for i, name in enumerate(("cosine", "cosine_var", "min_cosine_sample", "rel_l1", "rmse", "p_good"))})
+        out.update({name: drop[i] for i, name in enumerate(("drop_mean", "drop_var", "loo_cosine", "p_needed"))})
+        out.update({k: r[k] for k in ("n_used", "n_undefined", "n_poor", "n_needed", "min_cosine", "min_drop", "worst_cosine", "worst_at")})
+        self.log(f"Reconstruction: {r['n_poor']} of {G - r['n_undefined']} tumours below cosine {r['min_cosine']:g}, worst {r['worst_cosine']:.3g} "
+                 f"(tumour {r['worst_at']}); {r['n_needed']} (signature, tumour) pairs with a drop >= {r['min_drop']:g}", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

@@ -569,6 +569,60 @@ int bnmf_stability_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* 
                       const int32_t* extra_label, int X, double* point, double* factor, double* between, double* medoid, int64_t* medoid_at,
                       bnmf_stability_info* info);
 
+/* Reconstruction quality per tumour over recorded samples, on the device: how well is each tumour of the cohort the chain
+ * was run on reconstructed, and which signatures does it need?  Over the recorded samples flagged in used[] (oldest first; NULL = all),
+ * s = 1 .. S, per tumour g and mutation type k, with m the data cell as a double (for a Normal handle the fp64 data of bnmf_create_f64,
+ * negative cells included):
+ *   f_n       = (P_s[k,n] * A_s[n]) * E_s[n,g]                    bnmf_attribution's expression, the same bits
+ *   pre_0     = +0.0;  pre_{n+1} = pre_n + f_n                    n ascending
+ *   suf_{N-1} = +0.0;  suf_{n-1} = suf_n + f_n                    n descending
+ *   c    = pre_N                                                  the fit of the cell: bnmf_waic's c_s, the same bits
+ *   c_-n = pre_n + suf_n                                          the fit without factor n: no subtraction, never negative
+ *   d    = m - c
+ * Per (s, g), each sum over k ascending from +0.0 (bnmf_project's order for its fit rows):
+ *   dot = sum m c   cc = sum c c   l1 = sum |d|   sse = sum d d   dot_-n = sum m c_-n   cc_-n = sum c_-n c_-n
+ * Per g, once, in the same order:   mm = sum m m   t = sum |m|
+ *   cosv(dot, cc) = mm > 0 ? (cc > 0 ? dot / sqrt(mm * cc) : +0.0) : NaN     an empty fit explains nothing; an all-zero tumour is undefined
+ *   cos    = cosv(dot, cc);   rel_l1 = t > 0 ? l1 / t : 0.0;   rmse = sqrt(sse / (double)K)
+ *   cos_-n = A_s[n] != 0 ? cosv(dot_-n, cc_-n) : cos              an excluded factor is selected, not recomputed:
+ *   drop_n = A_s[n] != 0 ? cos - cos_-n        : +0.0             its drop is exactly +0.0
+ * The remaining exposures are NOT refitted after the removal.  The cosine does not depend on the scale of the fit, so no rescaling is
+ * needed, but a refit could recover part of the loss: drop_n is an upper bound of what removing signature n costs the tumour.
+ * Over s ascending every running mean and variance is bnmf_attribution's Welford (d = a - mu; mu = mu + d * (1 / s); M2 = M2 + d * (a - mu)),
+ * the rest are plain counts:
+ * tumour [BNMF_REC_NTUM][G]: 0 the mean of cos, 1 its variance M2 / (S - 1), 2 the smallest cos over the samples (from +inf, v < d ? v : d),
+ *   3 the mean rel_l1, 4 the mean rmse, 5 #(cos >= min_cosine) / S; a tumour with mm == 0 has NaN in rows 0, 1, 2 and 5.
+ * drop [BNMF_REC_NDROP][N*G], each row laid out n + N g: 0 the mean of drop_n, 1 its variance, 2 the mean of cos_-n, 3 #(drop_n >=
+ *   min_drop) / S, the probability that the tumour needs the signature; all rows NaN where mm == 0.
+ * series [S]: per used sample the mean cos over the defined tumours (mm > 0): the sum over g in the canonical W = 1024 order of
+ *   bnmf_attribution's series, an undefined tumour entered as +0.0, divided by the number of defined tumours; NaN if there is none.
+ * signature [BNMF_REC_NSIG][N]: 0 the number of tumours with drop row 3 >= 0.5, 1 the mean of drop row 0 (the canonical W = 64 sum over
+ *   the defined tumours ascending, divided by their number; NaN without one), 2 the largest drop row 0 over the defined tumours (NaN
+ *   without one).
+ * info: n_used = S; n_undefined = the all-zero tumours; n_poor = the defined tumours whose mean cosine is < min_cosine; n_needed = the
+ *   (n, g) with drop row 3 >= 0.5; min_cosine and min_drop as given; worst_cosine and worst_at = the smallest tumour row 0 and its g
+ *   (the first wins a tie; NaN and -1 if no tumour is defined).
+ * Only + - * /, sqrt, |.|, comparisons and whole numbers, no contraction, every sum in the order above: the bits depend on the samples,
+ * used[], the data and the two thresholds only, not on the batch size, the tiling or the form of the kernel.  Reads only the P, E and A
+ * rings and the data; works for every likelihood and prior; draws no random number, consumes none of the chain's streams and is
+ * read-only for the chain.  bnmf_reconstruction_at: the n_samples iterations that end at end_iter; the range rule, used[] and BNMF_ESIZE
+ * as for bnmf_attribution_at; bnmf_reconstruction(h, n, ...) is bnmf_reconstruction_at(h, iter, n, ...).  Refused before any device work:
+ * a null info, a used[] value other than 0 / 1 (the index named), a min_cosine or min_drop that is NaN or infinite with BNMF_EINVAL; fewer
+ * than 2 used samples with BNMF_ESIZE; window = 0, a poisoned handle or nothing recorded with BNMF_ESTATE. */
+#define BNMF_REC_NTUM  6         /* tumour rows: mean cos, its variance, smallest cos, mean rel_l1, mean rmse, share of samples with cos >= min_cosine */
+#define BNMF_REC_NDROP 4         /* drop rows: mean drop, its variance, mean leave-one-out cosine, share of samples with drop >= min_drop */
+#define BNMF_REC_NSIG  3         /* signature rows: tumours that need it, mean of the mean drop, largest mean drop */
+typedef struct { int32_t n_used, n_undefined; int64_t n_poor, n_needed, worst_at /* g; -1 if none */; double min_cosine, min_drop, worst_cosine; }
+    bnmf_reconstruction_info;
+int bnmf_reconstruction(bnmf_handle*, int last_n, const int32_t* used, double min_cosine, double min_drop,
+                        double* tumour    /* [BNMF_REC_NTUM][G]; may be NULL */,
+                        double* drop      /* [BNMF_REC_NDROP][N*G], each row laid out as E; may be NULL */,
+                        double* series    /* [S]; may be NULL */,
+                        double* signature /* [BNMF_REC_NSIG][N]; may be NULL */,
+                        bnmf_reconstruction_info* info);
+int bnmf_reconstruction_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double min_cosine, double min_drop, double* tumour,
+                           double* drop, double* series, double* signature, bnmf_reconstruction_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

@@ -243,6 +243,42 @@ bayesNMF_sampler_hip <- R6::R6Class(
       if (prob) out$prob <- array(r$prob, c(K, N, G))
       out
     },
+    # How well is every tumour of the cohort reconstructed, and which signatures does it need?  On the device
+    # (bnmf_reconstruction_at; not in the reference): over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC),
+    # restricted to idx, every sample gives per tumour the cosine between its data and its fit, the relative L1 error and the RMSE, and
+    # per signature the cosine of the fit without it.  The remaining exposures are not refitted after the removal, so the drop is an
+    # upper bound of what removing the signature costs the tumour.  list(tumour (6 x G: mean, variance and smallest cosine over the
+    # samples, mean relative L1 error, mean RMSE, share of samples with cosine >= min_cosine; NaN for an all-zero tumour) with its rows
+    # as cosine, cosine_var, min_cosine_sample, rel_l1, rmse, p_good; drop (4 x N x G: mean and variance of the drop, mean
+    # leave-one-out cosine, share of samples with drop >= min_drop) with its rows as drop_mean, drop_var, loo_cosine, p_needed (N x G);
+    # series (S), signature (3 x N: tumours that need it, mean and largest mean drop), n_used, n_undefined, n_poor, n_needed,
+    # min_cosine, min_drop, worst_cosine, worst_at (1-based tumour; NA if none)).
+    get_reconstruction = function(end_iter = self$state$iter, n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter),
+                                  idx = "MAP_idx", min_cosine = 0.9, min_drop = 0.01) {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      r <- .Call("C_bnmf_reconstruction", self$handle, as.integer(end_iter), as.integer(n_samples), used, as.double(min_cosine),
+                 as.double(min_drop), c(K, G, N))
+      drop <- aperm(array(r$drop, c(N, G, 4)), c(3, 1, 2))
+      out <- list(tumour = t(r$tumour), drop = drop, series = r$series, signature = t(r$signature),
+                  cosine = r$tumour[, 1], cosine_var = r$tumour[, 2], min_cosine_sample = r$tumour[, 3], rel_l1 = r$tumour[, 4],
+                  rmse = r$tumour[, 5], p_good = r$tumour[, 6], drop_mean = matrix(r$drop[, 1], N, G), drop_var = matrix(r$drop[, 2], N, G),
+                  loo_cosine = matrix(r$drop[, 3], N, G), p_needed = matrix(r$drop[, 4], N, G), n_used = r$n_used,
+                  n_undefined = r$n_undefined, n_poor = r$n_poor, n_needed = r$n_needed, min_cosine = r$min_cosine, min_drop = r$min_drop,
+                  worst_cosine = r$worst_cosine, worst_at = if (r$worst_at < 0) NA_integer_ else as.integer(r$worst_at) + 1L)
+      message(sprintf("Reconstruction: %d of %d tumours below cosine %g, worst %.3g; %d (signature, tumour) pairs with a drop >= %g",
+                      as.integer(r$n_poor), G - r$n_undefined, r$min_cosine, r$worst_cosine, as.integer(r$n_needed), r$min_drop))
+      out
+    },
     # Does the activity of a signature differ between groups of tumours?  On the device (bnmf_contrast_at; not in the reference): groups
     # is a vector of G labels, one per tumour (NA: the tumour is left out), numbered in order of first appearance.  Over iterations
     # end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample gives one draw of each group's mean

@@ -490,6 +490,62 @@ SEXP C_bnmf_attribution_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, S
   UNPROTECT(1);
   return out;
 }
+/* Reconstruction quality per tumour over recorded samples on the device (bnmf_reconstruction / bnmf_reconstruction_at):
+ * C_bnmf_reconstruction(ptr, end_iter (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL =
+ * all), min_cosine, min_drop, dims c(K,G,N)) -> list(n_used, n_undefined, n_poor, n_needed, min_cosine, min_drop, worst_cosine, worst_at
+ * (0-based tumour, -1 = none), tumour (G x 6: one column per row of the C output - mean cosine, its variance, smallest cosine, mean
+ * relative L1 error, mean RMSE, share of samples with cosine >= min_cosine), drop (N G x 4: mean drop, its variance, mean leave-one-out
+ * cosine, share of samples with drop >= min_drop - each laid out as E), series (S: the cohort's mean cosine per used sample), signature
+ * (N x 3: tumours that need the signature, mean and largest mean drop)) over iterations end_iter - n_samples + 1 ... end_iter.
+ * C_bnmf_reconstruction_at: the same with end_iter required */
+/* the result list with its arrays allocated, and the flags of used; returned unprotected */
+static SEXP rec_alloc(SEXP n_samples, SEXP used, SEXP dims, int32_t** u) {
+  const int n = INTEGER(n_samples)[0];
+  const int* d = INTEGER(dims);
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  *u = lgl_flags(used, n);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_undefined", "n_poor", "n_needed", "min_cosine", "min_drop", "worst_cosine", "worst_at", "tumour", "drop",
+                              "series", "signature"};
+  SEXP out = PROTECT(named_list(12, nms));
+  SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, d[1], BNMF_REC_NTUM));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, d[2] * d[1], BNMF_REC_NDROP));
+  SET_VECTOR_ELT(out, 10, Rf_allocVector(REALSXP, S));
+  SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, d[2], BNMF_REC_NSIG));
+  UNPROTECT(1);
+  return out;
+}
+static void rec_finish(SEXP out, const bnmf_reconstruction_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_undefined));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarReal((double)info->n_poor)); SET_VECTOR_ELT(out, 3, Rf_ScalarReal((double)info->n_needed));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarReal(info->min_cosine)); SET_VECTOR_ELT(out, 5, Rf_ScalarReal(info->min_drop));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarReal(info->worst_cosine)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal((double)info->worst_at));
+}
+SEXP C_bnmf_reconstruction(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP min_cosine, SEXP min_drop, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(rec_alloc(n_samples, used, dims, &u));
+  bnmf_reconstruction_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_reconstruction(get_handle(ptr), INTEGER(n_samples)[0], u, REAL(min_cosine)[0], REAL(min_drop)[0], map_buf(out, 8), map_buf(out, 9), map_buf(out, 10),
+                            map_buf(out, 11), &info));
+  else
+    chk(bnmf_reconstruction_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(min_cosine)[0], REAL(min_drop)[0], map_buf(out, 8),
+                               map_buf(out, 9), map_buf(out, 10), map_buf(out, 11), &info));
+  rec_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_reconstruction_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP min_cosine, SEXP min_drop, SEXP dims) {
+  int32_t* u = NULL;
+  SEXP out = PROTECT(rec_alloc(n_samples, used, dims, &u));
+  bnmf_reconstruction_info info;
+  chk(bnmf_reconstruction_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, REAL(min_cosine)[0], REAL(min_drop)[0], map_buf(out, 8),
+                             map_buf(out, 9), map_buf(out, 10), map_buf(out, 11), &info));
+  rec_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Group contrasts of exposures over recorded samples on the device (bnmf_contrast / bnmf_contrast_at): C_bnmf_contrast(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), groups (integer length G: the
  * 0-based label of every tumour, -1 or NA = left out), min_load, credible_interval (<= 0: no interval), want_series (logical),
@@ -1052,6 +1108,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_regress", (DL_FUNC)&C_bnmf_regress, 9}, {"C_bnmf_regress_at", (DL_FUNC)&C_bnmf_regress_at, 9},
   {"C_bnmf_coactivity", (DL_FUNC)&C_bnmf_coactivity, 9}, {"C_bnmf_coactivity_at", (DL_FUNC)&C_bnmf_coactivity_at, 9},
   {"C_bnmf_stability", (DL_FUNC)&C_bnmf_stability, 8}, {"C_bnmf_stability_at", (DL_FUNC)&C_bnmf_stability_at, 8},
+  {"C_bnmf_reconstruction", (DL_FUNC)&C_bnmf_reconstruction, 7}, {"C_bnmf_reconstruction_at", (DL_FUNC)&C_bnmf_reconstruction_at, 7},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
