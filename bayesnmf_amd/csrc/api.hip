@@ -235,6 +235,7 @@ struct bnmf_handle {
   double* dScal = nullptr;              // [BNMF_ID_MAX] broadcast scalars of bnmf_set_array (hyper-prior values given as one number)
   unsigned* dDrawOwn = nullptr; unsigned draw_seq = 0;   // k_draw: owner word per column of P, launch sequence number (kernels.h).  draw_seq is NOT part of
                                        // Pipe: it only has to differ from launch to launch, so bnmf_init leaves it running; bnmf_load_state zeroes it with dDrawOwn
+  bool draw_fixed_ok = true;           // BNMF_DRAWFIXED (read at bnmf_create): 0 = k_draw always in its dynamic form (sweep.h draw_fixed_form)
   int dbg_draw_no_p = 0;               // BNMF_DEBUG_DRAW_NO_P (tests): the P workgroups of k_draw leave without claiming their columns
   int dbg_main_delay_us = 0;           // BNMF_DEBUG_MAIN_DELAY_US (tests): a delay kernel in front of the main stream's kernels of every sweep
   int dbg_allside_delay_us = 0;        // BNMF_DEBUG_ALLSIDE_DELAY_US (tests): a delay kernel in front of EVERY kernel launched on the two side streams
@@ -892,6 +893,7 @@ static int create_small(bnmf_handle* h, const Switches& sw) {
   h->gate_forced = sw.gate;
   h->mh.side_main = sw.mh_side_main; h->mh.side_tail = sw.mh_side_tail;
   h->dbg_draw_no_p = sw.draw_no_p ? 1 : 0;
+  h->draw_fixed_ok = sw.draw_fixed;
   h->dbg_main_delay_us = sw.main_delay_us; h->dbg_allside_delay_us = sw.allside_delay_us; h->dbg_side_delay_us = sw.side_delay_us;
   {
     // A lane that polls inside a main-stream kernel for a side-stream kernel deadlocks (until its bound) when dispatches cannot

@@ -112,13 +112,15 @@ BNMF_DEV double ld_ag(const double* p) { return __hip_atomic_load(p, __ATOMIC_RE
 // wait for P); rgamma(s, shape, rate) is that value divided by the rate, so the result is the same bits.  lut: ralpha_fast's table.
 // It also carries the element's hyper-prior values and previous Alpha: loaded before the wait, not behind it.
 struct HyperPre { double g, hB, hC, hD, al_old; };
-template <int SIDE, bool RETRY_PRIO = false>
+// PRIOR >= 0: the prior is a constant of the instantiation (k_draw's fixed form: the other priors' code is not emitted).  LATE: hB, hC, hD
+// are left out — the caller loads them with hyper_late behind its wait, so that they are not carried across it.
+template <int SIDE, bool RETRY_PRIO = false, int PRIOR = -1, bool LATE = false>
 BNMF_DEV HyperPre hyper_pre(const Dev& d, int e, uint32_t t) {
   const HRef &hA = SIDE ? d.hA_e : d.hA_p, &hB = SIDE ? d.hB_e : d.hB_p;
-  HyperPre p{0.0, hy(hB, e), 0.0, 0.0, 0.0};
-  if (d.prior == BNMF_GAMMA) {
+  HyperPre p{0.0, LATE ? 0.0 : hy(hB, e), 0.0, 0.0, 0.0};
+  if ((PRIOR >= 0 ? PRIOR : d.prior) == BNMF_GAMMA) {
     const HRef &hC = SIDE ? d.hC_e : d.hC_p, &hD = SIDE ? d.hD_e : d.hD_p;
-    p.hC = hy(hC, e); p.hD = hy(hD, e);
+    if (!LATE) { p.hC = hy(hC, e); p.hD = hy(hD, e); }
     p.al_old = slot<SIDE>(d, SIDE ? d.Alpha_e : d.Alpha_p, t - 1)[e];
     Stream s(d.k0, d.k1, SIDE ? BNMF_V_BETA_E : BNMF_V_BETA_P, (uint32_t)e, t);
     p.g = rgamma<RETRY_PRIO>(s, hy(hA, e) + p.al_old, 1.0);
@@ -127,6 +129,10 @@ BNMF_DEV HyperPre hyper_pre(const Dev& d, int e, uint32_t t) {
   Stream s(d.k0, d.k1, SIDE ? BNMF_V_LAMBDA_E : BNMF_V_LAMBDA_P, (uint32_t)e, t);
   p.g = rgamma<RETRY_PRIO>(s, hy(hA, e) + 1.0, 1.0);
   return p;
+}
+template <int SIDE>
+BNMF_DEV void hyper_late(const Dev& d, int e, HyperPre& p) {   // Gamma prior: what hyper_pre<.., LATE = true> left out
+  p.hB = hy(SIDE ? d.hB_e : d.hB_p, e); p.hC = hy(SIDE ? d.hC_e : d.hC_p, e); p.hD = hy(SIDE ? d.hD_e : d.hD_p, e);
 }
 template <int SIDE, bool PRE = false>
 BNMF_DEV void hyper_elem(const Dev& d, int e, uint32_t t, double v, double* rec0 = nullptr, double* rec1 = nullptr, const HyperPre& pre = HyperPre{},
@@ -174,10 +180,10 @@ BNMF_DEV void hyper_elem(const Dev& d, int e, uint32_t t, double v, double* rec0
   }
 }
 // prior draw of an element of P / E: R/sample_Pn.R:12-30, R/sample_En.R:12-30
-template <int SIDE>
+template <int SIDE, int PRIOR = -1 /* >= 0: a constant of the instantiation (k_draw's fixed form) */>
 BNMF_DEV double prior_draw(const Dev& d, int e, uint32_t t) {
   Stream s(d.k0, d.k1, SIDE ? BNMF_V_E : BNMF_V_P, (uint32_t)e, t);
-  if (d.prior == BNMF_GAMMA) return rgamma(s, slot<SIDE>(d, SIDE ? d.Alpha_e : d.Alpha_p, t)[e], slot<SIDE>(d, SIDE ? d.Beta_e : d.Beta_p, t)[e]);
+  if ((PRIOR >= 0 ? PRIOR : d.prior) == BNMF_GAMMA) return rgamma(s, slot<SIDE>(d, SIDE ? d.Alpha_e : d.Alpha_p, t)[e], slot<SIDE>(d, SIDE ? d.Beta_e : d.Beta_p, t)[e]);
   if (d.prior == BNMF_EXPONENTIAL) return rexp(s, slot<SIDE>(d, SIDE ? d.Lam_e : d.Lam_p, t)[e]);
   return rtnorm0(s, slot<SIDE>(d, SIDE ? d.Mu_e : d.Mu_p, t)[e], dsqrt(slot<SIDE>(d, SIDE ? d.Sig_e : d.Sig_p, t)[e]));
 }
@@ -548,6 +554,222 @@ __global__ __launch_bounds__(DW) void k_draw(Dev d, uint32_t t, RecDst rec, Side
     e_role();                                             // P is complete: runs through
   }
   side_done(ed, tid);
+}
+
+// ---- k_draw_fixed: k_draw with its geometry at compile time (after zalloc_sort.h's ZSFixed) ----
+// k_draw above reads K, N, the workgroup width, the prior, the ring pointers, zsumk_accum and the fixed columns at run time, and is kept word for
+// word: a shared template body changed its code (SGPR spills 267 -> 341, or another order of its argument loads), and every shape but the
+// headline one runs it.  DrawFixed: K, N and the width are constants, the prior is Gamma (the other priors' code is not emitted), REC: every ring
+// pointer the fused recording sets (rec.P, .E, .A, .R, rec_next.pp[2], .pp[3]) is non-null (false: they are tested); zsumk_accum is off, no column
+// of P is fixed, N G fits 31 bits.  The host decides (sweep.h draw_fixed_form).  k_draw's operations in k_draw's order, the same bits: A CHANGE
+// OF ONE BODY IS A CHANGE OF THE OTHER (tests/test_gpu_draw_fixed.py compares them).
+template <int K_, int N_, int BW_, bool GAMMA_, bool REC_>
+struct DrawFixed {
+  static_assert(GAMMA_ /* the only prior built */ && K_ >= 1 && K_ <= DW && N_ >= 1 && BW_ >= 64 && BW_ <= DW && BW_ % 64 == 0, "DrawFixed: geometry");
+  static constexpr bool rec = REC_; static constexpr int K = K_, N = N_, BW = BW_;
+};
+using DrawFixHead = DrawFixed<96, 20, 896, true, true>;   // the metric configuration with recording on
+template <class FX>
+BNMF_DEV void draw_fixed_body(Dev d, uint32_t t, RecDst rec, SideDone pd, SideWait pw, RecDst rec_next, SideDone ed, unsigned* own, unsigned seq, int no_p) {
+  constexpr bool RECC = FX::rec;                          // the ring pointers are known to be set
+  constexpr int PRIOR = BNMF_GAMMA;
+  constexpr bool LATE = true;                             // hB, hC, hD of the hyper sweep are loaded behind the wait for P (hyper_late)
+  __shared__ double Pn[DW];
+  __shared__ double lutS[3 * ALUT_N];                     // E workgroups: ralpha_fast's table (its look-ups are dependent loads inside the Newton and attempt loops)
+  __shared__ int jobS;
+  constexpr int N = FX::N, K = FX::K, BW = FX::BW;
+  const int tid = threadIdx.x;
+  // column n of P by this workgroup (sample_Pn_poisson R/sample_Pn.R:98-120), Psum[n], and its share of the flag pd
+  auto p_column = [&](int n) __attribute__((always_inline)) {
+    const double a_n = d.A[n];
+    const double Esum = d.Esum[n];
+    for (int k = tid; k < K; k += BW) {
+      const int e = k + K * n;
+      double x;
+      if (a_n == 0.0) x = prior_draw<0, PRIOR>(d, e, t);
+      else {
+        const double shape = slot<0>(d, d.Alpha_p, t)[e] + (double)d.ZsumG[e], rate = slot<0>(d, d.Beta_p, t)[e] + a_n * Esum;
+        Stream s(d.k0, d.k1, BNMF_V_P, (uint32_t)e, t);
+        x = rgamma(s, shape, rate);
+      }
+      d.P[e] = x;
+      if (RECC || rec.P) rec.P[e] = x;
+      d.ZsumG[e] = 0;
+      if (k < DW) Pn[k] = x;
+    }
+    if ((RECC || rec.A) && tid == 0) rec.A[n] = a_n;
+    if ((RECC || rec.R) && tid == 0 && n == 0) *rec.R = (double)*d.R;
+    __syncthreads();
+    if (tid < 64) {
+      double acc = 0.0;
+      for (int k = tid; k < K; k += 64) acc = acc + (k < DW ? Pn[k] : d.P[k + K * n]);
+      acc = wave_tree64(acc);
+      if (tid == 0) st_wt(&d.Psum[n], acc);
+    }
+    side_done(pd, tid);
+  };
+  auto take = [&](int n) __attribute__((always_inline)) -> bool {                        // one lane: true if column n is now this workgroup's
+    return __hip_atomic_exchange(own + n, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq;
+  };
+  if ((int)blockIdx.x < N) {
+    if (no_p) return;
+    if (tid == 0) jobS = take((int)blockIdx.x) ? (int)blockIdx.x : -1;
+    __syncthreads();
+    if (jobS >= 0) p_column(jobS);
+    return;
+  }
+  // ---------------- E workgroups.  Round 5: no workgroup barrier after the head of the kernel.  Stamps of the waves (tools/drstamps.py) showed
+  // the barrier behind the wait for P costing every wave 2.4 us (the workgroup's slowest wave: a second pass of a rejection loop), and
+  // the kernel ending 6 us behind its median wave (Alpha: 2, 3 or 4 passes).  Now a wave waits for P by itself, the Alpha draws of a wave
+  // take two passes (ralpha_fast_wave), and a column of P that nobody has taken is drawn by ONE WAVE (p_column_wave).
+  const int lane = tid & 63;
+  // column n of P by one wavefront: p_column's operations in p_column's order (lane l takes rows l, l + 64, ...; Psum: the canonical W = 64 sum)
+  auto p_column_wave = [&](int n) __attribute__((always_inline)) {
+    const double a_n = d.A[n];
+    const double Esum = d.Esum[n];
+    double acc = 0.0;
+    for (int k = lane; k < K; k += 64) {                  // (fixed form, K = 96: two trips, the second for half the lanes)
+      const int e = k + K * n;
+      double x;
+      if (a_n == 0.0) x = prior_draw<0, PRIOR>(d, e, t);
+      else {
+        const double shape = slot<0>(d, d.Alpha_p, t)[e] + (double)d.ZsumG[e], rate = slot<0>(d, d.Beta_p, t)[e] + a_n * Esum;
+        Stream s(d.k0, d.k1, BNMF_V_P, (uint32_t)e, t);
+        x = rgamma(s, shape, rate);
+      }
+      d.P[e] = x;
+      if (RECC || rec.P) rec.P[e] = x;
+      d.ZsumG[e] = 0;
+      acc = acc + x;
+    }
+    if ((RECC || rec.A) && lane == 0) rec.A[n] = a_n;
+    if ((RECC || rec.R) && lane == 0 && n == 0) *rec.R = (double)*d.R;
+    acc = wave_tree64(acc);
+    if (lane == 0) st_wt(&d.Psum[n], acc);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's stores have left (side_done's hand-off, for one wave)
+    if (lane == 0 && pd.flag) {
+      const unsigned old = __hip_atomic_fetch_add(pd.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old == pd.nblk - 1) {
+        __hip_atomic_store(pd.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(pd.flag, pd.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  };
+  // lane 0 of the wave waits for the flag pd; after a while it looks for a column of P that nobody has taken (see the head of the
+  // kernel).  Returns the column this wave has to draw, or -1: P is complete.
+  auto wait_p = [&]() __attribute__((always_inline)) -> int {
+    int job = -1;
+    if (lane == 0) {
+      unsigned spins = 0;
+      while (__hip_atomic_load(pw.f0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pw.epoch) {
+        __builtin_amdgcn_s_sleep(1);
+        if (++spins > (1u << 24)) { __hip_atomic_store(pw.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        if ((spins & 7u) == 0u) {
+          for (int c = 0; c < N && job < 0; ++c)
+            if (__hip_atomic_load(own + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq && take(c)) job = c;
+          if (job >= 0) break;
+        }
+      }
+    }
+    return __builtin_amdgcn_readfirstlane(job);
+  };
+  // the element of this lane; the fixed form indexes in 32 bits (the host has checked that N G + DW fits) and takes n by a constant divisor
+  const int e = ((int)blockIdx.x - N) * BW + tid;
+  const bool live = (unsigned)e < (unsigned)d.lenE;
+  // the Alpha table: requested at the head of the kernel together with the element's own values; the one barrier of the E role
+  {                                                       // a fixed number of trips: every request is out before the first store
+    constexpr int TR = (3 * ALUT_N + FX::BW - 1) / FX::BW;
+    double v[TR];
+#pragma unroll
+    for (int j = 0; j < TR; ++j) { const int i = tid + j * FX::BW; v[j] = i < 3 * ALUT_N ? g_alut[i] : 0.0; }
+#pragma unroll
+    for (int j = 0; j < TR; ++j) { const int i = tid + j * FX::BW; if (i < 3 * ALUT_N) lutS[i] = v[j]; }
+  }
+  __syncthreads();
+  // where slots t and t + 1 of the E-side prior arrays begin, once (slot<1> works it out at every use)
+  const size_t so_t = (size_t)(t & 1u) * d.lenE, so_n = d.lenE - so_t;
+  // the E role of the wave; returns a column of P to draw first (then the role is run again from its start: the same streams, the same
+  // bits — so that no draw has to be kept in registers across the column's code), or -1 when done
+  auto e_role = [&]() __attribute__((always_inline)) -> int {
+    DRSTAMP(0);
+#ifdef ZSLIGHT
+    unsigned long long stA = 0;
+#endif
+    double x = 0.0, a_n = 0.0;
+    bool scaled = false;                                 // x is Gamma(shape, 1) and still has to be divided by the rate
+    double base = 0.0;                                   // the rate without its Psum term
+    HyperPre hpre{};                                     // Gamma(shape, 1) part of the hyper sweep's first draw and the element's hyper-prior values (need nothing from this iteration)
+    int n = 0;
+    if (live) {
+      n = (int)((unsigned)e % (unsigned)N);
+      a_n = d.A[n];
+      if (a_n == 0.0) x = prior_draw<1, PRIOR>(d, (int)e, t);
+      else {
+        const double shape = (d.Alpha_e + so_t)[e] + (double)d.ZsumK[e];
+        base = (d.Beta_e + so_t)[e];
+        Stream s(d.k0, d.k1, BNMF_V_E, (uint32_t)e, t);
+        x = rgamma<true>(s, shape, 1.0);
+        scaled = true;
+      }
+#ifdef ZSLIGHT
+      stA = __builtin_amdgcn_s_memtime();
+#endif
+      hpre = hyper_pre<1, true, PRIOR, LATE>(d, (int)e, t + 1);
+    }
+    DRSTAMP(1);
+    const int job = wait_p();
+    if (job >= 0) return job;
+    DRSTAMP(2);
+    double tau = 0.0;
+    if (live) {
+      if (LATE) hyper_late<1>(d, (int)e, hpre);           // requested together with Psum, not carried across the wait
+      if (scaled) {
+        const double rate = base + a_n * ld_ag(&d.Psum[n]);
+        // rgamma(shape, rate) ends in `g / rate`; rgamma(shape, 1.0) returned g / 1.0 = g
+        x = x / rate;
+      }
+      d.E[e] = x;
+      if (RECC || rec.E) rec.E[e] = x;
+    }
+    DRSTAMP(3);
+    // the E-side hyper sweep of t + 1 (hyper_elem<1, true>'s operations; the Alpha draws of the wave side by side)
+    {
+      if (live) {
+        const double b = hpre.g / (hpre.hB + x);                                                    // sample_Beta_En  :339-345
+        st_wt(&(d.Beta_e + so_n)[e], b);
+        if (RECC || rec_next.pp[3]) rec_next.pp[3][e] = b;
+        tau = (hpre.hD - dlog(clamp_tiny(b))) - dlog(clamp_tiny(x));
+      }
+      const double al = ralpha_fast_wave(live, d.k0, d.k1, BNMF_V_ALPHA_E, (uint32_t)e, t + 1, hpre.hC, tau, hpre.al_old, lutS);   // sample_Alpha_Eng :382-397
+      if (live) {
+        st_wt(&(d.Alpha_e + so_n)[e], al);
+        if (RECC || rec_next.pp[2]) rec_next.pp[2][e] = al;
+      }
+    }
+#ifdef ZSPROF
+    DRSTAMP(4);
+    if (live && lane == 0 && (e >> 6) < DRPROF_W - 1) {
+      unsigned long long* o = &g_drprof[8 * (e >> 6)];
+#ifdef ZSLIGHT
+      o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = st4; o[5] = stA; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = 1ull;   // absolute stamps of the last launch
+#else
+      o[0] += st1 - st0; o[1] += st2 - st1; o[2] += st3 - st2; o[3] += st4 - st3; o[5] += st4 - st0; o[6] = st0; o[7] += 1ull;
+#endif
+    }
+#endif
+    return -1;
+  };
+  int job = e_role();
+  if (__builtin_expect(job >= 0, 0)) {                    // never taken under in-order dispatch
+    do { p_column_wave(job); job = wait_p(); } while (job >= 0);
+    e_role();                                             // P is complete: runs through
+  }
+  side_done(ed, tid);
+}
+// the fixed form: a template, so that it is emitted behind every plain kernel and k_draw keeps its place in the code object (regress.h)
+template <class FX>
+__global__ __launch_bounds__(FX::BW) void k_draw_fixed(Dev d, uint32_t t, RecDst rec, SideDone pd, SideWait pw, RecDst rec_next, SideDone ed, unsigned* own /* [N] */, unsigned seq, int no_p) {
+  draw_fixed_body<FX>(d, t, rec, pd, pw, rec_next, ed, own, seq, no_p);
 }
 
 // log-prior of column n of P_t under iteration t's prior parameters: canonical W = 64 over k, as in k_pdraw

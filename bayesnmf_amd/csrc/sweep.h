@@ -768,6 +768,17 @@ static int ensure_draw_bw(bnmf_handle* h) {
   if (const char* e = getenv("BNMF_DRAWBW")) { const int v = atoi(e); if (v >= 64 && v <= DW && v % 64 == 0) h->draw_bw = v; }   // diagnostics
   return 0;
 }
+// May this launch take the geometry-fixed form of k_draw (kernels.h DrawFixed)?  Everything FX turns into a constant is checked against what the
+// dynamic form would read from the same arguments: K, N, the width, the Gamma prior, every ring pointer of the fused recording, no
+// accumulating ZsumK, no fixed column; and the element index must fit the form's 32 bits.  BNMF_DRAWFIXED=0 (read at bnmf_create): never.
+template <class FX>
+static bool draw_fixed_form(const bnmf_handle* h, const RecDst& r, const RecDst& rn) {
+  const Dev& d = h->dev;
+  const bool rec_set = r.P && r.E && r.A && r.R && rn.pp[2] && rn.pp[3];
+  return h->draw_fixed_ok && d.K == FX::K && d.N == FX::N && h->draw_bw == FX::BW && d.prior == BNMF_GAMMA && !h->cfg.learning_rank &&
+         rec_set == FX::rec && (FX::rec || !(r.P || r.E || r.A || r.R || rn.pp[2] || rn.pp[3])) && !d.zsumk_accum && !d.fixedP &&
+         d.lenE <= (size_t)INT32_MAX - DW;
+}
 // The head of the two-kernel sweeps (fixed rank and rank learning): k_pdraw, its completion as a stop event (ev_p: no marker packet on the
 // main stream)
 static void launch_pdraw_split(bnmf_handle* h, uint32_t t, bool rec, bool poll) {
@@ -830,9 +841,16 @@ static int sweep(bnmf_handle* h, int row, Timer& tm) {
       if (int rc = ensure_draw_bw(h)) return rc;
       const unsigned bw = (unsigned)h->draw_bw;
       const unsigned nE = (unsigned)(((size_t)h->cfg.N * h->cfg.G + bw - 1) / bw);
-      hipExtLaunchKernelGGL(k_draw, dim3(h->cfg.N + nE), dim3(bw), 0, h->stream, nullptr, h->ev_draw, 0, h->dev, t, rec_at(h, t, rec),
-                            SideDone{h->dFlags + 5, h->dFlags + 6, (unsigned)h->cfg.N, t}, SideWait{h->dFlags + 6, h->dFlags + 6, t, h->dErr},
-                            rec_at(h, t + 1, rec), SideDone{h->dFlags, h->dFlags + 1, nE, t + 1}, h->dDrawOwn, ++h->draw_seq, h->dbg_draw_no_p);
+      const RecDst r = rec_at(h, t, rec), rn = rec_at(h, t + 1, rec);
+      auto go = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3(h->cfg.N + nE), dim3(bw), 0, h->stream, nullptr, h->ev_draw, 0, h->dev, t, r,
+                              SideDone{h->dFlags + 5, h->dFlags + 6, (unsigned)h->cfg.N, t}, SideWait{h->dFlags + 6, h->dFlags + 6, t, h->dErr},
+                              rn, SideDone{h->dFlags, h->dFlags + 1, nE, t + 1}, h->dDrawOwn, ++h->draw_seq, h->dbg_draw_no_p);
+      };
+      if (draw_fixed_form<DrawFixHead>(h, r, rn)) {          // the metric configuration with recording on: K, N, the width, the prior and the ring pointers as constants
+        assert((size_t)h->cfg.N * h->cfg.G == h->dev.lenE && h->dev.lenE + DW <= (size_t)INT32_MAX);   // its element index has 32 bits
+        go(k_draw_fixed<DrawFixHead>);
+      } else go(k_draw);
       launch_side_merged(h, t + 1, tm);
       break;
     }

@@ -22,6 +22,7 @@ struct Switches {
   int gate = -1, serial = -1;          // BNMF_GATE, BNMF_SERIAL: -1 unset, else 0 / 1
   bool mh_side_main = true, mh_side_tail = true;   // BNMF_MHSIDE, BNMF_MHSIDETAIL
   bool draw_no_p = false;              // BNMF_DEBUG_DRAW_NO_P
+  bool draw_fixed = true;              // BNMF_DRAWFIXED=0: never the geometry-fixed form of k_draw (sweep.h draw_fixed_form)
   int main_delay_us = 0, allside_delay_us = 0, side_delay_us = 0;   // BNMF_DEBUG_{MAIN,ALLSIDE,SIDE}_DELAY_US, 0..20000
   bool rank_dbg = false, zt_dbg = false;   // BNMF_RANKDBG, BNMF_ZTDBG (set = on): the diagnostic buffers
   bool z_eager = false;                // BNMF_ZEAGER
@@ -45,7 +46,7 @@ struct Switches {
     s.gate = env_set("BNMF_GATE") ? (int)env_flag("BNMF_GATE", false) : -1;
     s.serial = env_set("BNMF_SERIAL") ? (int)env_flag("BNMF_SERIAL", false) : -1;
     s.mh_side_main = env_flag("BNMF_MHSIDE", true); s.mh_side_tail = env_flag("BNMF_MHSIDETAIL", true);
-    s.draw_no_p = env_flag("BNMF_DEBUG_DRAW_NO_P", false);
+    s.draw_no_p = env_flag("BNMF_DEBUG_DRAW_NO_P", false); s.draw_fixed = env_flag("BNMF_DRAWFIXED", true);
     s.main_delay_us = env_int("BNMF_DEBUG_MAIN_DELAY_US", 0, 0, 20000);
     s.allside_delay_us = env_int("BNMF_DEBUG_ALLSIDE_DELAY_US", 0, 0, 20000);
     s.side_delay_us = env_int("BNMF_DEBUG_SIDE_DELAY_US", 0, 0, 20000);
