@@ -43,6 +43,7 @@
 #include "coactivity.h"
 #include "stability.h"
 #include "reconstruction.h"
+#include "similarity.h"
 
 using namespace bnmf;
 

@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h and reconstruction.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h and similarity.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1437,6 +1437,105 @@ static int reconstruction_impl(bnmf_handle* h, const char* fn, Range r, const in
   return 0;
 }
 
+// Similarity of tumours over the samples of r that used[] flags (similarity.h): the member list and the row list are made
+// here; k_map_colsum and k_sim_norm run once over the range; then per band of rows k_sim_pairs leaves mean, variance and p_similar of
+// every (row, member) in the scratch, k_sim_select takes the row's neighbours, typicality and degree, and the rows that are queries are
+// copied out.  The row list is the member list, or, when only dense is asked for, the queries alone.  The outputs by tumour and the info
+// fields are similarity_finish's.
+static_assert(SM_NROW == BNMF_SIM_NNROW && SM_NROW == BNMF_SIM_NDROW && SM_NROW == BNMF_SIM_NTUM && SM_MAX_K == BNMF_SIM_MAX_K, "similarity.h and bnmf.h disagree");
+static constexpr size_t SIM_SCRATCH_CAP = (size_t)256 << 20;    // bytes of the call's scratch: the norms and a band's results
+static int similarity_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, const int32_t* query, int Q, int top_k,
+                           double min_cosine, int32_t* neighbour_at, double* neighbour, double* dense, double* tumour, bnmf_similarity_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members, place(G, -1);                  // place[g]: g's position in the member list
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) { place[g] = (int)members.size(); members.push_back(g); }
+  }
+  const int m = (int)members.size();
+  if (Q < 0) return fail(BNMF_EINVAL, "%s: Q = %d is negative", fn, Q);
+  if (Q > 0 && !query) return fail(BNMF_EINVAL, "%s: Q = %d but query is null", fn, Q);
+  for (int q = 0; q < Q; ++q) {
+    if (query[q] < 0 || query[q] >= G) return fail(BNMF_EINVAL, "%s: query[%d] = %d is outside 0..%d", fn, q, (int)query[q], G - 1);
+    if (place[query[q]] < 0) return fail(BNMF_EINVAL, "%s: query[%d] = %d is a tumour that include[] leaves out", fn, q, (int)query[q]);
+  }
+  if (top_k < 0 || top_k > BNMF_SIM_MAX_K) return fail(BNMF_EINVAL, "%s: top_k = %d is outside 0..%d", fn, top_k, BNMF_SIM_MAX_K);
+  if (!std::isfinite(min_cosine)) return fail(BNMF_EINVAL, "%s: min_cosine = %g is not a finite number", fn, min_cosine);
+  const int S = (int)slots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance of the cosines needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (m < 2) return fail(BNMF_ESIZE, "%s: %d included tumour%s, a pair needs 2", fn, m, m == 1 ? "" : "s");
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  const bool all = !(top_k == 0 && !tumour && Q > 0);       // the pass over all pairs
+  std::vector<int> rows(all ? m : Q);
+  for (size_t i = 0; i < rows.size(); ++i) rows[i] = all ? (int)i : place[query[i]];
+  const int nrows = (int)rows.size(), k = top_k;
+  const size_t fixed = ((size_t)S * N + (size_t)S * m) * sizeof(double), per = (size_t)SM_NROW * m * sizeof(double);   // the norms; a row of a band
+  long long want = (long long)std::max<size_t>(1, (SIM_SCRATCH_CAP > fixed ? SIM_SCRATCH_CAP - fixed : 0) / per);
+  if (want > SM_TILE) want -= want % SM_TILE;              // whole tiles of rows
+  if (const char* e = getenv("BNMF_SIM_BAND")) { const long long v = atoll(e); if (v >= 1) want = v; }    // tests, tools: the rows of a band
+  const int B = (int)std::min<long long>(want, nrows);
+  SimArgs a{};
+  double *cs, *dnn, *dres, *dnb = nullptr, *dtum = nullptr; int *dslots, *dmem, *drows; int32_t* dnat = nullptr;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); dnn = c.take<double>((size_t)S * m); dres = c.take<double>((size_t)SM_NROW * B * m);
+        if (all) { dnat = c.take<int32_t>((size_t)m * k); dnb = c.take<double>((size_t)SM_NROW * m * k); dtum = c.take<double>((size_t)SM_NROW * m); }
+        dslots = c.take<int>(S); dmem = c.take<int>(m); drows = c.take<int>(nrows);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(drows, rows.data(), (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const double *ringE = h->arr[BNMF_E].ring, *ringA = h->arr[BNMF_A].ring;
+  const size_t lenE = (size_t)N * G;
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, (size_t)K * N, K, N, (const int*)dslots, cs);
+  hipLaunchKernelGGL(k_sim_norm<SM_NROW>, dim3((unsigned)(((size_t)S * m + 255) / 256)), dim3(256), 0, h->stream, ringE, ringA, (const double*)cs,
+                     (const int*)dslots, (const int*)dmem, lenE, N, S, m, dnn);
+  a.ringE = ringE; a.ringA = ringA; a.cs = cs; a.nn = dnn; a.slots = dslots; a.members = dmem; a.res = dres; a.lenE = lenE; a.N = N; a.S = S; a.m = m;
+  a.min_cosine = min_cosine;
+  // the queries' rows in member order, [3][Q][m]: row r of a band is copied out where it is a query's
+  std::vector<double> hq(dense ? (size_t)SM_NROW * Q * m : 0);
+  for (int r0 = 0; r0 < nrows; r0 += B) {
+    const int nr = std::min(B, nrows - r0);
+    a.rows = drows + r0; a.nr = nr;
+    hipLaunchKernelGGL(k_sim_pairs<SM_NROW>, dim3((unsigned)((m + SM_TILE - 1) / SM_TILE), (unsigned)((nr + SM_TILE - 1) / SM_TILE)), dim3(SM_T), 0, h->stream, a);
+    if (all) hipLaunchKernelGGL(k_sim_select<SM_NROW>, dim3(nr), dim3(64), 0, h->stream, (const double*)dres, (const int*)(drows + r0), m, nr, r0, k, dnat, dnb,
+                                (size_t)m * k, dtum, (size_t)m);
+    HIPCHK(hipGetLastError());
+    if (dense)
+      for (int q = 0; q < Q; ++q) {
+        const int lr = (all ? place[query[q]] : q) - r0;    // the query's row of this band
+        if (lr < 0 || lr >= nr) continue;
+        for (int t = 0; t < SM_NROW; ++t)
+          HIPCHK(hipMemcpyAsync(hq.data() + ((size_t)t * Q + q) * m, dres + ((size_t)t * nr + lr) * m, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      }
+  }
+  std::vector<int32_t> hnat(all ? (size_t)m * k : 0);
+  std::vector<double> hnb(all ? (size_t)SM_NROW * m * k : 0), htum(all ? (size_t)SM_NROW * m : 0);
+  if (all) {
+    if (!hnat.empty()) HIPCHK(hipMemcpyAsync(hnat.data(), dnat, hnat.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (!hnb.empty()) HIPCHK(hipMemcpyAsync(hnb.data(), dnb, hnb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(htum.data(), dtum, htum.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  similarity_finish(members.data(), m, G, k, all ? hnat.data() : nullptr, all ? hnb.data() : nullptr, all ? htum.data() : nullptr, neighbour_at, neighbour,
+                    tumour, info);
+  info->n_used = S; info->top_k = top_k; info->n_query = Q; info->min_cosine = min_cosine;
+  if (dense) {
+    std::fill(dense, dense + (size_t)SM_NROW * Q * G, std::nan(""));
+    for (int t = 0; t < SM_NROW; ++t)
+      for (int q = 0; q < Q; ++q) {
+        const double* src = hq.data() + ((size_t)t * Q + q) * m;
+        double* dst = dense + ((size_t)t * Q + q) * G;
+        for (int i = 0; i < m; ++i) if (members[i] != query[q]) dst[members[i]] = src[i];
+      }
+  }
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1553,6 +1652,16 @@ int bnmf_reconstruction(bnmf_handle* h, int last_n, const int32_t* used, double 
 int bnmf_reconstruction_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, double min_cosine, double min_drop, double* tumour, double* drop,
                            double* series, double* signature, bnmf_reconstruction_info* info) {
   return reconstruction_impl(h, "bnmf_reconstruction_at", {true, end_iter, n_samples}, used, min_cosine, min_drop, tumour, drop, series, signature, info);
+}
+
+int bnmf_similarity(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, const int32_t* query, int Q, int top_k, double min_cosine,
+                    int32_t* neighbour_at, double* neighbour, double* dense, double* tumour, bnmf_similarity_info* info) {
+  return similarity_impl(h, "bnmf_similarity", {false, 0, last_n}, used, include, query, Q, top_k, min_cosine, neighbour_at, neighbour, dense, tumour, info);
+}
+int bnmf_similarity_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* query, int Q, int top_k,
+                       double min_cosine, int32_t* neighbour_at, double* neighbour, double* dense, double* tumour, bnmf_similarity_info* info) {
+  return similarity_impl(h, "bnmf_similarity_at", {true, end_iter, n_samples}, used, include, query, Q, top_k, min_cosine, neighbour_at, neighbour, dense,
+                         tumour, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

@@ -1,9 +1,10 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
-// (DESIGN.md 21), bnmf_stability's finish and bnmf_reconstruction's.  No device and no handle: posterior.h
-// includes it, and a stand-alone host program can (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp and
-// tools/reconstruction_reduce_check.cpp, built with -fsanitize=address,undefined by tests/test_coactivity_host.py,
-// tests/test_stability_host.py and tests/test_reconstruction_host.py).  Compile with -ffp-contract=off, as the library is.
+// (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's and bnmf_similarity's.  No
+// device and no handle: posterior.h includes it, and a stand-alone host program can (tools/coactivity_reduce_check.cpp,
+// tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp and tools/similarity_reduce_check.cpp, built with
+// -fsanitize=address,undefined by tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py and
+// tests/test_similarity_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -220,4 +221,36 @@ template <class Work> static void deal_threads(long nwork, Work work) {
     signature[(size_t)N + n] = ndef > 0 ? con_canon64(tmp.data(), (size_t)ndef, 1) / (double)ndef : nan;
     signature[2 * (size_t)N + n] = mx;
   }
+}
+
+// ---- bnmf_similarity's finish: from the rows in member order to the outputs by tumour and the info fields ----
+// members [m] ascending; nat [m][k] (the neighbours as places in the member list, -1 = none), nb [3][m][k], tum [3][m] as the device left
+// them, all null if the pass over all pairs did not run.  neighbour_at [G][k], neighbour [3][G][k], tumour [3][G] may each be null; a
+// left-out tumour holds -1 / NaN.  Of info n_included, n_left_out, n_pairs, n_similar_pairs, n_isolated, mean_similarity, least_typical and
+// least_typical_at are set.
+[[maybe_unused]] static void similarity_finish(const int* members, long m, long G, int k, const int32_t* nat, const double* nb, const double* tum,
+                                               int32_t* neighbour_at, double* neighbour, double* tumour, bnmf_similarity_info* info) {
+  const double nan = std::nan("");
+  info->n_included = (int32_t)m; info->n_left_out = (int32_t)(G - m); info->n_pairs = (int64_t)m * (int64_t)(m - 1) / 2;
+  info->n_similar_pairs = -1; info->n_isolated = -1; info->mean_similarity = nan; info->least_typical = nan; info->least_typical_at = -1;
+  const size_t Gk = (size_t)G * (size_t)k, mk = (size_t)m * (size_t)k;
+  if (neighbour_at) std::fill(neighbour_at, neighbour_at + Gk, (int32_t)-1);
+  if (neighbour) std::fill(neighbour, neighbour + 3 * Gk, nan);
+  if (tumour) std::fill(tumour, tumour + 3 * (size_t)G, nan);
+  if (!tum) return;
+  int64_t deg = 0, iso = 0, at = -1; double least = nan;
+  for (long i = 0; i < m; ++i) {
+    const size_t g = (size_t)members[i];
+    for (int t = 0; t < k; ++t) {
+      const size_t src = (size_t)i * k + t, dst = g * (size_t)k + t;
+      if (neighbour_at) neighbour_at[dst] = nat[src] < 0 ? -1 : (int32_t)members[nat[src]];
+      if (neighbour) for (int r = 0; r < 3; ++r) neighbour[r * Gk + dst] = nb[r * mk + src];
+    }
+    if (tumour) for (int r = 0; r < 3; ++r) tumour[(size_t)r * G + g] = tum[(size_t)r * m + i];
+    const double ty = tum[i], dg = tum[2 * (size_t)m + i];
+    deg += (int64_t)dg; iso += dg == 0.0 ? 1 : 0;
+    if (!std::isnan(ty) && (at < 0 || ty < least)) { least = ty; at = (int64_t)g; }
+  }
+  info->n_similar_pairs = deg / 2;                          // p_similar is bitwise symmetric: every pair was counted from both sides
+  info->n_isolated = iso; info->mean_similarity = con_canon64(tum, (size_t)m, 1) / (double)m; info->least_typical = least; info->least_typical_at = at;
 }

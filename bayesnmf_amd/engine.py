@@ -126,6 +126,12 @@ class BnmfReconstructionInfo(C.Structure):
                 ("min_cosine", C.c_double), ("min_drop", C.c_double), ("worst_cosine", C.c_double)]
 
 
+class BnmfSimilarityInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32), ("top_k", C.c_int32), ("n_query", C.c_int32),
+                ("_pad", C.c_int32), ("n_pairs", C.c_int64), ("n_similar_pairs", C.c_int64), ("n_isolated", C.c_int64),
+                ("least_typical_at", C.c_int64), ("mean_similarity", C.c_double), ("least_typical", C.c_double), ("min_cosine", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -150,6 +156,9 @@ STAB_FACTOR_ROWS = ["members", "stability", "min_silhouette", "mean_a", "mean_b"
 REC_TUMOUR_ROWS = ["cosine", "cosine_var", "min_cosine_sample", "rel_l1", "rmse", "p_good"]
 REC_DROP_ROWS = ["drop_mean", "drop_var", "loo_cosine", "p_needed"]
 REC_SIGNATURE_ROWS = ["n_tumours", "mean_drop", "max_drop"]
+SIM_ROWS = ["mean", "var", "p_similar"]
+SIM_TUMOUR_ROWS = ["typicality", "nearest_mean", "degree"]
+SIM_MAX_K = 32
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -169,7 +178,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
                "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
                "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
-               "bnmf_reconstruction", "bnmf_reconstruction_at"]
+               "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at"]
 
 
 def lib():
@@ -242,6 +251,8 @@ def lib():
         L.bnmf_stability_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, dp, ip, C.c_int, dp, dp, dp, dp, lp, C.POINTER(BnmfStabilityInfo)]
         L.bnmf_reconstruction.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfReconstructionInfo)]
         L.bnmf_reconstruction_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfReconstructionInfo)]
+        L.bnmf_similarity.argtypes = [C.c_void_p, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_double, ip, dp, dp, dp, C.POINTER(BnmfSimilarityInfo)]
+        L.bnmf_similarity_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_double, ip, dp, dp, dp, C.POINTER(BnmfSimilarityInfo)]
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -816,6 +827,47 @@ class Engine:
     def reconstruction_at(self, end_iter, n_samples, **kw):
         """reconstruction over the n_samples iterations that end at end_iter (bnmf_reconstruction_at)."""
         return self.reconstruction(n_samples, end_iter=end_iter, **kw)
+
+    def similarity(self, last_n, include=None, query=None, top_k=10, min_cosine=0.9, used=None, end_iter=None, tumour=True):
+        """Similarity of the tumours over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_similarity / bnmf_similarity_at), on the device.
+        include (length G of 0 / 1, None = all): the tumours that enter.  Per used sample the cosine of two tumours' renormalised
+        exposure vectors is one draw from its posterior; it is a sum over the factors, so label switching does not touch it.  Returns the
+        info fields; with top_k > 0 neighbour_at (G x top_k: the other members with the largest mean cosine, the lower tumour first
+        among equals, -1 = none) and neighbour (3 x G x top_k, the rows SIM_ROWS); with query (Q tumours) dense (3 x Q x G: the rows
+        SIM_ROWS of query[q] against every tumour, NaN on itself and on the left-out tumours); with tumour the 3 x G table and its rows by
+        name (SIM_TUMOUR_ROWS: the mean over the other members of the mean cosine, the mean cosine of the first neighbour, the number of
+        other members whose cosine is >= min_cosine in at least half of the samples).  top_k = 0, tumour = False and a query: only the Q
+        rows are computed."""
+        G = self.G
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"similarity: include has shape {inc.shape}, G = {G} flags are needed")
+        qv = None if query is None else np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        Q = 0 if qv is None else int(qv.size)
+        k = int(top_k)
+        u, _ = self._used("similarity", used, last_n)
+        kk = min(max(k, 0), SIM_MAX_K)                         # (an invalid top_k is refused by the library: the buffers only have to exist)
+        nat = np.empty((G, kk), dtype=np.int32) if kk > 0 else None
+        nb = np.empty((3, G, kk)) if kk > 0 else None
+        dn = np.empty((3, Q, G)) if Q > 0 else None
+        tum = np.empty((3, G)) if tumour else None
+        info = BnmfSimilarityInfo()
+        self._range_call("similarity", last_n, end_iter, u, None if inc is None else inc.ctypes.data_as(_IP), None if qv is None else qv.ctypes.data_as(_IP),
+                         Q, k, float(min_cosine), None if nat is None else nat.ctypes.data_as(_IP), _dp(nb), _dp(dn), _dp(tum), C.byref(info))
+        out = self._info(info)
+        if nat is not None:
+            out.update(neighbour_at=nat, neighbour=nb)
+        if dn is not None:
+            out.update(dense=dn, query=qv.copy())
+        if tumour:
+            out["tumour"] = tum
+            out.update({name: tum[i] for i, name in enumerate(SIM_TUMOUR_ROWS)})
+        return out
+
+    def similarity_at(self, end_iter, n_samples, **kw):
+        """similarity over the n_samples iterations that end at end_iter (bnmf_similarity_at)."""
+        return self.similarity(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

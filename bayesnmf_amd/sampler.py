@@ -137,6 +137,7 @@ class bayesNMF_sampler:
         if learning_rank and rank.min() != 0:
             rank = np.arange(0, rank.max() + 1)
         display_rank = f"{rank.min()}:{rank.max()}" if learning_rank else int(rank[0])
+        self.tumour_names = [str(c) for c in data.columns] if hasattr(data, "columns") else None   # (get_similarity's tables)
         data = np.asarray(data)
         n_iters = cc["maxiters"] + (post_warmup if MH else 0)
         if learning_rank:
@@ -968,8 +969,65 @@ class bayesNMF_sampler:
                  f"(tumour {r['worst_at']}); {r['n_needed']} (signature, tumour) pairs with a drop >= {r['min_drop']:g}", verbosity=1)
         return out
 
+    def get_similarity(self, include=None, query=None, top_k=10, min_cosine=0.9, end_iter=None, n_samples=None, idx="MAP_idx"):
+        """Which tumours have the exposure profile of this one, does the cohort fall into subtypes, which tumours resemble nobody?  On
+        the device (bnmf_similarity_at; not in the reference): over iterations end_iter - n_samples + 1 ... end_iter (defaults as
+        get_WAIC), restricted to `idx` (as get_contrast), every sample gives for every pair of included tumours the cosine of their
+        renormalised exposure vectors (the loads of get_MAP).  The cosine is a sum over the factors, so label switching does not touch
+        it.  include (G flags; None = all): a tumour with a 0, None or NaN is left out, as in get_coactivity.  query: tumours (indices,
+        or names where the data had column names) whose similarity to every tumour is returned in full.
+        Returns dict(neighbours (a data frame: tumour, rank (1 = nearest), neighbour, mean, sd, p_similar: per included tumour the top_k
+        others with the largest mean cosine; p_similar is the share of samples with cosine >= min_cosine), dense (3 x Q x G: mean,
+        variance and p_similar of every query against every tumour, NaN on itself and on left-out tumours) with query, tumours (a
+        data frame: tumour, typicality (the mean over the other tumours of the mean cosine), nearest_mean, degree (the other tumours
+        with p_similar >= 0.5), included), neighbour_at, neighbour, tumour (the arrays of the call), n_used, n_included, n_left_out,
+        top_k, n_query, n_pairs, n_similar_pairs, n_isolated, mean_similarity, least_typical, least_typical_at, min_cosine)."""
+        if not hasattr(self._chain, "similarity"):
+            raise ValueError("get_similarity needs an engine that compares tumours over its recorded samples (similarity); this engine_factory's cannot")
+        G = self.dims["G"]
+        names = self.tumour_names if getattr(self, "tumour_names", None) else None
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        qv = None
+        if query is not None:
+            qs = list(np.atleast_1d(query).tolist())
+            if names is not None and all(isinstance(q, str) for q in qs):
+                missing = [q for q in qs if q not in names]
+                if missing:
+                    raise ValueError(f"query names no tumour of the data: {missing[:5]}")
+                qs = [names.index(q) for q in qs]
+            qv = np.asarray(qs, dtype=np.int32)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.similarity(n, include=inc, query=qv, top_k=top_k, min_cosine=min_cosine, used=used, **kw)
+        label = (lambda g: names[g]) if names is not None else (lambda g: int(g))
+        k = int(r["top_k"])
+        nat = np.asarray(r["neighbour_at"]).reshape(G, k) if k > 0 else np.empty((G, 0), dtype=np.int32)
+        nb = np.asarray(r["neighbour"]).reshape(3, G, k) if k > 0 else np.empty((3, G, 0))
+        rows = [(label(g), j + 1, label(nat[g, j]), nb[0, g, j], float(np.sqrt(nb[1, g, j])), nb[2, g, j])
+                for g in range(G) for j in range(k) if nat[g, j] >= 0]
+        out = dict(neighbours=pd.DataFrame(rows, columns=["tumour", "rank", "neighbour", "mean", "sd", "p_similar"]), neighbour_at=nat, neighbour=nb)
+        tum = np.asarray(r["tumour"]).reshape(3, G)
+        included = np.ones(G, dtype=bool) if inc is None else inc.astype(bool)
+        out["tumour"] = tum
+        out["tumours"] = pd.DataFrame(dict(tumour=[label(g) for g in range(G)], typicality=tum[0], nearest_mean=tum[1], degree=tum[2], included=included))
+        if qv is not None:
+            out.update(dense=np.asarray(r["dense"]).reshape(3, qv.size, G), query=[label(g) for g in qv])
+        out.update({key: r[key] for key in ("n_used", "n_included", "n_left_out", "top_k", "n_query", "n_pairs", "n_similar_pairs", "n_isolated",
+                                            "mean_similarity", "least_typical", "least_typical_at", "min_cosine")})
+        self.log(f"Similarity: {r['n_included']} tumours included, {r['n_left_out']} left out; {r['n_similar_pairs']} of {r['n_pairs']} pairs similar "
+                 f"(cosine >= {r['min_cosine']:g} in at least half of the samples), {r['n_isolated']} tumours resemble nobody; mean similarity "
+                 f"{r['mean_similarity']:.3g}, least typical {r['least_typical']:.3g} (tumour {r['least_typical_at']})", verbosity=1)
+        return out
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

@@ -623,6 +623,65 @@ int bnmf_reconstruction(bnmf_handle*, int last_n, const int32_t* used, double mi
 int bnmf_reconstruction_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, double min_cosine, double min_drop, double* tumour,
                            double* drop, double* series, double* signature, bnmf_reconstruction_info* info);
 
+/* Similarity of tumours over recorded samples, on the device: which tumours have the exposure profile of this one, does the
+ * cohort fall into subtypes, which tumours resemble nobody?  The cosine of two tumours' exposure vectors is a sum over the factors, so it
+ * is immune to label switching: no bnmf_relabel is needed first.  The members are the m included tumours g_0 < g_1 < ... (include[g] != 0;
+ * NULL = all: bnmf_regress's member list); the samples are the recorded samples flagged in used[] (oldest first; NULL = all), s = 1 .. S.
+ * Per sample, with cs_s[n] bnmf_map's column sum of P_s:
+ *   x_s[n,g]   = A_s[n] != 0 ? E_s[n,g] * cs_s[n] : +0.0           bnmf_contrast's renormalised exposure, the same bits
+ *   nn_s[g]    = sum_n x_s[n,g] * x_s[n,g]                          n ascending from +0.0; multiply and add rounded separately
+ *   dot_s(g,h) = sum_n x_s[n,g] * x_s[n,h]                          the same order
+ *   c_s(g,h)   = nn_s[g] * nn_s[h] == 0 ? +0.0 : dot_s(g,h) / sqrt(nn_s[g] * nn_s[h])
+ * A tumour without any exposure in a sample resembles nothing (+0.0, which is also what a product that underflows to 0 gives); nn is a
+ * sum of squares, so the product is > 0, 0 or NaN, and a NaN or an infinity takes the division and propagates by IEEE.  c_s is bitwise
+ * symmetric in (g, h).  Per pair g != h of members, over s ascending, bnmf_attribution's Welford (d = c - mu; mu = mu + d * (1 / s);
+ * M2 = M2 + d * (c - mu)) and a count:   mean = mu,   variance = M2 / (S - 1),   p_similar = #(c_s >= min_cosine) / S.
+ * neighbour_at [G][top_k] (row-major) and neighbour [BNMF_SIM_NNROW][G][top_k]: for member g the top_k other members with the largest
+ *   mean, the mean descending and the lower tumour first among equal means; a NaN mean is never listed.  Rows: 0 mean, 1 variance,
+ *   2 p_similar.  Unfilled places (fewer than top_k candidates) and every place of a left-out tumour hold -1 / NaN.
+ * dense [BNMF_SIM_NDROW][Q][G]: rows 0 mean, 1 variance, 2 p_similar of query[q] against every tumour g; NaN where g is left out or
+ *   g == query[q].  query = all tumours of a small cohort gives the whole matrix.  A tumour may be named more than once.
+ * tumour [BNMF_SIM_NTUM][G]: 0 the typicality: the mean over the other members of the mean cosine, the sum taken as bnmf_regress's
+ *   blocked canonical sum (blocks of BNMF_REG_BLOCK members in member order, each the canonical W = 64 sum, the blocks added ascending
+ *   from +0.0) with the self term entered as +0.0, divided by m - 1; 1 the mean cosine of the first neighbour (the largest mean to
+ *   another member under the order above; NaN if every mean is NaN); 2 the degree: the other members with p_similar >= 0.5.  NaN for
+ *   a left-out tumour.
+ * info: n_used = S, n_included = m, n_left_out = G - m, top_k, n_query = Q, n_pairs = m (m - 1) / 2, min_cosine as given; and from the
+ *   pass over all pairs: n_similar_pairs = the unordered pairs with p_similar >= 0.5, n_isolated = the members of degree 0,
+ *   mean_similarity = the canonical W = 64 sum of tumour row 0 over the members ascending, divided by m; least_typical and
+ *   least_typical_at = the smallest non-NaN tumour row 0 and its g (the first wins; NaN and -1 without one).
+ * With top_k == 0, tumour == NULL and Q > 0 only the Q rows of dense are computed and the pass over all pairs does not run: then
+ * n_similar_pairs = n_isolated = -1, mean_similarity = least_typical = NaN and least_typical_at = -1.  In every other case the pass
+ * runs, whichever outputs are NULL.  Each of the four arrays may be NULL.
+ * Only + - * /, sqrt, comparisons and whole numbers, no contraction, every sum in the order above: the bits depend on the samples,
+ * used[], include[], query[], top_k and min_cosine only, not on the tiling, the band of rows that passes through the scratch or the form
+ * of the kernel.  A pair's values involve its two tumours only and every sum over tumours runs over the member list, so leaving tumours
+ * out through include[] gives the bits of a cohort without them.  Reads only the P, E and A rings; works for every likelihood and
+ * prior; draws no random number, consumes none of the chain's streams and is read-only for the chain.  bnmf_similarity_at: the
+ * n_samples iterations that end at end_iter; the range rule, used[] and BNMF_ESIZE as for bnmf_attribution_at; bnmf_similarity(h, n, ...)
+ * is bnmf_similarity_at(h, iter, n, ...).  Refused before any device work: a null info, a used[] or include[] value other than 0 / 1
+ * (the index named), Q < 0, Q > 0 with a null query, a query[q] outside 0 .. G-1 or left out (q named), top_k outside
+ * 0 .. BNMF_SIM_MAX_K, a min_cosine that is NaN or infinite with BNMF_EINVAL; fewer than 2 used samples or m < 2 with BNMF_ESIZE;
+ * window = 0, a poisoned handle or nothing recorded with BNMF_ESTATE. */
+#define BNMF_SIM_NNROW 3         /* neighbour rows: mean, variance, p_similar */
+#define BNMF_SIM_NDROW 3         /* dense rows: mean, variance, p_similar */
+#define BNMF_SIM_NTUM  3         /* tumour rows: typicality, mean cosine of the first neighbour, degree */
+#define BNMF_SIM_MAX_K 32        /* the largest top_k */
+typedef struct { int32_t n_used, n_included, n_left_out, top_k, n_query, _pad; int64_t n_pairs, n_similar_pairs, n_isolated,
+                 least_typical_at /* g; -1 if none */; double mean_similarity, least_typical, min_cosine; } bnmf_similarity_info;
+int bnmf_similarity(bnmf_handle*, int last_n, const int32_t* used,
+                    const int32_t* include /* [G] 0 / 1, NULL = all */,
+                    const int32_t* query /* [Q] tumours, may be NULL with Q = 0 */, int Q,
+                    int top_k, double min_cosine,
+                    int32_t* neighbour_at /* [G][top_k] row-major; may be NULL */,
+                    double*  neighbour    /* [BNMF_SIM_NNROW][G][top_k]; may be NULL */,
+                    double*  dense        /* [BNMF_SIM_NDROW][Q][G]; may be NULL */,
+                    double*  tumour       /* [BNMF_SIM_NTUM][G]; may be NULL */,
+                    bnmf_similarity_info* info);
+int bnmf_similarity_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* query, int Q,
+                       int top_k, double min_cosine, int32_t* neighbour_at, double* neighbour, double* dense, double* tumour,
+                       bnmf_similarity_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

@@ -382,6 +382,67 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       paste(sprintf("%s %g", names, r$n_credible[, 1]), collapse = ", ")))
       out
     },
+    # Similarity of the tumours, on the device (bnmf_similarity_at; not in the reference): which tumours have the exposure profile of
+    # this one, does the cohort fall into subtypes, which tumours resemble nobody?  Over iterations end_iter - n_samples + 1 ... end_iter
+    # (defaults as get_WAIC), restricted to idx, every sample gives for every pair of included tumours the cosine of their renormalised
+    # exposure vectors; it is a sum over the factors, so label switching does not touch it.  include: a logical of G flags (NULL = all);
+    # a tumour with FALSE or NA is left out.  query: tumours (1-based indices, or column names of the data) whose similarity to every
+    # tumour is returned in full.  list(neighbours (a data frame: tumour, rank, neighbour, mean, sd, p_similar: per included tumour the
+    # top_k others with the largest mean cosine; p_similar is the share of samples with cosine >= min_cosine), dense (3 x Q x G: mean,
+    # variance, p_similar; NA on the query itself and on left-out tumours) with query, tumours (a data frame: tumour, typicality,
+    # nearest_mean, degree, included), neighbour_at (G x top_k, 1-based, NA = none), neighbour (3 x G x top_k), n_used, n_included,
+    # n_left_out, top_k, n_query, n_pairs, n_similar_pairs, n_isolated, mean_similarity, least_typical, least_typical_at (1-based; NA if
+    # none), min_cosine).
+    get_similarity = function(include = NULL, query = NULL, top_k = 10, min_cosine = 0.9, end_iter = self$state$iter,
+                              n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      names <- colnames(self$data)
+      label <- function(g) if (is.null(names)) g else names[g]
+      q <- NULL
+      if (!is.null(query)) {
+        if (is.character(query)) {
+          q <- match(query, names)
+          if (anyNA(q)) stop("query names no tumour of the data: ", paste(utils::head(query[is.na(q)], 5), collapse = ", "))
+        } else q <- as.integer(query)
+      }
+      r <- .Call("C_bnmf_similarity", self$handle, as.integer(end_iter), as.integer(n_samples), used, include,
+                 if (is.null(q)) NULL else as.integer(q - 1L), c(as.integer(top_k), 1L), as.double(min_cosine), c(K, G, N))
+      k <- r$top_k
+      at <- if (k > 0) t(r$neighbour_at) else matrix(integer(0), G, 0)            # G x k, 0-based, -1 = none
+      nb <- if (k > 0) aperm(array(r$neighbour, c(k, G, 3)), c(3, 2, 1)) else array(numeric(0), c(3, G, 0))
+      rows <- which(t(at) >= 0, arr.ind = TRUE)                                   # (rank, tumour), the ranks of a tumour together
+      neighbours <- data.frame(tumour = label(rows[, 2]), rank = rows[, 1], neighbour = label(at[rows[, 2:1, drop = FALSE]] + 1L),
+                               mean = matrix(nb[1, , ], G, k)[rows[, 2:1, drop = FALSE]], sd = sqrt(matrix(nb[2, , ], G, k)[rows[, 2:1, drop = FALSE]]),
+                               p_similar = matrix(nb[3, , ], G, k)[rows[, 2:1, drop = FALSE]])
+      out <- list(neighbours = neighbours, neighbour_at = ifelse(at < 0, NA_integer_, at + 1L), neighbour = nb, tumour = t(r$tumour),
+                  tumours = data.frame(tumour = label(seq_len(G)), typicality = r$tumour[, 1], nearest_mean = r$tumour[, 2], degree = r$tumour[, 3],
+                                       included = if (is.null(include)) rep(TRUE, G) else include),
+                  n_used = r$n_used, n_included = r$n_included, n_left_out = r$n_left_out, top_k = k, n_query = r$n_query, n_pairs = r$n_pairs,
+                  n_similar_pairs = r$n_similar_pairs, n_isolated = r$n_isolated, mean_similarity = r$mean_similarity,
+                  least_typical = r$least_typical, least_typical_at = if (r$least_typical_at < 0) NA_integer_ else as.integer(r$least_typical_at) + 1L,
+                  min_cosine = r$min_cosine)
+      if (!is.null(q)) {
+        out$dense <- aperm(array(r$dense, c(G, length(q), 3)), c(3, 2, 1))
+        out$query <- label(q)
+      }
+      message(sprintf("Similarity: %d tumours included, %d left out; %g of %g pairs similar (cosine >= %g in at least half of the samples), %g tumours resemble nobody; mean similarity %.3g",
+                      r$n_included, r$n_left_out, r$n_similar_pairs, r$n_pairs, r$min_cosine, r$n_isolated, r$mean_similarity))
+      out
+    },
     # Co-activity of the signatures, on the device (bnmf_coactivity_at; not in the reference): do two signatures act in the same tumours
     # or exclude each other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are
     # negatively correlated)?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every

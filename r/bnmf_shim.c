@@ -742,6 +742,73 @@ SEXP C_bnmf_coactivity_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SE
   UNPROTECT(1);
   return out;
 }
+/* Similarity of tumours over recorded samples on the device (bnmf_similarity / bnmf_similarity_at): C_bnmf_similarity(ptr, end_iter
+ * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or
+ * NULL = all), query (integer, 0-based tumours; or NULL), opts (integer c(top_k, want_tumour 0 / 1)), min_cosine, dims c(K,G,N)) -> list(n_used,
+ * n_included, n_left_out, top_k, n_query, n_pairs, n_similar_pairs, n_isolated, least_typical_at (0-based tumour, -1 = none),
+ * mean_similarity, least_typical, min_cosine, neighbour_at (top_k x G integer: column g holds the 0-based neighbours of tumour g, -1 =
+ * none; NULL with top_k = 0), neighbour (top_k G x 3: one column per row of the C output - mean, variance, p_similar - each laid out as
+ * neighbour_at; or NULL), dense (G Q x 3: column r laid out as a G x Q matrix, one column per query; NULL without a query), tumour (G x 3:
+ * typicality, the first neighbour's mean, degree; NULL unless want_tumour is 1)) over iterations end_iter - n_samples + 1 ... end_iter.  With
+ * opts = c(0, 0) and a query only the queries' rows are computed.  C_bnmf_similarity_at: the same with end_iter required */
+/* the result list with its arrays allocated, the flags of used and include, the queries; returned unprotected */
+static SEXP sim_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP query, SEXP opts, SEXP dims, int32_t** u, int32_t** inc,
+                      int32_t** q, int* Q) {
+  const int n = INTEGER(n_samples)[0], G = INTEGER(dims)[1];
+  if (XLENGTH(opts) != 2) Rf_error("bnmf: opts has %ld entries, c(top_k, want_tumour) is needed", (long)XLENGTH(opts));
+  int k = INTEGER(opts)[0];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  *u = lgl_flags(used, n);
+  *inc = lgl_flags(include, G);
+  *Q = query == R_NilValue ? 0 : (int)XLENGTH(query);
+  *q = *Q > 0 ? (int32_t*)INTEGER(query) : NULL;
+  if (k < 0 || k > BNMF_SIM_MAX_K) k = 0;                                  /* (the library refuses it: nothing to allocate) */
+  static const char* nms[] = {"n_used", "n_included", "n_left_out", "top_k", "n_query", "n_pairs", "n_similar_pairs", "n_isolated", "least_typical_at",
+                              "mean_similarity", "least_typical", "min_cosine", "neighbour_at", "neighbour", "dense", "tumour"};
+  SEXP out = PROTECT(named_list(16, nms));
+  if (k > 0) {
+    SET_VECTOR_ELT(out, 12, Rf_allocMatrix(INTSXP, k, G));
+    SET_VECTOR_ELT(out, 13, Rf_allocMatrix(REALSXP, k * G, BNMF_SIM_NNROW));
+  }
+  if (*Q > 0) SET_VECTOR_ELT(out, 14, Rf_allocMatrix(REALSXP, G * *Q, BNMF_SIM_NDROW));
+  if (INTEGER(opts)[1] == 1) SET_VECTOR_ELT(out, 15, Rf_allocMatrix(REALSXP, G, BNMF_SIM_NTUM));
+  UNPROTECT(1);
+  return out;
+}
+static int32_t* sim_at_buf(SEXP out) { SEXP x = VECTOR_ELT(out, 12); return x == R_NilValue ? NULL : (int32_t*)INTEGER(x); }
+static void sim_finish(SEXP out, const bnmf_similarity_info* info) {
+  SET_VECTOR_ELT(out, 0, Rf_ScalarInteger(info->n_used)); SET_VECTOR_ELT(out, 1, Rf_ScalarInteger(info->n_included));
+  SET_VECTOR_ELT(out, 2, Rf_ScalarInteger(info->n_left_out)); SET_VECTOR_ELT(out, 3, Rf_ScalarInteger(info->top_k));
+  SET_VECTOR_ELT(out, 4, Rf_ScalarInteger(info->n_query)); SET_VECTOR_ELT(out, 5, Rf_ScalarReal((double)info->n_pairs));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarReal((double)info->n_similar_pairs)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal((double)info->n_isolated));
+  SET_VECTOR_ELT(out, 8, Rf_ScalarReal((double)info->least_typical_at)); SET_VECTOR_ELT(out, 9, Rf_ScalarReal(info->mean_similarity));
+  SET_VECTOR_ELT(out, 10, Rf_ScalarReal(info->least_typical)); SET_VECTOR_ELT(out, 11, Rf_ScalarReal(info->min_cosine));
+}
+SEXP C_bnmf_similarity(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP query, SEXP opts, SEXP min_cosine, SEXP dims) {
+  int32_t *u = NULL, *inc = NULL, *q = NULL; int Q = 0;
+  SEXP out = PROTECT(sim_alloc(n_samples, used, include, query, opts, dims, &u, &inc, &q, &Q));
+  bnmf_similarity_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_similarity(get_handle(ptr), INTEGER(n_samples)[0], u, inc, q, Q, INTEGER(opts)[0], REAL(min_cosine)[0], sim_at_buf(out), map_buf(out, 13),
+                        map_buf(out, 14), map_buf(out, 15), &info));
+  else
+    chk(bnmf_similarity_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, inc, q, Q, INTEGER(opts)[0], REAL(min_cosine)[0], sim_at_buf(out),
+                           map_buf(out, 13), map_buf(out, 14), map_buf(out, 15), &info));
+  sim_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_similarity_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP query, SEXP opts, SEXP min_cosine, SEXP dims) {
+  int32_t *u = NULL, *inc = NULL, *q = NULL; int Q = 0;
+  SEXP out = PROTECT(sim_alloc(n_samples, used, include, query, opts, dims, &u, &inc, &q, &Q));
+  bnmf_similarity_info info;
+  chk(bnmf_similarity_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, inc, q, Q, INTEGER(opts)[0], REAL(min_cosine)[0], sim_at_buf(out),
+                         map_buf(out, 13), map_buf(out, 14), map_buf(out, 15), &info));
+  sim_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Silhouette stability of the recorded signatures on the device (bnmf_stability / bnmf_stability_at): C_bnmf_stability(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), labels (integer n_samples x N
  * matrix of 0-based clusters, -1 / NA = left out; or NULL = the factor), extra_P (K x X real matrix, or NULL), extra_label (integer X,
@@ -1109,6 +1176,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_coactivity", (DL_FUNC)&C_bnmf_coactivity, 9}, {"C_bnmf_coactivity_at", (DL_FUNC)&C_bnmf_coactivity_at, 9},
   {"C_bnmf_stability", (DL_FUNC)&C_bnmf_stability, 8}, {"C_bnmf_stability_at", (DL_FUNC)&C_bnmf_stability_at, 8},
   {"C_bnmf_reconstruction", (DL_FUNC)&C_bnmf_reconstruction, 7}, {"C_bnmf_reconstruction_at", (DL_FUNC)&C_bnmf_reconstruction_at, 7},
+  {"C_bnmf_similarity", (DL_FUNC)&C_bnmf_similarity, 9}, {"C_bnmf_similarity_at", (DL_FUNC)&C_bnmf_similarity_at, 9},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
