@@ -44,6 +44,7 @@
 #include "stability.h"
 #include "reconstruction.h"
 #include "similarity.h"
+#include "subtypes.h"
 
 using namespace bnmf;
 

@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h and similarity.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h and subtypes.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1536,6 +1536,142 @@ static int similarity_impl(bnmf_handle* h, const char* fn, Range r, const int32_
   return 0;
 }
 
+// Subtypes of tumours over the samples of r that used[] flags (subtypes.h): the member list, the matched samples and
+// their perm rows are made here; k_map_colsum runs once over the matched samples; then per batch of samples k_subtypes runs every
+// sample's Lloyd steps with the labels in the scratch, k_sub_count adds the batch to the whole-number counts and, if asked for, the
+// batch's labels are copied out.  The outputs by tumour, the moments of the centres and sizes and the info fields are subtypes_finish's.
+static_assert(SB_NTUM == BNMF_SUB_NTUM && SB_NCROW == BNMF_SUB_NCROW && SB_NSER == BNMF_SUB_NSER && SB_MAX_C == BNMF_SUB_MAX_C && SB_MAX_N == BNMF_SUB_MAX_N,
+              "subtypes.h and bnmf.h disagree");
+static constexpr size_t SUB_SCRATCH_CAP = (size_t)256 << 20;    // bytes of a batch's labels, dmin and u
+static int subtypes_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, const int32_t* perm, const double* centres0,
+                         int C, int n_steps, const int32_t* query, int Q, double min_certainty, double* membership, int32_t* label, double* tumour,
+                         double* centre, double* size, double* together, int32_t* labels, double* series, bnmf_subtypes_info* info) {
+  if (int rc = range_enter(h, fn, h && info && centres0, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members, place(G, -1);                  // place[g]: g's position in the member list
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) { place[g] = (int)members.size(); members.push_back(g); }
+  }
+  const int m = (int)members.size();
+  if (C < 2 || C > BNMF_SUB_MAX_C) return fail(BNMF_EINVAL, "%s: C = %d is outside 2..%d", fn, C, BNMF_SUB_MAX_C);
+  if (n_steps < 1 || n_steps > BNMF_SUB_MAX_STEPS) return fail(BNMF_EINVAL, "%s: n_steps = %d is outside 1..%d", fn, n_steps, BNMF_SUB_MAX_STEPS);
+  if (Q < 0) return fail(BNMF_EINVAL, "%s: Q = %d is negative", fn, Q);
+  if (Q > 0 && !query) return fail(BNMF_EINVAL, "%s: Q = %d but query is null", fn, Q);
+  for (int q = 0; q < Q; ++q) {
+    if (query[q] < 0 || query[q] >= G) return fail(BNMF_EINVAL, "%s: query[%d] = %d is outside 0..%d", fn, q, (int)query[q], G - 1);
+    if (place[query[q]] < 0) return fail(BNMF_EINVAL, "%s: query[%d] = %d is a tumour that include[] leaves out", fn, q, (int)query[q]);
+  }
+  for (int c = 0; c < C; ++c) for (int j = 0; j < N; ++j) {
+    const double v = centres0[j + (size_t)N * c];
+    if (!std::isfinite(v) || v < 0.0) return fail(BNMF_EINVAL, "%s: centres0[%d, %d] = %g is not a finite number >= 0", fn, j, c, v);
+  }
+  if (!(min_certainty >= 0.0 && min_certainty <= 1.0)) return fail(BNMF_EINVAL, "%s: min_certainty = %g is outside [0, 1]", fn, min_certainty);
+  // the matched samples: rows[] is the row of the range of every used sample, mrow[] the used sample of every matched one
+  std::vector<int> rows, mrow, mslots, hperm;
+  for (int s = 0; s < r.n; ++s) if (!used || used[s]) rows.push_back(s);
+  const int S = (int)slots.size();
+  for (int s = 0; s < S; ++s) {
+    const int32_t* pr = perm ? perm + (size_t)rows[s] * N : nullptr;
+    bool none = pr != nullptr;
+    for (int n = 0; pr && n < N; ++n) none = none && pr[n] == -1;
+    if (none) continue;
+    if (pr) {
+      std::vector<char> seen(N, 0);
+      for (int n = 0; n < N; ++n) {
+        if (pr[n] < 0 || pr[n] >= N || seen[pr[n]])
+          return fail(BNMF_EINVAL, "%s: perm[%d] is neither a permutation of 0..%d nor -1 throughout (sample %d of the range, factor %d: %d)", fn, rows[s], N - 1,
+                      rows[s], n, (int)pr[n]);
+        seen[pr[n]] = 1;
+      }
+    }
+    mrow.push_back(s); mslots.push_back(slots[s]);
+    for (int n = 0; n < N; ++n) hperm.push_back(pr ? pr[n] : n);
+  }
+  const int Sm = (int)mrow.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (Sm < 2) return fail(BNMF_ESIZE, "%s: %d matched sample%s of %d used, the variance over the samples needs at least 2", fn, Sm, Sm == 1 ? "" : "s", S);
+  if (m < C) return fail(BNMF_ESIZE, "%s: %d included tumour%s for C = %d subtypes", fn, m, m == 1 ? "" : "s", C);
+  if (N > BNMF_SUB_MAX_N) return fail(BNMF_ESIZE, "%s: N = %d factors, at most %d are taken", fn, N, BNMF_SUB_MAX_N);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  bool small = N <= 8 && C <= 4;
+  if (const char* e = getenv("BNMF_SUB_FORM")) if (atoi(e) == 1) small = false;                            // tests, tools: the tiled form
+  const size_t per = (size_t)m * (sizeof(int32_t) + 2 * sizeof(double));                                   // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, SUB_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_SUB_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>(want, Sm);
+  const size_t NC = (size_t)N * C;
+  std::vector<int> qplace(std::max(Q, 1), 0);
+  for (int q = 0; q < Q; ++q) qplace[q] = place[query[q]];
+  SubArgs a{};
+  double *cs, *dc0; int *dslots, *dmem, *dperm, *dqp; int32_t *dcnt, *dasg, *dtog, *dboth;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)Sm * N); dc0 = c.take<double>(NC); a.centre = c.take<double>((size_t)Sm * NC); a.size = c.take<int32_t>((size_t)Sm * C);
+        a.inertia = c.take<double>(Sm); a.steps = c.take<int32_t>(Sm); a.assigned = c.take<int32_t>(Sm); a.changed = c.take<int32_t>(Sm);
+        a.lab = c.take<int32_t>((size_t)Sb * m); a.dmin = c.take<double>((size_t)Sb * m); a.u = c.take<double>((size_t)Sb * m);
+        dcnt = c.take<int32_t>((size_t)(C + 1 + 2 * Q) * m);                                               // cnt [C][m], assigned [m], together [Q][m], both [Q][m]
+        dslots = c.take<int>(Sm); dmem = c.take<int>(m); dperm = c.take<int>((size_t)Sm * N); dqp = c.take<int>(std::max(Q, 1));
+      })) return rc;
+  dasg = dcnt + (size_t)C * m; dtog = dasg + m; dboth = dtog + (size_t)Q * m;
+  HIPCHK(hipMemcpyAsync(dslots, mslots.data(), (size_t)Sm * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dperm, hperm.data(), (size_t)Sm * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dqp, qplace.data(), (size_t)std::max(Q, 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dc0, centres0, NC * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(dcnt, 0, (size_t)(C + 1 + 2 * Q) * m * sizeof(int32_t), h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(Sm, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, (size_t)K * N, K, N, (const int*)dslots, cs);
+  a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.cs = cs; a.slots = dslots; a.members = dmem; a.perm = dperm; a.centres0 = dc0;
+  a.lenE = (size_t)N * G; a.N = N; a.C = C; a.m = m; a.n_steps = n_steps;
+  std::vector<int32_t> hlab(labels ? (size_t)Sb * m : 0);
+  if (labels) std::fill(labels, labels + (size_t)S * G, (int32_t)-2);
+  for (int s0 = 0; s0 < Sm; s0 += Sb) {
+    const int ns = std::min(Sb, Sm - s0);
+    a.s0 = s0;
+    if (small) hipLaunchKernelGGL((k_subtypes<8, 4>), dim3(ns), dim3(SB_T), 0, h->stream, a);
+    else hipLaunchKernelGGL((k_subtypes<4, 8>), dim3(ns), dim3(SB_T), 0, h->stream, a);
+    for (int q0 = 0; q0 == 0 || q0 < Q; q0 += SB_QSLICE) {       // the queries in slices: the grid's y is 16 bits wide
+      const int nq = std::min(SB_QSLICE, Q - q0);
+      hipLaunchKernelGGL(k_sub_count<SB_NTUM>, dim3((unsigned)((m + 255) / 256), (unsigned)(1 + nq)), dim3(256), 0, h->stream, (const int32_t*)a.lab, ns, m, C,
+                         (const int*)dqp + q0, dcnt, dasg, dtog + (size_t)q0 * m, dboth + (size_t)q0 * m, q0 == 0 ? 1 : 0);
+    }
+    HIPCHK(hipGetLastError());
+    if (labels) {                                             // the batch's labels leave the device before the next batch overwrites them
+      HIPCHK(hipMemcpyAsync(hlab.data(), a.lab, (size_t)ns * m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+      for (int s = 0; s < ns; ++s) {
+        int32_t* dst = labels + (size_t)mrow[s0 + s] * G;
+        for (int i = 0; i < m; ++i) dst[members[i]] = hlab[(size_t)s * m + i];
+      }
+    }
+  }
+  std::vector<int32_t> hcnt((size_t)(C + 1 + 2 * Q) * m), hsize((size_t)Sm * C), hsteps(Sm), hasg(Sm), hchg(Sm);
+  std::vector<double> hcen((size_t)Sm * NC), hin(Sm);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), dcnt, hcnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hsize.data(), a.size, hsize.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hsteps.data(), a.steps, (size_t)Sm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hasg.data(), a.assigned, (size_t)Sm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hchg.data(), a.changed, (size_t)Sm * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hcen.data(), a.centre, hcen.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hin.data(), a.inertia, (size_t)Sm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  const int32_t* pc = hcnt.data();
+  subtypes_finish(members.data(), m, G, N, C, Sm, pc, pc + (size_t)C * m, Q, query, pc + (size_t)(C + 1) * m, pc + (size_t)(C + 1 + Q) * m, hcen.data(),
+                  hsize.data(), min_certainty, membership, label, tumour, centre, size, together, info);
+  info->n_used = S; info->n_matched = Sm; info->n_unmatched = S - Sm; info->C = C; info->n_steps = n_steps; info->n_query = Q; info->min_certainty = min_certainty;
+  for (int s = 0; s < Sm; ++s) info->n_not_converged += (hsteps[s] == n_steps && hchg[s]) ? 1 : 0;
+  if (series) {
+    std::fill(series, series + (size_t)SB_NSER * S, std::nan(""));
+    for (int s = 0; s < Sm; ++s) {
+      series[mrow[s]] = hin[s]; series[(size_t)S + mrow[s]] = (double)hsteps[s]; series[2 * (size_t)S + mrow[s]] = (double)hasg[s];
+    }
+  }
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1662,6 +1798,19 @@ int bnmf_similarity_at(bnmf_handle* h, int end_iter, int n_samples, const int32_
                        double min_cosine, int32_t* neighbour_at, double* neighbour, double* dense, double* tumour, bnmf_similarity_info* info) {
   return similarity_impl(h, "bnmf_similarity_at", {true, end_iter, n_samples}, used, include, query, Q, top_k, min_cosine, neighbour_at, neighbour, dense,
                          tumour, info);
+}
+
+int bnmf_subtypes(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, const int32_t* perm, const double* centres0, int C, int n_steps,
+                  const int32_t* query, int Q, double min_certainty, double* membership, int32_t* label, double* tumour, double* centre, double* size,
+                  double* together, int32_t* labels, double* series, bnmf_subtypes_info* info) {
+  return subtypes_impl(h, "bnmf_subtypes", {false, 0, last_n}, used, include, perm, centres0, C, n_steps, query, Q, min_certainty, membership, label, tumour, centre,
+                       size, together, labels, series, info);
+}
+int bnmf_subtypes_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm, const double* centres0, int C,
+                     int n_steps, const int32_t* query, int Q, double min_certainty, double* membership, int32_t* label, double* tumour, double* centre,
+                     double* size, double* together, int32_t* labels, double* series, bnmf_subtypes_info* info) {
+  return subtypes_impl(h, "bnmf_subtypes_at", {true, end_iter, n_samples}, used, include, perm, centres0, C, n_steps, query, Q, min_certainty, membership, label,
+                       tumour, centre, size, together, labels, series, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

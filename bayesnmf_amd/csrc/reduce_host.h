@@ -1,10 +1,11 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
-// (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's and bnmf_similarity's.  No
-// device and no handle: posterior.h includes it, and a stand-alone host program can (tools/coactivity_reduce_check.cpp,
-// tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp and tools/similarity_reduce_check.cpp, built with
-// -fsanitize=address,undefined by tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py and
-// tests/test_similarity_host.py).  Compile with -ffp-contract=off, as the library is.
+// (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's, bnmf_similarity's and
+// bnmf_subtypes' (DESIGN.md 25).  No device and no handle: posterior.h includes it, and a stand-alone host program can
+// (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp,
+// tools/similarity_reduce_check.cpp and tools/subtypes_reduce_check.cpp, built with -fsanitize=address,undefined by
+// tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py, tests/test_similarity_host.py and
+// tests/test_subtypes_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -253,4 +254,62 @@ template <class Work> static void deal_threads(long nwork, Work work) {
   }
   info->n_similar_pairs = deg / 2;                          // p_similar is bitwise symmetric: every pair was counted from both sides
   info->n_isolated = iso; info->mean_similarity = con_canon64(tum, (size_t)m, 1) / (double)m; info->least_typical = least; info->least_typical_at = at;
+}
+
+// ---- bnmf_subtypes' finish: from the counts over the matched samples to the outputs by tumour and the info fields ----
+// members [m] ascending; cnt [C][m], assigned [m], tog / both [Q][m] (null with Q = 0) the whole-number counts in member order as the device
+// left them; cen [Sm][N*C] and sizes [Sm][C] per matched sample.  membership [C][G], label [G], tumour [3][G], centre [4][N*C], size [4][C],
+// together [Q][G] may each be null; a left-out tumour holds NaN / -1.  Of info n_included, n_left_out, n_certain, n_never_assigned,
+// mean_certainty, least_certain(_at) and smallest_subtype(_at) are set.
+[[maybe_unused]] static void subtypes_finish(const int* members, long m, long G, int N, int C, int Sm, const int32_t* cnt, const int32_t* assigned, int Q,
+                                             const int32_t* query, const int32_t* tog, const int32_t* both, const double* cen, const int32_t* sizes,
+                                             double min_certainty, double* membership, int32_t* label, double* tumour, double* centre, double* size,
+                                             double* together, bnmf_subtypes_info* info) {
+  const double nan = std::nan("");
+  info->n_included = (int32_t)m; info->n_left_out = (int32_t)(G - m);
+  if (membership) std::fill(membership, membership + (size_t)C * G, nan);
+  if (label) std::fill(label, label + G, (int32_t)-1);
+  if (tumour) std::fill(tumour, tumour + (size_t)BNMF_SUB_NTUM * G, nan);
+  if (together) std::fill(together, together + (size_t)Q * G, nan);
+  std::vector<double> cert;                                   // the certainties of the members that have one, in member order
+  int32_t ncertain = 0, nnever = 0; int64_t at = -1; double least = nan;
+  for (long i = 0; i < m; ++i) {
+    const size_t g = (size_t)members[i];
+    const int32_t ag = assigned[i];
+    if (tumour) tumour[(size_t)G + g] = (double)ag / (double)Sm;
+    if (ag == 0) { ++nnever; continue; }
+    int best = 0, second = -1;
+    for (int c = 1; c < C; ++c) if (cnt[(size_t)c * m + i] > cnt[(size_t)best * m + i]) best = c;
+    for (int c = 0; c < C; ++c) if (c != best && (second < 0 || cnt[(size_t)c * m + i] > cnt[(size_t)second * m + i])) second = c;
+    const double ce = (double)cnt[(size_t)best * m + i] / (double)ag;
+    if (membership) for (int c = 0; c < C; ++c) membership[(size_t)c * G + g] = (double)cnt[(size_t)c * m + i] / (double)ag;
+    if (label) label[g] = best;
+    if (tumour) { tumour[g] = ce; tumour[2 * (size_t)G + g] = (double)cnt[(size_t)second * m + i] / (double)ag; }
+    cert.push_back(ce);
+    ncertain += ce >= min_certainty ? 1 : 0;
+    if (at < 0 || ce < least) { least = ce; at = (int64_t)g; }
+  }
+  info->n_certain = ncertain; info->n_never_assigned = nnever; info->least_certain = least; info->least_certain_at = at;
+  info->mean_certainty = cert.empty() ? nan : con_canon64(cert.data(), cert.size(), 1) / (double)cert.size();
+  if (together)
+    for (int q = 0; q < Q; ++q)
+      for (long i = 0; i < m; ++i) {
+        const size_t e = (size_t)q * m + i;
+        if (members[i] != query[q] && both[e] > 0) together[(size_t)q * G + (size_t)members[i]] = (double)tog[e] / (double)both[e];
+      }
+  // the centres and the sizes over the matched samples: con_rows at the fixed interval 0.95
+  const size_t NC = (size_t)N * C;
+  std::vector<double> x(Sm), tmp(Sm), row(4);
+  if (centre)
+    for (size_t e = 0; e < NC; ++e) {
+      for (int s = 0; s < Sm; ++s) x[s] = cen[(size_t)s * NC + e];
+      con_rows(x.data(), Sm, 0.95, tmp.data(), centre + e, NC);
+    }
+  info->smallest_subtype = nan; info->smallest_subtype_at = -1;
+  for (int c = 0; c < C; ++c) {
+    for (int s = 0; s < Sm; ++s) x[s] = (double)sizes[(size_t)s * C + c];
+    con_rows(x.data(), Sm, 0.95, tmp.data(), row.data(), 1);
+    if (size) for (int k = 0; k < 4; ++k) size[(size_t)k * C + c] = row[k];
+    if (!std::isnan(row[0]) && (info->smallest_subtype_at < 0 || row[0] < info->smallest_subtype)) { info->smallest_subtype = row[0]; info->smallest_subtype_at = c; }
+  }
 }

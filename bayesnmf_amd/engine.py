@@ -132,6 +132,13 @@ class BnmfSimilarityInfo(C.Structure):
                 ("least_typical_at", C.c_int64), ("mean_similarity", C.c_double), ("least_typical", C.c_double), ("min_cosine", C.c_double)]
 
 
+class BnmfSubtypesInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_matched", C.c_int32), ("n_unmatched", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32),
+                ("C", C.c_int32), ("n_steps", C.c_int32), ("n_query", C.c_int32), ("n_not_converged", C.c_int32), ("n_certain", C.c_int32),
+                ("n_never_assigned", C.c_int32), ("smallest_subtype_at", C.c_int32), ("least_certain_at", C.c_int64), ("mean_certainty", C.c_double),
+                ("least_certain", C.c_double), ("smallest_subtype", C.c_double), ("min_certainty", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -159,6 +166,9 @@ REC_SIGNATURE_ROWS = ["n_tumours", "mean_drop", "max_drop"]
 SIM_ROWS = ["mean", "var", "p_similar"]
 SIM_TUMOUR_ROWS = ["typicality", "nearest_mean", "degree"]
 SIM_MAX_K = 32
+SUB_TUMOUR_ROWS = ("certainty", "assigned", "runner_up")
+SUB_ROWS = ("mean", "var", "lower", "upper")
+SUB_SERIES_ROWS = ("inertia", "steps", "n_assigned")
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -178,7 +188,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_attribution", "bnmf_attribution_at", "bnmf_relabel", "bnmf_relabel_at", "bnmf_project", "bnmf_project_at",
                "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
                "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
-               "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at"]
+               "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at",
+               "bnmf_subtypes", "bnmf_subtypes_at"]
 
 
 def lib():
@@ -253,6 +264,9 @@ def lib():
         L.bnmf_reconstruction_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_double, C.c_double, dp, dp, dp, dp, C.POINTER(BnmfReconstructionInfo)]
         L.bnmf_similarity.argtypes = [C.c_void_p, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_double, ip, dp, dp, dp, C.POINTER(BnmfSimilarityInfo)]
         L.bnmf_similarity_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, ip, ip, C.c_int, C.c_int, C.c_double, ip, dp, dp, dp, C.POINTER(BnmfSimilarityInfo)]
+        sub = [ip, ip, ip, dp, C.c_int, C.c_int, ip, C.c_int, C.c_double, dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(BnmfSubtypesInfo)]
+        L.bnmf_subtypes.argtypes = [C.c_void_p, C.c_int] + sub
+        L.bnmf_subtypes_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + sub
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -868,6 +882,53 @@ class Engine:
     def similarity_at(self, end_iter, n_samples, **kw):
         """similarity over the n_samples iterations that end at end_iter (bnmf_similarity_at)."""
         return self.similarity(n_samples, end_iter=end_iter, **kw)
+
+    def subtypes(self, last_n, centres0, include=None, perm=None, n_steps=50, query=None, min_certainty=0.9, used=None, end_iter=None, labels=False):
+        """Subtypes of the tumours over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last
+        `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_subtypes / bnmf_subtypes_at), on the device: every
+        used sample's share profiles are clustered by at most n_steps Lloyd steps from centres0 (N x C), the same start for every sample.
+        include (length G of 0 / 1, None = all): the tumours that enter.  perm (last_n x N over the whole range, relabel's; a row of -1
+        leaves the sample out; None = identity) aligns the factors first.  Returns the info fields, membership (C x G), label (G, -1 =
+        none), tumour (3 x G) and its rows by name (SUB_TUMOUR_ROWS), centre (4 x N x C) and size (4 x C) (the rows SUB_ROWS over the
+        matched samples, interval 0.95), series (3 x S: SUB_SERIES_ROWS, NaN for an unmatched sample); with query (Q tumours) together
+        (Q x G: the share of samples in which query[q] and g carry the same label); with labels the S x G labels of every used sample
+        (-1 unassigned, -2 left out or unmatched)."""
+        G, N = self.G, self.N
+        c0 = np.asarray(centres0, dtype=np.float64)
+        if c0.ndim != 2 or c0.shape[0] != N:
+            raise BnmfError(-2, f"subtypes: centres0 has shape {c0.shape}, N = {N} rows are needed")
+        c0 = np.asfortranarray(c0)
+        Cn = int(c0.shape[1])
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"subtypes: include has shape {inc.shape}, G = {G} flags are needed")
+        pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        if pm is not None and pm.shape != (last_n, N):
+            raise BnmfError(-2, f"subtypes: perm is {pm.shape}, not {(last_n, N)}")
+        qv = None if query is None else np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        Q = 0 if qv is None else int(qv.size)
+        u, S = self._used("subtypes", used, last_n)
+        Cb = min(max(Cn, 1), 32)                               # (an invalid C is refused by the library: the buffers only have to exist)
+        mem, lab, tum = np.empty((Cb, G)), np.empty(G, dtype=np.int32), np.empty((3, G))
+        cen, siz, ser = np.empty((4, Cb, N)), np.empty((4, Cb)), np.empty((3, S))
+        tog = np.empty((Q, G)) if Q > 0 else None
+        lbs = np.empty((S, G), dtype=np.int32) if labels else None
+        info = BnmfSubtypesInfo()
+        ipt = lambda v: None if v is None else v.ctypes.data_as(_IP)  # noqa: E731
+        self._range_call("subtypes", last_n, end_iter, u, ipt(inc), ipt(pm), _dp(c0), Cn, int(n_steps), ipt(qv), Q, float(min_certainty), _dp(mem), ipt(lab),
+                         _dp(tum), _dp(cen), _dp(siz), _dp(tog), ipt(lbs), _dp(ser), C.byref(info))
+        out = self._info(info)
+        out.update(membership=mem, label=lab, tumour=tum, centre=np.ascontiguousarray(cen.transpose(0, 2, 1)), size=siz, series=ser)
+        out.update({name: tum[i] for i, name in enumerate(SUB_TUMOUR_ROWS)})
+        if tog is not None:
+            out.update(together=tog, query=qv.copy())
+        if lbs is not None:
+            out["labels"] = lbs
+        return out
+
+    def subtypes_at(self, end_iter, n_samples, centres0, **kw):
+        """subtypes over the n_samples iterations that end at end_iter (bnmf_subtypes_at)."""
+        return self.subtypes(n_samples, centres0, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

@@ -107,6 +107,25 @@ def regression_design(covariates, G, intercept=True, standardize=False):
     return np.asfortranarray(X), (None if complete.all() else complete.astype(np.int32)), names
 
 
+def subtype_seeds(profiles, C, member=None):
+    """The start of get_subtypes(n_subtypes = C): C tumours by a deterministic farthest-first walk over the share profiles (N x G; member:
+    G flags of the tumours that may be chosen, None = all).  The first seed is the member nearest (squared Euclidean distance) to the
+    members' mean profile; each next seed is the member farthest from its nearest chosen seed; the lower tumour wins a tie."""
+    prof = np.asarray(profiles, dtype=np.float64)
+    G = prof.shape[1]
+    mem = np.ones(G, dtype=bool) if member is None else np.asarray(member, dtype=bool)
+    if C < 1 or C > int(mem.sum()):
+        raise ValueError(f"{C} seeds cannot be chosen among {int(mem.sum())} tumours")
+    d = ((prof - prof[:, mem].mean(axis=1, keepdims=True)) ** 2).sum(axis=0)
+    seeds = [int(np.argmin(np.where(mem, d, np.inf)))]                     # (argmin and argmax return the first of equals: the lower tumour)
+    near = ((prof - prof[:, [seeds[0]]]) ** 2).sum(axis=0)
+    while len(seeds) < C:
+        g = int(np.argmax(np.where(mem, near, -np.inf)))
+        seeds.append(g)
+        near = np.minimum(near, ((prof - prof[:, [g]]) ** 2).sum(axis=0))
+    return np.asarray(seeds, dtype=np.int32)
+
+
 class bayesNMF_sampler:
     """Python mirror of the R6 class `bayesNMF_sampler` (public fields of R/bayesNMF_sampler.R:11-67)."""
 
@@ -1026,8 +1045,113 @@ class bayesNMF_sampler:
                  f"{r['mean_similarity']:.3g}, least typical {r['least_typical']:.3g} (tumour {r['least_typical_at']})", verbosity=1)
         return out
 
+    def get_subtypes(self, n_subtypes=None, centres=None, seeds=None, include=None, query=None, relabel=True, n_steps=50, min_certainty=0.9,
+                     end_iter=None, n_samples=None, idx="MAP_idx", labels=False):
+        """Does the cohort fall into subtypes, and how certain is the grouping?  On the device (bnmf_subtypes_at; not in the reference):
+        over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as get_contrast), every
+        sample's share profiles (each tumour's renormalised exposures divided by their sum) are clustered by at most n_steps Lloyd steps
+        from one common start, so subtype c means the same in every sample; a tumour's membership of c is the share of samples in which
+        it carries label c.  With relabel the range is first aligned by get_relabelling() and its perm is handed on; an unmatched
+        sample is left out.  The start: centres (N x C share profiles), or seeds (C tumours, indices or names: their posterior-mean
+        share profiles), or n_subtypes alone: seeds chosen by a deterministic farthest-first walk over the posterior-mean share profiles
+        (subtype_seeds).  include and query as in get_similarity.
+        Returns dict(tumours (a data frame: tumour, label, certainty, runner_up, assigned, included, membership_0 ...), subtypes (a data
+        frame: subtype, size, size_sd, size_lower, size_upper), centres (a data frame: subtype, factor, mean, sd, lower, upper),
+        consensus (a data frame: query, tumour, together; only with query), centres0, seeds, membership, label, tumour, centre, size,
+        series, together, labels (the arrays of the call) and its info fields)."""
+        if not hasattr(self._chain, "subtypes"):
+            raise ValueError("get_subtypes needs an engine that clusters tumours over its recorded samples (subtypes); this engine_factory's cannot")
+        G, N = self.dims["G"], self.dims["N"]
+        names = self.tumour_names if getattr(self, "tumour_names", None) else None
+
+        def tumours(v, what):
+            vs = list(np.atleast_1d(v).tolist())
+            if names is not None and all(isinstance(q, str) for q in vs):
+                missing = [q for q in vs if q not in names]
+                if missing:
+                    raise ValueError(f"{what} names no tumour of the data: {missing[:5]}")
+                vs = [names.index(q) for q in vs]
+            return np.asarray(vs, dtype=np.int32)
+
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        qv = None if query is None else tumours(query, "query")
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        perm = None
+        if relabel:
+            rows = np.asarray(self.get_relabelling(end_iter=end_iter, n_samples=n_samples, idx=idx)["perm"], dtype=np.int32)
+            perm = np.full((n, N), -1, dtype=np.int32)                   # perm has a row per used sample: scattered into the range's rows
+            perm[slice(None) if used is None else np.asarray(used) != 0] = rows
+        seed_at = None
+        if centres is not None:
+            c0 = np.asarray(centres, dtype=np.float64)
+            if c0.ndim != 2 or c0.shape[0] != N:
+                raise ValueError(f"centres is {c0.shape}, but a start is N = {N} rows by C columns")
+        else:
+            if seeds is None and n_subtypes is None:
+                raise ValueError("get_subtypes needs one of n_subtypes, centres and seeds")
+            prof = self._mean_share_profiles(n, used, perm, kw)
+            member = np.ones(G, dtype=bool) if inc is None else inc.astype(bool)
+            seed_at = tumours(seeds, "seeds") if seeds is not None else subtype_seeds(prof, int(n_subtypes), member)
+            if (~member[seed_at]).any():
+                raise ValueError("a seed is a tumour that include leaves out")
+            c0 = prof[:, seed_at]
+        if n_subtypes is not None and c0.shape[1] != int(n_subtypes):
+            raise ValueError(f"n_subtypes = {n_subtypes}, but the start has {c0.shape[1]} columns")
+        r = self._chain.subtypes(n, c0, include=inc, perm=perm, n_steps=n_steps, query=qv, min_certainty=min_certainty, used=used, labels=labels, **kw)
+        label = (lambda g: names[g]) if names is not None else (lambda g: int(g))
+        Cn = int(r["C"])
+        tum, mem = np.asarray(r["tumour"]).reshape(3, G), np.asarray(r["membership"]).reshape(Cn, G)
+        included = np.ones(G, dtype=bool) if inc is None else inc.astype(bool)
+        frame = dict(tumour=[label(g) for g in range(G)], label=np.asarray(r["label"]), certainty=tum[0], runner_up=tum[2], assigned=tum[1], included=included)
+        frame.update({f"membership_{c}": mem[c] for c in range(Cn)})
+        size, cen = np.asarray(r["size"]).reshape(4, Cn), np.asarray(r["centre"]).reshape(4, N, Cn)
+        out = dict(r)
+        out.update(tumours=pd.DataFrame(frame),
+                   subtypes=pd.DataFrame(dict(subtype=np.arange(Cn), size=size[0], size_sd=np.sqrt(size[1]), size_lower=size[2], size_upper=size[3])),
+                   centres=pd.DataFrame([(c, j, cen[0, j, c], float(np.sqrt(cen[1, j, c])), cen[2, j, c], cen[3, j, c]) for c in range(Cn) for j in range(N)],
+                                        columns=["subtype", "factor", "mean", "sd", "lower", "upper"]),
+                   centres0=np.asarray(c0), seeds=None if seed_at is None else [label(g) for g in seed_at])
+        if qv is not None:
+            tog = np.asarray(r["together"]).reshape(qv.size, G)
+            out["consensus"] = pd.DataFrame([(label(g), label(t), tog[i, t]) for i, g in enumerate(qv) for t in range(G)], columns=["query", "tumour", "together"])
+            out["query"] = [label(g) for g in qv]
+        self.log(f"Subtypes: {Cn} subtypes of {r['n_included']} tumours over {r['n_matched']} samples ({r['n_unmatched']} unmatched, {r['n_not_converged']} not "
+                 f"converged in {r['n_steps']} steps); {r['n_certain']} tumours with certainty >= {r['min_certainty']:g}, mean certainty "
+                 f"{r['mean_certainty']:.3g}, least certain {r['least_certain']:.3g} (tumour {r['least_certain_at']}); smallest subtype "
+                 f"{r['smallest_subtype_at']} with {r['smallest_subtype']:.3g} tumours", verbosity=1)
+        return out
+
+    def _mean_share_profiles(self, n, used, perm, kw):
+        """N x G: the mean over the used, matched samples of the range of every tumour's aligned share profile (the host's start of
+        get_subtypes; a sample in which a tumour has no exposure does not enter its mean)."""
+        it = self.state["iter"]
+        end = kw.get("end_iter", it)
+        back = it - (end - n + 1) + 1
+        win = {nm: self._chain.window(nm, back)[:n] for nm in ("P", "E", "A")}
+        N, G = self.dims["N"], self.dims["G"]
+        tot, cnt = np.zeros((N, G)), np.zeros(G)
+        for s in range(n):
+            if (used is not None and not used[s]) or (perm is not None and (perm[s] < 0).all()):
+                continue
+            x = np.asarray(win["E"][s], dtype=float) * np.asarray(win["P"][s], dtype=float).sum(axis=0)[:, None] * (np.ravel(win["A"][s]) != 0)[:, None]
+            t = x.sum(axis=0)
+            ok = (t > 0) & np.isfinite(t)
+            q = np.zeros((N, G))
+            q[np.arange(N) if perm is None else perm[s]] = np.where(ok, x / np.where(ok, t, 1.0), 0.0)
+            tot += q
+            cnt += ok
+        return tot / np.where(cnt > 0, cnt, 1.0)
+
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

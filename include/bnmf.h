@@ -682,6 +682,89 @@ int bnmf_similarity_at(bnmf_handle*, int end_iter, int n_samples, const int32_t*
                        int top_k, double min_cosine, int32_t* neighbour_at, double* neighbour, double* dense, double* tumour,
                        bnmf_similarity_info* info);
 
+/* Subtypes of tumours over recorded samples, on the device: does the cohort fall into subtypes, and how certain is the
+ * grouping?  Every recorded sample flagged in used[] (oldest first; NULL = all) is clustered by the same Lloyd iteration (k-means) from
+ * the same start centres0, so subtype c means the same thing in every sample; the statistics over the samples say how often a tumour
+ * carries which label.  The members are the m included tumours g_0 < g_1 < ... (include[g] != 0; NULL = all), position i = 0 .. m-1.
+ * Per used sample s, with cs_s[n] bnmf_map's column sum of P_s:
+ *   x[n,g] = A_s[n] != 0 ? E_s[n,g] * cs_s[n] : +0.0              bnmf_contrast's renormalised exposure, the same bits
+ *   t      = sum_n x[n,g]                                           n ascending from +0.0
+ *   g is unassigned in s unless t > 0 && t < inf: its label is -1, it enters every sum below as +0.0 and enters no count
+ *   u = 1 / t;  r[n] = x[n,g] * u                                   the share profile
+ *   q[perm[s][n]] = r[n]                                            the aligned profile; perm NULL: q = r
+ * perm [last_n][N] (row-major, a row per sample of the whole range, read for the used ones) is bnmf_relabel's: a row of -1 throughout
+ * leaves the sample out whole (unmatched, as bnmf_stability leaves it out); every other row must be a permutation of 0 .. N-1.  The
+ * matched samples are S' of the S used ones.
+ * Lloyd steps from mu = centres0 (N x C column-major, mu[j,c] at j + N c):
+ *   assign  d(g,c) = sum_j (q[j] - mu[j,c]) * (q[j] - mu[j,c])    j ascending from +0.0; subtract, multiply, add rounded separately
+ *           label = 0, dmin = d(g,0); for c = 1 .. C-1 in order: d(g,c) replaces them only if d(g,c) < dmin.  The lowest c wins a tie,
+ *           a NaN never replaces anything (a NaN d(g,0) stays: label 0, dmin NaN)
+ *   update  n_c = #(label == c);  where n_c > 0:  mu[j,c] = canonB_i(label_i == c ? q_i[j] : +0.0) / n_c;  n_c == 0 keeps the centre.
+ *           canonB is bnmf_regress's blocked canonical sum over the positions i of the member list: blocks of BNMF_REG_BLOCK positions,
+ *           each the canonical W = 64 sum (accumulator l adds positions l, l + 64, ... of the block ascending from +0.0, then the
+ *           halving tree), the block sums added ascending from +0.0
+ *   stop    after the first step that changes no label (step 1 is compared with all -1), or after n_steps.  steps_s = the steps run.
+ * The sample's labels are the last assignment's, its centres and n_c the update after it, inertia_s = canonB_i(dmin_i) of that assignment
+ * (an unassigned tumour +0.0).
+ * Over the matched samples, with count_c[g] = #(label_s[g] == c) and a_g = the samples in which g is assigned:
+ * membership [C][G]: count_c[g] / a_g; NaN where a_g == 0 or g is left out.
+ * label [G]: the c of the largest count, the lowest c among equals; -1 where a_g == 0 or g is left out.
+ * tumour [BNMF_SUB_NTUM][G]: 0 certainty = membership[label[g]][g]; 1 a_g / S'; 2 the runner-up: the largest membership of a c other
+ *   than label[g].  Rows 0 and 2 are NaN where a_g == 0; all rows NaN for a left-out tumour.
+ * centre [BNMF_SUB_NCROW][N*C] and size [BNMF_SUB_NCROW][C]: over the S' samples of every centre coordinate (j + N c) and of every n_c the
+ *   rows 0 mean (the canonical W = 64 sum / S'), 1 variance (the canonical sum of (v - mean)^2 / (S' - 1)), 2 and 3 the type-7 quantiles
+ *   at (1 - 0.95) / 2 and (1 + 0.95) / 2, as bnmf_contrast forms them.  The credible interval is fixed at 0.95.
+ * together [Q][G]: the consensus row of query[q]: #(label_s[query[q]] == label_s[g] >= 0) / #(both assigned in s); NaN where that is 0,
+ *   where g is left out or g == query[q].  All tumours of a small cohort as queries give the consensus matrix.
+ * labels [S][G] (a row per USED sample): the sample's labels; -2 for a left-out tumour, -1 for an unassigned one, -2 throughout for an
+ *   unmatched sample.
+ * series [BNMF_SUB_NSER][S]: 0 inertia_s, 1 steps_s, 2 the assigned tumours of s; NaN for an unmatched sample.
+ * info: n_used = S, n_matched = S', n_unmatched, n_included = m, n_left_out = G - m, C, n_steps, n_query = Q, min_certainty as given;
+ *   n_not_converged = the samples that ran n_steps steps and changed a label in the last; n_certain = the members with certainty >=
+ *   min_certainty; n_never_assigned = the members with a_g == 0; mean_certainty = the canonical W = 64 sum of the certainties of the
+ *   members that have one, in member order, divided by their number (NaN without one); least_certain and least_certain_at = the smallest
+ *   certainty and its g (the first wins; NaN and -1 without one); smallest_subtype and smallest_subtype_at = the smallest size row 0 and
+ *   its c (the first wins).
+ * Only + - * /, comparisons and whole numbers, no contraction, no square root, every sum in the order above: the bits depend on the
+ * samples, used[], include[], perm, centres0, n_steps and query[] only, not on the form of the kernel, its tiles or the batch of samples
+ * that passes through the scratch.  Every sum over tumours runs over the member list and a tumour's own values involve no other tumour,
+ * so include[] gives the bits of a cohort without the tumours left out.  Reads only the P, E and A rings; works for every likelihood
+ * and prior; draws no random number, consumes none of the chain's streams and is read-only for the chain.  bnmf_subtypes_at: the
+ * n_samples iterations that end at end_iter; the range rule, used[], BNMF_ESIZE and BNMF_ESTATE as for bnmf_similarity_at;
+ * bnmf_subtypes(h, n, ...) is bnmf_subtypes_at(h, iter, n, ...).  Every output array may be NULL.  Refused before any device work, with
+ * BNMF_EINVAL: a null info or centres0; a used[] or include[] value other than 0 / 1 (the index named); C outside 2 .. BNMF_SUB_MAX_C;
+ * n_steps outside 1 .. BNMF_SUB_MAX_STEPS; Q < 0 or Q > 0 with a null query; a query[q] outside 0 .. G-1 or left out (q named); a cell
+ * of centres0 that is NaN, infinite or negative (the first one named); a min_certainty that is NaN or outside [0, 1]; a perm row of a
+ * used sample that is neither a permutation nor -1 throughout (the sample named).  With BNMF_ESIZE: fewer than 2 used samples, fewer
+ * than 2 matched samples, m < C, N > BNMF_SUB_MAX_N.  With BNMF_ESTATE: window = 0, a poisoned handle or nothing recorded. */
+#define BNMF_SUB_NTUM  3         /* tumour rows: certainty, share of samples assigned, runner-up membership */
+#define BNMF_SUB_NCROW 4         /* centre and size rows: mean, variance, lower, upper (0.95) */
+#define BNMF_SUB_NSER  3         /* series rows: inertia, steps, assigned tumours */
+#define BNMF_SUB_MAX_C 32        /* the most subtypes */
+#define BNMF_SUB_MAX_N 128       /* the most factors */
+#define BNMF_SUB_MAX_STEPS 1000  /* the most Lloyd steps */
+typedef struct { int32_t n_used, n_matched, n_unmatched, n_included, n_left_out, C, n_steps, n_query, n_not_converged, n_certain,
+                 n_never_assigned, smallest_subtype_at /* c */; int64_t least_certain_at /* g; -1 if none */;
+                 double mean_certainty, least_certain, smallest_subtype, min_certainty; } bnmf_subtypes_info;
+int bnmf_subtypes(bnmf_handle*, int last_n, const int32_t* used,
+                  const int32_t* include  /* [G] 0 / 1, NULL = all */,
+                  const int32_t* perm     /* [last_n][N] row-major: bnmf_relabel's perm over the whole range; NULL = identity */,
+                  const double*  centres0 /* N x C column-major */, int C, int n_steps,
+                  const int32_t* query    /* [Q] tumours, may be NULL with Q = 0 */, int Q, double min_certainty,
+                  double*  membership /* [C][G]; may be NULL */,
+                  int32_t* label      /* [G]; may be NULL */,
+                  double*  tumour     /* [BNMF_SUB_NTUM][G]; may be NULL */,
+                  double*  centre     /* [BNMF_SUB_NCROW][N*C]; may be NULL */,
+                  double*  size       /* [BNMF_SUB_NCROW][C]; may be NULL */,
+                  double*  together   /* [Q][G]; may be NULL */,
+                  int32_t* labels     /* [S][G]; may be NULL */,
+                  double*  series     /* [BNMF_SUB_NSER][S]; may be NULL */,
+                  bnmf_subtypes_info* info);
+int bnmf_subtypes_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm,
+                     const double* centres0, int C, int n_steps, const int32_t* query, int Q, double min_certainty, double* membership,
+                     int32_t* label, double* tumour, double* centre, double* size, double* together, int32_t* labels, double* series,
+                     bnmf_subtypes_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

@@ -443,6 +443,97 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       r$n_included, r$n_left_out, r$n_similar_pairs, r$n_pairs, r$min_cosine, r$n_isolated, r$mean_similarity))
       out
     },
+    # Subtypes of the tumours, on the device (bnmf_subtypes_at; not in the reference): does the cohort fall into subtypes, and how certain
+    # is the grouping?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every sample's
+    # share profiles are clustered by at most n_steps Lloyd steps from one common start, so subtype c means the same in every sample; a
+    # tumour's membership of c is the share of samples in which it carries label c.  With relabel the range is first aligned by
+    # get_relabelling() and its perm is handed on; an unmatched sample is left out.  The start: centres (N x C share profiles), or seeds
+    # (C tumours, 1-based indices or column names: their share profiles in the MAP exposures), or n_subtypes alone: seeds chosen by a
+    # deterministic farthest-first walk over those profiles (the first is nearest the mean profile, each next is farthest from its
+    # nearest chosen seed, the lower tumour wins a tie).  include and query as in get_similarity.  list(tumours (a data frame: tumour,
+    # label (1-based, NA = none), certainty, runner_up, assigned, included), membership (C x G), subtypes (a data frame: subtype, size,
+    # size_sd, size_lower, size_upper), centre (4 x N x C: mean, variance, lower, upper at 0.95), consensus (Q x G, with query), series
+    # (3 x S: inertia, steps, assigned tumours), labels (S x G, 1-based, 0 = unassigned, NA = left out or unmatched; with labels = TRUE),
+    # centres0, seeds and the info fields).
+    get_subtypes = function(n_subtypes = NULL, centres = NULL, seeds = NULL, include = NULL, query = NULL, relabel = TRUE, n_steps = 50,
+                            min_certainty = 0.9, end_iter = self$state$iter,
+                            n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx", labels = FALSE) {
+      first <- end_iter - n_samples + 1
+      idx0 <- idx
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G; N <- self$dims$N
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      member <- if (is.null(include)) rep(TRUE, G) else include
+      names <- colnames(self$data)
+      label <- function(g) if (is.null(names)) g else names[g]
+      tumours <- function(v, what) {
+        if (is.character(v)) {
+          at <- match(v, names)
+          if (anyNA(at)) stop(what, " names no tumour of the data: ", paste(utils::head(v[is.na(at)], 5), collapse = ", "))
+          at
+        } else as.integer(v)
+      }
+      q <- if (is.null(query)) NULL else tumours(query, "query")
+      perm <- NULL
+      if (relabel) {
+        pm <- self$get_relabelling(end_iter = end_iter, n_samples = n_samples, idx = if (is.null(idx0)) NULL else idx0)$perm
+        pm <- t(matrix(as.integer(pm), nrow = N))                       # get_relabelling's is N x S: here S x N, 1-based labels, NA = unmatched
+        perm <- matrix(-1L, n_samples, N)
+        perm[if (is.null(used)) seq_len(n_samples) else which(used), ] <- ifelse(is.na(pm), -1L, pm - 1L)
+      }
+      seed_at <- NULL
+      if (!is.null(centres)) {
+        c0 <- as.matrix(centres)
+        if (nrow(c0) != N) stop("centres must have N = ", N, " rows")
+      } else {
+        if (is.null(seeds) && is.null(n_subtypes)) stop("get_subtypes needs one of n_subtypes, centres and seeds")
+        E <- matrix(0, N, G); E[self$MAP$keep_sigs, ] <- self$MAP$E
+        prof <- sweep(E, 2, pmax(colSums(E), .Machine$double.xmin), "/")
+        if (!is.null(seeds)) seed_at <- tumours(seeds, "seeds") else {
+          d <- colSums((prof - rowMeans(prof[, member, drop = FALSE]))^2); d[!member] <- Inf
+          seed_at <- which.min(d)                                       # (which.min and which.max return the first of equals)
+          near <- colSums((prof - prof[, seed_at])^2)
+          while (length(seed_at) < n_subtypes) {
+            g <- which.max(ifelse(member, near, -Inf)); seed_at <- c(seed_at, g)
+            near <- pmin(near, colSums((prof - prof[, g])^2))
+          }
+        }
+        if (any(!member[seed_at])) stop("a seed is a tumour that include leaves out")
+        c0 <- prof[, seed_at, drop = FALSE]
+      }
+      C <- ncol(c0)
+      r <- .Call("C_bnmf_subtypes", self$handle, as.integer(end_iter), as.integer(n_samples), used, include, perm, matrix(as.double(c0), N, C),
+                 if (is.null(q)) NULL else as.integer(q - 1L), as.double(c(n_steps, min_certainty, if (labels) 1 else 0, K, G, N)))
+      lab <- ifelse(r$label < 0, NA_integer_, r$label + 1L)
+      out <- r[c("n_used", "n_matched", "n_unmatched", "n_included", "n_left_out", "C", "n_steps", "n_query", "n_not_converged", "n_certain",
+                 "n_never_assigned", "mean_certainty", "least_certain", "smallest_subtype", "min_certainty")]
+      out$least_certain_at <- if (r$least_certain_at < 0) NA_integer_ else as.integer(r$least_certain_at) + 1L
+      out$smallest_subtype_at <- r$smallest_subtype_at + 1L
+      out$tumours <- data.frame(tumour = label(seq_len(G)), label = lab, certainty = r$tumour[, 1], runner_up = r$tumour[, 3], assigned = r$tumour[, 2],
+                                included = member)
+      out$membership <- t(r$membership)
+      out$subtypes <- data.frame(subtype = seq_len(C), size = r$size[, 1], size_sd = sqrt(r$size[, 2]), size_lower = r$size[, 3], size_upper = r$size[, 4])
+      out$centre <- aperm(array(r$centre, c(N, C, 4)), c(3, 1, 2))
+      out$series <- t(r$series)
+      out$centres0 <- c0
+      out$seeds <- if (is.null(seed_at)) NULL else label(seed_at)
+      if (!is.null(q)) { out$consensus <- t(r$together); out$query <- label(q) }
+      if (labels) out$labels <- t(ifelse(r$labels == -2L, NA_integer_, r$labels + 1L))
+      message(sprintf("Subtypes: %d subtypes of %d tumours over %d samples (%d unmatched, %d not converged in %d steps); %d tumours with certainty >= %g, mean certainty %.3g",
+                      C, r$n_included, r$n_matched, r$n_unmatched, r$n_not_converged, r$n_steps, r$n_certain, r$min_certainty, r$mean_certainty))
+      out
+    },
     # Co-activity of the signatures, on the device (bnmf_coactivity_at; not in the reference): do two signatures act in the same tumours
     # or exclude each other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are
     # negatively correlated)?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every

@@ -809,6 +809,92 @@ SEXP C_bnmf_similarity_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SE
   UNPROTECT(1);
   return out;
 }
+/* Subtypes of tumours over recorded samples on the device (bnmf_subtypes / bnmf_subtypes_at): C_bnmf_subtypes(ptr, end_iter (integer, or
+ * NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or NULL = all),
+ * perm (integer n_samples x N matrix of 0-based places, a row of -1 / NA = the sample is unmatched; or NULL = identity), centres0 (N x C
+ * real matrix), query (integer, 0-based tumours; or NULL), opts (real c(n_steps, min_certainty, want_labels 0 / 1, K, G, N))) ->
+ * list(n_used, n_matched, n_unmatched, n_included, n_left_out, C, n_steps, n_query, n_not_converged, n_certain, n_never_assigned,
+ * smallest_subtype_at (0-based), least_certain_at (0-based tumour, -1 = none), mean_certainty, least_certain, smallest_subtype,
+ * min_certainty, membership (G x C), label (integer G, 0-based, -1 = none), tumour (G x 3: certainty, share of samples assigned,
+ * runner-up), centre (N C x 4: mean, variance, lower, upper at 0.95, row j + N c), size (C x 4), together (G x Q; NULL without a
+ * query), labels (G x S integer, -1 unassigned, -2 left out or unmatched; NULL unless want_labels is 1), series (S x 3: inertia, steps,
+ * assigned tumours)) over iterations end_iter - n_samples + 1 ... end_iter.  C_bnmf_subtypes_at: the same with end_iter required */
+/* the result list with its arrays allocated and the inputs converted; returned unprotected */
+typedef struct { int32_t *u, *inc, *perm, *q; int Q, C, n_steps; double min_certainty; } sub_in;
+static SEXP sub_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP centres0, SEXP query, SEXP opts, sub_in* in) {
+  const int n = INTEGER(n_samples)[0];
+  if (XLENGTH(opts) != 6) Rf_error("bnmf: opts has %ld entries, c(n_steps, min_certainty, want_labels, K, G, N) is needed", (long)XLENGTH(opts));
+  const double* o = REAL(opts);
+  const int G = (int)o[4], N = (int)o[5];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  if (perm != R_NilValue && XLENGTH(perm) != (R_xlen_t)n * N) Rf_error("bnmf: perm has %ld entries for %d samples of %d factors", (long)XLENGTH(perm), n, N);
+  if (N < 1 || XLENGTH(centres0) < (R_xlen_t)N || XLENGTH(centres0) % N != 0)
+    Rf_error("bnmf: centres0 has %ld entries, whole columns of N = %d are needed", (long)XLENGTH(centres0), N);
+  in->u = lgl_flags(used, n);
+  in->inc = lgl_flags(include, G);
+  in->perm = NULL;
+  if (perm != R_NilValue) {                                                /* the R matrix is column-major: row s of the ABI is its row s */
+    in->perm = (int32_t*)R_alloc((size_t)n * N, sizeof(int32_t));
+    for (int s = 0; s < n; ++s) for (int j = 0; j < N; ++j) { const int v = INTEGER(perm)[s + (size_t)n * j]; in->perm[(size_t)s * N + j] = v == NA_INTEGER ? -1 : v; }
+  }
+  in->Q = query == R_NilValue ? 0 : (int)XLENGTH(query);
+  in->q = in->Q > 0 ? (int32_t*)INTEGER(query) : NULL;
+  in->C = (int)(XLENGTH(centres0) / N); in->n_steps = (int)o[0]; in->min_certainty = o[1];
+  int S = n < 0 ? 0 : n;
+  if (in->u) { S = 0; for (int i = 0; i < n; ++i) S += in->u[i]; }
+  const int Cb = in->C > BNMF_SUB_MAX_C ? BNMF_SUB_MAX_C : in->C;          /* (the library refuses a larger C: the buffers only have to exist) */
+  static const char* nms[] = {"n_used", "n_matched", "n_unmatched", "n_included", "n_left_out", "C", "n_steps", "n_query", "n_not_converged", "n_certain",
+                              "n_never_assigned", "smallest_subtype_at", "least_certain_at", "mean_certainty", "least_certain", "smallest_subtype",
+                              "min_certainty", "membership", "label", "tumour", "centre", "size", "together", "labels", "series"};
+  SEXP out = PROTECT(named_list(25, nms));
+  SET_VECTOR_ELT(out, 17, Rf_allocMatrix(REALSXP, G, Cb));
+  SET_VECTOR_ELT(out, 18, Rf_allocVector(INTSXP, G));
+  SET_VECTOR_ELT(out, 19, Rf_allocMatrix(REALSXP, G, BNMF_SUB_NTUM));
+  SET_VECTOR_ELT(out, 20, Rf_allocMatrix(REALSXP, N * Cb, BNMF_SUB_NCROW));
+  SET_VECTOR_ELT(out, 21, Rf_allocMatrix(REALSXP, Cb, BNMF_SUB_NCROW));
+  if (in->Q > 0) SET_VECTOR_ELT(out, 22, Rf_allocMatrix(REALSXP, G, in->Q));
+  if (o[2] == 1.0) SET_VECTOR_ELT(out, 23, Rf_allocMatrix(INTSXP, G, S));
+  SET_VECTOR_ELT(out, 24, Rf_allocMatrix(REALSXP, S, BNMF_SUB_NSER));
+  UNPROTECT(1);
+  return out;
+}
+static int32_t* sub_int_buf(SEXP out, int i) { SEXP x = VECTOR_ELT(out, i); return x == R_NilValue ? NULL : (int32_t*)INTEGER(x); }
+static void sub_finish(SEXP out, const bnmf_subtypes_info* info) {
+  const int32_t v[12] = {info->n_used, info->n_matched, info->n_unmatched, info->n_included, info->n_left_out, info->C, info->n_steps, info->n_query,
+                         info->n_not_converged, info->n_certain, info->n_never_assigned, info->smallest_subtype_at};
+  for (int i = 0; i < 12; ++i) SET_VECTOR_ELT(out, i, Rf_ScalarInteger(v[i]));
+  SET_VECTOR_ELT(out, 12, Rf_ScalarReal((double)info->least_certain_at)); SET_VECTOR_ELT(out, 13, Rf_ScalarReal(info->mean_certainty));
+  SET_VECTOR_ELT(out, 14, Rf_ScalarReal(info->least_certain)); SET_VECTOR_ELT(out, 15, Rf_ScalarReal(info->smallest_subtype));
+  SET_VECTOR_ELT(out, 16, Rf_ScalarReal(info->min_certainty));
+}
+SEXP C_bnmf_subtypes(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP centres0, SEXP query, SEXP opts) {
+  sub_in in;
+  SEXP out = PROTECT(sub_alloc(n_samples, used, include, perm, centres0, query, opts, &in));
+  bnmf_subtypes_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_subtypes(get_handle(ptr), INTEGER(n_samples)[0], in.u, in.inc, in.perm, REAL(centres0), in.C, in.n_steps, in.q, in.Q, in.min_certainty,
+                      map_buf(out, 17), sub_int_buf(out, 18), map_buf(out, 19), map_buf(out, 20), map_buf(out, 21), map_buf(out, 22), sub_int_buf(out, 23),
+                      map_buf(out, 24), &info));
+  else
+    chk(bnmf_subtypes_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.perm, REAL(centres0), in.C, in.n_steps, in.q, in.Q,
+                         in.min_certainty, map_buf(out, 17), sub_int_buf(out, 18), map_buf(out, 19), map_buf(out, 20), map_buf(out, 21), map_buf(out, 22),
+                         sub_int_buf(out, 23), map_buf(out, 24), &info));
+  sub_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_subtypes_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP centres0, SEXP query, SEXP opts) {
+  sub_in in;
+  SEXP out = PROTECT(sub_alloc(n_samples, used, include, perm, centres0, query, opts, &in));
+  bnmf_subtypes_info info;
+  chk(bnmf_subtypes_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.perm, REAL(centres0), in.C, in.n_steps, in.q, in.Q,
+                       in.min_certainty, map_buf(out, 17), sub_int_buf(out, 18), map_buf(out, 19), map_buf(out, 20), map_buf(out, 21), map_buf(out, 22),
+                       sub_int_buf(out, 23), map_buf(out, 24), &info));
+  sub_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Silhouette stability of the recorded signatures on the device (bnmf_stability / bnmf_stability_at): C_bnmf_stability(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), labels (integer n_samples x N
  * matrix of 0-based clusters, -1 / NA = left out; or NULL = the factor), extra_P (K x X real matrix, or NULL), extra_label (integer X,
@@ -1177,6 +1263,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_stability", (DL_FUNC)&C_bnmf_stability, 8}, {"C_bnmf_stability_at", (DL_FUNC)&C_bnmf_stability_at, 8},
   {"C_bnmf_reconstruction", (DL_FUNC)&C_bnmf_reconstruction, 7}, {"C_bnmf_reconstruction_at", (DL_FUNC)&C_bnmf_reconstruction_at, 7},
   {"C_bnmf_similarity", (DL_FUNC)&C_bnmf_similarity, 9}, {"C_bnmf_similarity_at", (DL_FUNC)&C_bnmf_similarity_at, 9},
+  {"C_bnmf_subtypes", (DL_FUNC)&C_bnmf_subtypes, 9}, {"C_bnmf_subtypes_at", (DL_FUNC)&C_bnmf_subtypes_at, 9},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
