@@ -45,6 +45,7 @@
 #include "reconstruction.h"
 #include "similarity.h"
 #include "subtypes.h"
+#include "residuals.h"
 
 using namespace bnmf;
 

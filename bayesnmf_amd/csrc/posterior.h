@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h and subtypes.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h and residuals.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1672,6 +1672,103 @@ static int subtypes_impl(bnmf_handle* h, const char* fn, Range r, const int32_t*
   return 0;
 }
 
+// Residual structure over the samples of r that used[] flags (residuals.h): the member list is made here; k_rec_data leaves
+// the data k-major once; then per batch of samples k_rec_x, k_res_z (z and chi in the scratch), k_res_b, k_res_gram (C_s), k_res_power
+// (the component, the series, flat), k_res_score and k_res_accum (the accumulators of the mean matrix), and the batch's scores and chi
+// are copied out.  k_res_mean ends the mean matrix; its component, the alignment, the moments and the info fields are residuals_finish's.
+static_assert(RS_NTYPE == BNMF_RES_NTYPE && RS_NCOMP == BNMF_RES_NCOMP && RS_NTUM == BNMF_RES_NTUM && RS_NSER == BNMF_RES_NSER && RS_MAX_K == BNMF_RES_MAX_K,
+              "residuals.h and bnmf.h disagree");
+static constexpr size_t RES_SCRATCH_CAP = (size_t)256 << 20;    // bytes of a batch's z, C_s, scores, chi and x
+static int residuals_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, int n_steps, double max_dispersion, double* gram,
+                          double* type, double* component, double* tumour, double* series, bnmf_residuals_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  const bool normal = h->cfg.likelihood == BNMF_NORMAL;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members;
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) members.push_back(g);
+  }
+  const int m = (int)members.size(), S = (int)slots.size();
+  if (n_steps < 1 || n_steps > BNMF_RES_MAX_STEPS) return fail(BNMF_EINVAL, "%s: n_steps = %d is outside 1..%d", fn, n_steps, BNMF_RES_MAX_STEPS);
+  if (!(max_dispersion >= 0.0)) return fail(BNMF_EINVAL, "%s: max_dispersion = %g is NaN or negative", fn, max_dispersion);
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (m < 2) return fail(BNMF_ESIZE, "%s: %d included tumour%s, at least 2 are needed", fn, m, m == 1 ? "" : "s");
+  if (K > BNMF_RES_MAX_K) return fail(BNMF_ESIZE, "%s: K = %d mutation types, at most %d are taken", fn, K, BNMF_RES_MAX_K);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring || (normal && !h->arr[BNMF_SIGMASQ].ring))
+    return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  int form = 0;
+  if (const char* e = getenv("BNMF_RES_FORM")) if (atoi(e) == 1) form = 1;                                // tests, tools: the small tile, any N
+  const bool reg = form == 0 && N <= RS_MAX_NT;
+  const int NS = reg ? ((N + 7) / 8) * 8 : N;
+  const size_t KK = (size_t)K * K, Km = (size_t)K * m, KNS = (size_t)K * NS;
+  const size_t per = (Km + KK + 2 * (size_t)m + KNS) * sizeof(double);                                     // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, RES_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_RES_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>({want, (long long)S, 65535LL});                                  // (a batch is the grid's y)
+  ResArgs a{};
+  double *dMt, *dmm, *dtt, *dxg, *dacc, *dgram; int *dslots, *dmem;
+  if (int rc = carve(h, [&](Carve& c) {
+        dMt = c.take<double>((size_t)K * G); dmm = c.take<double>(G); dtt = c.take<double>(G); dxg = c.take<double>((size_t)Sb * KNS);
+        a.z = c.take<double>((size_t)Sb * Km); a.chi = c.take<double>((size_t)Sb * m); a.t = c.take<double>((size_t)Sb * m); a.C = c.take<double>((size_t)Sb * KK);
+        a.b = c.take<double>((size_t)S * K); a.q = c.take<double>((size_t)S * K); a.v = c.take<double>((size_t)S * K); a.ser = c.take<double>(4 * (size_t)S);
+        a.flat = c.take<int>(S); dacc = c.take<double>(64 * KK); dgram = c.take<double>(KK); dslots = c.take<int>(S); dmem = c.take<int>(m);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(dacc, 0, 64 * KK * sizeof(double), h->stream));
+  hipLaunchKernelGGL(k_rec_data<RC_NTUM>, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)h->dMf, K, G, dMt, dmm, dtt);
+  a.ringE = h->arr[BNMF_E].ring; a.ringS = normal ? h->arr[BNMF_SIGMASQ].ring : nullptr; a.xg = dxg; a.Mt = dMt; a.slots = dslots; a.members = dmem;
+  a.lenE = (size_t)N * G; a.K = K; a.N = N; a.NS = NS; a.G = G; a.m = m; a.S = S; a.n_steps = n_steps;
+  using ZKernel = decltype(&k_res_z<false, 0>);
+  const ZKernel zp[5] = {k_res_z<false, 0>, k_res_z<false, 8>, k_res_z<false, 16>, k_res_z<false, 24>, k_res_z<false, 32>};
+  const ZKernel zn[5] = {k_res_z<true, 0>, k_res_z<true, 8>, k_res_z<true, 16>, k_res_z<true, 24>, k_res_z<true, 32>};
+  const ZKernel kz = (normal ? zn : zp)[reg ? NS / 8 : 0];
+  const int T = form == 0 ? 8 : 4, nt = (K + T - 1) / T;
+  const unsigned ntp = (unsigned)((size_t)nt * (nt + 1) / 2), gm = (unsigned)((m + RS_T - 1) / RS_T), gk = (unsigned)((KK + 255) / 256);
+  const double *ringP = h->arr[BNMF_P].ring, *ringA = h->arr[BNMF_A].ring;
+  std::vector<double> ht((size_t)S * m), hchi((size_t)S * m);
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0);
+    a.s0 = s0;
+    hipLaunchKernelGGL(k_rec_x<RC_NTUM>, dim3(nb), dim3(256), 0, h->stream, ringP, ringA, (size_t)K * N, K, N, NS, (const int*)dslots + s0, dxg);
+    hipLaunchKernelGGL(kz, dim3(gm, (unsigned)nb), dim3(RS_T), 0, h->stream, a);
+    hipLaunchKernelGGL(k_res_b<RS_NTYPE>, dim3((unsigned)K, (unsigned)nb), dim3(64), 0, h->stream, a);
+    if (form == 0) hipLaunchKernelGGL(k_res_gram<8>, dim3(ntp, (unsigned)nb), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_res_gram<4>, dim3(ntp, (unsigned)nb), dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL(k_res_power<RS_NTYPE>, dim3((unsigned)nb), dim3(RS_T), 2 * (size_t)K * sizeof(double), h->stream, a);
+    hipLaunchKernelGGL(k_res_score<RS_NTYPE>, dim3(gm, (unsigned)nb), dim3(RS_T), 0, h->stream, a);
+    hipLaunchKernelGGL(k_res_accum<RS_NTYPE>, dim3(gk), dim3(256), 0, h->stream, (const double*)a.C, (const int*)a.flat, s0, nb, KK, dacc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ht.data() + (size_t)s0 * m, a.t, (size_t)nb * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hchi.data() + (size_t)s0 * m, a.chi, (size_t)nb * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  hipLaunchKernelGGL(k_res_mean<RS_NTYPE>, dim3(gk), dim3(256), 0, h->stream, (const int*)a.flat, S, KK, dacc, dgram);
+  HIPCHK(hipGetLastError());
+  std::vector<double> hb((size_t)S * K), hq((size_t)S * K), hv((size_t)S * K), hser(4 * (size_t)S), hg(KK);
+  std::vector<int32_t> hflat(S);
+  HIPCHK(hipMemcpyAsync(hb.data(), a.b, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hq.data(), a.q, hq.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hv.data(), a.v, hv.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hser.data(), a.ser, hser.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hflat.data(), a.flat, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hg.data(), dgram, KK * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  int Sp = 0;
+  for (int s = 0; s < S; ++s) Sp += hflat[s] ? 0 : 1;
+  if (Sp < 2) return fail(BNMF_ESIZE, "%s: %d sample%s of %d used that %s not flat, the variance over the samples needs at least 2", fn, Sp, Sp == 1 ? "" : "s", S,
+                          Sp == 1 ? "is" : "are");
+  std::memset(info, 0, sizeof *info);
+  residuals_finish(members.data(), m, G, K, S, n_steps, max_dispersion, hflat.data(), hg.data(), hser.data(), hb.data(), hq.data(), hv.data(), ht.data(),
+                   hchi.data(), type, component, tumour, series, info);
+  info->n_used = S; info->n_steps = n_steps; info->max_dispersion = max_dispersion;
+  if (gram) std::memcpy(gram, hg.data(), KK * sizeof(double));
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1811,6 +1908,15 @@ int bnmf_subtypes_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t*
                      double* size, double* together, int32_t* labels, double* series, bnmf_subtypes_info* info) {
   return subtypes_impl(h, "bnmf_subtypes_at", {true, end_iter, n_samples}, used, include, perm, centres0, C, n_steps, query, Q, min_certainty, membership, label,
                        tumour, centre, size, together, labels, series, info);
+}
+
+int bnmf_residuals(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, int n_steps, double max_dispersion, double* gram, double* type,
+                   double* component, double* tumour, double* series, bnmf_residuals_info* info) {
+  return residuals_impl(h, "bnmf_residuals", {false, 0, last_n}, used, include, n_steps, max_dispersion, gram, type, component, tumour, series, info);
+}
+int bnmf_residuals_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_dispersion, double* gram,
+                      double* type, double* component, double* tumour, double* series, bnmf_residuals_info* info) {
+  return residuals_impl(h, "bnmf_residuals_at", {true, end_iter, n_samples}, used, include, n_steps, max_dispersion, gram, type, component, tumour, series, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

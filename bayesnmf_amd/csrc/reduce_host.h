@@ -1,11 +1,11 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
-// (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's, bnmf_similarity's and
-// bnmf_subtypes' (DESIGN.md 25).  No device and no handle: posterior.h includes it, and a stand-alone host program can
+// (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's, bnmf_similarity's,
+// bnmf_subtypes'  and bnmf_residuals' (DESIGN.md 26).  No device and no handle: posterior.h includes it, and a stand-alone host program can
 // (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp,
-// tools/similarity_reduce_check.cpp and tools/subtypes_reduce_check.cpp, built with -fsanitize=address,undefined by
-// tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py, tests/test_similarity_host.py and
-// tests/test_subtypes_host.py).  Compile with -ffp-contract=off, as the library is.
+// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp and tools/residuals_reduce_check.cpp, built with
+// -fsanitize=address,undefined by tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py,
+// tests/test_similarity_host.py, tests/test_subtypes_host.py and tests/test_residuals_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -312,4 +312,114 @@ template <class Work> static void deal_threads(long nwork, Work work) {
     if (size) for (int k = 0; k < 4; ++k) size[(size_t)k * C + c] = row[k];
     if (!std::isnan(row[0]) && (info->smallest_subtype_at < 0 || row[0] < info->smallest_subtype)) { info->smallest_subtype = row[0]; info->smallest_subtype_at = c; }
   }
+}
+
+// ---- bnmf_residuals' finish: the mean matrix's component, the alignment, the moments over the samples, the info fields ----
+// The leading component of the symmetric K x K matrix C (row-major), the routine of k_res_power operation for operation: v [K] the
+// component with its sign fixed, y [K] a work vector.  Returns false for a flat matrix (v is then undefined).
+struct res_lead { double trace, lambda, share, move; };
+[[maybe_unused]] static bool residuals_lead(const double* C, int K, int n_steps, double* v, double* y, res_lead* out) {
+  double tr = 0.0, best = C[0];
+  int ks = 0;
+  for (int k = 0; k < K; ++k) {
+    const double d = C[(size_t)k * K + k];
+    tr = tr + d;
+    if (d > best) { best = d; ks = k; }
+  }
+  out->trace = tr; out->lambda = out->share = out->move = std::nan("");
+  if (!(tr > 0.0 && std::isfinite(tr))) return false;
+  for (int k = 0; k < K; ++k) y[k] = C[(size_t)k * K + ks];
+  for (int step = 0; step <= n_steps + 1; ++step) {
+    double nn = 0.0;
+    for (int k = 0; k < K; ++k) nn = nn + y[k] * y[k];
+    if (!(nn > 0.0 && std::isfinite(nn))) return false;
+    const double r = std::sqrt(nn);
+    if (step == n_steps + 1) {
+      double l = 0.0, mx = 0.0;
+      for (int k = 0; k < K; ++k) l = l + v[k] * y[k];
+      for (int k = 0; k < K; ++k) { const double d = std::fabs(y[k] / r - v[k]); mx = d > mx ? d : mx; }
+      out->lambda = l; out->move = mx; out->share = l / tr;
+      break;
+    }
+    for (int k = 0; k < K; ++k) v[k] = y[k] / r;
+    for (int k = 0; k < K; ++k) {
+      double acc = 0.0;
+      const double* row = C + (size_t)k * K;
+      for (int j = 0; j < K; ++j) acc = acc + row[j] * v[j];
+      y[k] = acc;
+    }
+  }
+  int at = 0;
+  double big = std::fabs(v[0]);
+  for (int k = 1; k < K; ++k) { const double d = std::fabs(v[k]); if (d > big) { big = d; at = k; } }
+  if (v[at] < 0.0) for (int k = 0; k < K; ++k) v[k] = -v[k];
+  return true;
+}
+// members [m] ascending; flat [S]; gram [K*K] the mean matrix over the S' samples that are not flat (S' >= 2: the caller refuses less);
+// ser4 [4][S]: tr, lambda, share, move per used sample; bs, qs, vs [S][K]; ts, chis [S][m] in member order.  type [5][K], component
+// [4][K], tumour [3][G], series [5][S] may each be null.  Of info every field but n_used, n_steps and max_dispersion is set.
+[[maybe_unused]] static void residuals_finish(const int* members, long m, long G, int K, int S, int n_steps, double max_dispersion, const int32_t* flat,
+                                              const double* gram, const double* ser4, const double* bs, const double* qs, const double* vs, const double* ts,
+                                              const double* chis, double* type, double* component, double* tumour, double* series, bnmf_residuals_info* info) {
+  const double nan = std::nan("");
+  std::vector<int> live;                                      // the samples that are not flat, in order
+  for (int s = 0; s < S; ++s) if (!flat[s]) live.push_back(s);
+  const int Sp = (int)live.size();
+  info->n_flat = S - Sp; info->n_included = (int32_t)m; info->n_left_out = (int32_t)(G - m);
+  std::vector<double> vbar(K), y(K), x(Sp), tmp(Sp), row(4), a(S, nan), sgn(S, 1.0);
+  res_lead lead;
+  const bool ok = residuals_lead(gram, K, n_steps, vbar.data(), y.data(), &lead);
+  if (!ok) std::fill(vbar.begin(), vbar.end(), nan);
+  info->lambda = lead.lambda; info->share = lead.share; info->move = lead.move;
+  info->min_agreement = nan; info->min_agreement_at = -1;
+  for (int j = 0; j < Sp; ++j) {
+    const int s = live[j];
+    double d = 0.0;
+    for (int k = 0; k < K; ++k) d = d + vs[(size_t)s * K + k] * vbar[k];
+    a[s] = d; sgn[s] = d < 0.0 ? -1.0 : 1.0;
+    const double ad = std::fabs(d);
+    if (info->min_agreement_at < 0 || ad < info->min_agreement) { info->min_agreement = ad; info->min_agreement_at = s; }
+    x[j] = ser4[2 * (size_t)S + s];
+  }
+  info->mean_share = con_canon64(x.data(), Sp, 1) / (double)Sp;
+  if (series)
+    for (int s = 0; s < S; ++s) {
+      for (int q = 0; q < 4; ++q) series[(size_t)q * S + s] = flat[s] ? nan : ser4[(size_t)q * S + s];
+      series[4 * (size_t)S + s] = a[s];
+    }
+  // the rows by type and by component
+  info->n_biased = info->n_overdispersed = 0; info->worst_type = nan; info->worst_type_at = -1;
+  for (int k = 0; k < K; ++k) {
+    int pos = 0;
+    for (int j = 0; j < Sp; ++j) { x[j] = bs[(size_t)live[j] * K + k]; pos += x[j] > 0.0 ? 1 : 0; }
+    con_rows(x.data(), Sp, 0.0, tmp.data(), row.data(), 1);
+    const double pb = (double)pos / (double)Sp;
+    if (type) { type[k] = row[0]; type[(size_t)K + k] = row[1]; type[2 * (size_t)K + k] = pb; }
+    info->n_biased += (pb <= 0.025 || pb >= 0.975) ? 1 : 0;
+    for (int j = 0; j < Sp; ++j) x[j] = qs[(size_t)live[j] * K + k];
+    con_rows(x.data(), Sp, 0.0, tmp.data(), row.data(), 1);
+    if (type) { type[3 * (size_t)K + k] = row[0]; type[4 * (size_t)K + k] = row[1]; }
+    info->n_overdispersed += row[0] > max_dispersion ? 1 : 0;
+    if (!std::isnan(row[0]) && (info->worst_type_at < 0 || row[0] > info->worst_type)) { info->worst_type = row[0]; info->worst_type_at = k; }
+    if (component) {
+      pos = 0;
+      for (int j = 0; j < Sp; ++j) { x[j] = sgn[live[j]] * vs[(size_t)live[j] * K + k]; pos += x[j] > 0.0 ? 1 : 0; }
+      con_rows(x.data(), Sp, 0.0, tmp.data(), row.data(), 1);
+      component[k] = vbar[k]; component[(size_t)K + k] = row[0]; component[2 * (size_t)K + k] = row[1]; component[3 * (size_t)K + k] = (double)pos / (double)Sp;
+    }
+  }
+  if (!tumour) return;
+  std::fill(tumour, tumour + (size_t)BNMF_RES_NTUM * G, nan);
+  auto work = [&](long lo, long hi) {
+    std::vector<double> xx(Sp), tt(Sp), rr(4);
+    for (long i = lo; i < hi; ++i) {
+      const size_t g = (size_t)members[i];
+      for (int j = 0; j < Sp; ++j) xx[j] = sgn[live[j]] * ts[(size_t)live[j] * m + i];
+      con_rows(xx.data(), Sp, 0.0, tt.data(), rr.data(), 1);
+      tumour[g] = rr[0]; tumour[(size_t)G + g] = rr[1];
+      for (int j = 0; j < Sp; ++j) xx[j] = chis[(size_t)live[j] * m + i];
+      tumour[2 * (size_t)G + g] = con_canon64(xx.data(), Sp, 1) / (double)Sp;
+    }
+  };
+  deal_threads(m, work);
 }

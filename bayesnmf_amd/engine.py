@@ -139,6 +139,13 @@ class BnmfSubtypesInfo(C.Structure):
                 ("least_certain", C.c_double), ("smallest_subtype", C.c_double), ("min_certainty", C.c_double)]
 
 
+class BnmfResidualsInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_flat", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32), ("n_steps", C.c_int32),
+                ("n_biased", C.c_int32), ("n_overdispersed", C.c_int32), ("worst_type_at", C.c_int32), ("min_agreement_at", C.c_int32), ("_pad", C.c_int32),
+                ("lambda", C.c_double), ("share", C.c_double), ("move", C.c_double), ("mean_share", C.c_double), ("min_agreement", C.c_double),
+                ("worst_type", C.c_double), ("max_dispersion", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -169,6 +176,10 @@ SIM_MAX_K = 32
 SUB_TUMOUR_ROWS = ("certainty", "assigned", "runner_up")
 SUB_ROWS = ("mean", "var", "lower", "upper")
 SUB_SERIES_ROWS = ("inertia", "steps", "n_assigned")
+RES_TYPE_ROWS = ("bias", "bias_var", "p_positive", "dispersion", "dispersion_var")
+RES_COMPONENT_ROWS = ("vbar", "mean", "var", "p_positive")
+RES_TUMOUR_ROWS = ("score", "score_var", "chi")
+RES_SERIES_ROWS = ("trace", "lambda", "share", "move", "agreement")
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -189,7 +200,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
                "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
                "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at",
-               "bnmf_subtypes", "bnmf_subtypes_at"]
+               "bnmf_subtypes", "bnmf_subtypes_at", "bnmf_residuals", "bnmf_residuals_at"]
 
 
 def lib():
@@ -267,6 +278,9 @@ def lib():
         sub = [ip, ip, ip, dp, C.c_int, C.c_int, ip, C.c_int, C.c_double, dp, ip, dp, dp, dp, dp, ip, dp, C.POINTER(BnmfSubtypesInfo)]
         L.bnmf_subtypes.argtypes = [C.c_void_p, C.c_int] + sub
         L.bnmf_subtypes_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + sub
+        res = [ip, ip, C.c_int, C.c_double, dp, dp, dp, dp, dp, C.POINTER(BnmfResidualsInfo)]
+        L.bnmf_residuals.argtypes = [C.c_void_p, C.c_int] + res
+        L.bnmf_residuals_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + res
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -929,6 +943,34 @@ class Engine:
     def subtypes_at(self, end_iter, n_samples, centres0, **kw):
         """subtypes over the n_samples iterations that end at end_iter (bnmf_subtypes_at)."""
         return self.subtypes(n_samples, centres0, end_iter=end_iter, **kw)
+
+    def residuals(self, last_n, include=None, n_steps=100, max_dispersion=2.0, used=None, end_iter=None):
+        """Residual structure over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,
+        or with end_iter of the `last_n` that end at iteration end_iter (bnmf_residuals / bnmf_residuals_at), on the device: per used
+        sample the standardised residuals of every cell, their K x K second-moment matrix over the included tumours (include: length G
+        of 0 / 1, None = all), its leading component by n_steps power steps and every tumour's score on it.  Returns the info fields,
+        gram (K x K: the mean matrix), type (5 x K: RES_TYPE_ROWS), component (4 x K: RES_COMPONENT_ROWS), tumour (3 x G:
+        RES_TUMOUR_ROWS, NaN for a left-out tumour) and series (5 x S: RES_SERIES_ROWS, NaN for a flat sample), and the rows of type,
+        component and tumour by name.  max_dispersion only sets the count n_overdispersed: a reporting convention, not a test."""
+        G, K = self.G, self.K
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"residuals: include has shape {inc.shape}, G = {G} flags are needed")
+        u, S = self._used("residuals", used, last_n)
+        gram, typ, comp, tum, ser = np.empty((K, K)), np.empty((5, K)), np.empty((4, K)), np.empty((3, G)), np.empty((5, S))
+        info = BnmfResidualsInfo()
+        self._range_call("residuals", last_n, end_iter, u, None if inc is None else inc.ctypes.data_as(_IP), int(n_steps), float(max_dispersion), _dp(gram),
+                         _dp(typ), _dp(comp), _dp(tum), _dp(ser), C.byref(info))
+        out = self._info(info)
+        out.update(gram=gram, type=typ, component=comp, tumour=tum, series=ser)
+        out.update({name: typ[i] for i, name in enumerate(RES_TYPE_ROWS)})
+        out["vbar"] = comp[0]
+        out.update({name: tum[i] for i, name in enumerate(RES_TUMOUR_ROWS)})
+        return out
+
+    def residuals_at(self, end_iter, n_samples, **kw):
+        """residuals over the n_samples iterations that end at end_iter (bnmf_residuals_at)."""
+        return self.residuals(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

@@ -107,6 +107,16 @@ def regression_design(covariates, G, intercept=True, standardize=False):
     return np.asfortranarray(X), (None if complete.all() else complete.astype(np.int32)), names
 
 
+def residual_candidate(vbar):
+    """The candidate signature of get_residuals: the positive part of the component vbar (K), or of -vbar where the negative part has the
+    larger sum of squares, normalised to sum 1 (all NaN where vbar is not finite or has no such part)."""
+    v = np.asarray(vbar, dtype=np.float64)
+    pos, neg = np.maximum(v, 0.0), np.maximum(-v, 0.0)
+    part = neg if (neg * neg).sum() > (pos * pos).sum() else pos
+    tot = part.sum()
+    return part / tot if np.isfinite(tot) and tot > 0 else np.full(v.shape, np.nan)
+
+
 def subtype_seeds(profiles, C, member=None):
     """The start of get_subtypes(n_subtypes = C): C tumours by a deterministic farthest-first walk over the share profiles (N x G; member:
     G flags of the tumours that may be chosen, None = all).  The first seed is the member nearest (squared Euclidean distance) to the
@@ -1129,6 +1139,66 @@ class bayesNMF_sampler:
                  f"{r['smallest_subtype_at']} with {r['smallest_subtype']:.3g} tumours", verbosity=1)
         return out
 
+    def get_residuals(self, include=None, n_steps=100, max_dispersion=2.0, reference_P=None, end_iter=None, n_samples=None, idx="MAP_idx"):
+        """What does the model leave unexplained: is there a process in the leftovers?  On the device (bnmf_residuals_at; not in the
+        reference): over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as get_contrast),
+        every sample's standardised residuals, their second-moment matrix over the included tumours along the mutation types, its leading
+        component (n_steps power steps) and every tumour's score on it.  A direction that the misfits of many tumours share is what a
+        missing signature looks like: a rank that is too low.  include as in get_similarity.  max_dispersion = 2.0 is a reporting
+        convention like min_cosine = 0.9 (it only sets the count n_overdispersed), not a test.
+        Returns dict(types (a data frame: type, bias, bias_sd, p_positive, dispersion, dispersion_sd, component, component_mean,
+        component_sd), tumours (a data frame: tumour, score, score_sd, chi, included), candidate (K: the positive part of the mean
+        matrix's component, or of its negative where that part has the larger sum of squares, normalised to sum 1),
+        candidate_cosine (N: with the columns of the range's mean renormalised P); with reference_P (K x R, a data frame's columns name
+        the signatures) reference_cosine (R), best_reference and best_reference_cosine; gram, type, component, tumour, series (the arrays
+        of the call) and its info fields)."""
+        if not hasattr(self._chain, "residuals"):
+            raise ValueError("get_residuals needs an engine that forms residuals over its recorded samples (residuals); this engine_factory's cannot")
+        K, G, N = self.dims["K"], self.dims["G"], self.dims["N"]
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.residuals(n, include=inc, n_steps=n_steps, max_dispersion=max_dispersion, used=used, **kw)
+        out = dict(r)
+        typ, comp, tum = np.asarray(r["type"]).reshape(5, K), np.asarray(r["component"]).reshape(4, K), np.asarray(r["tumour"]).reshape(3, G)
+        out["candidate"] = cand = residual_candidate(comp[0])
+
+        def cosines(cols):
+            den = np.sqrt((cols * cols).sum(axis=0) * (cand * cand).sum())
+            return np.where(den > 0, (cols * cand[:, None]).sum(axis=0) / np.where(den > 0, den, 1.0), np.nan)
+
+        it = self.state["iter"]
+        back = it - (kw.get("end_iter", it) - n + 1) + 1
+        Ps = [np.asarray(p, dtype=float) for s, p in enumerate(self._chain.window("P", back)[:n]) if used is None or used[s]]
+        Pm = np.mean([p / np.where(p.sum(axis=0) > 0, p.sum(axis=0), 1.0) for p in Ps], axis=0)
+        out["candidate_cosine"] = cosines(Pm)
+        if reference_P is not None:
+            ref = np.asarray(reference_P, dtype=np.float64)
+            if ref.ndim != 2 or ref.shape[0] != K:
+                raise ValueError(f"reference_P is {ref.shape}, but a catalogue has K = {K} rows")
+            rc = cosines(ref)
+            best = int(np.nanargmax(rc)) if not np.isnan(rc).all() else -1
+            cols = list(reference_P.columns) if hasattr(reference_P, "columns") else list(range(ref.shape[1]))
+            out.update(reference_cosine=rc, best_reference=cols[best] if best >= 0 else None, best_reference_cosine=float(rc[best]) if best >= 0 else float("nan"))
+        names = self.tumour_names if getattr(self, "tumour_names", None) else None
+        included = np.ones(G, dtype=bool) if inc is None else inc.astype(bool)
+        out.update(types=pd.DataFrame(dict(type=np.arange(K), bias=typ[0], bias_sd=np.sqrt(typ[1]), p_positive=typ[2], dispersion=typ[3],
+                                           dispersion_sd=np.sqrt(typ[4]), component=comp[0], component_mean=comp[1], component_sd=np.sqrt(comp[2]))),
+                   tumours=pd.DataFrame(dict(tumour=[names[g] if names is not None else g for g in range(G)], score=tum[0], score_sd=np.sqrt(tum[1]), chi=tum[2],
+                                             included=included)))
+        self.log(f"Residuals: {r['n_included']} tumours over {r['n_used'] - r['n_flat']} samples ({r['n_flat']} flat); the leading component carries "
+                 f"{r['share']:.3g} of the mean matrix's trace (per sample {r['mean_share']:.3g} on average, smallest agreement {r['min_agreement']:.3g}); "
+                 f"{r['n_overdispersed']} types with dispersion > {r['max_dispersion']:g} (worst: type {r['worst_type_at']} at {r['worst_type']:.3g}), "
+                 f"{r['n_biased']} biased", verbosity=1)
+        return out
+
     def _mean_share_profiles(self, n, used, perm, kw):
         """N x G: the mean over the used, matched samples of the range of every tumour's aligned share profile (the host's start of
         get_subtypes; a sample in which a tumour has no exposure does not enter its mean)."""
@@ -1151,7 +1221,7 @@ class bayesNMF_sampler:
         return tot / np.where(cnt > 0, cnt, 1.0)
 
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes / get_residuals: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

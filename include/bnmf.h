@@ -765,6 +765,69 @@ int bnmf_subtypes_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* u
                      int32_t* label, double* tumour, double* centre, double* size, double* together, int32_t* labels, double* series,
                      bnmf_subtypes_info* info);
 
+/* Residual structure of recorded samples, on the device: what does the model leave unexplained, and do the misfits of
+ * different tumours point in the same direction?  A shared direction is what a missing signature looks like: a rank that is too LOW.
+ * The members are the m included tumours g_0 < g_1 < ... (include[g] != 0; NULL = all), position i = 0 .. m-1.  Per recorded sample s
+ * flagged in used[] (oldest first; NULL = all), member i (tumour g) and mutation type k, M the data cell as a double:
+ *   c = bnmf_reconstruction's pre_N (bnmf_waic's c_s), the same bits: from +0.0, n ascending, + (P_s[k,n] * A_s[n]) * E_s[n,g]
+ *   Poisson: lam = c < 1e-6 ? 1e-6 : c;  z = (M - lam) / sqrt(lam).     Normal: z = (M - c) / sqrt(sigmasq_s[g]), real-valued data included
+ *   C_s[k,k'] = canonB_i(z[k,i] * z[k',i]) / m  for k' <= k, mirrored: bitwise symmetric.  The product is rounded before it is added; canonB is
+ *     bnmf_regress's blocked canonical sum over the positions i of the member list (blocks of BNMF_REG_BLOCK, each the canonical W = 64 sum,
+ *     the block sums added ascending from +0.0)
+ *   b_s[k] = canonB_i(z[k,i]) / m;   q_s[k] = C_s[k,k];   tr_s = sum_k C_s[k,k], k ascending from +0.0;   chi_s[i] = (sum_k z z) / K, k ascending
+ * The leading component of a symmetric K x K matrix C, one routine for every C_s (device) and for the mean matrix (host):
+ *   1 k* = the largest diagonal element, the first wins;  y = C[:,k*]
+ *   2 nn = sum_k y[k] y[k], k ascending from +0.0;  v = y / sqrt(nn)
+ *   3 n_steps times: y[k] = sum_k' C[k,k'] v[k'], k' ascending from +0.0, multiply and add rounded separately; then 2
+ *   4 one further product y = C v:  lambda = sum_k v[k] y[k];  nn = sum_k y[k] y[k];  move = max_k |y[k] / sqrt(nn) - v[k]| (how far one
+ *     more step would go; the maximum from +0.0, k ascending)
+ *   5 v is flipped so that its element of largest magnitude (the first wins) is positive;  share = lambda / trace
+ *   The matrix is flat if its trace is not > 0 and finite or if any nn (that of 4 included) is not > 0 and finite.  A flat sample is left
+ *   out of everything below, as an unmatched sample is in bnmf_subtypes; S' of the S used samples are not flat.
+ *   t_s[i] = sum_k v_s[k] z[k,i], k ascending from +0.0: the tumour's score on the sample's component.
+ * Over the S' samples, means and variances in bnmf_contrast's canonical W = 64 forms over s (mean = canon(x) / S', variance =
+ * canon((x - mean)^2) / (S' - 1)):  gram [K*K] = the mean of C_s (row-major; symmetric), vbar, lambda, share, move its leading component;
+ * a_s = sum_k v_s[k] vbar[k], k ascending;  sgn_s = a_s < 0 ? -1 : 1.
+ * type [BNMF_RES_NTYPE][K]: 0 mean of b, 1 variance of b, 2 #(b > 0) / S', 3 mean of q (the Pearson dispersion of the type: 1 is what a
+ *   correct Poisson model gives), 4 variance of q.
+ * component [BNMF_RES_NCOMP][K]: 0 vbar, 1 mean of sgn_s v_s[k], 2 its variance, 3 #(sgn_s v_s[k] > 0) / S'.
+ * tumour [BNMF_RES_NTUM][G]: 0 mean of sgn_s t_s[g], 1 its variance, 2 mean of chi; all rows NaN for a left-out tumour.
+ * series [BNMF_RES_NSER][S]: tr_s, lambda_s, share_s, move_s, a_s; NaN in a flat sample's column.
+ * info: n_used = S, n_flat = S - S', n_included = m, n_left_out = G - m, n_steps, max_dispersion as given; lambda, share, move of the mean
+ *   matrix; mean_share = canon(share_s) / S'; min_agreement and min_agreement_at = the smallest |a_s| and its s among the used samples
+ *   (the first wins); n_biased = the types whose type row 2 is <= 0.025 or >= 0.975; n_overdispersed = the types whose row 3 is >
+ *   max_dispersion (a reporting convention like min_cosine = 0.9, not a test); worst_type and worst_type_at = the largest row 3 and its k
+ *   (the first wins).
+ * Only + - * /, sqrt, |.|, comparisons and whole numbers, no contraction, every sum in the order above: the bits depend on the samples,
+ * used[], include[], the data and n_steps only, not on the form of the kernel, its tiles or the batch of samples that passes through the
+ * scratch.  Every sum over tumours runs over the member list and a tumour's own values involve no other tumour, so include[] gives the bits
+ * of a cohort without the tumours left out.  Reads the P, E, A (Normal: and sigmasq) rings and the data; draws no random number, consumes
+ * none of the chain's streams and is read-only for the chain.  bnmf_residuals_at: the n_samples iterations that end at end_iter; the range
+ * rule, used[], BNMF_ESIZE and BNMF_ESTATE as for bnmf_similarity_at; bnmf_residuals(h, n, ...) is bnmf_residuals_at(h, iter, n, ...).
+ * Every output array may be NULL.  Refused before any device work, with BNMF_EINVAL: a null info; a used[] or include[] value other than
+ * 0 / 1 (the index named); n_steps outside 1 .. BNMF_RES_MAX_STEPS; a max_dispersion that is NaN or negative.  With BNMF_ESIZE: fewer than 2
+ * used samples, m < 2, K > BNMF_RES_MAX_K; and, known only after the device pass, S' < 2.  With BNMF_ESTATE: window = 0, a poisoned handle
+ * or nothing recorded. */
+#define BNMF_RES_NTYPE 5         /* type rows: mean b, variance of b, share of b > 0, mean q (dispersion), variance of q */
+#define BNMF_RES_NCOMP 4         /* component rows: vbar, mean, variance and share > 0 of the aligned v_s */
+#define BNMF_RES_NTUM  3         /* tumour rows: mean and variance of the aligned score, mean chi */
+#define BNMF_RES_NSER  5         /* series rows: trace, lambda, share, move, agreement */
+#define BNMF_RES_MAX_K 2048      /* the most mutation types */
+#define BNMF_RES_MAX_STEPS 10000 /* the most power steps */
+typedef struct { int32_t n_used, n_flat, n_included, n_left_out, n_steps, n_biased, n_overdispersed, worst_type_at /* k */,
+                 min_agreement_at /* s; -1 if none */, _pad;
+                 double lambda, share, move, mean_share, min_agreement, worst_type, max_dispersion; } bnmf_residuals_info;
+int bnmf_residuals(bnmf_handle*, int last_n, const int32_t* used,
+                   const int32_t* include   /* [G] 0 / 1, NULL = all */, int n_steps, double max_dispersion,
+                   double* gram      /* [K*K]; may be NULL */,
+                   double* type      /* [BNMF_RES_NTYPE][K]; may be NULL */,
+                   double* component /* [BNMF_RES_NCOMP][K]; may be NULL */,
+                   double* tumour    /* [BNMF_RES_NTUM][G]; may be NULL */,
+                   double* series    /* [BNMF_RES_NSER][S]; may be NULL */,
+                   bnmf_residuals_info* info);
+int bnmf_residuals_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_dispersion,
+                      double* gram, double* type, double* component, double* tumour, double* series, bnmf_residuals_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

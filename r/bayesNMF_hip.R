@@ -534,6 +534,67 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       C, r$n_included, r$n_matched, r$n_unmatched, r$n_not_converged, r$n_steps, r$n_certain, r$min_certainty, r$mean_certainty))
       out
     },
+    # Residual structure, on the device (bnmf_residuals_at; not in the reference): what does the model leave unexplained, and is there a
+    # process in the leftovers?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every
+    # sample gives the standardised residuals of every cell, their second-moment matrix over the included tumours along the mutation
+    # types, its leading component (n_steps power steps) and every tumour's score on it.  A direction that the misfits of many tumours
+    # share is what a missing signature looks like: a rank that is too low.  include as in get_similarity.  max_dispersion = 2.0 is a
+    # reporting convention like min_cosine = 0.9 (it only sets the count n_overdispersed), not a test.  list(types (a data frame: type,
+    # bias, bias_sd, p_positive, dispersion, dispersion_sd, component, component_mean, component_sd), tumours (a data frame: tumour, score,
+    # score_sd, chi, included), candidate (K: the positive part of the mean matrix's component, or of its negative where that part has
+    # the larger sum of squares, normalised to sum 1), candidate_cosine (with the columns of the MAP signatures), with reference_P (K x R)
+    # reference_cosine, best_reference and best_reference_cosine, gram (K x K), series (5 x S: trace, lambda, share, move, agreement) and
+    # the info fields).
+    get_residuals = function(include = NULL, n_steps = 100, max_dispersion = 2.0, reference_P = NULL, end_iter = self$state$iter,
+                             n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      K <- self$dims$K; G <- self$dims$G
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      member <- if (is.null(include)) rep(TRUE, G) else include
+      names <- colnames(self$data)
+      r <- .Call("C_bnmf_residuals", self$handle, as.integer(end_iter), as.integer(n_samples), used, include, as.double(c(n_steps, max_dispersion, K, G)))
+      out <- r[c("n_used", "n_flat", "n_included", "n_left_out", "n_steps", "n_biased", "n_overdispersed", "lambda", "share", "move", "mean_share",
+                 "min_agreement", "worst_type", "max_dispersion")]
+      out$worst_type_at <- r$worst_type_at + 1L
+      out$min_agreement_at <- if (r$min_agreement_at < 0) NA_integer_ else r$min_agreement_at + 1L
+      vbar <- r$component[, 1]
+      pos <- pmax(vbar, 0); neg <- pmax(-vbar, 0)
+      part <- if (isTRUE(sum(neg^2) > sum(pos^2))) neg else pos
+      cand <- if (isTRUE(sum(part) > 0) && is.finite(sum(part))) part / sum(part) else rep(NA_real_, K)
+      cosines <- function(cols) as.numeric(crossprod(cols, cand)) / sqrt(colSums(cols^2) * sum(cand^2))
+      out$candidate <- cand
+      out$candidate_cosine <- cosines(as.matrix(self$MAP$P))
+      if (!is.null(reference_P)) {
+        ref <- as.matrix(reference_P)
+        if (nrow(ref) != K) stop("reference_P must have K = ", K, " rows")
+        rc <- cosines(ref)
+        out$reference_cosine <- rc
+        best <- if (all(is.na(rc))) NA_integer_ else which.max(rc)
+        out$best_reference <- if (is.na(best)) NA else if (is.null(colnames(ref))) best else colnames(ref)[best]
+        out$best_reference_cosine <- if (is.na(best)) NA_real_ else rc[best]
+      }
+      out$types <- data.frame(type = seq_len(K), bias = r$type[, 1], bias_sd = sqrt(r$type[, 2]), p_positive = r$type[, 3], dispersion = r$type[, 4],
+                              dispersion_sd = sqrt(r$type[, 5]), component = vbar, component_mean = r$component[, 2], component_sd = sqrt(r$component[, 3]))
+      out$tumours <- data.frame(tumour = if (is.null(names)) seq_len(G) else names, score = r$tumour[, 1], score_sd = sqrt(r$tumour[, 2]), chi = r$tumour[, 3],
+                                included = member)
+      out$gram <- r$gram
+      out$series <- t(r$series)
+      message(sprintf("Residuals: %d tumours over %d samples (%d flat); the leading component carries %.3g of the mean matrix's trace; %d types with dispersion > %g, %d biased",
+                      r$n_included, r$n_used - r$n_flat, r$n_flat, r$share, r$n_overdispersed, r$max_dispersion, r$n_biased))
+      out
+    },
     # Co-activity of the signatures, on the device (bnmf_coactivity_at; not in the reference): do two signatures act in the same tumours
     # or exclude each other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are
     # negatively correlated)?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every

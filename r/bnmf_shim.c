@@ -895,6 +895,68 @@ SEXP C_bnmf_subtypes_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP
   UNPROTECT(1);
   return out;
 }
+/* Residual structure of recorded samples on the device (bnmf_residuals / bnmf_residuals_at): C_bnmf_residuals(ptr, end_iter (integer, or
+ * NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or NULL = all),
+ * opts (real c(n_steps, max_dispersion, K, G))) -> list(n_used, n_flat, n_included, n_left_out, n_steps, n_biased, n_overdispersed,
+ * worst_type_at (0-based), min_agreement_at (0-based used sample, -1 = none), lambda, share, move, mean_share, min_agreement, worst_type,
+ * max_dispersion, gram (K x K), type (K x 5: mean and variance of b, share of b > 0, mean and variance of q), component (K x 4: vbar,
+ * mean, variance and share > 0 of the aligned v_s), tumour (G x 3: mean and variance of the aligned score, mean chi), series (S x 5:
+ * trace, lambda, share, move, agreement)) over iterations end_iter - n_samples + 1 ... end_iter.  C_bnmf_residuals_at: the same with
+ * end_iter required */
+/* the result list with its arrays allocated and the flags converted; returned unprotected */
+static SEXP res_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP opts, int32_t** u, int32_t** inc) {
+  const int n = INTEGER(n_samples)[0];
+  if (XLENGTH(opts) != 4) Rf_error("bnmf: opts has %ld entries, c(n_steps, max_dispersion, K, G) is needed", (long)XLENGTH(opts));
+  const int K = (int)REAL(opts)[2], G = (int)REAL(opts)[3];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  *u = lgl_flags(used, n);
+  *inc = lgl_flags(include, G);
+  int S = n < 0 ? 0 : n;
+  if (*u) { S = 0; for (int i = 0; i < n; ++i) S += (*u)[i]; }
+  static const char* nms[] = {"n_used", "n_flat", "n_included", "n_left_out", "n_steps", "n_biased", "n_overdispersed", "worst_type_at", "min_agreement_at",
+                              "lambda", "share", "move", "mean_share", "min_agreement", "worst_type", "max_dispersion", "gram", "type", "component", "tumour",
+                              "series"};
+  SEXP out = PROTECT(named_list(21, nms));
+  SET_VECTOR_ELT(out, 16, Rf_allocMatrix(REALSXP, K, K));
+  SET_VECTOR_ELT(out, 17, Rf_allocMatrix(REALSXP, K, BNMF_RES_NTYPE));
+  SET_VECTOR_ELT(out, 18, Rf_allocMatrix(REALSXP, K, BNMF_RES_NCOMP));
+  SET_VECTOR_ELT(out, 19, Rf_allocMatrix(REALSXP, G, BNMF_RES_NTUM));
+  SET_VECTOR_ELT(out, 20, Rf_allocMatrix(REALSXP, S, BNMF_RES_NSER));
+  UNPROTECT(1);
+  return out;
+}
+static void res_finish(SEXP out, const bnmf_residuals_info* info) {
+  const int32_t v[9] = {info->n_used, info->n_flat, info->n_included, info->n_left_out, info->n_steps, info->n_biased, info->n_overdispersed,
+                        info->worst_type_at, info->min_agreement_at};
+  for (int i = 0; i < 9; ++i) SET_VECTOR_ELT(out, i, Rf_ScalarInteger(v[i]));
+  const double d[7] = {info->lambda, info->share, info->move, info->mean_share, info->min_agreement, info->worst_type, info->max_dispersion};
+  for (int i = 0; i < 7; ++i) SET_VECTOR_ELT(out, 9 + i, Rf_ScalarReal(d[i]));
+}
+SEXP C_bnmf_residuals(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP opts) {
+  int32_t *u = NULL, *inc = NULL;
+  SEXP out = PROTECT(res_alloc(n_samples, used, include, opts, &u, &inc));
+  bnmf_residuals_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_residuals(get_handle(ptr), INTEGER(n_samples)[0], u, inc, (int)REAL(opts)[0], REAL(opts)[1], map_buf(out, 16), map_buf(out, 17), map_buf(out, 18),
+                       map_buf(out, 19), map_buf(out, 20), &info));
+  else
+    chk(bnmf_residuals_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, inc, (int)REAL(opts)[0], REAL(opts)[1], map_buf(out, 16),
+                          map_buf(out, 17), map_buf(out, 18), map_buf(out, 19), map_buf(out, 20), &info));
+  res_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_residuals_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP opts) {
+  int32_t *u = NULL, *inc = NULL;
+  SEXP out = PROTECT(res_alloc(n_samples, used, include, opts, &u, &inc));
+  bnmf_residuals_info info;
+  chk(bnmf_residuals_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], u, inc, (int)REAL(opts)[0], REAL(opts)[1], map_buf(out, 16),
+                        map_buf(out, 17), map_buf(out, 18), map_buf(out, 19), map_buf(out, 20), &info));
+  res_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Silhouette stability of the recorded signatures on the device (bnmf_stability / bnmf_stability_at): C_bnmf_stability(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), labels (integer n_samples x N
  * matrix of 0-based clusters, -1 / NA = left out; or NULL = the factor), extra_P (K x X real matrix, or NULL), extra_label (integer X,
@@ -1264,6 +1326,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_reconstruction", (DL_FUNC)&C_bnmf_reconstruction, 7}, {"C_bnmf_reconstruction_at", (DL_FUNC)&C_bnmf_reconstruction_at, 7},
   {"C_bnmf_similarity", (DL_FUNC)&C_bnmf_similarity, 9}, {"C_bnmf_similarity_at", (DL_FUNC)&C_bnmf_similarity_at, 9},
   {"C_bnmf_subtypes", (DL_FUNC)&C_bnmf_subtypes, 9}, {"C_bnmf_subtypes_at", (DL_FUNC)&C_bnmf_subtypes_at, 9},
+  {"C_bnmf_residuals", (DL_FUNC)&C_bnmf_residuals, 6}, {"C_bnmf_residuals_at", (DL_FUNC)&C_bnmf_residuals_at, 6},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
