@@ -46,6 +46,7 @@
 #include "similarity.h"
 #include "subtypes.h"
 #include "residuals.h"
+#include "tradeoff.h"
 
 using namespace bnmf;
 

@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h and residuals.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals, bnmf_tradeoff (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h, residuals.h and tradeoff.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1769,6 +1769,129 @@ static int residuals_impl(bnmf_handle* h, const char* fn, Range r, const int32_t
   return 0;
 }
 
+// Trade-offs between signatures within a tumour over the samples of r that used[] flags (tradeoff.h): the member list, the
+// matched samples and their perm rows are made here; k_map_colsum runs once over the matched samples, k_trd_prep turns them into tables by
+// aligned place and k_trd_mean leaves every member's means.  Then per band of members, whose N x N covariances fit TRD_SCRATCH_CAP:
+// k_trd_comoment, k_trd_finish, k_trd_pair and k_trd_dense.  The divisions of the pair rows and the info fields are tradeoff_finish's.
+static_assert(TD_NTUM == BNMF_TRD_NTUM && TD_NPAIR == BNMF_TRD_NPAIR && TD_NSET == BNMF_TRD_NSET && TD_MAX_C == BNMF_TRD_MAX_C && TD_MAX_N == BNMF_TRD_MAX_N,
+              "tradeoff.h and bnmf.h disagree");
+static constexpr size_t TRD_SCRATCH_CAP = (size_t)256 << 20;    // bytes of a band's covariances
+static int tradeoff_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, const int32_t* perm, const int32_t* sets, int C,
+                         const int32_t* query, int Q, double min_corr, double* tumour, int32_t* pair_at, double* pair, double* dense, double* setstat,
+                         bnmf_tradeoff_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members, place(G, -1);                  // place[g]: g's position in the member list
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) { place[g] = (int)members.size(); members.push_back(g); }
+  }
+  const int m = (int)members.size();
+  if (C < 0 || C > BNMF_TRD_MAX_C) return fail(BNMF_EINVAL, "%s: C = %d is outside 0..%d", fn, C, BNMF_TRD_MAX_C);
+  if (C > 0 && !sets) return fail(BNMF_EINVAL, "%s: C = %d but sets is null", fn, C);
+  if (C > 0) {
+    std::vector<int> size(C, 0);
+    for (int n = 0; n < N; ++n) {
+      if (sets[n] < -1 || sets[n] >= C) return fail(BNMF_EINVAL, "%s: sets[%d] = %d is outside -1..%d", fn, n, (int)sets[n], C - 1);
+      if (sets[n] >= 0) ++size[sets[n]];
+    }
+    for (int c = 0; c < C; ++c) if (!size[c]) return fail(BNMF_EINVAL, "%s: set %d is empty", fn, c);
+  }
+  if (Q < 0) return fail(BNMF_EINVAL, "%s: Q = %d is negative", fn, Q);
+  if (Q > 0 && !query) return fail(BNMF_EINVAL, "%s: Q = %d but query is null", fn, Q);
+  for (int q = 0; q < Q; ++q) {
+    if (query[q] < 0 || query[q] >= G) return fail(BNMF_EINVAL, "%s: query[%d] = %d is outside 0..%d", fn, q, (int)query[q], G - 1);
+    if (place[query[q]] < 0) return fail(BNMF_EINVAL, "%s: query[%d] = %d is a tumour that include[] leaves out", fn, q, (int)query[q]);
+  }
+  if (!(min_corr >= 0.0 && min_corr <= 1.0)) return fail(BNMF_EINVAL, "%s: min_corr = %g is outside [0, 1]", fn, min_corr);
+  // the matched samples: rows[] is the row of the range of every used sample
+  std::vector<int> rows, mslots, hperm;
+  for (int s = 0; s < r.n; ++s) if (!used || used[s]) rows.push_back(s);
+  const int S = (int)slots.size();
+  for (int s = 0; s < S; ++s) {
+    const int32_t* pr = perm ? perm + (size_t)rows[s] * N : nullptr;
+    bool none = pr != nullptr;
+    for (int n = 0; pr && n < N; ++n) none = none && pr[n] == -1;
+    if (none) continue;
+    if (pr) {
+      std::vector<char> seen(N, 0);
+      for (int n = 0; n < N; ++n) {
+        if (pr[n] < 0 || pr[n] >= N || seen[pr[n]])
+          return fail(BNMF_EINVAL, "%s: perm[%d] is neither a permutation of 0..%d nor -1 throughout (sample %d of the range, factor %d: %d)", fn, rows[s], N - 1,
+                      rows[s], n, (int)pr[n]);
+        seen[pr[n]] = 1;
+      }
+    }
+    mslots.push_back(slots[s]);
+    for (int n = 0; n < N; ++n) hperm.push_back(pr ? pr[n] : n);
+  }
+  const int Sm = (int)mslots.size();
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the covariance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (Sm < 2) return fail(BNMF_ESIZE, "%s: %d matched sample%s of %d used, the covariance over the samples needs at least 2", fn, Sm, Sm == 1 ? "" : "s", S);
+  if (m < 1) return fail(BNMF_ESIZE, "%s: no included tumour", fn);
+  if (N > BNMF_TRD_MAX_N) return fail(BNMF_ESIZE, "%s: N = %d factors, at most %d are taken", fn, N, BNMF_TRD_MAX_N);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  int TL = 16;
+  if (const char* e = getenv("BNMF_TRD_FORM")) if (atoi(e) == 1) TL = 8;                                   // tests, tools: the tile of 8
+  const size_t NN = (size_t)N * N;
+  long long want = (long long)std::max<size_t>(1, TRD_SCRATCH_CAP / (NN * sizeof(double)));
+  if (want < m && want >= RG_BLOCK) want -= want % RG_BLOCK;                                              // whole blocks of canonB: no accumulator crosses a band
+  if (const char* e = getenv("BNMF_TRD_BAND")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the members of a band
+  const int mb = (int)std::min<long long>(want, m);
+  const bool crosses = mb < m && mb % RG_BLOCK != 0;                                                      // a band ends inside a block of canonB
+  std::vector<int> qplace(std::max(Q, 1), 0);
+  for (int q = 0; q < Q; ++q) qplace[q] = place[query[q]];
+  TrdArgs a{};
+  double *cs, *df, *dtum, *dsst, *drun, *dcarry, *ddense; long long* doff; int *don, *dslots, *dmem, *dperm, *dqp, *dsets; int32_t *dpat, *dcnt;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)Sm * N); df = c.take<double>((size_t)Sm * N); doff = c.take<long long>((size_t)Sm * N); don = c.take<int>((size_t)Sm * N);
+        a.mu = c.take<double>((size_t)m * N); a.cov = c.take<double>(NN * mb); dtum = c.take<double>((size_t)TD_NTUM * m); dpat = c.take<int32_t>(m);
+        dsst = c.take<double>((size_t)TD_NSET * std::max(C, 1) * m); drun = c.take<double>(NN * 2); dcnt = c.take<int32_t>(NN * 3);
+        dcarry = c.take<double>(crosses ? NN * 2 * 64 : 1); ddense = c.take<double>((size_t)std::max(Q, 1) * 2 * NN);
+        dslots = c.take<int>(Sm); dmem = c.take<int>(m); dperm = c.take<int>((size_t)Sm * N); dqp = c.take<int>(std::max(Q, 1)); dsets = c.take<int>(N);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, mslots.data(), (size_t)Sm * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dperm, hperm.data(), (size_t)Sm * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dqp, qplace.data(), (size_t)std::max(Q, 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (C > 0) HIPCHK(hipMemcpyAsync(dsets, sets, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(drun, 0, NN * 2 * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(dcnt, 0, NN * 3 * sizeof(int32_t), h->stream));
+  if (crosses) HIPCHK(hipMemsetAsync(dcarry, 0, NN * 2 * 64 * sizeof(double), h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(Sm, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, (size_t)K * N, K, N, (const int*)dslots, cs);
+  hipLaunchKernelGGL(k_trd_prep<TD_NTUM>, dim3((unsigned)(((size_t)Sm * N + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->arr[BNMF_A].ring, (const double*)cs,
+                     (const int*)dslots, (const int*)dperm, N, Sm, (size_t)N * G, doff, df, don);
+  a.ringE = h->arr[BNMF_E].ring; a.off = doff; a.f = df; a.on = don; a.members = dmem; a.N = N; a.S = Sm; a.m = m; a.mb = mb;
+  hipLaunchKernelGGL(k_trd_mean<TD_NTUM>, dim3((unsigned)(((size_t)m * N + 255) / 256)), dim3(256), 0, h->stream, a);
+  const int items = trd_items(N, TL), MB = TD_T / std::min(items, TD_T);
+  for (int i0 = 0; i0 < m; i0 += mb) {
+    a.i0 = i0; a.cnt = std::min(mb, m - i0);
+    const dim3 gc((unsigned)((a.cnt + MB - 1) / MB), (unsigned)((items + TD_T - 1) / TD_T));
+    if (TL == 16) hipLaunchKernelGGL(k_trd_comoment<16>, gc, dim3(TD_T), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_trd_comoment<8>, gc, dim3(TD_T), 0, h->stream, a);
+    hipLaunchKernelGGL(k_trd_finish<TD_NTUM>, dim3((unsigned)((a.cnt + 255) / 256)), dim3(256), 0, h->stream, a, (const int*)dsets, C, dtum, dpat, dsst);
+    if (N > 1) hipLaunchKernelGGL(k_trd_pair<TD_NTUM>, dim3((unsigned)N, (unsigned)N), dim3(64), 0, h->stream, a, min_corr, crosses ? dcarry : (double*)nullptr, drun, dcnt);
+    if (Q > 0 && dense) hipLaunchKernelGGL(k_trd_dense<TD_NTUM>, dim3((unsigned)Q), dim3(256), 0, h->stream, a, (const int*)dqp, ddense);
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> htum((size_t)TD_NTUM * m), hsst((size_t)TD_NSET * C * m), hrun(NN * 2);
+  std::vector<int32_t> hpat(m), hcnt(NN * 3);
+  HIPCHK(hipMemcpyAsync(htum.data(), dtum, htum.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hpat.data(), dpat, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (C > 0) HIPCHK(hipMemcpyAsync(hsst.data(), dsst, hsst.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hrun.data(), drun, hrun.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hcnt.data(), dcnt, hcnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (Q > 0 && dense) HIPCHK(hipMemcpyAsync(dense, ddense, (size_t)Q * 2 * NN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  tradeoff_finish(members.data(), m, G, N, C, min_corr, htum.data(), hpat.data(), hsst.data(), hrun.data(), hcnt.data(), tumour, pair_at, pair, setstat, info);
+  info->n_used = S; info->n_matched = Sm; info->n_unmatched = S - Sm; info->n_sets = C; info->n_query = Q; info->min_corr = min_corr;
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -1917,6 +2040,17 @@ int bnmf_residuals(bnmf_handle* h, int last_n, const int32_t* used, const int32_
 int bnmf_residuals_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_dispersion, double* gram,
                       double* type, double* component, double* tumour, double* series, bnmf_residuals_info* info) {
   return residuals_impl(h, "bnmf_residuals_at", {true, end_iter, n_samples}, used, include, n_steps, max_dispersion, gram, type, component, tumour, series, info);
+}
+
+int bnmf_tradeoff(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, const int32_t* perm, const int32_t* sets, int C, const int32_t* query,
+                  int Q, double min_corr, double* tumour, int32_t* pair_at, double* pair, double* dense, double* setstat, bnmf_tradeoff_info* info) {
+  return tradeoff_impl(h, "bnmf_tradeoff", {false, 0, last_n}, used, include, perm, sets, C, query, Q, min_corr, tumour, pair_at, pair, dense, setstat, info);
+}
+int bnmf_tradeoff_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm, const int32_t* sets, int C,
+                     const int32_t* query, int Q, double min_corr, double* tumour, int32_t* pair_at, double* pair, double* dense, double* setstat,
+                     bnmf_tradeoff_info* info) {
+  return tradeoff_impl(h, "bnmf_tradeoff_at", {true, end_iter, n_samples}, used, include, perm, sets, C, query, Q, min_corr, tumour, pair_at, pair, dense, setstat,
+                       info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

@@ -1,11 +1,11 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
 // (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's, bnmf_similarity's,
-// bnmf_subtypes'  and bnmf_residuals' (DESIGN.md 26).  No device and no handle: posterior.h includes it, and a stand-alone host program can
+// bnmf_subtypes' (DESIGN.md 25), bnmf_residuals'  and bnmf_tradeoff's.  No device and no handle: posterior.h includes it, and a stand-alone host program can
 // (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp,
-// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp and tools/residuals_reduce_check.cpp, built with
+// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp, tools/residuals_reduce_check.cpp and tools/tradeoff_reduce_check.cpp, built with
 // -fsanitize=address,undefined by tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py,
-// tests/test_similarity_host.py, tests/test_subtypes_host.py and tests/test_residuals_host.py).  Compile with -ffp-contract=off, as the library is.
+// tests/test_similarity_host.py, tests/test_subtypes_host.py, tests/test_residuals_host.py and tests/test_tradeoff_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -422,4 +422,43 @@ struct res_lead { double trace, lambda, share, move; };
     }
   };
   deal_threads(m, work);
+}
+
+// ---- bnmf_tradeoff's finish: from the rows in member order and the pairs' sums to the outputs by tumour and the info fields ----
+// members [m] ascending; tum [3][m], pat [m] and sst [4][C][m] in member order, run [N*N][2] (canonB of r where defined and of cov, set for
+// j > l) and cnts [N*N][3] (n_def, #(r <= -min_corr), #(r >= min_corr), set for j > l) as the device left them.  tumour [3][G], pair_at [G],
+// pair [5][N*N] and setstat [4][C][G] may each be null; a left-out tumour holds NaN / -1.  Of info n_included, n_left_out, n_traded,
+// strongest_pair(_at) and mean_ratio are set.
+[[maybe_unused]] static void tradeoff_finish(const int* members, long m, long G, int N, int C, double min_corr, const double* tum, const int32_t* pat,
+                                             const double* sst, const double* run, const int32_t* cnts, double* tumour, int32_t* pair_at, double* pair,
+                                             double* setstat, bnmf_tradeoff_info* info) {
+  const double nan = std::nan("");
+  const size_t NN = (size_t)N * N;
+  info->n_included = (int32_t)m; info->n_left_out = (int32_t)(G - m);
+  if (tumour) std::fill(tumour, tumour + (size_t)BNMF_TRD_NTUM * G, nan);
+  if (pair_at) std::fill(pair_at, pair_at + G, (int32_t)-1);
+  if (setstat) std::fill(setstat, setstat + (size_t)BNMF_TRD_NSET * C * G, nan);
+  std::vector<double> ratio;                                  // the ratios of the members that have one, in member order
+  int32_t traded = 0;
+  for (long i = 0; i < m; ++i) {
+    const size_t g = (size_t)members[i];
+    if (tumour) for (int k = 0; k < BNMF_TRD_NTUM; ++k) tumour[(size_t)k * G + g] = tum[(size_t)k * m + i];
+    if (pair_at) pair_at[g] = pat[i];
+    if (setstat) for (size_t k = 0; k < (size_t)BNMF_TRD_NSET * C; ++k) setstat[k * G + g] = sst[k * m + i];
+    traded += tum[i] <= -min_corr ? 1 : 0;                    // (a NaN compares false)
+    if (!std::isnan(tum[2 * (size_t)m + i])) ratio.push_back(tum[2 * (size_t)m + i]);
+  }
+  info->n_traded = traded;
+  info->mean_ratio = ratio.empty() ? nan : con_canon64(ratio.data(), ratio.size(), 1) / (double)ratio.size();
+  info->strongest_pair = nan; info->strongest_pair_at = -1;
+  if (pair) std::fill(pair, pair + (size_t)BNMF_TRD_NPAIR * NN, nan);
+  for (int j = 1; j < N; ++j)
+    for (int l = 0; l < j; ++l) {
+      const size_t p = (size_t)j * N + l, pt = (size_t)l * N + j;
+      const int32_t nd = cnts[p * 3];
+      const double row[BNMF_TRD_NPAIR] = {nd > 0 ? run[p * 2] / (double)nd : nan, (double)nd, nd > 0 ? (double)cnts[p * 3 + 1] / (double)nd : nan,
+                                          nd > 0 ? (double)cnts[p * 3 + 2] / (double)nd : nan, run[p * 2 + 1] / (double)m};
+      if (pair) for (int k = 0; k < BNMF_TRD_NPAIR; ++k) { pair[(size_t)k * NN + p] = row[k]; pair[(size_t)k * NN + pt] = row[k]; }
+      if (!std::isnan(row[0]) && (info->strongest_pair_at < 0 || row[0] < info->strongest_pair)) { info->strongest_pair = row[0]; info->strongest_pair_at = (int32_t)p; }
+    }
 }

@@ -146,6 +146,12 @@ class BnmfResidualsInfo(C.Structure):
                 ("worst_type", C.c_double), ("max_dispersion", C.c_double)]
 
 
+class BnmfTradeoffInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_matched", C.c_int32), ("n_unmatched", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32),
+                ("n_sets", C.c_int32), ("n_query", C.c_int32), ("n_traded", C.c_int32), ("strongest_pair_at", C.c_int32), ("_pad", C.c_int32),
+                ("strongest_pair", C.c_double), ("mean_ratio", C.c_double), ("min_corr", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -180,6 +186,10 @@ RES_TYPE_ROWS = ("bias", "bias_var", "p_positive", "dispersion", "dispersion_var
 RES_COMPONENT_ROWS = ("vbar", "mean", "var", "p_positive")
 RES_TUMOUR_ROWS = ("score", "score_var", "chi")
 RES_SERIES_ROWS = ("trace", "lambda", "share", "move", "agreement")
+TRD_TUMOUR_ROWS = ("min_corr", "n_defined", "total_ratio")
+TRD_PAIR_ROWS = ("mean_corr", "n_defined", "p_negative", "p_positive", "mean_cov")
+TRD_SET_ROWS = ("mean", "var_sum", "sum_var", "ratio")
+TRD_MAX_C = 32
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -200,7 +210,8 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_decompose", "bnmf_decompose_at", "bnmf_contrast", "bnmf_contrast_at", "bnmf_regress", "bnmf_regress_at",
                "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
                "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at",
-               "bnmf_subtypes", "bnmf_subtypes_at", "bnmf_residuals", "bnmf_residuals_at"]
+               "bnmf_subtypes", "bnmf_subtypes_at", "bnmf_residuals", "bnmf_residuals_at",
+               "bnmf_tradeoff", "bnmf_tradeoff_at"]
 
 
 def lib():
@@ -281,6 +292,9 @@ def lib():
         res = [ip, ip, C.c_int, C.c_double, dp, dp, dp, dp, dp, C.POINTER(BnmfResidualsInfo)]
         L.bnmf_residuals.argtypes = [C.c_void_p, C.c_int] + res
         L.bnmf_residuals_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + res
+        trd = [ip, ip, ip, ip, C.c_int, ip, C.c_int, C.c_double, dp, ip, dp, dp, dp, C.POINTER(BnmfTradeoffInfo)]
+        L.bnmf_tradeoff.argtypes = [C.c_void_p, C.c_int] + trd
+        L.bnmf_tradeoff_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + trd
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -971,6 +985,47 @@ class Engine:
     def residuals_at(self, end_iter, n_samples, **kw):
         """residuals over the n_samples iterations that end at end_iter (bnmf_residuals_at)."""
         return self.residuals(n_samples, end_iter=end_iter, **kw)
+
+    def tradeoff(self, last_n, include=None, perm=None, sets=None, query=None, min_corr=0.5, used=None, end_iter=None):
+        """Trade-offs between signatures within a tumour over the recorded samples flagged in used (length last_n, oldest first; None =
+        all) of the last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_tradeoff / bnmf_tradeoff_at), on
+        the device: per included tumour (include: length G of 0 / 1, None = all) the N x N covariance of its aligned renormalised
+        exposures over the samples.  perm (last_n x N over the whole range, relabel's; a row of -1 leaves the sample out; None =
+        identity) aligns the factors first.  sets (length N of 0 .. C-1, -1 = in no set; None = no sets).  Returns the info fields,
+        tumour (3 x G: TRD_TUMOUR_ROWS, NaN for a left-out tumour; not spread by name, min_corr is the info field), pair_at (G), pair
+        (5 x N x N: TRD_PAIR_ROWS, symmetric, the diagonal NaN), setstat (4 x C x G: TRD_SET_ROWS) and with query (Q tumours) dense
+        (Q x 2 x N x N: the covariance and the correlation matrix of every query tumour).  min_corr only sets the counts: a reporting
+        convention, not a test."""
+        G, N = self.G, self.N
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"tradeoff: include has shape {inc.shape}, G = {G} flags are needed")
+        pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        if pm is not None and pm.shape != (last_n, N):
+            raise BnmfError(-2, f"tradeoff: perm is {pm.shape}, not {(last_n, N)}")
+        st = None if sets is None else np.ascontiguousarray(sets, dtype=np.int32)
+        if st is not None and (st.ndim != 1 or st.size != N):
+            raise BnmfError(-2, f"tradeoff: sets has shape {st.shape}, N = {N} labels are needed")
+        Cn = 0 if st is None else int(st.max()) + 1
+        qv = None if query is None else np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        Q = 0 if qv is None else int(qv.size)
+        u, S = self._used("tradeoff", used, last_n)
+        Cb = min(max(Cn, 0), TRD_MAX_C)                        # (an invalid C is refused by the library: the buffers only have to exist)
+        tum, pat, par, sst = np.empty((3, G)), np.empty(G, dtype=np.int32), np.empty((5, N, N)), np.empty((4, Cb, G))
+        den = np.empty((Q, 2, N, N)) if Q > 0 else None
+        info = BnmfTradeoffInfo()
+        ipt = lambda v: None if v is None else v.ctypes.data_as(_IP)  # noqa: E731
+        self._range_call("tradeoff", last_n, end_iter, u, ipt(inc), ipt(pm), ipt(st), Cn, ipt(qv), Q, float(min_corr), _dp(tum), ipt(pat), _dp(par), _dp(den),
+                         _dp(sst) if Cb > 0 else None, C.byref(info))
+        out = self._info(info)
+        out.update(tumour=tum, pair_at=pat, pair=par, setstat=sst)
+        if den is not None:
+            out.update(dense=den, query=qv.copy())
+        return out
+
+    def tradeoff_at(self, end_iter, n_samples, **kw):
+        """tradeoff over the n_samples iterations that end at end_iter (bnmf_tradeoff_at)."""
+        return self.tradeoff(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

@@ -1199,6 +1199,85 @@ class bayesNMF_sampler:
                  f"{r['n_biased']} biased", verbosity=1)
         return out
 
+    def get_tradeoff(self, sets=None, query=None, include=None, relabel=True, min_corr=0.5, end_iter=None, n_samples=None, idx="MAP_idx"):
+        """Which signatures trade mutations within a tumour, and how uncertain is a SUM of exposures?  On the device (bnmf_tradeoff_at;
+        not in the reference): over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as
+        get_contrast), per tumour the N x N covariance of its renormalised exposures over the samples and the correlations.  Flat or
+        similar signatures exchange mutations from sample to sample: each marginal interval is wide while the sum is sharply determined,
+        and adding two marginal SDs overstates the uncertainty of the sum.  With relabel the range is first aligned by get_relabelling()
+        and its perm is handed on; an unmatched sample is left out.  sets: a label per signature (0 .. C-1, -1 = in no set) or a dict
+        name -> list of signature indices; query: tumours (indices or names) whose whole matrices are wanted; include as in
+        get_similarity.  min_corr = 0.5 is a reporting convention like min_cosine = 0.9 (it only sets the counts), not a test.
+        Returns dict(tumours (a data frame: tumour, min_corr, pair_j, pair_l, n_defined, total_ratio, included), pairs (a data frame:
+        j, l, mean_corr, n_defined, p_negative, p_positive, mean_cov for j > l), sets (a data frame: set, tumour, mean, sd_sum,
+        sd_if_independent, ratio; only with sets), set_names, tumour, pair_at, pair, setstat, dense (the arrays of the call) and its
+        info fields)."""
+        if not hasattr(self._chain, "tradeoff"):
+            raise ValueError("get_tradeoff needs an engine that forms covariances over its recorded samples (tradeoff); this engine_factory's cannot")
+        G, N = self.dims["G"], self.dims["N"]
+        names = self.tumour_names if getattr(self, "tumour_names", None) else None
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        st, set_names = None, None
+        if isinstance(sets, dict):
+            st, set_names = np.full(N, -1, dtype=np.int32), list(sets)
+            for c, nm in enumerate(set_names):
+                at = np.asarray(sets[nm], dtype=np.int64).reshape(-1)
+                if at.size == 0 or (at < 0).any() or (at >= N).any():
+                    raise ValueError(f"set {nm!r} is empty or names a signature outside 0 .. {N - 1}")
+                if (st[at] >= 0).any():
+                    raise ValueError(f"set {nm!r} holds a signature that another set holds")
+                st[at] = c
+        elif sets is not None:
+            st = np.asarray(sets, dtype=np.int32).reshape(-1)
+            if st.size != N:
+                raise ValueError(f"sets has {st.size} labels for {N} signatures")
+            set_names = list(range(int(st.max()) + 1))
+        qv = None
+        if query is not None:
+            vs = list(np.atleast_1d(query).tolist())
+            if names is not None and all(isinstance(q, str) for q in vs):
+                missing = [q for q in vs if q not in names]
+                if missing:
+                    raise ValueError(f"query names no tumour of the data: {missing[:5]}")
+                vs = [names.index(q) for q in vs]
+            qv = np.asarray(vs, dtype=np.int32)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        perm = None
+        if relabel:
+            rows = np.asarray(self.get_relabelling(end_iter=end_iter, n_samples=n_samples, idx=idx)["perm"], dtype=np.int32)
+            perm = np.full((n, N), -1, dtype=np.int32)                   # perm has a row per used sample: scattered into the range's rows
+            perm[slice(None) if used is None else np.asarray(used) != 0] = rows
+        r = self._chain.tradeoff(n, include=inc, perm=perm, sets=st, query=qv, min_corr=min_corr, used=used, **kw)
+        label = (lambda g: names[g]) if names is not None else (lambda g: int(g))
+        tum, pat, par = np.asarray(r["tumour"]).reshape(3, G), np.asarray(r["pair_at"]).reshape(G), np.asarray(r["pair"]).reshape(5, N, N)
+        included = np.ones(G, dtype=bool) if inc is None else inc.astype(bool)
+        out = dict(r)
+        out.update(tumours=pd.DataFrame(dict(tumour=[label(g) for g in range(G)], min_corr=tum[0], pair_j=np.where(pat >= 0, pat // N, -1),
+                                             pair_l=np.where(pat >= 0, pat % N, -1), n_defined=tum[1], total_ratio=tum[2], included=included)),
+                   pairs=pd.DataFrame([(j, l) + tuple(par[:, j, l]) for j in range(N) for l in range(j)],
+                                      columns=["j", "l", "mean_corr", "n_defined", "p_negative", "p_positive", "mean_cov"]),
+                   set_names=set_names)
+        if st is not None and set_names:
+            sst = np.asarray(r["setstat"]).reshape(4, len(set_names), G)
+            out["sets"] = pd.DataFrame([(nm, label(g), sst[0, c, g], float(np.sqrt(sst[1, c, g])), float(np.sqrt(sst[2, c, g])), sst[3, c, g])
+                                        for c, nm in enumerate(set_names) for g in range(G)],
+                                       columns=["set", "tumour", "mean", "sd_sum", "sd_if_independent", "ratio"])
+        if qv is not None:
+            out["query"] = [label(g) for g in qv]
+        sp = int(r["strongest_pair_at"])
+        self.log(f"Trade-offs: {r['n_included']} tumours over {r['n_matched']} samples ({r['n_unmatched']} unmatched); {r['n_traded']} tumours with a "
+                 f"correlation <= -{r['min_corr']:g}; mean variance ratio of the total {r['mean_ratio']:.3g}; strongest pair "
+                 f"{(sp // N, sp % N) if sp >= 0 else None} with mean correlation {r['strongest_pair']:.3g}", verbosity=1)
+        return out
+
     def _mean_share_profiles(self, n, used, perm, kw):
         """N x G: the mean over the used, matched samples of the range of every tumour's aligned share profile (the host's start of
         get_subtypes; a sample in which a tumour has no exposure does not enter its mean)."""
@@ -1221,7 +1300,7 @@ class bayesNMF_sampler:
         return tot / np.where(cnt > 0, cnt, 1.0)
 
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes / get_residuals: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes / get_residuals / get_tradeoff: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

@@ -828,6 +828,78 @@ int bnmf_residuals(bnmf_handle*, int last_n, const int32_t* used,
 int bnmf_residuals_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_dispersion,
                       double* gram, double* type, double* component, double* tumour, double* series, bnmf_residuals_info* info);
 
+/* Trade-offs between signatures within a tumour over recorded samples, on the device: which signatures exchange mutations
+ * from sample to sample in one tumour, and how uncertain is a SUM of exposures?  Flat or similar signatures trade mutations: each marginal
+ * interval is wide while their sum is sharply determined, which no per-signature output shows.  The members are the m included tumours
+ * g_0 < g_1 < ... (include[g] != 0; NULL = all), position i = 0 .. m-1.  The samples are the recorded ones flagged in used[] (oldest
+ * first; NULL = all).  perm [last_n][N] (row-major, a row per sample of the whole range, read for the used ones) is bnmf_relabel's, as
+ * bnmf_subtypes takes it: NULL = identity; a row of -1 throughout leaves the sample out (unmatched); every other row of a used sample
+ * must be a permutation of 0 .. N-1.  The S' matched samples of the S used ones are numbered t = 1 .. S' in order.
+ * Per matched sample and member g, with cs_s[n] bnmf_map's column sum of P_s:
+ *   x[n]            = A_s[n] != 0 ? E_s[n,g] * cs_s[n] : +0.0        bnmf_contrast's renormalised exposure, the same bits
+ *   q_t[perm[s][n]] = x[n]                                            the aligned exposure
+ * Two passes over the samples, per member:
+ *   mu[j]    = (sum_t q_t[j], t ascending from +0.0) / S'
+ *   d_t[j]   = q_t[j] - mu[j]
+ *   cov[j,l] = (sum_t d_t[j] * d_t[l], t ascending from +0.0; the product rounded before it is added) / (S' - 1)    for l <= j, mirrored
+ *   r[j,l]   = cov[j,j] * cov[l,l] > 0 and finite ? cov[j,l] / sqrt(cov[j,j] * cov[l,l]) : NaN   (j != l; "undefined": a factor never
+ *              active in this tumour, e.g. excluded by A in every sample, has variance 0);   r[j,j] = NaN
+ * The matrix is bitwise symmetric.
+ * tumour [BNMF_TRD_NTUM][G]: 0 the smallest defined r[j,l] over j > l (j ascending, then l ascending, the first wins; NaN without one);
+ *   1 the number of defined pairs j > l; 2 vt / sv, the variance of the tumour's total over the sum of the marginal variances:
+ *   vt = sum_j (sum_l cov[j,l]), l ascending inside and j ascending outside, both from +0.0; sv = sum_j cov[j,j]; NaN unless sv > 0 and
+ *   finite.  Below 1 the signatures trade mutations, 1 means they vary independently.  All rows NaN for a left-out tumour.
+ * pair_at [G]: j * N + l of row 0's pair; -1 without one or for a left-out tumour.
+ * pair [BNMF_TRD_NPAIR][N*N] (row-major j * N + l, symmetric, the diagonal NaN), over the members with a defined r[j,l], n_def of them:
+ *   0 the mean r: canonB over the member positions of (defined ? r : +0.0), divided by n_def (NaN if n_def = 0); canonB is bnmf_regress's
+ *   blocked canonical sum (blocks of BNMF_REG_BLOCK positions, each the canonical W = 64 sum, the block sums added ascending from +0.0);
+ *   1 n_def; 2 #(r <= -min_corr) / n_def; 3 #(r >= min_corr) / n_def (both NaN if n_def = 0); 4 the mean covariance canonB(cov[j,l]) / m
+ *   over all members.
+ * dense [Q][2][N*N]: for query[q] the covariance matrix, then the correlation matrix (the diagonal NaN).  A tumour may be named more than
+ *   once.
+ * setstat [BNMF_TRD_NSET][C][G], with sets [N] (values 0 .. C-1, or -1 for a signature in no set; NULL with C = 0: no sets), per set c and
+ *   member: 0 sum_{j in c} mu[j], j ascending from +0.0; 1 the variance of the set's summed exposure sum_{j in c} (sum_{l in c} cov[j,l]),
+ *   nested and ordered as vt (the SD^2 to quote for "SBS2 + SBS13"; no marginal output gives it); 2 sum_{j in c} cov[j,j]; 3 row 1 / row 2,
+ *   NaN unless row 2 > 0 and finite.  NaN for a left-out tumour.
+ * info (sizeof = 64): n_used = S, n_matched = S', n_unmatched, n_included = m, n_left_out = G - m, n_sets = C, n_query = Q, min_corr as
+ *   given; n_traded = the members whose tumour row 0 is <= -min_corr; strongest_pair and strongest_pair_at = the smallest pair row 0 over
+ *   j > l and its j * N + l (the first wins; NaN and -1 without one); mean_ratio = the canonical W = 64 sum of tumour row 2 over the
+ *   members that have one, in member order, divided by their number (NaN without one).  min_corr is a reporting convention like
+ *   min_cosine = 0.9, not a test.
+ * Only + - * /, sqrt, comparisons and whole numbers, no contraction, every sum in the order above: the bits depend on the samples, used[],
+ * include[], perm, sets, query and min_corr only, not on the form of the kernel, its tiles or the band of members whose covariances pass
+ * through the scratch.  A tumour's own values involve no other tumour and every sum over tumours runs over the member list, so include[]
+ * gives the bits of a cohort without the tumours left out.  Reads only the P, E and A rings; works for every likelihood and prior; draws
+ * no random number, consumes none of the chain's streams and is read-only for the chain.  bnmf_tradeoff_at: the n_samples iterations that
+ * end at end_iter; the range rule, used[], BNMF_ESIZE and BNMF_ESTATE as for bnmf_subtypes_at; bnmf_tradeoff(h, n, ...) is
+ * bnmf_tradeoff_at(h, iter, n, ...).  Every output array may be NULL.  Refused before any device work, with BNMF_EINVAL: a null info; a
+ * used[] or include[] value other than 0 / 1 (the index named); a perm row of a used sample that is neither a permutation nor -1
+ * throughout (the sample named); C outside 0 .. BNMF_TRD_MAX_C, C > 0 with a null sets, a sets value outside -1 .. C-1 (the factor
+ * named), an empty set (named); Q < 0 or Q > 0 with a null query; a query[q] outside 0 .. G-1 or left out (q named); a min_corr that is
+ * NaN or outside [0, 1].  With BNMF_ESIZE: fewer than 2 used samples, fewer than 2 matched samples, m < 1, N > BNMF_TRD_MAX_N.  With
+ * BNMF_ESTATE: window = 0, a poisoned handle or nothing recorded. */
+#define BNMF_TRD_NTUM  3         /* tumour rows: smallest correlation, defined pairs, variance of the total / sum of the variances */
+#define BNMF_TRD_NPAIR 5         /* pair rows: mean r, n_def, share r <= -min_corr, share r >= min_corr, mean covariance */
+#define BNMF_TRD_NSET  4         /* setstat rows: mean, variance of the sum, sum of the variances, their ratio */
+#define BNMF_TRD_MAX_C 32        /* the most sets */
+#define BNMF_TRD_MAX_N 128       /* the most factors */
+typedef struct { int32_t n_used, n_matched, n_unmatched, n_included, n_left_out, n_sets, n_query, n_traded, strongest_pair_at /* j * N + l; -1 if none */,
+                 _pad; double strongest_pair, mean_ratio, min_corr; } bnmf_tradeoff_info;
+int bnmf_tradeoff(bnmf_handle*, int last_n, const int32_t* used,
+                  const int32_t* include /* [G] 0 / 1, NULL = all */,
+                  const int32_t* perm    /* [last_n][N] row-major: bnmf_relabel's perm over the whole range; NULL = identity */,
+                  const int32_t* sets    /* [N] 0 .. C-1 or -1; NULL with C = 0 */, int C,
+                  const int32_t* query   /* [Q] tumours, may be NULL with Q = 0 */, int Q, double min_corr,
+                  double*  tumour  /* [BNMF_TRD_NTUM][G]; may be NULL */,
+                  int32_t* pair_at /* [G]; may be NULL */,
+                  double*  pair    /* [BNMF_TRD_NPAIR][N*N]; may be NULL */,
+                  double*  dense   /* [Q][2][N*N]; may be NULL */,
+                  double*  setstat /* [BNMF_TRD_NSET][C][G]; may be NULL */,
+                  bnmf_tradeoff_info* info);
+int bnmf_tradeoff_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm, const int32_t* sets, int C,
+                     const int32_t* query, int Q, double min_corr, double* tumour, int32_t* pair_at, double* pair, double* dense, double* setstat,
+                     bnmf_tradeoff_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

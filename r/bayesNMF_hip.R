@@ -595,6 +595,84 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       r$n_included, r$n_used - r$n_flat, r$n_flat, r$share, r$n_overdispersed, r$max_dispersion, r$n_biased))
       out
     },
+    # Trade-offs between signatures within a tumour, on the device (bnmf_tradeoff_at; not in the reference): which signatures exchange
+    # mutations from sample to sample in one tumour, and how uncertain is a SUM of exposures?  Over iterations end_iter - n_samples + 1
+    # ... end_iter (defaults as get_WAIC), restricted to idx, per tumour the N x N covariance of its renormalised exposures over the
+    # samples and the correlations.  With relabel the range is first aligned by get_relabelling() and its perm is handed on; an unmatched
+    # sample is left out.  sets: an integer label per signature (1-based, NA = in no set) or a named list of 1-based signature indices;
+    # query: tumours (1-based indices or column names) whose whole matrices are wanted; include as in get_similarity.  min_corr = 0.5 is a
+    # reporting convention like min_cosine = 0.9, not a test.  list(tumours (a data frame: tumour, min_corr, pair_j, pair_l (1-based, NA =
+    # none), n_defined, total_ratio, included), pair (a list of N x N symmetric matrices with an NA diagonal: mean_corr, n_defined,
+    # p_negative, p_positive, mean_cov), sets (a data frame: set, tumour, mean, sd_sum, sd_if_independent, ratio; with sets), dense (N x N
+    # x 2 x Q: covariance, correlation; with query) and the info fields).
+    get_tradeoff = function(sets = NULL, query = NULL, include = NULL, relabel = TRUE, min_corr = 0.5, end_iter = self$state$iter,
+                            n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      idx0 <- idx
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      G <- self$dims$G; N <- self$dims$N
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      member <- if (is.null(include)) rep(TRUE, G) else include
+      names <- colnames(self$data)
+      label <- function(g) if (is.null(names)) g else names[g]
+      set_names <- NULL; st <- NULL
+      if (is.list(sets)) {
+        set_names <- if (is.null(names(sets))) seq_along(sets) else names(sets)
+        st <- rep(-1L, N)
+        for (c in seq_along(sets)) {
+          at <- as.integer(sets[[c]])
+          if (length(at) == 0 || any(at < 1 | at > N)) stop("set ", set_names[c], " is empty or names a signature outside 1 .. ", N)
+          if (any(st[at] >= 0)) stop("set ", set_names[c], " holds a signature that another set holds")
+          st[at] <- c - 1L
+        }
+      } else if (!is.null(sets)) {
+        if (length(sets) != N) stop("sets must have one label per signature (N = ", N, ")")
+        st <- ifelse(is.na(sets), -1L, as.integer(sets) - 1L)
+        set_names <- seq_len(max(st) + 1L)
+      }
+      C <- if (is.null(st)) 0L else max(st) + 1L
+      q <- NULL
+      if (!is.null(query)) {
+        q <- if (is.character(query)) match(query, names) else as.integer(query)
+        if (anyNA(q)) stop("query names no tumour of the data: ", paste(utils::head(query[is.na(q)], 5), collapse = ", "))
+      }
+      perm <- NULL
+      if (relabel) {
+        pm <- self$get_relabelling(end_iter = end_iter, n_samples = n_samples, idx = if (is.null(idx0)) NULL else idx0)$perm
+        pm <- t(matrix(as.integer(pm), nrow = N))                       # get_relabelling's is N x S: here S x N, 1-based labels, NA = unmatched
+        perm <- matrix(-1L, n_samples, N)
+        perm[if (is.null(used)) seq_len(n_samples) else which(used), ] <- ifelse(is.na(pm), -1L, pm - 1L)
+      }
+      r <- .Call("C_bnmf_tradeoff", self$handle, as.integer(end_iter), as.integer(n_samples), used, include, perm, st,
+                 if (is.null(q)) NULL else as.integer(q - 1L), as.double(c(min_corr, C, G, N)))
+      out <- r[c("n_used", "n_matched", "n_unmatched", "n_included", "n_left_out", "n_sets", "n_query", "n_traded", "strongest_pair", "mean_ratio", "min_corr")]
+      out$strongest_pair_at <- if (r$strongest_pair_at < 0) NA_integer_ else c(r$strongest_pair_at %/% N, r$strongest_pair_at %% N) + 1L
+      at <- r$pair_at
+      out$tumours <- data.frame(tumour = label(seq_len(G)), min_corr = r$tumour[, 1], pair_j = ifelse(at < 0, NA_integer_, at %/% N + 1L),
+                                pair_l = ifelse(at < 0, NA_integer_, at %% N + 1L), n_defined = r$tumour[, 2], total_ratio = r$tumour[, 3], included = member)
+      rows <- c("mean_corr", "n_defined", "p_negative", "p_positive", "mean_cov")
+      out$pair <- setNames(lapply(seq_along(rows), function(k) matrix(r$pair[, k], N, N)), rows)
+      if (C > 0) {
+        sst <- array(r$setstat, c(G, C, 4))
+        out$sets <- do.call(rbind, lapply(seq_len(C), function(c) data.frame(set = set_names[c], tumour = label(seq_len(G)), mean = sst[, c, 1],
+                                                                             sd_sum = sqrt(sst[, c, 2]), sd_if_independent = sqrt(sst[, c, 3]), ratio = sst[, c, 4])))
+      }
+      if (!is.null(q)) { out$dense <- array(r$dense, c(N, N, 2, length(q))); out$query <- label(q) }
+      message(sprintf("Trade-offs: %d tumours over %d samples (%d unmatched); %d tumours with a correlation <= -%g; mean variance ratio of the total %.3g",
+                      r$n_included, r$n_matched, r$n_unmatched, r$n_traded, r$min_corr, r$mean_ratio))
+      out
+    },
     # Co-activity of the signatures, on the device (bnmf_coactivity_at; not in the reference): do two signatures act in the same tumours
     # or exclude each other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are
     # negatively correlated)?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every

@@ -957,6 +957,84 @@ SEXP C_bnmf_residuals_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEX
   UNPROTECT(1);
   return out;
 }
+/* Trade-offs between signatures within a tumour on the device (bnmf_tradeoff / bnmf_tradeoff_at): C_bnmf_tradeoff(ptr, end_iter (integer,
+ * or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or NULL = all),
+ * perm (integer n_samples x N matrix of 0-based places, a row of -1 / NA = the sample is unmatched; or NULL = identity), sets (integer N
+ * of 0-based sets, -1 / NA = in no set; or NULL), query (integer, 0-based tumours; or NULL), opts (real c(min_corr, C, G, N))) ->
+ * list(n_used, n_matched, n_unmatched, n_included, n_left_out, n_sets, n_query, n_traded, strongest_pair_at (0-based j * N + l, -1 =
+ * none), strongest_pair, mean_ratio, min_corr, tumour (G x 3: smallest correlation, defined pairs, variance ratio of the total), pair_at
+ * (integer G, 0-based j * N + l, -1 = none), pair (N N x 5: mean r, n_def, share r <= -min_corr, share r >= min_corr, mean covariance;
+ * row l + N j, symmetric), dense (N N x 2 x Q: covariance, correlation; NULL without a query), setstat (G x C x 4; NULL without sets))
+ * over iterations end_iter - n_samples + 1 ... end_iter.  C_bnmf_tradeoff_at: the same with end_iter required */
+typedef struct { int32_t *u, *inc, *perm, *sets, *q; int Q, C; double min_corr; } trd_in;
+static SEXP trd_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP sets, SEXP query, SEXP opts, trd_in* in) {
+  const int n = INTEGER(n_samples)[0];
+  if (XLENGTH(opts) != 4) Rf_error("bnmf: opts has %ld entries, c(min_corr, C, G, N) is needed", (long)XLENGTH(opts));
+  const double* o = REAL(opts);
+  const int G = (int)o[2], N = (int)o[3];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  if (perm != R_NilValue && XLENGTH(perm) != (R_xlen_t)n * N) Rf_error("bnmf: perm has %ld entries for %d samples of %d factors", (long)XLENGTH(perm), n, N);
+  if (sets != R_NilValue && XLENGTH(sets) != (R_xlen_t)N) Rf_error("bnmf: sets has %ld labels for %d factors", (long)XLENGTH(sets), N);
+  in->u = lgl_flags(used, n);
+  in->inc = lgl_flags(include, G);
+  in->perm = NULL;
+  if (perm != R_NilValue) {                                                /* the R matrix is column-major: row s of the ABI is its row s */
+    in->perm = (int32_t*)R_alloc((size_t)n * N, sizeof(int32_t));
+    for (int s = 0; s < n; ++s) for (int j = 0; j < N; ++j) { const int v = INTEGER(perm)[s + (size_t)n * j]; in->perm[(size_t)s * N + j] = v == NA_INTEGER ? -1 : v; }
+  }
+  in->sets = NULL;
+  if (sets != R_NilValue) {
+    in->sets = (int32_t*)R_alloc((size_t)N, sizeof(int32_t));
+    for (int j = 0; j < N; ++j) { const int v = INTEGER(sets)[j]; in->sets[j] = v == NA_INTEGER ? -1 : v; }
+  }
+  in->Q = query == R_NilValue ? 0 : (int)XLENGTH(query);
+  in->q = in->Q > 0 ? (int32_t*)INTEGER(query) : NULL;
+  in->min_corr = o[0]; in->C = (int)o[1];
+  const int Cb = in->C > BNMF_TRD_MAX_C ? BNMF_TRD_MAX_C : in->C;          /* (the library refuses a larger C: the buffers only have to exist) */
+  static const char* nms[] = {"n_used", "n_matched", "n_unmatched", "n_included", "n_left_out", "n_sets", "n_query", "n_traded", "strongest_pair_at",
+                              "strongest_pair", "mean_ratio", "min_corr", "tumour", "pair_at", "pair", "dense", "setstat"};
+  SEXP out = PROTECT(named_list(17, nms));
+  SET_VECTOR_ELT(out, 12, Rf_allocMatrix(REALSXP, G, BNMF_TRD_NTUM));
+  SET_VECTOR_ELT(out, 13, Rf_allocVector(INTSXP, G));
+  SET_VECTOR_ELT(out, 14, Rf_allocMatrix(REALSXP, N * N, BNMF_TRD_NPAIR));
+  if (in->Q > 0) SET_VECTOR_ELT(out, 15, Rf_allocVector(REALSXP, (R_xlen_t)N * N * 2 * in->Q));
+  if (Cb > 0) SET_VECTOR_ELT(out, 16, Rf_allocVector(REALSXP, (R_xlen_t)G * Cb * BNMF_TRD_NSET));
+  UNPROTECT(1);
+  return out;
+}
+static int32_t* trd_int_buf(SEXP out, int i) { SEXP x = VECTOR_ELT(out, i); return x == R_NilValue ? NULL : (int32_t*)INTEGER(x); }
+static void trd_finish(SEXP out, const bnmf_tradeoff_info* info) {
+  const int32_t v[9] = {info->n_used, info->n_matched, info->n_unmatched, info->n_included, info->n_left_out, info->n_sets, info->n_query, info->n_traded,
+                        info->strongest_pair_at};
+  for (int i = 0; i < 9; ++i) SET_VECTOR_ELT(out, i, Rf_ScalarInteger(v[i]));
+  SET_VECTOR_ELT(out, 9, Rf_ScalarReal(info->strongest_pair)); SET_VECTOR_ELT(out, 10, Rf_ScalarReal(info->mean_ratio));
+  SET_VECTOR_ELT(out, 11, Rf_ScalarReal(info->min_corr));
+}
+SEXP C_bnmf_tradeoff(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP sets, SEXP query, SEXP opts) {
+  trd_in in;
+  SEXP out = PROTECT(trd_alloc(n_samples, used, include, perm, sets, query, opts, &in));
+  bnmf_tradeoff_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_tradeoff(get_handle(ptr), INTEGER(n_samples)[0], in.u, in.inc, in.perm, in.sets, in.C, in.q, in.Q, in.min_corr, map_buf(out, 12), trd_int_buf(out, 13),
+                      map_buf(out, 14), map_buf(out, 15), map_buf(out, 16), &info));
+  else
+    chk(bnmf_tradeoff_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.perm, in.sets, in.C, in.q, in.Q, in.min_corr,
+                         map_buf(out, 12), trd_int_buf(out, 13), map_buf(out, 14), map_buf(out, 15), map_buf(out, 16), &info));
+  trd_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_tradeoff_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP sets, SEXP query, SEXP opts) {
+  trd_in in;
+  SEXP out = PROTECT(trd_alloc(n_samples, used, include, perm, sets, query, opts, &in));
+  bnmf_tradeoff_info info;
+  chk(bnmf_tradeoff_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.perm, in.sets, in.C, in.q, in.Q, in.min_corr,
+                       map_buf(out, 12), trd_int_buf(out, 13), map_buf(out, 14), map_buf(out, 15), map_buf(out, 16), &info));
+  trd_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Silhouette stability of the recorded signatures on the device (bnmf_stability / bnmf_stability_at): C_bnmf_stability(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), labels (integer n_samples x N
  * matrix of 0-based clusters, -1 / NA = left out; or NULL = the factor), extra_P (K x X real matrix, or NULL), extra_label (integer X,
@@ -1327,6 +1405,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_similarity", (DL_FUNC)&C_bnmf_similarity, 9}, {"C_bnmf_similarity_at", (DL_FUNC)&C_bnmf_similarity_at, 9},
   {"C_bnmf_subtypes", (DL_FUNC)&C_bnmf_subtypes, 9}, {"C_bnmf_subtypes_at", (DL_FUNC)&C_bnmf_subtypes_at, 9},
   {"C_bnmf_residuals", (DL_FUNC)&C_bnmf_residuals, 6}, {"C_bnmf_residuals_at", (DL_FUNC)&C_bnmf_residuals_at, 6},
+  {"C_bnmf_tradeoff", (DL_FUNC)&C_bnmf_tradeoff, 9}, {"C_bnmf_tradeoff_at", (DL_FUNC)&C_bnmf_tradeoff_at, 9},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
