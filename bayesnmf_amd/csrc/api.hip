@@ -47,6 +47,7 @@
 #include "subtypes.h"
 #include "residuals.h"
 #include "tradeoff.h"
+#include "prune.h"
 
 using namespace bnmf;
 

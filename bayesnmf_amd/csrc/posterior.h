@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals, bnmf_tradeoff (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h, residuals.h and tradeoff.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals, bnmf_tradeoff, bnmf_prune (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h, residuals.h, tradeoff.h and prune.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1892,6 +1892,111 @@ static int tradeoff_impl(bnmf_handle* h, const char* fn, Range r, const int32_t*
   return 0;
 }
 
+// Sparse per-tumour assignment with refit over the samples of r that used[] flags (prune.h): the member list is made here;
+// k_prn_data (the members' data k-major, mm and t) and k_map_colsum run once; then per batch of samples project.h's k_proj_x (the columns
+// of x that take part), k_prune (a lane per (s, member): the elimination; e_sparse and the five values in the scratch), attribution.h's
+// k_attr_share and k_attr_stats with G := m and k_prn_stats (the tumour rows continued in sample order, the series).  The outputs by
+// tumour, the signature rows and the info fields are prune_finish's.
+static_assert(PR_NLOAD == BNMF_PRN_NLOAD && PR_NLOAD == AT_NLOAD && PR_NTUM == BNMF_PRN_NTUM && PR_NSER == BNMF_PRN_NSER && PR_NSIG == BNMF_PRN_NSIG &&
+                  PR_MAX_N == BNMF_PRN_MAX_N && PR_MAX_N <= PJ_MAX_N, "prune.h, attribution.h, project.h and bnmf.h disagree");
+static constexpr size_t PRN_SCRATCH_CAP = (size_t)256 << 20;    // bytes of a batch's blocks of the scratch
+static int prune_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, int n_steps, double max_loss, double* load,
+                      double* tumour, double* series, double* signature, double* exposures, bnmf_prune_info* info) {
+  if (int rc = range_enter(h, fn, h && info, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  if (h->cfg.likelihood == BNMF_NORMAL)
+    return fail(BNMF_EMODEL, "%s: the handle has the Normal likelihood; its refit is a different algorithm (least squares, not the KL update) and is out of scope", fn);
+  std::vector<int> members;
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) members.push_back(g);
+  }
+  const int m = (int)members.size();
+  if (n_steps < 1 || n_steps > 100000) return fail(BNMF_EINVAL, "%s: n_steps = %d is not in 1..100000", fn, n_steps);
+  if (!std::isfinite(max_loss)) return fail(BNMF_EINVAL, "%s: max_loss = %g is not a finite number", fn, max_loss);
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  const int S = (int)slots.size();
+  if (S < 1) return fail(BNMF_ESIZE, "%s: no used sample", fn);
+  if (m < 1) return fail(BNMF_ESIZE, "%s: no included tumour", fn);
+  if (N > PR_MAX_N) return fail(BNMF_ESIZE, "%s: N = %d factors but at most BNMF_PRN_MAX_N = %d fit a lane's columns of the LDS", fn, N, PR_MAX_N);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  bool reg = N <= PR_MAX_NT;
+  if (const char* e = getenv("BNMF_PRN_FORM")) if (atoi(e) == 1) reg = false;                              // tests, tools: the LDS form at any N
+  const int NS = prn_row_stride(N, reg);
+  const size_t Nm = (size_t)N * m, KNS = (size_t)K * NS, lenP = (size_t)K * N;
+  const size_t per = (((reg ? 1 : 2) + (exposures ? 1 : 0)) * Nm + (size_t)(PR_NVAL + 1) * m + KNS + N) * sizeof(double);   // scratch bytes of one sample
+  long long want = (long long)std::max<size_t>(1, PRN_SCRATCH_CAP / per);
+  if (const char* e = getenv("BNMF_PRN_BATCH")) { const long long v = atoll(e); if (v >= 1) want = v; }   // tests: the batch size
+  const int Sb = (int)std::min<long long>({want, (long long)S, 65535LL});                                  // (a batch is the grid's y)
+  const bool stage = !reg && prn_lds_bytes(K, N, false, true) <= LDS_CAP;
+  const size_t lds = prn_lds_bytes(K, N, reg, stage);
+  if (lds > LDS_CAP) return fail(BNMF_ESIZE, "%s: N = %d factors need %zu bytes of LDS", fn, N, lds);      // (unreachable for N <= BNMF_PRN_MAX_N)
+  PrnArgs a{};
+  double *cs, *dMt, *dmm, *dtt, *dxg, *dscr, *dvals, *dstate, *du, *dst, *dload, *dser, *dtst, *dtum, *dtser, *dexp; int *dslots, *dmem, *dnin, *didx;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)S * N); dMt = c.take<double>((size_t)K * m); dmm = c.take<double>(m); dtt = c.take<double>(m);
+        dxg = c.take<double>((size_t)Sb * KNS); dscr = c.take<double>((size_t)Sb * Nm); dvals = c.take<double>((size_t)Sb * PR_NVAL * m);
+        dstate = reg ? nullptr : c.take<double>((size_t)Sb * Nm); du = c.take<double>((size_t)Sb * m);
+        dst = c.take<double>(AT_NLOAD * Nm); dload = c.take<double>(AT_NLOAD * Nm); dser = c.take<double>((size_t)S * N);
+        dtst = c.take<double>((size_t)PR_NTUM * m); dtum = c.take<double>((size_t)PR_NTUM * m); dtser = c.take<double>((size_t)PR_NSER * S);
+        dexp = exposures ? c.take<double>((size_t)Sb * Nm) : nullptr;
+        dslots = c.take<int>(S); dmem = c.take<int>(m); dnin = c.take<int>(Sb); didx = c.take<int>((size_t)Sb * N);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, slots.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const double *ringP = h->arr[BNMF_P].ring, *ringA = h->arr[BNMF_A].ring;
+  hipLaunchKernelGGL(k_prn_data<PR_NTUM>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const int32_t*)h->dM, (const double*)h->dMf, (const int*)dmem, K,
+                     m, dMt, dmm, dtt);
+  hipLaunchKernelGGL(k_map_colsum, dim3(S, N), dim3(64), 0, h->stream, ringP, lenP, K, N, (const int*)dslots, cs);
+  using PrnKernel = decltype(&k_prune<8, false>);
+  const PrnKernel regk[5] = {nullptr, k_prune<8, false>, k_prune<16, false>, k_prune<24, false>, k_prune<32, false>};
+  const PrnKernel kern = reg ? regk[NS / 8] : (stage ? k_prune<0, true> : k_prune<0, false>);
+  if (int rc = opt_in_lds(kern, lds)) return rc;
+  const int T = reg ? PR_T : PR_TL;
+  a.xg = dxg; a.ringE = h->arr[BNMF_E].ring; a.Mt = dMt; a.mm = dmm; a.tt = dtt; a.nin = dnin; a.idx = didx; a.members = dmem; a.scr = dscr; a.vals = dvals;
+  a.state = dstate; a.lenE = (size_t)N * G; a.K = K; a.N = N; a.G = G; a.m = m; a.n_steps = n_steps; a.max_loss = max_loss;
+  const double tiny = 0x1p-1074;                                        // k_attr_stats counts a >= min_load: with the smallest positive double, a > 0
+  std::vector<double> hexp(exposures ? (size_t)Sb * Nm : 0);
+  if (exposures) std::fill(exposures, exposures + (size_t)S * N * G, std::nan(""));
+  for (int s0 = 0; s0 < S; s0 += Sb) {
+    const int nb = std::min(Sb, S - s0), last = s0 + nb == S ? 1 : 0;
+    a.cs = cs + (size_t)s0 * N; a.slots = dslots + s0;
+    hipLaunchKernelGGL(k_proj_x, dim3(nb), dim3(256), 0, h->stream, ringP, ringA, lenP, K, N, NS, (const int*)dslots + s0, (const double*)cs + (size_t)s0 * N, dxg, dnin,
+                       didx);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((m + T - 1) / T), (unsigned)nb), dim3(T), lds, h->stream, a);
+    const size_t nsm = (size_t)nb * m;
+    hipLaunchKernelGGL(k_attr_share, dim3((unsigned)((nsm + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, m, du);
+    hipLaunchKernelGGL(k_attr_stats, dim3((unsigned)((size_t)nb * N + (Nm + AT_TT - 1) / AT_TT)), dim3(AT_TT), 0, h->stream, (const double*)dscr, (const double*)du, nb,
+                       N, m, S, s0, last, tiny, dst, dser, dload);
+    hipLaunchKernelGGL(k_prn_stats<PR_NTUM>, dim3((unsigned)(2 * (size_t)nb + ((size_t)m + PR_TT - 1) / PR_TT)), dim3(PR_TT), 0, h->stream, (const double*)dvals,
+                       (const double*)dmm, nb, m, S, s0, last, dtst, dtser, dtum);
+    HIPCHK(hipGetLastError());
+    if (exposures) {
+      hipLaunchKernelGGL(k_proj_exposures, dim3((unsigned)(((size_t)nb * Nm + 255) / 256)), dim3(256), 0, h->stream, (const double*)dscr, nb, N, m, dexp);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hexp.data(), dexp, (size_t)nb * Nm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));             // the next batch overwrites the scratch
+      for (int s = 0; s < nb; ++s)
+        for (int j = 0; j < m; ++j)
+          std::memcpy(exposures + ((size_t)(s0 + s) * G + (size_t)members[j]) * N, hexp.data() + ((size_t)s * m + j) * N, (size_t)N * sizeof(double));
+    }
+  }
+  std::vector<double> hl(AT_NLOAD * Nm), ht((size_t)PR_NTUM * m), htr(m), hs((size_t)PR_NSER * S), hm(m);
+  HIPCHK(hipMemcpyAsync(hl.data(), dload, hl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(ht.data(), dtum, ht.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(htr.data(), dtst + (size_t)6 * m, htr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hs.data(), dtser, hs.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hm.data(), dmm, hm.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::memset(info, 0, sizeof *info);
+  prune_finish(members.data(), m, G, N, S, hm.data(), hl.data(), ht.data(), htr.data(), hs.data(), load, tumour, signature, info);
+  info->n_used = S; info->n_steps = n_steps; info->max_loss = max_loss;
+  if (series) std::memcpy(series, hs.data(), hs.size() * sizeof(double));
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -2051,6 +2156,15 @@ int bnmf_tradeoff_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t*
                      bnmf_tradeoff_info* info) {
   return tradeoff_impl(h, "bnmf_tradeoff_at", {true, end_iter, n_samples}, used, include, perm, sets, C, query, Q, min_corr, tumour, pair_at, pair, dense, setstat,
                        info);
+}
+
+int bnmf_prune(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, int n_steps, double max_loss, double* load, double* tumour,
+               double* series, double* signature, double* exposures, bnmf_prune_info* info) {
+  return prune_impl(h, "bnmf_prune", Range{false, 0, last_n}, used, include, n_steps, max_loss, load, tumour, series, signature, exposures, info);
+}
+int bnmf_prune_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_loss, double* load,
+                  double* tumour, double* series, double* signature, double* exposures, bnmf_prune_info* info) {
+  return prune_impl(h, "bnmf_prune_at", Range{true, end_iter, n_samples}, used, include, n_steps, max_loss, load, tumour, series, signature, exposures, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

@@ -1,11 +1,11 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
 // (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's, bnmf_similarity's,
-// bnmf_subtypes' (DESIGN.md 25), bnmf_residuals'  and bnmf_tradeoff's.  No device and no handle: posterior.h includes it, and a stand-alone host program can
+// bnmf_subtypes' (DESIGN.md 25), bnmf_residuals' (DESIGN.md 26), bnmf_tradeoff's and bnmf_prune's.  No device and no handle: posterior.h includes it, and a stand-alone host program can
 // (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp,
-// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp, tools/residuals_reduce_check.cpp and tools/tradeoff_reduce_check.cpp, built with
+// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp, tools/residuals_reduce_check.cpp, tools/tradeoff_reduce_check.cpp and tools/prune_reduce_check.cpp, built with
 // -fsanitize=address,undefined by tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py,
-// tests/test_similarity_host.py, tests/test_subtypes_host.py, tests/test_residuals_host.py and tests/test_tradeoff_host.py).  Compile with -ffp-contract=off, as the library is.
+// tests/test_similarity_host.py, tests/test_subtypes_host.py, tests/test_residuals_host.py, tests/test_tradeoff_host.py and tests/test_prune_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -461,4 +461,48 @@ struct res_lead { double trace, lambda, share, move; };
       if (pair) for (int k = 0; k < BNMF_TRD_NPAIR; ++k) { pair[(size_t)k * NN + p] = row[k]; pair[(size_t)k * NN + pt] = row[k]; }
       if (!std::isnan(row[0]) && (info->strongest_pair_at < 0 || row[0] < info->strongest_pair)) { info->strongest_pair = row[0]; info->strongest_pair_at = (int32_t)p; }
     }
+}
+
+// ---- bnmf_prune's finish: from the rows in member order to the outputs by tumour, the signature rows and the info fields ----
+// members [m] ascending; mm [m] (a member is defined iff mm > 0), ld [4][N*m] (each row n + N j: mean e_sparse, its variance, mean share,
+// p_kept), tum [7][m] and trials [m] (every member's whole-number sum of trials over the samples) as the device left them; ser [2][S]: in,
+// the sums of n_kept and cos_f over the defined members; out, divided by their number (NaN without one).  load [4][N*G], tumour [7][G] and
+// signature [3][N] may each be null; a left-out or undefined tumour holds NaN.  signature: 0 the number of defined members with
+// p_kept >= 0.5, 1 the mean p_kept and 2 the sum of the mean loads, both the canonical W = 64 sum over the defined members ascending.
+// Of info n_included, n_undefined, n_single, trials and max_change are set.
+[[maybe_unused]] static void prune_finish(const int* members, long m, long G, int N, int S, const double* mm, const double* ld, const double* tum,
+                                          const double* trials, double* ser, double* load, double* tumour, double* signature, bnmf_prune_info* info) {
+  const double nan = std::nan("");
+  const size_t Nm = (size_t)N * (size_t)m, NG = (size_t)N * (size_t)G;
+  long ndef = 0;
+  for (long j = 0; j < m; ++j) ndef += mm[j] > 0.0 ? 1 : 0;
+  for (int r = 0; r < BNMF_PRN_NSER; ++r) for (int s = 0; s < S; ++s) ser[(size_t)r * S + s] = ndef > 0 ? ser[(size_t)r * S + s] / (double)ndef : nan;
+  if (load) std::fill(load, load + (size_t)BNMF_PRN_NLOAD * NG, nan);
+  if (tumour) std::fill(tumour, tumour + (size_t)BNMF_PRN_NTUM * G, nan);
+  int64_t total = 0; int32_t single = 0; double mx = 0.0;
+  for (long j = 0; j < m; ++j) {
+    if (!(mm[j] > 0.0)) continue;
+    const size_t g = (size_t)members[j];
+    if (load) for (int r = 0; r < BNMF_PRN_NLOAD; ++r) for (int n = 0; n < N; ++n) load[(size_t)r * NG + (size_t)n + (size_t)N * g] = ld[(size_t)r * Nm + (size_t)n + (size_t)N * j];
+    if (tumour) for (int r = 0; r < BNMF_PRN_NTUM; ++r) tumour[(size_t)r * G + g] = tum[(size_t)r * m + j];
+    total += (int64_t)trials[j];
+    single += tum[(size_t)4 * m + j] == 1.0 ? 1 : 0;
+    const double c = tum[(size_t)5 * m + j];
+    if (c > mx) mx = c;
+  }
+  info->n_included = (int32_t)m; info->n_undefined = (int32_t)(m - ndef); info->n_single = single; info->trials = total; info->max_change = mx;
+  if (!signature) return;
+  std::vector<double> tp((size_t)std::max<long>(ndef, 1)), tl((size_t)std::max<long>(ndef, 1));
+  for (int n = 0; n < N; ++n) {
+    long cnt = 0, i = 0;
+    for (long j = 0; j < m; ++j) {
+      if (!(mm[j] > 0.0)) continue;
+      const double p = ld[3 * Nm + (size_t)n + (size_t)N * j];
+      cnt += p >= 0.5 ? 1 : 0;
+      tp[(size_t)i] = p; tl[(size_t)i] = ld[(size_t)n + (size_t)N * j]; ++i;
+    }
+    signature[n] = (double)cnt;
+    signature[(size_t)N + n] = ndef > 0 ? con_canon64(tp.data(), (size_t)ndef, 1) / (double)ndef : nan;
+    signature[2 * (size_t)N + n] = con_canon64(tl.data(), (size_t)ndef, 1);
+  }
 }

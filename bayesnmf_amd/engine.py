@@ -152,6 +152,11 @@ class BnmfTradeoffInfo(C.Structure):
                 ("strongest_pair", C.c_double), ("mean_ratio", C.c_double), ("min_corr", C.c_double)]
 
 
+class BnmfPruneInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_included", C.c_int32), ("n_undefined", C.c_int32), ("n_single", C.c_int32), ("n_steps", C.c_int32),
+                ("_pad", C.c_int32), ("trials", C.c_int64), ("max_change", C.c_double), ("max_loss", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -190,6 +195,10 @@ TRD_TUMOUR_ROWS = ("min_corr", "n_defined", "total_ratio")
 TRD_PAIR_ROWS = ("mean_corr", "n_defined", "p_negative", "p_positive", "mean_cov")
 TRD_SET_ROWS = ("mean", "var_sum", "sum_var", "ratio")
 TRD_MAX_C = 32
+PRN_LOAD_ROWS = ("load_mean", "load_var", "share", "p_kept")
+PRN_TUMOUR_ROWS = ("cos_0", "cos_f", "n_kept", "n_kept_min", "n_kept_max", "rel_change", "mean_trials")
+PRN_SERIES_ROWS = ("n_kept", "cos_f")
+PRN_SIGNATURE_ROWS = ("n_tumours", "mean_p_kept", "total_load")
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -211,7 +220,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
                "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at",
                "bnmf_subtypes", "bnmf_subtypes_at", "bnmf_residuals", "bnmf_residuals_at",
-               "bnmf_tradeoff", "bnmf_tradeoff_at"]
+               "bnmf_tradeoff", "bnmf_tradeoff_at", "bnmf_prune", "bnmf_prune_at"]
 
 
 def lib():
@@ -295,6 +304,9 @@ def lib():
         trd = [ip, ip, ip, ip, C.c_int, ip, C.c_int, C.c_double, dp, ip, dp, dp, dp, C.POINTER(BnmfTradeoffInfo)]
         L.bnmf_tradeoff.argtypes = [C.c_void_p, C.c_int] + trd
         L.bnmf_tradeoff_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + trd
+        prn = [ip, ip, C.c_int, C.c_double, dp, dp, dp, dp, dp, C.POINTER(BnmfPruneInfo)]
+        L.bnmf_prune.argtypes = [C.c_void_p, C.c_int] + prn
+        L.bnmf_prune_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + prn
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -1026,6 +1038,37 @@ class Engine:
     def tradeoff_at(self, end_iter, n_samples, **kw):
         """tradeoff over the n_samples iterations that end at end_iter (bnmf_tradeoff_at)."""
         return self.tradeoff(n_samples, end_iter=end_iter, **kw)
+
+    def prune(self, last_n, include=None, n_steps=20, max_loss=0.01, used=None, end_iter=None, exposures=False):
+        """Sparse per-tumour assignment with refit over the recorded samples flagged in used (length last_n, oldest first; None = all) of
+        the last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_prune / bnmf_prune_at), on the device:
+        per sample and included tumour (include: length G of 0 / 1, None = all) backward elimination of the sample's signatures from its
+        own exposures, with n_steps KL steps of refit after every removal, while the cosine stays within max_loss of the full refit's.
+        Returns the info fields, load (4 x N x G) with its rows also by name (PRN_LOAD_ROWS: mean and variance of the sparse exposure,
+        mean share, the probability that the tumour keeps the signature), tumour (7 x G, PRN_TUMOUR_ROWS; not spread by name), series
+        (2 x S, PRN_SERIES_ROWS), signature (3 x N, PRN_SIGNATURE_ROWS) and with exposures also exposures (S x N x G: every used
+        sample's sparse exposures).  NaN for an all-zero or left-out tumour.  n_steps and max_loss are reporting conventions, not
+        tests; rel_change tells whether n_steps sufficed."""
+        G, N = self.G, self.N
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"prune: include has shape {inc.shape}, G = {G} flags are needed")
+        u, S = self._used("prune", used, last_n)
+        ld, tum, series, sig = np.empty((4, N * G)), np.empty((7, G)), np.empty((2, S)), np.empty((3, N))
+        ex = np.empty((S, N * G)) if exposures else None
+        info = BnmfPruneInfo()
+        self._range_call("prune", last_n, end_iter, u, None if inc is None else inc.ctypes.data_as(_IP), int(n_steps), float(max_loss), _dp(ld), _dp(tum),
+                         _dp(series), _dp(sig), _dp(ex), C.byref(info))
+        out = self._info(info)
+        out.update(load=np.stack([row.reshape((N, G), order="F") for row in ld]), tumour=tum, series=series, signature=sig)
+        out.update({name: out["load"][i] for i, name in enumerate(PRN_LOAD_ROWS)})
+        if exposures:
+            out["exposures"] = np.stack([row.reshape((N, G), order="F") for row in ex]) if S else np.empty((0, N, G))
+        return out
+
+    def prune_at(self, end_iter, n_samples, **kw):
+        """prune over the n_samples iterations that end at end_iter (bnmf_prune_at)."""
+        return self.prune(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

@@ -1278,6 +1278,48 @@ class bayesNMF_sampler:
                  f"{(sp // N, sp % N) if sp >= 0 else None} with mean correlation {r['strongest_pair']:.3g}", verbosity=1)
         return out
 
+    def get_sparse_assignment(self, max_loss=0.01, n_steps=20, include=None, end_iter=None, n_samples=None, exposures=False, idx="MAP_idx"):
+        """Which signatures does each tumour keep, and how large are they once the others are gone?  On the device (bnmf_prune_at; not
+        in the reference): over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to `idx` (as
+        get_contrast), per sample and tumour backward elimination of the sample's signatures with a refit of the remaining exposures
+        after every removal (n_steps KL steps), while the cosine of the fit stays within max_loss of the full refit's: the refit that
+        get_reconstruction's drop leaves out.  Over the samples this gives the probability p_kept that a tumour keeps a signature.
+        include as in get_similarity.  max_loss = 0.01 and n_steps = 20 are reporting conventions like min_cosine = 0.9, not tests;
+        rel_change tells whether n_steps sufficed.  Returns dict(assignment (a data frame: tumour, signature, load, p_kept for every
+        pair with p_kept >= 0.5), tumours (a data frame: tumour, cos_0, cos_f, n_kept, n_kept_min, n_kept_max, rel_change, mean_trials,
+        included), load, tumour, series, signature, exposures (the arrays of the call) and its info fields)."""
+        if not hasattr(self._chain, "prune"):
+            raise ValueError("get_sparse_assignment needs an engine that refits its recorded samples (prune); this engine_factory's cannot")
+        G, N = self.dims["G"], self.dims["N"]
+        if not np.isfinite(max_loss):
+            raise ValueError(f"max_loss = {max_loss} is not a finite number")
+        if int(n_steps) != n_steps or n_steps < 1:
+            raise ValueError(f"n_steps = {n_steps} is not a whole number >= 1")
+        names = self.tumour_names if getattr(self, "tumour_names", None) else None
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        r = self._chain.prune(n, include=inc, n_steps=int(n_steps), max_loss=float(max_loss), used=used, exposures=bool(exposures), **kw)
+        label = (lambda g: names[g]) if names is not None else (lambda g: int(g))
+        load, tum = np.asarray(r["load"]).reshape(4, N, G), np.asarray(r["tumour"]).reshape(7, G)
+        included = np.ones(G, dtype=bool) if inc is None else inc.astype(bool)
+        out = dict(r)
+        out.update(assignment=pd.DataFrame([(label(g), nn, load[0, nn, g], load[3, nn, g]) for g in range(G) for nn in range(N) if load[3, nn, g] >= 0.5],
+                                           columns=["tumour", "signature", "load", "p_kept"]),
+                   tumours=pd.DataFrame(dict(tumour=[label(g) for g in range(G)], cos_0=tum[0], cos_f=tum[1], n_kept=tum[2], n_kept_min=tum[3], n_kept_max=tum[4],
+                                             rel_change=tum[5], mean_trials=tum[6], included=included)))
+        self.log(f"Sparse assignment: {r['n_included']} tumours ({r['n_undefined']} all-zero) over {r['n_used']} samples, max_loss {r['max_loss']:g}, "
+                 f"{r['n_steps']} steps; {len(out['assignment'])} (tumour, signature) pairs kept with p >= 0.5; {r['n_single']} tumours with one signature; "
+                 f"{r['trials']} trials; largest last-step change {r['max_change']:.3g}", verbosity=1)
+        return out
+
     def _mean_share_profiles(self, n, used, perm, kw):
         """N x G: the mean over the used, matched samples of the range of every tumour's aligned share profile (the host's start of
         get_subtypes; a sample in which a tumour has no exposure does not enter its mean)."""
@@ -1300,7 +1342,7 @@ class bayesNMF_sampler:
         return tot / np.where(cnt > 0, cnt, 1.0)
 
     def _recorded_range(self, end_iter, n_samples, idx, want_mode=False):
-        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes / get_residuals / get_tradeoff: (n, used flags or None, mode of A over the range as 0 / 1 flags of
+        """The range and sample selection of get_WAIC / get_mixing / get_PPC / get_attribution / get_projection / get_decomposition / get_contrast / get_regression / get_coactivity / get_stability / get_reconstruction / get_similarity / get_subtypes / get_residuals / get_tradeoff / get_sparse_assignment: (n, used flags or None, mode of A over the range as 0 / 1 flags of
         the N factors if want_mode, end_iter keyword of the engine call)."""
         cc = self.specs["convergence_control"]
         it = self.state["iter"]

@@ -588,6 +588,7 @@ int bnmf_stability_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* 
  *   drop_n = A_s[n] != 0 ? cos - cos_-n        : +0.0             its drop is exactly +0.0
  * The remaining exposures are NOT refitted after the removal.  The cosine does not depend on the scale of the fit, so no rescaling is
  * needed, but a refit could recover part of the loss: drop_n is an upper bound of what removing signature n costs the tumour.
+ * (bnmf_prune below removes with a refit after every removal.)
  * Over s ascending every running mean and variance is bnmf_attribution's Welford (d = a - mu; mu = mu + d * (1 / s); M2 = M2 + d * (a - mu)),
  * the rest are plain counts:
  * tumour [BNMF_REC_NTUM][G]: 0 the mean of cos, 1 its variance M2 / (S - 1), 2 the smallest cos over the samples (from +inf, v < d ? v : d),
@@ -899,6 +900,76 @@ int bnmf_tradeoff(bnmf_handle*, int last_n, const int32_t* used,
 int bnmf_tradeoff_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm, const int32_t* sets, int C,
                      const int32_t* query, int Q, double min_corr, double* tumour, int32_t* pair_at, double* pair, double* dense, double* setstat,
                      bnmf_tradeoff_info* info);
+
+/* Sparse per-tumour assignment with refit over recorded samples, on the device: which signatures does a tumour keep, and how
+ * large are they once the others are gone?  Backward elimination with a KL refit of the remaining exposures after every removal, until the
+ * fit's cosine would fall by more than max_loss: the refit that bnmf_reconstruction's drop_n leaves out, and the table signature-assignment
+ * tools report.  Done for every recorded sample it also gives the probability that a tumour keeps a signature.  The members are the m
+ * included tumours g_0 < g_1 < ... (include[g] != 0; NULL = all).  The samples are the recorded ones flagged in used[] (oldest first;
+ * NULL = all), numbered s = 1 .. S.
+ * Only + - * /, sqrt, |.|, comparisons and whole numbers, no contraction, every sum in the order given here.  Per used sample s and member
+ * g, with m_k the data cell as a double:
+ *   set-up    cs[n] = bnmf_map's column sum of P_s[, n].  Factor n takes part iff A_s[n] != 0 and cs[n] > 0.  The places i = 0 .. N_in-1
+ *             are the factors that take part, ascending (bnmf_project's idx), and x[k,i] = P_s[k,idx[i]] / cs[idx[i]].
+ *             t = sum_k m_k, mm = sum_k m_k m_k, k ascending from +0.0.
+ *             Warm start: e_i = E_s[idx[i], g] * cs[idx[i]], the sample's own renormalised exposure (bnmf_contrast's x, the same bits).
+ *   step      with an active flag per place (a place that is not active holds e_i = +0.0):  every g_i = +0.0;  for k ascending:
+ *             c = sum_i x[k,i] * e_i (i ascending over all places from +0.0; an inactive place adds +0.0), q = c > 0 ? m_k / c : 0.0,
+ *             g_i = g_i + x[k,i] * q;  then e_i = active_i ? e_i * g_i : +0.0 and d = max_i |e_i(new) - e_i(old)| (from +0.0,
+ *             v > d ? v : d).  This is bnmf_project's step with the flags.
+ *   cosine    of a state: c_k as above, dot = sum_k m_k c_k, cc = sum_k c_k c_k (k ascending from +0.0);
+ *             cos = mm > 0 ? (cc > 0 ? dot / sqrt(mm * cc) : +0.0) : NaN   (bnmf_reconstruction's cosv)
+ *   round 0   every place active; n_steps steps from the warm start give the state and cos_0.
+ *   rounds    while more than one place is active: order the active places by (e_i ascending, i ascending).  For each candidate i in that
+ *             order: copy the state, set e_i = +0.0, clear its flag, run n_steps steps, cos_t = the cosine; every trial is counted.  The
+ *             first candidate with cos_t >= cos_0 - max_loss (the difference formed once; a comparison with NaN is false) becomes the
+ *             state and the next round starts.  If no candidate of a round passes, the elimination stops.
+ *   A tumour with mm == 0 is undefined: no trials, NaN outputs, counted in info.
+ *   Per (s, g): e_sparse[n] by factor number, exactly +0.0 for a removed or non-participating factor; cos_0; cos_f, the cosine of the last
+ *   accepted state; n_kept, the places still active; trials; change = t > 0 ? d / t : 0.0 with d of the last step of the last accepted
+ *   state (how a user judges n_steps).
+ * Over s ascending, bnmf_attribution's Welford (d = a - mu; mu = mu + d * (1 / s); M2 = M2 + d * (a - mu)) and plain counts:
+ * load [BNMF_PRN_NLOAD][N*G] (n + N g): 0 the mean of e_sparse; 1 its variance M2 / (S - 1) (NaN by IEEE for S = 1); 2 the mean share
+ *   (sum_s e_n * u) / S with u = 1 / sum_n e_n (n ascending from +0.0; 0.0 where the sum is not positive), bnmf_attribution's share rule;
+ *   3 p_kept = #(e_n > 0) / S.  NaN for an undefined or left-out tumour.
+ * tumour [BNMF_PRN_NTUM][G]: 0 the mean cos_0 and 1 the mean cos_f (Welford's mu); 2 the mean n_kept (the whole-number sum / S); 3 the
+ *   smallest and 4 the largest n_kept; 5 the largest change; 6 the mean trials (sum / S).  NaN for an undefined or left-out tumour.
+ * series [BNMF_PRN_NSER][S]: per used sample 0 the mean n_kept and 1 the mean cos_f over the defined members: the canonical W = 1024 sum
+ *   over the member positions (an undefined member entered as +0.0; bnmf_reconstruction's series order), divided by the number of defined
+ *   members (NaN without one).
+ * signature [BNMF_PRN_NSIG][N], over the defined members ascending: 0 the number with p_kept >= 0.5; 1 the mean p_kept and 2 the sum of
+ *   the mean loads (row 0 of load), both the canonical W = 64 sum, row 1 divided by their number (NaN without one).
+ * exposures [S][N*G]: every used sample's e_sparse, laid out as E (n + N g), as bnmf_project's exposures; NaN for an undefined or
+ *   left-out tumour.
+ * info (sizeof = 48): n_used = S, n_included = m, n_undefined, n_single = the defined members whose largest n_kept is 1, n_steps and
+ *   max_loss as given, trials = all trials of the call, max_change = the largest change of any defined member (from +0.0).
+ * n_steps = 20 and max_loss = 0.01 are the defaults of the Python and R layers: reporting conventions like min_cosine = 0.9, not tests.
+ * The bits depend on the samples, used[], include[], the data, n_steps and max_loss only: not on a tumour's place, the batch of samples
+ * that passes through the scratch (at most 256 MB; BNMF_PRN_BATCH overrides the batch for tests), the tiling or the form of the kernel
+ * (BNMF_PRN_FORM = 1 asks for the form with the lane's vectors in the LDS at any N).  A tumour's own values involve no other tumour and
+ * every sum over tumours runs over the member list, so include[] gives the bits of a cohort without the tumours left out.  Reads only the
+ * P, E and A rings and the data; draws no random number, consumes none of the chain's streams and is read-only for the chain.
+ * bnmf_prune_at: the n_samples iterations that end at end_iter; the range rule, used[], BNMF_ESIZE and BNMF_ESTATE as for bnmf_project_at;
+ * bnmf_prune(h, n, ...) is bnmf_prune_at(h, iter, n, ...).  Every output array may be NULL.  Refused before any device work: a null info
+ * (BNMF_EINVAL); the Normal likelihood (BNMF_EMODEL: the KL update needs counts); a used[] or include[] value other than 0 / 1 (the index
+ * named), n_steps outside 1 .. 100000, a max_loss that is not finite (BNMF_EINVAL); no used sample, no included tumour,
+ * N > BNMF_PRN_MAX_N (BNMF_ESIZE); window = 0, a poisoned handle or nothing recorded (BNMF_ESTATE). */
+#define BNMF_PRN_NLOAD 4         /* load rows: mean sparse exposure, its variance, mean share, p_kept */
+#define BNMF_PRN_NTUM  7         /* tumour rows: mean cos_0, mean cos_f, mean / smallest / largest n_kept, largest change, mean trials */
+#define BNMF_PRN_NSER  2         /* series rows: mean n_kept, mean cos_f */
+#define BNMF_PRN_NSIG  3         /* signature rows: tumours with p_kept >= 0.5, mean p_kept, sum of the mean loads */
+#define BNMF_PRN_MAX_N 128       /* the most factors */
+typedef struct { int32_t n_used, n_included, n_undefined, n_single, n_steps, _pad; int64_t trials; double max_change, max_loss; } bnmf_prune_info;
+int bnmf_prune(bnmf_handle*, int last_n, const int32_t* used,
+               const int32_t* include /* [G] 0 / 1, NULL = all */, int n_steps, double max_loss,
+               double* load      /* [BNMF_PRN_NLOAD][N*G]; may be NULL */,
+               double* tumour    /* [BNMF_PRN_NTUM][G]; may be NULL */,
+               double* series    /* [BNMF_PRN_NSER][S]; may be NULL */,
+               double* signature /* [BNMF_PRN_NSIG][N]; may be NULL */,
+               double* exposures /* [S][N*G]; may be NULL */,
+               bnmf_prune_info* info);
+int bnmf_prune_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_loss, double* load,
+                  double* tumour, double* series, double* signature, double* exposures, bnmf_prune_info* info);
 
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes

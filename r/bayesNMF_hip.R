@@ -673,6 +673,52 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       r$n_included, r$n_matched, r$n_unmatched, r$n_traded, r$min_corr, r$mean_ratio))
       out
     },
+    # Sparse per-tumour assignment with refit, on the device (bnmf_prune_at; not in the reference): which signatures does each tumour keep,
+    # and how large are they once the others are gone?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC),
+    # restricted to idx, per sample and tumour backward elimination of the sample's signatures with a refit of the remaining exposures
+    # after every removal (n_steps KL steps), while the cosine of the fit stays within max_loss of the full refit's: the refit that
+    # get_reconstruction's drop leaves out.  max_loss = 0.01 and n_steps = 20 are reporting conventions like min_cosine = 0.9, not tests;
+    # rel_change tells whether n_steps sufficed.  include: a logical of G flags (NULL = all).  list(assignment (a data frame: tumour,
+    # signature (1-based), load, p_kept for every pair with p_kept >= 0.5), tumours (a data frame), load (a list of N x G matrices:
+    # load_mean, load_var, share, p_kept), series (S x 2), signature (N x 3), exposures (N x G x S, with exposures = TRUE) and the info
+    # fields).  NA for an all-zero or left-out tumour.
+    get_sparse_assignment = function(max_loss = 0.01, n_steps = 20L, include = NULL, end_iter = self$state$iter,
+                                     n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), exposures = FALSE, idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      G <- self$dims$G; N <- self$dims$N
+      if (!is.finite(max_loss)) stop("max_loss must be a finite number")
+      if (n_steps < 1 || n_steps != as.integer(n_steps)) stop("n_steps must be a whole number >= 1")
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      member <- if (is.null(include)) rep(TRUE, G) else include
+      names <- colnames(self$data)
+      label <- function(g) if (is.null(names)) g else names[g]
+      r <- .Call("C_bnmf_prune", self$handle, as.integer(end_iter), as.integer(n_samples), used, include,
+                 as.double(c(n_steps, max_loss, if (exposures) 1 else 0, G, N)))
+      out <- r[c("n_used", "n_included", "n_undefined", "n_single", "n_steps", "trials", "max_change", "max_loss", "series", "signature")]
+      rows <- c("load_mean", "load_var", "share", "p_kept")
+      out$load <- setNames(lapply(seq_along(rows), function(k) matrix(r$load[, k], N, G)), rows)
+      kept <- which(!is.na(out$load$p_kept) & out$load$p_kept >= 0.5, arr.ind = TRUE)
+      kept <- kept[order(kept[, 2], kept[, 1]), , drop = FALSE]
+      out$assignment <- data.frame(tumour = label(kept[, 2]), signature = kept[, 1], load = out$load$load_mean[kept], p_kept = out$load$p_kept[kept])
+      out$tumours <- data.frame(tumour = label(seq_len(G)), cos_0 = r$tumour[, 1], cos_f = r$tumour[, 2], n_kept = r$tumour[, 3], n_kept_min = r$tumour[, 4],
+                                n_kept_max = r$tumour[, 5], rel_change = r$tumour[, 6], mean_trials = r$tumour[, 7], included = member)
+      if (exposures) out$exposures <- array(r$exposures, c(N, G, r$n_used))
+      message(sprintf("Sparse assignment: %d tumours (%d all-zero) over %d samples, max_loss %g, %d steps; %d pairs kept with p >= 0.5; largest last-step change %.3g",
+                      r$n_included, r$n_undefined, r$n_used, r$max_loss, r$n_steps, nrow(out$assignment), r$max_change))
+      out
+    },
     # Co-activity of the signatures, on the device (bnmf_coactivity_at; not in the reference): do two signatures act in the same tumours
     # or exclude each other, and is a signature split into two factors (a high cosine of two columns of P whose exposures are
     # negatively correlated)?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, every

@@ -1035,6 +1035,67 @@ SEXP C_bnmf_tradeoff_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP
   UNPROTECT(1);
   return out;
 }
+/* Sparse per-tumour assignment with refit on the device (bnmf_prune / bnmf_prune_at): C_bnmf_prune(ptr, end_iter (integer, or NULL = the
+ * current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or NULL = all), opts (real
+ * c(n_steps, max_loss, want_exposures 0 / 1, G, N))) -> list(n_used, n_included, n_undefined, n_single, n_steps, trials, max_change,
+ * max_loss, load (N G x 4: mean sparse exposure, its variance, mean share, p_kept - each laid out as E), tumour (G x 7: mean cos_0, mean
+ * cos_f, mean / smallest / largest n_kept, largest change, mean trials), series (S x 2: mean n_kept, mean cos_f per used sample), signature
+ * (N x 3: tumours with p_kept >= 0.5, mean p_kept, sum of the mean loads), exposures (N G x S, or NULL)) over iterations
+ * end_iter - n_samples + 1 ... end_iter.  C_bnmf_prune_at: the same with end_iter required */
+typedef struct { int32_t *u, *inc; int n_steps; double max_loss; } prn_in;
+static SEXP prn_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP opts, prn_in* in) {
+  const int n = INTEGER(n_samples)[0];
+  if (XLENGTH(opts) != 5) Rf_error("bnmf: opts has %ld entries, c(n_steps, max_loss, want_exposures, G, N) is needed", (long)XLENGTH(opts));
+  const double* o = REAL(opts);
+  const int G = (int)o[3], N = (int)o[4];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  in->u = lgl_flags(used, n);
+  in->inc = lgl_flags(include, G);
+  in->n_steps = (int)o[0]; in->max_loss = o[1];
+  int S = n < 0 ? 0 : n;
+  if (in->u) { S = 0; for (int i = 0; i < n; ++i) S += in->u[i]; }
+  static const char* nms[] = {"n_used", "n_included", "n_undefined", "n_single", "n_steps", "trials", "max_change", "max_loss", "load", "tumour", "series",
+                              "signature", "exposures"};
+  SEXP out = PROTECT(named_list(13, nms));
+  SET_VECTOR_ELT(out, 8, Rf_allocMatrix(REALSXP, N * G, BNMF_PRN_NLOAD));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, G, BNMF_PRN_NTUM));
+  SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, S, BNMF_PRN_NSER));
+  SET_VECTOR_ELT(out, 11, Rf_allocMatrix(REALSXP, N, BNMF_PRN_NSIG));
+  if (o[2] != 0.0) SET_VECTOR_ELT(out, 12, Rf_allocMatrix(REALSXP, N * G, S));
+  UNPROTECT(1);
+  return out;
+}
+static void prn_finish(SEXP out, const bnmf_prune_info* info) {
+  const int32_t v[5] = {info->n_used, info->n_included, info->n_undefined, info->n_single, info->n_steps};
+  for (int i = 0; i < 5; ++i) SET_VECTOR_ELT(out, i, Rf_ScalarInteger(v[i]));
+  SET_VECTOR_ELT(out, 5, Rf_ScalarReal((double)info->trials)); SET_VECTOR_ELT(out, 6, Rf_ScalarReal(info->max_change));
+  SET_VECTOR_ELT(out, 7, Rf_ScalarReal(info->max_loss));
+}
+SEXP C_bnmf_prune(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP opts) {
+  prn_in in;
+  SEXP out = PROTECT(prn_alloc(n_samples, used, include, opts, &in));
+  bnmf_prune_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_prune(get_handle(ptr), INTEGER(n_samples)[0], in.u, in.inc, in.n_steps, in.max_loss, map_buf(out, 8), map_buf(out, 9), map_buf(out, 10), map_buf(out, 11),
+                   map_buf(out, 12), &info));
+  else
+    chk(bnmf_prune_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.n_steps, in.max_loss, map_buf(out, 8), map_buf(out, 9),
+                      map_buf(out, 10), map_buf(out, 11), map_buf(out, 12), &info));
+  prn_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_prune_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP opts) {
+  prn_in in;
+  SEXP out = PROTECT(prn_alloc(n_samples, used, include, opts, &in));
+  bnmf_prune_info info;
+  chk(bnmf_prune_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.n_steps, in.max_loss, map_buf(out, 8), map_buf(out, 9),
+                    map_buf(out, 10), map_buf(out, 11), map_buf(out, 12), &info));
+  prn_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Silhouette stability of the recorded signatures on the device (bnmf_stability / bnmf_stability_at): C_bnmf_stability(ptr, end_iter
  * (integer, or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), labels (integer n_samples x N
  * matrix of 0-based clusters, -1 / NA = left out; or NULL = the factor), extra_P (K x X real matrix, or NULL), extra_label (integer X,
@@ -1406,6 +1467,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_subtypes", (DL_FUNC)&C_bnmf_subtypes, 9}, {"C_bnmf_subtypes_at", (DL_FUNC)&C_bnmf_subtypes_at, 9},
   {"C_bnmf_residuals", (DL_FUNC)&C_bnmf_residuals, 6}, {"C_bnmf_residuals_at", (DL_FUNC)&C_bnmf_residuals_at, 6},
   {"C_bnmf_tradeoff", (DL_FUNC)&C_bnmf_tradeoff, 9}, {"C_bnmf_tradeoff_at", (DL_FUNC)&C_bnmf_tradeoff_at, 9},
+  {"C_bnmf_prune", (DL_FUNC)&C_bnmf_prune, 6}, {"C_bnmf_prune_at", (DL_FUNC)&C_bnmf_prune_at, 6},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
