@@ -48,6 +48,7 @@
 #include "residuals.h"
 #include "tradeoff.h"
 #include "prune.h"
+#include "summary.h"
 
 using namespace bnmf;
 

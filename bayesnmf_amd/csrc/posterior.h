@@ -1,6 +1,6 @@
 // bayesnmf_amd/csrc/posterior.h — the posterior calls on a recorded range of samples: bnmf_map, bnmf_waic, bnmf_ppc, bnmf_attribution,
-// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals, bnmf_tradeoff, bnmf_prune (each with its _at form) and bnmf_label_switching.  Host code only: the
-// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h, residuals.h, tradeoff.h and prune.h.  Included by api.hip (one translation unit) behind sweep.h.
+// bnmf_mixing, bnmf_assign, bnmf_relabel, bnmf_project, bnmf_decompose, bnmf_contrast, bnmf_regress, bnmf_coactivity, bnmf_stability, bnmf_reconstruction, bnmf_similarity, bnmf_subtypes, bnmf_residuals, bnmf_tradeoff, bnmf_prune, bnmf_summary (each with its _at form) and bnmf_label_switching.  Host code only: the
+// kernels are in kernels.h, waic.h, ppc.h, attribution.h, mixing.h, relabel.h, project.h, decompose.h, contrast.h, regress.h, coactivity.h, stability.h, reconstruction.h, similarity.h, subtypes.h, residuals.h, tradeoff.h, prune.h and summary.h.  Included by api.hip (one translation unit) behind sweep.h.
 // The first part is the layer the calls share: the range and its slot list, the quiesce, the handle's one scratch buffer
 // and its carver, the reference catalogue, the dynamic-LDS opt-in.  A call supplies its own checks, its carve list, its launches and
 // its host reduction.
@@ -1997,6 +1997,131 @@ static int prune_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* us
   return 0;
 }
 
+// Cohort summary of signatures over the samples of r that used[] flags (summary.h): the member list, the aligned samples
+// and their perm rows are made here; k_map_colsum runs once over the aligned samples; then per batch of samples (u is Sb m doubles and the
+// general form's sorted chunks 2 Sb N nchunk chunk: the batch keeps the scratch under SUM_SCRATCH_CAP) k_sum_total, k_sum_scalar,
+// k_sum_tail and the order statistics (k_sum_rank, or k_sum_sort + k_sum_select through sorted chunks) leave every value of the series;
+// the statistics over the samples are summary_reduce's.
+static_assert(SM_NSCAL == BNMF_SUM_NSCAL && SM_MAX_Q == BNMF_SUM_MAX_Q && SM_MAX_CHUNK == CO_MAX_CHUNK, "summary.h, coactivity.h and bnmf.h disagree");
+static constexpr size_t SUM_SCRATCH_CAP = (size_t)256 << 20;    // bytes of u, sorted chunks and block partials per batch
+static int summary_impl(bnmf_handle* h, const char* fn, Range r, const int32_t* used, const int32_t* include, const int32_t* perm, double min_load,
+                        const double* probs, int L, double ci, double* stat, double* series, bnmf_summary_info* info) {
+  if (int rc = range_enter(h, fn, h && info && probs, r)) return rc;
+  const int K = h->cfg.K, N = h->cfg.N, G = h->cfg.G;
+  std::vector<int> slots;
+  if (int rc = range_slots(h, fn, r, used, true, slots)) return rc;
+  std::vector<int> members;
+  for (int g = 0; g < G; ++g) {
+    if (include && include[g] != 0 && include[g] != 1) return fail(BNMF_EINVAL, "%s: include[%d] = %d is neither 0 nor 1", fn, g, (int)include[g]);
+    if (!include || include[g]) members.push_back(g);
+  }
+  const int m = (int)members.size();
+  // the aligned samples: rows[] is the row of the range of every used sample, place[] its row among the aligned ones (-1: left out)
+  std::vector<int> rows, aslots, hperm, place;
+  for (int s = 0; s < r.n; ++s) if (!used || used[s]) rows.push_back(s);
+  const int S = (int)slots.size();
+  for (int s = 0; s < S; ++s) {
+    const int32_t* pr = perm ? perm + (size_t)rows[s] * N : nullptr;
+    bool none = pr != nullptr;
+    for (int n = 0; pr && n < N; ++n) none = none && pr[n] == -1;
+    if (none) { place.push_back(-1); continue; }
+    if (pr) {
+      std::vector<char> seen(N, 0);
+      for (int n = 0; n < N; ++n) {
+        if (pr[n] < 0 || pr[n] >= N || seen[pr[n]])
+          return fail(BNMF_EINVAL, "%s: perm[%d] is neither a permutation of 0..%d nor -1 throughout (sample %d of the range, factor %d: %d)", fn, rows[s], N - 1,
+                      rows[s], n, (int)pr[n]);
+        seen[pr[n]] = 1;
+      }
+    }
+    place.push_back((int)aslots.size());
+    aslots.push_back(slots[s]);
+    for (int n = 0; n < N; ++n) hperm.push_back(pr ? pr[n] : n);
+  }
+  const int Sa = (int)aslots.size();
+  if (!(min_load >= 0.0) || std::isinf(min_load)) return fail(BNMF_EINVAL, "%s: min_load = %g is not a finite number >= 0", fn, min_load);
+  if (L < 1 || L > BNMF_SUM_MAX_Q) return fail(BNMF_EINVAL, "%s: L = %d levels, 1..%d are possible", fn, L, BNMF_SUM_MAX_Q);
+  for (int l = 0; l < L; ++l) {
+    if (!(probs[l] >= 0.0 && probs[l] <= 1.0)) return fail(BNMF_EINVAL, "%s: probs[%d] = %g is outside [0, 1]", fn, l, probs[l]);
+    if (l > 0 && !(probs[l] > probs[l - 1])) return fail(BNMF_EINVAL, "%s: probs[%d] = %g is not above probs[%d] = %g", fn, l, probs[l], l - 1, probs[l - 1]);
+  }
+  if (!(ci < 1.0)) return fail(BNMF_EINVAL, "%s: credible_interval = %g must be below 1", fn, ci);
+  if (S < 2) return fail(BNMF_ESIZE, "%s: %d used sample%s, the variance over the samples needs at least 2", fn, S, S == 1 ? "" : "s");
+  if (Sa < 2) return fail(BNMF_ESIZE, "%s: %d aligned sample%s of %d used, the variance over the samples needs at least 2", fn, Sa, Sa == 1 ? "" : "s", S);
+  if (m < 1) return fail(BNMF_ESIZE, "%s: no included tumour", fn);
+  if (m > BNMF_COA_MAX_M) return fail(BNMF_ESIZE, "%s: %d included tumours, at most %d are taken", fn, m, BNMF_COA_MAX_M);
+  if (!h->arr[BNMF_P].ring || !h->arr[BNMF_E].ring || !h->arr[BNMF_A].ring) return fail(BNMF_ESTATE, "%s: nothing recorded yet", fn);
+  if (int rc = post_sync(h)) return rc;
+  auto env_int = [](const char* name, long long dflt) { const char* e = getenv(name); const long long v = e ? atoll(e) : 0; return v >= 1 ? v : dflt; };
+  int chunk = SM_MIN_CHUNK;                                                                                // a power of two in 64 .. 16,384
+  { const long long want = std::min<long long>(env_int("BNMF_SUM_CHUNK", SM_MAX_CHUNK), SM_MAX_CHUNK); while ((long long)chunk * 2 <= want) chunk *= 2; }   // tests: the general form at a small m
+  const int nchunk = (m + chunk - 1) / chunk;
+  const bool general = nchunk > 1;
+  int n2 = SM_MIN_CHUNK;                                                                                   // keys of the one-chunk form
+  while (n2 < m) n2 *= 2;
+  const int nb = (m + RG_BLOCK - 1) / RG_BLOCK, NSTAT = SM_NSCAL + 3 * L;
+  const size_t per = (size_t)m * 8 + (general ? 2 * (size_t)N * nchunk * chunk * 8 : 0) + (size_t)nb * N * 20 + 4 * 256;
+  const int Sb = (int)std::min<long long>({env_int("BNMF_SUM_BATCH", (long long)std::max<size_t>(1, SUM_SCRATCH_CAP / per)), (long long)Sa, 65535LL});   // tests: the batch
+  const size_t nser = (size_t)NSTAT * Sa * N;
+  SumArgs a{};
+  double *cs, *dprobs; int *dslots, *dmem, *dperm;
+  if (int rc = carve(h, [&](Carve& c) {
+        cs = c.take<double>((size_t)Sa * N); a.ser = c.take<double>(nser); a.u = c.take<double>((size_t)Sb * m);
+        a.part = c.take<double>((size_t)Sb * nb * N * 2); a.partC = c.take<int>((size_t)Sb * nb * N);
+        a.sorted = general ? c.take<double>(2 * (size_t)Sb * N * nchunk * chunk) : nullptr;
+        a.flag = c.take<int>((size_t)Sa * N); dprobs = c.take<double>(L);
+        dslots = c.take<int>(Sa); dmem = c.take<int>(m); dperm = c.take<int>((size_t)Sa * N);
+      })) return rc;
+  HIPCHK(hipMemcpyAsync(dslots, aslots.data(), (size_t)Sa * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dmem, members.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dperm, hperm.data(), (size_t)Sa * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dprobs, probs, (size_t)L * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (general) HIPCHK(hipMemsetAsync(a.flag, 0, (size_t)Sa * N * sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_map_colsum, dim3(Sa, N), dim3(64), 0, h->stream, (const double*)h->arr[BNMF_P].ring, (size_t)K * N, K, N, (const int*)dslots, cs);
+  a.ringE = h->arr[BNMF_E].ring; a.ringA = h->arr[BNMF_A].ring; a.cs = cs; a.slots = dslots; a.members = dmem; a.perm = dperm; a.probs = dprobs;
+  a.lenE = (size_t)N * G; a.N = N; a.S = Sa; a.Sb = Sb; a.m = m; a.nb = nb; a.chunk = chunk; a.nchunk = nchunk; a.L = L; a.min_load = min_load;
+  constexpr int T = 4;
+  const int nt = (N + T - 1) / T;
+  const size_t lds = (size_t)(general ? chunk : n2) * sizeof(double);
+  if (int rc = general ? opt_in_lds(k_sum_sort<SM_WIDTH>, lds, lds) : opt_in_lds(k_sum_rank<SM_WIDTH>, lds, lds)) return rc;   // (the workgroup vote keeps a static word of its own: ask for the keys only)
+  for (int s0 = 0; s0 < Sa; s0 += Sb) {
+    const int ns = std::min(Sb, Sa - s0);
+    a.s0 = s0;
+    hipLaunchKernelGGL(k_sum_total<256>, dim3((unsigned)((m + 255) / 256), ns), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(k_sum_scalar<T>, dim3(reg_units(nt, nb), ns), dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL(k_sum_tail<SM_NSCAL>, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, h->stream, a, ns);
+    if (!general) hipLaunchKernelGGL(k_sum_rank<SM_WIDTH>, dim3(N, ns), dim3(SM_WIDTH), lds, h->stream, a, n2);
+    else {
+      hipLaunchKernelGGL(k_sum_sort<SM_WIDTH>, dim3((unsigned)N * nchunk, ns, 2), dim3(SM_WIDTH), lds, h->stream, a);
+      hipLaunchKernelGGL(k_sum_select<64>, dim3(N, ns), dim3(64), 0, h->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  std::vector<double> hs(nser);
+  std::vector<int> hf((size_t)Sa * N);
+  HIPCHK(hipMemcpyAsync(hs.data(), a.ser, nser * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(hf.data(), a.flag, hf.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the series of the whole used range: a sample that perm leaves out is NaN throughout
+  std::vector<double> full;
+  const double* ser = hs.data();
+  if (Sa < S) {
+    full.assign((size_t)NSTAT * S * N, std::nan(""));
+    for (int q = 0; q < NSTAT; ++q)
+      for (int s = 0; s < S; ++s)
+        if (place[s] >= 0) std::memcpy(full.data() + ((size_t)q * S + s) * N, hs.data() + ((size_t)q * Sa + place[s]) * N, (size_t)N * sizeof(double));
+    ser = full.data();
+  }
+  if (series) std::memcpy(series, ser, (size_t)NSTAT * S * N * sizeof(double));
+  if (stat) summary_reduce(ser, S, N, NSTAT, ci, stat);
+  int64_t nbad = 0;
+  for (int f : hf) nbad += f ? 1 : 0;
+  std::memset(info, 0, sizeof *info);
+  info->n_used = S; info->n_aligned = Sa; info->n_included = m; info->n_left_out = G - m; info->n_levels = L; info->n_blocks = nb; info->n_nonfinite = nbad;
+  info->min_load = min_load; info->credible_interval = ci;
+  return 0;
+}
+
 extern "C" {
 
 int bnmf_map(bnmf_handle* h, int last_n, double ci, double* P_mean, double* E_mean, double* A_mode, double* top_A,
@@ -2165,6 +2290,15 @@ int bnmf_prune(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* i
 int bnmf_prune_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_loss, double* load,
                   double* tumour, double* series, double* signature, double* exposures, bnmf_prune_info* info) {
   return prune_impl(h, "bnmf_prune_at", Range{true, end_iter, n_samples}, used, include, n_steps, max_loss, load, tumour, series, signature, exposures, info);
+}
+
+int bnmf_summary(bnmf_handle* h, int last_n, const int32_t* used, const int32_t* include, const int32_t* perm, double min_load, const double* probs, int L,
+                 double credible_interval, double* stat, double* series, bnmf_summary_info* info) {
+  return summary_impl(h, "bnmf_summary", Range{false, 0, last_n}, used, include, perm, min_load, probs, L, credible_interval, stat, series, info);
+}
+int bnmf_summary_at(bnmf_handle* h, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm, double min_load,
+                    const double* probs, int L, double credible_interval, double* stat, double* series, bnmf_summary_info* info) {
+  return summary_impl(h, "bnmf_summary_at", Range{true, end_iter, n_samples}, used, include, perm, min_load, probs, L, credible_interval, stat, series, info);
 }
 
 // plot_label_switching's per-sample hungarian_assignment(P_t, reference_P, keep_all_est = TRUE) diagonal (R/postprocessing_visualizations.R:

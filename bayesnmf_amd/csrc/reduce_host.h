@@ -1,11 +1,11 @@
 // bayesnmf_amd/csrc/reduce_host.h — the host reductions over the used samples that the posterior calls share: the canonical W = 64 sum,
 // the mean / variance / type-7 rows of a series, the dealing of independent series to threads, bnmf_coactivity's reduction
 // (DESIGN.md 21), bnmf_stability's finish, bnmf_reconstruction's, bnmf_similarity's,
-// bnmf_subtypes' (DESIGN.md 25), bnmf_residuals' (DESIGN.md 26), bnmf_tradeoff's and bnmf_prune's.  No device and no handle: posterior.h includes it, and a stand-alone host program can
+// bnmf_subtypes' (DESIGN.md 25), bnmf_residuals' (DESIGN.md 26), bnmf_tradeoff's, bnmf_prune's and bnmf_summary's.  No device and no handle: posterior.h includes it, and a stand-alone host program can
 // (tools/coactivity_reduce_check.cpp, tools/stability_reduce_check.cpp, tools/reconstruction_reduce_check.cpp,
-// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp, tools/residuals_reduce_check.cpp, tools/tradeoff_reduce_check.cpp and tools/prune_reduce_check.cpp, built with
+// tools/similarity_reduce_check.cpp, tools/subtypes_reduce_check.cpp, tools/residuals_reduce_check.cpp, tools/tradeoff_reduce_check.cpp, tools/prune_reduce_check.cpp and tools/summary_reduce_check.cpp, built with
 // -fsanitize=address,undefined by tests/test_coactivity_host.py, tests/test_stability_host.py, tests/test_reconstruction_host.py,
-// tests/test_similarity_host.py, tests/test_subtypes_host.py, tests/test_residuals_host.py, tests/test_tradeoff_host.py and tests/test_prune_host.py).  Compile with -ffp-contract=off, as the library is.
+// tests/test_similarity_host.py, tests/test_subtypes_host.py, tests/test_residuals_host.py, tests/test_tradeoff_host.py, tests/test_prune_host.py and tests/test_summary_host.py).  Compile with -ffp-contract=off, as the library is.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -505,4 +505,28 @@ struct res_lead { double trace, lambda, share, move; };
     signature[(size_t)N + n] = ndef > 0 ? con_canon64(tp.data(), (size_t)ndef, 1) / (double)ndef : nan;
     signature[2 * (size_t)N + n] = con_canon64(tl.data(), (size_t)ndef, 1);
   }
+}
+
+// ---- bnmf_summary's reduction over the samples ----
+// ser [nstat][S][N] -> stat [nstat][BNMF_SUM_NROW][N]: per (q, n) over the S' samples whose value is not NaN the rows of con_rows (the
+// variance NaN for S' < 2) and S'; every row NaN and S' = 0 without one.  Every (q, n) is a series of its own: dealt to threads.
+[[maybe_unused]] static void summary_reduce(const double* ser, int S, int N, int nstat, double ci, double* stat) {
+  const long nwork = (long)nstat * N;
+  auto work = [&](long lo, long hi) {
+    std::vector<double> x(S), tmp(S);
+    double row[4];
+    for (long i = lo; i < hi; ++i) {
+      const long q = i / N, n = i % N;
+      const double* v = ser + (size_t)q * S * N + n;
+      int nv = 0;
+      for (int s = 0; s < S; ++s) { const double d = v[(size_t)s * N]; if (!std::isnan(d)) x[nv++] = d; }
+      for (int k = 0; k < 4; ++k) row[k] = std::nan("");
+      if (nv) con_rows(x.data(), nv, ci, tmp.data(), row, 1);
+      if (nv < 2) row[1] = std::nan("");
+      double* o = stat + (size_t)q * BNMF_SUM_NROW * N + n;
+      for (int k = 0; k < 4; ++k) o[(size_t)k * N] = row[k];
+      o[4 * (size_t)N] = (double)nv;
+    }
+  };
+  deal_threads(nwork, work);
 }

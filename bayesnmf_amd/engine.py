@@ -157,6 +157,11 @@ class BnmfPruneInfo(C.Structure):
                 ("_pad", C.c_int32), ("trials", C.c_int64), ("max_change", C.c_double), ("max_loss", C.c_double)]
 
 
+class BnmfSummaryInfo(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_included", C.c_int32), ("n_left_out", C.c_int32), ("n_levels", C.c_int32),
+                ("n_blocks", C.c_int32), ("n_nonfinite", C.c_int64), ("min_load", C.c_double), ("credible_interval", C.c_double)]
+
+
 class BnmfRelabelInfo(C.Structure):
     _fields_ = [("n_used", C.c_int32), ("n_aligned", C.c_int32), ("n_unmatched", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32),
                 ("n_switched", C.c_int32), ("n_changed_last", C.c_int32), ("_pad", C.c_int32), ("mean_cosine", C.c_double),
@@ -199,6 +204,10 @@ PRN_LOAD_ROWS = ("load_mean", "load_var", "share", "p_kept")
 PRN_TUMOUR_ROWS = ("cos_0", "cos_f", "n_kept", "n_kept_min", "n_kept_max", "rel_change", "mean_trials")
 PRN_SERIES_ROWS = ("n_kept", "cos_f")
 PRN_SIGNATURE_ROWS = ("n_tumours", "mean_p_kept", "total_load")
+SUM_SCALARS = ("prevalence", "total", "fraction", "mean_present")
+SUM_FAMILIES = ("load_all", "load_present", "share_all")
+SUM_ROWS = ("mean", "var", "lower", "upper", "n_valid")
+SUM_MAX_Q = 8
 PPC_COL_ROWS = ["T1_obs_col", "T1_rep_col", "p_T1_col", "T2_obs_col", "T2_rep_col", "p_T2_col"]
 PPC_SERIES_ROWS = ["T1_obs", "T1_rep", "T2_obs", "T2_rep"]
 PPC_CELL_ROWS = ["mean_cell", "var_cell", "p_less_cell", "p_equal_cell"]
@@ -220,7 +229,7 @@ ABI_SYMBOLS = ["bnmf_create", "bnmf_create_f64", "bnmf_destroy", "bnmf_set_array
                "bnmf_coactivity", "bnmf_coactivity_at", "bnmf_stability", "bnmf_stability_at",
                "bnmf_reconstruction", "bnmf_reconstruction_at", "bnmf_similarity", "bnmf_similarity_at",
                "bnmf_subtypes", "bnmf_subtypes_at", "bnmf_residuals", "bnmf_residuals_at",
-               "bnmf_tradeoff", "bnmf_tradeoff_at", "bnmf_prune", "bnmf_prune_at"]
+               "bnmf_tradeoff", "bnmf_tradeoff_at", "bnmf_prune", "bnmf_prune_at", "bnmf_summary", "bnmf_summary_at"]
 
 
 def lib():
@@ -307,6 +316,9 @@ def lib():
         prn = [ip, ip, C.c_int, C.c_double, dp, dp, dp, dp, dp, C.POINTER(BnmfPruneInfo)]
         L.bnmf_prune.argtypes = [C.c_void_p, C.c_int] + prn
         L.bnmf_prune_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + prn
+        smy = [ip, ip, ip, C.c_double, dp, C.c_int, C.c_double, dp, dp, C.POINTER(BnmfSummaryInfo)]
+        L.bnmf_summary.argtypes = [C.c_void_p, C.c_int] + smy
+        L.bnmf_summary_at.argtypes = [C.c_void_p, C.c_int, C.c_int] + smy
         L.bnmf_relabel.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_relabel_at.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, dp, C.c_int, ip, dp, lp, dp, dp, dp, dp, C.POINTER(BnmfRelabelInfo)]
         L.bnmf_last_error.restype = C.c_char_p
@@ -1069,6 +1081,45 @@ class Engine:
     def prune_at(self, end_iter, n_samples, **kw):
         """prune over the n_samples iterations that end at end_iter (bnmf_prune_at)."""
         return self.prune(n_samples, end_iter=end_iter, **kw)
+
+    def summary(self, last_n, probs=(0.05, 0.25, 0.5, 0.75, 0.95), include=None, perm=None, min_load=1.0, credible_interval=0.95, used=None,
+                end_iter=None, series=False):
+        """Cohort summary of the signatures over the recorded samples flagged in used (length last_n, oldest first; None = all) of the
+        last `last_n`, or with end_iter of the `last_n` that end at iteration end_iter (bnmf_summary / bnmf_summary_at), on the device:
+        per used sample and factor the prevalence (the share of the included tumours with a load >= min_load), the total load, its
+        fraction of the cohort's, the mean load of the carriers, and at every level of probs (1 .. SUM_MAX_Q values in [0, 1],
+        ascending) the exact type-7 quantile of all loads, of the carriers' loads and of the shares.  include (length G of 0 / 1,
+        None = all): the tumours that enter.  perm (last_n x N over the whole range, relabel's; a row of -1 leaves the sample out; None
+        = identity): a value goes to the place of its label.  Returns the info fields, names (the 4 + 3 L statistics: SUM_SCALARS, then
+        per family of SUM_FAMILIES and level "family_level"), probs and stat (NSTAT x 5 x N: the rows SUM_ROWS over the samples whose
+        value is not NaN); with series also series (NSTAT x S x N).  credible_interval None or <= 0: no interval."""
+        N, G = self.N, self.G
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        L = int(pr.size)
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.int32)
+        if inc is not None and (inc.ndim != 1 or inc.size != G):
+            raise BnmfError(-2, f"summary: include has shape {inc.shape}, G = {G} flags are needed")
+        pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        if pm is not None and pm.shape != (last_n, N):
+            raise BnmfError(-2, f"summary: perm is {pm.shape}, not {(last_n, N)}")
+        u, S = self._used("summary", used, last_n)
+        Lb = min(max(L, 1), SUM_MAX_Q)                         # (an invalid L is refused by the library: the buffers only have to exist)
+        nstat = 4 + 3 * Lb
+        st = np.empty((nstat, 5, N))
+        ser = np.empty((nstat, S, N)) if series else None
+        ci = 0.0 if credible_interval is None else float(credible_interval)
+        info = BnmfSummaryInfo()
+        ipt = lambda v: None if v is None else v.ctypes.data_as(_IP)  # noqa: E731
+        self._range_call("summary", last_n, end_iter, u, ipt(inc), ipt(pm), float(min_load), _dp(pr), L, ci, _dp(st), _dp(ser), C.byref(info))
+        out = self._info(info)
+        out.update(stat=st, probs=pr.copy(), names=list(SUM_SCALARS) + [f"{fam}_{p:g}" for fam in SUM_FAMILIES for p in pr])
+        if series:
+            out["series"] = ser
+        return out
+
+    def summary_at(self, end_iter, n_samples, **kw):
+        """summary over the n_samples iterations that end at end_iter (bnmf_summary_at)."""
+        return self.summary(n_samples, end_iter=end_iter, **kw)
 
     def mixing(self, last_n, used=None, end_iter=None, keep=None, arrays=True):
         """Mixing diagnostics over the recorded samples flagged in used (length last_n, oldest first; None = all) of the last `last_n`,

@@ -3,8 +3,9 @@
 argument meaning, defaults, field names and error messages — driving the HIP engine through the C ABI
 (one call per block of <= MAP_every iterations instead of R-level work per iteration).
 
-Only the sampling path is mirrored.  Post-processing (reference assignment, plots, summary) is out of
-scope.  New optional trailing arguments: seed, chain_id, device, save_Z.
+The sampling path is mirrored, and of the post-processing the reference assignment
+(assign_signatures_ensemble), summary() and summarize_samplers() (R/postprocessing.R:18-152); the plots
+are out of scope.  New optional trailing arguments: seed, chain_id, device, save_Z.
 """
 import datetime
 import os
@@ -1320,6 +1321,104 @@ class bayesNMF_sampler:
                  f"{r['trials']} trials; largest last-step change {r['max_change']:.3g}", verbosity=1)
         return out
 
+    def get_summary(self, probs=(0.05, 0.25, 0.5, 0.75, 0.95), min_load=1.0, include=None, relabel=True, credible_interval=0.95, series=False,
+                    end_iter=None, n_samples=None, idx="MAP_idx"):
+        """How is a signature's load distributed across the cohort?  On the device (bnmf_summary_at; the reference's summary() reports
+        the carriers' median and the prevalence of the MAP point estimate alone): over iterations end_iter - n_samples + 1 ... end_iter
+        (defaults as get_WAIC), restricted to `idx` (as get_contrast), per sample and signature the prevalence (tumours with a load >=
+        min_load), the total load, its fraction of the cohort's, the carriers' mean and, at every level of probs, the exact quantile of
+        all loads (load_all_<p>), of the carriers' loads (load_present_<p>) and of the shares (share_all_<p>): each a posterior with an
+        interval.  With relabel the range is first aligned by get_relabelling() and its perm is handed on; an unmatched sample is left
+        out.  include as in get_similarity.  Returns a dict per statistic name of dict(mean, var, lower, upper, n_valid), each of
+        length N, plus names, probs, stat, the info fields and with series the series (NSTAT x S x N)."""
+        if not hasattr(self._chain, "summary"):
+            raise ValueError("get_summary needs an engine that sorts the loads of its recorded samples (summary); this engine_factory's cannot")
+        G, N = self.dims["G"], self.dims["N"]
+        inc = None
+        if include is not None:
+            vals = list(include.tolist()) if hasattr(include, "tolist") else list(include)
+            v = np.array([np.nan if x is None or x is pd.NA else float(x) for x in vals], dtype=np.float64)
+            if v.size != G:
+                raise ValueError(f"include has {v.size} values for {G} tumours")
+            if (~np.isnan(v) & (v != 0) & (v != 1)).any():
+                raise ValueError("include holds a value other than 0, 1 and None / NaN")
+            inc = (v == 1).astype(np.int32)
+        n, used, _, kw = self._recorded_range(end_iter, n_samples, idx)
+        perm = None
+        if relabel:
+            rows = np.asarray(self.get_relabelling(end_iter=end_iter, n_samples=n_samples, idx=idx)["perm"], dtype=np.int32)
+            perm = np.full((n, N), -1, dtype=np.int32)                   # perm has a row per used sample: scattered into the range's rows
+            perm[slice(None) if used is None else np.asarray(used) != 0] = rows
+        r = self._chain.summary(n, probs=probs, include=inc, perm=perm, min_load=float(min_load), credible_interval=credible_interval, used=used,
+                                series=bool(series), **kw)
+        st = np.asarray(r["stat"])
+        out = dict(r)
+        for q, name in enumerate(r["names"]):
+            out[name] = dict(mean=st[q, 0], var=st[q, 1], lower=st[q, 2], upper=st[q, 3], n_valid=st[q, 4])
+        self._summary_posterior = dict(out, min_load=float(min_load))
+        self.reference_comparison["summary"] = None                      # the frame gains the posterior columns: made again on demand
+        prev = out["prevalence"]["mean"]
+        self.log(f"Summary: {r['n_included']} tumours over {r['n_aligned']} of {r['n_used']} samples, {r['n_levels']} levels, min_load {r['min_load']:g}; "
+                 f"mean prevalence {np.nanmin(prev):.3g} .. {np.nanmax(prev):.3g}; {r['n_nonfinite']} (sample, signature) with a load that is not finite",
+                 verbosity=1)
+        return out
+
+    def summary(self, reference_P=None, reference_names=None):
+        """summary.bayesNMF_sampler (R/postprocessing.R:18-91): one row per signature of the MAP with G, N, K, Signature,
+        Med_Contribution (the median load among the tumours with a load >= 1) and Prop_atleast_1 (their share); with reference_P (K x R;
+        no catalogue is bundled, so "cosmic" is not a default) also Reference_Signature and Cosine_Similarity through
+        assign_signatures_ensemble.  Kept in self.reference_comparison["summary"] and returned from there until the reference changes.
+        After a get_summary() whose probs hold 0.5 and whose min_load is 1 the frame also has Med_Contribution_post, _lower, _upper,
+        Prop_atleast_1_post, _lower and _upper: the device's posterior of the same two quantities."""
+        K = self.dims["K"]
+        if isinstance(reference_P, str):
+            raise ValueError("Parameter `reference_P` must be a matrix or None: no catalogue is bundled")
+        ref = None if reference_P is None else np.asarray(reference_P, dtype=float)
+        if ref is not None and ref.shape[0] != K:
+            self.log(f"Reference matrix has {ref.shape[0]} rows, but data has {K} rows. Setting `reference_P` to NULL.", verbosity=1)
+            ref = None
+        rc = self.reference_comparison
+        if ref is not None:
+            same = rc.get("reference_P") is not None and np.array_equal(np.asarray(rc["reference_P"]), ref) and rc.get("assignments") is not None
+            if not same:                                                  # only reassigns signatures if the reference set has changed
+                self.assign_signatures_ensemble(ref, reference_names=reference_names)
+                rc["summary"] = None
+            asg = rc["assignments"]
+            sig_est, sig_ref, cos = list(asg["sig_est"]), list(asg["sig_ref"]), list(asg["MAP_cosine"])
+        else:
+            sig_est = list(range(1, np.asarray(self.MAP["P"]).shape[1] + 1))
+            sig_ref, cos = sig_est, None
+        if rc.get("summary") is not None and (("Reference_Signature" in rc["summary"].columns) == (ref is not None)):
+            return rc["summary"]
+        E = np.asarray(self.MAP["E"], dtype=float)
+        # the row of MAP["E"] of every summary row (MAP$sig_idx) and the factor it is among the chain's N (the place in get_summary's arrays)
+        if ref is not None:
+            rows_at, factor = np.asarray(self.MAP["sig_idx"], dtype=int), np.asarray(rc["keep_sigs"], dtype=int)
+        else:
+            rows_at = np.arange(len(sig_est))
+            ks = np.asarray(self.MAP.get("keep_sigs", rows_at), dtype=int)
+            factor = ks if len(ks) == len(rows_at) else rows_at
+        post = getattr(self, "_summary_posterior", None)
+        lvl = None
+        if post is not None and post["min_load"] == 1.0 and (np.asarray(post["probs"]) == 0.5).any():
+            lvl = f"load_present_{0.5:g}"
+        rows = []
+        for i, est in enumerate(sig_est):
+            row = E[rows_at[i]]
+            one = row >= 1
+            d = dict(G=self.dims["G"], N=self.dims["N"], K=K, Signature=est, Med_Contribution=float(np.median(row[one])) if one.any() else float("nan"),
+                     Prop_atleast_1=float(one.mean()))
+            if ref is not None:
+                d.update(Reference_Signature=sig_ref[i], Cosine_Similarity=cos[i])
+            if lvl is not None:
+                lab = int(factor[i])
+                med, prv = post[lvl], post["prevalence"]
+                d.update(Med_Contribution_post=med["mean"][lab], Med_Contribution_lower=med["lower"][lab], Med_Contribution_upper=med["upper"][lab],
+                         Prop_atleast_1_post=prv["mean"][lab], Prop_atleast_1_lower=prv["lower"][lab], Prop_atleast_1_upper=prv["upper"][lab])
+            rows.append(d)
+        rc["summary"] = pd.DataFrame(rows)
+        return rc["summary"]
+
     def _mean_share_profiles(self, n, used, perm, kw):
         """N x G: the mean over the used, matched samples of the range of every tumour's aligned share profile (the host's start of
         get_subtypes; a sample in which a tumour has no exposure does not enter its mean)."""
@@ -1526,6 +1625,26 @@ class bayesNMF_sampler:
         if getattr(self, "_chain", None) is not None:
             self._chain.close()
             self._chain = None
+
+
+def summarize_samplers(sampler_dict, reference_P=None):
+    """summarize_samplers (R/postprocessing.R:114-152): the summary() frames of a dict name -> sampler under one another, each with a
+    Name column "name (G)".  A sampler that has not finished (state["converged"] unset or false; the reference tests is.null) is
+    reported and skipped; samplers of differing K are refused.  No catalogue is bundled, so reference_P is a matrix or None."""
+    if isinstance(reference_P, str):
+        raise ValueError("Parameter `reference_P` must be a matrix or None: no catalogue is bundled")
+    rows = [s.dims["K"] for s in sampler_dict.values()]
+    if len(set(rows)) > 1:
+        raise ValueError("All samplers must have the same number of variables.")
+    frames = []
+    for name, s in sampler_dict.items():
+        if not s.state.get("converged"):
+            print(f"not done: {name}")
+            continue
+        df = s.summary(reference_P).copy()
+        df["Name"] = f"{name} ({s.dims['G']})"
+        frames.append(df)
+    return pd.concat(frames, ignore_index=True) if frames else None
 
 
 ENGINE_STATE_FILE = "engine_state.bin"

@@ -971,6 +971,66 @@ int bnmf_prune(bnmf_handle*, int last_n, const int32_t* used,
 int bnmf_prune_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, int n_steps, double max_loss, double* load,
                   double* tumour, double* series, double* signature, double* exposures, bnmf_prune_info* info);
 
+/* Cohort summary of signatures over recorded samples, on the device: how is a signature's load distributed across the
+ * cohort?  Per recorded sample the median and the other quantiles of its load among all tumours and among its carriers, its prevalence, its
+ * total and its part of the cohort's mutations: one draw each from the posterior of that statistic.  (The reference package's summary()
+ * reports the carriers' median and the prevalence of the MAP point estimate alone.)  The members are the m included tumours g_0 < g_1 <
+ * ... (include[g] != 0; NULL = all), position i = 0 .. m-1.  The samples are the recorded ones flagged in used[] (oldest first; NULL =
+ * all), S of them.  perm [last_n][N] (row-major, a row per sample of the whole range, read for the used ones) is bnmf_relabel's: a row of -1
+ * throughout leaves the sample out (every value of its series row is NaN); every other row must be a permutation of 0 .. N-1; NULL is the
+ * identity.  The aligned samples are S_a of the S used ones.  Per aligned sample s and factor n, with cs_s[n] bnmf_map's column sum of P_s:
+ *   x_i = (A_s[n] != 0 ? E_s[n,g_i] * cs_s[n] : +0.0) + 0.0     bnmf_contrast's renormalised load; + 0.0 maps -0.0 to +0.0, so ties carry
+ *                                                               one bit pattern
+ *   t_i = sum_n x_s[n,g_i]                                      n ascending from +0.0
+ *   u_i = t_i > 0 ? 1 / t_i : 0.0;   r_i = x_i * u_i + 0.0      bnmf_contrast's share
+ *   b_i = (x_i >= min_load);   c = #b
+ * Every value goes to the place of its label perm[s][n].  With canonB bnmf_regress's blocked canonical sum over the members:
+ *   prevalence   = c / m
+ *   total        = canonB_i(x_i)
+ *   fraction     = total_n / sum_n' total_n' (n' ascending from +0.0); NaN unless the denominator is > 0
+ *   mean_present = canonB_i(b_i ? x_i : +0.0) / c; NaN for c = 0
+ * and per level p = probs[l], l = 0 .. L-1 (1 <= L <= BNMF_SUM_MAX_Q, every level in [0, 1], strictly ascending) the type-7 order
+ * statistic of a set sorted ascending y[0 .. k):  h = (double)(k - 1) * p, j = floor(h), g = h - j, a = y[j], b = y[min(j + 1, k - 1)],
+ * the value a == b ? a : (1.0 - g) * a + g * b (bnmf_map's map_interp):
+ *   load_all[l]      of the m loads x_i
+ *   load_present[l]  of the c loads with b_i (the suffix [m - c, m) of the sorted loads); NaN for c = 0
+ *   share_all[l]     of the m shares r_i
+ * If a load or a share of the factor among the members is not finite in a sample, its 3 L order statistics of that sample are NaN and
+ * the (sample, factor) is counted in info.n_nonfinite.  Where the sample excludes the factor every x is +0.0 and the formulas apply as
+ * they stand.  The NSTAT = 4 + 3 L statistics are numbered prevalence, total, fraction, mean_present, load_all[0 .. L), load_present[0 ..
+ * L), share_all[0 .. L).
+ * stat [NSTAT][BNMF_SUM_NROW][N]: per statistic and label over the S' samples whose value is not NaN rows 0 the mean (the canonical W = 64
+ *   sum / S'), 1 the variance in its S' - 1 form (NaN for S' < 2), 2 and 3 the type-7 quantiles at (1 -+ credible_interval) / 2 (NaN for
+ *   credible_interval <= 0), 4 n_valid = S'; rows 0 - 3 NaN for S' = 0.
+ * series [NSTAT][S][N]: every used sample's values.
+ * info (sizeof = 48): n_used = S, n_aligned = S_a, n_included = m, n_left_out = G - m, n_levels = L, n_blocks = the blocks of canonB,
+ *   n_nonfinite, min_load and credible_interval as given.
+ * Only + - * /, comparisons and counts in a fixed order; an order statistic is exact and does not depend on any order of evaluation.  The
+ * bits depend on the samples, used[], include[], perm, min_load, probs and credible_interval only: not on the form of the kernel (a cohort
+ * of more than 16,384 members is sorted in chunks and every order statistic selected across them; BNMF_SUM_CHUNK asks for smaller chunks)
+ * or the batch of samples that passes through the scratch (at most 256 MB; BNMF_SUM_BATCH overrides the batch), both for tests.  Reads
+ * only the P, E and A rings; works for every likelihood and prior, real-valued data with negative loads included; draws no random number,
+ * consumes none of the chain's streams and is read-only for the chain.  bnmf_summary_at: the n_samples iterations that end at end_iter;
+ * the range rule, used[], BNMF_ESIZE and BNMF_ESTATE as for bnmf_waic_at; bnmf_summary(h, n, ...) is bnmf_summary_at(h, iter, n, ...).
+ * stat and series may each be NULL.  Refused before any device work, with BNMF_EINVAL: a null info or probs; a used[] or include[] value
+ * other than 0 / 1 (the index named); a perm row that is neither a permutation nor -1 throughout (the sample named); a min_load that is
+ * NaN, infinite or negative; L outside 1 .. BNMF_SUM_MAX_Q; a level that is NaN, outside [0, 1] or not above the level before it (the
+ * index named); a credible_interval that is NaN or >= 1.  With BNMF_ESIZE: fewer than 2 used samples, fewer than 2 aligned samples, m < 1,
+ * m > BNMF_COA_MAX_M.  With BNMF_ESTATE: window = 0, a poisoned handle or nothing recorded. */
+#define BNMF_SUM_MAX_Q 8         /* the most levels */
+#define BNMF_SUM_NROW  5         /* stat rows: mean, variance, lower, upper, n_valid */
+#define BNMF_SUM_NSCAL 4         /* the statistics before the order statistics: prevalence, total, fraction, mean_present */
+typedef struct { int32_t n_used, n_aligned, n_included, n_left_out, n_levels, n_blocks; int64_t n_nonfinite; double min_load, credible_interval; } bnmf_summary_info;
+int bnmf_summary(bnmf_handle*, int last_n, const int32_t* used,
+                 const int32_t* include /* [G] 0 / 1, NULL = all */,
+                 const int32_t* perm /* [last_n][N] row-major (bnmf_relabel's), NULL = identity */,
+                 double min_load, const double* probs /* [L] */, int L, double credible_interval,
+                 double* stat   /* [4 + 3 L][BNMF_SUM_NROW][N]; may be NULL */,
+                 double* series /* [4 + 3 L][S][N]; may be NULL */,
+                 bnmf_summary_info* info);
+int bnmf_summary_at(bnmf_handle*, int end_iter, int n_samples, const int32_t* used, const int32_t* include, const int32_t* perm, double min_load,
+                    const double* probs, int L, double credible_interval, double* stat, double* series, bnmf_summary_info* info);
+
 /* Label-switching correction of a recorded range, on the device.  The model is invariant under permutations of its factors,
  * so a chain may exchange two labels at any iteration; every element-wise summary (bnmf_map, bnmf_mixing, bnmf_attribution) then mixes
  * signatures.  This call aligns every recorded sample flagged in used[] (oldest first; NULL = all), numbered s = 0 .. S-1, to a pivot and

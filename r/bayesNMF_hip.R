@@ -673,6 +673,57 @@ bayesNMF_sampler_hip <- R6::R6Class(
                       r$n_included, r$n_matched, r$n_unmatched, r$n_traded, r$min_corr, r$mean_ratio))
       out
     },
+    # Cohort summary of the signatures, on the device (bnmf_summary_at; the reference's summary() reports the carriers' median and the
+    # prevalence of the MAP point estimate alone): how is a signature's load distributed across the cohort?  Over iterations end_iter -
+    # n_samples + 1 ... end_iter (defaults as get_WAIC), restricted to idx, per sample and signature the prevalence (tumours with a load
+    # >= min_load), the total load, its fraction of the cohort's, the carriers' mean and at every level of probs the exact type-7 quantile
+    # of all loads (load_all_<p>), of the carriers' loads (load_present_<p>) and of the shares (share_all_<p>).  With relabel the range is
+    # first aligned by get_relabelling() and its perm is handed on; an unmatched sample is left out.  include: a logical of G flags (NULL =
+    # all).  A list with, per statistic name, a data frame (signature, mean, var, lower, upper, n_valid), the info fields, names and
+    # probs; with series also series (N x S x NSTAT).
+    get_summary = function(probs = c(0.05, 0.25, 0.5, 0.75, 0.95), min_load = 1, include = NULL, relabel = TRUE, credible_interval = 0.95,
+                           series = FALSE, end_iter = self$state$iter,
+                           n_samples = min(self$specs$convergence_control$MAP_over, self$state$iter), idx = "MAP_idx") {
+      first <- end_iter - n_samples + 1
+      idx0 <- idx
+      if (is.character(idx)) {
+        if (idx != "MAP_idx") stop("Parameter `idx` must be 'MAP_idx', NULL or a vector of recorded iterations")
+        idx <- self$MAP$idx
+      }
+      used <- NULL
+      if (!is.null(idx)) {
+        idx <- idx[idx >= first & idx <= end_iter]
+        used <- rep(FALSE, n_samples); used[idx - first + 1] <- TRUE
+      }
+      G <- self$dims$G; N <- self$dims$N
+      if (!is.null(include)) {
+        if (length(include) != G) stop("include must have one flag per tumour (G = ", G, ")")
+        include <- as.logical(include); include[is.na(include)] <- FALSE
+      }
+      perm <- NULL
+      if (relabel) {
+        pm <- self$get_relabelling(end_iter = end_iter, n_samples = n_samples, idx = if (is.null(idx0)) NULL else idx0)$perm
+        pm <- t(matrix(as.integer(pm), nrow = N))                       # get_relabelling's is N x S: here S x N, 1-based labels, NA = unmatched
+        perm <- matrix(-1L, n_samples, N)
+        perm[if (is.null(used)) seq_len(n_samples) else which(used), ] <- ifelse(is.na(pm), -1L, pm - 1L)
+      }
+      ci <- if (is.null(credible_interval)) 0 else credible_interval
+      r <- .Call("C_bnmf_summary", self$handle, as.integer(end_iter), as.integer(n_samples), used, include, perm, as.double(probs),
+                 as.double(c(min_load, ci, if (series) 1 else 0, G, N)))
+      L <- length(probs)
+      nms <- c("prevalence", "total", "fraction", "mean_present",
+               as.vector(sapply(c("load_all", "load_present", "share_all"), function(f) paste0(f, "_", format(probs, trim = TRUE)))))
+      out <- r[c("n_used", "n_aligned", "n_included", "n_left_out", "n_levels", "n_blocks", "n_nonfinite", "min_load", "credible_interval")]
+      out$names <- nms; out$probs <- probs
+      for (q in seq_along(nms)) {
+        at <- 5L * (q - 1L)
+        out[[nms[q]]] <- data.frame(signature = seq_len(N), mean = r$stat[, at + 1L], var = r$stat[, at + 2L], lower = r$stat[, at + 3L],
+                                    upper = r$stat[, at + 4L], n_valid = r$stat[, at + 5L])
+      }
+      if (series) out$series <- array(r$series, c(N, r$n_used, length(nms)))
+      message(sprintf("Summary: %d tumours over %d of %d samples, %d levels, min_load %g", r$n_included, r$n_aligned, r$n_used, L, r$min_load))
+      out
+    },
     # Sparse per-tumour assignment with refit, on the device (bnmf_prune_at; not in the reference): which signatures does each tumour keep,
     # and how large are they once the others are gone?  Over iterations end_iter - n_samples + 1 ... end_iter (defaults as get_WAIC),
     # restricted to idx, per sample and tumour backward elimination of the sample's signatures with a refit of the remaining exposures

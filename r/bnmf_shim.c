@@ -1035,6 +1035,72 @@ SEXP C_bnmf_tradeoff_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP
   UNPROTECT(1);
   return out;
 }
+/* Cohort summary of signatures over recorded samples on the device (bnmf_summary / bnmf_summary_at): C_bnmf_summary(ptr, end_iter (integer,
+ * or NULL = the current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or NULL = all),
+ * perm (integer n_samples x N matrix of 0-based places, a row of -1 / NA = the sample is left out; or NULL = identity), probs (real, the
+ * L levels), opts (real c(min_load, credible_interval, want_series 0 / 1, G, N))) -> list(n_used, n_aligned, n_included, n_left_out,
+ * n_levels, n_blocks, n_nonfinite, min_load, credible_interval, stat (N x 5 NSTAT: column 5 q + i = row i — mean, variance, lower, upper,
+ * n_valid — of statistic q; NSTAT = 4 + 3 L: prevalence, total, fraction, mean_present, then L of load_all, load_present, share_all),
+ * series (N x NSTAT S: column S q + s; or NULL)) over iterations end_iter - n_samples + 1 ... end_iter.  C_bnmf_summary_at: the same with
+ * end_iter required */
+typedef struct { int32_t *u, *inc, *perm; int L; double min_load, ci; } sum_in;
+static SEXP sum_alloc(SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP probs, SEXP opts, sum_in* in) {
+  const int n = INTEGER(n_samples)[0];
+  if (XLENGTH(opts) != 5) Rf_error("bnmf: opts has %ld entries, c(min_load, credible_interval, want_series, G, N) is needed", (long)XLENGTH(opts));
+  const double* o = REAL(opts);
+  const int G = (int)o[3], N = (int)o[4];
+  if (used != R_NilValue && XLENGTH(used) != (R_xlen_t)n) Rf_error("bnmf: used has %ld entries for %d samples", (long)XLENGTH(used), n);
+  if (include != R_NilValue && XLENGTH(include) != (R_xlen_t)G) Rf_error("bnmf: include has %ld flags for %d tumours", (long)XLENGTH(include), G);
+  if (perm != R_NilValue && XLENGTH(perm) != (R_xlen_t)n * N) Rf_error("bnmf: perm has %ld entries for %d samples of %d factors", (long)XLENGTH(perm), n, N);
+  in->u = lgl_flags(used, n);
+  in->inc = lgl_flags(include, G);
+  in->perm = NULL;
+  if (perm != R_NilValue) {                                                /* the R matrix is column-major: row s of the ABI is its row s */
+    in->perm = (int32_t*)R_alloc((size_t)n * N, sizeof(int32_t));
+    for (int s = 0; s < n; ++s) for (int j = 0; j < N; ++j) { const int v = INTEGER(perm)[s + (size_t)n * j]; in->perm[(size_t)s * N + j] = v == NA_INTEGER ? -1 : v; }
+  }
+  in->L = (int)XLENGTH(probs); in->min_load = o[0]; in->ci = o[1];
+  const int Lb = in->L > BNMF_SUM_MAX_Q ? BNMF_SUM_MAX_Q : in->L;          /* (the library refuses more levels: the buffers only have to exist) */
+  const int nstat = BNMF_SUM_NSCAL + 3 * Lb;
+  int S = n < 0 ? 0 : n;
+  if (in->u) { S = 0; for (int i = 0; i < n; ++i) S += in->u[i]; }
+  static const char* nms[] = {"n_used", "n_aligned", "n_included", "n_left_out", "n_levels", "n_blocks", "n_nonfinite", "min_load", "credible_interval",
+                              "stat", "series"};
+  SEXP out = PROTECT(named_list(11, nms));
+  SET_VECTOR_ELT(out, 9, Rf_allocMatrix(REALSXP, N, BNMF_SUM_NROW * nstat));
+  if (o[2] != 0.0) SET_VECTOR_ELT(out, 10, Rf_allocMatrix(REALSXP, N, nstat * S));
+  UNPROTECT(1);
+  return out;
+}
+static void sum_finish(SEXP out, const bnmf_summary_info* info) {
+  const int32_t v[6] = {info->n_used, info->n_aligned, info->n_included, info->n_left_out, info->n_levels, info->n_blocks};
+  for (int i = 0; i < 6; ++i) SET_VECTOR_ELT(out, i, Rf_ScalarInteger(v[i]));
+  SET_VECTOR_ELT(out, 6, Rf_ScalarReal((double)info->n_nonfinite)); SET_VECTOR_ELT(out, 7, Rf_ScalarReal(info->min_load));
+  SET_VECTOR_ELT(out, 8, Rf_ScalarReal(info->credible_interval));
+}
+SEXP C_bnmf_summary(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP probs, SEXP opts) {
+  sum_in in;
+  SEXP out = PROTECT(sum_alloc(n_samples, used, include, perm, probs, opts, &in));
+  bnmf_summary_info info;
+  if (end_iter == R_NilValue)
+    chk(bnmf_summary(get_handle(ptr), INTEGER(n_samples)[0], in.u, in.inc, in.perm, in.min_load, REAL(probs), in.L, in.ci, map_buf(out, 9), map_buf(out, 10), &info));
+  else
+    chk(bnmf_summary_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.perm, in.min_load, REAL(probs), in.L, in.ci, map_buf(out, 9),
+                        map_buf(out, 10), &info));
+  sum_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
+SEXP C_bnmf_summary_at(SEXP ptr, SEXP end_iter, SEXP n_samples, SEXP used, SEXP include, SEXP perm, SEXP probs, SEXP opts) {
+  sum_in in;
+  SEXP out = PROTECT(sum_alloc(n_samples, used, include, perm, probs, opts, &in));
+  bnmf_summary_info info;
+  chk(bnmf_summary_at(get_handle(ptr), INTEGER(end_iter)[0], INTEGER(n_samples)[0], in.u, in.inc, in.perm, in.min_load, REAL(probs), in.L, in.ci, map_buf(out, 9),
+                      map_buf(out, 10), &info));
+  sum_finish(out, &info);
+  UNPROTECT(1);
+  return out;
+}
 /* Sparse per-tumour assignment with refit on the device (bnmf_prune / bnmf_prune_at): C_bnmf_prune(ptr, end_iter (integer, or NULL = the
  * current iteration), n_samples, used (logical length n_samples, or NULL = all), include (logical length G, or NULL = all), opts (real
  * c(n_steps, max_loss, want_exposures 0 / 1, G, N))) -> list(n_used, n_included, n_undefined, n_single, n_steps, trials, max_change,
@@ -1468,6 +1534,7 @@ static const R_CallMethodDef call_methods[] = {
   {"C_bnmf_residuals", (DL_FUNC)&C_bnmf_residuals, 6}, {"C_bnmf_residuals_at", (DL_FUNC)&C_bnmf_residuals_at, 6},
   {"C_bnmf_tradeoff", (DL_FUNC)&C_bnmf_tradeoff, 9}, {"C_bnmf_tradeoff_at", (DL_FUNC)&C_bnmf_tradeoff_at, 9},
   {"C_bnmf_prune", (DL_FUNC)&C_bnmf_prune, 6}, {"C_bnmf_prune_at", (DL_FUNC)&C_bnmf_prune_at, 6},
+  {"C_bnmf_summary", (DL_FUNC)&C_bnmf_summary, 8}, {"C_bnmf_summary_at", (DL_FUNC)&C_bnmf_summary_at, 8},
   {NULL, NULL, 0}};
 void R_init_bayesNMFhip(DllInfo* dll) {
   R_registerRoutines(dll, NULL, call_methods, NULL, NULL);
